@@ -1,6 +1,6 @@
 """Headline benchmark: compressed video-tokens / s of the HICom compressor on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: launched by torchrun)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: launched by torchrun)
 
 A "step" = one DROP-IN forward -- HIComProjector.forward(...) as hicom_arch.py:212 calls it, result complete on the
 caller's stream -- of the release configuration (mm_projector_type local43_global32_coarse, use_guide=direct,
@@ -9,11 +9,14 @@ spatial_unpad/no_token, hidden 896) over synthetic SigLIP features already resid
 weak scaling).  The inputs rotate through 3 distinct buffer sets (645 MB per GPU: HBM, not Infinity Cache).
 `python bench.py --gpus N` with N > 1 starts its own N ranks (or run it under torch.distributed.run).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`ms_per_step` = one timed step).  --dump-outputs DIR writes the compressed tokens of the last timed step as
+DIR/compressed_tokens.npy (float32; same arguments -> same inputs).  --full adds everything else, among it:
   roofline     dominant kernel (the fused local+global stream): ALGORITHMIC bytes / its mean launch
                time (HIP events on its own stream, measured here) against the 8 TB/s HBM3E peak
   cpu_baseline the CPU oracle (a port of the reference's PyTorch path) timed on this host's
                cores on the same 64-frame workload (bounded number of repetitions)
+  ms_per_step_* spreads and other loop forms, parity, secondary recipes, neighbours, mfma_util, sharded_step.parity
 """
 from __future__ import annotations
 
@@ -221,9 +224,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--frames-per-gpu", type=int, default=64)
     ap.add_argument("--hidden", type=int, default=896)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the use_guide=None sweep")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed loop and the roofline (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (spreads, roofline, parity, secondary recipes, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output as DIR/compressed_tokens.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the use_guide=None sweep")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) only the timed loop and the roofline (profiling runs)")
     ap.add_argument("--graph", action="store_true", help="hipGraph replay of the cached plan (measured slower than the C launch loop on ROCm 7.2)")
     ap.add_argument("--no-graph", action="store_true", help="(default) eager launches: one C call per step")
     args = ap.parse_args()
@@ -350,7 +356,7 @@ def main():
                     pl.release()
         out = step()
         assert out.shape == (n_out, args.hidden)
-        if distributed:
+        if distributed and args.full:
             dist_guard["parity"] = dist_parity(module, sets[0], sharded_forward(module, *sets[0], total_frames), total_frames, world, device)
         # ---- pre-warm-up: convergence rule (PREWARM_* above); every rank follows rank 0's decision ----
         t_pw = time.perf_counter()
@@ -371,10 +377,20 @@ def main():
                       "windows": len(windows), "steps": len(windows) * PREWARM_WINDOW, "seconds": round(time.perf_counter() - t_pw, 3),
                       "converged": len(windows) >= 3 and (max(windows[-3:]) - min(windows[-3:])) <= PREWARM_TOL * min(windows[-3:]),
                       "first_window_us": round(windows[0], 2), "last_windows_us": [round(w, 2) for w in windows[-3:]]}
+        # the rotation restarts at set 0 here, whatever number of pre-warm-up windows ran (at most two more untimed steps reach the
+        # boundary, so no set is read twice in a row): the last timed step always reads input set (W + K - 1) mod N_INPUT_SETS, and
+        # runs with the same arguments compute the same outputs (--dump-outputs)
+        while counter[0] % N_INPUT_SETS:
+            headline()
+        counter[0] = 0
         for _ in range(args.warmup):       # the W warm-up steps run right in front of the timed region
             out = headline()
         ms_per_step, out = timed(headline, args.steps, host_marks)
         gc.enable()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "compressed_tokens.npy"), out.float().cpu().numpy())
     if distributed:
         t = torch.tensor([ms_per_step], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -386,14 +402,14 @@ def main():
                          "enqueue_us_first": round(hd[0], 2), "final_fence_us": round(hd[-1], 2)}
 
     extras = {}
-    if distributed and args.no_extras:
+    if args.full and distributed and args.no_extras:
         # the joined latency of the sharded call belongs to every N > 1 line (the headline there is the pipelined loop)
         with torch.no_grad():
             jb = sorted(timed(step, max(5, min(args.steps, 50)))[0] for _ in range(3))
         t = torch.tensor([jb[1]], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         extras["ms_per_step_joined"] = {"median": float(t.item()), "min": jb[0], "api": "sharded_forward(...) with the result joined on the caller's stream"}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         with torch.no_grad():
             gc.disable()
             # spread of the same loop: median over internal batches (the GPU boxes are shared machines)
@@ -431,7 +447,7 @@ def main():
                 extras[k]["median"] = float(t.item())
 
     # ---- roofline of the dominant kernel (HIP events on the stream it is launched on) ----------
-    roofline = dominant_kernel_roofline(module, sets, args.steps)
+    roofline = dominant_kernel_roofline(module, sets, args.steps) if args.full else None
 
     # in-launch hand-offs (query prep granules, the GEMV chain under readout GEMM 2 / in the FINISH phase) whose bounded spin expired
     # during everything above: such a step returns NaN rows and only counts it -- the line carries the counters
@@ -466,15 +482,15 @@ def main():
         **extras,
         **({"sharded_step": dist_guard} if dist_guard is not None else {}),
         "handoff_failures": handoff,
-        "roofline": roofline,
+        **({"roofline": roofline} if roofline is not None else {}),
     }
     if args.hidden == 896 and "ms_per_step_batches" in extras:
         result["whole_step_hbm_frac_median"] = alg_step / (extras["ms_per_step_batches"]["median"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-    mu = mfma_util_from_profiles()
+    mu = mfma_util_from_profiles() if args.full else None
     if mu is not None:
         result["mfma_util"] = mu
     if rank == 0:
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             result["parity"] = parity_probe(device)
             if not distributed and not args.no_secondary:
                 result["secondary"] = secondary_sweep(args, device, ff, fe, guide)

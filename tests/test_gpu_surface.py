@@ -417,7 +417,7 @@ def test_bench_distributed_branch_world1_prints_one_json_line():
     env = dict(os.environ, HICOM_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-extras"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -427,6 +427,33 @@ def test_bench_distributed_branch_world1_prints_one_json_line():
     assert "frame-shard" in d["config"]["parallelism"] and "RCCL" in d["config"]["parallelism"]
     assert d["ms_per_step_joined"]["median"] > 0 and d["ms_per_step"] > 0
     assert d["roofline"]["frac"] > 0
+
+
+def test_bench_plain_run_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline only (the --full measurements are absent), and --dump-outputs writes the
+    last timed step's tokens: two runs whose last timed step reads the same input set write the same array."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for steps in (3, 6):                         # (warm-up 1 + steps - 1) mod 3 input sets = set 0 in both runs
+        d_out = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(d_out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["metric"] == "compressed_video_tokens_per_sec" and d["unit"] == "tokens/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "bf16" and d["steps"] == steps and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 1328 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert not {"roofline", "parity", "secondary", "neighbours", "cpu_baseline", "ms_per_step_batches", "mfma_util"} & set(d)
+        a = np.load(d_out / "compressed_tokens.npy")
+        assert a.dtype == np.float32 and a.shape == (1328, 896) and np.isfinite(a).all() and np.abs(a).max() > 0
+        got.append(a)
+    assert np.array_equal(got[0], got[1])
 
 
 @pytest.mark.parametrize("name", ["G1_direct_T8", "G11_c1_shape", "G2_off_T8", "G9_anyres"])

@@ -11,7 +11,7 @@ for rep in 1 2; do
   i=0
   for envs in "$@"; do
     i=$((i+1))
-    env $envs timeout 300 python3 bench.py --steps 1000 --warmup 50 --no-cpu-baseline --no-secondary 2> $O/bench_${i}_$rep.err | grep '^{' > $O/bench_${i}_$rep.json
+    env $envs timeout 300 python3 bench.py --steps 1000 --warmup 50 --full --no-cpu-baseline --no-secondary 2> $O/bench_${i}_$rep.err | grep '^{' > $O/bench_${i}_$rep.json
     python3 - "$envs" $O/bench_${i}_$rep.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

@@ -9,7 +9,7 @@ i=0
 for envs in "$@"; do
   i=$((i+1))
   export $envs
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$i -- python3 bench.py --steps 500 --warmup 50 --no-extras > $O/stats_$i.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$i -- python3 bench.py --steps 500 --warmup 50 --full --no-extras > $O/stats_$i.log 2>&1
   for v in $envs; do unset ${v%%=*}; done
   f=$(ls $O/stats_$i/*/*kernel_stats.csv | head -1)
   cp $f $O/kernel_stats_$i.csv

@@ -24,5 +24,5 @@ sl = d["stamps_late"]; print("stamps late mean", sum(sl)/len(sl), "final", d["fi
 PY
 cd /tmp && export TMPDIR=/tmp
 cd $R
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras > $O/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extras > $O/trace.log 2>&1
 python3 tools/region_trace.py $O/trace 20 | tee $O/region_trace.txt

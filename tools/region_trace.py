@@ -1,4 +1,4 @@
-"""Dev tool: per-step timeline of the LAST K release steps in front of the roofline launches of a `bench.py --steps K --no-extras` run under
+"""Dev tool: per-step timeline of the LAST K release steps in front of the roofline launches of a `bench.py --steps K --full --no-extras` run under
 `rocprofv3 --kernel-trace` (the timed region): per-step kernel durations, gaps between the launches, start-to-start period."""
 import csv, glob, sys
 d, K = sys.argv[1], int(sys.argv[2])
