@@ -3,7 +3,8 @@
 // The reference runs HIComProjector.forward (projector.py:676-708) as ~60 eager PyTorch ops on one stream.  Here the forward
 // is a fixed plan of kernel launches over a caller-owned workspace, issued from C++ (no per-op Python / ctypes / allocator cost).
 //
-// Release recipe (use_guide = direct, exact window partition; `can_fuse`): FIVE launches on ONE stream, no events --
+// Release recipe (use_guide = direct, exact window partition; `can_fuse`; bf16 or -- tok_dt, single-stream form -- fp16 tokens): FIVE launches
+// on ONE stream, no events --
 //
 //   query_prep (q_proj -> granule hand-off -> fold: folded queries hi/lo, score-side pos table, local query rows, r0)
 //   -> fused ring kernel (local windows + global attention: frames_embed and frames_feature each read once)
@@ -33,16 +34,28 @@ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct WsLayout {
     size_t ctx_local, hid_local, ctx_hi, ctx_lo, hid_hi, hid_lo, pooled_q, ctx16, hid16, ad_hid, ad_hid2, ad_ky, ad_vy, qp, qhi, qlo, pos_a, prep_state, tail_state, tail_sync, lq_inj, gq_inj, inj_l_s, inj_g_s, scores, part_m, part_l, part_acc, scratch, ml, acc,
-        ctx_g, o, qres, pre, hid_g, tok, po, o_fix, r0, part_marg, total;
+        ctx_g, o, qres, pre, hid_g, tok, po, o_fix, r0, part_marg, qf32, total;
     int nw, R, rows_pad, nparts, P;
     long N, score_stride;
     bool marg;      // generic global path: the stream kernel keeps the positional marginals itself (no logit tensor; `scores` holds them)
 };
 
-// The fused local+global stream kernel applies to the release recipe: shared bf16 local query
+// fp16 tokens (tok_dt = HICOM_DT_F16) run on ONE form of the release step: the single-stream call (query prep | fp16 ring kernel |
+// readout GEMM 1 + merge role | readout GEMM 2 + GEMV chain role -> the 32 global rows) of a solo, joined STREAM + FINISH call.  The
+// environment's A/B switches of that step are checked where the step is enqueued (HICOM_EUNSUP there).
+bool f16_form(const hicom_compressor_args& a, int nw) {
+    const bool prep1 = a.nq == 1 && a.E % 128 == 0 && a.E <= 1536 && a.E / a.nh <= 128;
+    const bool chain_ok = a.hidden <= 1536 || (nw >= 1000 && a.hidden <= 4096 && a.hidden % 8 == 0);
+    return !a.local_logits && (a.phases & HICOM_PHASE_STREAM) && (a.phases & HICOM_PHASE_FINISH) && !(a.phases & HICOM_PHASE_MERGE_ON_NEXT) &&
+           a.lw0_f16 && a.lw2_f16 && !a.state_out && !a.state_sets && prep1 && a.gc0 && chain_ok && !a.vpe_f16 && a.E % 64 == 0 && a.hidden % 64 == 0;
+}
+
+// The fused local+global stream kernel applies to the release recipe: shared local query in the token type
 // ("direct"), plain 1/sqrt(d) logits, windows that partition the grid, <= 14 folded global rows.
 bool can_fuse(const hicom_compressor_args& a) {
-    if (!(a.has_local && a.has_global) || !a.lq || a.lq_stride != 0 || a.lq_dt != HICOM_DT_BF16 || a.l2norm != 0 || a.gq_dt != HICOM_DT_BF16 ||
+    if (a.tok_dt != HICOM_DT_BF16 && a.tok_dt != HICOM_DT_F16) return false;
+    const int gdt = a.tok_dt;                     // the guide (local query = injected global query) comes in the token type
+    if (!(a.has_local && a.has_global) || !a.lq || a.lq_stride != 0 || a.lq_dt != gdt || a.l2norm != 0 || a.gq_dt != gdt ||
         a.inj_l.mode || a.inj_g.mode) return false;
     if (a.ak.w0 || a.av.w0) return false;         // adapted local streams: the two stages no longer share their tokens
     if (a.E != 1152 || a.nq * a.nh > 12) return false;
@@ -64,6 +77,7 @@ bool can_fuse(const hicom_compressor_args& a) {
     // compact pos-emb slots a workgroup can touch: 8 frames + the grid rows and columns of its windows (<= 64)
     const int rows_t = ((wpw + a.ax.nwin - 2) / a.ax.nwin + 1) * a.ay.k, cols_t = wpw * a.ax.k;
     if (a.H > 64 || a.W > 64 || 8 + (rows_t < a.H ? rows_t : a.H) + (cols_t < a.W ? cols_t : a.W) > 64) return false;
+    if (a.tok_dt == HICOM_DT_F16 && !(f16_form(a, nw) && nparts <= 256)) return false;
     return wpw <= 32 && ((wpw + per_t - 2) / per_t + 1) * a.at.k <= 8;
 }
 
@@ -149,6 +163,8 @@ WsLayout make_layout(const hicom_compressor_args& a) {
         w.r0 = take((size_t)a.hidden * 4);
         // (release step, round 6: normalised positional marginals of the ring kernel's partial states, fp16 [nparts][R][marg_slots])
         w.part_marg = take(a.vpe_f16 && a.marg_slots > 0 ? (size_t)w.nparts * w.R * a.marg_slots * 2 : 0);
+        // (fp16 tokens: the folded global queries as f32 rows, split by the fp16 ring kernel itself)
+        w.qf32 = take(a.tok_dt == HICOM_DT_F16 ? (size_t)16 * a.E * 4 : 0);
     }
     w.total = off;
     return w;
@@ -230,7 +246,8 @@ int check_args(const hicom_compressor_args& a) {
                       "compressor: global weights");
         HICOM_REQUIRE(!a.inj_g.mode || a.inj_g.visual, HICOM_EINVAL, "compressor: the global injector needs the rows it injects into");
         HICOM_REQUIRE(a.n_global_rows >= a.nq && a.n_global_rows % a.nq == 0, HICOM_EINVAL, "compressor: global row count");
-        HICOM_REQUIRE(a.gq_dt == HICOM_DT_BF16 || a.gq_dt == HICOM_DT_F32, HICOM_EINVAL, "compressor: gq_dt");
+        HICOM_REQUIRE(a.gq_dt == HICOM_DT_BF16 || a.gq_dt == HICOM_DT_F32 || (a.gq_dt == HICOM_DT_F16 && a.tok_dt == HICOM_DT_F16), HICOM_EINVAL,
+                      "compressor: gq_dt");
         HICOM_REQUIRE((a.pe == nullptr) == (a.kpe == nullptr), HICOM_EINVAL, "compressor: pe and kpe go together");
     }
     if ((a.has_local && a.inj_l.mode) || (a.has_global && a.inj_g.mode)) {
@@ -241,6 +258,11 @@ int check_args(const hicom_compressor_args& a) {
     }
     if (a.has_local && a.has_global && (a.phases & HICOM_PHASE_STREAM))
         HICOM_REQUIRE(a.stream_side && a.ev_fork && a.ev_join, HICOM_EINVAL, "compressor: side stream and events required");
+    HICOM_REQUIRE(a.tok_dt == HICOM_DT_BF16 || a.tok_dt == HICOM_DT_F16, HICOM_EINVAL, "compressor: tok_dt %d", a.tok_dt);
+    // fp16 tokens are read by the fp16 instantiation of the fused ring kernel only: every other kernel of this call would read them as bf16
+    HICOM_REQUIRE(a.tok_dt != HICOM_DT_F16 || can_fuse(a), HICOM_EUNSUP,
+                  "compressor: fp16 tokens run on the release recipe's single-stream step only (direct guide in fp16, windows of 16..64 tokens "
+                  "partitioning the grid, one solo STREAM + FINISH call with fp16 readout weights and gc0, no local_logits / RING_MARG); cast to bf16");
     return HICOM_OK;
 }
 
@@ -476,9 +498,14 @@ extern "C" int hicom_compressor_fwd(const hicom_compressor_args* ap) {
         static const bool ring_marg_env = getenv("HICOM_RING_MARG") && getenv("HICOM_RING_MARG")[0] == '1';
         const bool marg_out = single && tail5 && tail_env <= 4 && a.pe && a.vpe_f16 && a.marg_slots == 8 * (a.E / 64) &&
                               a.T + a.H + a.W <= a.marg_slots && ring_marg_env;
+        const bool tok16 = a.tok_dt == HICOM_DT_F16;
+        HICOM_REQUIRE(!tok16 || (single && tail4 && tail_env == 4 && !marg_out && !shard4 && prep1), HICOM_EUNSUP,
+                      "compressor: fp16 tokens take the four-launch single-stream step (HICOM_TAIL_LAUNCHES / HICOM_CHAIN_WIDE / HICOM_RING_MARG "
+                      "select another form)");
         if (prep1)
             CHK(hicom_query_prep_fwd(a.gq, a.lq, a.wq, a.bq, a.wk, a.kpe, a.nh, a.E, a.P, qscale, ws + w.qhi, ws + w.qlo, F(w.pos_a), a.P,
-                                     w.R, (tail5 || shard4) ? a.gw0 : nullptr, a.gb0, a.bo, a.hidden, shard4 ? a.r0_buf : F(w.r0), ws + w.prep_state, sm));
+                                     w.R, (tail5 || shard4) ? a.gw0 : nullptr, a.gb0, a.bo, a.hidden, shard4 ? a.r0_buf : F(w.r0), ws + w.prep_state,
+                                     tok16 ? HICOM_DT_F16 : HICOM_DT_BF16, tok16 ? F(w.qf32) : nullptr, sm));
         else CHK(query_prep(sm, true));
         if (fold_ev && !merge_on_next && !single) hicom_host::set_stop_event(a.ev_fork);      // "record ev_fork" rides on the launch
         CHK(hicom_fused_stream_fwd(a.ff, a.fe ? a.fe : a.ff, a.local_logits, a.T, a.H, a.W, a.E, a.at.k, a.ay.k, ws + w.qhi, ws + w.qlo,
@@ -486,7 +513,8 @@ extern "C" int hicom_compressor_fwd(const hicom_compressor_args* ap) {
                                    a.x_index0, F(w.part_m), F(w.part_l), F(w.part_acc),
                                    w.nparts, nullptr, f16 ? nullptr : ws + w.ctx_hi, f16 ? nullptr : ws + w.ctx_lo, f16 ? ws + w.ctx_hi : nullptr,
                                    single ? ws + w.o_fix : nullptr, single ? (int64_t)a.E * 8 : 0, (single || shard4) ? ws + w.part_acc : nullptr,
-                                   marg_out ? ws + w.part_marg : nullptr, marg_out ? a.marg_slots : 0, sm));
+                                   marg_out ? ws + w.part_marg : nullptr, marg_out ? a.marg_slots : 0, tok16 ? HICOM_DT_F16 : HICOM_DT_BF16,
+                                   tok16 ? F(w.qf32) : nullptr, sm));
         if (shard4) {
             hicom_r16_role r1;
             memset(&r1, 0, sizeof(r1));

@@ -95,6 +95,9 @@ struct RingParams {
     // marginals by v_proj . pe^T, a weight-only table (merge_item.hpp).
     _Float16* part_marg;   // [nparts][R][marg_slots], or NULL
     int marg_slots;
+    // fp16 tokens (fused_ring_kernel<.., F16 = true>): the folded global queries as fp32 rows [16][E] (rows < R); the kernel splits them
+    // into its fp16 operand itself (rows >= R of qhi still carry the local query, the fp16 guide, exactly)
+    const float* qf32;
 };
 
 // Position of 16-byte chunk c of image row r inside the row: c ^ fswz(r).  The row -> XOR map is chosen so that
@@ -115,13 +118,48 @@ __device__ __forceinline__ void ring_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// ---- token type (F16 = false: bf16 tokens; true: fp16 tokens) ----------------------------------------------------------------
+// The ring, the swizzles and ds_read_b64_tr_b16 move 16-bit words whatever they encode; only the MFMAs and the operands the kernel
+// builds itself (the split softmax weights, the marginals, the folded global queries) depend on the format.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// (macros rather than inline functions: the bf16 instantiation then compiles to exactly the instructions of the bf16-only kernel)
+#define RING_MFMA32(a, b, c)                                                                                                        \
+    (F16 ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, (a)), __builtin_bit_cast(f16x8, (b)), (c), 0, 0, 0)      \
+         : __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0))
+#define RING_MFMA16(a, b, c)                                                                                                        \
+    (F16 ? __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, (a)), __builtin_bit_cast(f16x4, (b)), (c), 0, 0, 0)       \
+         : __builtin_amdgcn_mfma_f32_16x16x16bf16_1k((a), (b), (c), 0, 0, 0))
+// x ~= hi + lo in the token type.  fp16 has 5 exponent bits, so a plain hi / lo split of a small value puts lo among the subnormals
+// (spacing 2^-24); the fp16 callers therefore hand in x already scaled by a power of two (kF16PScale, or a per-row 2^s for the folded
+// queries) so that |x| < 2^15 and the quantity of interest is large: |x - hi - lo| <= 2^-12 |x - hi| + 2^-25 <= 2^-23 |x| + 2^-25.
+__device__ __forceinline__ void split_f16(float x, uint16_t& hi, uint16_t& lo) {
+    const _Float16 h = (_Float16)x;
+    const _Float16 l = (_Float16)(x - (float)h);
+    hi = __builtin_bit_cast(uint16_t, h);
+    lo = __builtin_bit_cast(uint16_t, l);
+}
+template <bool F16>
+__device__ __forceinline__ void split_tok(float x, uint16_t& hi, uint16_t& lo) {
+    if constexpr (F16) split_f16(x, hi, lo);
+    else split_bf16(x, hi, lo);
+}
+// fp16: the softmax weights p in [0, 1] enter the P.x operand as p * 2^14 (<= 2^14, far from the fp16 maximum), so the split error of a
+// weight is <= 2^-23 p + 2^-39 (2^-25 / 2^14): over the <= 2^16 tokens a row ever sees, <= 2^-22 of the row's normaliser l >= 1.  The
+// accumulators therefore carry 2^14 x (their true value) through the token stream; the window emit folds 2^-14 into 1 / l, the pos-emb
+// tail first brings them down to 2^4 (the marginals it splits are <= 2048 tokens' worth of weight: 2^15 at that scale), the partial
+// state write divides the rest out.  All factors are powers of two: exact.
+constexpr float kF16PScale = 16384.f;
+constexpr float kF16PeScale = 16.f;
+
 // LOGITS = false: both visual tensors are streamed (frames_embed for the local scores);  LOGITS = true: the local logits come
 // precomputed (RingParams::llog: SURVEY.md §8 row f2 -- the producer of frames_embed, the SigLIP head projection of reference
 // encoder.py:284-286, hands over fe_n . guide per token from its GEMM epilogue, so frames_embed is never written or read) and the
 // ring's four slots all carry frames_feature: everything of tile t+3 is requested right behind barrier [B] of tile t, the compute
 // waves fetch the 4 logits of their token slots one tile ahead with ordinary loads, no local score MFMAs.  ONE kernel body: the
 // two forms differ in the loader schedule, the score operand and the cadence of the pos-emb images behind the stream.
-template <int NB, bool LOGITS>
+// F16: frames_feature / frames_embed / the pe planes / the local query are fp16 (v_mfma_f32_16x16x32_f16); two-tensor form only.
+template <int NB, bool LOGITS, bool F16 = false>
 __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint16_t* ff0, const uint16_t* fe0, int H0, int W0, int kt0, int ks0, int nwy0, int nwx0, int NW0, int WSZ0, int wpw0,
                                                                      RingParams p_in) {
     // (the leading scalars repeat what the loaders' FIRST requests depend on -- stream bases and the window geometry: preloaded into SGPRs at
@@ -144,6 +182,7 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
     static_assert(3 * PPL <= 63, "vmcnt is a 6-bit counter");
     static_assert(E % (16 * kRingC) == 0 && PIECES % kRingL == 0 && kRingL == 4, "slice / piece split");
     static_assert(SLICE % 16 == 0 && kRegroup % 16 == 0 && kRegroup / 4 <= 64, "row regroup: hops of kRegroup channels, one float4 per lane");
+    static_assert(!(F16 && LOGITS), "fp16 tokens: two-tensor form only");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ffbuf = smem;                                                // [2][TILE_BYTES] frames_feature ring (LOGITS: [4])
@@ -450,6 +489,37 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
             alo_t = *reinterpret_cast<const bf16x4*>(p.qlo + off + 32 * K32 + 4 * kg);
         }
     }
+    // fp16 tokens: the global rows of the operand come as fp32 rows (p.qf32) and are split here at a power of two per row, 2^s with
+    // max_row |q| * 2^s in [2^14, 2^15): |q 2^s - hi - lo| <= 2^-23 |q 2^s| + 2^-25, i.e. <= 2^-22 of the row's max |q| (split_f16).  The
+    // logits of the row are multiplied by qsc = 2^-s after the channel-slice exchange.  The row max needs every wave's slice: one value
+    // per (wave, row) through the regroup scratch, read behind barrier [P].
+    float qsc = 1.f;
+    float qv[F16 ? K32 : 1][8], qv_t[4];
+    if constexpr (F16) {
+        float mx = 0.f;
+        const float* qr = p.qf32 + (long)r16 * E + SLICE * wave;
+#pragma unroll
+        for (int s = 0; s < K32; ++s) {
+            const f32x4 u0 = r16 < R ? *reinterpret_cast<const f32x4*>(qr + 32 * s + 8 * kg) : f32x4{0.f, 0.f, 0.f, 0.f};
+            const f32x4 u1 = r16 < R ? *reinterpret_cast<const f32x4*>(qr + 32 * s + 8 * kg + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                qv[s][i] = u0[i];
+                qv[s][4 + i] = u1[i];
+                mx = fmaxf(mx, fmaxf(fabsf(u0[i]), fabsf(u1[i])));
+            }
+        }
+        if (KTAIL) {
+            const f32x4 u = r16 < R ? *reinterpret_cast<const f32x4*>(qr + 32 * K32 + 4 * kg) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                qv_t[i] = u[i];
+                mx = fmaxf(mx, fabsf(u[i]));
+            }
+        }
+        mx = xrow4_max(mx);                                            // the four k groups of row r16: this wave's slice
+        if (kg == 0) cscr[wave * kRegroup + r16] = mx;
+    }
     if (part == 0 && p.zero_ptr)                                     // (fixed-point accumulators of the merge + v_proj launch behind us)
         for (int i = ctid; i < p.zero_n; i += 64 * kRingC) p.zero_ptr[i] = 0ull;
 
@@ -544,12 +614,42 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
 #pragma unroll
             for (int u = 0; u < PG; ++u) {
                 const bf16x8 b2 = bf16x8{bv[u][0], bv[u][1], bv[u][2], bv[u][3], bv[u][0], bv[u][1], bv[u][2], bv[u][3]};
-                accr[g0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_op, b2, accr[g0 + u], 0, 0, 0);
+                accr[g0 + u] = RING_MFMA32(a_op, b2, accr[g0 + u]);
             }
         }
     };
     HICOM_TR(0); HICOM_TR(1);   // prologue done (this wave)
     lds_barrier();                                                     // [P] tables ready
+    if constexpr (F16) {
+        float rm = 0.f;
+#pragma unroll
+        for (int k = 0; k < kRingC; ++k) rm = fmaxf(rm, cscr[k * kRegroup + r16]);
+        int ex = 0;
+        (void)frexpf(rm, &ex);                                         // rm = m 2^ex, m in [0.5, 1)
+        ex = min(max(ex, -100), 100);
+        const float up = rm > 0.f ? ldexpf(1.f, 15 - ex) : 1.f;
+        qsc = 1.f / up;
+        if (r16 < R) {
+#pragma unroll
+            for (int s = 0; s < K32; ++s)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    uint16_t h, l;
+                    split_f16(qv[s][i] * up, h, l);
+                    ahi[s][i] = (short)h;
+                    alo[s][i] = (short)l;
+                }
+            if (KTAIL) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    uint16_t h, l;
+                    split_f16(qv_t[i] * up, h, l);
+                    ahi_t[i] = (short)h;
+                    alo_t[i] = (short)l;
+                }
+            }
+        }
+    }
     const int nslot_tiles = (p.pe_hi || p.part_marg) ? (__builtin_amdgcn_readfirstlane(slot_row[64]) + 15) >> 4 : 0;   // 16-slot tiles of the compact pos-emb slots
     // raw local logits of this lane's 4 token slots, fetched one tile ahead (slots past the stream re-read its last token)
     auto fetch_logits = [&](int tile) -> f32x4 {
@@ -611,16 +711,16 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
             if (KG < K32) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < KG; ++u) {
-                if constexpr (!LOGITS) e0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfe[u], ahi[g0 + u], e0, 0, 0, 0);
-                f0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bff[u], ahi[g0 + u], f0, 0, 0, 0);
-                f1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bff[u], alo[g0 + u], f1, 0, 0, 0);
+                if constexpr (!LOGITS) e0 = RING_MFMA32(bfe[u], ahi[g0 + u], e0);
+                f0 = RING_MFMA32(bff[u], ahi[g0 + u], f0);
+                f1 = RING_MFMA32(bff[u], alo[g0 + u], f1);
             }
             if (KG < K32) __builtin_amdgcn_sched_barrier(0);
         }
         if (KTAIL) {
-            if constexpr (!LOGITS) e0 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(bfe_t, ahi_t, e0, 0, 0, 0);
-            f0 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(bff_t, ahi_t, f0, 0, 0, 0);
-            f1 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(bff_t, alo_t, f1, 0, 0, 0);
+            if constexpr (!LOGITS) e0 = RING_MFMA16(bfe_t, ahi_t, e0);
+            f0 = RING_MFMA16(bff_t, ahi_t, f0);
+            f1 = RING_MFMA16(bff_t, alo_t, f1);
         }
         // The accumulators are read by VALU right away.  Required software wait states, CDNA4 ISA §4.1 (data-hazard table,
         // "XDL write VGPR -> VALU read / write of that VGPR"; summarised in cdna_hip_programming.md §5.7 item 2): an 8-pass
@@ -642,6 +742,9 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
         f32x4 lg = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < kRingC; ++k) lg += *reinterpret_cast<const f32x4*>(red + k * 256 + r16 * 16 + 4 * fxg(r16, kg));
+        if constexpr (F16) {
+            if (r16 < R) lg *= qsc;                                    // the row's query scale 2^-s (exact)
+        }
         if (p.pos_a && r16 < R) lg += *reinterpret_cast<const f32x4*>(red + kRingC * 256 + r16 * 16 + 4 * fxg(r16, kg));
         float pr[4];
         float tmax = -1.0e30f;
@@ -676,7 +779,8 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             uint16_t h, l;
-            split_bf16(pr[j], h, l);
+            if constexpr (F16) split_f16(pr[j] * kF16PScale, h, l);
+            else split_bf16(pr[j], h, l);
             pw[j] = (short)h;
             pw[4 + j] = (short)l;
         }
@@ -704,10 +808,10 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const bool hit = col == (tsv[u] & 255) || col == ((tsv[u] >> 8) & 255) || col == (tsv[u] >> 16);
-                bm[u] = hit ? (short)0x3F80 : (short)0;
+                bm[u] = hit ? (short)(F16 ? 0x3C00 : 0x3F80) : (short)0;     // 1.0 in the token type
             }
             const bf16x8 bm2 = bf16x8{bm[0], bm[1], bm[2], bm[3], bm[0], bm[1], bm[2], bm[3]};
-            const f32x4 mg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pw, bm2, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            const f32x4 mg = RING_MFMA32(pw, bm2, (f32x4{0.f, 0.f, 0.f, 0.f}));
             asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");             // MFMA -> VALU read, as above
 #pragma unroll
             for (int j = 0; j < 4; ++j) mgacc[j] = fmaf(mgacc[j], al[j], mg[j]);
@@ -723,7 +827,8 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
         if (i0 + 16 >= p.WSZ) {
             const int w = wb + wr0;
             const int row = __builtin_amdgcn_readfirstlane(rowA);
-            const float linv = 1.0f / __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l_run), row));
+            float linv = 1.0f / __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l_run), row));
+            if constexpr (F16) linv *= 1.0f / kF16PScale;                  // (the accumulators carry 2^14: see kF16PScale)
             const int rk = row >> 2, rj = row & 3;
             // The row sits in 16 lanes as KS values 16 channels apart.  A hop through a wave-private scratch
             // inside red (idle between the softmax reads and the next [A]... see the barrier below) regroups it
@@ -813,6 +918,12 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
     
         } else {
             float* mgs = red;                                              // [64 slots][16 rows]  (red: 9 x 256 floats)
+            if constexpr (F16) {                                           // accumulators and marginals from 2^14 down to 2^4 (kF16PScale)
+#pragma unroll
+                for (int cb = 0; cb < KS; ++cb) acc[cb] *= kF16PeScale / kF16PScale;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mgacc[j] *= kF16PeScale / kF16PScale;
+            }
             for (int b = 0; b < nslot_tiles; ++b) {
                 const int t = ntile + b;
                 lds_barrier();                                             // [A] pe tile b landed; red idle
@@ -827,7 +938,7 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
     #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     uint16_t h, l;
-                    split_bf16(mgs[(16 * b + ts0 + u) * 16 + r16], h, l);
+                    split_tok<F16>(mgs[(16 * b + ts0 + u) * 16 + r16], h, l);
                     pwp[u] = (short)h;
                     pwp[4 + u] = (short)l;
                 }
@@ -875,6 +986,11 @@ __global__ __launch_bounds__(kRingThreads, 1) void fused_ring_kernel(const uint1
     }
     lds_barrier();                                                     // [E] every wave done with the ring
     HICOM_TR(0); HICOM_TR(1);   // tail: value-side pos-emb done
+    if constexpr (F16) {                                               // the accumulators back at their true value
+        const float un = p.pe_hi ? 1.0f / kF16PeScale : 1.0f / kF16PScale;
+#pragma unroll
+        for (int cb = 0; cb < KS; ++cb) acc[cb] *= un;
+    }
     // ---- partial global state of this workgroup --------------------------------------------------
     const long prow = (long)part * 16;
     if (wave == 0 && kg == 0 && r16 < R) {
@@ -982,7 +1098,11 @@ extern "C" int hicom_fused_stream_fwd(const void* ff, const void* fe, const floa
                                       float* part_m, float* part_l,
                                       float* part_acc, int32_t nparts, float* ctx_local, void* ctx_hi,
                                       void* ctx_lo, void* ctx_f16, void* zero_ptr, int64_t zero_bytes, void* part_ctx_f16,
-                                      void* part_marg_f16, int32_t marg_slots, void* stream) {
+                                      void* part_marg_f16, int32_t marg_slots, int32_t tok_dt, const float* q_f32, void* stream) {
+    HICOM_REQUIRE(tok_dt == HICOM_DT_BF16 || tok_dt == HICOM_DT_F16, HICOM_EINVAL, "fused_stream: tok_dt %d (bf16 or fp16 tokens)", tok_dt);
+    // fp16 tokens: the two-tensor form with the pe planes behind the stream (no local_logits, no part_marg), the folded queries as fp32 rows
+    HICOM_REQUIRE(tok_dt != HICOM_DT_F16 || (!local_logits && !part_marg_f16 && q_f32 && (uintptr_t)q_f32 % 16 == 0), HICOM_EUNSUP,
+                  "fused_stream: fp16 tokens take frames_embed (no local_logits), the pe planes (no part_marg_f16) and 16-byte aligned fp32 query rows");
     HICOM_REQUIRE(ff && (fe || local_logits) && q_hi && q_lo && part_m && part_l && (part_acc || part_ctx_f16) && ((pe_hi && pe_lo) || part_marg_f16 || !pos_a) &&
                       (pos_a || !(pe_hi || part_marg_f16)), HICOM_EINVAL, "fused_stream: NULL pointer");
     HICOM_REQUIRE(!part_marg_f16 || (!pe_hi && !pe_lo && part_ctx_f16 && marg_slots >= T + H + W && marg_slots % 8 == 0 && (uintptr_t)part_marg_f16 % 16 == 0), HICOM_EINVAL,
@@ -1028,17 +1148,22 @@ extern "C" int hicom_fused_stream_fwd(const void* ff, const void* fe, const floa
                   "fused_stream: zero_ptr / zero_bytes");
     p.zero_ptr = (unsigned long long*)zero_ptr; p.zero_n = zero_ptr ? (int)(zero_bytes / 8) : 0;
     p.part_marg = (_Float16*)part_marg_f16; p.marg_slots = part_marg_f16 ? marg_slots : 0;
+    p.qf32 = q_f32;
     static bool attr_set = false;
     if (!attr_set) {
         HICOM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_ring_kernel<9, false>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 163840) == hipSuccess &&
                           hipFuncSetAttribute(reinterpret_cast<const void*>(fused_ring_kernel<9, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 163840) == hipSuccess &&
+                          hipFuncSetAttribute(reinterpret_cast<const void*>(fused_ring_kernel<9, false, true>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 163840) == hipSuccess,
                       HICOM_ELAUNCH, "fused_stream: 160 KiB of LDS per workgroup not available");
         attr_set = true;
     }
     // precomputed local logits win over frames_embed when both are given: frames_embed is then not read at all
-    if (local_logits) HICOM_LAUNCH((fused_ring_kernel<9, true>), dim3((unsigned)nparts), dim3(kRingThreads), smem, (hipStream_t)stream,
+    if (tok_dt == HICOM_DT_F16) HICOM_LAUNCH((fused_ring_kernel<9, false, true>), dim3((unsigned)nparts), dim3(kRingThreads), smem, (hipStream_t)stream,
+                                             p.ff, p.fe, p.H, p.W, p.kt, p.ks, p.nwy, p.nwx, p.NW, p.WSZ, p.wpw, p);
+    else if (local_logits) HICOM_LAUNCH((fused_ring_kernel<9, true>), dim3((unsigned)nparts), dim3(kRingThreads), smem, (hipStream_t)stream,
                                    p.ff, p.fe, p.H, p.W, p.kt, p.ks, p.nwy, p.nwx, p.NW, p.WSZ, p.wpw, p);
     else HICOM_LAUNCH((fused_ring_kernel<9, false>), dim3((unsigned)nparts), dim3(kRingThreads), smem, (hipStream_t)stream,
                       p.ff, p.fe, p.H, p.W, p.kt, p.ks, p.nwy, p.nwx, p.NW, p.WSZ, p.wpw, p);

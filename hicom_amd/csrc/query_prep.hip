@@ -51,6 +51,8 @@ struct PrepParams {
     unsigned long long* gran; // [E] granules {tag << 32 | f32 bits}
     unsigned* state;          // [0..1] 64-bit arrival counter, [2] failed hand-offs (sticky count), [3] grid size of the first launch
     int nq_wg, nr_wg, nf_wg, np_wg;      // workgroups per role, in block order: q_proj | r0 | fold-w | fold-pos
+    int g16;                  // the guide (g, lq) is fp16 (fp16 tokens: the local query rows are copied bit for bit, exact fp16 operands)
+    float* qf32;              // [16, E] or NULL: the folded global rows as f32, unsplit (fp16 tokens: the ring kernel splits them itself)
 };
 
 // (round 4: 2 / 4 rows per wave -- 299 workgroups, 18 / 36 KB of cold weights each -- measured 10.9 us against 9.3 us: more than
@@ -66,7 +68,7 @@ constexpr int kQRows = 4;                // q_proj outputs per wave (72 workgrou
 constexpr int kRRows = 4;                // r0 outputs per wave (round 5: 8 made the 28 r0 workgroups -- 73 KB of cold weights each -- the LAST to leave the launch, tools/prep_trace.py)
 constexpr int kPrepCh = 3;               // 16-byte chunks per lane and row: K <= 1536
 
-__device__ __forceinline__ void prep_load_x(const uint16_t* g, const uint16_t* add, int K, int lane, float (&x)[kPrepCh][8]) {
+__device__ __forceinline__ void prep_load_x(const uint16_t* g, const uint16_t* add, int K, int lane, float (&x)[kPrepCh][8], int g16 = 0) {
 #pragma unroll
     for (int c = 0; c < kPrepCh; ++c) {
         const int k = (lane + 64 * c) * 8;
@@ -74,8 +76,13 @@ __device__ __forceinline__ void prep_load_x(const uint16_t* g, const uint16_t* a
             const u32x4 v = *reinterpret_cast<const u32x4*>(g + k);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                x[c][2 * i] = bf16lo_to_f32(v[i]);
-                x[c][2 * i + 1] = bf16hi_to_f32(v[i]);
+                if (g16) {                                           // (fp16 guide: exact in f32)
+                    x[c][2 * i] = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[i] & 0xFFFFu));
+                    x[c][2 * i + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[i] >> 16));
+                } else {
+                    x[c][2 * i] = bf16lo_to_f32(v[i]);
+                    x[c][2 * i + 1] = bf16hi_to_f32(v[i]);
+                }
             }
             if (add) {
                 const u32x4 a = *reinterpret_cast<const u32x4*>(add + k);
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const uint16_t* g0, con
         const int n0 = (b * 4 + wave) * kQRows;
         prep_load_w<kQRows>(p.wq, p.E, p.E, n0 < p.E ? n0 : 0, lane, wv);
         float x[kPrepCh][8];
-        prep_load_x(p.g, nullptr, p.E, lane, x);
+        prep_load_x(p.g, nullptr, p.E, lane, x, p.g16);
         // the epoch is needed at the store only: its (memory-side) read runs under the weight loads; so does the bias
         const unsigned epoch = read_epoch(cnt);
         const int nb = n0 + (lane < kQRows ? lane : 0);
@@ -178,7 +185,7 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const uint16_t* g0, con
         const int n0 = ((b - p.nq_wg) * 4 + wave) * kRRows;
         prep_load_w<kRRows>(p.gw0, p.hidden, p.E, n0 < p.hidden ? n0 : 0, lane, wv);
         float x[kPrepCh][8];
-        prep_load_x(p.g, p.bo, p.E, lane, x);
+        prep_load_x(p.g, p.bo, p.E, lane, x, p.g16);
         const int nb = n0 + (lane < kRRows ? lane : 0);
         const float bias = nb < p.hidden ? bf16_to_f32(p.gb0[nb]) : 0.f;
         float out[kRRows];
@@ -271,11 +278,15 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const uint16_t* g0, con
                     v1 += red[g2][2 * tid + 1];
                 }
                 v0 *= p.scale; v1 *= p.scale;
+                if (p.qf32) {
+                    *reinterpret_cast<float2*>(p.qf32 + (long)h * p.E + c) = make_float2(v0, v1);
+                } else {
                 uint16_t h0, l0, h1, l1;
                 split_bf16(v0, h0, l0);
                 split_bf16(v1, h1, l1);
                 *reinterpret_cast<uint32_t*>(p.qhi + (long)h * p.E + c) = (uint32_t)h0 | ((uint32_t)h1 << 16);
                 *reinterpret_cast<uint32_t*>(p.qlo + (long)h * p.E + c) = (uint32_t)l0 | ((uint32_t)l1 << 16);
+                }
             } else if (tid < 128) {
                 // local query rows R .. 15 of the hi plane = the guide (lo plane stays zero): rows R + h, R + h + nh, ...
                 const int c = slab * 128 + 2 * (tid - 64);
@@ -320,7 +331,9 @@ extern "C" int64_t hicom_query_prep_state_bytes(int32_t E) { return (int64_t)E *
 extern "C" int hicom_query_prep_fwd(const void* guide, const void* local_q, const void* w_q, const void* b_q, const void* w_k, const float* kpe,
                                     int32_t nh, int32_t E, int32_t P, float scale, void* qt_hi, void* qt_lo, float* pos_a,
                                     int32_t pos_stride, int32_t rows, const void* g_w0, const void* g_b0, const void* b_o,
-                                    int32_t hidden, float* r0, void* state, void* stream) {
+                                    int32_t hidden, float* r0, void* state, int32_t g_dt, float* qt_f32, void* stream) {
+    HICOM_REQUIRE(g_dt == HICOM_DT_BF16 || (g_dt == HICOM_DT_F16 && qt_f32 && (uintptr_t)qt_f32 % 16 == 0), HICOM_EINVAL,
+                  "query_prep: g_dt %d (bf16, or fp16 with 16-byte aligned f32 query rows)", g_dt);
     HICOM_REQUIRE(guide && local_q && w_q && w_k && qt_hi && qt_lo && state, HICOM_EINVAL, "query_prep: NULL pointer");
     HICOM_REQUIRE(nh > 0 && E > 0 && E % nh == 0 && E / nh <= 128 && E % 128 == 0 && E <= 1536 && rows == nh && rows <= 16, HICOM_EINVAL,
                   "query_prep: bad shape (E %% 128, head dim <= 128, one query row per head)");
@@ -334,6 +347,7 @@ extern "C" int hicom_query_prep_fwd(const void* guide, const void* local_q, cons
     p.qhi = (uint16_t*)qt_hi; p.qlo = (uint16_t*)qt_lo; p.pos_a = pos_a; p.pos_stride = pos_stride; p.R = rows;
     p.gw0 = (const uint16_t*)g_w0; p.gb0 = (const uint16_t*)g_b0; p.bo = (const uint16_t*)b_o; p.hidden = g_w0 ? hidden : 0; p.r0 = r0;
     p.gran = (unsigned long long*)((char*)state + kPrepStateHead); p.state = (unsigned*)state;
+    p.g16 = g_dt == HICOM_DT_F16 ? 1 : 0; p.qf32 = g_dt == HICOM_DT_F16 ? qt_f32 : nullptr;
     p.nq_wg = (E + 4 * kQRows - 1) / (4 * kQRows);
     p.nr_wg = p.hidden ? (p.hidden + 4 * kRRows - 1) / (4 * kRRows) : 0;
     p.nf_wg = nh * (E / 128);

@@ -55,6 +55,7 @@ struct AuxGemv {
     long ldd, row0;
     const long long* x_fixed;   // alternative x: fixed-point accumulators (value * HICOM_FIXED_SCALE), or NULL
     int x_clear;                // GEMV_CHAIN: role workgroup 0 clears x_fixed once every workgroup has read it
+    int dst_f16;                // dst is fp16 (saturating) rather than bf16 (dst_f32 == 0)
 };
 
 struct R16Params {
@@ -64,8 +65,9 @@ struct R16Params {
     int b_f32;
     int M, N, K, act;
     _Float16* o16;          // fp16 plane [M][N] (hidden activations for the next GEMM), or NULL
-    void* y;                // packed rows of the final tensor (dtype y_f32 ? f32 : bf16), or NULL
+    void* y;                // packed rows of the final tensor (dtype y_f32 ? f32 : y_f16 ? fp16 (saturating) : bf16), or NULL
     int y_f32;
+    int y_f16;
     long ldy, row0;
     int nl_group;
     int vec, bvec;
@@ -228,6 +230,7 @@ __device__ __forceinline__ void aux_gemv_role(const AuxGemv& g, int aux_idx, int
                 for (int j = 0; j < CB; ++j)
                     if (n0 + j < n_end) {
                         if (g.dst_f32) reinterpret_cast<float*>(g.dst)[o + j] = vout[j];
+                        else if (g.dst_f16) reinterpret_cast<_Float16*>(g.dst)[o + j] = to_f16_sat(vout[j]);
                         else reinterpret_cast<uint16_t*>(g.dst)[o + j] = f32_to_bf16(vout[j]);
                     }
             }
@@ -300,7 +303,7 @@ struct ChainLate {
     float *y1, *y2;
     void* dst;
     long ldd, row0;
-    int b1_f32, b2_f32, act1, act2, dst_f32, reps, x_clear, K2;
+    int b1_f32, b2_f32, act1, act2, dst_f32, reps, x_clear, K2, dst_f16;
 };
 typedef const __attribute__((address_space(4))) R16Params* r16_kernarg_ptr;
 template <bool W1F32, class Mid, bool BIG = false, bool LATE = false>
@@ -376,10 +379,12 @@ __device__ __forceinline__ void gemv_chain_role(const R16Params& p, int ai, int 
         L.xb = late->aux.xb; L.b1 = late->aux.b; L.b2 = late->aux2.b; L.res1 = late->aux.res; L.res2 = late->aux2.res; L.y1 = late->aux.y; L.y2 = late->aux2.y;
         L.dst = late->aux2.dst; L.ldd = late->aux2.ldd; L.row0 = late->aux2.row0; L.b1_f32 = late->aux.b_f32; L.b2_f32 = late->aux2.b_f32;
         L.act1 = late->aux.act; L.act2 = late->aux2.act; L.dst_f32 = late->aux2.dst_f32; L.reps = late->aux2.reps; L.x_clear = late->aux.x_clear; L.K2 = late->aux2.K;
+        L.dst_f16 = late->aux2.dst_f16;
     } else {
         L.xb = g1.xb; L.b1 = g1.b; L.b2 = g2.b; L.res1 = g1.res; L.res2 = g2.res; L.y1 = g1.y; L.y2 = g2.y;
         L.dst = g2.dst; L.ldd = g2.ldd; L.row0 = g2.row0; L.b1_f32 = g1.b_f32; L.b2_f32 = g2.b_f32;
         L.act1 = g1.act; L.act2 = g2.act; L.dst_f32 = g2.dst_f32; L.reps = g2.reps; L.x_clear = g1.x_clear; L.K2 = g2.K;
+        L.dst_f16 = g2.dst_f16;
     }
     const unsigned b1raw = bias_raw(L.b1, L.b1_f32, g1.w, g1.N, n_lo + tid), b2raw = bias_raw(L.b2, L.b2_f32, g2.w, g2.N, m_lo + tid);
     __builtin_amdgcn_sched_barrier(0);
@@ -549,6 +554,7 @@ __device__ __forceinline__ void gemv_chain_role(const R16Params& p, int ai, int 
             const int rr = idx / ncol, c = idx - rr * ncol;
             const long o = (L.row0 + rr) * L.ldd + m_lo + c;
             if (L.dst_f32) reinterpret_cast<float*>(L.dst)[o] = yl[c];
+            else if (L.dst_f16) reinterpret_cast<_Float16*>(L.dst)[o] = to_f16_sat(yl[c]);
             else reinterpret_cast<uint16_t*>(L.dst)[o] = f32_to_bf16(yl[c]);
         }
     }
@@ -996,7 +1002,8 @@ __device__ __forceinline__ bool r16_tile(const R16Params& p, int tile, char* lds
         constexpr int TP = TN + 8;                                 // row pitch in 16-bit elements: 16-byte aligned rows, shifted banks
         uint16_t* tl = reinterpret_cast<uint16_t*>(lds);
         __syncthreads();                                           // every wave has read its last fragments out of the ring
-        const bool to_f16 = p.o16 != nullptr;
+        const bool to_f16 = p.o16 != nullptr;                      // (destination: the fp16 plane, else y)
+        const bool cvt_f16 = to_f16 || p.y_f16;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             float bias[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1021,7 +1028,7 @@ __device__ __forceinline__ bool r16_tile(const R16Params& p, int tile, char* lds
                     float v = acc[j][im][q] + bias[q];
                     if (p.act == HICOM_ACT_GELU) v = gelu_erf(v);
                     if (MODE == R16_CONSUME && poisoned) v = __uint_as_float(0x7FC00000u);     // the row block never arrived: fail loudly
-                    if (to_f16) {
+                    if (cvt_f16) {
                         const _Float16 hv = to_f16_sat(v);
                         h[q] = __builtin_bit_cast(uint16_t, hv);
                     } else {
@@ -1104,6 +1111,11 @@ __device__ __forceinline__ bool r16_tile(const R16Params& p, int tile, char* lds
                     if (vec) *reinterpret_cast<float4*>(yo) = make_float4(v[0], v[1], v[2], v[3]);
                     else
                         for (int q = 0; q < 4 && n + q < p.N; ++q) yo[q] = v[q];
+                } else if (p.y_f16) {
+                    _Float16* yo = reinterpret_cast<_Float16*>(p.y) + orow * p.ldy + n;
+                    if (vec) *reinterpret_cast<half4*>(yo) = half4{to_f16_sat(v[0]), to_f16_sat(v[1]), to_f16_sat(v[2]), to_f16_sat(v[3])};
+                    else
+                        for (int q = 0; q < 4 && n + q < p.N; ++q) yo[q] = to_f16_sat(v[q]);
                 } else {
                     uint16_t* yo = reinterpret_cast<uint16_t*>(p.y) + orow * p.ldy + n;
                     if (vec) {
@@ -1376,7 +1388,7 @@ static int r16_build(const void* a, const void* w, const void* b, int32_t b_dt,
     HICOM_REQUIRE(((uintptr_t)a % 16 == 0) && ((uintptr_t)w % 16 == 0) && M < (1 << 30), HICOM_EINVAL, "readout16_gemm: alignment");
     const bool vec = N % 4 == 0 && (!out_f16 || ((uintptr_t)out_f16 % 8 == 0)) && (!y || (ldy % 4 == 0 && (uintptr_t)y % 16 == 0));
     p.a = (const _Float16*)a; p.w = (const _Float16*)w; p.b = b; p.b_f32 = b_dt == HICOM_DT_F32;
-    p.M = M; p.N = N; p.K = K; p.act = act; p.o16 = (_Float16*)out_f16; p.y = y; p.y_f32 = y_dt == HICOM_DT_F32;
+    p.M = M; p.N = N; p.K = K; p.act = act; p.o16 = (_Float16*)out_f16; p.y = y; p.y_f32 = y_dt == HICOM_DT_F32; p.y_f16 = y_dt == HICOM_DT_F16;
     p.ldy = (long)ldy; p.row0 = (long)row0; p.nl_group = nl_group; p.vec = vec ? 1 : 0; p.bvec = (b && (uintptr_t)b % 16 == 0) ? 1 : 0;
     {
         const bool y16 = y && y_dt != HICOM_DT_F32;
@@ -1416,7 +1428,7 @@ static int r16_build(const void* a, const void* w, const void* b, int32_t b_dt,
         return AuxGemv{aux->xs, aux->x_parts, (long)aux->x_stride, (const uint16_t*)aux->xb, aux->w,
                        aux->b, (const uint16_t*)aux->res, aux->N, aux->K, aux->act, aux->y, aux->w_dt == HICOM_DT_F32, aux->b_dt == HICOM_DT_F32,
                        aux->rows_dst, aux->rows_dt == HICOM_DT_F32, aux->rows_dst ? aux->rows_reps : 0, (long)aux->rows_ld, (long)aux->rows_row0,
-                       (const long long*)aux->x_fixed, aux->x_fixed_clear ? 1 : 0};
+                       (const long long*)aux->x_fixed, aux->x_fixed_clear ? 1 : 0, aux->rows_dt == HICOM_DT_F16 ? 1 : 0};
     };
     auto check_gemv = [](const hicom_aux_gemv* aux, bool needs_x, bool needs_out = true, int kmax = 1536) -> int {
         HICOM_REQUIRE(aux->w && (!needs_out || aux->y || aux->rows_dst) && aux->N > 0 && aux->K > 0 && aux->K % 8 == 0 && aux->K <= kmax && ((uintptr_t)aux->w % 16 == 0), HICOM_EINVAL,

@@ -348,15 +348,36 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float* x, int row
     lo[i] = l;
 }
 
-__global__ __launch_bounds__(256) void scatter_rows_kernel(const void* src, int src_f32, int src_rows, int ncols,
-                                                           void* dst, int dst_f32, long ldd, long row0, long row_step,
+// the fp16 form (hicom_split16_fwd): x ~= hi + lo, |x - hi - lo| <= 2^-23 |x| + 2^-25 (lo may be subnormal)
+__global__ __launch_bounds__(256) void split_f16_kernel(const float* x, int rows, int rows_pad, int E, _Float16* hi, _Float16* lo) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)rows_pad * E) return;
+    const long r = i / E;
+    _Float16 h = (_Float16)0.f, l = (_Float16)0.f;
+    if (r < rows) {
+        h = (_Float16)x[i];
+        l = (_Float16)(x[i] - (float)h);
+    }
+    hi[i] = h;
+    lo[i] = l;
+}
+
+// one element of a row copy: f32 / bf16 / fp16 in, f32 / bf16 / fp16 (saturating) out
+__device__ __forceinline__ float load_dt(const void* p, long i, int dt) {
+    if (dt == HICOM_DT_F32) return reinterpret_cast<const float*>(p)[i];
+    const uint16_t u = reinterpret_cast<const uint16_t*>(p)[i];
+    return dt == HICOM_DT_F16 ? (float)__builtin_bit_cast(_Float16, u) : bf16_to_f32(u);
+}
+
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const void* src, int src_dt, int src_rows, int ncols,
+                                                           void* dst, int dst_dt, long ldd, long row0, long row_step,
                                                            int nl_group, int count) {
     const int i = blockIdx.x;
     const long sr = i % src_rows, dr = row0 + (long)i * row_step + (nl_group > 0 ? i / nl_group : 0);
     for (int c = threadIdx.x; c < ncols; c += 256) {
-        const float v = src_f32 ? reinterpret_cast<const float*>(src)[sr * ncols + c]
-                                : bf16_to_f32(reinterpret_cast<const uint16_t*>(src)[sr * ncols + c]);
-        if (dst_f32) reinterpret_cast<float*>(dst)[dr * ldd + c] = v;
+        const float v = load_dt(src, sr * ncols + c, src_dt);
+        if (dst_dt == HICOM_DT_F32) reinterpret_cast<float*>(dst)[dr * ldd + c] = v;
+        else if (dst_dt == HICOM_DT_F16) reinterpret_cast<_Float16*>(dst)[dr * ldd + c] = (_Float16)fminf(fmaxf(v, -65504.f), 65504.f);
         else reinterpret_cast<uint16_t*>(dst)[dr * ldd + c] = f32_to_bf16(v);
     }
 }
@@ -664,14 +685,27 @@ extern "C" int hicom_split_bf16_fwd(const float* x, int32_t rows, int32_t rows_p
     return hicom_host::check_launch("split_bf16");
 }
 
+extern "C" int hicom_split16_fwd(const float* x, int32_t rows, int32_t rows_pad, int32_t E, int32_t dt, void* hi, void* lo, void* stream) {
+    HICOM_REQUIRE(dt == HICOM_DT_BF16 || dt == HICOM_DT_F16, HICOM_EINVAL, "split16: dt %d (bf16 or fp16 planes)", dt);
+    if (dt == HICOM_DT_BF16) return hicom_split_bf16_fwd(x, rows, rows_pad, E, hi, lo, stream);
+    HICOM_REQUIRE(x && hi && lo, HICOM_EINVAL, "split16: NULL pointer");
+    HICOM_REQUIRE(rows > 0 && rows_pad >= rows && E > 0, HICOM_EINVAL, "split16: bad shape");
+    const long n = (long)rows_pad * E;
+    hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, rows, rows_pad, E, (_Float16*)hi,
+                       (_Float16*)lo);
+    return hicom_host::check_launch("split16");
+}
+
 extern "C" int hicom_scatter_rows_fwd(const void* src, int32_t src_dt, int32_t src_rows, int32_t ncols,
                                       void* dst, int32_t dst_dt, int64_t ldd, int64_t row0, int64_t row_step,
                                       int32_t nl_group, int32_t count, void* stream) {
     HICOM_REQUIRE(src && dst, HICOM_EINVAL, "scatter_rows: NULL pointer");
     HICOM_REQUIRE(src_rows > 0 && ncols > 0 && count >= 0 && ldd >= ncols && nl_group >= 0, HICOM_EINVAL, "scatter_rows: bad shape");
     if (count == 0) return HICOM_OK;
+    HICOM_REQUIRE(src_dt >= HICOM_DT_BF16 && src_dt <= HICOM_DT_F16 && dst_dt >= HICOM_DT_BF16 && dst_dt <= HICOM_DT_F16, HICOM_EINVAL,
+                  "scatter_rows: dtypes %d -> %d", src_dt, dst_dt);
     hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)count), dim3(256), 0, (hipStream_t)stream, src,
-                       src_dt == HICOM_DT_F32, src_rows, ncols, dst, dst_dt == HICOM_DT_F32, (long)ldd, (long)row0,
+                       src_dt, src_rows, ncols, dst, dst_dt, (long)ldd, (long)row0,
                        (long)row_step, nl_group, count);
     return hicom_host::check_launch("scatter_rows");
 }

@@ -102,16 +102,29 @@ def _fill_injector(j, inj, mode, guide, visual, keep):
     keep.append(guide)
 
 
+class Fp16NotFused(NotImplementedError):
+    """fp16 tokens: this call does not take the fused release step (the fp16 projector then casts its inputs to bf16)."""
+
+
 def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, t_offset=0,
                phases=nv.PHASE_STREAM | nv.PHASE_FINISH, local_out=None, state_out=None,
-               state_sets=None, state_set_stride=0, nsets=0, global_row0=None, stages=("local", "global"), local_row0=0) -> nv.CompressorArgs:
+               state_sets=None, state_set_stride=0, nsets=0, global_row0=None, stages=("local", "global"), local_row0=0,
+               tok16=False) -> nv.CompressorArgs:
     """`stages` / `local_row0`: one SEGMENT of an anyres dict input (reference projector.py:679-689: the base image takes the local stage
-    only; the patch grid both, its rows behind the base image's) written into rows of a shared output."""
+    only; the patch grid both, its rows behind the base image's) written into rows of a shared output.
+    tok16: fp16 frames_feature / frames_embed / guide (hicom_compressor_args.tok_dt; the release step only: Fp16NotFused otherwise)."""
     from .projector import _require_bf16_cuda
+
+    def _require_tok(name, t):
+        if not tok16:
+            return _require_bf16_cuda(name, t)
+        if not t.is_cuda or t.dtype != torch.float16:
+            raise Fp16NotFused(f"{name}: fp16 tokens take fp16 CUDA tensors (got {t.dtype} on {t.device})")
     lc = proj.local_compressor if "local" in stages else None
     gc = proj.global_compressor if "global" in stages else None
     a = nv.CompressorArgs()
-    _require_bf16_cuda("frames_feature", ff)
+    _require_tok("frames_feature", ff)
+    a.tok_dt = nv.DT_F16 if tok16 else nv.DT_BF16
     T, H, W, E = ff.shape
     a.ff, a.T, a.H, a.W, a.E = ff.data_ptr(), T, H, W, E
     a.fe = None
@@ -125,7 +138,7 @@ def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, 
     if lc is not None:
         lc._check_native()
         if fe is not None:
-            _require_bf16_cuda("frames_embed", fe)
+            _require_tok("frames_embed", fe)
             if fe.shape != ff.shape:
                 raise ValueError("frames_embed must have the shape of frames_feature")
             a.fe = fe.data_ptr()
@@ -159,10 +172,10 @@ def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, 
             a.lq, a.lq_dt, a.lq_stride = ext_l[0].data_ptr(), nv.DT_F32, 0 if rows == 1 else E
         elif lc.use_guide == "direct":
             g = guide_embed
-            _require_bf16_cuda("guide_embed", g)
+            _require_tok("guide_embed", g)
             if g.ndim != 1 or g.shape[0] != E:
                 raise ValueError("direct guide injection takes a [D] guide embedding")
-            a.lq, a.lq_dt, a.lq_stride = g.data_ptr(), nv.DT_BF16, 0
+            a.lq, a.lq_dt, a.lq_stride = g.data_ptr(), nv._dt(g), 0
             a._guide_ptr_fields += ("lq",)
             keep.append(g)
         else:
@@ -203,6 +216,14 @@ def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, 
             ext_g = torch.empty((q_in.shape[0], E), dtype=torch.float32, device=ff.device)
             q_in = ext_g
             a.gq_dt = nv.DT_F32
+        elif tok16:
+            # (the fp16 release step: the injected query row IS the fp16 guide -- direct mode through a plain injector)
+            if not (gc.use_guide == "direct" and gc.is_plain and guide_embed is not None):
+                raise Fp16NotFused("fp16 tokens: the global stage takes the direct guide")
+            _require_tok("guide_embed", guide_embed)
+            q_in, n_rows = guide_embed.reshape(1, -1), gc.num_queries
+            a.gq_dt = nv.DT_F16
+            keep.append(q_in)
         else:
             q_in, n_rows = gc.injected_queries(guide_embed)
             a.gq_dt = nv.DT_BF16
@@ -224,7 +245,7 @@ def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, 
             keep.append(c0)
         if gc.use_pos_emb:
             pe, kpe, cap = gc.pos_and_kpe(t_offset + T, H, W, ff.device)
-            pe_hi, pe_lo = gc.pos_planes(t_offset + T, H, W, ff.device)
+            pe_hi, pe_lo = gc.pos_planes(t_offset + T, H, W, ff.device, torch.float16 if tok16 else torch.bfloat16)
             a.pe, a.kpe, a.P = pe.data_ptr(), kpe.data_ptr(), pe.shape[0]
             a.pe_hi, a.pe_lo = pe_hi.data_ptr(), pe_lo.data_ptr()
             a.t_index0, a.y_index0, a.x_index0 = t_offset, cap, cap + H
@@ -430,7 +451,8 @@ def run_anyres(proj, frames_feature, frames_embed, guide_embed, modal, image_new
     return out
 
 
-def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferred: bool = False, local_logits=None, adapt_y=None, segment=None):
+def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferred: bool = False, local_logits=None, adapt_y=None, segment=None,
+              tok16: bool = False):
     """HIComProjector.forward for a dense [T,H,W,E] input through hicom_compressor_fwd.
 
     adapt_y = (y_k, y_v): fp16 [T*H*W, E] outputs of the k / v adaptor MLPs the caller computed itself (the training forward keeps
@@ -442,9 +464,15 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
 
     deferred=True returns (out, event): the main stream does not wait for the side stream's global chain (merge +
     the four small linears that produce the 32 global rows); `event` fires when they are written.  Back-to-back
-    forwards of independent videos then overlap that latency-bound chain with the next video's streaming."""
+    forwards of independent videos then overlap that latency-bound chain with the next video's streaming.
+
+    tok16=True: fp16 frames_feature / frames_embed / guide / newline (an fp16 projector's bf16 twin, HIComProjector._forward_half) straight
+    into the release step's fp16 kernels; raises Fp16NotFused, before any workspace is allocated, when the plan is not that step."""
     from .projector import _require_bf16_cuda
-    _require_bf16_cuda("frames_feature", ff)          # fail loudly on CPU tensors before touching any stream
+    if not tok16:
+        _require_bf16_cuda("frames_feature", ff)      # fail loudly on CPU tensors before touching any stream
+    elif deferred or segment is not None or local_logits is not None or adapt_y is not None:
+        raise Fp16NotFused("fp16 tokens: dense, joined calls only")
     stages = segment["stages"] if segment is not None else ("local", "global")
     lc = proj.local_compressor if "local" in stages else None
     gc = proj.global_compressor if "global" in stages else None
@@ -463,7 +491,7 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
            (ff.data_ptr(), _p(fe), _p(guide), _p(nl), _p(ll), None if adapt_y is None else tuple(_p(t) for t in adapt_y)) if graph else None,
            ll is not None,
            None if adapt_y is None else tuple(t is not None for t in adapt_y),     # (supplied adaptor outputs: the workspace has no regions for them)
-           seg_key)
+           seg_key, ff.dtype)
     plans = proj.__dict__.setdefault("_engine_plans", {})
     plan = plans.get(key)
     sig = plan_sig(proj)
@@ -491,7 +519,9 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
         hidden = (lc or gc).readout[2].out_features
         row0 = segment["row0"] if segment is not None else 0
         probe = segment["out"] if segment is not None else torch.empty((n_local + n_global, hidden), dtype=out_dtype, device=dev)
-        a = build_args(proj, ff, fe, guide, modal, nl, probe, layout, global_row0=row0 + n_local, stages=stages, local_row0=row0)
+        a = build_args(proj, ff, fe, guide, modal, nl, probe, layout, global_row0=row0 + n_local, stages=stages, local_row0=row0, tok16=tok16)
+        if tok16 and not nv.compressor_is_fused(a):
+            raise Fp16NotFused("fp16 tokens: this geometry / recipe does not run on the fused release step")
         if adapt_y is not None:             # (before the workspace is sized: make_layout skips the regions of supplied outputs)
             a.ak.y = _p(adapt_y[0])
             a.av.y = _p(adapt_y[1])

@@ -16,14 +16,14 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 # HICOM_NATIVE_LIB: dev override (instrumented builds from tools/); the product loads the in-tree library
 LIB_PATH = os.environ.get("HICOM_NATIVE_LIB") or os.path.join(HERE, "libhicom_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 DT_BF16, DT_F32, DT_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_GELU_TANH = 0, 1, 2
 
 EXPORTS = (
     "hicom_abi_version", "hicom_last_error", "hicom_local_attn_fwd", "hicom_local_attn_bwd", "hicom_trilinear_pool_fwd",
-    "hicom_linear_fwd", "hicom_fold_query_fwd", "hicom_split_bf16_fwd", "hicom_global_stream_fwd",
+    "hicom_linear_fwd", "hicom_fold_query_fwd", "hicom_split_bf16_fwd", "hicom_split16_fwd", "hicom_global_stream_fwd",
     "hicom_global_stream_nparts", "hicom_global_merge_fwd", "hicom_global_combine_fwd",
     "hicom_readout_gemm_fwd", "hicom_scatter_rows_fwd", "hicom_fold_query_split_fwd",
     "hicom_global_combine_strided_fwd", "hicom_compressor_workspace_bytes", "hicom_compressor_zero_prefix_bytes", "hicom_compressor_is_fused",
@@ -133,6 +133,7 @@ class CompressorArgs(C.Structure):
         ("vpe_f16", C.c_void_p), ("marg_slots", C.c_int32),
         ("ag_fn", C.c_void_p), ("ag_comm", C.c_void_p), ("ag_send", C.c_void_p), ("ag_recv", C.c_void_p), ("ag_bytes", C.c_int64),
         ("ag_group_start", C.c_void_p), ("ag_group_end", C.c_void_p), ("ag_send2", C.c_void_p), ("ag_recv2", C.c_void_p), ("ag_bytes2", C.c_int64),
+        ("tok_dt", C.c_int32),
     ]
 
 
@@ -163,6 +164,7 @@ def lib() -> C.CDLL:
     L.hicom_linear_fwd.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
     L.hicom_fold_query_fwd.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
     L.hicom_split_bf16_fwd.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.hicom_split16_fwd.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     L.hicom_global_stream_fwd.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64,
                                           vp, vp, vp, i32, vp]
     L.hicom_global_stream_nparts.argtypes = [i64, i32]
@@ -177,7 +179,7 @@ def lib() -> C.CDLL:
                                          vp, vp, vp, i32, vp]
     L.hicom_linear_to_rows_fwd.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_fused_stream_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, i32, vp, vp, i32, i32, i32,
-                                         vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp]
+                                         vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
     L.hicom_readout16_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, C.POINTER(AuxGemv), vp]
     L.hicom_readout16_gemm_role_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, C.POINTER(R16Role), vp]
     L.hicom_r16_chain_state_bytes.argtypes = [i32]
@@ -219,7 +221,7 @@ def lib() -> C.CDLL:
     L.hicom_fused_stream_nparts.argtypes = [i32]
     L.hicom_query_prep_state_bytes.argtypes = [i32]
     L.hicom_query_prep_state_bytes.restype = i64
-    L.hicom_query_prep_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.hicom_query_prep_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
     L.hicom_planes_gemm_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i64, i64, i32, vp]
     L.hicom_row_ln_fwd.argtypes = [vp, i32, i64, vp, i64, vp, i64, vp, vp, i32, vp, i32, i64, vp, i32, f32, vp, i32, i64,
                                    i32, i32, vp]
@@ -271,7 +273,7 @@ def _dt(t: torch.Tensor) -> int:
         return DT_F32
     if t.dtype == torch.float16:
         return DT_F16
-    raise HicomNativeError(f"unsupported dtype {t.dtype} (bf16 or f32 only)")
+    raise HicomNativeError(f"unsupported dtype {t.dtype} (bf16, fp16 or f32)")
 
 
 def _stream():
@@ -421,6 +423,14 @@ def fold_query(qp, w_k, nh, scale, qt):
 def split_bf16(x, rows_pad, hi, lo):
     rows, E = x.shape
     _check(lib().hicom_split_bf16_fwd(_ptr(x), rows, rows_pad, E, _ptr(hi), _ptr(lo), _stream()), "hicom_split_bf16_fwd")
+
+
+def split16(x, rows_pad, hi, lo):
+    """f32 rows -> hi + lo planes of hi's 16-bit type (bf16 or fp16), zero rows up to rows_pad (hicom_split16_fwd)."""
+    rows, E = x.shape
+    if lo.dtype != hi.dtype:
+        raise HicomNativeError("split16: hi and lo planes of one dtype")
+    _check(lib().hicom_split16_fwd(_ptr(x), rows, rows_pad, E, _dt(hi), _ptr(hi), _ptr(lo), _stream()), "hicom_split16_fwd")
 
 
 def global_stream_nparts(N, rows_pad) -> int:
@@ -622,10 +632,12 @@ def fused_stream_nparts(n_windows: int) -> int:
 
 
 def fused_stream(ff, fe, kt, ks, qhi, qlo, rows, l_scale, l_bias, pos_a, pe_hi, pe_lo, t0i, y0i, x0i, part_m, part_l,
-                 part_acc, ctx_local, ctx_hi=None, ctx_lo=None, ctx_f16=None, local_logits=None, zero=None, part_ctx_f16=None, part_marg=None):
+                 part_acc, ctx_local, ctx_hi=None, ctx_lo=None, ctx_f16=None, local_logits=None, zero=None, part_ctx_f16=None, part_marg=None,
+                 q_f32=None):
     """pos_a f32 [16, P] + pe_hi / pe_lo bf16 [P, E] (all three or none): the kernel folds the value-side
     pos-emb into part_acc.  local_logits f32 [T*H*W] (fe . local query per token) replaces the frames_embed stream.
-    part_marg fp16 [nparts, rows, S] (with pe_hi = pe_lo = None): the normalised positional marginals leave the kernel instead."""
+    part_marg fp16 [nparts, rows, S] (with pe_hi = pe_lo = None): the normalised positional marginals leave the kernel instead.
+    fp16 ff / fe: the kernel's fp16 instantiation; the folded global rows then come as q_f32 f32 [16, E] and pe_hi / pe_lo are fp16."""
     T, H, W, E = ff.shape
     _check(lib().hicom_fused_stream_fwd(_ptr(ff), _ptr(fe), _ptr(local_logits), T, H, W, E, kt, ks, _ptr(qhi), _ptr(qlo), rows, l_scale,
                                         l_bias, _ptr(pos_a), pos_a.shape[1] if pos_a is not None else 0,
@@ -633,7 +645,8 @@ def fused_stream(ff, fe, kt, ks, qhi, qlo, rows, l_scale, l_bias, pos_a, pe_hi, 
                                         _ptr(part_m), _ptr(part_l), _ptr(part_acc), part_m.shape[0], _ptr(ctx_local),
                                         _ptr(ctx_hi), _ptr(ctx_lo), _ptr(ctx_f16), _ptr(zero),
                                         zero.numel() * zero.element_size() if zero is not None else 0, _ptr(part_ctx_f16),
-                                        _ptr(part_marg), part_marg.shape[-1] if part_marg is not None else 0, _stream()),
+                                        _ptr(part_marg), part_marg.shape[-1] if part_marg is not None else 0, _dt(ff), _ptr(q_f32),
+                                        _stream()),
            "hicom_fused_stream_fwd")
 
 
@@ -1007,13 +1020,15 @@ def query_prep_state(E, device):
     return torch.zeros(int(lib().hicom_query_prep_state_bytes(E)), dtype=torch.uint8, device=device)
 
 
-def query_prep(guide, local_q, w_q, b_q, w_k, kpe, nh, scale, qhi, qlo, pos_a, state, g_w0=None, g_b0=None, b_o=None, r0=None):
-    """One-launch q_proj + fold (+ positional table, local query rows, r0) of the direct recipe; see include/hicom_hip.h."""
+def query_prep(guide, local_q, w_q, b_q, w_k, kpe, nh, scale, qhi, qlo, pos_a, state, g_w0=None, g_b0=None, b_o=None, r0=None, q_f32=None):
+    """One-launch q_proj + fold (+ positional table, local query rows, r0) of the direct recipe; see include/hicom_hip.h.
+    An fp16 guide writes the folded global rows unsplit into q_f32 (f32 [16, E]) for the fp16 ring kernel."""
     E = w_q.shape[0]
     _check(lib().hicom_query_prep_fwd(_ptr(guide), _ptr(local_q), _ptr(w_q), _ptr(b_q), _ptr(w_k), _ptr(kpe), nh, E,
                                       kpe.shape[1] if kpe is not None else 0, scale, _ptr(qhi), _ptr(qlo), _ptr(pos_a),
                                       pos_a.shape[1] if pos_a is not None else 0, nh, _ptr(g_w0), _ptr(g_b0), _ptr(b_o),
-                                      g_w0.shape[0] if g_w0 is not None else 0, _ptr(r0), _ptr(state), _stream()), "hicom_query_prep_fwd")
+                                      g_w0.shape[0] if g_w0 is not None else 0, _ptr(r0), _ptr(state), _dt(guide), _ptr(q_f32), _stream()),
+           "hicom_query_prep_fwd")
 
 
 def merge_vproj(part_m, part_l, part_acc, rows, w_v, po, out_ml=None, out_ctx=None):

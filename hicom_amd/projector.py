@@ -638,15 +638,16 @@ class GlobalCompressor(_TrackedWeights, nn.Module):
                 self._cache_gen += 1
         return hit[0]
 
-    def pos_planes(self, t_cap: int, H: int, W: int, device):
-        """bf16 hi / lo planes of the pe table (the fused kernel multiplies them on matrix cores), cached with it."""
+    def pos_planes(self, t_cap: int, H: int, W: int, device, dtype=torch.bfloat16):
+        """bf16 (or fp16: the fused kernel's fp16 instantiation) hi / lo planes of the pe table (the fused kernel multiplies them on
+        matrix cores), cached with it."""
         pe, cap = self.pos_tables(t_cap, H, W, device)
-        key = ("planes", H, W, cap, str(device))
+        key = ("planes", H, W, cap, str(device)) + (() if dtype == torch.bfloat16 else (str(dtype),))
         hit = self._pe_cache.get(key)
         if hit is None or hit[2] != pe.data_ptr():
-            hi = torch.empty(pe.shape, dtype=torch.bfloat16, device=device)
+            hi = torch.empty(pe.shape, dtype=dtype, device=device)
             lo = torch.empty_like(hi)
-            nv.split_bf16(pe, pe.shape[0], hi, lo)
+            nv.split16(pe, pe.shape[0], hi, lo)
             hit = (hi, lo, pe.data_ptr())
             self._pe_cache[key] = hit
             self._cache_gen += 1
@@ -935,11 +936,14 @@ class HIComProjector(nn.Module):
 
     def _forward_half(self, frames_feature, frames_embed, guide_embed, modal, image_newline, local_logits):
         """An fp16 projector with fp16 inputs -- the reference's inference default (`--dtype float16`,
-        inference_video_mcqa_videomme.py:323; `load_mm_projector` casts the loaded weights to fp16, projector.py:53).  The kernels
-        compute on bf16 tokens and weights, so the call runs on a bf16 TWIN of this module: its weights are cast once per weight state
-        (a checkpoint trained in bf16 and loaded as fp16 converts back exactly; a genuinely fp16-trained weight is rounded to 8
-        significand bits), the inputs are cast per call by hicom_cast16_fwd (fp16 activations are ROUNDED to bf16: 2^-9 relative -- the
-        price of this width, stated here rather than hidden), the result is cast back to fp16.  Inference only."""
+        inference_video_mcqa_videomme.py:323; `load_mm_projector` casts the loaded weights to fp16, projector.py:53).  The call runs on
+        a bf16 TWIN of this module: its weights are cast once per weight state (a checkpoint trained in bf16 and loaded as fp16 converts
+        back exactly; a genuinely fp16-trained weight is rounded to 8 significand bits).
+        Release recipe (dense input, fp16 frames_feature / frames_embed, fp16 or no guide / newline, a plan the executor fuses): the fp16
+        tokens go straight into the fp16 instantiation of the fused stream kernel -- no cast, no rounding of the tokens, the output written
+        in fp16 (or f32 under return_fp32) from the fp32 accumulators.  Every other call casts its inputs to bf16 by hicom_cast16_fwd (fp16
+        activations are ROUNDED to bf16: 2^-9 relative -- the price of this width, stated here rather than hidden) and the result back to
+        fp16.  Inference only."""
         import copy
         from . import engine
         if local_logits is not None:
@@ -965,6 +969,23 @@ class HIComProjector(nn.Module):
                 mod.return_fp32 = getattr(self, "return_fp32", False)
             twin = (mod, sig)
             self.__dict__["_bf16_twin"] = twin
+
+        def f16_or_none(t):
+            return t is None or (isinstance(t, torch.Tensor) and t.dtype == torch.float16 and t.is_cuda)
+        if (isinstance(frames_feature, torch.Tensor) and isinstance(frames_embed, torch.Tensor) and f16_or_none(frames_feature)
+                and f16_or_none(frames_embed) and f16_or_none(guide_embed) and f16_or_none(image_newline) and twin[0].use_executor):
+            mod = twin[0]
+            out_dtype = torch.float32 if mod.return_fp32 else torch.float16
+            key = (tuple(frames_feature.shape), tuple(frames_embed.shape), None if guide_embed is None else tuple(guide_embed.shape), modal,
+                   None if image_newline is None else tuple(image_newline.shape), out_dtype)
+            refused = mod.__dict__.setdefault("_f16_refused", set())      # (calls whose plan is not the fused step: decided once)
+            if key not in refused and mod._executor_covers():
+                try:
+                    with torch.no_grad():
+                        nv.begin_inference()
+                        return engine.run_dense(mod, frames_feature, frames_embed, guide_embed, modal, image_newline, out_dtype, tok16=True)
+                except NotImplementedError:                  # (engine.Fp16NotFused, or a recipe the executor refuses: the cast path below)
+                    refused.add(key)
 
         def down(t):
             if t is None:

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HICOM_ABI_VERSION 15
+#define HICOM_ABI_VERSION 16
 
 #define HICOM_OK         0
 #define HICOM_EINVAL    -1   /* bad argument (shape, alignment, NULL)        */
@@ -203,17 +203,25 @@ int hicom_fold_query_split_fwd(const float* qp, const void* w_k, const float* kp
  * calls with ONE problem shape (words 0-1 arrival counter, word 2 failed hand-offs, word 3 grid size of the first launch,
  * then the granules; the kernel maintains it).  A hand-off that fails -- a bounded spin that gave up, or a launch whose grid
  * differs from the first one on this block -- writes NaN into qt_hi / qt_lo / pos_a (every output token then is NaN) and
- * counts in word 2: a missed hand-off never passes for a result. */
+ * counts in word 2: a missed hand-off never passes for a result.
+ * ABI 16, fp16 tokens: g_dt = HICOM_DT_F16 takes an fp16 guide and local_q (local_q is copied into qt_hi bit for bit: the local query
+ * rows then are exact fp16 operands), and qt_f32 (f32 [16, E], 16-byte aligned) receives the folded global query rows UNSPLIT: the
+ * fp16 instantiation of the ring kernel splits them itself at a power-of-two scale per row (hicom_fused_stream_fwd's q_f32); qt_hi /
+ * qt_lo rows < nh are then not written.  g_dt = HICOM_DT_BF16: as before, qt_f32 ignored (may be NULL). */
 int64_t hicom_query_prep_state_bytes(int32_t E);
 int hicom_query_prep_fwd(const void* guide, const void* local_q, const void* w_q, const void* b_q, const void* w_k, const float* kpe,
                          int32_t nh, int32_t E, int32_t P, float scale, void* qt_hi, void* qt_lo, float* pos_a,
                          int32_t pos_stride, int32_t rows, const void* g_w0, const void* g_b0, const void* b_o,
-                         int32_t hidden, float* r0, void* state, void* stream);
+                         int32_t hidden, float* r0, void* state, int32_t g_dt, float* qt_f32, void* stream);
 
 /* Split f32 rows into bf16 hi + lo parts (x ~= hi + lo to 2^-16), zero-padding the row count
  * to rows_pad: the MFMA operand format for fp32 intermediates (SURVEY.md §7 strategy B). */
 int hicom_split_bf16_fwd(const float* x, int32_t rows, int32_t rows_pad, int32_t E,
                          void* hi, void* lo, void* stream);
+/* ABI 16: the same split into hi + lo of a 16-bit type, dt = HICOM_DT_BF16 (= hicom_split_bf16_fwd) or HICOM_DT_F16 (fp16 planes, for the
+ * fp16 instantiation of hicom_fused_stream_fwd: |x - hi - lo| <= 2^-23 |x| + 2^-25, i.e. 2^-20 of a row whose max |x| is >= 2^-3 --
+ * the pe table's rows, sinusoids whose max is near 1) */
+int hicom_split16_fwd(const float* x, int32_t rows, int32_t rows_pad, int32_t E, int32_t dt, void* hi, void* lo, void* stream);
 
 /* ---- global compressor: streaming multi-query attention over all tokens -------------------
  * One pass over x = frames_feature[n0 : n0+N) (bf16 [N,E], E = 1152 | 768) computing, for a
@@ -319,7 +327,11 @@ int hicom_global_stream_nparts(int64_t N, int32_t rows_pad);
  *                 into the partial contexts; the kernel writes the t / y / x MARGINALS of every partial's softmax weights instead,
  *                 normalised like part_ctx_f16 (marginal / l), fp16 [nparts][rows][marg_slots] in absolute slot order
  *                 [T frames | H grid rows | W grid columns | zeros], marg_slots >= T + H + W and a multiple of 8 -- for the merge role
- *                 of hicom_readout16_gemm_role_fwd (hicom_r16_role.part_marg), which multiplies the merged marginals by v_proj . pe^T */
+ *                 of hicom_readout16_gemm_role_fwd (hicom_r16_role.part_marg), which multiplies the merged marginals by v_proj . pe^T
+ *   tok_dt (ABI 16): HICOM_DT_BF16, or HICOM_DT_F16: ff / fe, pe_hi / pe_lo (fp16 planes: hicom_split16_fwd) and the local query rows of
+ *                 q_hi are fp16, and the folded global queries come as f32 rows q_f32 [16, E] (hicom_query_prep_fwd's qt_f32; q_hi / q_lo rows
+ *                 < rows are then ignored) which the kernel splits into its fp16 operand per row at a power-of-two scale.  fp16 tokens take
+ *                 the two-tensor form only (local_logits NULL, part_marg_f16 NULL); HICOM_EUNSUP otherwise */
 int hicom_fused_stream_fwd(const void* ff, const void* fe, const float* local_logits, int32_t T, int32_t H, int32_t W, int32_t E,
                            int32_t kt, int32_t ks, const void* q_hi, const void* q_lo, int32_t rows,
                            float l_scale, float l_bias, const float* pos_a, int32_t pos_stride,
@@ -327,7 +339,7 @@ int hicom_fused_stream_fwd(const void* ff, const void* fe, const float* local_lo
                            int32_t t_index0, int32_t y_index0, int32_t x_index0,
                            float* part_m, float* part_l, float* part_acc, int32_t nparts, float* ctx_local,
                            void* ctx_hi, void* ctx_lo, void* ctx_f16, void* zero_ptr, int64_t zero_bytes, void* part_ctx_f16,
-                           void* part_marg_f16, int32_t marg_slots, void* stream);
+                           void* part_marg_f16, int32_t marg_slots, int32_t tok_dt, const float* q_f32, void* stream);
 int hicom_fused_stream_nparts(int32_t n_windows);
 
 /* ---- merge the partials (+ the value-side positional term) --------------------------------
@@ -489,8 +501,9 @@ int hicom_merge_vproj_sets_fwd(const float* sets, int64_t set_stride, int32_t ns
 int hicom_to_f16_fwd(const void* src, int32_t src_dt, void* dst, int64_t n, void* stream);
 /* ABI 15: contiguous 16-bit <-> 16-bit cast, fp16 -> bf16 (round to nearest even) or bf16 -> fp16 (saturating); 16-byte aligned tensors.
  * The boundary's fp16 width: the reference's inference default is fp16 (inference_video_mcqa_videomme.py:323, model/__init__.py:44,
- * projector.py:53 `load_mm_projector` casts to fp16) -- an fp16 projector runs on the bf16 kernels through casts of its inputs and of its
- * result (hicom_amd/projector.py: HIComProjector._forward_half). */
+ * projector.py:53 `load_mm_projector` casts to fp16).  The release recipe takes fp16 tokens natively (hicom_compressor_args.tok_dt,
+ * ABI 16: no cast, fp16 output from the fp32 accumulators); every other path of an fp16 projector still runs on the bf16 kernels through
+ * casts of its inputs and of its result (hicom_amd/projector.py: HIComProjector._forward_half). */
 int hicom_cast16_fwd(const void* src, int32_t src_dt, void* dst, int32_t dst_dt, int64_t n, void* stream);
 int hicom_to_f16_padded_fwd(const void* src, int32_t src_dt, int64_t rows, int64_t cols, void* dst, int64_t ld_dst, void* stream);
 
@@ -755,7 +768,8 @@ typedef struct hicom_compressor_args {
     float* r0_buf;
     /* dtype of gq (HICOM_DT_BF16 = 0, the learnable queries / the guide, or HICOM_DT_F32: queries a guide injector produced on the
      * caller's side -- coarse / fine injection, projector.py:369-397 -- handed in as f32 rows; with lq f32 [windows, E] the same way).
-     * The release-recipe paths (query_prep kernel, fused stream kernel) take bf16 queries only. */
+     * The release-recipe paths (query_prep kernel, fused stream kernel) take bf16 queries, or -- ABI 16, tok_dt = HICOM_DT_F16 -- the
+     * fp16 guide (HICOM_DT_F16, with lq_dt = HICOM_DT_F16). */
     int32_t gq_dt;
     /* optional hipEvent_t: the main stream waits for it in front of the local stage's first launch -- the caller produces lq (injected
      * per-window queries) on a stream of its own, beside the global stage's stream kernel, and records this event behind it */
@@ -801,6 +815,11 @@ typedef struct hicom_compressor_args {
     const void* ag_send2;
     void* ag_recv2;
     int64_t ag_bytes2;
+    /* ABI 16: dtype of ff / fe, HICOM_DT_BF16 (0) or HICOM_DT_F16.  fp16 tokens run on the release recipe's single-stream form only
+     * (hicom_compressor_is_fused reports it: fused stream kernel in its fp16 instantiation, an fp16 guide -- lq_dt = gq_dt = HICOM_DT_F16
+     * -- or a bf16 one, output in out_dt = HICOM_DT_F16 / F32 / BF16 from the fp32 accumulators); every other path given fp16 tokens
+     * returns HICOM_EUNSUP and never reads them as bf16. */
+    int32_t tok_dt;
 } hicom_compressor_args;
 
 /* Byte offset, inside the workspace, of the fp16 plane [windows, E] of the local stage's window contexts (the A operand of readout
@@ -817,7 +836,7 @@ int hicom_compressor_takes_shard4(const hicom_compressor_args* args);
  * state blocks: out[0] = query prep, out[1] = the GEMV chain.  Synchronous (two 4-byte device reads on `stream` + a stream sync):
  * for tests, benches and debug checks, not for the hot loop. */
 int hicom_compressor_handoff_failures(const hicom_compressor_args* args, int32_t* out, void* stream);
-/* 1 when hicom_compressor_fwd takes the release-recipe (single streaming kernel) path for these arguments. */
+/* 1 when hicom_compressor_fwd takes the release-recipe (single streaming kernel) path for these arguments (fp16 tokens included). */
 int hicom_compressor_is_fused(const hicom_compressor_args* args);
 
 int64_t hicom_compressor_workspace_bytes(const hicom_compressor_args* args);
