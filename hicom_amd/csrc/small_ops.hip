@@ -355,8 +355,9 @@ __global__ __launch_bounds__(256) void split_f16_kernel(const float* x, int rows
     const long r = i / E;
     _Float16 h = (_Float16)0.f, l = (_Float16)0.f;
     if (r < rows) {
-        h = (_Float16)x[i];
-        l = (_Float16)(x[i] - (float)h);
+        // saturating like every other fp16 conversion of the library: an unclamped |x| > 65504 gave hi = +inf, lo = -inf (NaN downstream)
+        h = (_Float16)fminf(fmaxf(x[i], -65504.f), 65504.f);
+        l = (_Float16)fminf(fmaxf(x[i] - (float)h, -65504.f), 65504.f);
     }
     hi[i] = h;
     lo[i] = l;
@@ -475,11 +476,13 @@ __global__ __launch_bounds__(320) void global_dx_kernel(const float* S, const fl
     __shared__ float coef[64][2 * RMAX];
     const int tid = threadIdx.x;
     const long n0 = (long)blockIdx.x * 64;
-    for (int idx = tid; idx < 64 * rows; idx += blockDim.x) {
+    // every coefficient the unrolled loop below reads is written here: rows >= `rows` as zeros (stale LDS holding Inf / NaN would
+    // otherwise meet the zeroed wq / wd and give NaN)
+    for (int idx = tid; idx < 64 * RMAX; idx += blockDim.x) {
         const int r = idx / 64, t = idx - r * 64;
         const long n = n0 + t;
         float a = 0.f, b = 0.f;
-        if (n < N) {
+        if (r < rows && n < N) {
             a = dS[(long)r * stride + n];
             b = expf(S[(long)r * stride + n] - ml[2 * r]) / ml[2 * r + 1];
         }

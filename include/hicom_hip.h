@@ -220,7 +220,8 @@ int hicom_split_bf16_fwd(const float* x, int32_t rows, int32_t rows_pad, int32_t
                          void* hi, void* lo, void* stream);
 /* ABI 16: the same split into hi + lo of a 16-bit type, dt = HICOM_DT_BF16 (= hicom_split_bf16_fwd) or HICOM_DT_F16 (fp16 planes, for the
  * fp16 instantiation of hicom_fused_stream_fwd: |x - hi - lo| <= 2^-23 |x| + 2^-25, i.e. 2^-20 of a row whose max |x| is >= 2^-3 --
- * the pe table's rows, sinusoids whose max is near 1) */
+ * the pe table's rows, sinusoids whose max is near 1; the fp16 planes saturate: |x| > 65504 gives hi = +-65504 and lo = the saturating
+ * fp16 of x - hi, never Inf) */
 int hicom_split16_fwd(const float* x, int32_t rows, int32_t rows_pad, int32_t E, int32_t dt, void* hi, void* lo, void* stream);
 
 /* ---- global compressor: streaming multi-query attention over all tokens -------------------

@@ -1,0 +1,222 @@
+"""Plain float64 restatements of the small operators declared in include/hicom_hip.h (torch on the CPU; no call into hicom_amd).
+
+Shared by tests/test_gpu_ops_small.py (the kernels against these) and tests/test_ops_references.py (these against float64 autograd
+and the oracle, so that a wrong reference cannot bless a wrong kernel).  Every function takes the values the kernel received,
+up-cast: `up(t)` of the bf16 / fp16 / f32 tensor that was uploaded.  Functions that feed a tolerance also return the same
+expression evaluated on absolute values (the sum of |terms| an fp32 summation error is proportional to)."""
+import math
+
+import torch
+
+EPS23 = 2.0 ** -23          # one unit in the last place of an fp32 value in [1, 2)
+
+
+def up(t):
+    return t.detach().cpu().double()
+
+
+def sum_tol(k, abs_sum):
+    """fp32 error bound of a k-term sum / FMA chain in any order: k * 2^-23 * sum |terms| (first order; Higham 4.4)."""
+    return k * EPS23 * abs_sum
+
+
+# ---- d frames_feature of the global stage -----------------------------------------------------------------------------------
+def global_dx_ref(S, dS, ml, qt, dctx, N, dx0=None):
+    """dx[n, :] (+)= sum_r dS[r, n] qt[r, :] + exp(S[r, n] - M_r) / L_r dctx[r, :];  S, dS [rows, >= N], ml [rows, 2].
+    Returns (dx, abs_terms, p) with p = exp(S - M) / L."""
+    rows = qt.shape[0]
+    S, dS = S[:rows, :N], dS[:rows, :N]
+    p = torch.exp(S - ml[:, 0:1]) / ml[:, 1:2]
+    dx = dS.t() @ qt + p.t() @ dctx
+    ab = dS.abs().t() @ qt.abs() + p.t() @ dctx.abs()
+    if dx0 is not None:
+        dx, ab = dx + dx0, ab + dx0.abs()
+    return dx, ab, p
+
+
+def global_attention_backward_ref(qt, x, g):
+    """Folded global attention f = sum_r ctx_r . g_r, ctx_r = sum_n softmax_n(qt_r . x_n) x_n: the tensors its backward leaves
+    (S, ml, dS as hicom_global_stream_bwd defines them: dS = p (dP - delta), dP = g_r . x_n, delta_r = g_r . ctx_r)."""
+    S = qt @ x.t()
+    M = S.max(1).values
+    L = torch.exp(S - M[:, None]).sum(1)
+    p = torch.exp(S - M[:, None]) / L[:, None]
+    dP = g @ x.t()
+    delta = (p * dP).sum(1)
+    dS = p * (dP - delta[:, None])
+    return S, torch.stack([M, L], 1), dS, delta
+
+
+# ---- clip-scale global stage ------------------------------------------------------------------------------------------------
+def clip_query_prep_ref(qp, b_k, nh, scale):
+    """qhat = qp / ||qp||_2 over E;  c[q * nh + h] = scale * sum_j qhat[q, h hd + j] b_k[h hd + j]  (0 without b_k)."""
+    nq, E = qp.shape
+    qhat = qp / qp.norm(dim=1, keepdim=True)
+    if b_k is None:
+        z = torch.zeros(nq * nh, dtype=torch.float64)
+        return qhat, z, z.clone()
+    prod = (qhat * b_k[None, :]).reshape(nq, nh, E // nh)
+    return qhat, scale * prod.sum(-1).reshape(-1), abs(scale) * prod.abs().sum(-1).reshape(-1)
+
+
+def fold_query_ref(qp, w_k, nh, scale):
+    """qt[q nh + h, c] = scale sum_j w_k[h hd + j, c] qp[q, h hd + j]."""
+    nq, E = qp.shape
+    hd = E // nh
+    return scale * torch.einsum("qhj,hjc->qhc", qp.reshape(nq, nh, hd), w_k.reshape(nh, hd, E)).reshape(nq * nh, E)
+
+
+def inv_norm_ref(ssq):
+    return 1.0 / torch.sqrt(ssq.sum(0))
+
+
+def token_axes(N, H, W):
+    n = torch.arange(N)
+    return n // (H * W), (n // W) % H, n % W
+
+
+def clip_attention_ref(q, x, inv, row_const, pos_a=None, pe=None, H=1, W=1, t0i=0, y0i=0, x0i=0):
+    """logit[r, n] = (q_r . x_n + pos_a[r, t0i + t] + pos_a[r, y0i + y] + pos_a[r, x0i + x] + row_const[r]) * inv[n];
+    ctx_r = sum_n softmax_n(logit[r, :]) (x_n + pe[t0i + t] + pe[y0i + y] + pe[x0i + x]).
+    Returns (logit, ctx, abs terms of logit, sum_n p (|x_n| + |pe rows|): the value-side terms are summed separately)."""
+    N = x.shape[0]
+    dot, ab = q @ x.t(), q.abs() @ x.abs().t()
+    val = vabs = x
+    if pos_a is not None:
+        t, y, xx = token_axes(N, H, W)
+        pos = pos_a[:, t0i + t] + pos_a[:, y0i + y] + pos_a[:, x0i + xx]
+        dot, ab = dot + pos, ab + pos_a[:, t0i + t].abs() + pos_a[:, y0i + y].abs() + pos_a[:, x0i + xx].abs()
+        val = x + pe[t0i + t] + pe[y0i + y] + pe[x0i + xx]
+        vabs = x.abs() + pe[t0i + t].abs() + pe[y0i + y].abs() + pe[x0i + xx].abs()
+    S = (dot + row_const[:, None]) * inv[None, :]
+    ab = (ab + row_const.abs()[:, None]) * inv[None, :]
+    p = torch.softmax(S, dim=1)
+    return S, p @ val, ab, p @ vabs.abs()
+
+
+# ---- row operators over the token stream ------------------------------------------------------------------------------------
+def l2norm_ref(x):
+    return x / x.norm(dim=1, keepdim=True)
+
+
+def layer_norm_stats(y, eps):
+    mu = y.mean(-1, keepdim=True)
+    var = ((y - mu) ** 2).mean(-1, keepdim=True)
+    return mu, 1.0 / torch.sqrt(var + eps)
+
+
+def ln_blend_ref(x, gamma, beta, src=None, alpha=1.0, eps=1e-6):
+    """(1 - alpha) src + alpha (LayerNorm_eps(x) gamma + beta); also the same with every term's absolute value."""
+    mu, rstd = layer_norm_stats(x, eps)
+    ln = (x - mu) * rstd * gamma + beta
+    ab = (x.abs() + mu.abs()) * rstd * gamma.abs() + beta.abs()
+    if src is None:
+        return ln, ab
+    return (1 - alpha) * src + alpha * ln, abs(1 - alpha) * src.abs() + abs(alpha) * ab
+
+
+def ln_fp32_tol(x, gamma, beta, eps):
+    """fp32 error bound of LayerNorm_eps(x) gamma + beta computed with E-term fp32 sums, from the reference's own quantities:
+      mean:  |d mu| <= E 2^-23 mean|x|                                   (E-term sum)
+      var:   relative error of var + eps <= (2 |d mu| mean|x - mu| + E 2^-23 var) / (var + eps); rstd takes half of it, + 2^-22
+             for the square root and the division
+      value: |d mu| rstd |gamma| + |x - mu| rstd |gamma| rel(rstd) + 4 roundings of the final expression."""
+    E = x.shape[-1]
+    mu, rstd = layer_norm_stats(x, eps)
+    d = x - mu
+    var = (d * d).mean(-1, keepdim=True)
+    dmu = E * EPS23 * x.abs().mean(-1, keepdim=True)
+    rel = 0.5 * (2 * dmu * d.abs().mean(-1, keepdim=True) + E * EPS23 * var) / (var + eps) + 2.0 ** -22
+    ab = (x.abs() + mu.abs()) * rstd * gamma.abs() + beta.abs()
+    return dmu * rstd * gamma.abs() + d.abs() * rstd * gamma.abs() * rel + 4 * EPS23 * ab
+
+
+def small_mha_ref(q, k, v, nh, scale):
+    M, E = q.shape
+    hd = E // nh
+    qh, kh, vh = (t.reshape(-1, nh, hd).permute(1, 0, 2) for t in (q, k, v))
+    S = qh @ kh.transpose(1, 2) * scale
+    p = torch.softmax(S, dim=-1)
+    out = (p @ vh).permute(1, 0, 2).reshape(M, E)
+    ab = (p @ vh.abs()).permute(1, 0, 2).reshape(M, E)
+    sab = (qh.abs() @ kh.abs().transpose(1, 2) * abs(scale))        # [nh, M, L]
+    return out, ab, sab
+
+
+# ---- window attention with the adaptor blends: backward ---------------------------------------------------------------------
+def window_of_token(T, H, W, kt, ks):
+    """Window index of every token of an exact (kt, ks, ks) partition, window order (t1, h1, w1) row-major."""
+    assert T % kt == 0 and H % ks == 0 and W % ks == 0
+    t, y, x = token_axes(T * H * W, H, W)
+    return ((t // kt) * (H // ks) + y // ks) * (W // ks) + x // ks
+
+
+def blend_rows(x, y, gamma, beta, alpha, eps):
+    """K_n = (1 - a) x_n + a (gamma yhat_n + beta); returns (K, yhat).  y None: K = x."""
+    if y is None:
+        return x, None
+    mu, rstd = layer_norm_stats(y, eps)
+    yhat = (y - mu) * rstd
+    return (1 - alpha) * x + alpha * (yhat * gamma + beta), yhat
+
+
+def adapt_bwd_ref(kx, ky, kg, kb, ak, vx, vy, vg, vb, av, win, nw, q, scale, bias, dctx, eps=1e-6):
+    """The six outputs of hicom_local_attn_adapt_bwd in closed form.  kx, vx [N, D]; ky, vy [N, D] or None; win [N] window of
+    each token; q [nw, D] (a shared query repeated); dctx [nw, D].
+    Returns dict(ds, pw [N]; sxk, syk, sxv, syv [nw, D]) and dict of absolute-term companions."""
+    N, D = kx.shape
+    K, yk = blend_rows(kx, ky, kg, kb, ak, eps)
+    V, yv = blend_rows(vx, vy, vg, vb, av, eps)
+    s = (K * q[win]).sum(1) * scale + bias
+    dP = (V * dctx[win]).sum(1)
+    ds, pw = torch.empty(N, dtype=torch.float64), torch.empty(N, dtype=torch.float64)
+    for w in range(nw):
+        m = win == w
+        p = torch.softmax(s[m], 0)
+        delta = (p * dP[m]).sum()
+        pw[m] = p
+        ds[m] = scale * p * (dP[m] - delta)
+    out = {"ds": ds, "pw": pw}
+    ab = {"s": (K.abs() * q[win].abs()).sum(1) * abs(scale), "dP": (V.abs() * dctx[win].abs()).sum(1)}
+
+    def wsum(c, rows):
+        o = torch.zeros(nw, D, dtype=torch.float64)
+        o.index_add_(0, win, c[:, None] * rows)
+        return o
+    for name, c, rows in (("sxk", ds, kx), ("syk", ds, yk), ("sxv", pw, vx), ("syv", pw, yv)):
+        if rows is not None:
+            out[name], ab[name] = wsum(c, rows), wsum(c.abs(), rows.abs())
+    return out, ab
+
+
+def adapt_dy_ref(y, gamma, vec_tok, coef, alpha, eps=1e-6):
+    """dy = d/dy of alpha LN(y) gamma for the upstream gradient coef[tok] vec[w(tok)]:  g = alpha coef (vec gamma),
+    dy = rstd (g - mean(g) - yhat mean(g yhat));  r1 = (1 - alpha) coef vec.  vec_tok [N, D] = vec[w(tok)]."""
+    mu, rstd = layer_norm_stats(y, eps)
+    yhat = (y - mu) * rstd
+    g = alpha * coef[:, None] * vec_tok * gamma
+    m1, m2 = g.mean(1, keepdim=True), (g * yhat).mean(1, keepdim=True)
+    dy = rstd * (g - m1 - yhat * m2)
+    ab = rstd * (g.abs() + g.abs().mean(1, keepdim=True) + yhat.abs() * (g * yhat).abs().mean(1, keepdim=True))
+    return dy, (1 - alpha) * coef[:, None] * vec_tok, ab
+
+
+# ---- elementwise ------------------------------------------------------------------------------------------------------------
+def gelu_ref(h):
+    """erf GELU, and |d GELU / d erf| = |h| / 2 (what an error of the device erf is multiplied by)."""
+    return 0.5 * h * (1.0 + torch.erf(h / math.sqrt(2.0))), 0.5 * h.abs()
+
+
+def gelu_grad_ref(h):
+    """Phi(h) + h phi(h); second value: the magnitudes of its two transcendental factors, erf / 2 and h phi(h)."""
+    erf = torch.erf(h / math.sqrt(2.0))
+    hphi = h * torch.exp(-h * h / 2) / math.sqrt(2 * math.pi)
+    return 0.5 * (1 + erf) + hphi, 0.5 * erf.abs() + hphi.abs()
+
+
+def sequential_f32_sum(parts):
+    """s = 0; s += parts[k] for k in slice order, every step rounded to fp32 (parts f32 [nparts, M])."""
+    s = torch.zeros(parts.shape[1], dtype=torch.float32)
+    for k in range(parts.shape[0]):
+        s = s + parts[k]
+    return s
