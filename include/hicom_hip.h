@@ -315,12 +315,13 @@ int hicom_global_stream_nparts(int64_t N, int32_t rows_pad);
  *                 part_acc by the kernel itself (marginals of the weights x pe rows, as extra P.x steps), so the
  *                 partials merge with hicom_global_merge_fwd(pe = NULL).
  *   part_*      : as hicom_global_stream_fwd with rows_pad = 16; nparts from
- *                 hicom_fused_stream_nparts(number of windows)
+ *                 hicom_fused_stream_nparts(number of windows).  Partial p covers the contiguous window-major range
+ *                 [p * wpw, min((p + 1) * wpw, Nw)) with wpw = ceil(Nw / nparts); an nparts that leaves a range empty is refused
  *   ctx_local   : f32 [Nw, E], window order (t1,h1,w1), and/or ctx_hi + ctx_lo: the same contexts as
  *                 bf16 planes (hi + lo) for hicom_planes_gemm_fwd, and/or ctx_f16: one fp16 plane (saturating) for
  *                 hicom_readout16_gemm_fwd; unused outputs NULL
  *   part_ctx_f16: not NULL: instead of part_acc (which may then be NULL) the kernel writes the NORMALISED partial contexts
- *                 acc / l as one fp16 plane [nparts][16][E] (rows < rows), for hicom_merge_vproj_fixed_fwd(part_dt = HICOM_DT_F16):
+ *                 acc / l as one fp16 plane (saturating at +-65504, like ctx_f16) [nparts][16][E] (rows < rows), for hicom_merge_vproj_fixed_fwd(part_dt = HICOM_DT_F16):
  *                 half the bytes of the partial states; the rounding (2^-12 relative per partial) averages over the partials
  *   zero_ptr    : zero_bytes (multiple of 8, 8-byte aligned) of scratch that the kernel clears for the launches behind it on the
  *                 stream (the fixed-point accumulators of hicom_merge_vproj_fixed_fwd), or NULL

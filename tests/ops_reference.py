@@ -220,3 +220,104 @@ def sequential_f32_sum(parts):
     for k in range(parts.shape[0]):
         s = s + parts[k]
     return s
+
+
+# ---- fused local + global stream (hicom_fused_stream_fwd) and its query producer (hicom_query_prep_fwd) -----------------------
+def ring_partitions(NW, nparts):
+    """Partition of every window: the contiguous window-major ranges [p wpw, min((p + 1) wpw, NW)), wpw = ceil(NW / nparts)."""
+    wpw = (NW + nparts - 1) // nparts
+    return torch.arange(NW) // wpw
+
+
+def _seg_max(src, idx, n):
+    """max of src[..., k] over the k with idx[k] == s, for s < n (-inf for an empty segment)."""
+    out = torch.full(src.shape[:-1] + (n,), -math.inf, dtype=src.dtype)
+    return out.scatter_reduce(-1, idx.expand(src.shape), src, "amax")
+
+
+def fused_ring_ref(ff, T, H, W, kt, ks, q_local, l_scale, l_bias, qt, fe=None, llog=None, pos_a=None, pe=None, t0i=0, y0i=0, x0i=0,
+                   nparts=1, win=None, part_of_window=None, value_pe=True, local_p_map=None):
+    """What include/hicom_hip.h promises for hicom_fused_stream_fwd, in float64.  ff (fe) [N, E] in token order (t, y, x);
+    q_local [E]; qt [rows, E] the folded global queries as the kernel received them (hi + lo planes, or the q_f32 rows);
+    llog [N] replaces fe_n . q_local;  pos_a [rows, P], pe [P, E] (hi + lo planes summed) or both None.
+    win / part_of_window (-1: in no partition) / value_pe / local_p_map override the token -> window map, the window -> partition
+    map, the value-side pe rows and the un-normalised local weights: the defects tests/test_ops_references.py plants.
+    Returns a dict; `x_ab` beside `x` is the same expression on absolute values."""
+    N, E = ff.shape
+    rows = qt.shape[0]
+    if win is None:
+        win = window_of_token(T, H, W, kt, ks)
+    NW = (T // kt) * (H // ks) * (W // ks)
+    o = {"win": win, "NW": NW}
+    # local window contexts
+    if llog is not None:
+        d, d_ab = llog, llog.abs()
+    else:
+        d, d_ab = fe @ q_local, fe.abs() @ q_local.abs()
+    s = l_scale * d + l_bias
+    m_w = _seg_max(s, win, NW)
+    e = torch.exp(s - m_w[win])
+    l_w = torch.zeros(NW, dtype=torch.float64).index_add_(0, win, e)
+    ew = e if local_p_map is None else local_p_map(e)
+    o["ctx_local"] = torch.zeros(NW, E, dtype=torch.float64).index_add_(0, win, ew[:, None] * ff) / l_w[:, None]
+    o["ctx_local_ab"] = torch.zeros(NW, E, dtype=torch.float64).index_add_(0, win, e[:, None] * ff.abs()) / l_w[:, None]
+    o["local_s"], o["local_dot_ab"], o["local_m"] = s, d_ab, m_w
+    # global logits
+    S, qx_ab = qt @ ff.t(), qt.abs() @ ff.abs().t()
+    S_ab = qx_ab
+    val, val_ab = ff, ff.abs()
+    t, y, x = token_axes(N, H, W)
+    if pos_a is not None:
+        cols = (t0i + t, y0i + y, x0i + x)
+        for c in cols:
+            S, S_ab = S + pos_a[:, c], S_ab + pos_a[:, c].abs()
+        if value_pe:
+            val = ff + pe[cols[0]] + pe[cols[1]] + pe[cols[2]]
+            val_ab = ff.abs() + pe[cols[0]].abs() + pe[cols[1]].abs() + pe[cols[2]].abs()
+    o["S"], o["S_ab"], o["qx_ab"] = S, S_ab, qx_ab
+    # partitions
+    if part_of_window is None:
+        part_of_window = ring_partitions(NW, nparts)
+    part = part_of_window[win]
+    order = torch.argsort(part, stable=True)
+    counts = torch.bincount(part[part >= 0], minlength=nparts)
+    start = int((part < 0).sum())
+    slots = T + H + W
+    lse = torch.empty(nparts, rows, dtype=torch.float64)
+    ctx = torch.empty(nparts, rows, E, dtype=torch.float64)
+    ctx_ab, marg = torch.empty_like(ctx), torch.zeros(nparts, rows, slots, dtype=torch.float64)
+    tokens = []
+    for p in range(nparts):
+        idx = order[start:start + int(counts[p])]
+        start += int(counts[p])
+        tokens.append(idx)
+        Sp = S[:, idx]
+        M = Sp.max(1, keepdim=True).values
+        ep = torch.exp(Sp - M)
+        L = ep.sum(1, keepdim=True)
+        lse[p] = (M + torch.log(L))[:, 0]
+        ctx[p], ctx_ab[p] = ep @ val[idx] / L, ep @ val_ab[idx] / L
+        for base, ax in ((0, t), (T, y), (T + H, x)):
+            marg[p].index_add_(1, base + ax[idx], ep / L)
+    o["part_tokens"], o["lse"], o["part_ctx"], o["part_ctx_ab"], o["marg"] = tokens, lse, ctx, ctx_ab, marg
+    w = torch.softmax(lse, 0)                                        # weight of every partition in the whole softmax
+    o["merged"], o["merged_ab"] = (w[:, :, None] * ctx).sum(0), (w[:, :, None] * ctx_ab).sum(0)
+    return o
+
+
+def query_prep_ref(guide, w_q, b_q, w_k, kpe, nh, scale, g_w0, g_b0, b_o):
+    """hicom_query_prep_fwd: qp = w_q guide + b_q;  qt[h] = scale w_k[h]^T qp[h];  pos_a[h] = scale kpe[h]^T qp[h] (kpe [E, P] or None);
+    r0 = g_w0 (b_o + guide) + g_b0 (g_w0 None: no r0).  Returns (qt, pos_a, r0) and their absolute terms, the inner qp sum included."""
+    E = w_q.shape[0]
+    hd = E // nh
+    qp, qp_ab = w_q @ guide + b_q, w_q.abs() @ guide.abs() + b_q.abs()
+    qt = scale * torch.einsum("hje,hj->he", w_k.view(nh, hd, E), qp.view(nh, hd))
+    qt_ab = abs(scale) * torch.einsum("hje,hj->he", w_k.abs().view(nh, hd, E), qp_ab.view(nh, hd))
+    pa = pa_ab = r0 = r0_ab = None
+    if kpe is not None:
+        P = kpe.shape[1]
+        pa = scale * torch.einsum("hjp,hj->hp", kpe.view(nh, hd, P), qp.view(nh, hd))
+        pa_ab = abs(scale) * torch.einsum("hjp,hj->hp", kpe.abs().view(nh, hd, P), qp_ab.view(nh, hd))
+    if g_w0 is not None:
+        r0, r0_ab = g_w0 @ (b_o + guide) + g_b0, g_w0.abs() @ (b_o.abs() + guide.abs()) + g_b0.abs()
+    return (qt, pa, r0), (qt_ab, pa_ab, r0_ab)

@@ -157,3 +157,200 @@ def test_window_index_and_sequential_sum():
     assert int(win[(1 * 4 + 3) * 6 + 5]) == (0 * 2 + 1) * 3 + 2 and int(win[(2 * 4 + 0) * 6 + 0]) == 6
     parts = torch.tensor([[1e8], [1.0], [-1e8], [1.0]], dtype=torch.float32)
     assert float(R.sequential_f32_sum(parts)[0]) == 1.0            # (1e8 + 1) rounds to 1e8 in fp32: order is visible
+
+
+# ---- hicom_fused_stream_fwd / hicom_query_prep_fwd: the references of tests/test_gpu_fused_ring.py ---------------------------
+from types import SimpleNamespace
+
+import test_gpu_fused_ring as G                                          # (its inputs, limits and tolerances need no GPU)
+
+
+def _small_ring(seed, rows=3, with_pos=True):
+    T, H, W, kt, ks, E = 4, 4, 6, 2, 2, 24
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    N, P = T * H * W, T + H + W + 5
+    a = dict(ff=rnd(N, E), fe=rnd(N, E), q_local=rnd(E), qt=0.4 * rnd(rows, E), pos_a=rnd(rows, P) if with_pos else None,
+             pe=rnd(P, E) if with_pos else None, t0i=2, y0i=2 + T + 1, x0i=2 + T + 1 + H)
+    return (T, H, W, kt, ks, E), a
+
+
+def _ring(shape, a, nparts, **kw):
+    T, H, W, kt, ks, _ = shape
+    return R.fused_ring_ref(a["ff"], T, H, W, kt, ks, a["q_local"], 0.3, 0.7, a["qt"], fe=a["fe"], pos_a=a["pos_a"], pe=a["pe"], t0i=a["t0i"],
+                            y0i=a["y0i"], x0i=a["x0i"], nparts=nparts, **kw)
+
+
+@pytest.mark.parametrize("nparts", [1, 2, 4, 12])
+def test_fused_ring_reference_against_explicit_loops_and_the_direct_softmax(nparts):
+    shape, a = _small_ring(nparts)
+    T, H, W, kt, ks, E = shape
+    o = _ring(shape, a, nparts)
+    idx = orc.window_token_index(T, H, W, kt, ks)                        # the oracle's windows: [NW, wsz] token ids
+    NW = idx.shape[0]
+    assert o["NW"] == NW
+    pos = lambda n: (a["t0i"] + n // (H * W), a["y0i"] + (n // W) % H, a["x0i"] + n % W)
+    S = torch.empty(a["qt"].shape[0], T * H * W, dtype=torch.float64)
+    val = torch.empty(T * H * W, E, dtype=torch.float64)
+    for n in range(T * H * W):
+        pt, py, px = pos(n)
+        S[:, n] = a["qt"] @ a["ff"][n] + a["pos_a"][:, pt] + a["pos_a"][:, py] + a["pos_a"][:, px]
+        val[n] = a["ff"][n] + a["pe"][pt] + a["pe"][py] + a["pe"][px]
+    assert _maxabs(o["S"], S) <= TOL
+    for w in range(NW):
+        p = torch.softmax(0.3 * (a["fe"][idx[w]] @ a["q_local"]) + 0.7, 0)
+        assert _maxabs(o["ctx_local"][w], p @ a["ff"][idx[w]]) <= TOL
+    wpw = -(-NW // nparts)
+    for p_ in range(nparts):
+        toks = idx[p_ * wpw:min((p_ + 1) * wpw, NW)].reshape(-1)
+        assert sorted(toks.tolist()) == sorted(o["part_tokens"][p_].tolist())
+        assert _maxabs(o["lse"][p_], torch.logsumexp(S[:, toks], 1)) <= TOL
+        pw = torch.softmax(S[:, toks], 1)
+        assert _maxabs(o["part_ctx"][p_], pw @ val[toks]) <= TOL
+        # marginals x pe rows = the positional part of the context
+        pe_sel = torch.cat([a["pe"][a["t0i"]:a["t0i"] + T], a["pe"][a["y0i"]:a["y0i"] + H], a["pe"][a["x0i"]:a["x0i"] + W]])
+        assert _maxabs(o["marg"][p_] @ pe_sel, pw @ (val[toks] - a["ff"][toks])) <= TOL
+        assert _maxabs(o["marg"][p_][:, :T].sum(1), torch.ones(S.shape[0], dtype=torch.float64)) <= TOL
+    assert _maxabs(o["merged"], torch.softmax(S, 1) @ val) <= TOL       # merged over the partitions = the direct softmax over all tokens
+    assert bool((o["merged_ab"] >= o["merged"].abs() - 1e-12).all()) and bool((o["part_ctx_ab"] >= o["part_ctx"].abs() - 1e-12).all())
+    # precomputed logits in place of frames_embed
+    o2 = R.fused_ring_ref(a["ff"], T, H, W, kt, ks, a["q_local"], 0.3, 0.7, a["qt"], llog=a["fe"] @ a["q_local"], nparts=nparts)
+    assert _maxabs(o2["ctx_local"], o["ctx_local"]) <= TOL
+
+
+def test_query_prep_reference_against_the_unfused_chain():
+    g = torch.Generator().manual_seed(4)
+    E, nh, P, hidden = 36, 3, 7, 10
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    guide, wq, bq, wk, kpe, gw0, gb0, bo = rnd(E), rnd(E, E), rnd(E), rnd(E, E), rnd(E, P), rnd(hidden, E), rnd(hidden), rnd(E)
+    (qt, pa, r0), (qt_ab, pa_ab, r0_ab) = R.query_prep_ref(guide, wq, bq, wk, kpe, nh, 0.5, gw0, gb0, bo)
+    qp = (wq @ guide + bq)[None, :]
+    assert _maxabs(qt, R.fold_query_ref(qp, wk, nh, 0.5)) <= TOL
+    hd = E // nh
+    for h in range(nh):
+        assert _maxabs(pa[h], 0.5 * qp[0, h * hd:(h + 1) * hd] @ kpe[h * hd:(h + 1) * hd]) <= TOL
+    assert _maxabs(r0, gw0 @ (bo + guide) + gb0) <= TOL
+    assert bool((qt_ab >= qt.abs() - 1e-12).all()) and bool((pa_ab >= pa.abs() - 1e-12).all()) and bool((r0_ab >= r0.abs() - 1e-12).all())
+
+
+def test_ring_limits_restatement_matches_the_issue_list():
+    """Every listed shape has valid partitions for rows 1 / 9 / 12 except the LDS overflows; nparts = 1 is mostly a frame-span refusal."""
+    assert all(G.valid_nparts(s, r, f) for s in G.SHAPES for r in (1, 2, 9) for f in G.FORMS)
+    assert sum(G.ring_refusal(*s, 9, 1, False) is not None for s in G.SHAPES) >= 6
+    assert not G.valid_nparts((4, 36, 36, 4, 3), 9, "logits") and G.valid_nparts((4, 36, 36, 4, 3), 9, "bf16")
+
+
+# Defect sensitivity: each defect is planted into the reference on input sets of the GPU test; on at least one set it has to differ
+# from the reference by >= 2 x the GPU test's own tolerance (a kernel with the defect then misses the bound by >= 1 x of it whatever
+# its legitimate rounding does).  A non-finite result counts: check() asserts finiteness first.
+_SETS = [(fam, form, shape, rows) for fam in ("plain", "flat", "offsets", "extremes") for form in ("bf16", "f16")
+         for shape, rows in (((8, 6, 6, 4, 3), 9), ((12, 9, 6, 4, 3), 12), ((4, 4, 8, 1, 4), 9))]
+assert all((fam, shape, rows, form) in G.FAMILY_CASES or (fam == "plain" and (shape, rows, form) in G.CASES) for fam, form, shape, rows in _SETS)
+
+
+def _ratio(i, ref, bounds, bad, keys):
+    worst = 0.0
+    for k in keys:
+        r = ((bad[k] - ref[k]).abs() / bounds[k])
+        r = torch.nan_to_num(r, nan=math.inf)
+        worst = max(worst, float(r.max()))
+    return worst
+
+
+def _x_neighbour(i):
+    T, H, W, kt, ks = i.shape
+    win = R.window_of_token(*i.shape).clone()
+    x = torch.arange(T * H * W) % W
+    win[x == ks - 1] += 1                                                # the last column of the first window column goes to its x neighbour
+    return dict(win=win)
+
+
+def _drop_last_window(i, nparts):
+    pw = R.ring_partitions(G.n_windows(*i.shape), nparts).clone()
+    for p in range(nparts):
+        own = torch.nonzero(pw == p)[:, 0]
+        if own.numel() > 1:
+            pw[own[-1]] = -1
+    return dict(part_of_window=pw)
+
+
+def _padded_tables(i):
+    """pos_a / pe with NaN slots behind the last one: a swapped base may look past the table (on the device: whatever lies there)."""
+    pad = max(i.shape[1:3])
+    pe = R.up(i.pe_hi) + R.up(i.pe_lo)
+    nan = lambda r, c: torch.full((r, c), float("nan"), dtype=torch.float64)
+    return dict(pos_a=torch.cat([R.up(i.pos_a[:i.rows]), nan(i.rows, pad)], 1), pe=torch.cat([pe, nan(pad, pe.shape[1])], 0))
+
+
+_LOCAL, _GLOBAL = ("ctx_local",), ("lse", "part_ctx", "merged")
+DEFECTS = {
+    "x_neighbour_column": (lambda i, n: _x_neighbour(i), _LOCAL + _GLOBAL, None),
+    "partition_loses_last_window": (_drop_last_window, _GLOBAL, None),
+    "t_index0_ignored": (lambda i, n: dict(t0i=0), _GLOBAL, None),
+    "y_x_bases_swapped": (lambda i, n: dict(y0i=i.x0i, x0i=i.y0i, **_padded_tables(i)), _GLOBAL, None),
+    "value_pe_omitted": (lambda i, n: dict(value_pe=False), _GLOBAL, None),
+    "pe_lo_dropped": (lambda i, n: dict(pe=R.up(i.pe_hi)), _GLOBAL, "bf16"),
+    "local_weight_lo_dropped": (lambda i, n: dict(local_p_map=lambda e: e.bfloat16().double()), _LOCAL, "bf16"),
+    "global_row_as_local_query": (lambda i, n: dict(q_local_override=0), _LOCAL, None),
+    "fp16_query_without_row_scale": (lambda i, n: dict(qt_override=i.qt.clamp(-65504, 65504).half().double()), _GLOBAL, "f16"),
+}
+
+
+def _defect_reference(i, nparts, over):
+    over = dict(over)
+    j = SimpleNamespace(**vars(i))
+    if "q_local_override" in over:
+        j.q_local = i.qt[over.pop("q_local_override")]
+    if "qt_override" in over:
+        j.qt = over.pop("qt_override")
+    return G.ring_reference(j, nparts, **over)
+
+
+
+def _sweep(name):
+    make, keys, only_form = DEFECTS[name]
+    best = (0.0, None)
+    for fam, form, shape, rows in _SETS:
+        if only_form and form != only_form:
+            continue
+        i = G.ring_inputs(fam, form, shape, rows)
+        for nparts in G.valid_nparts(shape, rows, form):
+            ref = G.ring_reference(i, nparts)
+            b = G.ring_bounds(i, ref)
+            r = _ratio(i, ref, b, _defect_reference(i, nparts, make(i, nparts)), keys)
+            if r > best[0]:
+                best = (r, (fam, form, shape, rows, nparts))
+    print(f"RING_DEFECT {name} ratio={best[0]:.3e} on {best[1]}")
+    return best[0]
+
+
+@pytest.mark.parametrize("name", sorted(DEFECTS))
+def test_ring_defect_exceeds_twice_the_gpu_tolerance(name):
+    assert _sweep(name) >= 2.0
+
+
+def test_ring_defect_ctx_lo_dropped_exceeds_twice_the_plane_tolerance():
+    worst = 0.0
+    for fam, form, shape, rows in _SETS:
+        i = G.ring_inputs(fam, form, shape, rows)
+        ref = G.ring_reference(i, G.n_windows(*shape))
+        tol = G.ring_bounds(i, ref)["ctx_local"] + G.BF16_PLANES * ref["ctx_local"].abs()
+        worst = max(worst, float(((ref["ctx_local"].bfloat16().double() - ref["ctx_local"]).abs() / tol).max()))
+    print(f"RING_DEFECT ctx_lo_dropped ratio={worst:.3e}")
+    assert worst >= 2.0
+
+
+def test_ring_defect_query_lo_plane_dropped_is_reported():
+    """The lo plane of the bf16 global queries (2^-9 of q) against the worst-case 2 E-term fp32 bound on the same logits (2^-11.8 of
+    sum |q||x|): reachable only with coherent inputs (family `coherent`).  Measured ratio: 10.2 with the coherent
+    inputs (printed below), so it is asserted at 2 like the required defects."""
+    best = 0.0
+    for shape, rows in (((8, 6, 6, 4, 3), 9), ((12, 9, 6, 4, 3), 12)):
+        i = G.ring_inputs("coherent", "bf16", shape, rows)
+        for nparts in G.valid_nparts(shape, rows, "bf16"):
+            ref = G.ring_reference(i, nparts)
+            b = G.ring_bounds(i, ref)
+            bad = _defect_reference(i, nparts, dict(qt_override=R.up(i.q_hi[:rows])))
+            best = max(best, _ratio(i, ref, b, bad, _GLOBAL))
+    print(f"RING_DEFECT query_lo_dropped ratio={best:.3e}")
+    assert best >= 2.0
