@@ -1,0 +1,253 @@
+// Row and window scaffold shared by the windowed-attention kernels (local_attn.hip) and the row-wise kernels (rowwise_ops.hip).
+//
+// A token row of D = NV * 384 channels is spread over the 64 lanes of a wave as NV segments of 64 x 6 channels: lane l holds
+// channels 384 s + 6 l .. + 5 of segment s in a float [NV][6] (12 B of bf16 / fp16 per lane and segment: global_load_dwordx3,
+// fully coalesced 768-B runs).  Everything here keeps the element order (s outer, j inner) and one accumulator chain per sum, so a
+// kernel written with these helpers rounds exactly as the loops they replace.
+#pragma once
+#include "common.hpp"
+
+namespace hicom {
+
+struct __attribute__((packed, aligned(4))) Seg12 { uint32_t a, b, c; };
+
+// ---- row loads -----------------------------------------------------------------------------------------------------------------
+template <int NV>
+__device__ __forceinline__ void load_row(const uint16_t* row, int lane, float (&v)[NV][6]) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        const Seg12 g = *reinterpret_cast<const Seg12*>(row + 384 * s + 6 * lane);
+        v[s][0] = bf16lo_to_f32(g.a); v[s][1] = bf16hi_to_f32(g.a);
+        v[s][2] = bf16lo_to_f32(g.b); v[s][3] = bf16hi_to_f32(g.b);
+        v[s][4] = bf16lo_to_f32(g.c); v[s][5] = bf16hi_to_f32(g.c);
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void load_row_f32(const float* row, int lane, float (&v)[NV][6]) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        const Seg12 a = *reinterpret_cast<const Seg12*>(row + 384 * s + 6 * lane);
+        const Seg12 b = *reinterpret_cast<const Seg12*>(row + 384 * s + 6 * lane + 3);
+        v[s][0] = __uint_as_float(a.a); v[s][1] = __uint_as_float(a.b); v[s][2] = __uint_as_float(a.c);
+        v[s][3] = __uint_as_float(b.a); v[s][4] = __uint_as_float(b.b); v[s][5] = __uint_as_float(b.c);
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void load_row_f16(const _Float16* row, int lane, float (&v)[NV][6]) {
+    typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        const Seg12 g = *reinterpret_cast<const Seg12*>(row + 384 * s + 6 * lane);
+        const half2_t a = __builtin_bit_cast(half2_t, g.a), b = __builtin_bit_cast(half2_t, g.b), c = __builtin_bit_cast(half2_t, g.c);
+        v[s][0] = (float)a[0]; v[s][1] = (float)a[1]; v[s][2] = (float)b[0]; v[s][3] = (float)b[1]; v[s][4] = (float)c[0]; v[s][5] = (float)c[1];
+    }
+}
+
+// stream dtype code: 0 = bf16 (raw tokens), 1 = fp32, 2 = fp16 (alpha-blended adaptor outputs)
+template <int NV>
+__device__ __forceinline__ void load_stream_row(const void* base, int dt, long token, int lane, float (&v)[NV][6]) {
+    constexpr int D = NV * 384;
+    if (dt == 1) load_row_f32<NV>(reinterpret_cast<const float*>(base) + token * D, lane, v);
+    else if (dt == 2) load_row_f16<NV>(reinterpret_cast<const _Float16*>(base) + token * D, lane, v);
+    else load_row<NV>(reinterpret_cast<const uint16_t*>(base) + token * D, lane, v);
+}
+
+// query fragment of this lane (fp32): row `win` of a bf16 or f32 [Nw | 1, D] matrix (stride 0: one shared query)
+template <int NV>
+__device__ __forceinline__ void load_query(const void* query, int query_f32, long query_stride, int win, int lane, float (&q)[NV][6]) {
+    if (query_f32) {
+        const float* qp = reinterpret_cast<const float*>(query) + (long)win * query_stride;
+#pragma unroll
+        for (int s = 0; s < NV; ++s)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) q[s][j] = qp[384 * s + 6 * lane + j];
+    } else {
+        load_row<NV>(reinterpret_cast<const uint16_t*>(query) + (long)win * query_stride, lane, q);
+    }
+}
+
+__device__ __forceinline__ float read_alpha(const void* a, int is_f32) {
+    return is_f32 ? *reinterpret_cast<const float*>(a) : bf16_to_f32(*reinterpret_cast<const uint16_t*>(a));
+}
+
+// ---- bf16 row segments: six floats of a lane <-> the 12 bytes it stores --------------------------------------------------------------
+__device__ __forceinline__ void seg12_accum(float (&e)[6], const Seg12 w) {
+    e[0] += bf16lo_to_f32(w.a); e[1] += bf16hi_to_f32(w.a); e[2] += bf16lo_to_f32(w.b); e[3] += bf16hi_to_f32(w.b);
+    e[4] += bf16lo_to_f32(w.c); e[5] += bf16hi_to_f32(w.c);
+}
+__device__ __forceinline__ void seg12_add(float (&e)[6], const uint16_t* o) { seg12_accum(e, *reinterpret_cast<const Seg12*>(o)); }
+
+// rounds and stores one segment; returns the words as stored (a caller that sums what it wrote sums the ROUNDED values)
+__device__ __forceinline__ Seg12 store_seg12(uint16_t* o, const float (&e)[6]) {
+    Seg12 w;
+    w.a = f32_to_bf16(e[0]) | ((uint32_t)f32_to_bf16(e[1]) << 16);
+    w.b = f32_to_bf16(e[2]) | ((uint32_t)f32_to_bf16(e[3]) << 16);
+    w.c = f32_to_bf16(e[4]) | ((uint32_t)f32_to_bf16(e[5]) << 16);
+    *reinterpret_cast<Seg12*>(o) = w;
+    return w;
+}
+
+// this lane's part of a bf16 row from elem(s, j); accumulate: added to what the row holds (read-modify-write)
+template <int NV, class F>
+__device__ __forceinline__ void store_row_bf16(uint16_t* row, int lane, bool accumulate, F&& elem) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        float e[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) e[j] = elem(s, j);
+        if (accumulate) seg12_add(e, row + 384 * s + 6 * lane);
+        store_seg12(row + 384 * s + 6 * lane, e);
+    }
+}
+
+// ---- row primitives over a lane's float [NV][6] (per-lane partials: the caller reduces over the wave) -----------------------------------
+template <int NV>
+__device__ __forceinline__ void row_zero(float (&a)[NV][6]) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) a[s][j] = 0.f;
+}
+
+template <int NV>
+__device__ __forceinline__ float row_dot(const float (&a)[NV][6], const float (&b)[NV][6]) {
+    float d = 0.f;
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) d = fmaf(a[s][j], b[s][j], d);
+    return d;
+}
+
+template <int NV>
+__device__ __forceinline__ float row_sum(const float (&a)[NV][6]) {
+    float t = 0.f;
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) t += a[s][j];
+    return t;
+}
+
+// acc = fmaf(w, x, acc)
+template <int NV>
+__device__ __forceinline__ void row_axpy(float w, const float (&x)[NV][6], float (&acc)[NV][6]) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) acc[s][j] = fmaf(w, x[s][j], acc[s][j]);
+}
+
+template <int NV>
+__device__ __forceinline__ void row_mul(const float (&a)[NV][6], const float (&b)[NV][6], float (&out)[NV][6]) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) out[s][j] = a[s][j] * b[s][j];
+}
+
+// LayerNorm statistics of a row in registers (two passes, fp32); every lane gets both
+template <int NV>
+__device__ __forceinline__ void ln_stats(const float (&y)[NV][6], float eps, float& mu, float& rstd) {
+    constexpr int D = NV * 384;
+    mu = wave_sum_fast(row_sum<NV>(y)) * (1.0f / D);
+    float s2 = 0.f;
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) { const float d = y[s][j] - mu; s2 = fmaf(d, d, s2); }
+    rstd = 1.0f / sqrtf(wave_sum_fast(s2) * (1.0f / D) + eps);
+}
+
+// what a vector v needs to meet a LayerNorm-affine row without forming it:  vg = v gamma,  cg = sum(v gamma),  cb = v . beta
+template <int NV>
+__device__ __forceinline__ void affine_prep(const float (&v)[NV][6], const uint16_t* gamma, const uint16_t* beta, int lane, float (&vg)[NV][6],
+                                            float& cg, float& cb) {
+    float g[NV][6], b[NV][6];
+    load_row<NV>(gamma, lane, g);
+    load_row<NV>(beta, lane, b);
+    row_mul<NV>(v, g, vg);
+    cg = wave_sum_fast(row_sum<NV>(vg));
+    cb = wave_sum_fast(row_dot<NV>(v, b));
+}
+
+// v . ((1 - a) x + a (gamma yhat + beta)) for one token of an adaptor-blended stream, yhat = LN(y), from the x row, the y row and
+// affine_prep(v):  (1 - a) v.x + a (rstd (vg.y - mu cg) + cb).  Leaves the LayerNorm statistics of y.  has_y false: the plain v.x.
+template <int NV>
+__device__ __forceinline__ float blend_dot(const float (&x)[NV][6], const float (&y)[NV][6], bool has_y, const float (&v)[NV][6],
+                                          const float (&vg)[NV][6], float cg, float cb, float a, float eps, float& mu, float& rstd) {
+    const float dx = wave_sum_fast(row_dot<NV>(v, x));
+    if (!has_y) return dx;
+    const float dy = wave_sum_fast(row_dot<NV>(vg, y));
+    ln_stats<NV>(y, eps, mu, rstd);
+    return (1.0f - a) * dx + a * (rstd * (dy - mu * cg) + cb);
+}
+
+// ---- one window of the [T, H, W] token grid --------------------------------------------------------------------------------------
+// Window `win` (t-major over at.nwin x ay.nwin x ax.nwin) starts at (t0, y0, x0) and holds WIN = kt * ks2 tokens, t-major too.
+struct WindowGeom {
+    int t1, h1, w1, t0, y0, x0, kx, ks2, WIN, H, W;
+    __device__ __forceinline__ WindowGeom(const hicom_axis& at, const hicom_axis& ay, const hicom_axis& ax, int win) {
+        w1 = win % ax.nwin;
+        h1 = (win / ax.nwin) % ay.nwin;
+        t1 = win / (ax.nwin * ay.nwin);
+        t0 = axis_start(at, t1); y0 = axis_start(ay, h1); x0 = axis_start(ax, w1);
+        kx = ax.k;
+        ks2 = ay.k * ax.k;
+        WIN = at.k * ks2;
+        H = ay.n; W = ax.n;
+    }
+    // i-th token of the window -> token index
+    __device__ __forceinline__ long token_of(int i) const {
+        const int t2 = i / ks2, r = i - t2 * ks2;
+        const int h2 = r / kx, w2 = r - h2 * kx;
+        return ((long)(t0 + t2) * H + (y0 + h2)) * W + (x0 + w2);
+    }
+    // the inverse, for an EXACT partition (every token in one window): token index -> window
+    __device__ __forceinline__ static long window_of(const hicom_axis& at, const hicom_axis& ay, const hicom_axis& ax, long tok) {
+        const int H = ay.n, W = ax.n;
+        const int t = (int)(tok / ((long)H * W)), rem = (int)(tok - (long)t * H * W), yy = rem / W, xx = rem - yy * W;
+        return ((long)(t / at.k) * ay.nwin + yy / ay.k) * ax.nwin + xx / ax.k;
+    }
+};
+
+// softmax statistics over the window's scores in LDS (every wave redundantly; WIN is tiny).  With dp (the backward):
+// also delta = sum_i p_i dp_i.
+__device__ __forceinline__ void softmax_stats(const float* sc, int WIN, int lane, float& mx, float& inv_sum, const float* dp = nullptr,
+                                              float* delta = nullptr) {
+    mx = -3.0e38f;
+    for (int i = lane; i < WIN; i += 64) mx = fmaxf(mx, sc[i]);
+    mx = wave_max_fast(mx);
+    float sum = 0.f, pd = 0.f;
+    for (int i = lane; i < WIN; i += 64) {
+        const float e = expf(sc[i] - mx);
+        sum += e;
+        if (dp) pd = fmaf(e, dp[i], pd);
+    }
+    inv_sum = 1.0f / wave_sum_fast(sum);
+    if (dp) *delta = wave_sum_fast(pd) * inv_sum;
+}
+
+// ---- the four waves' partial rows through a [4][D] slab of LDS -------------------------------------------------------------------------
+template <int NV>
+__device__ __forceinline__ void store_partial_row(float* part, int wave, int lane, const float (&a)[NV][6]) {
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) part[wave * (NV * 384) + 384 * s + 6 * lane + j] = a[s][j];
+}
+
+// after a barrier: emit(c, sum of the four rows at column c), the columns strided over the workgroup
+template <int NV, class F>
+__device__ __forceinline__ void sum_partial_rows(const float* part, int tid, F&& emit) {
+    constexpr int D = NV * 384;
+    for (int c = tid; c < D; c += 256) emit(c, (part[c] + part[D + c]) + (part[2 * D + c] + part[3 * D + c]));
+}
+template <int NV>
+__device__ __forceinline__ void sum_partial_rows(const float* part, int tid, float* out) {
+    sum_partial_rows<NV>(part, tid, [&](int c, float v) { out[c] = v; });
+}
+
+}  // namespace hicom

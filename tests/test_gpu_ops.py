@@ -55,6 +55,31 @@ def test_local_attn_matches_oracle(T, H, W, kt, ks, shared_query):
     assert maxabs(ctx, want.reshape(nw, D)) <= 2e-5          # fp32 accumulation-order noise only
 
 
+@pytest.mark.parametrize("Dm", [768, 1152])
+def test_local_attn_fp16_stream_and_ctx_f16(Dm):
+    """The executor's form of the forward: fp16 value stream, fp32 and fp16 contexts from one launch, at both widths.  Windows overlap
+    on every axis and hold 18 tokens (no multiple of the 12 or 8 a workgroup takes per pass)."""
+    T, H, W, kt, ks = 3, 7, 5, 2, 3
+    x = synth.synth_inputs(T, H, W, Dm, tag="loc16")
+    key, value, g = bf(x["fe"]), torch.from_numpy(x["ff"]).half().cuda(), bf(x["g"])
+    at, ay, ax = geo.axis_tiling(T, kt), geo.axis_tiling(H, ks), geo.axis_tiling(W, ks)
+    axes = tuple(nv.Axis(a.n, a.k, a.nwin, a.nfull) for a in (at, ay, ax))
+    nw = at.nwin * ay.nwin * ax.nwin
+    ctx, ctx16 = f32((nw, Dm)), torch.empty((nw, Dm), dtype=torch.float16, device="cuda")
+    nv.local_attn(key, value, axes, g, 0, 1 / math.sqrt(Dm), 0.0, 0, ctx, ctx16)
+    torch.cuda.synchronize()
+    # fp64 window attention over the same 16-bit values (widened exactly)
+    idx = orc.window_token_index(T, H, W, kt, ks)
+    assert idx.shape == (nw, 18)
+    k64, v64 = key.cpu().double().reshape(-1, Dm)[idx], value.cpu().double().reshape(-1, Dm)[idx]
+    p = torch.softmax((k64 @ g.cpu().double()) / math.sqrt(Dm), dim=1)
+    want = (p.unsqueeze(-1) * v64).sum(dim=1)
+    err = float((ctx.cpu().double() - want).abs().max())
+    print(f"local_attn fp16 stream D={Dm}: max |ctx - fp64| = {err:.3e}")
+    assert err <= 2e-5          # fp32 accumulation-order noise only, as in test_local_attn_matches_oracle
+    assert torch.equal(ctx16, ctx.clamp(-65504, 65504).half())          # both stored from one fp32 value
+
+
 def test_local_attn_clip_scale_and_uniform():
     T, H, W = 4, 6, 6
     x = synth.synth_inputs(T, H, W, D, tag="clip")
