@@ -40,6 +40,7 @@ EXPORTS = (
     "hicom_act_rows_fwd", "hicom_act_bwd_rows_fwd", "hicom_readout16_gemm_role_fwd", "hicom_r16_chain_state_bytes", "hicom_dense16_gemm_pair_fwd", "hicom_gemv_chain_fwd",
     "hicom_merge_vproj_sets_fwd", "hicom_readout_tail_fwd", "hicom_readout_tail_state_bytes",
     "hicom_compressor_ctx16_offset",
+    "hicom_compressor_batch_fwd", "hicom_compressor_batch_workspace_bytes",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -134,6 +135,28 @@ class CompressorArgs(C.Structure):
         ("ag_fn", C.c_void_p), ("ag_comm", C.c_void_p), ("ag_send", C.c_void_p), ("ag_recv", C.c_void_p), ("ag_bytes", C.c_int64),
         ("ag_group_start", C.c_void_p), ("ag_group_end", C.c_void_p), ("ag_send2", C.c_void_p), ("ag_recv2", C.c_void_p), ("ag_bytes2", C.c_int64),
         ("tok_dt", C.c_int32),
+    ]
+
+
+class CompressorBatchArgs(C.Structure):
+    """hicom_compressor_batch_args (include/hicom_hip.h) -- field order and types must match the header."""
+    _fields_ = [
+        ("ff", C.c_void_p), ("fe", C.c_void_p), ("guide", C.c_void_p),
+        ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("E", C.c_int32), ("hidden", C.c_int32),
+        ("kt", C.c_int32), ("ks", C.c_int32), ("nh", C.c_int32), ("P", C.c_int32),
+        ("l_scale", C.c_float), ("chunks", C.c_int32),
+        ("lw0_f16", C.c_void_p), ("lb0", C.c_void_p), ("lw2_f16", C.c_void_p), ("lb2", C.c_void_p),
+        ("wq", C.c_void_p), ("bq", C.c_void_p), ("wk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p),
+        ("wo", C.c_void_p), ("bo", C.c_void_p),
+        ("gw0", C.c_void_p), ("gb0", C.c_void_p), ("gw2", C.c_void_p), ("gb2", C.c_void_p),
+        ("pe", C.c_void_p), ("kpe", C.c_void_p),
+        ("t_index0", C.c_int32), ("y_index0", C.c_int32), ("x_index0", C.c_int32), ("out_dt", C.c_int32),
+        ("out", C.c_void_p),
+        ("ldo", C.c_int64), ("item_rows", C.c_int64), ("global_row0", C.c_int64),
+        ("n_global_rows", C.c_int32), ("nl_group", C.c_int32), ("nl_count", C.c_int32), ("reserved_", C.c_int32),
+        ("nl_first", C.c_int64), ("nl_step", C.c_int64),
+        ("newline", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("stream", C.c_void_p),
     ]
 
 
@@ -238,6 +261,8 @@ def lib() -> C.CDLL:
     L.hicom_compressor_takes_shard4.argtypes = [ap]
     L.hicom_compressor_handoff_failures.argtypes = [ap, C.POINTER(C.c_int32), vp]
     L.hicom_compressor_fwd.argtypes = [ap]
+    L.hicom_compressor_batch_fwd.argtypes = [C.POINTER(CompressorBatchArgs)]
+    L.hicom_compressor_batch_workspace_bytes.argtypes = [C.POINTER(CompressorBatchArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -246,6 +271,7 @@ def lib() -> C.CDLL:
         getattr(L, name).restype = C.c_int
     L.hicom_compressor_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_zero_prefix_bytes.restype = C.c_int64
+    L.hicom_compressor_batch_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -568,6 +594,20 @@ def compressor_workspace(args: CompressorArgs):
 
 def compressor_fwd(args: CompressorArgs):
     _check(lib().hicom_compressor_fwd(C.byref(args)), "hicom_compressor_fwd")
+
+
+def compressor_batch_workspace(args: CompressorBatchArgs) -> int:
+    n = lib().hicom_compressor_batch_workspace_bytes(C.byref(args))
+    if n < 0:
+        msg = lib().hicom_last_error().decode(errors="replace")
+        if n == -2:                      # HICOM_EUNSUP: a limit of the batched kernels
+            raise NotImplementedError(f"forward_batch: {msg}")
+        raise HicomNativeError(f"hicom_compressor_batch_workspace_bytes failed ({n}): {msg}")
+    return n
+
+
+def compressor_batch_fwd(args: CompressorBatchArgs):
+    _check(lib().hicom_compressor_batch_fwd(C.byref(args)), "hicom_compressor_batch_fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

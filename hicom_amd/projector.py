@@ -512,11 +512,11 @@ class LocalCompressor(_TrackedWeights, nn.Module):
         return out.view(*grid, -1)
 
 
-def _refuse_grad(module: nn.Module):
+def _refuse_grad(module: nn.Module, what: str = None):
     """The stage modules have no autograd graph of their own (HIComProjector.forward has: hicom_amd/autograd.py).
     Returning a detached tensor to a training loop would silently freeze the projector, so refuse instead."""
     if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
-        raise RuntimeError(f"{type(module).__name__}.forward builds no autograd graph: call it under torch.no_grad(), or "
+        raise RuntimeError(f"{what or type(module).__name__ + '.forward'} builds no autograd graph: call it under torch.no_grad(), or "
                            "go through HIComProjector.forward, which does")
     nv.begin_inference()
 
@@ -818,6 +818,7 @@ class HIComProjector(nn.Module):
         self.__dict__["_engine_params_gen"] = self.__dict__.get("_engine_params_gen", 0) + 1
         self.__dict__.pop("_engine_plans", None)
         self.__dict__.pop("_shard_plans", None)
+        self.__dict__.pop("_batch_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1056,6 +1057,17 @@ class HIComProjector(nn.Module):
         from . import engine
         return engine.run_dense(self, frames_feature, frames_embed, guide_embed, modal, image_newline, _out_dtype(self),
                                 deferred=True)
+
+    def forward_batch(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None):
+        """B items of ONE shape in one native call: frames_feature / frames_embed bf16 [B, T, H, W, E] (what `frames_features.split(...)`
+        of reference hicom_arch.py:164 yields for a uniform batch, viewed 5-D: no copy), guide_embeds bf16 [B, E], one instruction per
+        item.  Returns [B, rows_per_item, hidden]; row b is laid out as forward(frames_feature[b], frames_embed[b], guide_embeds[b], modal,
+        image_newline) and equals it to the kernels' rounding.  The launch count does not depend on B (csrc/batch.hip).
+        Release recipe only (local + global compressor, use_guide="direct", no adaptors, no clip scale, bf16 module, exact window
+        partition): everything else raises NotImplementedError.  Inference only: with autograd on and trainable parameters it raises.
+        `chunks`: workgroups per item of the segmented global stream (None: chosen so that B x chunks fills the chip)."""
+        from . import batch
+        return batch.run_batch(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
 
     def forward_stepwise(self, frames_feature, frames_embed, guide_embed, modal, image_newline=None):
         """Same result, one C-ABI call per operator (anyres dict inputs; also the cross-check of the

@@ -845,6 +845,49 @@ int64_t hicom_compressor_workspace_bytes(const hicom_compressor_args* args);
 int64_t hicom_compressor_zero_prefix_bytes(const hicom_compressor_args* args);
 int hicom_compressor_fwd(const hicom_compressor_args* args);
 
+/* ---- batched compressor step: B items of ONE shape in one call --------------------------------------------------------
+ * What hicom/model/hicom_arch.py:166-178 does with one projector call per item of a batch (all items of equal length), for the
+ * release recipe only (local + global compressor, use_guide = "direct", no adaptors, no clip-scale, bf16): twelve launches on
+ * `stream` whatever B is.  Item b of the output equals hicom_compressor_fwd on item b alone (same math; the window
+ * contexts and the hidden layer of the local readout pass through fp16 planes as there).
+ *   ff, fe   : bf16 [B, T, H, W, E] (fe NULL: the local keys are ff); guide bf16 [B, E], one instruction per item
+ *   kt, ks   : local window (kt = 1 for images); T % kt == H % ks == W % ks == 0, kt ks ks <= 64; E == 1152, nh <= 16 heads,
+ *              hidden % 64 == 0; HICOM_EUNSUP otherwise
+ *   pe, kpe  : the tables of hicom_compressor_args, both NULL = no pos-emb; the frame index of the positional terms restarts at
+ *              t_index0 for every item
+ *   chunks   : workgroups per item of the segmented global stream, 0 = chosen so that B x chunks fills the chip (one per item
+ *              once B alone does).  A workgroup streams tokens of ONE item; the (m, l, ACC) states of an item's chunks are merged
+ *              per item, a tail tile is masked
+ *   out      : [B, item_rows, ldo] of out_dt (bf16 | f32), item_rows = global_row0 + n_global_rows.  Rows [0, global_row0) of an
+ *              item: its local tokens, one newline gap after every nl_group of them (0: none), the newline token (bf16) in rows
+ *              nl_first + i nl_step, i < nl_count; rows from global_row0: n_global_rows identical copies of its global token
+ *   ws       : hicom_compressor_batch_workspace_bytes(args) bytes (depends on the shape, B and chunks), 256-byte aligned, nothing
+ *              to zero; not shared between concurrently running calls */
+typedef struct hicom_compressor_batch_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t B, T, H, W, E, hidden, kt, ks, nh, P;
+    float l_scale;
+    int32_t chunks;
+    const void *lw0_f16, *lb0, *lw2_f16, *lb2;      /* local readout: fp16 copies of the weights, bf16 biases */
+    const void *wq, *bq, *wk, *wv, *bv, *wo, *bo;   /* global attention, bf16 */
+    const void *gw0, *gb0, *gw2, *gb2;              /* global readout, bf16 */
+    const float* pe;
+    const float* kpe;
+    int32_t t_index0, y_index0, x_index0, out_dt;
+    void* out;
+    int64_t ldo, item_rows, global_row0;
+    int32_t n_global_rows, nl_group, nl_count, reserved_;
+    int64_t nl_first, nl_step;
+    const void* newline;
+    void* ws;
+    int64_t ws_bytes;
+    void* stream;
+} hicom_compressor_batch_args;
+int64_t hicom_compressor_batch_workspace_bytes(const hicom_compressor_batch_args* args);
+int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* args);
+
 #ifdef __cplusplus
 }
 #endif
