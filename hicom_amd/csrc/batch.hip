@@ -15,12 +15,12 @@
 //     readout layers as one GEMM pair over all B x windows_per_item contexts (hicom_readout16_gemm_fwd), and ONE placement launch
 //     that writes every item's packed rows: local tokens around the newline gaps, newline rows, the 32 copies of the global row.
 // Twelve launches for any B.  Everything on the caller's stream, nothing synchronises the host.
-#include "window_rows.hpp"
+#include "segment_item.hpp"
 
 namespace hicom {
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Local stage: one wave per window of the stacked grid, the item's guide row as the query.  WIN <= 64: lane i keeps logit i.
+// Local stage: one wave per window of the stacked grid, the item's guide row as the query (segment_item.hpp: local_window_ctx16).
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <int NV>
 __global__ __launch_bounds__(256) void batch_local_attn_kernel(const uint16_t* key, const uint16_t* value, const uint16_t* guide,
@@ -31,343 +31,63 @@ __global__ __launch_bounds__(256) void batch_local_attn_kernel(const uint16_t* k
     const int win = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (win >= nwin) return;
     const WindowGeom g(at, ay, ax, win);
-    float q[NV][6];
-    load_row<NV>(guide + (long)(win / wpi) * D, lane, q);
-    float sc = -3.0e38f;
-    for (int i = 0; i < g.WIN; ++i) {
-        float k[NV][6];
-        load_row<NV>(key + g.token_of(i) * D, lane, k);
-        const float d = wave_sum_fast(row_dot<NV>(q, k)) * scale;
-        if (lane == i) sc = d;
-    }
-    const float mx = wave_max_fast(sc);
-    const float e = lane < g.WIN ? expf(sc - mx) : 0.f;
-    const float pw = e / wave_sum_fast(e);
-    float acc[NV][6];
-    row_zero<NV>(acc);
-    for (int i = 0; i < g.WIN; ++i) {
-        float v[NV][6];
-        load_row<NV>(value + g.token_of(i) * D, lane, v);
-        row_axpy<NV>(__shfl(pw, i, 64), v, acc);
-    }
-    _Float16* o = ctx16 + (long)win * D;
-#pragma unroll
-    for (int s = 0; s < NV; ++s)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) o[384 * s + 6 * lane + j] = (_Float16)fminf(fmaxf(acc[s][j], -65504.f), 65504.f);
+    local_window_ctx16<NV>(key, value, guide + (long)(win / wpi) * D, g, lane, scale, ctx16 + (long)win * D);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Segmented global stream.  Tile staging, swizzle, MFMA operand layouts and the per-tile order of operations are those of
-// global_stream_kernel (global_stream.hip); see there for the CDNA4 mapping.  grid = (chunks, B).
+// Segmented global stream: grid = (chunks, B), workgroup (part, item) walks chunk `part` of the item's tiles (segment_item.hpp:
+// stream_segment).
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct BatchStreamParams {
+    SegStreamParams c;
     const uint16_t* x;      // [B][N][E]
     int N;                  // tokens per item
     int ntiles;             // 16-token tiles per item
-    const uint16_t* qhi;    // [B * rows][E] folded queries, item-major
-    const uint16_t* qlo;
-    const float* pos_a;     // [B * rows][pos_stride]
-    int pos_stride;
-    int rows;               // folded rows per item (heads), <= 16
-    int H, W, HW;
-    int t0i, y0i, x0i;
     float* scores;          // [B][16][score_stride]
     long score_stride;
-    float* part_m;          // [B][chunks][16]
-    float* part_l;
-    float* part_acc;        // [B][chunks][16][E]
 };
-
-__device__ __forceinline__ int bswz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ int bsig(int g) { return ((g & 1) << 1) | (g >> 1); }
 
 template <int NB>
 __global__ __launch_bounds__(256, 2) void batch_global_stream_kernel(BatchStreamParams p) {
     constexpr int E = NB * 128;
-    constexpr int SLICE = E / 4;
-    constexpr int KSTEPS = SLICE / 32;
-    constexpr int CBLK = SLICE / 16;
-    constexpr int TILE_BYTES = NB * 4096;
-    constexpr int PIECES = NB * 4;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* tilebuf = smem;                                           // [2][TILE_BYTES]
-    float* red = reinterpret_cast<float*>(smem + 2 * TILE_BYTES);  // [4 waves][16 rows][16 tokens]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, kg = lane >> 4;
     const int part = blockIdx.x, item = blockIdx.y, nparts = gridDim.x;
     const int tb = (int)(((long)p.ntiles * part) / nparts);
     const int te = (int)(((long)p.ntiles * (part + 1)) / nparts);
-    const bool row_ok = r16 < p.rows;
-    const long qrow = (long)item * p.rows + r16;
-    const uint16_t* xi = p.x + (long)item * p.N * E;                // this item's tokens: nothing below indexes past them
-
-    // ---- A operand: the item's folded queries (rows >= p.rows: zero), this wave's channel slice ----
-    bf16x8 ahi[KSTEPS], alo[KSTEPS];
-    {
-        const long off = qrow * E + SLICE * wave + 8 * kg;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            ahi[s] = row_ok ? *reinterpret_cast<const bf16x8*>(p.qhi + off + 32 * s) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            alo[s] = row_ok ? *reinterpret_cast<const bf16x8*>(p.qlo + off + 32 * s) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    }
-
-    f32x4 acc[CBLK];
-#pragma unroll
-    for (int cb = 0; cb < CBLK; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -1.0e30f, l_run = 0.f;
-
-    auto stage = [&](int tile, int buf) {
-        const int r = lane >> 4, cpos = lane & 15;
-        static_assert(PIECES % 4 == 0, "pieces are dealt round-robin to the 4 waves");
-#pragma unroll
-        for (int i = 0; i < PIECES / 4; ++i) {
-            const int pi = wave + 4 * i;
-            const int blk = pi >> 2, row = 4 * (pi & 3) + r;
-            int tok = tile * 16 + row;
-            tok = tok < p.N ? tok : p.N - 1;   // tail tile: the item's own last token again (masked below), never a neighbour's
-            const char* src = reinterpret_cast<const char*>(xi) + (long)tok * (E * 2) + blk * 256 + 16 * (cpos ^ bswz(row));
-            char* dst = tilebuf + buf * TILE_BYTES + pi * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),
-                                             (__attribute__((address_space(3))) void*)(dst), 16, 0, 0);
-        }
-    };
-
-    const int q4 = (lane >> 2) & 3, pp = lane & 3;
-    const int trow = 4 * bsig(kg) + q4;
-    const int rd_row_off = r16 * 256, rd_swz = bswz(r16);
-    const int tr_row_off = trow * 256 + 8 * (pp & 1), tr_swz = bswz(trow);
-    const float* pa = (p.pos_a && row_ok) ? p.pos_a + qrow * p.pos_stride : nullptr;
-
-    // positional logit terms, one tile ahead (see global_stream_kernel); the token index is item-local: t restarts at 0 per item
-    float pt[4] = {0.f, 0.f, 0.f, 0.f}, py[4] = {0.f, 0.f, 0.f, 0.f}, px[4] = {0.f, 0.f, 0.f, 0.f};
-    auto fetch_pos = [&](int tile) {
-        if (pa) {
-            const int nb = tile * 16 + 4 * bsig(kg);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int n = nb + j;
-                n = n < p.N ? n : p.N - 1;
-                const unsigned un = (unsigned)n;
-                const unsigned t = un / (unsigned)p.HW, rem = un - t * (unsigned)p.HW;
-                const unsigned y = rem / (unsigned)p.W, xx = rem - y * (unsigned)p.W;
-                pt[j] = pa[p.t0i + t];
-                py[j] = pa[p.y0i + y];
-                px[j] = pa[p.x0i + xx];
-            }
-        }
-    };
-
-    if (tb < te) {
-        fetch_pos(tb);
-        stage(tb, 0);
-    }
-
-    for (int tile = tb; tile < te; ++tile) {
-        const int cur = (tile - tb) & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        float padd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) padd[j] = pt[j] + py[j] + px[j];
-        if (tile + 1 < te) {
-            fetch_pos(tile + 1);
-            stage(tile + 1, cur ^ 1);
-        }
-        const char* img = tilebuf + cur * TILE_BYTES;
-
-        f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const int ch0 = SLICE * wave + 32 * s;
-            const int blk = ch0 >> 7, cbase = (ch0 & 127) >> 3;
-            const bf16x8 b = *reinterpret_cast<const bf16x8*>(img + blk * 4096 + rd_row_off + 16 * ((cbase + kg) ^ rd_swz));
-            s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[s], b, s4, 0, 0, 0);
-            s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[s], b, s4, 0, 0, 0);
-        }
-        float* rw = red + wave * 256;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rw[(4 * kg + j) * 16 + r16] = s4[j];
-        lds_barrier();
-
-        const float* rb = red + r16 * 16 + 4 * bsig(kg);
-        f32x4 lg = *reinterpret_cast<const f32x4*>(rb);
-        lg += *reinterpret_cast<const f32x4*>(rb + 256);
-        lg += *reinterpret_cast<const f32x4*>(rb + 512);
-        lg += *reinterpret_cast<const f32x4*>(rb + 768);
-        const int n0 = tile * 16 + 4 * bsig(kg);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) lg[j] += padd[j];
-        if (wave == 0 && row_ok) *reinterpret_cast<f32x4*>(p.scores + ((long)item * 16 + r16) * p.score_stride + n0) = lg;
-
-        float tmax = -1.0e30f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tmax = (n0 + j < p.N) ? fmaxf(tmax, lg[j]) : tmax;
-        tmax = xrow4_max(tmax);
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = expf(m_run - m_new);
-        float pr[4], lsum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            pr[j] = (n0 + j < p.N) ? expf(lg[j] - m_new) : 0.f;
-            lsum += pr[j];
-        }
-        lsum = xrow4_sum(lsum);
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-        if (__any(alpha != 1.0f)) {
-            const float a0 = __shfl(alpha, 4 * kg + 0, 64), a1 = __shfl(alpha, 4 * kg + 1, 64);
-            const float a2 = __shfl(alpha, 4 * kg + 2, 64), a3 = __shfl(alpha, 4 * kg + 3, 64);
-#pragma unroll
-            for (int cb = 0; cb < CBLK; ++cb) {
-                acc[cb][0] *= a0; acc[cb][1] *= a1; acc[cb][2] *= a2; acc[cb][3] *= a3;
-            }
-        }
-        bf16x4 phi, plo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint16_t h, l;
-            split_bf16(pr[j], h, l);
-            phi[j] = (short)h;
-            plo[j] = (short)l;
-        }
-#pragma unroll
-        for (int cb = 0; cb < CBLK; ++cb) {
-            const int ch0 = SLICE * wave + 16 * cb;
-            const int blk = ch0 >> 7, c2 = (ch0 & 127) >> 3;
-            const char* a = img + blk * 4096 + tr_row_off + 16 * ((c2 + (pp >> 1)) ^ tr_swz);
-            const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a));
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(phi, b, acc[cb], 0, 0, 0);
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(plo, b, acc[cb], 0, 0, 0);
-        }
-    }
-
-    // ---- this (item, chunk)'s partial state ----
-    const long prow = ((long)item * nparts + part) * 16;
-    if (wave == 0 && kg == 0 && row_ok) {
-        p.part_m[prow + r16] = m_run;
-        p.part_l[prow + r16] = l_run;
-    }
-#pragma unroll
-    for (int cb = 0; cb < CBLK; ++cb) {
-        float* o = p.part_acc + (prow + 4 * kg) * E + SLICE * wave + 16 * cb + r16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (4 * kg + j < p.rows) o[(long)j * E] = acc[cb][j];
-    }
+    stream_segment<NB>(p.c, p.x + (long)item * p.N * E, p.N, tb, te, item, p.scores + (long)item * 16 * p.score_stride, p.score_stride,
+                       (long)item * nparts + part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Merge per (item, head): ctx = sum_p e^(m_p - M) ACC_p / L + sum_s marg[s] pe[s], marg = the row's softmax weights summed over the
-// other two axes (slots [T | H | W]), from the logits of the item.  Fixed summation orders: bit-reproducible.  grid = (rows, B).
+// Merge per (item, head) (segment_item.hpp: merge_segments).  grid = (rows, B).
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct BatchMergeParams {
-    const float* part_m;
-    const float* part_l;
-    const float* part_acc;
+    SegMergeParams c;
     const float* scores;
     long score_stride;
-    const float* pe;        // [P][E]
-    int nparts, rows, E, T, H, W;
-    int t0i, y0i, x0i;
+    int nparts, rows, T;
     float* ctx;             // [B * rows][E]
 };
 
 __global__ __launch_bounds__(256) void batch_merge_kernel(BatchMergeParams p) {
     extern __shared__ float ms[];
-    const int r = blockIdx.x, item = blockIdx.y, tid = threadIdx.x;
-    const int T = p.T, H = p.H, W = p.W;
-    float* rowsum = ms;                 // [T][H]: weights summed over x
-    float* colsum = ms + T * H;         // [T][W]: weights summed over y
-    float* marg = colsum + T * W;       // [T + H + W]
-    const long pbase = (long)item * p.nparts * 16 + r;
-    float M = -1.0e30f;
-    for (int c = 0; c < p.nparts; ++c) M = fmaxf(M, p.part_m[pbase + c * 16]);
-    float L = 0.f;
-    for (int c = 0; c < p.nparts; ++c) L += p.part_l[pbase + c * 16] * expf(p.part_m[pbase + c * 16] - M);
-    const float invL = 1.0f / L;
-    const float* s = p.scores + ((long)item * 16 + r) * p.score_stride;
-    if (p.pe) {
-        for (int i = tid; i < T * H; i += 256) {
-            float a = 0.f;
-            for (int x = 0; x < W; ++x) a += expf(s[(long)i * W + x] - M);
-            rowsum[i] = a;
-        }
-        for (int i = tid; i < T * W; i += 256) {
-            const int t = i / W, x = i - t * W;
-            float a = 0.f;
-            for (int y = 0; y < H; ++y) a += expf(s[((long)t * H + y) * W + x] - M);
-            colsum[i] = a;
-        }
-        __syncthreads();
-        for (int i = tid; i < T + H + W; i += 256) {
-            float a = 0.f;
-            if (i < T) {
-                for (int y = 0; y < H; ++y) a += rowsum[i * H + y];
-            } else if (i < T + H) {
-                for (int t = 0; t < T; ++t) a += rowsum[t * H + (i - T)];
-            } else {
-                for (int t = 0; t < T; ++t) a += colsum[t * W + (i - T - H)];
-            }
-            marg[i] = a * invL;
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < p.E; e += 256) {
-        float v = 0.f;
-        for (int c = 0; c < p.nparts; ++c)
-            v += expf(p.part_m[pbase + c * 16] - M) * p.part_acc[((long)item * p.nparts + c) * 16 * p.E + (long)r * p.E + e];
-        v *= invL;
-        if (p.pe) {
-            float pos = 0.f;
-            for (int t = 0; t < T; ++t) pos = fmaf(marg[t], p.pe[(long)(p.t0i + t) * p.E + e], pos);
-            for (int y = 0; y < H; ++y) pos = fmaf(marg[T + y], p.pe[(long)(p.y0i + y) * p.E + e], pos);
-            for (int x = 0; x < W; ++x) pos = fmaf(marg[T + H + x], p.pe[(long)(p.x0i + x) * p.E + e], pos);
-            v += pos;
-        }
-        p.ctx[((long)item * p.rows + r) * p.E + e] = v;
-    }
+    const int r = blockIdx.x, item = blockIdx.y;
+    merge_segments(p.c, ms, r, threadIdx.x, p.T, p.nparts, (long)item * p.nparts, p.scores + ((long)item * 16 + r) * p.score_stride,
+                   p.ctx + ((long)item * p.rows + r) * p.c.E);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Placement of every item's packed rows (byte work): grid = B * item_rows, one output row per workgroup.
-//   rows >= global_row0: the item's global row (f32, rounded once: the n_global copies are bit-identical);
-//   newline rows nl_first + i nl_step, i < nl_count; every other row: local token m = r - r / (nl_group + 1) of the item.
+// Placement of every item's packed rows (segment_item.hpp: place_row): grid = B * item_rows, one output row per workgroup.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct BatchPlaceParams {
-    const void* loc;        // [B * wpi][hidden], out dtype
-    const float* tok;       // [B][hidden]
-    const uint16_t* newline;// bf16 [hidden] or NULL
-    void* out;
-    int out_f32, hidden, wpi, nl_group, nl_count;
+    SegPlaceParams c;
+    int wpi, nl_group, nl_count;
     long item_rows, global_row0, nl_first, nl_step, ldo;
 };
 
 __global__ __launch_bounds__(128) void batch_place_kernel(BatchPlaceParams p) {
     const long row = blockIdx.x;
     const long item = row / p.item_rows, r = row - item * p.item_rows;
-    const long o = row * p.ldo;
-    const bool is_nl = p.nl_count > 0 && r >= p.nl_first && r < p.global_row0 && (r - p.nl_first) % p.nl_step == 0 &&
-                       (r - p.nl_first) / p.nl_step < p.nl_count;
-    for (int c = threadIdx.x; c < p.hidden; c += 128) {
-        if (r >= p.global_row0) {
-            const float v = p.tok[item * p.hidden + c];
-            if (p.out_f32) reinterpret_cast<float*>(p.out)[o + c] = v;
-            else reinterpret_cast<uint16_t*>(p.out)[o + c] = f32_to_bf16(v);
-        } else if (is_nl) {
-            if (p.out_f32) reinterpret_cast<float*>(p.out)[o + c] = bf16_to_f32(p.newline[c]);
-            else reinterpret_cast<uint16_t*>(p.out)[o + c] = p.newline[c];
-        } else {
-            const long m = p.nl_group ? r - r / (p.nl_group + 1) : r;
-            const long src = (item * p.wpi + m) * p.hidden + c;
-            if (p.out_f32) reinterpret_cast<float*>(p.out)[o + c] = reinterpret_cast<const float*>(p.loc)[src];
-            else reinterpret_cast<uint16_t*>(p.out)[o + c] = reinterpret_cast<const uint16_t*>(p.loc)[src];
-        }
-    }
+    place_row(p.c, r, row * p.ldo, item, item * p.wpi, p.nl_group, p.nl_count, p.global_row0, p.nl_first, p.nl_step);
 }
 
 }  // namespace hicom
@@ -376,24 +96,14 @@ using namespace hicom;
 
 namespace {
 
-constexpr int kBatchMax = 4096;          // items per call (grid y of the segmented kernels, far below the limit)
-constexpr int kBatchMaxChunks = 64;
-
-int batch_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
+constexpr int kBatchMax = hicom_host::kSegMaxItems;
+constexpr int kBatchMaxChunks = hicom_host::kSegMaxChunks;
 
 // workgroups per item of the segmented stream: B x chunks fills the chip twice over (two resident workgroups per CU); one chunk
 // per item once B alone does
 int batch_chunks(const hicom_compressor_batch_args* a) {
     const long ntiles = ((long)a->T * a->H * a->W + 15) / 16;
-    long c = a->chunks > 0 ? a->chunks : (2L * batch_num_cus() + a->B - 1) / a->B;
+    long c = a->chunks > 0 ? a->chunks : (2L * hicom_host::num_cus() + a->B - 1) / a->B;
     if (c > ntiles) c = ntiles;
     if (c > kBatchMaxChunks) c = kBatchMaxChunks;
     return (int)(c < 1 ? 1 : c);
@@ -512,13 +222,13 @@ extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) 
     {
         BatchStreamParams p;
         p.x = (const uint16_t*)a->ff; p.N = N; p.ntiles = (N + 15) / 16;
-        p.qhi = (const uint16_t*)(ws + l.qhi); p.qlo = (const uint16_t*)(ws + l.qlo);
-        p.pos_a = pos_a; p.pos_stride = a->P; p.rows = nh;
-        p.H = a->H; p.W = a->W; p.HW = a->H * a->W;
-        p.t0i = a->t_index0; p.y0i = a->y_index0; p.x0i = a->x_index0;
+        p.c.qhi = (const uint16_t*)(ws + l.qhi); p.c.qlo = (const uint16_t*)(ws + l.qlo);
+        p.c.pos_a = pos_a; p.c.pos_stride = a->P; p.c.rows = nh;
+        p.c.H = a->H; p.c.W = a->W; p.c.HW = a->H * a->W;
+        p.c.t0i = a->t_index0; p.c.y0i = a->y_index0; p.c.x0i = a->x_index0;
         p.scores = (float*)(ws + l.scores); p.score_stride = l.score_stride;
-        p.part_m = (float*)(ws + l.part_m); p.part_l = (float*)(ws + l.part_l); p.part_acc = (float*)(ws + l.part_acc);
-        constexpr int smem = 2 * 9 * 4096 + 4096;
+        p.c.part_m = (float*)(ws + l.part_m); p.c.part_l = (float*)(ws + l.part_l); p.c.part_acc = (float*)(ws + l.part_acc);
+        constexpr int smem = hicom_host::kSegStreamSmem;
         static bool attr_set = false;
         if (!attr_set) {
             hipFuncSetAttribute(reinterpret_cast<const void*>(batch_global_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -532,10 +242,10 @@ extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) 
     // 5: merge per item
     {
         BatchMergeParams p;
-        p.part_m = (const float*)(ws + l.part_m); p.part_l = (const float*)(ws + l.part_l); p.part_acc = (const float*)(ws + l.part_acc);
+        p.c.part_m = (const float*)(ws + l.part_m); p.c.part_l = (const float*)(ws + l.part_l); p.c.part_acc = (const float*)(ws + l.part_acc);
         p.scores = (const float*)(ws + l.scores); p.score_stride = l.score_stride;
-        p.pe = a->pe; p.nparts = l.chunks; p.rows = nh; p.E = E; p.T = a->T; p.H = a->H; p.W = a->W;
-        p.t0i = a->t_index0; p.y0i = a->y_index0; p.x0i = a->x_index0;
+        p.c.pe = a->pe; p.nparts = l.chunks; p.rows = nh; p.c.E = E; p.T = a->T; p.c.H = a->H; p.c.W = a->W;
+        p.c.t0i = a->t_index0; p.c.y0i = a->y_index0; p.c.x0i = a->x_index0;
         p.ctx = ctxg;
         const size_t smem = ((size_t)a->T * a->H + (size_t)a->T * a->W + a->T + a->H + a->W) * 4;
         HICOM_LAUNCH(batch_merge_kernel, dim3((unsigned)nh, (unsigned)B), dim3(256), smem, s, p);
@@ -564,8 +274,8 @@ extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) 
     // 12: every item's packed rows
     {
         BatchPlaceParams p;
-        p.loc = ws + l.loc; p.tok = tok; p.newline = (const uint16_t*)a->newline; p.out = a->out;
-        p.out_f32 = a->out_dt == HICOM_DT_F32; p.hidden = hidden; p.wpi = l.wpi; p.nl_group = a->nl_group; p.nl_count = a->nl_count;
+        p.c.loc = ws + l.loc; p.c.tok = tok; p.c.newline = (const uint16_t*)a->newline; p.c.out = a->out;
+        p.c.out_f32 = a->out_dt == HICOM_DT_F32; p.c.hidden = hidden; p.wpi = l.wpi; p.nl_group = a->nl_group; p.nl_count = a->nl_count;
         p.item_rows = a->item_rows; p.global_row0 = a->global_row0; p.nl_first = a->nl_first; p.nl_step = a->nl_step > 0 ? a->nl_step : 1; p.ldo = a->ldo;
         HICOM_LAUNCH(batch_place_kernel, dim3((unsigned)((long)B * a->item_rows)), dim3(128), 0, s, p);
         st = hicom_host::check_launch("compressor_batch: placement");

@@ -41,6 +41,7 @@ EXPORTS = (
     "hicom_merge_vproj_sets_fwd", "hicom_readout_tail_fwd", "hicom_readout_tail_state_bytes",
     "hicom_compressor_ctx16_offset",
     "hicom_compressor_batch_fwd", "hicom_compressor_batch_workspace_bytes",
+    "hicom_compressor_ragged_fwd", "hicom_compressor_ragged_workspace_bytes", "hicom_compressor_ragged_prepare",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -160,6 +161,33 @@ class CompressorBatchArgs(C.Structure):
     ]
 
 
+class RaggedItem(C.Structure):
+    """hicom_ragged_item (include/hicom_hip.h): one item of a ragged call, plain integers."""
+    _fields_ = [("T", C.c_int32), ("kt", C.c_int32), ("nl_group", C.c_int32), ("nl_count", C.c_int32), ("nl_first", C.c_int32),
+                ("nl_step", C.c_int32), ("n_global_rows", C.c_int32)]
+
+
+class CompressorRaggedArgs(C.Structure):
+    """hicom_compressor_ragged_args (include/hicom_hip.h) -- field order and types must match the header."""
+    _fields_ = [
+        ("ff", C.c_void_p), ("fe", C.c_void_p), ("guide", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("E", C.c_int32), ("hidden", C.c_int32),
+        ("ks", C.c_int32), ("nh", C.c_int32), ("P", C.c_int32),
+        ("l_scale", C.c_float), ("chunks", C.c_int32),
+        ("items", C.POINTER(RaggedItem)),
+        ("lw0_f16", C.c_void_p), ("lb0", C.c_void_p), ("lw2_f16", C.c_void_p), ("lb2", C.c_void_p),
+        ("wq", C.c_void_p), ("bq", C.c_void_p), ("wk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p),
+        ("wo", C.c_void_p), ("bo", C.c_void_p),
+        ("gw0", C.c_void_p), ("gb0", C.c_void_p), ("gw2", C.c_void_p), ("gb2", C.c_void_p),
+        ("pe", C.c_void_p), ("kpe", C.c_void_p),
+        ("t_index0", C.c_int32), ("y_index0", C.c_int32), ("x_index0", C.c_int32), ("out_dt", C.c_int32),
+        ("out", C.c_void_p),
+        ("ldo", C.c_int64),
+        ("newline", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("stream", C.c_void_p),
+    ]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -263,6 +291,9 @@ def lib() -> C.CDLL:
     L.hicom_compressor_fwd.argtypes = [ap]
     L.hicom_compressor_batch_fwd.argtypes = [C.POINTER(CompressorBatchArgs)]
     L.hicom_compressor_batch_workspace_bytes.argtypes = [C.POINTER(CompressorBatchArgs)]
+    L.hicom_compressor_ragged_fwd.argtypes = [C.POINTER(CompressorRaggedArgs)]
+    L.hicom_compressor_ragged_prepare.argtypes = [C.POINTER(CompressorRaggedArgs)]
+    L.hicom_compressor_ragged_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -272,6 +303,7 @@ def lib() -> C.CDLL:
     L.hicom_compressor_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_zero_prefix_bytes.restype = C.c_int64
     L.hicom_compressor_batch_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_ragged_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -608,6 +640,24 @@ def compressor_batch_workspace(args: CompressorBatchArgs) -> int:
 
 def compressor_batch_fwd(args: CompressorBatchArgs):
     _check(lib().hicom_compressor_batch_fwd(C.byref(args)), "hicom_compressor_batch_fwd")
+
+
+def compressor_ragged_workspace(args: CompressorRaggedArgs) -> int:
+    n = lib().hicom_compressor_ragged_workspace_bytes(C.byref(args))
+    if n < 0:
+        msg = lib().hicom_last_error().decode(errors="replace")
+        if n == -2:                      # HICOM_EUNSUP: a limit of the ragged kernels
+            raise NotImplementedError(f"forward_ragged: {msg}")
+        raise HicomNativeError(f"hicom_compressor_ragged_workspace_bytes failed ({n}): {msg}")
+    return int(n)
+
+
+def compressor_ragged_prepare(args: CompressorRaggedArgs):
+    _check(lib().hicom_compressor_ragged_prepare(C.byref(args)), "hicom_compressor_ragged_prepare")
+
+
+def compressor_ragged_fwd(args: CompressorRaggedArgs):
+    _check(lib().hicom_compressor_ragged_fwd(C.byref(args)), "hicom_compressor_ragged_fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -819,6 +819,7 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_engine_plans", None)
         self.__dict__.pop("_shard_plans", None)
         self.__dict__.pop("_batch_plans", None)
+        self.__dict__.pop("_ragged_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1068,6 +1069,23 @@ class HIComProjector(nn.Module):
         `chunks`: workgroups per item of the segmented global stream (None: chosen so that B x chunks fills the chip)."""
         from . import batch
         return batch.run_batch(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
+
+    def forward_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None):
+        """B items of UNEQUAL length and mixed modality in one native call: frames_feature / frames_embed bf16 [sum T_i, H, W, E], the
+        stacked tensor of reference hicom_arch.py:159-164 before `.split` (read in place; frames_embed may be None), guide_embeds bf16
+        [B, E], split_sizes the B frame counts T_i, modals "image" / "video" as one string or one per item.  H and W are common to the
+        call.  Returns the list of the B per-item outputs, views of ONE [sum rows_i, hidden] tensor; item i is laid out as
+        forward(frames_feature[t0_i : t0_i + T_i], frames_embed[...], guide_embeds[i], modals[i], image_newline) -- its own temporal
+        window (1 for images and 1-frame items), its own packing and newline rows, the positional frame index starting at 0 -- and
+        equals it to the kernels' rounding.  The launch count depends neither on B nor on the mix (csrc/ragged.hip).
+        Scope and refusals as forward_batch: release recipe, bf16 module and inputs, no anyres dicts, every item's windows partition
+        its grid exactly (NotImplementedError names the item otherwise), inference only.
+        `chunks`: work units per item of the segmented global stream, each clamped to the item's 16-token tiles (None: every item gets
+        its share of 2 x #CUs units by token count).
+        Not timed yet (tools/ragged_bench.py).  It is the twelve launches of forward_batch, so its ~180 us floor is to
+        be expected here too: one to three small items are probably faster through a loop of forward()."""
+        from . import ragged
+        return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
 
     def forward_stepwise(self, frames_feature, frames_embed, guide_embed, modal, image_newline=None):
         """Same result, one C-ABI call per operator (anyres dict inputs; also the cross-check of the

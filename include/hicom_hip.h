@@ -888,6 +888,55 @@ typedef struct hicom_compressor_batch_args {
 int64_t hicom_compressor_batch_workspace_bytes(const hicom_compressor_batch_args* args);
 int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* args);
 
+/* ---- ragged compressor step: B items of UNEQUAL length and mixed modality in one call ------------------------------
+ * The batch of hicom/model/hicom_arch.py:146-180 as it comes: the vision tower's stacked [sum T_i, H, W, E] tensor (:159-164, before
+ * .split) with single images, clips of any length and 1-frame "videos" side by side, read in place.  Same recipe, same math per item
+ * and the same twelve launches as the batched step above; item i of the output equals hicom_compressor_fwd on item i alone.
+ *   ff, fe   : bf16 [sum T_i, H, W, E] (fe NULL: the local keys are ff); guide bf16 [B, E]
+ *   items    : HOST array of B descriptors.  T frames; kt the item's temporal window (1 for images and 1-frame items), T % kt == 0;
+ *              the item's packed rows as in hicom_compressor_batch_args: a newline gap after every nl_group local tokens (0: none),
+ *              the newline token in rows nl_first + i nl_step, i < nl_count, then n_global_rows copies of its global token.  An item
+ *              has (T / kt)(H / ks)(W / ks) + nl_count + n_global_rows rows; the items' rows follow each other in `out`
+ *   H, W, ks : common to the call, H % ks == W % ks == 0, kt ks ks <= 64; E == 1152, nh <= 16, hidden % 64 == 0
+ *   pe, kpe  : as above; the frame index of the positional terms restarts at t_index0 for every item (the tables hold max T_i frames)
+ *   chunks   : work units per item of the segmented global stream, each clamped to the item's 16-token tiles; 0 = the item's share
+ *              of 2 x #CUs units by its tile count, in [1, 64].  A unit streams tokens of ONE item, tiles counted from the item's
+ *              first token
+ *   out      : [sum rows_i, ldo] of out_dt (bf16 | f32)
+ *   ws       : hicom_compressor_ragged_workspace_bytes(args) bytes, 256-byte aligned.  Its head is a table region (item table, work
+ *              units {item, first tile, last tile, partial-state slot}, window -> item and row -> item lookups) that
+ *              hicom_compressor_ragged_prepare(args) derives on the host and writes ONCE per (items, shape, chunks, ws): it copies to
+ *              the device and synchronises `stream`, so it runs outside the hot loop (and outside a graph capture).
+ * hicom_compressor_ragged_fwd then only launches: no copy, no synchronisation, no allocation, O(B) integer work on the host.  It
+ * trusts the table region: calling it on a workspace that prepare has not filled for the same items is undefined. */
+typedef struct hicom_ragged_item {
+    int32_t T, kt, nl_group, nl_count, nl_first, nl_step, n_global_rows;
+} hicom_ragged_item;
+typedef struct hicom_compressor_ragged_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t B, H, W, E, hidden, ks, nh, P;
+    float l_scale;
+    int32_t chunks;
+    const hicom_ragged_item* items;                 /* HOST memory, B entries */
+    const void *lw0_f16, *lb0, *lw2_f16, *lb2;      /* local readout: fp16 copies of the weights, bf16 biases */
+    const void *wq, *bq, *wk, *wv, *bv, *wo, *bo;   /* global attention, bf16 */
+    const void *gw0, *gb0, *gw2, *gb2;              /* global readout, bf16 */
+    const float* pe;
+    const float* kpe;
+    int32_t t_index0, y_index0, x_index0, out_dt;
+    void* out;
+    int64_t ldo;
+    const void* newline;
+    void* ws;
+    int64_t ws_bytes;
+    void* stream;
+} hicom_compressor_ragged_args;
+int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compressor_ragged_args* args);
+int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_args* args);
+int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* args);
+
 #ifdef __cplusplus
 }
 #endif
