@@ -2,7 +2,9 @@
 
 The reference runs its projector once per item of a batch (hicom_arch.py:166-178).  For single images and short clips an item is a
 few dozen windows and every forward() is launch latency on an idle chip; here a batch of equal-shaped items is ONE C call and twelve
-launches whatever B is.  Release recipe only; everything else raises NotImplementedError.
+launches whatever B is.  The two released recipes only -- `local43_global32` and, with the k / v adaptor MLPs as two more launches
+over all tokens of the call and the LayerNorm blend fused into the local stage's row loads, `local43_adaptkv_global32` (fourteen
+launches); everything else raises NotImplementedError.  The module's recipe alone decides which entry point runs.
 
 Plans (filled argument block + the workspace it owns) are cached on the module by shape, B included, like engine.run_dense's; the
 input / output pointers are patched per call."""
@@ -19,12 +21,55 @@ _MAX_PLANS = 16
 
 
 class _BatchPlan:
-    __slots__ = ("args", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep")
+    __slots__ = ("args", "io", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "adapt_bytes")
 
     def __init__(self, args, ws, rows, hidden, sig):
+        # args: the block the entry point takes; io: the plain block inside it (args itself for the plain recipe), whose input / output
+        # pointers are patched per call; adapt_bytes: the adaptor regions behind the plain workspace layout (0 for the plain recipe)
         self.args, self.ws, self.rows, self.hidden, self.sig = args, ws, rows, hidden, sig
+        self.io = getattr(args, "base", args)
         self.fresh = self.refresh = self.keep = None
-        self.hits = 0
+        self.hits = self.adapt_bytes = 0
+
+
+def seg_recipe(proj):
+    """The recipe of the batched / ragged step a projector runs: "plain" (local43_global32), "adaptkv" (adapt_k and / or adapt_v on the
+    local compressor), or None for everything outside their scope."""
+    lc, gc = proj.local_compressor, proj.global_compressor
+    if (lc is None or gc is None or lc.use_guide != "direct" or gc.use_guide != "direct" or not lc.queries_native or not gc.is_plain
+            or proj.local_use_clip_scale or proj.global_use_clip_scale):
+        return None
+    return "adaptkv" if (lc.adapt_k or lc.adapt_v) else "plain"
+
+
+def adaptor_streams(lc):
+    """(field of the argument block, MLP, LayerNorm, alpha) per adapted stream of the local compressor."""
+    return [s for on, s in ((lc.adapt_k, ("ak", lc.k_proj, lc.k_norm, lc.k_alpha)), (lc.adapt_v, ("av", lc.v_proj, lc.v_norm, lc.v_alpha))) if on]
+
+
+def fill_adaptors(a, lc, what, ptr):
+    """The adaptor descriptors of a Compressor{Batch,Ragged}AdaptArgs block from the local compressor's parameters; `ptr` registers a
+    tensor with the plan and returns its address.  The fp16 copy of the second layer's weight is the cached one of
+    injector._f16_weight (range-checked when first built, refreshed in place: the plan holds its address)."""
+    from . import injector as inj
+    from .projector import _linear_params, _require_bf16_cuda
+    for field, mlp, norm, alpha in adaptor_streams(lc):
+        d = getattr(a, field)
+        (w0, b0), (w2, b2) = _linear_params(mlp[0]), _linear_params(mlp[2])
+        if w0.shape[0] % 64 or w0.shape[1] % 64 or w2.shape[0] % 64 or w0.shape != w2.shape:
+            raise NotImplementedError(f"{what}: adaptor widths must be multiples of 64")
+        _require_bf16_cuda("adaptor norm", norm.weight)
+        d.w0, d.b0 = ptr(w0), ptr(b0)
+        d.w2_f16, d.b2 = ptr(inj._f16_weight(mlp[2])), ptr(b2)
+        d.gamma, d.beta, d.alpha = ptr(norm.weight.detach()), ptr(norm.bias.detach()), ptr(alpha.detach())
+        a.alpha_dt, a.eps = nv._dt(alpha), norm.eps
+
+
+def refresh_adaptors(lc):
+    """Rebuilds, in place, the cached fp16 weight copies the adaptor descriptors point at (a no-op while the weights have not moved)."""
+    from . import injector as inj
+    for _, mlp, _, _ in adaptor_streams(lc):
+        inj._f16_weight(mlp[2])
 
 
 def _scope(proj, ff, fe, guides, modal, nl):
@@ -33,10 +78,9 @@ def _scope(proj, ff, fe, guides, modal, nl):
     lc, gc = proj.local_compressor, proj.global_compressor
     if isinstance(ff, dict) or isinstance(fe, dict):
         raise NotImplementedError("forward_batch: anyres dict inputs have no batched path (call forward() per image)")
-    if (lc is None or gc is None or lc.use_guide != "direct" or gc.use_guide != "direct" or not lc.is_plain or not gc.is_plain
-            or proj.local_use_clip_scale or proj.global_use_clip_scale):
-        raise NotImplementedError("forward_batch is built for the release recipe only (local + global compressor, "
-                                  "use_guide='direct', no adaptors, no clip scale)")
+    if seg_recipe(proj) is None:
+        raise NotImplementedError("forward_batch is built for the two release recipes only (local + global compressor, "
+                                  "use_guide='direct', no adaptors but adapt_k / adapt_v on the local stage, no clip scale)")
     wdt = lc.readout[0].weight.dtype
     if wdt != torch.bfloat16:
         raise NotImplementedError(f"forward_batch: a {wdt} projector; the batched step takes a bfloat16 module and bfloat16 inputs")
@@ -75,7 +119,9 @@ def _build(proj, B, T, H, W, E, tiles, has_fe, modal, nl, out_dtype, chunks, dev
     lay = proj._layout((at.nwin, ay.nwin, ax.nwin), modal, nl is not None, False)
     att = gc.attn_layer
     hidden = lc.readout[2].out_features
-    a = nv.CompressorBatchArgs()
+    adapt = seg_recipe(proj) == "adaptkv"
+    args = nv.CompressorBatchAdaptArgs() if adapt else nv.CompressorBatchArgs()
+    a = args.base if adapt else args
     a.B, a.T, a.H, a.W, a.E, a.hidden = B, T, H, W, E, hidden
     a.kt, a.ks, a.nh = at.k, ay.k, att.num_heads
     a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
@@ -113,14 +159,18 @@ def _build(proj, B, T, H, W, E, tiles, has_fe, modal, nl, out_dtype, chunks, dev
     if lay.newline_rows:
         a.nl_first = lay.newline_rows[0]
         a.nl_step = lay.newline_rows[1] - lay.newline_rows[0] if len(lay.newline_rows) > 1 else 1
-    nbytes = nv.compressor_batch_workspace(a)          # (NotImplementedError for a limit of the kernels, B among them)
+    if adapt:
+        fill_adaptors(args, lc, "forward_batch", ptr)
+    nbytes = nv.compressor_batch_workspace(args)       # (NotImplementedError for a limit of the kernels, B among them)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     a.ws, a.ws_bytes = ws.data_ptr(), nbytes
-    plan = _BatchPlan(a, ws, a.item_rows, hidden, None)
+    plan = _BatchPlan(args, ws, a.item_rows, hidden, None)
     plan.keep = keep
+    plan.adapt_bytes = nbytes - nv.compressor_batch_workspace(a) if adapt else 0
 
     def refresh():
         lc.readout_f16()
+        refresh_adaptors(lc)
         if gc.use_pos_emb:
             gc.pos_and_kpe(T, H, W, dev)
     plan.refresh = refresh
@@ -138,7 +188,8 @@ def run_batch(proj, ff, fe, guides, modal, nl, chunks=None):
     nl = nl.contiguous() if nl is not None else None
     out_dtype = _out_dtype(proj)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    key = (B, T, H, W, E, fe is not None, modal, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0))
+    key = (B, T, H, W, E, fe is not None, modal, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
+           seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
     plans = proj.__dict__.setdefault("_batch_plans", {})
     plan = plans.get(key)
     sig = engine.plan_sig(proj)
@@ -159,7 +210,7 @@ def run_batch(proj, ff, fe, guides, modal, nl, chunks=None):
             plans.pop(next(iter(plans)))
         plans[key] = plan
     plan.hits += 1
-    a = plan.args
+    a = plan.io
     out = torch.empty((B, plan.rows, plan.hidden), dtype=out_dtype, device=dev)
     a.ff = ff.data_ptr()
     a.fe = fe.data_ptr() if fe is not None else None
@@ -167,5 +218,5 @@ def run_batch(proj, ff, fe, guides, modal, nl, chunks=None):
     a.newline = nl.data_ptr() if (nl is not None and a.nl_count > 0) else None
     a.out = out.data_ptr()
     a.stream = stream
-    nv.compressor_batch_fwd(a)
+    nv.compressor_batch_fwd(plan.args)
     return out

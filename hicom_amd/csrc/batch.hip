@@ -15,6 +15,11 @@
 //     readout layers as one GEMM pair over all B x windows_per_item contexts (hicom_readout16_gemm_fwd), and ONE placement launch
 //     that writes every item's packed rows: local tokens around the newline gaps, newline rows, the 32 copies of the global row.
 // Twelve launches for any B.  Everything on the caller's stream, nothing synchronises the host.
+//
+// The k / v adaptor recipe (`local43_adaptkv_global32`, hicom_compressor_batch_adapt_*) is the same step with two more launches in
+// front of the local stage -- the two layers of the adaptor MLPs as dense GEMMs over all B N tokens (segment_item.hpp: seg_adapt_mlps)
+// -- and batch_local_attn_adapt_kernel in the local stage's place: fourteen launches.  One host implementation serves both; the plain
+// entry points are its "no adaptor" case and run exactly the kernels and the workspace layout they ran before.
 #include "segment_item.hpp"
 
 namespace hicom {
@@ -32,6 +37,20 @@ __global__ __launch_bounds__(256) void batch_local_attn_kernel(const uint16_t* k
     if (win >= nwin) return;
     const WindowGeom g(at, ay, ax, win);
     local_window_ctx16<NV>(key, value, guide + (long)(win / wpi) * D, g, lane, scale, ctx16 + (long)win * D);
+}
+
+// The same with the k / v adaptor blends fused into the row loads (segment_item.hpp: local_window_adapt_ctx16); ky / vy rows are indexed
+// like the tokens of the stacked grid.
+template <int NV>
+__global__ __launch_bounds__(256) void batch_local_attn_adapt_kernel(const uint16_t* key, const uint16_t* value, const uint16_t* guide,
+                                                                     SegAdaptParams ad, hicom_axis at, hicom_axis ay, hicom_axis ax, int wpi,
+                                                                     int nwin, float scale, _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const WindowGeom g(at, ay, ax, win);
+    local_window_adapt_ctx16<NV>(key, ad.ky, value, ad.vy, ad, guide + (long)(win / wpi) * D, g, lane, scale, ctx16 + (long)win * D);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -111,11 +130,13 @@ int batch_chunks(const hicom_compressor_batch_args* a) {
 
 struct BatchLayout {
     long qp, qhi, qlo, pos_a, scores, part_m, part_l, part_acc, ctxg, o, pre, hid, tok, ctx16, hid16, loc, total;
+    hicom_host::SegAdaptLayout ad;      // behind the plain layout, whose offsets and total do not depend on it
     long score_stride;
     int chunks, wpi, rows_all;
 };
 
-BatchLayout batch_layout(const hicom_compressor_batch_args* a) {
+// ad: the k / v adaptors of the local stage, NULL for the plain recipe (hicom_compressor_batch_*)
+BatchLayout batch_layout(const hicom_compressor_batch_args* a, const hicom_host::SegAdapt* ad) {
     BatchLayout l;
     long off = 0;
     auto take = [&](long bytes) { const long at = off; off += (bytes + 255) / 256 * 256; return at; };
@@ -141,11 +162,12 @@ BatchLayout batch_layout(const hicom_compressor_batch_args* a) {
     l.ctx16 = take((long)l.rows_all * E * 2);
     l.hid16 = take((long)l.rows_all * a->hidden * 2);
     l.loc = take((long)l.rows_all * a->hidden * odt);
+    l.ad = hicom_host::seg_adapt_layout(ad, B * N, E, take);
     l.total = off;
     return l;
 }
 
-int batch_check(const hicom_compressor_batch_args* a) {
+int batch_check(const hicom_compressor_batch_args* a, const hicom_host::SegAdapt* ad) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_batch: NULL arguments");
     HICOM_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->hidden > 0 && a->kt > 0 && a->ks > 0, HICOM_EINVAL, "compressor_batch: bad shape");
     HICOM_REQUIRE(a->B <= kBatchMax, HICOM_EUNSUP, "compressor_batch: B=%d items (<= %d per call)", a->B, kBatchMax);
@@ -160,23 +182,23 @@ int batch_check(const hicom_compressor_batch_args* a) {
                   "compressor_batch: T=%d frames of %dx%d: the merge keeps T (H + W) marginal sums in LDS", a->T, a->H, a->W);
     HICOM_REQUIRE(a->out_dt == HICOM_DT_BF16 || a->out_dt == HICOM_DT_F32, HICOM_EUNSUP, "compressor_batch: output dtype %d (bf16 | f32)", a->out_dt);
     HICOM_REQUIRE(!a->pe == !a->kpe && (!a->pe || a->P > 0), HICOM_EINVAL, "compressor_batch: pe and kpe come together");
-    return HICOM_OK;
+    return hicom_host::seg_adapt_check("compressor_batch", ad, (long)a->B * a->T * a->H * a->W, a->E);
 }
 
-}  // namespace
-
-extern "C" int64_t hicom_compressor_batch_workspace_bytes(const hicom_compressor_batch_args* a) {
-    const int st = batch_check(a);
+int64_t batch_workspace_bytes(const hicom_compressor_batch_args* a, const hicom_host::SegAdapt* ad) {
+    const int st = batch_check(a, ad);
     if (st != HICOM_OK) return st;
-    return batch_layout(a).total;
+    return batch_layout(a, ad).total;
 }
 
-extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) {
-    int st = batch_check(a);
+int batch_fwd(const hicom_compressor_batch_args* a, const hicom_host::SegAdapt* ad) {
+    int st = batch_check(a, ad);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->ff && a->guide && a->out && a->ws, HICOM_EINVAL, "compressor_batch: NULL pointer");
     HICOM_REQUIRE(a->lw0_f16 && a->lw2_f16 && a->wq && a->wk && a->wv && a->wo && a->gw0 && a->gw2, HICOM_EINVAL, "compressor_batch: NULL weight");
-    const BatchLayout l = batch_layout(a);
+    st = hicom_host::seg_adapt_check_weights("compressor_batch", ad);
+    if (st != HICOM_OK) return st;
+    const BatchLayout l = batch_layout(a, ad);
     HICOM_REQUIRE(a->ws_bytes >= l.total && (uintptr_t)a->ws % 256 == 0, HICOM_EINVAL, "compressor_batch: workspace of %ld bytes, 256-byte aligned",
                   l.total);
     HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (!a->fe || (uintptr_t)a->fe % 16 == 0) && (uintptr_t)a->guide % 16 == 0, HICOM_EINVAL,
@@ -207,13 +229,21 @@ extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) 
                                     a->stream);
     if (st != HICOM_OK) return st;
 
-    // 3: local stage over the stacked window grid
+    // 3: local stage over the stacked window grid (adaptor recipe: the two layers of the adaptor MLPs over all tokens in front of it)
     {
         const hicom_axis at{B * a->T, a->kt, B * a->T / a->kt, B * a->T / a->kt};
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
-        HICOM_LAUNCH(batch_local_attn_kernel<3>, dim3((unsigned)((l.rows_all + 3) / 4)), dim3(256), 0, s,
-                     (const uint16_t*)(a->fe ? a->fe : a->ff), (const uint16_t*)a->ff, (const uint16_t*)a->guide, at, ay, ax, l.wpi, l.rows_all,
-                     a->l_scale, (_Float16*)(ws + l.ctx16));
+        const uint16_t* key_x = (const uint16_t*)(a->fe ? a->fe : a->ff);
+        if (ad) {
+            st = hicom_host::seg_adapt_mlps(*ad, key_x, a->ff, (long)B * N, E, ws, l.ad, a->stream);
+            if (st != HICOM_OK) return st;
+            HICOM_LAUNCH(batch_local_attn_adapt_kernel<3>, dim3((unsigned)((l.rows_all + 3) / 4)), dim3(256), 0, s, key_x, (const uint16_t*)a->ff,
+                         (const uint16_t*)a->guide, hicom_host::seg_adapt_params(*ad, ws, l.ad), at, ay, ax, l.wpi, l.rows_all, a->l_scale,
+                         (_Float16*)(ws + l.ctx16));
+        } else {
+            HICOM_LAUNCH(batch_local_attn_kernel<3>, dim3((unsigned)((l.rows_all + 3) / 4)), dim3(256), 0, s, key_x, (const uint16_t*)a->ff,
+                         (const uint16_t*)a->guide, at, ay, ax, l.wpi, l.rows_all, a->l_scale, (_Float16*)(ws + l.ctx16));
+        }
         st = hicom_host::check_launch("compressor_batch: local stage");
         if (st != HICOM_OK) return st;
     }
@@ -281,4 +311,23 @@ extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) 
         st = hicom_host::check_launch("compressor_batch: placement");
     }
     return st;
+}
+
+}  // namespace
+
+extern "C" int64_t hicom_compressor_batch_workspace_bytes(const hicom_compressor_batch_args* a) { return batch_workspace_bytes(a, nullptr); }
+
+extern "C" int hicom_compressor_batch_fwd(const hicom_compressor_batch_args* a) { return batch_fwd(a, nullptr); }
+
+// ---- the adaptor recipe: the same step with the k / v adaptors on the local stage -------------------------------------------------------
+extern "C" int64_t hicom_compressor_batch_adapt_workspace_bytes(const hicom_compressor_batch_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_batch: NULL arguments");
+    const hicom_host::SegAdapt ad{&a->ak, &a->av, a->alpha_dt, a->eps};
+    return batch_workspace_bytes(&a->base, &ad);
+}
+
+extern "C" int hicom_compressor_batch_adapt_fwd(const hicom_compressor_batch_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_batch: NULL arguments");
+    const hicom_host::SegAdapt ad{&a->ak, &a->av, a->alpha_dt, a->eps};
+    return batch_fwd(&a->base, &ad);
 }

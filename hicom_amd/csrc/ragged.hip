@@ -14,6 +14,10 @@
 // item's own (T, kt) and offsets the token index by the item's first token.  The four lookups are wave-uniform loads through a
 // kernel-argument pointer with a uniform index: they land in SGPRs.
 // Launches 1-2 and 6-11 are the existing entry points with M = B or M = sum windows.  hicom_compressor_ragged_fwd only launches.
+//
+// The k / v adaptor recipe (hicom_compressor_ragged_adapt_*) adds what batch.hip adds: the adaptor MLPs as two dense GEMM launches over
+// the whole stack in front of the local stage (token-wise: they need no item boundaries) and ragged_local_attn_adapt_kernel in the
+// local stage's place -- fourteen launches.  The plain entry points are the "no adaptor" case of the one host implementation below.
 #include <vector>
 
 #include "segment_item.hpp"
@@ -48,6 +52,25 @@ __global__ __launch_bounds__(256) void ragged_local_attn_kernel(const uint16_t* 
     const WindowGeom g(at, ay, ax, win - it.win0);
     const long first = (long)it.tok0 * D;
     local_window_ctx16<NV>(key + first, value + first, guide + (long)item * D, g, lane, scale, ctx16 + (long)win * D);
+}
+
+// ... with the k / v adaptor blends fused into the row loads (segment_item.hpp: local_window_adapt_ctx16); the y rows of an item start
+// at its first token like its x rows
+template <int NV>
+__global__ __launch_bounds__(256) void ragged_local_attn_adapt_kernel(const uint16_t* key, const uint16_t* value, const uint16_t* guide,
+                                                                      SegAdaptParams ad, const RaggedItem* items, const int* win_item,
+                                                                      hicom_axis ay, hicom_axis ax, int nwin, float scale, _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const int item = win_item[win];
+    const RaggedItem it = items[item];
+    const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+    const WindowGeom g(at, ay, ax, win - it.win0);
+    const long first = (long)it.tok0 * D;
+    local_window_adapt_ctx16<NV>(key + first, ad.ky ? ad.ky + first : nullptr, value + first, ad.vy ? ad.vy + first : nullptr, ad,
+                                 guide + (long)item * D, g, lane, scale, ctx16 + (long)win * D);
 }
 
 // ---- 4: segmented global stream, one workgroup per work unit ----
@@ -118,13 +141,15 @@ int ragged_chunks(long ntiles, long ntiles_sum, int chunks, int ncu) {
 struct RaggedLayout {
     long items, units, win_item, row_item, table_bytes;     // the table region
     long qp, qhi, qlo, pos_a, scores, part_m, part_l, part_acc, ctxg, o, pre, hid, tok, ctx16, hid16, loc, total;
+    hicom_host::SegAdaptLayout ad;                          // behind the plain layout, whose offsets and total do not depend on it
     long tokens, windows, rows, score16, ntiles_sum, units_n;
     int max_T, wps;
 };
 
 inline long item_windows(const hicom_compressor_ragged_args* a, const hicom_ragged_item& it, int wps) { return (long)(it.T / it.kt) * wps; }
 
-RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a) {
+// ad: the k / v adaptors of the local stage, NULL for the plain recipe (hicom_compressor_ragged_*)
+RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a, const hicom_host::SegAdapt* ad) {
     RaggedLayout l{};
     const long B = a->B, E = a->E, HW = (long)a->H * a->W, R = B * a->nh;
     l.wps = (a->H / a->ks) * (a->W / a->ks);
@@ -164,11 +189,12 @@ RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a) {
     l.ctx16 = take(l.windows * E * 2);
     l.hid16 = take(l.windows * a->hidden * 2);
     l.loc = take(l.windows * a->hidden * odt);
+    l.ad = hicom_host::seg_adapt_layout(ad, l.tokens, E, take);
     l.total = off;
     return l;
 }
 
-int ragged_check(const hicom_compressor_ragged_args* a) {
+int ragged_check(const hicom_compressor_ragged_args* a, const hicom_host::SegAdapt* ad) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_ragged: NULL arguments");
     HICOM_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && a->hidden > 0 && a->ks > 0 && a->items, HICOM_EINVAL, "compressor_ragged: bad shape");
     HICOM_REQUIRE(a->B <= hicom_host::kSegMaxItems, HICOM_EUNSUP, "compressor_ragged: B=%d items (<= %d per call)", a->B, hicom_host::kSegMaxItems);
@@ -199,7 +225,7 @@ int ragged_check(const hicom_compressor_ragged_args* a) {
     HICOM_REQUIRE(tokens + 16L * a->B < (1L << 27), HICOM_EUNSUP, "compressor_ragged: too many tokens in one call");
     HICOM_REQUIRE(((long)max_T * a->H + (long)max_T * a->W + max_T + a->H + a->W) * 4 <= 48 * 1024, HICOM_EUNSUP,
                   "compressor_ragged: T=%d frames of %dx%d: the merge keeps T (H + W) marginal sums in LDS", max_T, a->H, a->W);
-    return HICOM_OK;
+    return hicom_host::seg_adapt_check("compressor_ragged", ad, tokens, a->E);
 }
 
 int ragged_check_ws(const hicom_compressor_ragged_args* a, const RaggedLayout& l) {
@@ -208,18 +234,16 @@ int ragged_check_ws(const hicom_compressor_ragged_args* a, const RaggedLayout& l
     return HICOM_OK;
 }
 
-}  // namespace
-
-extern "C" int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compressor_ragged_args* a) {
-    const int st = ragged_check(a);
+int64_t ragged_workspace_bytes(const hicom_compressor_ragged_args* a, const hicom_host::SegAdapt* ad) {
+    const int st = ragged_check(a, ad);
     if (st != HICOM_OK) return st;
-    return ragged_layout(a).total;
+    return ragged_layout(a, ad).total;
 }
 
-extern "C" int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_args* a) {
-    int st = ragged_check(a);
+int ragged_prepare(const hicom_compressor_ragged_args* a, const hicom_host::SegAdapt* ad) {
+    int st = ragged_check(a, ad);
     if (st != HICOM_OK) return st;
-    const RaggedLayout l = ragged_layout(a);
+    const RaggedLayout l = ragged_layout(a, ad);
     st = ragged_check_ws(a, l);
     if (st != HICOM_OK) return st;
     std::vector<int> tab((size_t)(l.table_bytes / 4), 0);
@@ -255,12 +279,14 @@ extern "C" int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_arg
     return HICOM_OK;
 }
 
-extern "C" int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* a) {
-    int st = ragged_check(a);
+int ragged_fwd(const hicom_compressor_ragged_args* a, const hicom_host::SegAdapt* ad) {
+    int st = ragged_check(a, ad);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->ff && a->guide && a->out, HICOM_EINVAL, "compressor_ragged: NULL pointer");
     HICOM_REQUIRE(a->lw0_f16 && a->lw2_f16 && a->wq && a->wk && a->wv && a->wo && a->gw0 && a->gw2, HICOM_EINVAL, "compressor_ragged: NULL weight");
-    const RaggedLayout l = ragged_layout(a);
+    st = hicom_host::seg_adapt_check_weights("compressor_ragged", ad);
+    if (st != HICOM_OK) return st;
+    const RaggedLayout l = ragged_layout(a, ad);
     st = ragged_check_ws(a, l);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (!a->fe || (uintptr_t)a->fe % 16 == 0) && (uintptr_t)a->guide % 16 == 0, HICOM_EINVAL,
@@ -284,12 +310,21 @@ extern "C" int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* a
                                     a->stream);
     if (st != HICOM_OK) return st;
 
-    // 3: local stage over the concatenated window list
+    // 3: local stage over the concatenated window list (adaptor recipe: the two layers of the adaptor MLPs over all tokens in front of it)
     {
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
-        HICOM_LAUNCH(ragged_local_attn_kernel<3>, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, s, (const uint16_t*)(a->fe ? a->fe : a->ff),
-                     (const uint16_t*)a->ff, (const uint16_t*)a->guide, items, (const int*)(ws + l.win_item), ay, ax, (int)l.windows, a->l_scale,
-                     (_Float16*)(ws + l.ctx16));
+        const uint16_t* key_x = (const uint16_t*)(a->fe ? a->fe : a->ff);
+        if (ad) {
+            st = hicom_host::seg_adapt_mlps(*ad, key_x, a->ff, l.tokens, E, ws, l.ad, a->stream);
+            if (st != HICOM_OK) return st;
+            HICOM_LAUNCH(ragged_local_attn_adapt_kernel<3>, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, s, key_x, (const uint16_t*)a->ff,
+                         (const uint16_t*)a->guide, hicom_host::seg_adapt_params(*ad, ws, l.ad), items, (const int*)(ws + l.win_item), ay, ax,
+                         (int)l.windows, a->l_scale, (_Float16*)(ws + l.ctx16));
+        } else {
+            HICOM_LAUNCH(ragged_local_attn_kernel<3>, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, s, key_x, (const uint16_t*)a->ff,
+                         (const uint16_t*)a->guide, items, (const int*)(ws + l.win_item), ay, ax, (int)l.windows, a->l_scale,
+                         (_Float16*)(ws + l.ctx16));
+        }
         st = hicom_host::check_launch("compressor_ragged: local stage");
         if (st != HICOM_OK) return st;
     }
@@ -359,4 +394,31 @@ extern "C" int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* a
         st = hicom_host::check_launch("compressor_ragged: placement");
     }
     return st;
+}
+
+}  // namespace
+
+extern "C" int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compressor_ragged_args* a) { return ragged_workspace_bytes(a, nullptr); }
+
+extern "C" int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_args* a) { return ragged_prepare(a, nullptr); }
+
+extern "C" int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* a) { return ragged_fwd(a, nullptr); }
+
+// ---- the adaptor recipe: the same step with the k / v adaptors on the local stage; the table region is the plain one ----------------
+extern "C" int64_t hicom_compressor_ragged_adapt_workspace_bytes(const hicom_compressor_ragged_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_ragged: NULL arguments");
+    const hicom_host::SegAdapt ad{&a->ak, &a->av, a->alpha_dt, a->eps};
+    return ragged_workspace_bytes(&a->base, &ad);
+}
+
+extern "C" int hicom_compressor_ragged_adapt_prepare(const hicom_compressor_ragged_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_ragged: NULL arguments");
+    const hicom_host::SegAdapt ad{&a->ak, &a->av, a->alpha_dt, a->eps};
+    return ragged_prepare(&a->base, &ad);
+}
+
+extern "C" int hicom_compressor_ragged_adapt_fwd(const hicom_compressor_ragged_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_ragged: NULL arguments");
+    const hicom_host::SegAdapt ad{&a->ak, &a->av, a->alpha_dt, a->eps};
+    return ragged_fwd(&a->base, &ad);
 }

@@ -41,6 +41,83 @@ __device__ __forceinline__ void local_window_ctx16(const uint16_t* key, const ui
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The same window with the k / v adaptor blends fused into its row loads (local_attn.hip: local_attn_adapt_kernel has the algebra):
+//   key_n = (1 - a_k) x_n + a_k (LN(y_n) gamma_k + beta_k),  y = MLP_k(x) from the two dense GEMMs in front, likewise the values.
+// The blended streams are never written: a logit is blend_dot's four wave reductions over the x row and the y row, the context comes
+// from two accumulators (sum p_n v_n and sum p_n rstd_n y_n) and the scalar sum p_n rstd_n mu_n; the LayerNorm statistics are fp32,
+// from the row in registers.  One wave per window as above (WIN <= 64, lane i keeps logit i; no LDS, no barrier: the four waves of a
+// workgroup are four independent windows); one token (x row + y row) in flight.  kx / ky / vx / vy point at the ITEM's first token;
+// ky or vy may be NULL (that stream is not adapted), not both.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct SegAdaptParams {
+    const _Float16* ky;        // MLP_k(key tokens) fp16 [all tokens][D] or NULL
+    const uint16_t* kgamma; const uint16_t* kbeta; const void* kalpha;
+    const _Float16* vy;        // MLP_v(value tokens) fp16 [all tokens][D] or NULL
+    const uint16_t* vgamma; const uint16_t* vbeta; const void* valpha;
+    int alpha_f32;
+    float eps;
+};
+
+template <int NV>
+__device__ __forceinline__ void local_window_adapt_ctx16(const uint16_t* kx, const _Float16* ky, const uint16_t* vx, const _Float16* vy,
+                                                         const SegAdaptParams& ad, const uint16_t* qrow, const WindowGeom& g, int lane,
+                                                         float scale, _Float16* o) {
+    constexpr int D = NV * 384;
+    const float ak = ky ? read_alpha(ad.kalpha, ad.alpha_f32) : 0.f, av = vy ? read_alpha(ad.valpha, ad.alpha_f32) : 0.f;
+    float sc = -3.0e38f;
+    {
+        float q[NV][6], qg[NV][6];
+        float cg = 0.f, cb = 0.f;
+        load_row<NV>(qrow, lane, q);
+        if (ky) affine_prep<NV>(q, ad.kgamma, ad.kbeta, lane, qg, cg, cb);
+        for (int i = 0; i < g.WIN; ++i) {
+            const long tok = g.token_of(i);
+            float x[NV][6], y[NV][6];
+            load_row<NV>(kx + tok * D, lane, x);
+            if (ky) load_row_f16<NV>(ky + tok * D, lane, y);
+            float mu, rstd;
+            const float d = blend_dot<NV>(x, y, ky != nullptr, q, qg, cg, cb, ak, ad.eps, mu, rstd) * scale;
+            if (lane == i) sc = d;
+        }
+    }
+    const float mx = wave_max_fast(sc);
+    const float e = lane < g.WIN ? expf(sc - mx) : 0.f;
+    const float pw = e / wave_sum_fast(e);
+    float accx[NV][6], accy[NV][6];
+    float smu = 0.f;                                // sum_n p_n rstd_n mu_n (identical in every lane)
+    row_zero<NV>(accx);
+    row_zero<NV>(accy);
+    for (int i = 0; i < g.WIN; ++i) {
+        const long tok = g.token_of(i);
+        float x[NV][6], y[NV][6];
+        load_row<NV>(vx + tok * D, lane, x);
+        if (vy) load_row_f16<NV>(vy + tok * D, lane, y);
+        const float pi = __shfl(pw, i, 64);
+        row_axpy<NV>(pi, x, accx);
+        if (vy) {
+            float mu, rstd;
+            ln_stats<NV>(y, ad.eps, mu, rstd);
+            const float wy = pi * rstd;
+            smu = fmaf(wy, mu, smu);
+            row_axpy<NV>(wy, y, accy);
+        }
+    }
+    if (vy) {
+        float gm[NV][6], bt[NV][6];
+        load_row<NV>(ad.vgamma, lane, gm);
+        load_row<NV>(ad.vbeta, lane, bt);
+#pragma unroll
+        for (int s = 0; s < NV; ++s)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) accx[s][j] = (1.0f - av) * accx[s][j] + av * (gm[s][j] * (accy[s][j] - smu) + bt[s][j]);
+    }
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) o[384 * s + 6 * lane + j] = (_Float16)fminf(fmaxf(accx[s][j], -65504.f), 65504.f);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Segmented global stream.  Tile staging, swizzle, MFMA operand layouts and the per-tile order of operations are those of
 // global_stream_kernel (global_stream.hip); see there for the CDNA4 mapping.  A workgroup walks the 16-token tiles [tb, te) of ONE
 // item, counted from the item's first token.
@@ -359,5 +436,80 @@ inline int num_cus() {
 constexpr int kSegMaxItems = 4096;       // items per call (grid y of the merge kernels, far below the limit)
 constexpr int kSegMaxChunks = 64;        // workgroups per item of the segmented stream
 constexpr int kSegStreamSmem = 2 * 9 * 4096 + 4096;
+
+// ---- k / v adaptors of the local stage, shared by the two many-item steps (NULL: the plain recipe) ------------------------------------
+struct SegAdapt {
+    const hicom_seg_adaptor* ak;
+    const hicom_seg_adaptor* av;
+    int alpha_dt;
+    float eps;
+    bool k() const { return ak->w0 != nullptr; }
+    bool v() const { return av->w0 != nullptr; }
+};
+
+// workspace regions behind the plain layout: fp16 [tokens, E] each, absent (0) for a stream without adaptor
+struct SegAdaptLayout { long hid_k = 0, hid_v = 0, ky = 0, vy = 0; };
+
+template <class Take>
+inline SegAdaptLayout seg_adapt_layout(const SegAdapt* ad, long tokens, long E, Take&& take) {
+    SegAdaptLayout l;
+    if (!ad) return l;
+    if (ad->k()) l.hid_k = take(tokens * E * 2);
+    if (ad->v()) l.hid_v = take(tokens * E * 2);
+    if (ad->k()) l.ky = take(tokens * E * 2);
+    if (ad->v()) l.vy = take(tokens * E * 2);
+    return l;
+}
+
+inline int seg_adapt_check(const char* who, const SegAdapt* ad, long tokens, int E) {
+    if (!ad) return HICOM_OK;
+    HICOM_REQUIRE(ad->k() || ad->v(), HICOM_EINVAL, "%s: neither stream has an adaptor (the plain entry point runs that recipe)", who);
+    HICOM_REQUIRE(E % 64 == 0, HICOM_EUNSUP, "%s: adaptor width %d (multiple of 64)", who, E);
+    HICOM_REQUIRE(tokens * E < (1L << 32), HICOM_EUNSUP, "%s: %ld tokens: the adaptor GEMMs take operands below 2^32 elements", who, tokens);
+    HICOM_REQUIRE(ad->alpha_dt == HICOM_DT_BF16 || ad->alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", who, ad->alpha_dt);
+    return HICOM_OK;
+}
+
+inline int seg_adapt_check_weights(const char* who, const SegAdapt* ad) {
+    if (!ad) return HICOM_OK;
+    for (const hicom_seg_adaptor* s : {ad->ak, ad->av})
+        if (s->w0) HICOM_REQUIRE(s->w2_f16 && s->gamma && s->beta && s->alpha, HICOM_EINVAL, "%s: adaptor weights", who);
+    return HICOM_OK;
+}
+
+// y = MLP(x) of the adapted streams over all `tokens` of the call: two launches.  Both adaptors with matching biases: each layer of the
+// two MLPs is one paired launch; otherwise (one adaptor: two launches as well) the single-problem entry point per layer.
+inline int seg_adapt_mlps(const SegAdapt& ad, const void* key_x, const void* ff, long tokens, int E, char* ws, const SegAdaptLayout& l, void* stream) {
+    const hicom_seg_adaptor &k = *ad.ak, &v = *ad.av;
+    const int M = (int)tokens;
+    if (ad.k() && ad.v() && !k.b0 == !v.b0 && !k.b2 == !v.b2) {
+        const int st = hicom_dense16_gemm_pair_fwd(key_x, k.w0, k.b0, ws + l.hid_k, nullptr, ff, v.w0, v.b0, ws + l.hid_v, nullptr, E, E, HICOM_DT_BF16,
+                                                   HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, E, E, 0, stream);
+        if (st != HICOM_OK) return st;
+        return hicom_dense16_gemm_pair_fwd(ws + l.hid_k, k.w2_f16, k.b2, ws + l.ky, nullptr, ws + l.hid_v, v.w2_f16, v.b2, ws + l.vy, nullptr, E, E,
+                                           HICOM_DT_F16, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, E, E, 0, stream);
+    }
+    auto mlp = [&](const hicom_seg_adaptor& a, const void* x, long hid, long y) -> int {
+        const int st = hicom_dense16_gemm_fwd(x, E, a.w0, E, HICOM_DT_BF16, a.b0, HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, ws + hid, E, E, nullptr, 0, nullptr,
+                                              0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
+        if (st != HICOM_OK) return st;
+        return hicom_dense16_gemm_fwd(ws + hid, E, a.w2_f16, E, HICOM_DT_F16, a.b2, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, ws + y, E, E, nullptr, 0, nullptr,
+                                      0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
+    };
+    if (ad.k()) { const int st = mlp(k, key_x, l.hid_k, l.ky); if (st != HICOM_OK) return st; }
+    if (ad.v()) { const int st = mlp(v, ff, l.hid_v, l.vy); if (st != HICOM_OK) return st; }
+    return HICOM_OK;
+}
+
+inline hicom::SegAdaptParams seg_adapt_params(const SegAdapt& ad, const char* ws, const SegAdaptLayout& l) {
+    hicom::SegAdaptParams p;
+    p.ky = ad.k() ? (const _Float16*)(ws + l.ky) : nullptr;
+    p.kgamma = (const uint16_t*)ad.ak->gamma; p.kbeta = (const uint16_t*)ad.ak->beta; p.kalpha = ad.ak->alpha;
+    p.vy = ad.v() ? (const _Float16*)(ws + l.vy) : nullptr;
+    p.vgamma = (const uint16_t*)ad.av->gamma; p.vbeta = (const uint16_t*)ad.av->beta; p.valpha = ad.av->alpha;
+    p.alpha_f32 = ad.alpha_dt == HICOM_DT_F32;
+    p.eps = ad.eps;
+    return p;
+}
 
 }  // namespace hicom_host

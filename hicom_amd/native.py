@@ -42,6 +42,8 @@ EXPORTS = (
     "hicom_compressor_ctx16_offset",
     "hicom_compressor_batch_fwd", "hicom_compressor_batch_workspace_bytes",
     "hicom_compressor_ragged_fwd", "hicom_compressor_ragged_workspace_bytes", "hicom_compressor_ragged_prepare",
+    "hicom_compressor_batch_adapt_fwd", "hicom_compressor_batch_adapt_workspace_bytes",
+    "hicom_compressor_ragged_adapt_fwd", "hicom_compressor_ragged_adapt_workspace_bytes", "hicom_compressor_ragged_adapt_prepare",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -188,6 +190,22 @@ class CompressorRaggedArgs(C.Structure):
     ]
 
 
+class SegAdaptor(C.Structure):
+    """hicom_seg_adaptor (include/hicom_hip.h): one k / v adaptor of the batched / ragged step; w0 NULL = that stream is not adapted."""
+    _fields_ = [("w0", C.c_void_p), ("b0", C.c_void_p), ("w2_f16", C.c_void_p), ("b2", C.c_void_p), ("gamma", C.c_void_p),
+                ("beta", C.c_void_p), ("alpha", C.c_void_p)]
+
+
+class CompressorBatchAdaptArgs(C.Structure):
+    """hicom_compressor_batch_adapt_args (include/hicom_hip.h): the plain block first, then the two adaptors."""
+    _fields_ = [("base", CompressorBatchArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
+
+
+class CompressorRaggedAdaptArgs(C.Structure):
+    """hicom_compressor_ragged_adapt_args (include/hicom_hip.h): the plain block first, then the two adaptors."""
+    _fields_ = [("base", CompressorRaggedArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -294,6 +312,11 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_fwd.argtypes = [C.POINTER(CompressorRaggedArgs)]
     L.hicom_compressor_ragged_prepare.argtypes = [C.POINTER(CompressorRaggedArgs)]
     L.hicom_compressor_ragged_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedArgs)]
+    L.hicom_compressor_batch_adapt_fwd.argtypes = [C.POINTER(CompressorBatchAdaptArgs)]
+    L.hicom_compressor_batch_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorBatchAdaptArgs)]
+    L.hicom_compressor_ragged_adapt_fwd.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
+    L.hicom_compressor_ragged_adapt_prepare.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
+    L.hicom_compressor_ragged_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -304,6 +327,8 @@ def lib() -> C.CDLL:
     L.hicom_compressor_zero_prefix_bytes.restype = C.c_int64
     L.hicom_compressor_batch_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_batch_adapt_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_ragged_adapt_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -628,8 +653,15 @@ def compressor_fwd(args: CompressorArgs):
     _check(lib().hicom_compressor_fwd(C.byref(args)), "hicom_compressor_fwd")
 
 
-def compressor_batch_workspace(args: CompressorBatchArgs) -> int:
-    n = lib().hicom_compressor_batch_workspace_bytes(C.byref(args))
+def _adapt(args) -> bool:
+    """True for the argument blocks of the adaptor recipe (the plain block is their first member)."""
+    return isinstance(args, (CompressorBatchAdaptArgs, CompressorRaggedAdaptArgs))
+
+
+def compressor_batch_workspace(args) -> int:
+    """args: CompressorBatchArgs or CompressorBatchAdaptArgs (as for compressor_batch_fwd)."""
+    L = lib()
+    n = (L.hicom_compressor_batch_adapt_workspace_bytes if _adapt(args) else L.hicom_compressor_batch_workspace_bytes)(C.byref(args))
     if n < 0:
         msg = lib().hicom_last_error().decode(errors="replace")
         if n == -2:                      # HICOM_EUNSUP: a limit of the batched kernels
@@ -638,12 +670,17 @@ def compressor_batch_workspace(args: CompressorBatchArgs) -> int:
     return n
 
 
-def compressor_batch_fwd(args: CompressorBatchArgs):
-    _check(lib().hicom_compressor_batch_fwd(C.byref(args)), "hicom_compressor_batch_fwd")
+def compressor_batch_fwd(args):
+    if _adapt(args):
+        _check(lib().hicom_compressor_batch_adapt_fwd(C.byref(args)), "hicom_compressor_batch_adapt_fwd")
+    else:
+        _check(lib().hicom_compressor_batch_fwd(C.byref(args)), "hicom_compressor_batch_fwd")
 
 
-def compressor_ragged_workspace(args: CompressorRaggedArgs) -> int:
-    n = lib().hicom_compressor_ragged_workspace_bytes(C.byref(args))
+def compressor_ragged_workspace(args) -> int:
+    """args: CompressorRaggedArgs or CompressorRaggedAdaptArgs (as for compressor_ragged_prepare / _fwd)."""
+    L = lib()
+    n = (L.hicom_compressor_ragged_adapt_workspace_bytes if _adapt(args) else L.hicom_compressor_ragged_workspace_bytes)(C.byref(args))
     if n < 0:
         msg = lib().hicom_last_error().decode(errors="replace")
         if n == -2:                      # HICOM_EUNSUP: a limit of the ragged kernels
@@ -652,12 +689,18 @@ def compressor_ragged_workspace(args: CompressorRaggedArgs) -> int:
     return int(n)
 
 
-def compressor_ragged_prepare(args: CompressorRaggedArgs):
-    _check(lib().hicom_compressor_ragged_prepare(C.byref(args)), "hicom_compressor_ragged_prepare")
+def compressor_ragged_prepare(args):
+    if _adapt(args):
+        _check(lib().hicom_compressor_ragged_adapt_prepare(C.byref(args)), "hicom_compressor_ragged_adapt_prepare")
+    else:
+        _check(lib().hicom_compressor_ragged_prepare(C.byref(args)), "hicom_compressor_ragged_prepare")
 
 
-def compressor_ragged_fwd(args: CompressorRaggedArgs):
-    _check(lib().hicom_compressor_ragged_fwd(C.byref(args)), "hicom_compressor_ragged_fwd")
+def compressor_ragged_fwd(args):
+    if _adapt(args):
+        _check(lib().hicom_compressor_ragged_adapt_fwd(C.byref(args)), "hicom_compressor_ragged_adapt_fwd")
+    else:
+        _check(lib().hicom_compressor_ragged_fwd(C.byref(args)), "hicom_compressor_ragged_fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

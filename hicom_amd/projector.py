@@ -1064,8 +1064,10 @@ class HIComProjector(nn.Module):
         of reference hicom_arch.py:164 yields for a uniform batch, viewed 5-D: no copy), guide_embeds bf16 [B, E], one instruction per
         item.  Returns [B, rows_per_item, hidden]; row b is laid out as forward(frames_feature[b], frames_embed[b], guide_embeds[b], modal,
         image_newline) and equals it to the kernels' rounding.  The launch count does not depend on B (csrc/batch.hip).
-        Release recipe only (local + global compressor, use_guide="direct", no adaptors, no clip scale, bf16 module, exact window
-        partition): everything else raises NotImplementedError.  Inference only: with autograd on and trainable parameters it raises.
+        The two release recipes only (local + global compressor, use_guide="direct", no clip scale, bf16 module, exact window
+        partition; `local43_global32`, or adapt_k / adapt_v on the local stage as in `local43_adaptkv_global32`: the adaptor MLPs then
+        run as two more launches over all tokens of the call, fourteen in all, and the module's recipe alone decides which path runs):
+        everything else raises NotImplementedError.  Inference only: with autograd on and trainable parameters it raises.
         `chunks`: workgroups per item of the segmented global stream (None: chosen so that B x chunks fills the chip)."""
         from . import batch
         return batch.run_batch(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
@@ -1078,8 +1080,8 @@ class HIComProjector(nn.Module):
         forward(frames_feature[t0_i : t0_i + T_i], frames_embed[...], guide_embeds[i], modals[i], image_newline) -- its own temporal
         window (1 for images and 1-frame items), its own packing and newline rows, the positional frame index starting at 0 -- and
         equals it to the kernels' rounding.  The launch count depends neither on B nor on the mix (csrc/ragged.hip).
-        Scope and refusals as forward_batch: release recipe, bf16 module and inputs, no anyres dicts, every item's windows partition
-        its grid exactly (NotImplementedError names the item otherwise), inference only.
+        Scope and refusals as forward_batch: the two release recipes (with k / v adaptors: fourteen launches), bf16 module and inputs,
+        no anyres dicts, every item's windows partition its grid exactly (NotImplementedError names the item otherwise), inference only.
         `chunks`: work units per item of the segmented global stream, each clamped to the item's 16-token tiles (None: every item gets
         its share of 2 x #CUs units by token count).
         Not timed yet (tools/ragged_bench.py).  It is the twelve launches of forward_batch, so its ~180 us floor is to

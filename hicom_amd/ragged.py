@@ -3,7 +3,8 @@
 The reference stacks whatever a batch holds -- single images, clips of 4, 8 or 16 frames, the odd 1-frame "video" -- into one
 [(b t), H, W, E] tensor, splits it by image_video_split_size and runs its projector once per item (hicom_arch.py:146-180).  Here the
 stacked tensor is read in place by ONE C call and the twelve launches of the batched step (batch.py), whatever B and the mix are.
-Release recipe only; everything else raises NotImplementedError.
+The two released recipes only, as there: `local43_global32`, and `local43_adaptkv_global32` with the adaptor MLPs as two more launches
+over the whole stack (fourteen); everything else raises NotImplementedError.
 
 Plans (filled argument block, the host item descriptors and the workspace, whose head holds the device tables) are cached on the
 module by (split_sizes, modals, grid, ...), like batch.py's; the input / output pointers are patched per call.
@@ -20,18 +21,21 @@ import torch
 
 from . import engine
 from . import native as nv
+from .batch import fill_adaptors, refresh_adaptors, seg_recipe
 
 _MAX_PLANS = 16
 MAX_CHUNKS = 64          # work units per item (csrc/segment_item.hpp: kSegMaxChunks)
 
 
 class _RaggedPlan:
-    __slots__ = ("args", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables")
+    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes")
 
     def __init__(self, args, items, ws, rows, hidden):
+        # args / io / adapt_bytes: as batch._BatchPlan's
         self.args, self.items, self.ws, self.rows, self.hidden = args, items, ws, rows, hidden
+        self.io = getattr(args, "base", args)
         self.sig = self.fresh = self.refresh = self.keep = self.tables = None
-        self.hits = 0
+        self.hits = self.adapt_bytes = 0
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -86,10 +90,9 @@ def _scope(proj, ff, fe, guides, split_sizes, modals, nl):
     lc, gc = proj.local_compressor, proj.global_compressor
     if isinstance(ff, dict) or isinstance(fe, dict):
         raise NotImplementedError("forward_ragged: anyres dict inputs have no ragged path (call forward() per image)")
-    if (lc is None or gc is None or lc.use_guide != "direct" or gc.use_guide != "direct" or not lc.is_plain or not gc.is_plain
-            or proj.local_use_clip_scale or proj.global_use_clip_scale):
-        raise NotImplementedError("forward_ragged is built for the release recipe only (local + global compressor, "
-                                  "use_guide='direct', no adaptors, no clip scale)")
+    if seg_recipe(proj) is None:
+        raise NotImplementedError("forward_ragged is built for the two release recipes only (local + global compressor, "
+                                  "use_guide='direct', no adaptors but adapt_k / adapt_v on the local stage, no clip scale)")
     wdt = lc.readout[0].weight.dtype
     if wdt != torch.bfloat16:
         raise NotImplementedError(f"forward_ragged: a {wdt} projector; the ragged step takes a bfloat16 module and bfloat16 inputs")
@@ -158,7 +161,9 @@ def _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, strea
     att = gc.attn_layer
     hidden = lc.readout[2].out_features
     items = (nv.RaggedItem * B)(*[nv.RaggedItem(*d) for d in desc])
-    a = nv.CompressorRaggedArgs()
+    adapt = seg_recipe(proj) == "adaptkv"
+    args = nv.CompressorRaggedAdaptArgs() if adapt else nv.CompressorRaggedArgs()
+    a = args.base if adapt else args
     a.B, a.H, a.W, a.E, a.hidden = B, H, W, E, hidden
     a.ks, a.nh = ks, att.num_heads
     a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
@@ -191,16 +196,20 @@ def _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, strea
     a.out_dt = nv.DT_F32 if out_dtype == torch.float32 else nv.DT_BF16
     a.ldo = hidden
     a.stream = stream
-    nbytes = nv.compressor_ragged_workspace(a)         # (NotImplementedError for a limit of the kernels)
+    if adapt:
+        fill_adaptors(args, lc, "forward_ragged", ptr)
+    nbytes = nv.compressor_ragged_workspace(args)      # (NotImplementedError for a limit of the kernels)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     a.ws, a.ws_bytes = ws.data_ptr(), nbytes
-    nv.compressor_ragged_prepare(a)                    # the device tables, once per plan (synchronises the stream)
+    nv.compressor_ragged_prepare(args)                 # the device tables, once per plan (synchronises the stream)
     tables = plan_tables(desc, H, W, ks, torch.cuda.get_device_properties(dev).multi_processor_count, a.chunks)
-    plan = _RaggedPlan(a, items, ws, tables.rows, hidden)
+    plan = _RaggedPlan(args, items, ws, tables.rows, hidden)
     plan.keep, plan.tables = keep, tables
+    plan.adapt_bytes = nbytes - nv.compressor_ragged_workspace(a) if adapt else 0
 
     def refresh():
         lc.readout_f16()
+        refresh_adaptors(lc)
         if gc.use_pos_emb:
             gc.pos_and_kpe(t_max, H, W, dev)
     plan.refresh = refresh
@@ -218,7 +227,8 @@ def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
     nl = nl.contiguous() if nl is not None else None
     out_dtype = _out_dtype(proj)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0))
+    key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
+           seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
     plans = proj.__dict__.setdefault("_ragged_plans", {})
     plan = plans.get(key)
     sig = engine.plan_sig(proj)
@@ -239,7 +249,7 @@ def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
             plans.pop(next(iter(plans)))
         plans[key] = plan
     plan.hits += 1
-    a = plan.args
+    a = plan.io
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
     a.ff = ff.data_ptr()
     a.fe = fe.data_ptr() if fe is not None else None
@@ -247,5 +257,5 @@ def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
     a.newline = nl.data_ptr() if nl is not None else None
     a.out = out.data_ptr()
     a.stream = stream
-    nv.compressor_ragged_fwd(a)
+    nv.compressor_ragged_fwd(plan.args)
     return list(out.split(plan.rows))

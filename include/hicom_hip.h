@@ -937,6 +937,47 @@ int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compressor_ragged_ar
 int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_args* args);
 int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* args);
 
+/* ---- the batched and the ragged step for the k / v adaptor recipe (`local43_adaptkv_global32`) ----------------------
+ * The adaptors sit on the local stage only (projector.py:431-457, :533-534: key = (1 - a_k) x + a_k LN(MLP_k(x)) over ALL tokens of
+ * the key stream, likewise the values over ff); the global stage reads the raw tokens, so launches 1-2 and 4-12 are those of the
+ * plain steps above.  In front of the local stage the two adaptor MLPs run over M = all tokens of the call as dense MFMA GEMMs
+ * (layer 1: raw bf16 tokens x bf16 weights -> fp16 hidden with GELU; layer 2: fp16 hidden x the fp16 weight copy -> fp16 y): with
+ * both adaptors each layer is ONE paired launch (hicom_dense16_gemm_pair_fwd), with one adaptor two single launches -- fourteen
+ * launches either way, whatever B and the mix are.  The local stage then blends LayerNorm(y) into the rows it loads (one wave per
+ * window, the blended streams are never written) and leaves the same saturating fp16 context plane as the plain step.
+ *   ak, av   : the adaptor of the key / of the value stream; w0 == NULL: that stream is not adapted (at least one of the two is).
+ *              The k adaptor reads fe (ff when fe is NULL), the v adaptor ff.  Widths are E (E % 64 == 0)
+ *   alpha_dt : dtype of the two alpha scalars (HICOM_DT_BF16 | HICOM_DT_F32); eps: the LayerNorms' epsilon
+ *   ws       : the *_adapt_workspace_bytes of these arguments.  The plain layout (the table region of the ragged step included) keeps
+ *              its offsets; BEHIND it come one fp16 [tokens, E] hidden plane and one fp16 [tokens, E] y plane per adapted stream --
+ *              token-sized, unlike everything in front of them (2 x 2304 bytes per token and adapted stream)
+ * Limits, error codes and the no-synchronisation contract of the *_fwd calls are those of the plain entry points; in addition
+ * tokens x E < 2^32 (the dense GEMM's operand limit), HICOM_EUNSUP otherwise.  hicom_compressor_ragged_adapt_prepare writes the same
+ * table region as hicom_compressor_ragged_prepare. */
+typedef struct hicom_seg_adaptor {
+    const void *w0, *b0;       /* Linear(E, E): bf16 [E, E], bf16 [E] (or NULL) */
+    const void *w2_f16, *b2;   /* Linear(E, E): fp16 copy of the weight (cached by the caller per weight state), bf16 bias (or NULL) */
+    const void *gamma, *beta;  /* LayerNorm: bf16 [E] */
+    const void* alpha;         /* device scalar of dtype alpha_dt */
+} hicom_seg_adaptor;
+typedef struct hicom_compressor_batch_adapt_args {
+    hicom_compressor_batch_args base;
+    hicom_seg_adaptor ak, av;
+    int32_t alpha_dt;
+    float eps;
+} hicom_compressor_batch_adapt_args;
+int64_t hicom_compressor_batch_adapt_workspace_bytes(const hicom_compressor_batch_adapt_args* args);
+int hicom_compressor_batch_adapt_fwd(const hicom_compressor_batch_adapt_args* args);
+typedef struct hicom_compressor_ragged_adapt_args {
+    hicom_compressor_ragged_args base;
+    hicom_seg_adaptor ak, av;
+    int32_t alpha_dt;
+    float eps;
+} hicom_compressor_ragged_adapt_args;
+int64_t hicom_compressor_ragged_adapt_workspace_bytes(const hicom_compressor_ragged_adapt_args* args);
+int hicom_compressor_ragged_adapt_prepare(const hicom_compressor_ragged_adapt_args* args);
+int hicom_compressor_ragged_adapt_fwd(const hicom_compressor_ragged_adapt_args* args);
+
 #ifdef __cplusplus
 }
 #endif

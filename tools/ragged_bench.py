@@ -1,9 +1,9 @@
 """Times HIComProjector.forward_ragged on mixed batches (single images next to clips of several lengths) against the two ways a user
 has without it, on the same inputs: (b) a loop of forward() per item, (c) bucketing the items by shape, one forward_batch per bucket
 and the torch.stack copies that needs.  One process, HIP events, after warm-up; inputs rotate through three sets.  Writes
-profiles/ragged_step.json.
+profiles/ragged_step.json, or with --recipe adaptkv (the k / v adaptor recipe, timed the same three ways) profiles/ragged_step_adaptkv.json.
 
-    python tools/ragged_bench.py [--iters 30] [--warmup 5] [--out profiles/ragged_step.json]"""
+    python tools/ragged_bench.py [--recipe plain|adaptkv] [--iters 30] [--warmup 5] [--out profiles/ragged_step.json]"""
 import argparse
 import json
 import os
@@ -14,8 +14,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import bench                                           # noqa: E402  (release_config / make_projector: the benchmark's module)
-from batch_bench import timed, D, GRID, SETS           # noqa: E402
+from batch_bench import timed, recipe_projector, default_out, RECIPES, D, GRID, SETS           # noqa: E402
 
 # name -> [(modal, T)] in batch order (images and clips interleaved as a data loader would deliver them)
 MIXES = {
@@ -45,10 +44,12 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=896)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ragged_step.json"))
+    ap.add_argument("--recipe", choices=sorted(RECIPES), default="plain")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or default_out("ragged_step", args.recipe)
     dev = torch.device("cuda")
-    m = bench.make_projector(bench.release_config(args.hidden, 32), dev)
+    m = recipe_projector(args.recipe, args.hidden, 32, dev)
     gen = torch.Generator(device=dev).manual_seed(7)
     rows = []
     with torch.no_grad():
@@ -83,7 +84,7 @@ def main():
             dev_abs = max(float((a.float() - b.float()).abs().max()) for a, b in zip(rag(sets[0]), want))
             dev_abs_c = max(float((a.float() - b.float()).abs().max()) for a, b in zip(bucketed(sets[0]), want))
             t_a, t_b, t_c = (timed(f, sets, args.iters, args.warmup) for f in (rag, loop, bucketed))
-            row = dict(mix=name, B=B, frames=frames, buckets=len(buckets), grid=GRID, hidden=args.hidden, ragged_us=round(t_a, 1),
+            row = dict(recipe=args.recipe, mix=name, B=B, frames=frames, buckets=len(buckets), grid=GRID, hidden=args.hidden, ragged_us=round(t_a, 1),
                        loop_us=round(t_b, 1), bucketed_us=round(t_c, 1), loop_over_ragged=round(t_b / t_a, 2),
                        bucketed_over_ragged=round(t_c / t_a, 2), max_abs_vs_loop=dev_abs, bucketed_max_abs_vs_loop=dev_abs_c)
             if len(buckets) == 1:                       # the control: forward_batch on the 5-D view of the same tensor, no copy
@@ -95,7 +96,7 @@ def main():
             del sets
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
-        json.dump(dict(tool="tools/ragged_bench.py", device=torch.cuda.get_device_name(0), iters=args.iters, warmup=args.warmup,
+        json.dump(dict(tool="tools/ragged_bench.py", recipe=args.recipe, device=torch.cuda.get_device_name(0), iters=args.iters, warmup=args.warmup,
                        timing="median of HIP-event intervals around one forward_ragged call (ragged), the per-item forward() loop (loop) or "
                               "one forward_batch per shape bucket with its torch.stack copies (bucketed); inputs rotate through 3 sets",
                        rows=rows), f, indent=1)
