@@ -1,0 +1,293 @@
+// Host side of a many-item compressor step, shared by the equal-shape step (batch.hip) and the ragged step (ragged.hip): the limits,
+// the k / v adaptors of the local stage, the checks, the workspace layout and the launch sequence that do not depend on how a wave finds
+// its item.  The two files keep their kernels, the code that launches them, their chunk policy and their own layout checks.  The shared
+// functions are templates over the argument block (hicom_compressor_batch_args / hicom_compressor_ragged_args name every common field
+// alike) and read `a->field` directly; `who` is the message prefix ("compressor_batch" / "compressor_ragged").
+#pragma once
+#include "segment_item.hpp"
+
+namespace hicom_host {
+
+// compute units of the current device (the work division of the segmented stream fills the chip twice over)
+inline int num_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else n = 256;
+    }
+    return n;
+}
+
+constexpr int kSegMaxItems = 4096;       // items per call (grid y of the merge kernels, far below the limit)
+constexpr int kSegMaxChunks = 64;        // workgroups per item of the segmented stream
+constexpr int kSegStreamSmem = 2 * 9 * 4096 + 4096;
+
+// ---- k / v adaptors of the local stage, shared by the two many-item steps (NULL: the plain recipe) ------------------------------------
+struct SegAdapt {
+    const hicom_seg_adaptor* ak;
+    const hicom_seg_adaptor* av;
+    int alpha_dt;
+    float eps;
+    bool k() const { return ak->w0 != nullptr; }
+    bool v() const { return av->w0 != nullptr; }
+};
+
+// workspace regions behind the plain layout: fp16 [tokens, E] each, absent (0) for a stream without adaptor
+struct SegAdaptLayout { long hid_k = 0, hid_v = 0, ky = 0, vy = 0; };
+
+template <class Take>
+inline SegAdaptLayout seg_adapt_layout(const SegAdapt* ad, long tokens, long E, Take&& take) {
+    SegAdaptLayout l;
+    if (!ad) return l;
+    if (ad->k()) l.hid_k = take(tokens * E * 2);
+    if (ad->v()) l.hid_v = take(tokens * E * 2);
+    if (ad->k()) l.ky = take(tokens * E * 2);
+    if (ad->v()) l.vy = take(tokens * E * 2);
+    return l;
+}
+
+inline int seg_adapt_check(const char* who, const SegAdapt* ad, long tokens, int E) {
+    if (!ad) return HICOM_OK;
+    HICOM_REQUIRE(ad->k() || ad->v(), HICOM_EINVAL, "%s: neither stream has an adaptor (the plain entry point runs that recipe)", who);
+    HICOM_REQUIRE(E % 64 == 0, HICOM_EUNSUP, "%s: adaptor width %d (multiple of 64)", who, E);
+    HICOM_REQUIRE(tokens * E < (1L << 32), HICOM_EUNSUP, "%s: %ld tokens: the adaptor GEMMs take operands below 2^32 elements", who, tokens);
+    HICOM_REQUIRE(ad->alpha_dt == HICOM_DT_BF16 || ad->alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", who, ad->alpha_dt);
+    return HICOM_OK;
+}
+
+inline int seg_adapt_check_weights(const char* who, const SegAdapt* ad) {
+    if (!ad) return HICOM_OK;
+    for (const hicom_seg_adaptor* s : {ad->ak, ad->av})
+        if (s->w0) HICOM_REQUIRE(s->w2_f16 && s->gamma && s->beta && s->alpha, HICOM_EINVAL, "%s: adaptor weights", who);
+    return HICOM_OK;
+}
+
+// y = MLP(x) of the adapted streams over all `tokens` of the call: two launches.  Both adaptors with matching biases: each layer of the
+// two MLPs is one paired launch; otherwise (one adaptor: two launches as well) the single-problem entry point per layer.
+inline int seg_adapt_mlps(const SegAdapt& ad, const void* key_x, const void* ff, long tokens, int E, char* ws, const SegAdaptLayout& l, void* stream) {
+    const hicom_seg_adaptor &k = *ad.ak, &v = *ad.av;
+    const int M = (int)tokens;
+    if (ad.k() && ad.v() && !k.b0 == !v.b0 && !k.b2 == !v.b2) {
+        const int st = hicom_dense16_gemm_pair_fwd(key_x, k.w0, k.b0, ws + l.hid_k, nullptr, ff, v.w0, v.b0, ws + l.hid_v, nullptr, E, E, HICOM_DT_BF16,
+                                                   HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, E, E, 0, stream);
+        if (st != HICOM_OK) return st;
+        return hicom_dense16_gemm_pair_fwd(ws + l.hid_k, k.w2_f16, k.b2, ws + l.ky, nullptr, ws + l.hid_v, v.w2_f16, v.b2, ws + l.vy, nullptr, E, E,
+                                           HICOM_DT_F16, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, E, E, 0, stream);
+    }
+    auto mlp = [&](const hicom_seg_adaptor& a, const void* x, long hid, long y) -> int {
+        const int st = hicom_dense16_gemm_fwd(x, E, a.w0, E, HICOM_DT_BF16, a.b0, HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, ws + hid, E, E, nullptr, 0, nullptr,
+                                              0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
+        if (st != HICOM_OK) return st;
+        return hicom_dense16_gemm_fwd(ws + hid, E, a.w2_f16, E, HICOM_DT_F16, a.b2, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, ws + y, E, E, nullptr, 0, nullptr,
+                                      0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
+    };
+    if (ad.k()) { const int st = mlp(k, key_x, l.hid_k, l.ky); if (st != HICOM_OK) return st; }
+    if (ad.v()) { const int st = mlp(v, ff, l.hid_v, l.vy); if (st != HICOM_OK) return st; }
+    return HICOM_OK;
+}
+
+inline hicom::SegAdaptParams seg_adapt_params(const SegAdapt& ad, const char* ws, const SegAdaptLayout& l) {
+    hicom::SegAdaptParams p;
+    p.ky = ad.k() ? (const _Float16*)(ws + l.ky) : nullptr;
+    p.kgamma = (const uint16_t*)ad.ak->gamma; p.kbeta = (const uint16_t*)ad.ak->beta; p.kalpha = ad.ak->alpha;
+    p.vy = ad.v() ? (const _Float16*)(ws + l.vy) : nullptr;
+    p.vgamma = (const uint16_t*)ad.av->gamma; p.vbeta = (const uint16_t*)ad.av->beta; p.valpha = ad.av->alpha;
+    p.alpha_f32 = ad.alpha_dt == HICOM_DT_F32;
+    p.eps = ad.eps;
+    return p;
+}
+
+// the entry points of the adaptor recipe (hicom_compressor_{batch,ragged}_adapt_*): f(plain block, adaptors) of an adaptor-recipe block
+template <class AdaptArgs, class F>
+inline auto seg_with_adapt(const char* who, const AdaptArgs* a, F&& f) -> decltype(f(&a->base, (const SegAdapt*)nullptr)) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", who);
+    const SegAdapt ad{&a->ak, &a->av, a->alpha_dt, a->eps};
+    return f(&a->base, &ad);
+}
+
+// ---- checks both steps make ---------------------------------------------------------------------------------------------------------------
+// LDS of the merge kernels: T (H + W) marginal sums and the T + H + W marginals of the longest item
+inline long seg_merge_smem(long T, long H, long W) { return (T * H + T * W + T + H + W) * 4; }
+
+// behind the caller's own "bad shape" check (B, H, W, hidden, ks > 0)
+template <class A>
+inline int seg_check_shape(const char* who, const A* a) {
+    HICOM_REQUIRE(a->B <= kSegMaxItems, HICOM_EUNSUP, "%s: B=%d items (<= %d per call)", who, a->B, kSegMaxItems);
+    HICOM_REQUIRE(a->E == 1152, HICOM_EUNSUP, "%s: E=%d (only 1152)", who, a->E);
+    HICOM_REQUIRE(a->nh > 0 && a->nh <= 16 && a->E % a->nh == 0, HICOM_EUNSUP, "%s: %d heads (<= 16 folded rows per item)", who, a->nh);
+    HICOM_REQUIRE(a->hidden % 64 == 0, HICOM_EUNSUP, "%s: hidden=%d (multiple of 64: fp16 readout planes)", who, a->hidden);
+    HICOM_REQUIRE(a->out_dt == HICOM_DT_BF16 || a->out_dt == HICOM_DT_F32, HICOM_EUNSUP, "%s: output dtype %d (bf16 | f32)", who, a->out_dt);
+    HICOM_REQUIRE(!a->pe == !a->kpe && (!a->pe || a->P > 0), HICOM_EINVAL, "%s: pe and kpe come together", who);
+    return HICOM_OK;
+}
+
+// T: the longest item's frames
+template <class A>
+inline int seg_check_merge_lds(const char* who, const A* a, int T) {
+    HICOM_REQUIRE(seg_merge_smem(T, a->H, a->W) <= 48 * 1024, HICOM_EUNSUP, "%s: T=%d frames of %dx%d: the merge keeps T (H + W) marginal sums in LDS", who,
+                  T, a->H, a->W);
+    return HICOM_OK;
+}
+
+template <class A>
+inline int seg_check_ws(const char* who, const A* a, long total) {
+    HICOM_REQUIRE(a->ws && a->ws_bytes >= total && (uintptr_t)a->ws % 256 == 0, HICOM_EINVAL, "%s: workspace of %ld bytes, 256-byte aligned", who, total);
+    return HICOM_OK;
+}
+
+// what a *_fwd call checks on top of its shape checks, in front of the first launch
+template <class A>
+inline int seg_check_fwd(const char* who, const A* a, const SegAdapt* ad, long ws_total) {
+    HICOM_REQUIRE(a->ff && a->guide && a->out, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE(a->lw0_f16 && a->lw2_f16 && a->wq && a->wk && a->wv && a->wo && a->gw0 && a->gw2, HICOM_EINVAL, "%s: NULL weight", who);
+    int st = seg_adapt_check_weights(who, ad);
+    if (st != HICOM_OK) return st;
+    st = seg_check_ws(who, a, ws_total);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (!a->fe || (uintptr_t)a->fe % 16 == 0) && (uintptr_t)a->guide % 16 == 0, HICOM_EINVAL,
+                  "%s: 16-byte aligned inputs", who);
+    return HICOM_OK;
+}
+
+// ---- workspace: the sixteen regions of the step from the call's totals, the adaptor planes behind them --------------------------------------
+struct SegTotals {
+    long score_floats;      // logits the stream leaves: 16 rows per item, the item's tokens padded to a tile
+    long slots;             // partial states (m, l, ACC) = workgroups of the segmented stream
+    long windows, tokens;   // over all items
+};
+
+struct SegLayout {
+    long qp, qhi, qlo, pos_a, scores, part_m, part_l, part_acc, ctxg, o, pre, hid, tok, ctx16, hid16, loc, total;
+    SegAdaptLayout ad;      // behind the plain layout, whose offsets and total do not depend on it
+    SegTotals n;
+};
+
+// off: bytes in front of the first region (the ragged step's tables), a multiple of 256
+template <class A>
+inline SegLayout seg_layout(const A* a, const SegAdapt* ad, const SegTotals& n, long off) {
+    SegLayout l;
+    auto take = [&](long bytes) { const long at = off; off += (bytes + 255) / 256 * 256; return at; };
+    const long B = a->B, E = a->E, R = B * a->nh, hidden = a->hidden;
+    const int odt = a->out_dt == HICOM_DT_F32 ? 4 : 2;
+    l.n = n;
+    l.qp = take(B * E * 4);
+    l.qhi = take(R * E * 2);
+    l.qlo = take(R * E * 2);
+    l.pos_a = take(R * (long)(a->P > 0 ? a->P : 1) * 4);
+    l.scores = take(n.score_floats * 4);
+    l.part_m = take(n.slots * 16 * 4);
+    l.part_l = take(n.slots * 16 * 4);
+    l.part_acc = take(n.slots * 16 * E * 4);
+    l.ctxg = take(R * E * 4);
+    l.o = take(B * E * 4);
+    l.pre = take(B * E * 4);
+    l.hid = take(B * hidden * 4);
+    l.tok = take(B * hidden * 4);
+    l.ctx16 = take(n.windows * E * 2);
+    l.hid16 = take(n.windows * hidden * 2);
+    l.loc = take(n.windows * hidden * odt);
+    l.ad = seg_adapt_layout(ad, n.tokens, E, take);
+    l.total = off;
+    return l;
+}
+
+inline int seg_check_launch(const char* who, const char* stage) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return HICOM_OK;
+    set_error("%s: %s: %s", who, stage, hipGetErrorString(e));
+    return HICOM_ELAUNCH;
+}
+
+// ---- the step: twelve launches, fourteen with adaptors ------------------------------------------------------------------------------------
+// `item` launches the four kernels that know where an item lives, each on the common part of its parameter block:
+//   item.local(key_x, adapt)   3: local stage into ws + l.ctx16; adapt: the fused blends' parameters, NULL for the plain recipe
+//   item.stream(c)             4: segmented global stream
+//   item.merge(c)              5: merge per (item, head) into ws + l.ctxg
+//   item.place(c)             12: every item's packed rows
+// Everything else is the same call for both steps, with M = B rows or M = all windows.  Only launches: nothing here allocates, copies or
+// synchronises.
+template <class A, class Item>
+inline int seg_step(const char* who, const A* a, const SegAdapt* ad, const SegLayout& l, const Item& item) {
+    char* ws = (char*)a->ws;
+    const int B = a->B, E = a->E, nh = a->nh, hd = E / nh, hidden = a->hidden, windows = (int)l.n.windows;
+    float* qp = (float*)(ws + l.qp);
+    float* pos_a = a->pe ? (float*)(ws + l.pos_a) : nullptr;
+    float* ctxg = (float*)(ws + l.ctxg);
+    float *o = (float*)(ws + l.o), *pre = (float*)(ws + l.pre), *hid = (float*)(ws + l.hid), *tok = (float*)(ws + l.tok);
+
+    // 1-2: queries per item
+    int st = hicom_linear_fwd(a->guide, HICOM_DT_BF16, a->wq, HICOM_DT_BF16, a->bq, HICOM_DT_BF16, nullptr, 0, B, E, E, 0, 0, HICOM_ACT_NONE, qp, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_fold_query_split_fwd(qp, a->wk, a->kpe, B, nh, E, a->P, 1.0f / sqrtf((float)hd), ws + l.qhi, ws + l.qlo, pos_a, a->P, nullptr, 0, 0,
+                                    a->stream);
+    if (st != HICOM_OK) return st;
+
+    // 3: local stage (adaptor recipe: the two layers of the adaptor MLPs over all tokens in front of it)
+    {
+        const uint16_t* key_x = (const uint16_t*)(a->fe ? a->fe : a->ff);
+        if (ad) {
+            st = seg_adapt_mlps(*ad, key_x, a->ff, l.n.tokens, E, ws, l.ad, a->stream);
+            if (st != HICOM_OK) return st;
+            const hicom::SegAdaptParams p = seg_adapt_params(*ad, ws, l.ad);
+            item.local(key_x, &p);
+        } else {
+            item.local(key_x, nullptr);
+        }
+        st = seg_check_launch(who, "local stage");
+        if (st != HICOM_OK) return st;
+    }
+
+    // 4: segmented global stream
+    {
+        hicom::SegStreamParams c;
+        c.qhi = (const uint16_t*)(ws + l.qhi); c.qlo = (const uint16_t*)(ws + l.qlo);
+        c.pos_a = pos_a; c.pos_stride = a->P; c.rows = nh;
+        c.H = a->H; c.W = a->W; c.HW = a->H * a->W;
+        c.t0i = a->t_index0; c.y0i = a->y_index0; c.x0i = a->x_index0;
+        c.part_m = (float*)(ws + l.part_m); c.part_l = (float*)(ws + l.part_l); c.part_acc = (float*)(ws + l.part_acc);
+        item.stream(c);
+        st = seg_check_launch(who, "global stream");
+        if (st != HICOM_OK) return st;
+    }
+
+    // 5: merge per item
+    {
+        hicom::SegMergeParams c;
+        c.part_m = (const float*)(ws + l.part_m); c.part_l = (const float*)(ws + l.part_l); c.part_acc = (const float*)(ws + l.part_acc);
+        c.pe = a->pe; c.E = E; c.H = a->H; c.W = a->W;
+        c.t0i = a->t_index0; c.y0i = a->y_index0; c.x0i = a->x_index0;
+        item.merge(c);
+        st = seg_check_launch(who, "merge");
+        if (st != HICOM_OK) return st;
+    }
+
+    // 6-9: the global tail with M = B rows
+    st = hicom_linear_fwd(ctxg, HICOM_DT_F32, a->wv, HICOM_DT_BF16, a->bv, HICOM_DT_BF16, nullptr, 0, B, E, E, nh, hd, HICOM_ACT_NONE, o, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_linear_fwd(o, HICOM_DT_F32, a->wo, HICOM_DT_BF16, a->bo, HICOM_DT_BF16, a->guide, 2, B, E, E, 0, 0, HICOM_ACT_NONE, pre, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_linear_fwd(pre, HICOM_DT_F32, a->gw0, HICOM_DT_BF16, a->gb0, HICOM_DT_BF16, nullptr, 0, B, hidden, E, 0, 0, HICOM_ACT_GELU, hid, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_linear_fwd(hid, HICOM_DT_F32, a->gw2, HICOM_DT_BF16, a->gb2, HICOM_DT_BF16, nullptr, 0, B, hidden, hidden, 0, 0, HICOM_ACT_NONE, tok, a->stream);
+    if (st != HICOM_OK) return st;
+
+    // 10-11: the local readout as one GEMM pair over all items' windows
+    st = hicom_readout16_gemm_fwd(ws + l.ctx16, a->lw0_f16, a->lb0, HICOM_DT_BF16, windows, hidden, E, HICOM_ACT_GELU, ws + l.hid16, nullptr, 0, 0, 0, 0, nullptr,
+                                  a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_readout16_gemm_fwd(ws + l.hid16, a->lw2_f16, a->lb2, HICOM_DT_BF16, windows, hidden, hidden, HICOM_ACT_NONE, nullptr, ws + l.loc, a->out_dt, hidden,
+                                  0, 0, nullptr, a->stream);
+    if (st != HICOM_OK) return st;
+
+    // 12: every item's packed rows
+    {
+        hicom::SegPlaceParams c;
+        c.loc = ws + l.loc; c.tok = tok; c.newline = (const uint16_t*)a->newline; c.out = a->out;
+        c.out_f32 = a->out_dt == HICOM_DT_F32; c.hidden = hidden;
+        item.place(c);
+    }
+    return seg_check_launch(who, "placement");
+}
+
+}  // namespace hicom_host

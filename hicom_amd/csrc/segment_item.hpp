@@ -419,97 +419,3 @@ __device__ __forceinline__ void place_row(const SegPlaceParams& p, long r, long 
 }
 
 }  // namespace hicom
-
-namespace hicom_host {
-
-// compute units of the current device (the work division of the segmented stream fills the chip twice over)
-inline int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
-constexpr int kSegMaxItems = 4096;       // items per call (grid y of the merge kernels, far below the limit)
-constexpr int kSegMaxChunks = 64;        // workgroups per item of the segmented stream
-constexpr int kSegStreamSmem = 2 * 9 * 4096 + 4096;
-
-// ---- k / v adaptors of the local stage, shared by the two many-item steps (NULL: the plain recipe) ------------------------------------
-struct SegAdapt {
-    const hicom_seg_adaptor* ak;
-    const hicom_seg_adaptor* av;
-    int alpha_dt;
-    float eps;
-    bool k() const { return ak->w0 != nullptr; }
-    bool v() const { return av->w0 != nullptr; }
-};
-
-// workspace regions behind the plain layout: fp16 [tokens, E] each, absent (0) for a stream without adaptor
-struct SegAdaptLayout { long hid_k = 0, hid_v = 0, ky = 0, vy = 0; };
-
-template <class Take>
-inline SegAdaptLayout seg_adapt_layout(const SegAdapt* ad, long tokens, long E, Take&& take) {
-    SegAdaptLayout l;
-    if (!ad) return l;
-    if (ad->k()) l.hid_k = take(tokens * E * 2);
-    if (ad->v()) l.hid_v = take(tokens * E * 2);
-    if (ad->k()) l.ky = take(tokens * E * 2);
-    if (ad->v()) l.vy = take(tokens * E * 2);
-    return l;
-}
-
-inline int seg_adapt_check(const char* who, const SegAdapt* ad, long tokens, int E) {
-    if (!ad) return HICOM_OK;
-    HICOM_REQUIRE(ad->k() || ad->v(), HICOM_EINVAL, "%s: neither stream has an adaptor (the plain entry point runs that recipe)", who);
-    HICOM_REQUIRE(E % 64 == 0, HICOM_EUNSUP, "%s: adaptor width %d (multiple of 64)", who, E);
-    HICOM_REQUIRE(tokens * E < (1L << 32), HICOM_EUNSUP, "%s: %ld tokens: the adaptor GEMMs take operands below 2^32 elements", who, tokens);
-    HICOM_REQUIRE(ad->alpha_dt == HICOM_DT_BF16 || ad->alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", who, ad->alpha_dt);
-    return HICOM_OK;
-}
-
-inline int seg_adapt_check_weights(const char* who, const SegAdapt* ad) {
-    if (!ad) return HICOM_OK;
-    for (const hicom_seg_adaptor* s : {ad->ak, ad->av})
-        if (s->w0) HICOM_REQUIRE(s->w2_f16 && s->gamma && s->beta && s->alpha, HICOM_EINVAL, "%s: adaptor weights", who);
-    return HICOM_OK;
-}
-
-// y = MLP(x) of the adapted streams over all `tokens` of the call: two launches.  Both adaptors with matching biases: each layer of the
-// two MLPs is one paired launch; otherwise (one adaptor: two launches as well) the single-problem entry point per layer.
-inline int seg_adapt_mlps(const SegAdapt& ad, const void* key_x, const void* ff, long tokens, int E, char* ws, const SegAdaptLayout& l, void* stream) {
-    const hicom_seg_adaptor &k = *ad.ak, &v = *ad.av;
-    const int M = (int)tokens;
-    if (ad.k() && ad.v() && !k.b0 == !v.b0 && !k.b2 == !v.b2) {
-        const int st = hicom_dense16_gemm_pair_fwd(key_x, k.w0, k.b0, ws + l.hid_k, nullptr, ff, v.w0, v.b0, ws + l.hid_v, nullptr, E, E, HICOM_DT_BF16,
-                                                   HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, E, E, 0, stream);
-        if (st != HICOM_OK) return st;
-        return hicom_dense16_gemm_pair_fwd(ws + l.hid_k, k.w2_f16, k.b2, ws + l.ky, nullptr, ws + l.hid_v, v.w2_f16, v.b2, ws + l.vy, nullptr, E, E,
-                                           HICOM_DT_F16, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, E, E, 0, stream);
-    }
-    auto mlp = [&](const hicom_seg_adaptor& a, const void* x, long hid, long y) -> int {
-        const int st = hicom_dense16_gemm_fwd(x, E, a.w0, E, HICOM_DT_BF16, a.b0, HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, ws + hid, E, E, nullptr, 0, nullptr,
-                                              0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
-        if (st != HICOM_OK) return st;
-        return hicom_dense16_gemm_fwd(ws + hid, E, a.w2_f16, E, HICOM_DT_F16, a.b2, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, ws + y, E, E, nullptr, 0, nullptr,
-                                      0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
-    };
-    if (ad.k()) { const int st = mlp(k, key_x, l.hid_k, l.ky); if (st != HICOM_OK) return st; }
-    if (ad.v()) { const int st = mlp(v, ff, l.hid_v, l.vy); if (st != HICOM_OK) return st; }
-    return HICOM_OK;
-}
-
-inline hicom::SegAdaptParams seg_adapt_params(const SegAdapt& ad, const char* ws, const SegAdaptLayout& l) {
-    hicom::SegAdaptParams p;
-    p.ky = ad.k() ? (const _Float16*)(ws + l.ky) : nullptr;
-    p.kgamma = (const uint16_t*)ad.ak->gamma; p.kbeta = (const uint16_t*)ad.ak->beta; p.kalpha = ad.ak->alpha;
-    p.vy = ad.v() ? (const _Float16*)(ws + l.vy) : nullptr;
-    p.vgamma = (const uint16_t*)ad.av->gamma; p.vbeta = (const uint16_t*)ad.av->beta; p.valpha = ad.av->alpha;
-    p.alpha_f32 = ad.alpha_dt == HICOM_DT_F32;
-    p.eps = ad.eps;
-    return p;
-}
-
-}  // namespace hicom_host

@@ -658,49 +658,40 @@ def _adapt(args) -> bool:
     return isinstance(args, (CompressorBatchAdaptArgs, CompressorRaggedAdaptArgs))
 
 
-def compressor_batch_workspace(args) -> int:
-    """args: CompressorBatchArgs or CompressorBatchAdaptArgs (as for compressor_batch_fwd)."""
-    L = lib()
-    n = (L.hicom_compressor_batch_adapt_workspace_bytes if _adapt(args) else L.hicom_compressor_batch_workspace_bytes)(C.byref(args))
+def _seg_call(args, step, fn, py_name=None):
+    """hicom_compressor_<step>_<fn> on a plain argument block, hicom_compressor_<step>_adapt_<fn> on one of the adaptor recipe; returns its
+    result, raises for a negative one.  With `py_name` (the workspace functions) HICOM_EUNSUP, a limit of the step's kernels, becomes
+    NotImplementedError under that name."""
+    sym = f"hicom_compressor_{step}_{'adapt_' if _adapt(args) else ''}{fn}"
+    n = getattr(lib(), sym)(C.byref(args))
     if n < 0:
         msg = lib().hicom_last_error().decode(errors="replace")
-        if n == -2:                      # HICOM_EUNSUP: a limit of the batched kernels
-            raise NotImplementedError(f"forward_batch: {msg}")
-        raise HicomNativeError(f"hicom_compressor_batch_workspace_bytes failed ({n}): {msg}")
-    return n
+        if n == -2 and py_name:
+            raise NotImplementedError(f"{py_name}: {msg}")
+        raise HicomNativeError(f"{f'hicom_compressor_{step}_{fn}' if py_name else sym} failed ({n}): {msg}")
+    return int(n)
+
+
+def compressor_batch_workspace(args) -> int:
+    """args: CompressorBatchArgs or CompressorBatchAdaptArgs (as for compressor_batch_fwd)."""
+    return _seg_call(args, "batch", "workspace_bytes", "forward_batch")
 
 
 def compressor_batch_fwd(args):
-    if _adapt(args):
-        _check(lib().hicom_compressor_batch_adapt_fwd(C.byref(args)), "hicom_compressor_batch_adapt_fwd")
-    else:
-        _check(lib().hicom_compressor_batch_fwd(C.byref(args)), "hicom_compressor_batch_fwd")
+    _seg_call(args, "batch", "fwd")
 
 
 def compressor_ragged_workspace(args) -> int:
     """args: CompressorRaggedArgs or CompressorRaggedAdaptArgs (as for compressor_ragged_prepare / _fwd)."""
-    L = lib()
-    n = (L.hicom_compressor_ragged_adapt_workspace_bytes if _adapt(args) else L.hicom_compressor_ragged_workspace_bytes)(C.byref(args))
-    if n < 0:
-        msg = lib().hicom_last_error().decode(errors="replace")
-        if n == -2:                      # HICOM_EUNSUP: a limit of the ragged kernels
-            raise NotImplementedError(f"forward_ragged: {msg}")
-        raise HicomNativeError(f"hicom_compressor_ragged_workspace_bytes failed ({n}): {msg}")
-    return int(n)
+    return _seg_call(args, "ragged", "workspace_bytes", "forward_ragged")
 
 
 def compressor_ragged_prepare(args):
-    if _adapt(args):
-        _check(lib().hicom_compressor_ragged_adapt_prepare(C.byref(args)), "hicom_compressor_ragged_adapt_prepare")
-    else:
-        _check(lib().hicom_compressor_ragged_prepare(C.byref(args)), "hicom_compressor_ragged_prepare")
+    _seg_call(args, "ragged", "prepare")
 
 
 def compressor_ragged_fwd(args):
-    if _adapt(args):
-        _check(lib().hicom_compressor_ragged_adapt_fwd(C.byref(args)), "hicom_compressor_ragged_adapt_fwd")
-    else:
-        _check(lib().hicom_compressor_ragged_fwd(C.byref(args)), "hicom_compressor_ragged_fwd")
+    _seg_call(args, "ragged", "fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -2,40 +2,23 @@
 
 The reference stacks whatever a batch holds -- single images, clips of 4, 8 or 16 frames, the odd 1-frame "video" -- into one
 [(b t), H, W, E] tensor, splits it by image_video_split_size and runs its projector once per item (hicom_arch.py:146-180).  Here the
-stacked tensor is read in place by ONE C call and the twelve launches of the batched step (batch.py), whatever B and the mix are.
-The two released recipes only, as there: `local43_global32`, and `local43_adaptkv_global32` with the adaptor MLPs as two more launches
-over the whole stack (fourteen); everything else raises NotImplementedError.
-
-Plans (filled argument block, the host item descriptors and the workspace, whose head holds the device tables) are cached on the
-module by (split_sizes, modals, grid, ...), like batch.py's; the input / output pointers are patched per call.
+stacked tensor is read in place by ONE C call and the twelve launches of the batched step (fourteen for `local43_adaptkv_global32`),
+whatever B and the mix are.  Scope, plan and plan cache are segments.py's, shared with forward_batch.  Plans are keyed by (split_sizes,
+modals, grid, ...); a ragged plan also holds the host item descriptors, and the head of its workspace holds the device tables.
 
 `plan_tables` restates the table arithmetic of hicom_compressor_ragged_prepare in Python: forward_ragged takes the items' row counts
 from it, and the tests hold the device's table region against it."""
 from __future__ import annotations
 
-import math
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import engine
 from . import native as nv
-from .batch import fill_adaptors, refresh_adaptors, seg_recipe
+from . import segments as seg
 
-_MAX_PLANS = 16
-MAX_CHUNKS = 64          # work units per item (csrc/segment_item.hpp: kSegMaxChunks)
-
-
-class _RaggedPlan:
-    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes")
-
-    def __init__(self, args, items, ws, rows, hidden):
-        # args / io / adapt_bytes: as batch._BatchPlan's
-        self.args, self.items, self.ws, self.rows, self.hidden = args, items, ws, rows, hidden
-        self.io = getattr(args, "base", args)
-        self.sig = self.fresh = self.refresh = self.keep = self.tables = None
-        self.hits = self.adapt_bytes = 0
+MAX_CHUNKS = 64          # work units per item (csrc/segment_host.hpp: kSegMaxChunks)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -86,133 +69,58 @@ def table_image(t) -> np.ndarray:
 def _scope(proj, ff, fe, guides, split_sizes, modals, nl):
     """Raises for everything outside the ragged step's scope that does not need the per-item geometry; returns (B, H, W, E,
     split_sizes, modals) with the last two as tuples."""
-    from .projector import _require_bf16_cuda
-    lc, gc = proj.local_compressor, proj.global_compressor
-    if isinstance(ff, dict) or isinstance(fe, dict):
-        raise NotImplementedError("forward_ragged: anyres dict inputs have no ragged path (call forward() per image)")
-    if seg_recipe(proj) is None:
-        raise NotImplementedError("forward_ragged is built for the two release recipes only (local + global compressor, "
-                                  "use_guide='direct', no adaptors but adapt_k / adapt_v on the local stage, no clip scale)")
-    wdt = lc.readout[0].weight.dtype
-    if wdt != torch.bfloat16:
-        raise NotImplementedError(f"forward_ragged: a {wdt} projector; the ragged step takes a bfloat16 module and bfloat16 inputs")
-    if not isinstance(ff, torch.Tensor) or ff.ndim != 4:
-        raise ValueError("forward_ragged: frames_feature is the stacked [sum T_i, H, W, E] tensor")
-    _require_bf16_cuda("frames_feature", ff)
-    Tsum, H, W, E = ff.shape
-    if fe is not None:
-        _require_bf16_cuda("frames_embed", fe)
-        if tuple(fe.shape) != tuple(ff.shape):
-            raise ValueError(f"forward_ragged: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
-    try:
-        split_sizes = tuple(int(t) for t in split_sizes)
-    except TypeError:
-        raise ValueError("forward_ragged: split_sizes is a sequence of positive ints, one per item") from None
-    B = len(split_sizes)
-    if B == 0 or any(t <= 0 for t in split_sizes):
-        raise ValueError(f"forward_ragged: split_sizes is a sequence of positive ints, one per item (got {split_sizes})")
-    if sum(split_sizes) != Tsum:
-        raise ValueError(f"forward_ragged: sum(split_sizes) = {sum(split_sizes)} vs {Tsum} stacked frames")
-    modals = (modals,) * B if isinstance(modals, str) else tuple(modals)
-    if len(modals) != B:
-        raise ValueError(f"forward_ragged: {len(modals)} modals for {B} items (one string, or one per item)")
-    if any(m not in ("image", "video") for m in modals):
-        raise ValueError(f"forward_ragged: modals are 'image' or 'video' (got {modals})")
-    if not isinstance(guides, torch.Tensor) or tuple(guides.shape) != (B, E):
-        raise ValueError(f"forward_ragged: guide_embeds is [B, E] = [{B}, {E}], one instruction per item "
-                         f"(got {None if guides is None else tuple(guides.shape)})")
-    _require_bf16_cuda("guide_embeds", guides)
-    if nl is not None:
-        _require_bf16_cuda("image_newline", nl)
+    def count_items():
+        nonlocal split_sizes, modals
+        try:
+            split_sizes = tuple(int(t) for t in split_sizes)
+        except TypeError:
+            raise ValueError("forward_ragged: split_sizes is a sequence of positive ints, one per item") from None
+        B = len(split_sizes)
+        if B == 0 or any(t <= 0 for t in split_sizes):
+            raise ValueError(f"forward_ragged: split_sizes is a sequence of positive ints, one per item (got {split_sizes})")
+        if sum(split_sizes) != ff.shape[0]:
+            raise ValueError(f"forward_ragged: sum(split_sizes) = {sum(split_sizes)} vs {ff.shape[0]} stacked frames")
+        modals = (modals,) * B if isinstance(modals, str) else tuple(modals)
+        if len(modals) != B:
+            raise ValueError(f"forward_ragged: {len(modals)} modals for {B} items (one string, or one per item)")
+        if any(m not in ("image", "video") for m in modals):
+            raise ValueError(f"forward_ragged: modals are 'image' or 'video' (got {modals})")
+        return B
+    B, E = seg.check_inputs("forward_ragged", "ragged", proj, ff, fe, guides, nl, 4, "the stacked [sum T_i, H, W, E] tensor", count_items)
     for i, (t, m) in enumerate(zip(split_sizes, modals)):
         if m == "image" and t != 1:
             raise ValueError(f"forward_ragged: item {i}: image modality expects a single frame (T = {t})")
-    return B, H, W, E, split_sizes, modals
+    return B, ff.shape[1], ff.shape[2], E, split_sizes, modals
 
 
 def item_descriptors(proj, split_sizes, modals, H, W, has_newline):
     """The fields of hicom_ragged_item per item, (T, kt, nl_group, nl_count, nl_first, nl_step, n_global_rows), and the spatial
     window ks: LocalCompressor.tilings and HIComProjector._layout on every item alone."""
-    lc, gc = proj.local_compressor, proj.global_compressor
     items, ks = [], None
     for i, (T, modal) in enumerate(zip(split_sizes, modals)):
-        try:
-            tiles = lc.tilings(T, H, W, modal)
-        except RuntimeError as e:
-            raise NotImplementedError(f"forward_ragged: item {i}: the windows must partition the grid exactly ({e})") from None
-        if any(a.nwin * a.k != a.n or a.nfull != a.nwin for a in tiles):
-            raise NotImplementedError(f"forward_ragged: item {i}: the windows must partition the grid exactly (T={T} H={H} W={W}, windows "
-                                      f"{tiles[0].k}x{tiles[1].k}x{tiles[2].k}); such items go through forward()")
-        if tiles[1].k != tiles[2].k:
-            raise NotImplementedError("forward_ragged: square spatial windows only")
-        at, ay, ax = tiles
+        at, ay, ax = seg.exact_tilings("forward_ragged", proj, T, H, W, modal, f"item {i}: ")
         ks = ay.k
         lay = proj._layout((at.nwin, ay.nwin, ax.nwin), modal, has_newline, False)
         nlr = lay.newline_rows
-        items.append((T, at.k, lay.nl_group, len(nlr), nlr[0] if nlr else 0, (nlr[1] - nlr[0]) if len(nlr) > 1 else 1, gc.num_queries))
+        items.append((T, at.k, lay.nl_group, len(nlr), nlr[0] if nlr else 0, (nlr[1] - nlr[0]) if len(nlr) > 1 else 1,
+                      proj.global_compressor.num_queries))
     return items, ks
 
 
 def _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, stream):
-    from .projector import _linear_params
-    lc, gc = proj.local_compressor, proj.global_compressor
     desc, ks = item_descriptors(proj, split_sizes, modals, H, W, nl is not None)
-    B = len(desc)
-    att = gc.attn_layer
-    hidden = lc.readout[2].out_features
-    items = (nv.RaggedItem * B)(*[nv.RaggedItem(*d) for d in desc])
-    adapt = seg_recipe(proj) == "adaptkv"
-    args = nv.CompressorRaggedAdaptArgs() if adapt else nv.CompressorRaggedArgs()
-    a = args.base if adapt else args
-    a.B, a.H, a.W, a.E, a.hidden = B, H, W, E, hidden
-    a.ks, a.nh = ks, att.num_heads
-    a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
-    a.chunks = int(chunks or 0)
-    a.items = items
-    keep = []
-
-    def ptr(t):
-        if t is None:
-            return None
-        keep.append(t)
-        return t.data_ptr()
-    w0h, w2h = lc.readout_f16()
-    a.lw0_f16, a.lw2_f16 = ptr(w0h), ptr(w2h)
-    a.lb0, a.lb2 = ptr(_linear_params(lc.readout[0])[1]), ptr(_linear_params(lc.readout[2])[1])
-    for name, lin in (("q", att.q_proj), ("k", att.k_proj), ("v", att.v_proj), ("o", att.out_proj)):
-        w, b = _linear_params(lin)
-        setattr(a, "w" + name, ptr(w))
-        if name != "k":                      # b_k shifts every logit of a row: softmax cancels it
-            setattr(a, "b" + name, ptr(b))
-    for name, lin in (("0", gc.readout[0]), ("2", gc.readout[2])):
-        w, b = _linear_params(lin)
-        setattr(a, "gw" + name, ptr(w))
-        setattr(a, "gb" + name, ptr(b))
-    t_max = max(split_sizes)
-    if gc.use_pos_emb:
-        pe, kpe, cap = gc.pos_and_kpe(t_max, H, W, dev)
-        a.pe, a.kpe, a.P = ptr(pe), ptr(kpe), pe.shape[0]
-        a.t_index0, a.y_index0, a.x_index0 = 0, cap, cap + H
-    a.out_dt = nv.DT_F32 if out_dtype == torch.float32 else nv.DT_BF16
-    a.ldo = hidden
+    items = (nv.RaggedItem * len(desc))(*[nv.RaggedItem(*d) for d in desc])
+    args, a, keep, ptr = seg.new_args(proj, nv.CompressorRaggedArgs, nv.CompressorRaggedAdaptArgs)
+    a.B, a.E, a.ks, a.items = len(desc), E, ks, items
+    refresh = seg.fill_common(a, proj, max(split_sizes), H, W, dev, out_dtype, chunks, ptr)
     a.stream = stream
-    if adapt:
-        fill_adaptors(args, lc, "forward_ragged", ptr)
-    nbytes = nv.compressor_ragged_workspace(args)      # (NotImplementedError for a limit of the kernels)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+    if args is not a:
+        seg.fill_adaptors(args, proj.local_compressor, "forward_ragged", ptr)
+    ws, adapt_bytes = seg.alloc_workspace(args, a, nv.compressor_ragged_workspace, dev)
     nv.compressor_ragged_prepare(args)                 # the device tables, once per plan (synchronises the stream)
     tables = plan_tables(desc, H, W, ks, torch.cuda.get_device_properties(dev).multi_processor_count, a.chunks)
-    plan = _RaggedPlan(args, items, ws, tables.rows, hidden)
-    plan.keep, plan.tables = keep, tables
-    plan.adapt_bytes = nbytes - nv.compressor_ragged_workspace(a) if adapt else 0
-
-    def refresh():
-        lc.readout_f16()
-        refresh_adaptors(lc)
-        if gc.use_pos_emb:
-            gc.pos_and_kpe(t_max, H, W, dev)
-    plan.refresh = refresh
+    plan = seg.SegPlan(args, ws, tables.rows, a.hidden, items, tables)
+    plan.keep, plan.adapt_bytes, plan.refresh = keep, adapt_bytes, refresh
     return plan
 
 
@@ -228,27 +136,8 @@ def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
     out_dtype = _out_dtype(proj)
     stream = torch.cuda.current_stream(dev).cuda_stream
     key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
-           seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
-    plans = proj.__dict__.setdefault("_ragged_plans", {})
-    plan = plans.get(key)
-    sig = engine.plan_sig(proj)
-    if plan is not None and plan.sig == sig:
-        fresh = engine.content_sig(proj)
-        if plan.fresh != fresh:              # the weights changed in place: rebuild the weight-derived tables into their buffers
-            plan.refresh()
-            sig = engine.plan_sig(proj)
-            plan.fresh = fresh
-    if plan is not None and plan.sig != sig:
-        plans.pop(key)
-        plan = None
-    if plan is None:
-        plan = _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, stream)
-        plan.sig = engine.plan_sig(proj)     # (building may have (re)built the cached positional tables)
-        plan.fresh = engine.content_sig(proj)
-        if len(plans) >= _MAX_PLANS:
-            plans.pop(next(iter(plans)))
-        plans[key] = plan
-    plan.hits += 1
+           seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
+    plan = seg.cached_plan(proj, "_ragged_plans", key, lambda: _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, stream))
     a = plan.io
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
     a.ff = ff.data_ptr()

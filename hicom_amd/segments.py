@@ -1,0 +1,201 @@
+"""What HIComProjector.forward_batch (batch.py) and forward_ragged (ragged.py) share on the Python side: the scope rule, the input checks,
+the plan (filled argument block + the workspace it owns), the fields of the argument block that come from the module alone, and the
+plan-cache protocol.  The two modules keep what depends on how items are described: one (T, H, W) shape and B, or split sizes, modals and
+the table arithmetic.
+
+Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`: at most MAX_PLANS each), like engine.run_dense's; the
+input / output pointers are patched per call."""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import engine
+from . import native as nv
+
+MAX_PLANS = 16
+
+
+class SegPlan:
+    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes")
+
+    def __init__(self, args, ws, rows, hidden, items=None, tables=None):
+        # args: the block the entry point takes; io: the plain block inside it (args itself for the plain recipe), whose input / output
+        # pointers are patched per call; adapt_bytes: the adaptor regions behind the plain workspace layout (0 for the plain recipe);
+        # items / tables: the host item descriptors and the table arithmetic of a ragged plan, None for a batch plan
+        self.args, self.ws, self.rows, self.hidden, self.items, self.tables = args, ws, rows, hidden, items, tables
+        self.io = getattr(args, "base", args)
+        self.sig = self.fresh = self.refresh = self.keep = None
+        self.hits = self.adapt_bytes = 0
+
+
+def seg_recipe(proj):
+    """The recipe of the batched / ragged step a projector runs: "plain" (local43_global32), "adaptkv" (adapt_k and / or adapt_v on the
+    local compressor), or None for everything outside their scope."""
+    lc, gc = proj.local_compressor, proj.global_compressor
+    if (lc is None or gc is None or lc.use_guide != "direct" or gc.use_guide != "direct" or not lc.queries_native or not gc.is_plain
+            or proj.local_use_clip_scale or proj.global_use_clip_scale):
+        return None
+    return "adaptkv" if (lc.adapt_k or lc.adapt_v) else "plain"
+
+
+def adaptor_streams(lc):
+    """(field of the argument block, MLP, LayerNorm, alpha) per adapted stream of the local compressor."""
+    return [s for on, s in ((lc.adapt_k, ("ak", lc.k_proj, lc.k_norm, lc.k_alpha)), (lc.adapt_v, ("av", lc.v_proj, lc.v_norm, lc.v_alpha))) if on]
+
+
+def fill_adaptors(a, lc, what, ptr):
+    """The adaptor descriptors of a Compressor{Batch,Ragged}AdaptArgs block from the local compressor's parameters; `ptr` registers a
+    tensor with the plan and returns its address.  The fp16 copy of the second layer's weight is the cached one of
+    injector._f16_weight (range-checked when first built, refreshed in place: the plan holds its address)."""
+    from . import injector as inj
+    from .projector import _linear_params, _require_bf16_cuda
+    for field, mlp, norm, alpha in adaptor_streams(lc):
+        d = getattr(a, field)
+        (w0, b0), (w2, b2) = _linear_params(mlp[0]), _linear_params(mlp[2])
+        if w0.shape[0] % 64 or w0.shape[1] % 64 or w2.shape[0] % 64 or w0.shape != w2.shape:
+            raise NotImplementedError(f"{what}: adaptor widths must be multiples of 64")
+        _require_bf16_cuda("adaptor norm", norm.weight)
+        d.w0, d.b0 = ptr(w0), ptr(b0)
+        d.w2_f16, d.b2 = ptr(inj._f16_weight(mlp[2])), ptr(b2)
+        d.gamma, d.beta, d.alpha = ptr(norm.weight.detach()), ptr(norm.bias.detach()), ptr(alpha.detach())
+        a.alpha_dt, a.eps = nv._dt(alpha), norm.eps
+
+
+def refresh_adaptors(lc):
+    """Rebuilds, in place, the cached fp16 weight copies the adaptor descriptors point at (a no-op while the weights have not moved)."""
+    from . import injector as inj
+    for _, mlp, _, _ in adaptor_streams(lc):
+        inj._f16_weight(mlp[2])
+
+
+def check_inputs(what, step, proj, ff, fe, guides, nl, ndim, ff_layout, count_items):
+    """The input checks of `what` ("forward_batch" / "forward_ragged", the `step` "batched" / "ragged"): raises for a module or tensors
+    outside the step's scope.  frames_feature has `ndim` axes (`ff_layout` says which); count_items() is called once frames_feature and
+    frames_embed have passed, checks what describes the items and returns B.  Returns (B, E)."""
+    from .projector import _require_bf16_cuda
+    if isinstance(ff, dict) or isinstance(fe, dict):
+        raise NotImplementedError(f"{what}: anyres dict inputs have no {step} path (call forward() per image)")
+    if seg_recipe(proj) is None:
+        raise NotImplementedError(f"{what} is built for the two release recipes only (local + global compressor, "
+                                  "use_guide='direct', no adaptors but adapt_k / adapt_v on the local stage, no clip scale)")
+    wdt = proj.local_compressor.readout[0].weight.dtype
+    if wdt != torch.bfloat16:
+        raise NotImplementedError(f"{what}: a {wdt} projector; the {step} step takes a bfloat16 module and bfloat16 inputs")
+    if not isinstance(ff, torch.Tensor) or ff.ndim != ndim:
+        raise ValueError(f"{what}: frames_feature is {ff_layout}")
+    _require_bf16_cuda("frames_feature", ff)
+    E = ff.shape[-1]
+    if fe is not None:
+        _require_bf16_cuda("frames_embed", fe)
+        if tuple(fe.shape) != tuple(ff.shape):
+            raise ValueError(f"{what}: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
+    B = count_items()
+    if not isinstance(guides, torch.Tensor) or tuple(guides.shape) != (B, E):
+        raise ValueError(f"{what}: guide_embeds is [B, E] = [{B}, {E}], one instruction per item "
+                         f"(got {None if guides is None else tuple(guides.shape)})")
+    _require_bf16_cuda("guide_embeds", guides)
+    if nl is not None:
+        _require_bf16_cuda("image_newline", nl)
+    return B, E
+
+
+def exact_tilings(what, proj, T, H, W, modal, item=""):
+    """LocalCompressor.tilings of one item shape; raises unless the windows partition the grid exactly, with square spatial windows."""
+    try:
+        tiles = proj.local_compressor.tilings(T, H, W, modal)
+    except RuntimeError as e:
+        raise NotImplementedError(f"{what}: {item}the windows must partition the grid exactly ({e})") from None
+    if any(a.nwin * a.k != a.n or a.nfull != a.nwin for a in tiles):
+        raise NotImplementedError(f"{what}: {item}the windows must partition the grid exactly (T={T} H={H} W={W}, windows "
+                                  f"{tiles[0].k}x{tiles[1].k}x{tiles[2].k}); such items go through forward()")
+    if tiles[1].k != tiles[2].k:
+        raise NotImplementedError(f"{what}: square spatial windows only")
+    return tiles
+
+
+def new_args(proj, plain, adapt):
+    """(the block the entry point takes, the plain block inside it, keep, ptr) for the module's recipe: an instance of `adapt` (plain block
+    first) for the adaptor recipe, of `plain` otherwise.  ptr(t) registers a tensor with the plan (`keep`) and returns its address."""
+    args = adapt() if seg_recipe(proj) == "adaptkv" else plain()
+    keep = []
+
+    def ptr(t):
+        if t is None:
+            return None
+        keep.append(t)
+        return t.data_ptr()
+    return args, getattr(args, "base", args), keep, ptr
+
+
+def fill_common(a, proj, T_for_pos, H, W, dev, out_dtype, chunks, ptr):
+    """The fields of a plain argument block that the module alone decides (everything but the items' shapes, their packed-row layout, the
+    workspace and the per-call pointers); T_for_pos: the frames the positional tables must cover.  Returns the plan's refresh(): rebuilds,
+    in place, the weight-derived tables whose addresses the block holds."""
+    from .projector import _linear_params
+    lc, gc = proj.local_compressor, proj.global_compressor
+    att = gc.attn_layer
+    a.H, a.W, a.hidden, a.nh = H, W, lc.readout[2].out_features, att.num_heads
+    a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
+    a.chunks = int(chunks or 0)
+    w0h, w2h = lc.readout_f16()
+    a.lw0_f16, a.lw2_f16 = ptr(w0h), ptr(w2h)
+    a.lb0, a.lb2 = ptr(_linear_params(lc.readout[0])[1]), ptr(_linear_params(lc.readout[2])[1])
+    for name, lin in (("q", att.q_proj), ("k", att.k_proj), ("v", att.v_proj), ("o", att.out_proj)):
+        w, b = _linear_params(lin)
+        setattr(a, "w" + name, ptr(w))
+        if name != "k":                      # b_k shifts every logit of a row: softmax cancels it
+            setattr(a, "b" + name, ptr(b))
+    for name, lin in (("0", gc.readout[0]), ("2", gc.readout[2])):
+        w, b = _linear_params(lin)
+        setattr(a, "gw" + name, ptr(w))
+        setattr(a, "gb" + name, ptr(b))
+    if gc.use_pos_emb:
+        pe, kpe, cap = gc.pos_and_kpe(T_for_pos, H, W, dev)
+        a.pe, a.kpe, a.P = ptr(pe), ptr(kpe), pe.shape[0]
+        a.t_index0, a.y_index0, a.x_index0 = 0, cap, cap + H
+    a.out_dt = nv.DT_F32 if out_dtype == torch.float32 else nv.DT_BF16
+    a.ldo = a.hidden
+
+    def refresh():
+        lc.readout_f16()
+        refresh_adaptors(lc)
+        if gc.use_pos_emb:
+            gc.pos_and_kpe(T_for_pos, H, W, dev)
+    return refresh
+
+
+def alloc_workspace(args, a, workspace_bytes, dev):
+    """Allocates the workspace `workspace_bytes(args)` asks for (NotImplementedError for a limit of the kernels) and enters it into the plain
+    block `a`; returns (workspace, bytes of the adaptor regions behind the plain layout)."""
+    nbytes = workspace_bytes(args)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+    return ws, (nbytes - workspace_bytes(a) if args is not a else 0)
+
+
+def cached_plan(proj, store, key, build):
+    """The plan of `key` in the module's store `store` ("_batch_plans" / "_ragged_plans"), built by build() when there is none or the
+    module's parameters were replaced; weights changed in place are followed by the plan's refresh().  Counts the use."""
+    plans = proj.__dict__.setdefault(store, {})
+    plan = plans.get(key)
+    sig = engine.plan_sig(proj)
+    if plan is not None and plan.sig == sig:
+        fresh = engine.content_sig(proj)
+        if plan.fresh != fresh:              # the weights changed in place: rebuild the weight-derived tables into their buffers
+            plan.refresh()
+            sig = engine.plan_sig(proj)
+            plan.fresh = fresh
+    if plan is not None and plan.sig != sig:
+        plans.pop(key)
+        plan = None
+    if plan is None:
+        plan = build()
+        plan.sig = engine.plan_sig(proj)     # (building may have (re)built the cached positional tables)
+        plan.fresh = engine.content_sig(proj)
+        if len(plans) >= MAX_PLANS:
+            plans.pop(next(iter(plans)))
+        plans[key] = plan
+    plan.hits += 1
+    return plan

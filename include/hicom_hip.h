@@ -847,9 +847,10 @@ int hicom_compressor_fwd(const hicom_compressor_args* args);
 
 /* ---- batched compressor step: B items of ONE shape in one call --------------------------------------------------------
  * What hicom/model/hicom_arch.py:166-178 does with one projector call per item of a batch (all items of equal length), for the
- * release recipe only (local + global compressor, use_guide = "direct", no adaptors, no clip-scale, bf16): twelve launches on
- * `stream` whatever B is.  Item b of the output equals hicom_compressor_fwd on item b alone (same math; the window
- * contexts and the hidden layer of the local readout pass through fp16 planes as there).
+ * release recipe only (local + global compressor, use_guide = "direct", no clip-scale, bf16; no adaptors here -- the k / v adaptors
+ * of the local stage go through hicom_compressor_batch_adapt_* below, fourteen launches): twelve launches on `stream` whatever B
+ * is.  Item b of the output equals hicom_compressor_fwd on item b alone (same math; the window contexts and the hidden
+ * layer of the local readout pass through fp16 planes as there).
  *   ff, fe   : bf16 [B, T, H, W, E] (fe NULL: the local keys are ff); guide bf16 [B, E], one instruction per item
  *   kt, ks   : local window (kt = 1 for images); T % kt == H % ks == W % ks == 0, kt ks ks <= 64; E == 1152, nh <= 16 heads,
  *              hidden % 64 == 0; HICOM_EUNSUP otherwise
