@@ -1,0 +1,91 @@
+"""HIComProjector.forward_multi_guide: ONE clip, Q instructions through hicom_compressor_multiguide_fwd (csrc/multi_guide.hip).
+
+The reference's Video-MME driver asks every question of a video with its own projector run over the same video tensor
+(hicom/eval/video/inference_video_mcqa_videomme.py:268-303).  The guide is only the query of the two stages, so here the visual tokens
+are streamed once for all Q guides: the local stage loads each window row once per group of guides, the global stage runs the 9 Q folded
+rows through the many-row stream kernel of the guide-off recipe.  Scope rule, input checks, plan and plan cache are segments.py's, shared
+with forward_batch and forward_ragged; the plain release recipe only.  Plans are keyed by shape, Q included."""
+from __future__ import annotations
+
+import torch
+
+from . import native as nv
+from . import segments as seg
+
+MAX_GUIDES = 32         # 9 heads x 32 guides = 288 folded rows, the row count the many-row stream kernel is proven at
+STORE = "_multi_guide_plans"
+
+
+def _scope(proj, ff, fe, guides, modal, nl):
+    """Raises for everything outside the step's scope; returns (Q, T, H, W, E, tilings)."""
+    what = "forward_multi_guide"
+    if not isinstance(ff, dict) and not isinstance(fe, dict) and seg.seg_recipe(proj) != "plain":
+        raise NotImplementedError(f"{what} is built for the plain release recipe only (local + global compressor, use_guide='direct', no "
+                                  "adaptors, no clip scale); the adaptor recipe and everything else go through forward() per guide")
+
+    def count_guides():
+        E = ff.shape[-1]
+        if not isinstance(guides, torch.Tensor) or guides.ndim != 2 or guides.shape[1] != E:
+            raise ValueError(f"{what}: guide_embeds is [Q, E] = [Q, {E}], one instruction per row "
+                             f"(got {tuple(guides.shape) if isinstance(guides, torch.Tensor) else None})")
+        if not 1 <= guides.shape[0] <= MAX_GUIDES:
+            raise ValueError(f"{what}: Q={guides.shape[0]} guides (1 <= Q <= {MAX_GUIDES} per call)")
+        return guides.shape[0]
+    Q, E = seg.check_inputs(what, "multi-guide", proj, ff, fe, guides, nl, 4, "[T, H, W, E]", count_guides)
+    T, H, W, _ = ff.shape
+    if modal == "image" and T != 1:
+        raise ValueError(f"{what}: image modality expects a single frame [1, H, W, E]")
+    return Q, T, H, W, E, seg.exact_tilings(what, proj, T, H, W, modal)
+
+
+def _build(proj, Q, T, H, W, E, tiles, modal, nl, out_dtype, chunks, dev):
+    gc = proj.global_compressor
+    at, ay, ax = tiles
+    lay = proj._layout((at.nwin, ay.nwin, ax.nwin), modal, nl is not None, False)
+    a = nv.CompressorMultiGuideArgs()
+    keep = []
+
+    def ptr(t):
+        if t is None:
+            return None
+        keep.append(t)
+        return t.data_ptr()
+    a.Q, a.T, a.E, a.kt, a.ks = Q, T, E, at.k, ay.k
+    refresh = seg.fill_common(a, proj, T, H, W, dev, out_dtype, chunks, ptr)
+    a.global_row0 = lay.n_rows
+    a.n_global_rows = gc.num_queries
+    a.item_rows = lay.n_rows + gc.num_queries
+    a.nl_group = lay.nl_group
+    a.nl_count = len(lay.newline_rows)
+    if lay.newline_rows:
+        a.nl_first = lay.newline_rows[0]
+        a.nl_step = lay.newline_rows[1] - lay.newline_rows[0] if len(lay.newline_rows) > 1 else 1
+    ws, _ = seg.alloc_workspace(a, a, nv.compressor_multiguide_workspace, dev)      # (the kernels' limits raise here, in front of any launch)
+    plan = seg.SegPlan(a, ws, a.item_rows, a.hidden)
+    plan.keep, plan.refresh = keep, refresh
+    return plan
+
+
+def run_multi_guide(proj, ff, fe, guides, modal, nl, chunks=None):
+    from .projector import _out_dtype, _refuse_grad
+    Q, T, H, W, E, tiles = _scope(proj, ff, fe, guides, modal, nl)
+    _refuse_grad(proj, "HIComProjector.forward_multi_guide")
+    dev = ff.device
+    ff = ff.contiguous()
+    fe = fe.contiguous() if fe is not None else None
+    guides = guides.contiguous()
+    nl = nl.contiguous() if nl is not None else None
+    out_dtype = _out_dtype(proj)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    key = (Q, T, H, W, E, fe is not None, modal, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0))
+    plan = seg.cached_plan(proj, STORE, key, lambda: _build(proj, Q, T, H, W, E, tiles, modal, nl, out_dtype, chunks, dev))
+    a = plan.io
+    out = torch.empty((Q, plan.rows, plan.hidden), dtype=out_dtype, device=dev)
+    a.ff = ff.data_ptr()
+    a.fe = fe.data_ptr() if fe is not None else None
+    a.guide = guides.data_ptr()
+    a.newline = nl.data_ptr() if (nl is not None and a.nl_count > 0) else None
+    a.out = out.data_ptr()
+    a.stream = stream
+    nv.compressor_multiguide_fwd(plan.args)
+    return out

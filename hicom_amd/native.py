@@ -44,6 +44,7 @@ EXPORTS = (
     "hicom_compressor_ragged_fwd", "hicom_compressor_ragged_workspace_bytes", "hicom_compressor_ragged_prepare",
     "hicom_compressor_batch_adapt_fwd", "hicom_compressor_batch_adapt_workspace_bytes",
     "hicom_compressor_ragged_adapt_fwd", "hicom_compressor_ragged_adapt_workspace_bytes", "hicom_compressor_ragged_adapt_prepare",
+    "hicom_compressor_multiguide_fwd", "hicom_compressor_multiguide_workspace_bytes",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -206,6 +207,12 @@ class CompressorRaggedAdaptArgs(C.Structure):
     _fields_ = [("base", CompressorRaggedArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
 
 
+class CompressorMultiGuideArgs(C.Structure):
+    """hicom_compressor_multiguide_args (include/hicom_hip.h): the fields of hicom_compressor_batch_args with Q guides of ONE clip in the
+    place of B items -- field order and types must match the header."""
+    _fields_ = [(("Q" if name == "B" else name), ctype) for name, ctype in CompressorBatchArgs._fields_]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -317,6 +324,8 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_adapt_fwd.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
     L.hicom_compressor_ragged_adapt_prepare.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
     L.hicom_compressor_ragged_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
+    L.hicom_compressor_multiguide_fwd.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
+    L.hicom_compressor_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -329,6 +338,7 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_batch_adapt_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_adapt_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_multiguide_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -692,6 +702,14 @@ def compressor_ragged_prepare(args):
 
 def compressor_ragged_fwd(args):
     _seg_call(args, "ragged", "fwd")
+
+
+def compressor_multiguide_workspace(args: CompressorMultiGuideArgs) -> int:
+    return _seg_call(args, "multiguide", "workspace_bytes", "forward_multi_guide")
+
+
+def compressor_multiguide_fwd(args: CompressorMultiGuideArgs):
+    _seg_call(args, "multiguide", "fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -820,6 +820,7 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_shard_plans", None)
         self.__dict__.pop("_batch_plans", None)
         self.__dict__.pop("_ragged_plans", None)
+        self.__dict__.pop("_multi_guide_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1088,6 +1089,23 @@ class HIComProjector(nn.Module):
         be expected here too: one to three small items are probably faster through a loop of forward()."""
         from . import ragged
         return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
+
+    def forward_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None):
+        """ONE image or clip, Q instructions in one native call: frames_feature / frames_embed bf16 [T, H, W, E] as for forward()
+        (frames_embed may be None), guide_embeds bf16 [Q, E], 1 <= Q <= 32 -- the questions a Video-MME style loop asks about one video
+        (reference inference_video_mcqa_videomme.py:268-303).  Returns [Q, rows, hidden]; out[q] is laid out as forward(frames_feature,
+        frames_embed, guide_embeds[q], modal, image_newline) and equals it to the kernels' rounding.  The visual tokens are streamed
+        once for all guides (the global stage: once per 32 folded rows, so Q <= 3 is a single pass); the launch count does not depend
+        on Q (csrc/multi_guide.hip).
+        The plain release recipe only (local + global compressor, use_guide="direct", no adaptors, no clip scale, bf16 module and
+        inputs, exact window partition): everything else raises NotImplementedError / ValueError in front of the first launch.
+        Inference only: with autograd on and trainable parameters it raises.
+        `chunks`: token chunks of the global stream (None: the stream kernel's own choice).
+        Which path when (DESIGN.md §3.8, 27 x 27 grid): the crossover against a loop of forward() is Q = 3 -- 230 against 226 us on a
+        64-frame clip, 133 against 136 us on 8 frames.  One or two guides belong to forward() (Q = 1: 178 against 77 us, the step is a
+        thirteen-launch sequence); from four guides up this call wins, 1.2 x at Q = 6 and 1.75 x at Q = 16 on 64 frames."""
+        from . import multi_guide
+        return multi_guide.run_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
 
     def forward_stepwise(self, frames_feature, frames_embed, guide_embed, modal, image_newline=None):
         """Same result, one C-ABI call per operator (anyres dict inputs; also the cross-check of the

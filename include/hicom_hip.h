@@ -979,6 +979,48 @@ int64_t hicom_compressor_ragged_adapt_workspace_bytes(const hicom_compressor_rag
 int hicom_compressor_ragged_adapt_prepare(const hicom_compressor_ragged_adapt_args* args);
 int hicom_compressor_ragged_adapt_fwd(const hicom_compressor_ragged_adapt_args* args);
 
+/* ---- multi-guide compressor step: ONE clip, Q instructions, the tokens read once ------------------------------------
+ * What hicom/eval/video/inference_video_mcqa_videomme.py:268-303 does with one projector call per question on the same video tensor.
+ * The guide enters both stages only as a query, so Q guides cost one pass over the tokens plus Q times the window-sized work.  The
+ * plain release recipe only (no adaptors), bf16; a launch sequence on `stream` whose length does not depend on Q.  Guide q of the
+ * output equals hicom_compressor_fwd with guide row q alone to the kernels' rounding.
+ *   ff, fe   : bf16 [T, H, W, E] (fe NULL: the local keys are ff); guide bf16 [Q, E], 1 <= Q <= 32
+ *   kt, ks   : local window; T % kt == H % ks == W % ks == 0, kt ks ks <= 64; E == 1152, nh <= 16 heads, hidden % 64 == 0;
+ *              HICOM_EUNSUP otherwise
+ *   pe, kpe  : the tables of hicom_compressor_args, both NULL = no pos-emb
+ *   chunks   : token chunks (workgroups per 32-row pass) of the global stream, 0 = hicom_global_stream_nparts; clamped to the
+ *              16-token tiles of the clip and to 256
+ *   out      : [Q, item_rows, ldo] of out_dt (bf16 | f32); the packed-row layout integers are those of hicom_compressor_batch_args
+ *              and hold for every guide: local tokens with a newline gap after every nl_group of them, then n_global_rows identical
+ *              copies of the guide's global token
+ *   ws       : hicom_compressor_multiguide_workspace_bytes(args) bytes (depends on the shape, Q and chunks), 256-byte aligned, nothing
+ *              to zero; not shared between concurrently running calls
+ * hicom_compressor_multiguide_fwd only launches: no copy, no synchronisation, no allocation. */
+typedef struct hicom_compressor_multiguide_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t Q, T, H, W, E, hidden, kt, ks, nh, P;
+    float l_scale;
+    int32_t chunks;
+    const void *lw0_f16, *lb0, *lw2_f16, *lb2;      /* local readout: fp16 copies of the weights, bf16 biases */
+    const void *wq, *bq, *wk, *wv, *bv, *wo, *bo;   /* global attention, bf16 */
+    const void *gw0, *gb0, *gw2, *gb2;              /* global readout, bf16 */
+    const float* pe;
+    const float* kpe;
+    int32_t t_index0, y_index0, x_index0, out_dt;
+    void* out;
+    int64_t ldo, item_rows, global_row0;
+    int32_t n_global_rows, nl_group, nl_count, reserved_;
+    int64_t nl_first, nl_step;
+    const void* newline;
+    void* ws;
+    int64_t ws_bytes;
+    void* stream;
+} hicom_compressor_multiguide_args;
+int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compressor_multiguide_args* args);
+int hicom_compressor_multiguide_fwd(const hicom_compressor_multiguide_args* args);
+
 #ifdef __cplusplus
 }
 #endif
