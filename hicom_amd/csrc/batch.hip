@@ -84,19 +84,9 @@ __global__ __launch_bounds__(256) void batch_merge_kernel(BatchMergeParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Placement of every item's packed rows (segment_item.hpp: place_row): grid = B * item_rows, one output row per workgroup.
+// Placement of every item's packed rows (segment_item.hpp: place_equal_row): grid = B * item_rows, one output row per workgroup.
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct BatchPlaceParams {
-    SegPlaceParams c;
-    int wpi, nl_group, nl_count;
-    long item_rows, global_row0, nl_first, nl_step, ldo;
-};
-
-__global__ __launch_bounds__(128) void batch_place_kernel(BatchPlaceParams p) {
-    const long row = blockIdx.x;
-    const long item = row / p.item_rows, r = row - item * p.item_rows;
-    place_row(p.c, r, row * p.ldo, item, item * p.wpi, p.nl_group, p.nl_count, p.global_row0, p.nl_first, p.nl_step);
-}
+__global__ __launch_bounds__(128) void batch_place_kernel(EqualPlaceParams p) { place_equal_row(p); }
 
 }  // namespace hicom
 
@@ -130,14 +120,14 @@ BatchLayout batch_layout(const hicom_compressor_batch_args* a, const SegAdapt* a
     l.chunks = batch_chunks(a);
     l.wpi = (a->T / a->kt) * (a->H / a->ks) * (a->W / a->ks);
     l.score_stride = (N + 15) / 16 * 16;
-    l.s = seg_layout(a, ad, SegTotals{B * 16 * l.score_stride, B * l.chunks, B * l.wpi, B * N}, 0);
+    l.s = seg_layout(a, ad, SegTotals{B * 16 * l.score_stride, B * l.chunks, B * l.wpi, B * N, B * a->nh, B * l.chunks * 16, 0}, 0);
     return l;
 }
 
 int batch_check(const hicom_compressor_batch_args* a, const SegAdapt* ad) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_batch: NULL arguments");
     HICOM_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->hidden > 0 && a->kt > 0 && a->ks > 0, HICOM_EINVAL, "compressor_batch: bad shape");
-    int st = seg_check_shape(kWho, a);
+    int st = seg_check_items_shape(kWho, a);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->T % a->kt == 0 && a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP,
                   "compressor_batch: needs an exact window partition (T=%d H=%d W=%d, windows %dx%dx%d)", a->T, a->H, a->W, a->kt, a->ks, a->ks);
@@ -161,7 +151,7 @@ struct BatchItem {
     char* ws() const { return (char*)a->ws; }
     hipStream_t s() const { return (hipStream_t)a->stream; }
 
-    void local(const uint16_t* key_x, const SegAdaptParams* ad) const {
+    int local(const uint16_t* key_x, const SegAdaptParams* ad) const {
         const int B = a->B, nwin = (int)l.s.n.windows;
         const hicom_axis at{B * a->T, a->kt, B * a->T / a->kt, B * a->T / a->kt};
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
@@ -171,9 +161,10 @@ struct BatchItem {
         else
             HICOM_LAUNCH(batch_local_attn_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, s(), key_x, (const uint16_t*)a->ff,
                          (const uint16_t*)a->guide, at, ay, ax, l.wpi, nwin, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
+        return seg_check_launch(kWho, "local stage");
     }
 
-    void stream(const SegStreamParams& c) const {
+    int stream(const SegStreamParams& c) const {
         BatchStreamParams p;
         const int N = a->T * a->H * a->W;
         p.c = c;
@@ -185,24 +176,20 @@ struct BatchItem {
             attr_set = true;
         }
         HICOM_LAUNCH(batch_global_stream_kernel<9>, dim3((unsigned)l.chunks, (unsigned)a->B), dim3(256), kSegStreamSmem, s(), p);
+        return seg_check_launch(kWho, "global stream");
     }
 
-    void merge(const SegMergeParams& c) const {
+    int merge(const SegMergeParams& c) const {
         BatchMergeParams p;
         p.c = c;
         p.scores = (const float*)(ws() + l.s.scores); p.score_stride = l.score_stride;
         p.nparts = l.chunks; p.rows = a->nh; p.T = a->T;
         p.ctx = (float*)(ws() + l.s.ctxg);
         HICOM_LAUNCH(batch_merge_kernel, dim3((unsigned)a->nh, (unsigned)a->B), dim3(256), (size_t)seg_merge_smem(a->T, a->H, a->W), s(), p);
+        return seg_check_launch(kWho, "merge");
     }
 
-    void place(const SegPlaceParams& c) const {
-        BatchPlaceParams p;
-        p.c = c;
-        p.wpi = l.wpi; p.nl_group = a->nl_group; p.nl_count = a->nl_count;
-        p.item_rows = a->item_rows; p.global_row0 = a->global_row0; p.nl_first = a->nl_first; p.nl_step = a->nl_step > 0 ? a->nl_step : 1; p.ldo = a->ldo;
-        HICOM_LAUNCH(batch_place_kernel, dim3((unsigned)((long)a->B * a->item_rows)), dim3(128), 0, s(), p);
-    }
+    int place(const SegPlaceParams& c) const { return seg_place_equal(kWho, batch_place_kernel, a, c, l.wpi); }
 };
 
 int batch_fwd(const hicom_compressor_batch_args* a, const SegAdapt* ad) {
@@ -212,17 +199,9 @@ int batch_fwd(const hicom_compressor_batch_args* a, const SegAdapt* ad) {
     const BatchLayout l = batch_layout(a, ad);
     st = seg_check_fwd(kWho, a, ad, l.s.total);
     if (st != HICOM_OK) return st;
-    const long item_local = (long)l.wpi + (a->nl_group ? l.wpi / a->nl_group : 0);
-    HICOM_REQUIRE(a->n_global_rows > 0 && a->global_row0 >= item_local && a->item_rows == a->global_row0 + a->n_global_rows && a->ldo >= a->hidden &&
-                      a->nl_group >= 0 && (!a->nl_group || l.wpi % a->nl_group == 0),
-                  HICOM_EINVAL, "compressor_batch: output layout");
-    HICOM_REQUIRE(a->nl_count == 0 || (a->newline && a->nl_step > 0 && a->nl_first >= 0 &&
-                                       a->nl_first + (long)(a->nl_count - 1) * a->nl_step < a->global_row0),
-                  HICOM_EINVAL, "compressor_batch: newline rows");
-    // every local row of an item is a token row or a newline row
-    HICOM_REQUIRE(a->global_row0 == (long)l.wpi + a->nl_count, HICOM_EINVAL, "compressor_batch: %ld local rows for %d tokens + %d newline rows",
-                  (long)a->global_row0, l.wpi, a->nl_count);
-    return seg_step(kWho, a, ad, l.s, BatchItem{a, l});
+    st = seg_check_equal_rows(kWho, a, l.wpi);
+    if (st != HICOM_OK) return st;
+    return seg_step(a, ad, l.s, BatchItem{a, l});
 }
 
 }  // namespace

@@ -163,6 +163,8 @@ RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a, const SegAdapt
     }
     const int ncu = a->chunks > 0 ? 0 : num_cus();
     for (int i = 0; i < a->B; ++i) n.slots += ragged_chunks((a->items[i].T * HW + 15) / 16, l.ntiles_sum, a->chunks, ncu);
+    n.rows = (long)a->B * a->nh;
+    n.part_rows = n.slots * 16;
     long off = 0;
     auto take = [&](long bytes) { const long at = off; off += (bytes + 255) / 256 * 256; return at; };
     l.items = take(a->B * (long)sizeof(RaggedItem));
@@ -177,7 +179,7 @@ RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a, const SegAdapt
 int ragged_check(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_ragged: NULL arguments");
     HICOM_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && a->hidden > 0 && a->ks > 0 && a->items, HICOM_EINVAL, "compressor_ragged: bad shape");
-    int st = seg_check_shape(kWho, a);
+    int st = seg_check_items_shape(kWho, a);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP, "compressor_ragged: needs an exact window partition (H=%d W=%d, windows %dx%d)",
                   a->H, a->W, a->ks, a->ks);
@@ -257,7 +259,7 @@ struct RaggedItems {
     hipStream_t s() const { return (hipStream_t)a->stream; }
     const RaggedItem* items() const { return (const RaggedItem*)(ws() + l.items); }
 
-    void local(const uint16_t* key_x, const SegAdaptParams* ad) const {
+    int local(const uint16_t* key_x, const SegAdaptParams* ad) const {
         const long windows = l.s.n.windows;
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
         if (ad)
@@ -268,9 +270,10 @@ struct RaggedItems {
             HICOM_LAUNCH(ragged_local_attn_kernel<3>, dim3((unsigned)((windows + 3) / 4)), dim3(256), 0, s(), key_x, (const uint16_t*)a->ff,
                          (const uint16_t*)a->guide, items(), (const int*)(ws() + l.win_item), ay, ax, (int)windows, a->l_scale,
                          (_Float16*)(ws() + l.s.ctx16));
+        return seg_check_launch(kWho, "local stage");
     }
 
-    void stream(const SegStreamParams& c) const {
+    int stream(const SegStreamParams& c) const {
         RaggedStreamParams p;
         p.c = c;
         p.x = (const uint16_t*)a->ff;
@@ -282,22 +285,25 @@ struct RaggedItems {
             attr_set = true;
         }
         HICOM_LAUNCH(ragged_global_stream_kernel<9>, dim3((unsigned)l.s.n.slots), dim3(256), kSegStreamSmem, s(), p);
+        return seg_check_launch(kWho, "global stream");
     }
 
-    void merge(const SegMergeParams& c) const {
+    int merge(const SegMergeParams& c) const {
         RaggedMergeParams p;
         p.c = c;
         p.scores = (const float*)(ws() + l.s.scores);
         p.items = items(); p.rows = a->nh;
         p.ctx = (float*)(ws() + l.s.ctxg);
         HICOM_LAUNCH(ragged_merge_kernel, dim3((unsigned)a->nh, (unsigned)a->B), dim3(256), (size_t)seg_merge_smem(l.max_T, a->H, a->W), s(), p);
+        return seg_check_launch(kWho, "merge");
     }
 
-    void place(const SegPlaceParams& c) const {
+    int place(const SegPlaceParams& c) const {
         RaggedPlaceParams p;
         p.c = c;
         p.items = items(); p.row_item = (const int*)(ws() + l.row_item); p.ldo = a->ldo;
         HICOM_LAUNCH(ragged_place_kernel, dim3((unsigned)l.rows), dim3(128), 0, s(), p);
+        return seg_check_launch(kWho, "placement");
     }
 };
 
@@ -310,7 +316,7 @@ int ragged_fwd(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
     HICOM_REQUIRE(a->ldo >= a->hidden, HICOM_EINVAL, "compressor_ragged: output layout");
     for (int i = 0; i < a->B; ++i)
         HICOM_REQUIRE(a->items[i].nl_count == 0 || a->newline, HICOM_EINVAL, "compressor_ragged: item %d has newline rows and there is no newline token", i);
-    return seg_step(kWho, a, ad, l.s, RaggedItems{a, l});
+    return seg_step(a, ad, l.s, RaggedItems{a, l});
 }
 
 }  // namespace

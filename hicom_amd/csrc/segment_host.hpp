@@ -1,8 +1,9 @@
-// Host side of a many-item compressor step, shared by the equal-shape step (batch.hip) and the ragged step (ragged.hip): the limits,
-// the k / v adaptors of the local stage, the checks, the workspace layout and the launch sequence that do not depend on how a wave finds
-// its item.  The two files keep their kernels, the code that launches them, their chunk policy and their own layout checks.  The shared
-// functions are templates over the argument block (hicom_compressor_batch_args / hicom_compressor_ragged_args name every common field
-// alike) and read `a->field` directly; `who` is the message prefix ("compressor_batch" / "compressor_ragged").
+// Host side of a many-item compressor step, shared by the equal-shape step (batch.hip), the ragged step (ragged.hip) and the multi-guide
+// step (multi_guide.hip, whose items are the guides of one clip): the limits, the k / v adaptors of the local stage, the checks, the
+// workspace layout and the launch sequence that do not depend on how a wave finds its item.  The three files keep their kernels, the code
+// that launches them, their chunk policy and their own layout checks.  The shared functions are templates over the argument block
+// (hicom_compressor_batch_args / _ragged_args / _multiguide_args name every common field alike; the item count is B or Q: seg_items) and
+// read `a->field` directly; `who` is the message prefix ("compressor_batch" / "compressor_ragged" / "compressor_multiguide").
 #pragma once
 #include "segment_item.hpp"
 
@@ -106,20 +107,32 @@ inline auto seg_with_adapt(const char* who, const AdaptArgs* a, F&& f) -> declty
     return f(&a->base, &ad);
 }
 
-// ---- checks both steps make ---------------------------------------------------------------------------------------------------------------
+// items of the call: B of a batch / ragged block, Q (guides) of a multi-guide block
+template <class A>
+inline auto seg_items(const A* a) -> decltype(a->B) { return a->B; }
+template <class A>
+inline auto seg_items(const A* a) -> decltype(a->Q) { return a->Q; }
+
+// ---- checks the steps make ----------------------------------------------------------------------------------------------------------------
 // LDS of the merge kernels: T (H + W) marginal sums and the T + H + W marginals of the longest item
 inline long seg_merge_smem(long T, long H, long W) { return (T * H + T * W + T + H + W) * 4; }
 
-// behind the caller's own "bad shape" check (B, H, W, hidden, ks > 0)
+// behind the caller's own "bad shape" check (items, H, W, hidden, ks > 0) and its limit on the item count; `item`: what the step calls one
 template <class A>
-inline int seg_check_shape(const char* who, const A* a) {
-    HICOM_REQUIRE(a->B <= kSegMaxItems, HICOM_EUNSUP, "%s: B=%d items (<= %d per call)", who, a->B, kSegMaxItems);
+inline int seg_check_shape(const char* who, const char* item, const A* a) {
     HICOM_REQUIRE(a->E == 1152, HICOM_EUNSUP, "%s: E=%d (only 1152)", who, a->E);
-    HICOM_REQUIRE(a->nh > 0 && a->nh <= 16 && a->E % a->nh == 0, HICOM_EUNSUP, "%s: %d heads (<= 16 folded rows per item)", who, a->nh);
+    HICOM_REQUIRE(a->nh > 0 && a->nh <= 16 && a->E % a->nh == 0, HICOM_EUNSUP, "%s: %d heads (<= 16 folded rows per %s)", who, a->nh, item);
     HICOM_REQUIRE(a->hidden % 64 == 0, HICOM_EUNSUP, "%s: hidden=%d (multiple of 64: fp16 readout planes)", who, a->hidden);
     HICOM_REQUIRE(a->out_dt == HICOM_DT_BF16 || a->out_dt == HICOM_DT_F32, HICOM_EUNSUP, "%s: output dtype %d (bf16 | f32)", who, a->out_dt);
     HICOM_REQUIRE(!a->pe == !a->kpe && (!a->pe || a->P > 0), HICOM_EINVAL, "%s: pe and kpe come together", who);
     return HICOM_OK;
+}
+
+// batch / ragged: the item count, then seg_check_shape
+template <class A>
+inline int seg_check_items_shape(const char* who, const A* a) {
+    HICOM_REQUIRE(a->B <= kSegMaxItems, HICOM_EUNSUP, "%s: B=%d items (<= %d per call)", who, a->B, kSegMaxItems);
+    return seg_check_shape(who, "item", a);
 }
 
 // T: the longest item's frames
@@ -150,25 +163,46 @@ inline int seg_check_fwd(const char* who, const A* a, const SegAdapt* ad, long w
     return HICOM_OK;
 }
 
-// ---- workspace: the sixteen regions of the step from the call's totals, the adaptor planes behind them --------------------------------------
+// the packed-row layout of a step whose items share one shape (batch, multi-guide), in front of the first launch; wpi: windows per item
+template <class A>
+inline int seg_check_equal_rows(const char* who, const A* a, int wpi) {
+    const long item_local = (long)wpi + (a->nl_group ? wpi / a->nl_group : 0);
+    HICOM_REQUIRE(a->n_global_rows > 0 && a->global_row0 >= item_local && a->item_rows == a->global_row0 + a->n_global_rows && a->ldo >= a->hidden &&
+                      a->nl_group >= 0 && (!a->nl_group || wpi % a->nl_group == 0),
+                  HICOM_EINVAL, "%s: output layout", who);
+    HICOM_REQUIRE(a->nl_count == 0 || (a->newline && a->nl_step > 0 && a->nl_first >= 0 &&
+                                       a->nl_first + (long)(a->nl_count - 1) * a->nl_step < a->global_row0),
+                  HICOM_EINVAL, "%s: newline rows", who);
+    // every local row of an item is a token row or a newline row
+    HICOM_REQUIRE(a->global_row0 == (long)wpi + a->nl_count, HICOM_EINVAL, "%s: %ld local rows for %d tokens + %d newline rows", who, (long)a->global_row0,
+                  wpi, a->nl_count);
+    return HICOM_OK;
+}
+
+// ---- workspace: the regions of the step from the call's totals, the adaptor planes behind them ----------------------------------------------
 struct SegTotals {
-    long score_floats;      // logits the stream leaves: 16 rows per item, the item's tokens padded to a tile
-    long slots;             // partial states (m, l, ACC) = workgroups of the segmented stream
+    long score_floats;      // what the stream leaves for the merge: 16 rows of logits per item, the item's tokens padded to a tile (multi-guide:
+                            // the larger of its logits and its in-kernel marginals)
+    long slots;             // workgroups of the segmented stream (multi-guide: token chunks of the many-row stream)
     long windows, tokens;   // over all items
+    long rows;              // folded query rows: heads x items (multi-guide: rounded up to a pass of the many-row stream)
+    long part_rows;         // rows of partial state (m, l, ACC): 16 per slot (multi-guide: `rows` per chunk)
+    long scratch_floats;    // scratch of the many-row merge, with its (M, L) per row behind it; 0: the segmented merge needs neither
 };
 
 struct SegLayout {
-    long qp, qhi, qlo, pos_a, scores, part_m, part_l, part_acc, ctxg, o, pre, hid, tok, ctx16, hid16, loc, total;
+    long qp, qhi, qlo, pos_a, scores, part_m, part_l, part_acc, scratch, ml, ctxg, o, pre, hid, tok, ctx16, hid16, loc, total;
     SegAdaptLayout ad;      // behind the plain layout, whose offsets and total do not depend on it
     SegTotals n;
 };
 
-// off: bytes in front of the first region (the ragged step's tables), a multiple of 256
+// off: bytes in front of the first region (the ragged step's tables), a multiple of 256.  Every region is rounded up to 256 bytes on its own:
+// an absent (zero-byte) region moves nothing.
 template <class A>
 inline SegLayout seg_layout(const A* a, const SegAdapt* ad, const SegTotals& n, long off) {
     SegLayout l;
     auto take = [&](long bytes) { const long at = off; off += (bytes + 255) / 256 * 256; return at; };
-    const long B = a->B, E = a->E, R = B * a->nh, hidden = a->hidden;
+    const long B = seg_items(a), E = a->E, R = n.rows, hidden = a->hidden;
     const int odt = a->out_dt == HICOM_DT_F32 ? 4 : 2;
     l.n = n;
     l.qp = take(B * E * 4);
@@ -176,9 +210,11 @@ inline SegLayout seg_layout(const A* a, const SegAdapt* ad, const SegTotals& n, 
     l.qlo = take(R * E * 2);
     l.pos_a = take(R * (long)(a->P > 0 ? a->P : 1) * 4);
     l.scores = take(n.score_floats * 4);
-    l.part_m = take(n.slots * 16 * 4);
-    l.part_l = take(n.slots * 16 * 4);
-    l.part_acc = take(n.slots * 16 * E * 4);
+    l.part_m = take(n.part_rows * 4);
+    l.part_l = take(n.part_rows * 4);
+    l.part_acc = take(n.part_rows * E * 4);
+    l.scratch = take(n.scratch_floats * 4);
+    l.ml = take(n.scratch_floats ? R * 2 * 4 : 0);
     l.ctxg = take(R * E * 4);
     l.o = take(B * E * 4);
     l.pre = take(B * E * 4);
@@ -199,18 +235,30 @@ inline int seg_check_launch(const char* who, const char* stage) {
     return HICOM_ELAUNCH;
 }
 
-// ---- the step: twelve launches, fourteen with adaptors ------------------------------------------------------------------------------------
-// `item` launches the four kernels that know where an item lives, each on the common part of its parameter block:
+// placement of a step whose items share one packed-row layout: `kernel` is the caller's one-line wrapper of place_equal_row
+template <class A>
+inline int seg_place_equal(const char* who, void (*kernel)(hicom::EqualPlaceParams), const A* a, const hicom::SegPlaceParams& c, int wpi) {
+    hicom::EqualPlaceParams p;
+    p.c = c;
+    p.wpi = wpi; p.nl_group = a->nl_group; p.nl_count = a->nl_count;
+    p.item_rows = a->item_rows; p.global_row0 = a->global_row0; p.nl_first = a->nl_first; p.nl_step = a->nl_step > 0 ? a->nl_step : 1; p.ldo = a->ldo;
+    HICOM_LAUNCH(kernel, dim3((unsigned)((long)seg_items(a) * a->item_rows)), dim3(128), 0, (hipStream_t)a->stream, p);
+    return seg_check_launch(who, "placement");
+}
+
+// ---- the step: twelve launches, fourteen with adaptors (multi-guide: thirteen or fourteen, its merge being two or three) ------------------
+// `item` launches what knows where an item lives, each hook on the common part of its parameter block (which a hook may ignore), and
+// returns the status of its launches (seg_check_launch, or that of the entry point it called):
 //   item.local(key_x, adapt)   3: local stage into ws + l.ctx16; adapt: the fused blends' parameters, NULL for the plain recipe
-//   item.stream(c)             4: segmented global stream
+//   item.stream(c)             4: global stream
 //   item.merge(c)              5: merge per (item, head) into ws + l.ctxg
 //   item.place(c)             12: every item's packed rows
-// Everything else is the same call for both steps, with M = B rows or M = all windows.  Only launches: nothing here allocates, copies or
-// synchronises.
+// Everything else is the same call for the three steps, with M = items or M = all windows.  Only launches: nothing here allocates, copies
+// or synchronises.
 template <class A, class Item>
-inline int seg_step(const char* who, const A* a, const SegAdapt* ad, const SegLayout& l, const Item& item) {
+inline int seg_step(const A* a, const SegAdapt* ad, const SegLayout& l, const Item& item) {
     char* ws = (char*)a->ws;
-    const int B = a->B, E = a->E, nh = a->nh, hd = E / nh, hidden = a->hidden, windows = (int)l.n.windows;
+    const int B = seg_items(a), E = a->E, nh = a->nh, hd = E / nh, hidden = a->hidden, windows = (int)l.n.windows;
     float* qp = (float*)(ws + l.qp);
     float* pos_a = a->pe ? (float*)(ws + l.pos_a) : nullptr;
     float* ctxg = (float*)(ws + l.ctxg);
@@ -230,15 +278,14 @@ inline int seg_step(const char* who, const A* a, const SegAdapt* ad, const SegLa
             st = seg_adapt_mlps(*ad, key_x, a->ff, l.n.tokens, E, ws, l.ad, a->stream);
             if (st != HICOM_OK) return st;
             const hicom::SegAdaptParams p = seg_adapt_params(*ad, ws, l.ad);
-            item.local(key_x, &p);
+            st = item.local(key_x, &p);
         } else {
-            item.local(key_x, nullptr);
+            st = item.local(key_x, nullptr);
         }
-        st = seg_check_launch(who, "local stage");
         if (st != HICOM_OK) return st;
     }
 
-    // 4: segmented global stream
+    // 4: global stream
     {
         hicom::SegStreamParams c;
         c.qhi = (const uint16_t*)(ws + l.qhi); c.qlo = (const uint16_t*)(ws + l.qlo);
@@ -246,8 +293,7 @@ inline int seg_step(const char* who, const A* a, const SegAdapt* ad, const SegLa
         c.H = a->H; c.W = a->W; c.HW = a->H * a->W;
         c.t0i = a->t_index0; c.y0i = a->y_index0; c.x0i = a->x_index0;
         c.part_m = (float*)(ws + l.part_m); c.part_l = (float*)(ws + l.part_l); c.part_acc = (float*)(ws + l.part_acc);
-        item.stream(c);
-        st = seg_check_launch(who, "global stream");
+        st = item.stream(c);
         if (st != HICOM_OK) return st;
     }
 
@@ -257,12 +303,11 @@ inline int seg_step(const char* who, const A* a, const SegAdapt* ad, const SegLa
         c.part_m = (const float*)(ws + l.part_m); c.part_l = (const float*)(ws + l.part_l); c.part_acc = (const float*)(ws + l.part_acc);
         c.pe = a->pe; c.E = E; c.H = a->H; c.W = a->W;
         c.t0i = a->t_index0; c.y0i = a->y_index0; c.x0i = a->x_index0;
-        item.merge(c);
-        st = seg_check_launch(who, "merge");
+        st = item.merge(c);
         if (st != HICOM_OK) return st;
     }
 
-    // 6-9: the global tail with M = B rows
+    // 6-9: the global tail with M = items rows
     st = hicom_linear_fwd(ctxg, HICOM_DT_F32, a->wv, HICOM_DT_BF16, a->bv, HICOM_DT_BF16, nullptr, 0, B, E, E, nh, hd, HICOM_ACT_NONE, o, a->stream);
     if (st != HICOM_OK) return st;
     st = hicom_linear_fwd(o, HICOM_DT_F32, a->wo, HICOM_DT_BF16, a->bo, HICOM_DT_BF16, a->guide, 2, B, E, E, 0, 0, HICOM_ACT_NONE, pre, a->stream);
@@ -281,13 +326,10 @@ inline int seg_step(const char* who, const A* a, const SegAdapt* ad, const SegLa
     if (st != HICOM_OK) return st;
 
     // 12: every item's packed rows
-    {
-        hicom::SegPlaceParams c;
-        c.loc = ws + l.loc; c.tok = tok; c.newline = (const uint16_t*)a->newline; c.out = a->out;
-        c.out_f32 = a->out_dt == HICOM_DT_F32; c.hidden = hidden;
-        item.place(c);
-    }
-    return seg_check_launch(who, "placement");
+    hicom::SegPlaceParams c;
+    c.loc = ws + l.loc; c.tok = tok; c.newline = (const uint16_t*)a->newline; c.out = a->out;
+    c.out_f32 = a->out_dt == HICOM_DT_F32; c.hidden = hidden;
+    return item.place(c);
 }
 
 }  // namespace hicom_host

@@ -1,7 +1,8 @@
 // What one wave / workgroup does for ONE item of a many-item compressor step, shared by the equal-shape step (batch.hip: the item
-// comes from a constant stride) and the ragged step (ragged.hip: the item comes from a device table).  Each function gets the
-// item's own pointers, token count and layout integers from its caller and indexes nothing outside them, so the two callers round
-// identically: an item's result does not depend on which of the two steps ran it.
+// comes from a constant stride) and the ragged step (ragged.hip: the item comes from a device table); the multi-guide step
+// (multi_guide.hip: the item is a guide) takes the placement.  Each function gets the item's own pointers, token count and layout
+// integers from its caller and indexes nothing outside them, so the callers round identically: an item's result does not depend on
+// which of the steps ran it.
 #pragma once
 #include "window_rows.hpp"
 
@@ -416,6 +417,20 @@ __device__ __forceinline__ void place_row(const SegPlaceParams& p, long r, long 
             else reinterpret_cast<uint16_t*>(p.out)[o + c] = reinterpret_cast<const uint16_t*>(p.loc)[src];
         }
     }
+}
+
+// Placement for items of ONE packed-row layout (batch.hip: item = item of the batch; multi_guide.hip: item = guide): output row /
+// item_rows = item.  grid = items * item_rows, one output row per workgroup.
+struct EqualPlaceParams {
+    SegPlaceParams c;
+    int wpi, nl_group, nl_count;
+    long item_rows, global_row0, nl_first, nl_step, ldo;
+};
+
+__device__ __forceinline__ void place_equal_row(const EqualPlaceParams& p) {
+    const long row = blockIdx.x;
+    const long item = row / p.item_rows, r = row - item * p.item_rows;
+    place_row(p.c, r, row * p.ldo, item, item * p.wpi, p.nl_group, p.nl_count, p.global_row0, p.nl_first, p.nl_step);
 }
 
 }  // namespace hicom

@@ -125,26 +125,13 @@ def _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, strea
 
 
 def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
-    from .projector import _out_dtype, _refuse_grad
     B, H, W, E, split_sizes, modals = _scope(proj, ff, fe, guides, split_sizes, modals, nl)
-    _refuse_grad(proj, "HIComProjector.forward_ragged")
-    dev = ff.device
-    ff = ff.contiguous()
-    fe = fe.contiguous() if fe is not None else None
-    guides = guides.contiguous()
-    nl = nl.contiguous() if nl is not None else None
-    out_dtype = _out_dtype(proj)
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, "forward_ragged", ff, fe, guides, nl)
     key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
            seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
     plan = seg.cached_plan(proj, "_ragged_plans", key, lambda: _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, stream))
     a = plan.io
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
-    a.ff = ff.data_ptr()
-    a.fe = fe.data_ptr() if fe is not None else None
-    a.guide = guides.data_ptr()
-    a.newline = nl.data_ptr() if nl is not None else None
-    a.out = out.data_ptr()
-    a.stream = stream
+    seg.patch_io(a, ff, fe, guides, nl, out, stream)         # (the newline pointer whenever given: items differ in their newline rows)
     nv.compressor_ragged_fwd(plan.args)
     return list(out.split(plan.rows))

@@ -1,10 +1,11 @@
-"""What HIComProjector.forward_batch (batch.py) and forward_ragged (ragged.py) share on the Python side: the scope rule, the input checks,
-the plan (filled argument block + the workspace it owns), the fields of the argument block that come from the module alone, and the
-plan-cache protocol.  The two modules keep what depends on how items are described: one (T, H, W) shape and B, or split sizes, modals and
-the table arithmetic.
+"""What HIComProjector.forward_batch (batch.py), forward_ragged (ragged.py) and forward_multi_guide (multi_guide.py) share on the Python
+side: the scope rule, the input checks, the plan (filled argument block + the workspace it owns), the fields of the argument block that
+come from the module alone, the plan builder of the two steps whose items share one shape, the call prologue, the per-call pointer patch
+and the plan-cache protocol.  The modules keep what depends on how items are described: one (T, H, W) shape and B or Q, or split sizes,
+modals and the table arithmetic.
 
-Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`: at most MAX_PLANS each), like engine.run_dense's; the
-input / output pointers are patched per call."""
+Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`, `proj._multi_guide_plans`: at most MAX_PLANS each),
+like engine.run_dense's; the input / output pointers are patched per call."""
 from __future__ import annotations
 
 import math
@@ -117,8 +118,9 @@ def exact_tilings(what, proj, T, H, W, modal, item=""):
 
 def new_args(proj, plain, adapt):
     """(the block the entry point takes, the plain block inside it, keep, ptr) for the module's recipe: an instance of `adapt` (plain block
-    first) for the adaptor recipe, of `plain` otherwise.  ptr(t) registers a tensor with the plan (`keep`) and returns its address."""
-    args = adapt() if seg_recipe(proj) == "adaptkv" else plain()
+    first) for the adaptor recipe, of `plain` otherwise (adapt None: a step without adaptor recipe).  ptr(t) registers a tensor with the
+    plan (`keep`) and returns its address."""
+    args = adapt() if adapt is not None and seg_recipe(proj) == "adaptkv" else plain()
     keep = []
 
     def ptr(t):
@@ -173,6 +175,53 @@ def alloc_workspace(args, a, workspace_bytes, dev):
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     a.ws, a.ws_bytes = ws.data_ptr(), nbytes
     return ws, (nbytes - workspace_bytes(a) if args is not a else 0)
+
+
+def build_equal_plan(proj, what, plain, adapt, count, shape, tiles, modal, nl, out_dtype, chunks, dev, workspace_bytes):
+    """The plan of a step whose items share one shape (T, H, W, E) and so one packed-row layout (HIComProjector._layout): `shape` =
+    (items, T, H, W, E), `count` the field of the block that takes the item count ("B" / "Q")."""
+    n, T, H, W, E = shape
+    at, ay, ax = tiles
+    lay = proj._layout((at.nwin, ay.nwin, ax.nwin), modal, nl is not None, False)
+    args, a, keep, ptr = new_args(proj, plain, adapt)
+    setattr(a, count, n)
+    a.T, a.E, a.kt, a.ks = T, E, at.k, ay.k
+    refresh = fill_common(a, proj, T, H, W, dev, out_dtype, chunks, ptr)
+    a.global_row0 = lay.n_rows
+    a.n_global_rows = proj.global_compressor.num_queries
+    a.item_rows = lay.n_rows + a.n_global_rows
+    a.nl_group = lay.nl_group
+    a.nl_count = len(lay.newline_rows)
+    if lay.newline_rows:
+        a.nl_first = lay.newline_rows[0]
+        a.nl_step = lay.newline_rows[1] - lay.newline_rows[0] if len(lay.newline_rows) > 1 else 1
+    if args is not a:
+        fill_adaptors(args, proj.local_compressor, what, ptr)
+    ws, adapt_bytes = alloc_workspace(args, a, workspace_bytes, dev)      # (the kernels' limits raise here, in front of any launch)
+    plan = SegPlan(args, ws, a.item_rows, a.hidden)
+    plan.keep, plan.adapt_bytes, plan.refresh = keep, adapt_bytes, refresh
+    return plan
+
+
+def call_inputs(proj, what, ff, fe, guides, nl):
+    """The prologue of a call behind its scope checks: (device, the four inputs made contiguous, output dtype, stream)."""
+    from .projector import _out_dtype, _refuse_grad
+    _refuse_grad(proj, f"HIComProjector.{what}")
+    dev = ff.device
+
+    def dense(t):
+        return t.contiguous() if t is not None else None
+    return dev, ff.contiguous(), dense(fe), guides.contiguous(), dense(nl), _out_dtype(proj), torch.cuda.current_stream(dev).cuda_stream
+
+
+def patch_io(a, ff, fe, guides, nl, out, stream):
+    """The per-call fields of a plan's plain block; nl None: no newline pointer."""
+    a.ff = ff.data_ptr()
+    a.fe = fe.data_ptr() if fe is not None else None
+    a.guide = guides.data_ptr()
+    a.newline = nl.data_ptr() if nl is not None else None
+    a.out = out.data_ptr()
+    a.stream = stream
 
 
 def cached_plan(proj, store, key, build):
