@@ -21,10 +21,15 @@ backward on the dense MFMA GEMM, NT and TN forms: round 4, no token-stream sized
 (adapt_q, adapt_guide, coarse / fine injection) acts on small tensors only and is differentiated as a torch graph
 (_query_chain_backward).  `frames_feature` comes from the frozen tower body: asking for its gradient raises instead of returning
 None silently, and so do input gradients of the guide-off recipe, clip-scale projectors and text2qk projections.
+
+`compressor_backward` is a driver over one state object `st` (inputs, fp32 weights, `grads`, `d_guide`, `ff_grad`): _local_backward (_local_inputs,
+_readout_backward, _window_queries, _window_backward_adapt | _window_backward_plain, _route_dq, the pool adjoint), then _global_backward
+(_global_tail_backward, _global_stream_backward, _global_dff, _global_fold_backward | _global_clip_backward, _global_query_backward).
 """
 from __future__ import annotations
 
 import math
+import types
 
 import torch
 
@@ -71,10 +76,6 @@ def _f32_params(proj):
         out[n] = flat[o:o + p.numel()].view(p.shape)
         o += p.numel()
     return out
-
-
-def _is_plain(proj) -> bool:
-    return all(c is None or c.is_plain for c in (proj.local_compressor, proj.global_compressor))
 
 
 def _ln_backward(g, xhat, rstd):
@@ -429,10 +430,7 @@ def _ff_grad_supported(proj) -> bool:
     (and, without frames_embed, key-side) gradient per token, the pooled per-window queries send theirs back through the trilinear pooling
     (reference projector.py:539-540), the global stage's is dS^T qt + P^T dctx; with k / v adaptors the streams' input gradients come out of
     the adaptor MLPs' backward (their skip path included).  Not with clip-scale."""
-    lc, gc = proj.local_compressor, proj.global_compressor
-    if proj.local_logit is not None or proj.global_logit is not None:
-        return False
-    return True
+    return proj.local_logit is None and proj.global_logit is None
 
 
 def _backward_outputs(dout, proj, ff, fe, guide, modal, nl, names, want, want_fe, want_guide, want_nl, store=None, gstore=None, ctx16=None,
@@ -458,15 +456,17 @@ def _backward_outputs(dout, proj, ff, fe, guide, modal, nl, names, want, want_fe
             (d_nl.to(nl.dtype) if (want_nl and d_nl is not None) else None))
 
 
-def _reads_frames_embed(proj, want_fe, want_guide, have_ctx) -> bool:
-    """Whether compressor_backward reads frames_embed: for the window contexts (unless the forward kept them) and in the window-attention
-    backward (input gradients, adaptors, injected / adapted queries)."""
-    lc = proj.local_compressor
-    if lc is None:
-        return False
+def _window_backward_runs(lc, want_fe, want_guide, clip, ff_grad_wanted) -> bool:
+    """Whether the local stage's window-attention backward runs: input gradients, adaptors, injected / adapted queries, clip-scale."""
     mode = lc.use_guide if lc.use_guide not in (None, "off") else None
     query_params = mode in ("coarse", "fine") or lc.adapt_q or lc.adapt_guide
-    return (not have_ctx) or want_fe or lc.adapt_k or lc.adapt_v or query_params or (want_guide and mode is not None) or proj.local_logit is not None
+    return bool(want_fe or lc.adapt_k or lc.adapt_v or query_params or (want_guide and mode is not None) or clip is not None or ff_grad_wanted)
+
+
+def _reads_frames_embed(proj, want_fe, want_guide, have_ctx) -> bool:
+    """Whether compressor_backward reads frames_embed: for the window contexts (unless the forward kept them) and in the window-attention backward."""
+    lc = proj.local_compressor
+    return lc is not None and (not have_ctx or _window_backward_runs(lc, want_fe, want_guide, proj.local_logit, False))
 
 
 _MAX_BWD_GRAPHS = 4
@@ -619,17 +619,361 @@ def _global_clip_backward(ff, pe, pos0, scores, ds, R, nq, nh, hd, q32, Wq, bq, 
     return (dqhat - qhat * (qhat * dqhat).sum(-1, keepdim=True)) / nrm
 
 
+def _readout_backward(x, pre, W2, dy, prefix, grads):
+    """Backward of a stage's readout MLP y = W2 GELU(pre) + b2 (pre = W0 x + b0 as that stage computes it): fills `prefix`{0,2}.*, returns d pre."""
+    grads[prefix + "2.weight"] = dy.t() @ torch.nn.functional.gelu(pre)
+    grads[prefix + "2.bias"] = _sum0(dy)
+    dpre = _gelu_bwd(dy @ W2, pre)
+    grads[prefix + "0.weight"] = dpre.t() @ x
+    grads[prefix + "0.bias"] = _sum0(dpre)
+    return dpre
+
+
+def _local_inputs(st, lc, adaptor_saved, ctx_local16):
+    """(rec_k, rec_v, ctx_l): the k / v adaptors' intermediates and the fp32 window contexts [Nw, E], kept by the training forward or recomputed."""
+    ff, fe = st.ff, st.fe
+    E = ff.shape[-1]
+    # k / v adaptors: ONE recomputation of the two MLPs over all tokens (with what their backward needs) serves the window contexts below as well
+    adapt = lc.adapt_k or lc.adapt_v
+    rec_k = rec_v = None
+    if adapt and adaptor_saved is not None:
+        rec_k, rec_v = adaptor_saved                                   # kept by the training forward (_AdaptorStore)
+    elif adapt:
+        key_ = fe if fe is not None else ff
+        rec_k = _adaptor_recompute(key_.reshape(-1, E), lc.k_proj) if lc.adapt_k else None
+        rec_v = _adaptor_recompute(ff.reshape(-1, E), lc.v_proj) if lc.adapt_v else None
+    if ctx_local16 is not None:                                         # kept by the training forward (the executor's fp16 plane,
+        return rec_k, rec_v, ctx_local16.float()                        # or the operator-by-operator forward's own fp32 contexts)
+    ctx_l, _ = lc.window_context(ff, fe, st.guide, st.modal, *st.proj._logit_args("local"),     # HIP: [Nw, E] fp32 window contexts
+                                 adapt_y=(rec_k[2] if rec_k else None, rec_v[2] if rec_v else None) if adapt else None)
+    return rec_k, rec_v, ctx_l
+
+
+def _through_guide_norm(dgh, guide_q, g_nrm, shape):
+    """d guide_embed from the gradient w.r.t. the guide rows L2-normalised by clip-scale, ghat = g / ||g|| (identity without: g_nrm None)."""
+    if g_nrm is None or dgh is None:
+        return dgh
+    gh = guide_q.reshape(g_nrm.shape[0], -1)
+    dgh = dgh.reshape(gh.shape)
+    return ((dgh - gh * (gh * dgh).sum(-1, keepdim=True)) / g_nrm).reshape(shape)
+
+
+def _window_queries(st, lc, mode, guide_q, grid):
+    """(q, pooled): the (adapted) guide as ONE shared row (direct; pooled None), else a row per window: frames_feature pooled, adapted, injected."""
+    from . import injector as inj
+    if mode == "direct":
+        q, _ = inj.inject(lc.guide_injector, "direct", None, guide_q.contiguous())     # the (adapted) guide, one row
+        return q.reshape(-1).contiguous(), None
+    E = st.ff.shape[-1]
+    pooled = torch.empty((*grid, E), dtype=torch.float32, device=st.dev)
+    nv.trilinear_pool(st.ff, pooled)                                       # HIP: the per-window query (ref :539-540)
+    q = pooled = pooled.view(-1, E)
+    if lc.adapt_q:
+        q = inj.adapt_query(q, lc.q_proj, lc.q_norm, lc.q_alpha)                        # HIP (ref :541)
+    if mode in ("coarse", "fine"):
+        q, _ = inj.inject(lc.guide_injector, mode, q.reshape(-1, E), guide_q.contiguous())   # HIP (ref :369-397)
+    return q, pooled
+
+
+def _plain_stream_grad(y, norm, vec, vec_stride, coef, axes):
+    """d x_n = coef_n vec[w(n)] of a PLAIN stream beside an adapted one (its y, norm): the rank-1 branch of hicom_adapt_dy_fwd (alpha = 0)."""
+    dx, junk = torch.empty(y.shape, dtype=torch.bfloat16, device=y.device), torch.empty(y.shape, dtype=torch.bfloat16, device=y.device)
+    nv.adapt_dy(y, norm.weight.detach(), vec, vec_stride, coef, torch.zeros(1, dtype=torch.float32, device=y.device), axes, junk, dx, eps=norm.eps)
+    return dx
+
+
+def _window_backward_adapt(st, lc, axes, exact, q, scale, dctx_l, rec_k, rec_v):
+    """Window backward through the k / v adaptor blends, then the adaptor MLPs' backward: fills their gradients, returns (dq_w, d_kx, d_vx)."""
+    ff, fe, f32, grads, dev = st.ff, st.fe, st.f32, st.grads, st.dev
+    nw, E = dctx_l.shape
+    N = ff.numel() // E
+    key = fe if fe is not None else ff
+    kx2, vx2 = key.reshape(N, E), ff.reshape(N, E)
+    ds = torch.empty((N,), dtype=torch.float32, device=dev)
+    pw = torch.empty_like(ds)
+    sxk, sxv = torch.empty((nw, E), dtype=torch.float32, device=dev), torch.empty((nw, E), dtype=torch.float32, device=dev)
+    syk = torch.empty_like(sxk) if lc.adapt_k else None
+    syv = torch.empty_like(sxv) if lc.adapt_v else None
+    qc = q.contiguous()
+    shared_q = qc.ndim == 1 or qc.shape[0] == 1
+    q_stride = 0 if shared_q else E
+    nv.local_attn_adapt_bwd(key, rec_k[2] if rec_k else None, lc.k_norm if rec_k else None, lc.k_alpha.detach() if rec_k else None,
+                            ff, rec_v[2] if rec_v else None, lc.v_norm if rec_v else None, lc.v_alpha.detach() if rec_v else None,
+                            axes, qc, q_stride, scale, 0.0, dctx_l, ds, pw, sxk, syk, sxv, syv, eps=(lc.k_norm if rec_k else lc.v_norm).eps)
+    L = "local_compressor."
+    qf = qc.float().reshape(1 if shared_q else nw, E)
+    d_kx = d_vx = None
+    # the key stream's input gradient: for d frames_embed, or -- without frames_embed the keys are frames_feature rows (reference :532) -- d frames_feature
+    want_kx = (st.want_fe and fe is not None) or (st.ff_grad is not None and fe is None)
+    if st.ff_grad is not None and not exact:
+        raise NotImplementedError("hicom_amd backward: d frames_feature needs an exact window partition")
+    if lc.adapt_k:
+        ak, gk = lc.k_alpha.detach().float(), f32[L + "k_norm.weight"]
+        dq_w = (1.0 - ak) * sxk + ak * gk * syk
+        grads[L + "k_alpha"] = (qf * (gk * syk - sxk)).sum().reshape(1)
+        grads[L + "k_norm.weight"] = ak * (qf * syk).sum(0)
+        grads[L + "k_norm.bias"] = torch.zeros(E, dtype=torch.float32, device=dev)    # a k sum_w q_w sum_n dS_n: the dS of a window sum to zero
+        d_kx = _adaptor_mlp_backward(kx2, lc.k_proj, lc.k_norm, lc.k_alpha, rec_k, ds, qc, q_stride, axes, L, "k", grads, want_kx)
+    else:
+        dq_w = sxk
+        if want_kx:                                                        # plain key stream beside a value adaptor: d key_n = ds_n q_w
+            d_kx = _plain_stream_grad(rec_v[2], lc.v_norm, qc, q_stride, ds, axes)
+    if lc.adapt_v:
+        av, gv, bvv = lc.v_alpha.detach().float(), f32[L + "v_norm.weight"], f32[L + "v_norm.bias"]
+        grads[L + "v_alpha"] = (dctx_l * (gv * syv + bvv - sxv)).sum().reshape(1)
+        grads[L + "v_norm.weight"] = av * (dctx_l * syv).sum(0)
+        grads[L + "v_norm.bias"] = av * dctx_l.sum(0)
+        d_vx = _adaptor_mlp_backward(vx2, lc.v_proj, lc.v_norm, lc.v_alpha, rec_v, pw, dctx_l, E, axes, L, "v", grads, st.ff_grad is not None)
+    elif st.ff_grad is not None:                                           # plain value stream beside a key adaptor: d value_n = p_n dctx_w
+        d_vx = _plain_stream_grad(rec_k[2], lc.k_norm, dctx_l, E, pw, axes)
+    return dq_w, d_kx, d_vx
+
+
+def _window_backward_plain(st, axes, q, q_stride, scale, bias, dctx_l, l2k, clip):
+    """Window backward without k / v adaptors: fills st.ff_grad["d_ff"] (local share) and clip-scale's logit gradients, returns (dq_w, d_fe)."""
+    ff, fe, dev = st.ff, st.fe, st.dev
+    dq_w = torch.empty(dctx_l.shape, dtype=torch.float32, device=dev)
+    d_fe = torch.empty_like(fe) if (st.want_fe and fe is not None) else None
+    dls = torch.empty((dctx_l.shape[0],), dtype=torch.float32, device=dev) if clip is not None else None
+    d_ffl = None
+    if st.ff_grad is not None:
+        # d frames_feature, local share: dv_n = p_n dctx_w (rank 1 per token, written by the same window backward); without
+        # frames_embed the keys are these rows too (projector.py:532) and their gradient is added in
+        d_ffl = st.ff_grad["d_ff"] = torch.empty_like(ff)      # (overlapping windows: the kernel accumulates per parity class, csrc/local_attn.hip)
+    nv.local_attn_bwd(fe if fe is not None else ff, ff, axes, q, q_stride, scale, bias, dctx_l, dq_w, d_fe, l2norm_key=l2k, dls=dls,
+                      dvalue=d_ffl, value_is_key=(d_ffl is not None and fe is None))
+    if clip is not None:
+        st.grads["local_logit_scale"] = dls.sum().reshape(1)       # d s_i / d ls = s_i - lb
+        st.grads["local_logit_bias"] = torch.zeros(1, dtype=torch.float32, device=dev)   # a shift of a window's logits: softmax cancels it
+    return dq_w, d_fe
+
+
+def _route_dq(st, lc, mode, dq_w, pooled, guide_q, g_nrm):
+    """Sends the windows' dq on into the injector's / query adaptors' gradients and st.d_guide; returns d pooled queries (d frames_feature only) or None."""
+    plain_q = not (lc.adapt_q or lc.adapt_guide)                       # plain direct / coarse / off: the hand-written paths
+    d_pool = dg = None
+    if mode == "direct" and plain_q:
+        dg = dq_w.sum(0) if st.want_guide else None
+    elif mode == "coarse" and plain_q:
+        d_pool, dg = _coarse_backward(lc.guide_injector, "local_compressor.guide_injector.", pooled, guide_q, dq_w, st.grads)
+    elif mode in ("coarse", "fine") or not plain_q or (st.want_guide and mode is not None):
+        d_inj = dq_w.sum(0, keepdim=True) if mode == "direct" else dq_w
+        d_pool, dg = _query_chain_backward(lc, "local_compressor.", pooled, guide_q, d_inj, st.f32, st.grads, st.want_guide,
+                                           want_vis=st.ff_grad is not None and mode != "direct")
+    elif mode is None:
+        d_pool = dq_w                                                   # guide off, no query adaptor: the pooled rows ARE the queries (:544)
+    if st.want_guide and dg is not None:
+        st.d_guide += _through_guide_norm(dg, guide_q, g_nrm, st.guide.shape).reshape(st.d_guide.shape)
+    return d_pool
+
+
+def _local_backward(st, lc, nl, dout, is_anyres, adaptor_saved, ctx_local16):
+    """The local stage (reference projector.py:524-559, packing mm_utils.py:92-140): returns (rows it packs, d image_newline, d frames_embed (bf16))."""
+    proj, ff, fe, guide, f32, grads = st.proj, st.ff, st.fe, st.guide, st.f32, st.grads
+    T, H, W, E = ff.shape
+    tiles = lc.tilings(T, H, W, st.modal)
+    grid = tuple(a.nwin for a in tiles)
+    lay = proj._layout(grid, st.modal, nl is not None, is_anyres)
+    idx = torch.arange(grid[0] * grid[1] * grid[2], device=st.dev)
+    dY = dout[idx + (idx // lay.nl_group if lay.nl_group else 0)]       # packing row map of the readout store
+    d_nl = dout[_row_index(lay.newline_rows, st.dev)].sum(0) if lay.newline_rows else None
+    rec_k, rec_v, ctx_l = _local_inputs(st, lc, adaptor_saved, ctx_local16)
+    W0, b0 = f32["local_compressor.readout.0.weight"], f32["local_compressor.readout.0.bias"]
+    dpre = _readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32["local_compressor.readout.2.weight"], dY, "local_compressor.readout.", grads)
+    clip = proj.local_logit
+    if not _window_backward_runs(lc, st.want_fe, st.want_guide, clip, st.ff_grad is not None):
+        return lay.n_rows, d_nl, None
+    mode = lc.use_guide if lc.use_guide not in (None, "off") else None
+    # clip-scale on the local stage (reference projector.py:527-529, :549; `local_logit_scale` / `local_logit_bias` are trainable under
+    # `attn_scale`, train.py:730-733): frames_embed and guide_embed enter L2-normalised (only when frames_embed is given), the logits
+    # are e^ls (q . khat) + lb.  The window backward takes the normalisation of the keys itself (l2norm_key); the guide's -- a
+    # handful of rows -- is differentiated here: ghat = g / ||g||, d g = (d ghat - ghat (ghat . d ghat)) / ||g||.
+    l2k = clip is not None and fe is not None
+    guide_q, g_nrm = guide, None
+    if l2k and mode is not None:
+        g_rows = guide.detach().float().reshape(-1, E)
+        g_nrm = g_rows.norm(dim=-1, keepdim=True)
+        guide_q = (g_rows / g_nrm).reshape(guide.shape)
+    adapt = lc.adapt_k or lc.adapt_v
+    exact = all(a.nwin * a.k == a.n for a in tiles)
+    if adapt and not exact:
+        raise NotImplementedError("hicom_amd backward: the adaptor gradients need an exact window "
+                                  f"partition (T, H, W = {T}, {H}, {W} against kernel {tiles[0].k}, {tiles[1].k}, {tiles[2].k})")
+    axes = tuple(nv.Axis(a.n, a.k, a.nwin, a.nfull) for a in tiles)
+    dctx_l = (dpre @ W0).contiguous()
+    scale, bias = (math.exp(clip[0]), float(clip[1])) if clip is not None else (1.0 / math.sqrt(lc.qk_dim), 0.0)
+    q, pooled = _window_queries(st, lc, mode, guide_q, grid)
+    if adapt:
+        dq_w, d_kx, d_vx = _window_backward_adapt(st, lc, axes, exact, q, scale, dctx_l, rec_k, rec_v)
+        d_fe = d_kx.to(fe.dtype).view(fe.shape) if (st.want_fe and fe is not None) else None
+        if st.ff_grad is not None:
+            # d frames_feature, local share: the value stream's input gradient (through the v adaptor, skip path included) and, without frames_embed, the key's
+            dff = d_vx.float() + d_kx.float() if fe is None else d_vx
+            st.ff_grad["d_ff"] = dff.to(ff.dtype).view(ff.shape)
+    else:
+        dq_w, d_fe = _window_backward_plain(st, axes, q, 0 if mode == "direct" else E, scale, bias, dctx_l, l2k, clip)
+    d_pool = _route_dq(st, lc, mode, dq_w, pooled, guide_q, g_nrm)
+    if st.ff_grad is not None and d_pool is not None and mode != "direct":
+        # through the trilinear pooling of frames_feature to the window grid (reference :539-540: F.interpolate(size = grid, 'trilinear')):
+        # its adjoint on a [1, E, t', h', w'] cotangent (an ATen library call on a window-count sized tensor), added to the value-side share
+        g5 = d_pool.reshape(*grid, E).permute(3, 0, 1, 2).unsqueeze(0).contiguous().float()
+        dpf = torch.ops.aten.upsample_trilinear3d_backward(g5, list(grid), [1, E, T, H, W], False, None, None, None)
+        st.ff_grad["d_ff"] = (st.ff_grad["d_ff"].float() + dpf[0].permute(1, 2, 3, 0)).to(ff.dtype)
+    return lay.n_rows, d_nl, d_fe
+
+
+def _global_tail_backward(st, nh, hd, ml, acc, q32, dtok):
+    """Everything behind the global attention, forward and backward on [nq, E] tensors: fills readout.* / out_proj.* / v_proj.*, returns (dpre, dctx, delta)."""
+    f32, grads, P = st.f32, st.grads, "global_compressor."
+    nq, E = q32.shape
+    Wv, bv = f32[P + "attn_layer.v_proj.weight"], f32[P + "attn_layer.v_proj.bias"]
+    Wo, bo = f32[P + "attn_layer.out_proj.weight"], f32[P + "attn_layer.out_proj.bias"]
+    G0, gb0 = f32[P + "readout.0.weight"], f32[P + "readout.0.bias"]
+    ctxg = (acc / ml[:, 1:2]).view(nq, nh, E)                          # per-(query, head) contexts
+    o = torch.einsum("hje,qhe->qhj", Wv.view(nh, hd, E), ctxg).reshape(nq, E) + bv    # ref :182,:215 after folding
+    pre = o @ Wo.t() + bo + q32                                        # out_proj + residual with the injected query (:646)
+    dpre = _readout_backward(pre, pre @ G0.t() + gb0, f32[P + "readout.2.weight"], dtok, P + "readout.", grads) @ G0
+    grads[P + "attn_layer.out_proj.weight"] = dpre.t() @ o
+    grads[P + "attn_layer.out_proj.bias"] = _sum0(dpre)
+    do = dpre @ Wo                                                     # [nq, E]
+    grads[P + "attn_layer.v_proj.bias"] = _sum0(do)
+    grads[P + "attn_layer.v_proj.weight"] = torch.einsum("qhj,qhe->hje", do.view(nq, nh, hd), ctxg).reshape(E, E)
+    dctx = torch.einsum("hje,qhj->qhe", Wv.view(nh, hd, E), do.view(nq, nh, hd)).reshape(-1, E).contiguous()
+    return dpre, dctx, (dctx * ctxg.reshape(-1, E)).sum(1).contiguous()
+
+
+def _global_stream_backward(st, scores, ml, dctx, delta, pe, pos0, need_ds):
+    """Attention backward over the token stream (HIP): returns (part: partial sums of dS x, dS or None, the (t, y, x) marginals of dS or None)."""
+    ff, dev = st.ff, st.dev
+    T, H, W, E = ff.shape
+    N, R = T * H * W, ml.shape[0]
+    rows_pad = (R + 15) // 16 * 16
+    dhi = torch.empty((rows_pad, E), dtype=torch.bfloat16, device=dev)
+    dlo = torch.empty_like(dhi)
+    nv.split_bf16(dctx, rows_pad, dhi, dlo)
+    pos_b = None
+    if pe is not None:
+        pos_b = torch.zeros((rows_pad, pe.shape[0]), dtype=torch.float32, device=dev)
+        nv.linear(dctx, pe, None, pos_b, M=R)
+    nparts = nv.global_stream_nparts(N, rows_pad)
+    part = torch.empty((nparts, rows_pad, E), dtype=torch.float32, device=dev)
+    if pe is not None and nv.global_stream_has_marg(N, E, rows_pad, H, W, nparts) and not need_ds:
+        # many rows: the kernel leaves the t / y / x marginals of dS per token chunk, [rows, N] dS is never written (need_ds: d frames_feature, clip-scale)
+        pm = torch.empty((nparts, rows_pad, nv.global_stream_marg_width(H, W)), dtype=torch.float32, device=dev)
+        nv.global_stream_bwd(ff.view(N, E), N, dhi, dlo, pos_b, H, W, *pos0, scores, ml, delta, None, part, R, part_marg=pm)
+        ybase, xbase = 16, 16 + 16 * ((H + 15) // 16)
+        mT = torch.zeros((R, T), dtype=torch.float32, device=dev)
+        mT.index_add_(1, nv.marg_frame_index(N, H, W, nparts, dev).reshape(-1), pm[:, :R, :8].permute(1, 0, 2).reshape(R, -1))
+        return part, None, (mT, pm[:, :R, ybase:ybase + H].sum(0), pm[:, :R, xbase:xbase + W].sum(0))
+    ds = torch.empty_like(scores)
+    nv.global_stream_bwd(ff.view(N, E), N, dhi, dlo, pos_b, H if pe is not None else 1, W if pe is not None else N, *pos0, scores, ml, delta, ds, part, R)
+    dS = ds[:R, :N].view(R, T, H, W)
+    return part, ds, ((dS.sum((2, 3)), dS.sum((1, 3)), dS.sum((1, 2))) if pe is not None else None)
+
+
+def _global_dff(st, att, q_in, Wq, bq, Wk, scores, ds, ml, dctx):
+    """d frames_feature, global share: d x_n = sum_r dS[r, n] qt_r + p[r, n] dctx_r, added to the local stage's share in st.ff_grad["d_ff"]."""
+    # (scores and values are both x in the folded form; the positional terms do not depend on x)
+    ff, ff_grad, nh, hd = st.ff, st.ff_grad, att.num_heads, att.head_dim
+    E, R, N = ff.shape[-1], ml.shape[0], ff.numel() // ff.shape[-1]
+    qp_ = (q_in.float() @ Wq.t() + bq).view(-1, nh, hd)
+    qt_ = (att.scale * torch.einsum("hje,qhj->qhe", Wk.view(nh, hd, E), qp_)).reshape(R, E).contiguous()
+    have = ff_grad.get("d_ff") is not None
+    if not have:
+        ff_grad["d_ff"] = torch.empty_like(ff)
+    if R <= 16 and E <= 1280:
+        nv.global_dx(scores, ds, ml, qt_, dctx, N, ff_grad["d_ff"].view(N, E), accumulate=have)
+    else:
+        # 32 distinct queries x heads (guide off / coarse / fine): a [N, 2 R] x [2 R, E] product -- plain library GEMMs
+        pr = torch.exp(scores[:R, :N] - ml[:, 0:1]) / ml[:, 1:2]
+        dxg = ds[:R, :N].t() @ qt_ + pr.t() @ dctx
+        cur = ff_grad["d_ff"].view(N, E)
+        cur.copy_(dxg + cur.float() if have else dxg)
+
+
+def _global_fold_backward(st, att, part, marg, pe, pos0, q32, Wq, bq, Wk):
+    """Through the fold qt[q,h] = scale W_k,h^T (W_q q + b_q)[q, h-slice] (ref :180-181,:193-197): fills k_proj.*, returns d (W_q q + b_q)."""
+    T, H, W, E = st.ff.shape
+    nq, nh, hd, P = q32.shape[0], att.num_heads, att.head_dim, "global_compressor."
+    dqt = part.sum(0)[:nq * nh]                                        # sum_n dS[r, n] x_n
+    if pe is not None:
+        (t0i, y0i, x0i), (mT, mY, mX) = pos0, marg
+        dqt = dqt + mT @ pe[t0i:t0i + T] + mY @ pe[y0i:y0i + H] + mX @ pe[x0i:x0i + W]
+    dqt = dqt.view(nq, nh, E)
+    qp = (q32 @ Wq.t() + bq).view(nq, nh, hd)
+    st.grads[P + "attn_layer.k_proj.weight"] = att.scale * torch.einsum("qhj,qhe->hje", qp, dqt).reshape(E, E)
+    st.grads[P + "attn_layer.k_proj.bias"] = torch.zeros(E, device=st.dev)   # a per-row logit shift: softmax cancels it exactly
+    return att.scale * torch.einsum("hje,qhe->qhj", Wk.view(nh, hd, E), dqt).reshape(nq, E)
+
+
+def _global_query_backward(st, gc, d_in):
+    """The global stage's query side: d_in, the gradient of the injected queries, into the learnable queries, the injector's parameters and st.d_guide."""
+    P = "global_compressor."
+    if gc.use_guide in (None, "off"):
+        st.grads[P + "query"] = d_in                                   # the learnable queries: through q_proj and the residual
+    elif gc.use_guide == "fine" or gc.adapt_guide:                     # fine injection / adapted guide: the small-tensor graph
+        direct_g = gc.use_guide == "direct"
+        _, dg = _query_chain_backward(gc, P, None if direct_g else gc.query.detach().float(), st.guide, d_in.sum(0, keepdim=True) if direct_g else d_in,
+                                      st.f32, st.grads, st.want_guide, vis_param=None if direct_g else "query")
+        if st.want_guide and dg is not None:
+            st.d_guide += dg.reshape(st.d_guide.shape)
+    elif gc.use_guide == "coarse":                                     # injected = LN(query (1 + scale) + shift) (:369-372)
+        dvis, dg = _coarse_backward(gc.guide_injector, P + "guide_injector.", gc.query.detach().float(), st.guide, d_in, st.grads)
+        st.grads[P + "query"] = dvis
+        if st.want_guide:
+            st.d_guide += dg
+    else:
+        st.d_guide += _sum0(d_in)                                      # direct: the injected query IS the guide (:352-368)
+
+
+def _global_backward(st, gc, dout, n_local, global_saved):
+    """The global stage (reference projector.py:634-646 + :166-228): fills its gradients, adds its shares to st.d_guide / st.ff_grad["d_ff"]."""
+    proj, ff, f32, grads = st.proj, st.ff, st.f32, st.grads
+    T, H, W, E = ff.shape
+    att = gc.attn_layer
+    nh, hd = att.num_heads, att.head_dim
+    # injected queries: the guide itself, one row ("direct": 32 identical output rows), or the 32 learnable queries (guide off: IdentityMap, ref :586-587)
+    q_in, n_rows = gc.injected_queries(st.guide)
+    nq = q_in.shape[0]
+    clip_g = proj.global_logit                                         # (log scale, bias): clip-scale on the global stage (reference :184-191)
+    if global_saved is not None and clip_g is None:
+        ml, acc, scores = global_saved                                 # kept by the training forward (_GlobalStore)
+    else:                                                              # HIP: forward logits + softmax state, rows q*nh + h
+        ml, acc, scores = gc.partial_context(ff, q_in, need_scores=True, logit_scale=None if clip_g is None else clip_g[0])
+    q32 = q_in.float()
+    dtok = dout[n_local:n_local + n_rows].view(n_rows // nq, nq, -1).sum(0)   # direct: the 32 global rows are copies of one row
+    dpre, dctx, delta = _global_tail_backward(st, nh, hd, ml, acc, q32, dtok)
+    pe, pos0 = None, (0, 0, 0)
+    if gc.use_pos_emb:
+        pe, cap = gc.pos_tables(T, H, W, st.dev)
+        pos0 = (0, cap, cap + H)
+    part, ds, marg = _global_stream_backward(st, scores, ml, dctx, delta, pe, pos0, need_ds=st.ff_grad is not None or clip_g is not None)
+    A = "global_compressor.attn_layer."
+    Wq, bq, Wk = f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"]
+    if st.ff_grad is not None:
+        _global_dff(st, att, q_in, Wq, bq, Wk, scores, ds, ml, dctx)
+    if clip_g is None:
+        dqp = _global_fold_backward(st, att, part, marg, pe, pos0, q32, Wq, bq, Wk)
+    else:
+        dqp = _global_clip_backward(ff, pe, pos0, scores, ds, ml.shape[0], nq, nh, hd, q32, Wq, bq, Wk, f32.get(A + "k_proj.bias"),
+                                    float(clip_g[0]), grads, "global_compressor.")
+    grads[A + "q_proj.weight"] = dqp.t() @ q32
+    grads[A + "q_proj.bias"] = _sum0(dqp)
+    if gc.use_guide != "direct" or gc.adapt_guide or st.want_guide:    # (plain direct: `query` does not enter the forward, ref :352-368 uses only its shape)
+        _global_query_backward(st, gc, dqp @ Wq + dpre)
+
+
 def compressor_backward(proj, ff, fe, guide, modal, nl, dout, want_fe=False, want_guide=False, adaptor_saved=None, global_saved=None,
                         stages=("local", "global"), is_anyres=False, ctx_local16=None, ff_grad=None):
     """(fp32 gradients {parameter name: tensor} of sum(out * dout), d image_newline, d frames_embed (bf16) or None,
     d guide_embed (fp32) or None).  Restates autograd through reference projector.py:524-559 (local), :634-646 + :166-228
-    (global) and mm_utils.py:92-140 (packing).  The input gradients exist for the direct recipe only.
+    (global) and mm_utils.py:92-140 (packing): _local_backward, then _global_backward, over one shared state `st`.
     `stages` / `is_anyres`: one SEGMENT of an anyres dict input (reference :679-689: the base image goes through the local stage
     only, the patch grid through both, packed with the anyres layout); `dout` holds that segment's rows."""
     lc = proj.local_compressor if "local" in stages else None
     gc = proj.global_compressor if "global" in stages else None
     dev = ff.device
-    d_fe = d_guide = None
+    d_guide = None
     if want_fe or want_guide:
         if want_guide and not any(c is not None and c.use_guide in ("direct", "coarse", "fine") for c in (lc, gc)):
             want_guide = False         # guide off: guide_embed does not enter the forward: no gradient (None), as in the reference
@@ -640,318 +984,14 @@ def compressor_backward(proj, ff, fe, guide, modal, nl, dout, want_fe=False, wan
         # (guide off with a local stage: frames_embed are the window keys, reference :544-551 -- d frames_embed[n] = dS_n q_w with the
         # pooled query of the token's window, the same kernel as the direct recipe's with one query row per window)
     dout = dout.float()
-    f32 = _f32_params(proj)
-    T, H, W, E = ff.shape
-    grads = {}
-    d_nl = None
-    n_local = 0
+    st = types.SimpleNamespace(proj=proj, ff=ff, fe=fe, guide=guide, modal=modal, dev=dev, f32=_f32_params(proj), grads={}, d_guide=d_guide,
+                               ff_grad=ff_grad, want_fe=want_fe, want_guide=want_guide)
+    n_local, d_nl, d_fe = 0, None, None
     if lc is not None:
-        at, ay, ax = lc.tilings(T, H, W, modal)
-        grid = (at.nwin, ay.nwin, ax.nwin)
-        lay = proj._layout(grid, modal, nl is not None, is_anyres)
-        nw = grid[0] * grid[1] * grid[2]
-        n_local = lay.n_rows
-        idx = torch.arange(nw, device=dev)
-        rows = idx + (idx // lay.nl_group if lay.nl_group else 0)          # packing row map of the readout store
-        dY = dout[rows]
-        if lay.newline_rows:
-            d_nl = dout[_row_index(lay.newline_rows, dev)].sum(0)
-        # k / v adaptors: ONE recomputation of the two MLPs over all tokens (with the intermediates their backward needs) serves the
-        # window contexts below as well
-        adapt = lc.adapt_k or lc.adapt_v
-        rec_k = rec_v = None
-        if adapt and adaptor_saved is not None:
-            rec_k, rec_v = adaptor_saved                                   # kept by the training forward (_AdaptorStore)
-        elif adapt:
-            key_ = fe if fe is not None else ff
-            rec_k = _adaptor_recompute(key_.reshape(-1, E), lc.k_proj) if lc.adapt_k else None
-            rec_v = _adaptor_recompute(ff.reshape(-1, E), lc.v_proj) if lc.adapt_v else None
-        if ctx_local16 is not None:                                         # kept by the training forward (the executor's fp16 plane,
-            ctx_l = ctx_local16.float()                                     # or the operator-by-operator forward's own fp32 contexts)
-        else:
-            ctx_l, _ = lc.window_context(ff, fe, guide, modal, *proj._logit_args("local"),     # HIP: [Nw, E] fp32 window contexts
-                                         adapt_y=(rec_k[2] if rec_k else None, rec_v[2] if rec_v else None) if adapt else None)
-        W0, b0 = f32["local_compressor.readout.0.weight"], f32["local_compressor.readout.0.bias"]
-        W2 = f32["local_compressor.readout.2.weight"]
-        pre = torch.addmm(b0, ctx_l, W0.t())
-        h = torch.nn.functional.gelu(pre)
-        grads["local_compressor.readout.2.weight"] = dY.t() @ h
-        grads["local_compressor.readout.2.bias"] = dY.sum(0)
-        dpre = _gelu_bwd(dY @ W2, pre)
-        grads["local_compressor.readout.0.weight"] = dpre.t() @ ctx_l
-        grads["local_compressor.readout.0.bias"] = dpre.sum(0)
-        mode = lc.use_guide if lc.use_guide not in (None, "off") else None
-        plain_q = not (lc.adapt_q or lc.adapt_guide)                       # plain direct / coarse / off: the hand-written paths below
-        query_params = mode in ("coarse", "fine") or lc.adapt_q or lc.adapt_guide
-        # clip-scale on the local stage (reference projector.py:527-529, :549; `local_logit_scale` / `local_logit_bias` are trainable under
-        # `attn_scale`, train.py:730-733): frames_embed and guide_embed enter L2-normalised (only when frames_embed is given), the logits
-        # are e^ls (q . khat) + lb.  The window backward takes the normalisation of the keys itself (l2norm_key); the guide's -- a
-        # handful of rows -- is differentiated here: ghat = g / ||g||, d g = (d ghat - ghat (ghat . d ghat)) / ||g||.
-        clip = proj.local_logit if "local" in stages else None
-        l2k = clip is not None and fe is not None
-        guide_q, g_nrm = guide, None
-        if l2k and mode is not None:
-            g_rows = guide.detach().float().reshape(-1, E)
-            g_nrm = g_rows.norm(dim=-1, keepdim=True)
-            guide_q = (g_rows / g_nrm).reshape(guide.shape)
-
-        def through_guide_norm(dgh):
-            """d guide_embed from the gradient w.r.t. the normalised guide rows (identity without clip-scale)."""
-            if g_nrm is None or dgh is None:
-                return dgh
-            gh = guide_q.reshape(-1, E)
-            dgh = dgh.reshape(-1, E)
-            return ((dgh - gh * (gh * dgh).sum(-1, keepdim=True)) / g_nrm).reshape(guide.shape)
-
-        if want_fe or adapt or query_params or (want_guide and mode is not None) or clip is not None or ff_grad is not None:
-            # ---- attention backward of the windows: dq per window, d key stream, d value stream -------------------------
-            from . import injector as inj
-            exact = all(a.nwin * a.k == a.n for a in (at, ay, ax))
-            if adapt and not exact:
-                raise NotImplementedError("hicom_amd backward: the adaptor gradients need an exact window "
-                                          f"partition (T, H, W = {T}, {H}, {W} against kernel {at.k}, {ay.k}, {ax.k})")
-            axes = tuple(nv.Axis(a.n, a.k, a.nwin, a.nfull) for a in (at, ay, ax))
-            dctx_l = (dpre @ W0).contiguous()
-            scale, bias = (math.exp(clip[0]), float(clip[1])) if clip is not None else (1.0 / math.sqrt(lc.qk_dim), 0.0)
-            key = fe if fe is not None else ff
-            pooled = None
-            if mode == "direct":
-                q, _ = inj.inject(lc.guide_injector, "direct", None, guide_q.contiguous())     # the (adapted) guide, one row
-                q = q.reshape(-1).contiguous()
-            else:
-                pooled = torch.empty((*grid, E), dtype=torch.float32, device=dev)
-                nv.trilinear_pool(ff, pooled)                              # HIP: the per-window query (ref :539-540)
-                pooled = pooled.view(nw, E)
-                q = pooled
-                if lc.adapt_q:
-                    q = inj.adapt_query(q, lc.q_proj, lc.q_norm, lc.q_alpha)                    # HIP (ref :541)
-                if mode in ("coarse", "fine"):
-                    q, _ = inj.inject(lc.guide_injector, mode, q.reshape(nw, E), guide_q.contiguous())   # HIP (ref :369-397)
-            if adapt:
-                # ---- k / v adaptors: window-attention backward with the blends (two streaming passes over x_k, y_k, x_v, y_v), then
-                # the adaptor MLPs' backward per stream; everything token-stream sized runs on HIP kernels --------------------------
-                N = T * H * W
-                kx2, vx2 = key.reshape(N, E), ff.reshape(N, E)
-                ds = torch.empty((N,), dtype=torch.float32, device=dev)
-                pw = torch.empty_like(ds)
-                sxk, sxv = torch.empty((nw, E), dtype=torch.float32, device=dev), torch.empty((nw, E), dtype=torch.float32, device=dev)
-                syk = torch.empty_like(sxk) if lc.adapt_k else None
-                syv = torch.empty_like(sxv) if lc.adapt_v else None
-                qc = q.contiguous()
-                shared_q = qc.ndim == 1 or qc.shape[0] == 1
-                q_stride = 0 if shared_q else E
-                nv.local_attn_adapt_bwd(key, rec_k[2] if rec_k else None, lc.k_norm if rec_k else None, lc.k_alpha.detach() if rec_k else None,
-                                        ff, rec_v[2] if rec_v else None, lc.v_norm if rec_v else None, lc.v_alpha.detach() if rec_v else None,
-                                        axes, qc, q_stride, scale, 0.0, dctx_l, ds, pw, sxk, syk, sxv, syv,
-                                        eps=(lc.k_norm if rec_k else lc.v_norm).eps)
-                L = "local_compressor."
-                qf = qc.float().reshape(1 if shared_q else nw, E)
-                d_kx = None
-                # the key stream's input gradient is wanted for d frames_embed, or -- without frames_embed the keys are frames_feature rows
-                # (reference :532) -- for d frames_feature
-                want_kx = (want_fe and fe is not None) or (ff_grad is not None and fe is None)
-                if ff_grad is not None and not exact:
-                    raise NotImplementedError("hicom_amd backward: d frames_feature needs an exact window partition")
-                if lc.adapt_k:
-                    ak, gk = lc.k_alpha.detach().float(), f32[L + "k_norm.weight"]
-                    dq_w = (1.0 - ak) * sxk + ak * gk * syk
-                    grads[L + "k_alpha"] = (qf * (gk * syk - sxk)).sum().reshape(1)
-                    grads[L + "k_norm.weight"] = ak * (qf * syk).sum(0)
-                    grads[L + "k_norm.bias"] = torch.zeros(E, dtype=torch.float32, device=dev)    # a k sum_w q_w sum_n dS_n: the dS of a window sum to zero
-                    d_kx = _adaptor_mlp_backward(kx2, lc.k_proj, lc.k_norm, lc.k_alpha, rec_k, ds, qc, q_stride, axes, L, "k", grads, want_kx)
-                else:
-                    dq_w = sxk
-                    if want_kx:
-                        # plain key stream beside a value adaptor: d key_n = ds_n q_w, written by the rank-1 branch of hicom_adapt_dy_fwd (alpha = 0)
-                        d_kx = torch.empty((N, E), dtype=torch.bfloat16, device=dev)
-                        junk = torch.empty((N, E), dtype=torch.bfloat16, device=dev)
-                        nv.adapt_dy(rec_v[2], lc.v_norm.weight.detach(), qc, q_stride, ds, torch.zeros(1, dtype=torch.float32, device=dev), axes, junk, d_kx,
-                                    eps=lc.v_norm.eps)
-                        del junk
-                if lc.adapt_v:
-                    av, gv, bvv = lc.v_alpha.detach().float(), f32[L + "v_norm.weight"], f32[L + "v_norm.bias"]
-                    grads[L + "v_alpha"] = (dctx_l * (gv * syv + bvv - sxv)).sum().reshape(1)
-                    grads[L + "v_norm.weight"] = av * (dctx_l * syv).sum(0)
-                    grads[L + "v_norm.bias"] = av * dctx_l.sum(0)
-                    d_vx = _adaptor_mlp_backward(vx2, lc.v_proj, lc.v_norm, lc.v_alpha, rec_v, pw, dctx_l, E, axes, L, "v", grads, ff_grad is not None)
-                elif ff_grad is not None:
-                    # plain value stream beside a key adaptor: d value_n = p_n dctx_w, the rank-1 branch of hicom_adapt_dy_fwd (alpha = 0)
-                    d_vx = torch.empty((N, E), dtype=torch.bfloat16, device=dev)
-                    junk = torch.empty((N, E), dtype=torch.bfloat16, device=dev)
-                    nv.adapt_dy(rec_k[2], lc.k_norm.weight.detach(), dctx_l, E, pw, torch.zeros(1, dtype=torch.float32, device=dev), axes, junk, d_vx,
-                                eps=lc.k_norm.eps)
-                    del junk
-                if want_fe and fe is not None:
-                    d_fe = d_kx.to(fe.dtype).view(fe.shape)
-                if ff_grad is not None:
-                    # d frames_feature, local share: the value stream's input gradient (through the v adaptor's MLP and its skip path) and --
-                    # without frames_embed -- the key stream's
-                    dff = d_vx.float() + d_kx.float() if fe is None else d_vx
-                    ff_grad["d_ff"] = dff.to(ff.dtype).view(ff.shape)
-            else:
-                dq_w = torch.empty((nw, E), dtype=torch.float32, device=dev)
-                if want_fe and fe is not None:
-                    d_fe = torch.empty_like(fe)
-                dls = torch.empty((nw,), dtype=torch.float32, device=dev) if clip is not None else None
-                d_ffl = None
-                if ff_grad is not None:
-                    # d frames_feature, local share: dv_n = p_n dctx_w (rank 1 per token, written by the same window backward); without
-                    # frames_embed the keys are these rows too (projector.py:532) and their gradient is added in
-                    d_ffl = ff_grad["d_ff"] = torch.empty_like(ff)      # (overlapping windows: the kernel accumulates per parity class, csrc/local_attn.hip)
-                nv.local_attn_bwd(key, ff, axes, q, 0 if mode == "direct" else E, scale, bias, dctx_l, dq_w, d_fe, l2norm_key=l2k, dls=dls,
-                                  dvalue=d_ffl, value_is_key=(d_ffl is not None and fe is None))
-                if clip is not None:
-                    grads["local_logit_scale"] = dls.sum().reshape(1)       # d s_i / d ls = s_i - lb
-                    grads["local_logit_bias"] = torch.zeros(1, dtype=torch.float32, device=dev)   # a shift of a window's logits: softmax cancels it
-            d_pool = None                                                   # gradient of the pooled per-window queries (d frames_feature only)
-            if mode == "direct" and plain_q:
-                if want_guide:
-                    d_guide += through_guide_norm(dq_w.sum(0)).reshape(d_guide.shape)
-            elif mode == "coarse" and plain_q:
-                d_pool, dg = _coarse_backward(lc.guide_injector, "local_compressor.guide_injector.", pooled, guide_q, dq_w, grads)
-                if want_guide:
-                    d_guide += through_guide_norm(dg).reshape(d_guide.shape)
-            elif query_params or (want_guide and mode is not None):
-                d_inj = dq_w.sum(0, keepdim=True) if mode == "direct" else dq_w
-                d_pool, dg = _query_chain_backward(lc, "local_compressor.", pooled, guide_q, d_inj, f32, grads, want_guide,
-                                                   want_vis=ff_grad is not None and mode != "direct")
-                if want_guide and dg is not None:
-                    d_guide += through_guide_norm(dg).reshape(d_guide.shape)
-            elif mode is None:
-                d_pool = dq_w                                               # guide off, no query adaptor: the pooled rows ARE the queries (:544)
-            if ff_grad is not None and d_pool is not None and mode != "direct":
-                # through the trilinear pooling of frames_feature to the window grid (reference :539-540: F.interpolate(size = grid, 'trilinear')):
-                # its adjoint on a [1, E, t', h', w'] cotangent (an ATen library call on a window-count sized tensor), added to the value-side share
-                g5 = d_pool.reshape(*grid, E).permute(3, 0, 1, 2).unsqueeze(0).contiguous().float()
-                dpf = torch.ops.aten.upsample_trilinear3d_backward(g5, list(grid), [1, E, T, H, W], False, None, None, None)
-                ff_grad["d_ff"] = (ff_grad["d_ff"].float() + dpf[0].permute(1, 2, 3, 0)).to(ff.dtype)
+        n_local, d_nl, d_fe = _local_backward(st, lc, nl, dout, is_anyres, adaptor_saved, ctx_local16)
     if gc is not None:
-        att = gc.attn_layer
-        nh, hd = att.num_heads, att.head_dim
-        # injected queries: the guide itself, one row ("direct": 32 identical output rows), or the 32 learnable queries
-        # (guide off, reference stage 1: IdentityMap injector, :586-587)
-        q_in, n_rows = gc.injected_queries(guide)
-        nq = q_in.shape[0]
-        clip_g = proj.global_logit if "global" in stages else None        # (log scale, bias): clip-scale on the global stage (reference :184-191)
-        if global_saved is not None and clip_g is None:
-            ml, acc, scores = global_saved                                 # kept by the training forward (_GlobalStore)
-        else:
-            ml, acc, scores = gc.partial_context(ff, q_in, need_scores=True,   # HIP: forward logits + softmax state, rows q*nh + h
-                                                 logit_scale=None if clip_g is None else clip_g[0])
-        R = ml.shape[0]
-        ctxg = (acc / ml[:, 1:2]).view(nq, nh, E)                          # per-(query, head) contexts
-        q32 = q_in.float()
-        A = "global_compressor.attn_layer."
-        Wq, bq = f32[A + "q_proj.weight"], f32[A + "q_proj.bias"]
-        Wk = f32[A + "k_proj.weight"]
-        Wv, bv = f32[A + "v_proj.weight"], f32[A + "v_proj.bias"]
-        Wo, bo = f32[A + "out_proj.weight"], f32[A + "out_proj.bias"]
-        G0, gb0 = f32["global_compressor.readout.0.weight"], f32["global_compressor.readout.0.bias"]
-        G2 = f32["global_compressor.readout.2.weight"]
-        o = torch.einsum("hje,qhe->qhj", Wv.view(nh, hd, E), ctxg).reshape(nq, E) + bv    # ref :182,:215 after folding
-        pre = o @ Wo.t() + bo + q32                                        # out_proj + residual with the injected query (:646)
-        a1 = pre @ G0.t() + gb0
-        hid = torch.nn.functional.gelu(a1)
-        dtok = dout[n_local:n_local + n_rows].view(n_rows // nq, nq, -1).sum(0)   # direct: the 32 global rows are copies of one row
-        P = "global_compressor."
-        grads[P + "readout.2.weight"] = dtok.t() @ hid
-        grads[P + "readout.2.bias"] = _sum0(dtok)
-        da1 = _gelu_bwd(dtok @ G2, a1)
-        grads[P + "readout.0.weight"] = da1.t() @ pre
-        grads[P + "readout.0.bias"] = _sum0(da1)
-        dpre = da1 @ G0
-        grads[P + "attn_layer.out_proj.weight"] = dpre.t() @ o
-        grads[P + "attn_layer.out_proj.bias"] = _sum0(dpre)
-        do = dpre @ Wo                                                     # [nq, E]
-        grads[P + "attn_layer.v_proj.bias"] = _sum0(do)
-        grads[P + "attn_layer.v_proj.weight"] = torch.einsum("qhj,qhe->hje", do.view(nq, nh, hd), ctxg).reshape(E, E)
-        dctx = torch.einsum("hje,qhj->qhe", Wv.view(nh, hd, E), do.view(nq, nh, hd)).reshape(R, E).contiguous()
-        delta = (dctx * ctxg.reshape(R, E)).sum(1).contiguous()
-        # ---- attention backward over the token stream (HIP) ------------------------------------------------
-        rows_pad = (R + 15) // 16 * 16
-        dhi = torch.empty((rows_pad, E), dtype=torch.bfloat16, device=dev)
-        dlo = torch.empty_like(dhi)
-        nv.split_bf16(dctx, rows_pad, dhi, dlo)
-        N = T * H * W
-        pe = None
-        t0i = y0i = x0i = 0
-        pos_b = None
-        if gc.use_pos_emb:
-            pe, cap = gc.pos_tables(T, H, W, dev)
-            t0i, y0i, x0i = 0, cap, cap + H
-            pos_b = torch.zeros((rows_pad, pe.shape[0]), dtype=torch.float32, device=dev)
-            nv.linear(dctx, pe, None, pos_b, M=R)
-        nparts = nv.global_stream_nparts(N, rows_pad)
-        part = torch.empty((nparts, rows_pad, E), dtype=torch.float32, device=dev)
-        in_kernel = (pe is not None and nv.global_stream_has_marg(N, E, rows_pad, H, W, nparts) and ff_grad is None   # (d frames_feature reads dS)
-                     and clip_g is None)                                  # (so does clip-scale: the key norms scale it per token)
-        if in_kernel:
-            # many rows: the stream kernel leaves the t / y / x marginals of dS per token chunk -- the [rows, N] dS tensor is never written
-            pm = torch.empty((nparts, rows_pad, nv.global_stream_marg_width(H, W)), dtype=torch.float32, device=dev)
-            nv.global_stream_bwd(ff.view(N, E), N, dhi, dlo, pos_b, H, W, t0i, y0i, x0i, scores, ml, delta, None, part, R, part_marg=pm)
-            ybase, xbase = 16, 16 + 16 * ((H + 15) // 16)
-            mT = torch.zeros((R, T), dtype=torch.float32, device=dev)
-            mT.index_add_(1, nv.marg_frame_index(N, H, W, nparts, dev).reshape(-1), pm[:, :R, :8].permute(1, 0, 2).reshape(R, -1))
-            mY, mX = pm[:, :R, ybase:ybase + H].sum(0), pm[:, :R, xbase:xbase + W].sum(0)
-        else:
-            ds = torch.empty_like(scores)
-            nv.global_stream_bwd(ff.view(N, E), N, dhi, dlo, pos_b, H if pe is not None else 1, W if pe is not None else N,
-                                 t0i, y0i, x0i, scores, ml, delta, ds, part, R)
-            if ff_grad is not None:
-                # d frames_feature, global share: d x_n = sum_r dS[r, n] qt_r + p[r, n] dctx_r (scores and values are both x in the folded
-                # form; the positional terms do not depend on x), added to the local stage's share
-                qp_ = (q_in.float() @ Wq.t() + bq).view(nq, nh, hd)
-                qt_ = (att.scale * torch.einsum("hje,qhj->qhe", Wk.view(nh, hd, E), qp_)).reshape(R, E).contiguous()
-                have = ff_grad.get("d_ff") is not None
-                if not have:
-                    ff_grad["d_ff"] = torch.empty_like(ff)
-                if R <= 16 and E <= 1280:
-                    nv.global_dx(scores, ds, ml, qt_, dctx, N, ff_grad["d_ff"].view(N, E), accumulate=have)
-                else:
-                    # 32 distinct queries x heads (guide off / coarse / fine): a [N, 2 R] x [2 R, E] product -- plain library GEMMs
-                    pr = torch.exp(scores[:R, :N] - ml[:, 0:1]) / ml[:, 1:2]
-                    dxg = ds[:R, :N].t() @ qt_ + pr.t() @ dctx
-                    cur = ff_grad["d_ff"].view(N, E)
-                    cur.copy_(dxg + cur.float() if have else dxg)
-            if pe is not None:
-                dS = ds[:R, :N].view(R, T, H, W)
-                mT, mY, mX = dS.sum((2, 3)), dS.sum((1, 3)), dS.sum((1, 2))
-        if clip_g is None:
-            dqt = part.sum(0)[:R]                                          # sum_n dS[r, n] x_n
-            if pe is not None:
-                dqt = dqt + mT @ pe[t0i:t0i + T] + mY @ pe[y0i:y0i + H] + mX @ pe[x0i:x0i + W]
-            dqt = dqt.view(nq, nh, E)
-            # ---- through the fold: qt[q,h] = scale W_k,h^T (W_q q + b_q)[q, h-slice]  (ref :180-181,:193-197) ---------
-            scale = att.scale
-            qp = (q32 @ Wq.t() + bq).view(nq, nh, hd)
-            grads[P + "attn_layer.k_proj.weight"] = scale * torch.einsum("qhj,qhe->hje", qp, dqt).reshape(E, E)
-            grads[P + "attn_layer.k_proj.bias"] = torch.zeros(E, device=dev)   # a per-row logit shift: softmax cancels it exactly
-            dqp = scale * torch.einsum("hje,qhe->qhj", Wk.view(nh, hd, E), dqt).reshape(nq, E)
-        else:
-            dqp = _global_clip_backward(ff, pe, (t0i, y0i, x0i), scores, ds, R, nq, nh, hd, q32, Wq, bq, Wk, f32.get(A + "k_proj.bias"),
-                                        float(clip_g[0]), grads, P)
-        grads[P + "attn_layer.q_proj.weight"] = dqp.t() @ q32
-        grads[P + "attn_layer.q_proj.bias"] = _sum0(dqp)
-        if gc.use_guide in (None, "off"):
-            grads[P + "query"] = dqp @ Wq + dpre                           # the learnable queries: through q_proj and the residual
-        elif gc.use_guide == "fine" or gc.adapt_guide:                     # fine injection / adapted guide: the small-tensor graph
-            d_in = dqp @ Wq + dpre
-            direct_g = gc.use_guide == "direct"
-            _, dg = _query_chain_backward(gc, P, None if direct_g else gc.query.detach().float(), guide,
-                                          d_in.sum(0, keepdim=True) if direct_g else d_in, f32, grads, want_guide,
-                                          vis_param=None if direct_g else "query")
-            if want_guide and dg is not None:
-                d_guide += dg.reshape(d_guide.shape)
-        elif gc.use_guide == "coarse":                                     # injected = LN(query (1 + scale) + shift) (:369-372)
-            dvis, dg = _coarse_backward(gc.guide_injector, P + "guide_injector.", gc.query.detach().float(), guide,
-                                        dqp @ Wq + dpre, grads)
-            grads[P + "query"] = dvis
-            if want_guide:
-                d_guide += dg
-        elif want_guide:
-            d_guide += _sum0(dqp @ Wq + dpre)                            # direct: the injected query IS the guide (:352-368)
-        # (direct: global_compressor.query does not enter the forward, ref :352-368 uses only its shape: no gradient)
-    return grads, d_nl, d_fe, d_guide
+        _global_backward(st, gc, dout, n_local, global_saved)
+    return st.grads, d_nl, d_fe, st.d_guide
 
 
 class _AnyresFn(torch.autograd.Function):
