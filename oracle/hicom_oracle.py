@@ -38,6 +38,12 @@ Tensor = torch.Tensor
 
 LN_EPS = 1e-6  # projector.py:318,403,565  norm_layer=partial(nn.LayerNorm, eps=1e-6)
 
+# The oracle's two softmaxes, reached through module-level names: torch.softmax, both.  tests/softmax_mutants.py rebinds them inside
+# a `with` block to run the oracle with a deliberately wrong softmax (how far must an input family move the output of a wrong
+# kernel?); nothing else may.
+softmax_mha = torch.softmax          # mha(): the global stage (and the fine injector)
+softmax_local = torch.softmax        # local_context(): the window attention
+
 
 # --------------------------------------------------------------------------
 # projector-type string parsing            (projector.py:231-304)
@@ -156,7 +162,7 @@ def mha(query: Tensor, key: Tensor, value: Tensor, sd, prefix: str, num_heads: i
     kh = k.reshape(Lk, num_heads, hd).permute(1, 0, 2)
     vh = v.reshape(Lk, num_heads, hd).permute(1, 0, 2)
     scores = torch.matmul(qh, kh.transpose(1, 2)) * scale + bias   # :197
-    p = torch.softmax(scores.float(), dim=-1).to(q.dtype)          # :213 (fp32 softmax)
+    p = softmax_mha(scores.float(), dim=-1).to(q.dtype)          # :213 (fp32 softmax)
     o = torch.matmul(p, vh).permute(1, 0, 2).reshape(Lq, E)        # :215,223-224
     out = linear(o, sd, prefix + ".out_proj")                      # :226
     if return_scores:
@@ -320,7 +326,7 @@ def local_context(spec: dict, mode, sd, prefix: str, ff: Tensor, fe: Optional[Te
         s = s * logit_scale.exp() + logit_bias                     # :549
     else:
         s = s / math.sqrt(D)                                       # :551  (qk_dim, not head dim)
-    attn = torch.softmax(s, dim=-1)                                # input-dtype softmax (:549/:551)
+    attn = softmax_local(s, dim=-1)                                # input-dtype softmax (:549/:551)
     ctx = torch.einsum("nk,nkd->nd", attn, vw)                     # :553
     return ctx.reshape(*out_size, D), attn                         # :554-558
 

@@ -2,7 +2,14 @@
 item alone, plus the properties that only a batched kernel can break: isolation of the items' softmax states, the positional frame
 index restarting per item, masked tail tiles, several chunks per item, replay / view / plan-cache behaviour, refusals.
 
-Tolerance: <= 1e-3 max-abs on the fp32 output, the bar tests/test_gpu_parity.py holds forward() to."""
+Tolerance: <= 1e-3 max-abs on the fp32 output, the bar tests/test_gpu_parity.py holds forward() to.
+
+Input families (tests/many_item_inputs.py: `edge`, `edge_outlier`, `item_scales`): the same bar per item and per region (local rows, the
+32 global rows), HEAVY_REL x max |oracle out| under `edge_outlier`; tests/test_many_item_power.py shows on the oracle alone that a wrong
+softmax moves every region by at least 4 bars under them.  The test prints the per-region max-abs of every item.
+Measured on an MI355X: hidden 64, `edge` / `item_scales` local 3.7e-5 .. 8.9e-5 (3.6e-4 on the x 4 item), global 9.2e-7 .. 4.7e-6;
+`edge_outlier` local 5.6e-4 / 9.7e-4 of a bar of 1.5e-3 / 2.5e-3, global 3.2e-6 .. 5.1e-6; hidden 896 local 1.6e-4 .. 2.6e-4, global 5.7e-6 ..
+7.3e-6; hidden 3584 local 6.3e-4 / 8.2e-4 (max |out| 2.5 / 2.7), global 1.1e-5 / 1.3e-5."""
 import functools
 from types import SimpleNamespace
 
@@ -12,6 +19,7 @@ import torch
 
 import cases
 import hicom_amd
+import many_item_inputs as mi
 from gpu_util import build_module, dev_bf16
 from hicom_amd import synth
 from oracle import hicom_oracle as orc
@@ -21,6 +29,7 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-3
 D = cases.D
+NG = 32
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,6 +81,22 @@ def test_parity_per_item_against_oracle(key):
     if key[5]:
         nl = torch.from_numpy(batch_case(*key).newline).cuda()
         assert torch.equal(out[:, -33], nl.expand(key[0], -1))          # the newline row in front of the global rows, bit for bit
+
+
+@pytest.mark.parametrize("id", [e.id for e in mi.entries("batch")])
+def test_input_families_per_item_and_region_against_oracle(id):
+    """The cases of tests/many_item_inputs.py for this step under the families `edge`, `edge_outlier`, `item_scales`: softmax mass on an
+    item's first token, both sides of its first tile boundary, of its chunk boundaries and its last token (tests/test_many_item_power.py:
+    a wrong softmax moves each region by >= 4 bars).  Per item and per region (local rows, the 32 global rows); bar: TOL, and
+    HEAVY_REL x max |oracle out| under `edge_outlier`."""
+    c, want = mi.build(id), mi.oracle_outputs(id)
+    out = run_batch(c, **({} if c.entry.chunks is None else {"chunks": c.entry.chunks}))
+    bad = []
+    for b in range(c.B):
+        assert out[b].dtype == torch.float32 and tuple(out[b].shape) == want[b].shape, (b, tuple(out[b].shape), want[b].shape)
+        assert torch.equal(out[b][-NG:], out[b][-1:].expand(NG, -1)), f"item {b}: the {NG} global rows differ"
+        bad += mi.check_item(c.entry, f"item {b}", out[b].cpu().numpy(), want[b])
+    assert not bad, f"{id}: " + "; ".join(bad)
 
 
 def test_output_dtype_follows_the_module():

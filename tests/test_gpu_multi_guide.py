@@ -5,7 +5,13 @@ plan-cache behaviour, refusals.
 
 Tolerance: <= 1e-3 max-abs on the fp32 output against the oracle, the bar tests/test_gpu_parity.py holds forward() to.  Against forward()
 itself (each side within 1e-3 of the oracle) the bar is 2e-3; measured on an MI355X: 1.2e-5 .. 3.2e-5 against the oracle, 9.0e-7 .. 2.3e-5
-against forward()."""
+against forward().
+
+Input families (tests/many_item_inputs.py: `edge`, `edge_outlier`, `item_scales`): the same bar per item and per region (local rows, the
+32 global rows), HEAVY_REL x max |oracle out| under `edge_outlier`; tests/test_many_item_power.py shows on the oracle alone that a wrong
+softmax moves every region by at least 4 bars under them.  The test prints the per-region max-abs of every item.
+Measured on an MI355X: `edge` local 2.8e-5 .. 1.9e-4, global 1.0e-6 .. 2.2e-6; hidden 896 local 4.2e-4 .. 5.1e-4, global 5.8e-6 .. 7.0e-6;
+`edge_outlier` local 4.9e-4 .. 6.1e-4 of bars of 1.5e-3 .. 1.9e-3, global 2.9e-6 .. 5.2e-6."""
 import functools
 from types import SimpleNamespace
 
@@ -15,6 +21,7 @@ import torch
 
 import cases
 import hicom_amd
+import many_item_inputs as mi
 from gpu_util import build_module, dev_bf16
 from hicom_amd import synth
 from oracle import hicom_oracle as orc
@@ -110,6 +117,22 @@ def test_without_frames_embed_the_keys_are_frames_feature():
     # not vacuous: the two references lie further apart than two tolerances, so no output is within TOL of both
     assert np.abs(want_fe[0][:-NG] - want_ff[0][:-NG]).max() > 2 * TOL
     check_against_oracle(VIDEO3, with_fe=False)
+
+
+@pytest.mark.parametrize("id", [e.id for e in mi.entries("multi_guide")])
+def test_input_families_per_item_and_region_against_oracle(id):
+    """The cases of tests/many_item_inputs.py for this step under the families `edge`, `edge_outlier`, `item_scales`: softmax mass on an
+    item's first token, both sides of its first tile boundary, of its chunk boundaries and its last token (tests/test_many_item_power.py:
+    a wrong softmax moves each region by >= 4 bars).  Per item and per region (local rows, the 32 global rows); bar: TOL, and
+    HEAVY_REL x max |oracle out| under `edge_outlier`."""
+    c, want = mi.build(id), mi.oracle_outputs(id)
+    out = run_mg(c, with_fe=c.entry.with_fe)
+    bad = []
+    for b in range(c.Q):
+        assert out[b].dtype == torch.float32 and tuple(out[b].shape) == want[b].shape, (b, tuple(out[b].shape), want[b].shape)
+        assert torch.equal(out[b][-NG:], out[b][-1:].expand(NG, -1)), f"guide {b}: the {NG} global rows differ"
+        bad += mi.check_item(c.entry, f"guide {b}", out[b].cpu().numpy(), want[b])
+    assert not bad, f"{id}: " + "; ".join(bad)
 
 
 # ---- isolation and position independence ---------------------------------------------------------------------------------------------

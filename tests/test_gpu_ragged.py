@@ -4,7 +4,13 @@ that changes between neighbours, per-item packing, isolation, permutation, the p
 division, replay / view / plan-cache behaviour, refusals.
 
 Tolerance: <= 1e-3 max-abs on the fp32 output, the bar tests/test_gpu_parity.py holds forward() and tests/test_gpu_batch.py holds
-forward_batch to."""
+forward_batch to.
+
+Input families (tests/many_item_inputs.py: `edge`, `edge_outlier`, `item_scales`): the same bar per item and per region (local rows, the
+32 global rows), HEAVY_REL x max |oracle out| under `edge_outlier`; tests/test_many_item_power.py shows on the oracle alone that a wrong
+softmax moves every region by at least 4 bars under them.  The test prints the per-region max-abs of every item.
+Measured on an MI355X: `edge` local 4.4e-5 .. 8.5e-5, global 9.1e-7 .. 1.4e-6; `item_scales` local 6.9e-5 and 4.1e-4 (the x 4 item), global
+1.0e-6 / 5.8e-6; `edge_outlier` local 5.4e-4 .. 8.6e-4 of bars of 1.7e-3 .. 2.4e-3, global 2.6e-6 .. 6.0e-6."""
 import functools
 from types import SimpleNamespace
 
@@ -14,6 +20,7 @@ import torch
 
 import cases
 import hicom_amd
+import many_item_inputs as mi
 from gpu_util import build_module, dev_bf16
 from hicom_amd import ragged, synth
 from oracle import hicom_oracle as orc
@@ -84,6 +91,22 @@ def test_mixed_parity_6x6():
     """Offsets 36 / 180 / 216 / 504 tokens, a masked tail tile in every item, kt 1 / 4 / 1 / 4 / 1, item 2 a 1-frame "video"."""
     out = check_against_oracle(MIX6)
     assert [o.shape[0] for o in out] == [36, 36, 36, 40, 36]
+
+
+@pytest.mark.parametrize("id", [e.id for e in mi.entries("ragged")])
+def test_input_families_per_item_and_region_against_oracle(id):
+    """The cases of tests/many_item_inputs.py for this step under the families `edge`, `edge_outlier`, `item_scales`: softmax mass on an
+    item's first token, both sides of its first tile boundary, of its chunk boundaries and its last token (tests/test_many_item_power.py:
+    a wrong softmax moves each region by >= 4 bars).  Per item and per region (local rows, the 32 global rows); bar: TOL, and
+    HEAVY_REL x max |oracle out| under `edge_outlier`."""
+    c, want = mi.build(id), mi.oracle_outputs(id)
+    out = run_ragged(c)
+    bad = []
+    for b in range(c.B):
+        assert out[b].dtype == torch.float32 and tuple(out[b].shape) == want[b].shape, (b, tuple(out[b].shape), want[b].shape)
+        assert torch.equal(out[b][-NG:], out[b][-1:].expand(NG, -1)), f"item {b}: the {NG} global rows differ"
+        bad += mi.check_item(c.entry, f"item {b}", out[b].cpu().numpy(), want[b])
+    assert not bad, f"{id}: " + "; ".join(bad)
 
 
 def test_device_tables_equal_the_host_mirror():

@@ -3,7 +3,13 @@ tokens of the call and the LayerNorm + alpha blend fused into the per-item windo
 local_window_adapt_ctx16), against the CPU oracle run on each item alone.
 
 Tolerance: <= 1e-3 max-abs on the fp32 output, the bar tests/test_gpu_parity.py, test_gpu_batch.py and test_gpu_ragged.py hold every
-forward path to.  Grids are 6x6 / 9x9, width 1152, hidden 896.  The helpers restate those of test_gpu_ragged.py / test_gpu_batch.py."""
+forward path to.  Grids are 6x6 / 9x9, width 1152, hidden 896.  The helpers restate those of test_gpu_ragged.py / test_gpu_batch.py.
+
+Input families (tests/many_item_inputs.py: `edge`, `edge_outlier`, `item_scales`): the same bar per item and per region (local rows, the
+32 global rows), HEAVY_REL x max |oracle out| under `edge_outlier`; tests/test_many_item_power.py shows on the oracle alone that a wrong
+softmax moves every region by at least 4 bars under them.  The test prints the per-region max-abs of every item.
+Measured on an MI355X (hidden 896, max |out| 1.1 .. 1.8): `edge` local 1.4e-4 .. 3.7e-4, global 4.9e-6 .. 6.5e-6; `edge_outlier` local
+1.1e-3 .. 1.8e-3 of bars of 3.5e-3 .. 5.7e-3, global 1.5e-5 .. 2.4e-5."""
 import functools
 from types import SimpleNamespace
 
@@ -13,6 +19,7 @@ import torch
 
 import cases
 import hicom_amd
+import many_item_inputs as mi
 from gpu_util import build_module, dev_bf16
 from hicom_amd import native as nv
 from hicom_amd import ragged, synth
@@ -120,6 +127,22 @@ def test_one_adaptor_only(recipe):
     """The NULL-stream branches of the window kernel and the single-problem GEMM launches."""
     check_not_vacuous(MIX6 + (recipe,))
     check_ragged(MIX6 + (recipe,))
+
+
+@pytest.mark.parametrize("id", [e.id for e in mi.entries("adapt")])
+def test_input_families_per_item_and_region_against_oracle(id):
+    """The cases of tests/many_item_inputs.py for this step under the families `edge`, `edge_outlier`, `item_scales`: softmax mass on an
+    item's first token, both sides of its first tile boundary, of its chunk boundaries and its last token (tests/test_many_item_power.py:
+    a wrong softmax moves each region by >= 4 bars).  Per item and per region (local rows, the 32 global rows); bar: TOL, and
+    HEAVY_REL x max |oracle out| under `edge_outlier`."""
+    c, want = mi.build(id), mi.oracle_outputs(id)
+    out = run_ragged(c)
+    bad = []
+    for b in range(c.B):
+        assert out[b].dtype == torch.float32 and tuple(out[b].shape) == want[b].shape, (b, tuple(out[b].shape), want[b].shape)
+        assert torch.equal(out[b][-NG:], out[b][-1:].expand(NG, -1)), f"item {b}: the {NG} global rows differ"
+        bad += mi.check_item(c.entry, f"item {b}", out[b].cpu().numpy(), want[b])
+    assert not bad, f"{id}: " + "; ".join(bad)
 
 
 # ---- 3 -------------------------------------------------------------------------------------------------------------------------
