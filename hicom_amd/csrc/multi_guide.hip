@@ -15,64 +15,10 @@
 // Launches 1-2 and 6-11, the workspace regions and the common checks are segment_host.hpp's, with M = Q; this file holds the local kernel,
 // the four launches that know a guide, the chunk policy and the step's own limits.  The packed-row layout integers are those of the batched
 // step and hold for every guide.
+#include "multi_window.hpp"
 #include "segment_host.hpp"
 
 namespace hicom {
-
-constexpr int kGuideGroup = 4;      // guides a wave carries through one walk over a window's rows (72 query / accumulator floats per lane)
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Local stage: the window of local_window_ctx16 (segment_item.hpp) for NG guides at once.  Each key row meets NG queries, each value
-// row NG accumulators; every guide keeps its own logit, softmax and accumulator chain, written as the single-guide loop writes them,
-// so a guide's context does not depend on NG, on its place in the group or on its neighbours.  qrows: the group's first guide row;
-// o: its context row, the next guide's `plane` elements further.
-// ---------------------------------------------------------------------------------------------------------------------------------
-template <int NV, int NG>
-__device__ __forceinline__ void multi_window_ctx16(const uint16_t* key, const uint16_t* value, const uint16_t* qrows, const WindowGeom& g,
-                                                   int lane, float scale, _Float16* o, long plane) {
-    constexpr int D = NV * 384;
-    float sc[NG];
-    {
-        float q[NG][NV][6];
-#pragma unroll
-        for (int u = 0; u < NG; ++u) {
-            load_row<NV>(qrows + (long)u * D, lane, q[u]);
-            sc[u] = -3.0e38f;
-        }
-        for (int i = 0; i < g.WIN; ++i) {
-            float k[NV][6];
-            load_row<NV>(key + g.token_of(i) * D, lane, k);
-#pragma unroll
-            for (int u = 0; u < NG; ++u) {
-                const float d = wave_sum_fast(row_dot<NV>(q[u], k)) * scale;
-                if (lane == i) sc[u] = d;
-            }
-        }
-    }
-    float pw[NG];
-#pragma unroll
-    for (int u = 0; u < NG; ++u) {
-        const float mx = wave_max_fast(sc[u]);
-        const float e = lane < g.WIN ? expf(sc[u] - mx) : 0.f;
-        pw[u] = e / wave_sum_fast(e);
-    }
-    float acc[NG][NV][6];
-#pragma unroll
-    for (int u = 0; u < NG; ++u) row_zero<NV>(acc[u]);
-    for (int i = 0; i < g.WIN; ++i) {
-        float v[NV][6];
-        load_row<NV>(value + g.token_of(i) * D, lane, v);
-#pragma unroll
-        for (int u = 0; u < NG; ++u) row_axpy<NV>(__shfl(pw[u], i, 64), v, acc[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < NG; ++u)
-#pragma unroll
-        for (int s = 0; s < NV; ++s)
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-                o[(long)u * plane + 384 * s + 6 * lane + j] = (_Float16)fminf(fmaxf(acc[u][s][j], -65504.f), 65504.f);
-}
 
 // One wave per window of the clip's grid; for Q > kGuideGroup the wave walks further groups over the same window (its rows are then
 // expected to come from L2).  ctx16: [Q][nwin][D].

@@ -45,6 +45,7 @@ EXPORTS = (
     "hicom_compressor_batch_adapt_fwd", "hicom_compressor_batch_adapt_workspace_bytes",
     "hicom_compressor_ragged_adapt_fwd", "hicom_compressor_ragged_adapt_workspace_bytes", "hicom_compressor_ragged_adapt_prepare",
     "hicom_compressor_multiguide_fwd", "hicom_compressor_multiguide_workspace_bytes",
+    "hicom_compressor_ragged_multiguide_fwd", "hicom_compressor_ragged_multiguide_workspace_bytes", "hicom_compressor_ragged_multiguide_prepare",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -213,6 +214,14 @@ class CompressorMultiGuideArgs(C.Structure):
     _fields_ = [(("Q" if name == "B" else name), ctype) for name, ctype in CompressorBatchArgs._fields_]
 
 
+class CompressorRaggedMultiGuideArgs(C.Structure):
+    """hicom_compressor_ragged_multiguide_args (include/hicom_hip.h): the fields of hicom_compressor_ragged_args with the HOST array of the
+    items' guide counts and its length behind `items` -- field order and types must match the header."""
+    _fields_ = [f for name, ctype in CompressorRaggedArgs._fields_ for f in
+                ([(name, ctype)] + ([("guide_counts", C.POINTER(C.c_int32)), ("n_guide_counts", C.c_int32), ("reserved_", C.c_int32)]
+                                    if name == "items" else []))]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -326,6 +335,9 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
     L.hicom_compressor_multiguide_fwd.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
     L.hicom_compressor_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
+    L.hicom_compressor_ragged_multiguide_fwd.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
+    L.hicom_compressor_ragged_multiguide_prepare.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
+    L.hicom_compressor_ragged_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -339,6 +351,7 @@ def lib() -> C.CDLL:
     L.hicom_compressor_batch_adapt_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_adapt_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_multiguide_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_ragged_multiguide_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -710,6 +723,18 @@ def compressor_multiguide_workspace(args: CompressorMultiGuideArgs) -> int:
 
 def compressor_multiguide_fwd(args: CompressorMultiGuideArgs):
     _seg_call(args, "multiguide", "fwd")
+
+
+def compressor_ragged_multiguide_workspace(args: CompressorRaggedMultiGuideArgs) -> int:
+    return _seg_call(args, "ragged_multiguide", "workspace_bytes", "forward_ragged_multi_guide")
+
+
+def compressor_ragged_multiguide_prepare(args: CompressorRaggedMultiGuideArgs):
+    _seg_call(args, "ragged_multiguide", "prepare")
+
+
+def compressor_ragged_multiguide_fwd(args: CompressorRaggedMultiGuideArgs):
+    _seg_call(args, "ragged_multiguide", "fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -821,6 +821,7 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_batch_plans", None)
         self.__dict__.pop("_ragged_plans", None)
         self.__dict__.pop("_multi_guide_plans", None)
+        self.__dict__.pop("_ragged_multi_guide_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1106,6 +1107,28 @@ class HIComProjector(nn.Module):
         thirteen-launch sequence); from four guides up this call wins, 1.2 x at Q = 6 and 1.75 x at Q = 16 on 64 frames."""
         from . import multi_guide
         return multi_guide.run_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
+
+    def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
+                                   chunks=None):
+        """B items of UNEQUAL length and mixed modality, item i with its own Q_i instructions, in one native call -- a Video-MME style
+        evaluation batch (several videos x 3 questions), or a batch of multi-question items.  frames_feature / frames_embed bf16
+        [sum T_i, H, W, E], split_sizes and modals as for forward_ragged (frames_embed may be None); guide_counts the B positive ints Q_i,
+        1 <= Q_i <= 32; guide_embeds bf16 [sum Q_i, E], the guides of item i in the rows [sum_(j<i) Q_j, + Q_i).  Returns the list of B
+        tensors [Q_i, rows_i, hidden], views that tile ONE storage in item-major, then guide-major order; out[i][q] is laid out as
+        forward() on item i alone with its guide q and equals it to the kernels' rounding.  Every item's tokens are read once by the
+        local stage and once per 32 folded rows by the global stream (Q_i <= 3: one pass, Q_i <= 7: two, Q_i = 32: nine); twelve launches
+        whatever B, the Q_i and the mix are (csrc/ragged_multi_guide.hip).
+        The plain release recipe only (local + global compressor, use_guide="direct", no adaptors, no clip scale, bf16 module and
+        inputs, no anyres dicts, every item's windows partition its grid exactly): everything else raises NotImplementedError /
+        ValueError in front of the first launch.  Inference only: with autograd on and trainable parameters it raises.
+        `chunks`: token chunks per item and pass of the global stream, each clamped to the item's 16-token tiles (None: every item gets
+        its share of 2 x #CUs work units by tiles x passes).  With `chunks` given, a pair's result depends on its item's tokens, its own
+        guide and its row's pass only.
+        Which path when: DESIGN.md §3.9 has the measured table against the loop of forward_multi_guide, forward_ragged on replicated
+        tokens and the loop of forward()."""
+        from . import ragged_multi_guide
+        return ragged_multi_guide.run_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals,
+                                                         image_newline, chunks)
 
     def forward_stepwise(self, frames_feature, frames_embed, guide_embed, modal, image_newline=None):
         """Same result, one C-ABI call per operator (anyres dict inputs; also the cross-check of the

@@ -5,7 +5,8 @@ and the plan-cache protocol.  The modules keep what depends on how items are des
 modals and the table arithmetic.
 
 Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`, `proj._multi_guide_plans`: at most MAX_PLANS each),
-like engine.run_dense's; the input / output pointers are patched per call."""
+like engine.run_dense's; the input / output pointers are patched per call.  forward_ragged_multi_guide (ragged_multi_guide.py: the product
+of the last two, `proj._ragged_multi_guide_plans`) is built on the same functions."""
 from __future__ import annotations
 
 import math

@@ -1021,6 +1021,60 @@ typedef struct hicom_compressor_multiguide_args {
 int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compressor_multiguide_args* args);
 int hicom_compressor_multiguide_fwd(const hicom_compressor_multiguide_args* args);
 
+/* ---- ragged multi-guide compressor step: B items of unequal length, item i with its own Q_i instructions -----------
+ * The product of the ragged and the multi-guide step: a Video-MME evaluation batch (several videos x 3 questions), or a batch of
+ * multi-question items through hicom/model/hicom_arch.py:146-180.  A PAIR is one (item, guide); pairs are numbered item-major, then
+ * guide-major, M = sum Q_i of them.  Pair (i, q) of the output equals hicom_compressor_fwd on item i alone with its guide q to the
+ * kernels' rounding.  The plain release recipe only (no adaptors), bf16.  Every item's tokens are read once by the local stage and once
+ * per pass of 32 folded rows by the global stream (nh = 9: one pass for Q_i <= 3, two for Q_i <= 7, nine at Q_i = 32); the launch
+ * sequence is the twelve launches of the ragged step whatever B, the Q_i and the mix are.
+ *   ff, fe   : bf16 [sum T_i, H, W, E] (fe NULL: the local keys are ff), as in hicom_compressor_ragged_args
+ *   guide    : bf16 [M, E]; the guides of item i are the rows [sum_{j<i} Q_j, + Q_i)
+ *   items    : HOST array of B descriptors, as in hicom_compressor_ragged_args; the packed-row layout of an item holds for each of
+ *              its pairs
+ *   guide_counts, n_guide_counts : HOST array of the Q_i and its length, which must be B; 1 <= Q_i <= 32
+ *   chunks   : token chunks per item and pass of the global stream, each clamped to the item's 16-token tiles and to 64; 0 = the
+ *              item's share of 2 x #CUs work units by tiles x passes.  A work unit {item, first tile, last tile, row pass, partial-state
+ *              slot} streams tokens of ONE item, tiles counted from the item's first token, for 32 densely packed folded rows (guide q
+ *              of an item owns rows nh q .. nh q + nh - 1 of the item's row space)
+ *   out      : [sum Q_i rows_i, ldo] of out_dt (bf16 | f32): the pairs' packed rows follow each other
+ *   ws       : hicom_compressor_ragged_multiguide_workspace_bytes(args) bytes, 256-byte aligned.  Its head is a table region (item
+ *              table, work units, window -> item lookup, pair table, row -> pair lookup) that
+ *              hicom_compressor_ragged_multiguide_prepare(args) derives on the host and writes ONCE per (items, guide counts, shape,
+ *              chunks, ws): it copies to the device and synchronises `stream`, so it runs outside the hot loop and outside a capture.
+ * Limits (HICOM_EUNSUP beyond them; the device tables hold int32 offsets): B <= 4096 items, M <= 4096 pairs (grid y of the merge);
+ * per item T H W < 2^27 tokens; over the call sum N_i + 16 B < 2^27 tokens, sum Q_i ceil16(N_i) < 2^27 token x guide products (the
+ * logits are 32 rows per pass and token, their offsets counted in 16 floats) and sum Q_i windows_i < 2^20 context rows; the grid,
+ * window and merge-LDS limits of hicom_compressor_ragged_args.
+ * hicom_compressor_ragged_multiguide_fwd then only launches: no copy, no synchronisation, no allocation, O(B) integer work on the host.
+ * It trusts the table region as hicom_compressor_ragged_fwd does. */
+typedef struct hicom_compressor_ragged_multiguide_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t B, H, W, E, hidden, ks, nh, P;
+    float l_scale;
+    int32_t chunks;
+    const hicom_ragged_item* items;                 /* HOST memory, B entries */
+    const int32_t* guide_counts;                    /* HOST memory, n_guide_counts entries */
+    int32_t n_guide_counts, reserved_;
+    const void *lw0_f16, *lb0, *lw2_f16, *lb2;      /* local readout: fp16 copies of the weights, bf16 biases */
+    const void *wq, *bq, *wk, *wv, *bv, *wo, *bo;   /* global attention, bf16 */
+    const void *gw0, *gb0, *gw2, *gb2;              /* global readout, bf16 */
+    const float* pe;
+    const float* kpe;
+    int32_t t_index0, y_index0, x_index0, out_dt;
+    void* out;
+    int64_t ldo;
+    const void* newline;
+    void* ws;
+    int64_t ws_bytes;
+    void* stream;
+} hicom_compressor_ragged_multiguide_args;
+int64_t hicom_compressor_ragged_multiguide_workspace_bytes(const hicom_compressor_ragged_multiguide_args* args);
+int hicom_compressor_ragged_multiguide_prepare(const hicom_compressor_ragged_multiguide_args* args);
+int hicom_compressor_ragged_multiguide_fwd(const hicom_compressor_ragged_multiguide_args* args);
+
 #ifdef __cplusplus
 }
 #endif
