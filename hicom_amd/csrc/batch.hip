@@ -61,8 +61,8 @@ __global__ __launch_bounds__(256, 2) void batch_global_stream_kernel(BatchStream
     const int part = blockIdx.x, item = blockIdx.y, nparts = gridDim.x;
     const int tb = (int)(((long)p.ntiles * part) / nparts);
     const int te = (int)(((long)p.ntiles * (part + 1)) / nparts);
-    stream_segment<NB>(p.c, p.x + (long)item * p.N * E, p.N, tb, te, item, p.scores + (long)item * 16 * p.score_stride, p.score_stride,
-                       (long)item * nparts + part);
+    stream_segment<NB, 1>(p.c, p.x + (long)item * p.N * E, p.N, tb, te, 0, p.c.rows, (long)item * p.c.rows, p.scores + (long)item * 16 * p.score_stride,
+                          p.score_stride, (long)item * nparts + part, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -172,10 +172,10 @@ struct BatchItem {
         p.scores = (float*)(ws() + l.s.scores); p.score_stride = l.score_stride;
         static bool attr_set = false;
         if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(batch_global_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, kSegStreamSmem);
+            hipFuncSetAttribute(reinterpret_cast<const void*>(batch_global_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, seg_stream_smem(1));
             attr_set = true;
         }
-        HICOM_LAUNCH(batch_global_stream_kernel<9>, dim3((unsigned)l.chunks, (unsigned)a->B), dim3(256), kSegStreamSmem, s(), p);
+        HICOM_LAUNCH(batch_global_stream_kernel<9>, dim3((unsigned)l.chunks, (unsigned)a->B), dim3(256), seg_stream_smem(1), s(), p);
         return seg_check_launch(kWho, "global stream");
     }
 

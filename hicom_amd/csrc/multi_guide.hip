@@ -30,17 +30,7 @@ __global__ __launch_bounds__(256) void multi_guide_local_kernel(const uint16_t* 
     const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (win >= nwin) return;
     const WindowGeom g(at, ay, ax, win);
-    const long plane = (long)nwin * D;
-    for (int g0 = 0; g0 < Q; g0 += kGuideGroup) {
-        const uint16_t* q = guide + (long)g0 * D;
-        _Float16* o = ctx16 + (long)g0 * plane + (long)win * D;
-        switch (Q - g0 < kGuideGroup ? Q - g0 : kGuideGroup) {      // (wave-uniform)
-            case 1: multi_window_ctx16<NV, 1>(key, value, q, g, lane, scale, o, plane); break;
-            case 2: multi_window_ctx16<NV, 2>(key, value, q, g, lane, scale, o, plane); break;
-            case 3: multi_window_ctx16<NV, 3>(key, value, q, g, lane, scale, o, plane); break;
-            default: multi_window_ctx16<NV, 4>(key, value, q, g, lane, scale, o, plane); break;
-        }
-    }
+    multi_window_guides_ctx16<NV>(key, value, guide, 0, Q, g, lane, scale, ctx16 + (long)win * D, (long)nwin * D);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -60,4 +60,23 @@ __device__ __forceinline__ void multi_window_ctx16(const uint16_t* key, const ui
                 o[(long)u * plane + 384 * s + 6 * lane + j] = (_Float16)fminf(fmaxf(acc[u][s][j], -65504.f), 65504.f);
 }
 
+// All Q guides of one window, in groups of kGuideGroup (the window's rows are expected to come from L2 from the second group on).
+// guide: the guide rows, the window's first guide is row q0; o: the first guide's context row, guide q's `plane` elements times q
+// further.  Q and q0 must be wave-uniform.
+template <int NV>
+__device__ __forceinline__ void multi_window_guides_ctx16(const uint16_t* key, const uint16_t* value, const uint16_t* guide, int q0, int Q,
+                                                          const WindowGeom& g, int lane, float scale, _Float16* o, long plane) {
+    constexpr int D = NV * 384;
+    for (int g0 = 0; g0 < Q; g0 += kGuideGroup) {
+        const uint16_t* q = guide + (long)(q0 + g0) * D;
+        _Float16* og = o + (long)g0 * plane;
+        switch (Q - g0 < kGuideGroup ? Q - g0 : kGuideGroup) {
+            case 1: multi_window_ctx16<NV, 1>(key, value, q, g, lane, scale, og, plane); break;
+            case 2: multi_window_ctx16<NV, 2>(key, value, q, g, lane, scale, og, plane); break;
+            case 3: multi_window_ctx16<NV, 3>(key, value, q, g, lane, scale, og, plane); break;
+            default: multi_window_ctx16<NV, 4>(key, value, q, g, lane, scale, og, plane); break;
+        }
+    }
+}
+
 }  // namespace hicom

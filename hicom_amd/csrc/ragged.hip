@@ -12,7 +12,9 @@
 //   * window -> item and output row -> item lookups (one int each) for the local stage and the placement.
 // The stacked tensor is not one window grid (kt differs between neighbours), so the local stage builds each window's geometry from its
 // item's own (T, kt) and offsets the token index by the item's first token.  The four lookups are wave-uniform loads through a
-// kernel-argument pointer with a uniform index: they land in SGPRs.  hicom_compressor_ragged_fwd only launches.
+// kernel-argument pointer with a uniform index: they land in SGPRs.  hicom_compressor_ragged_fwd only launches.  The stream is
+// stream_segment (segment_item.hpp) with one row group; the per-item requirements, the chunk share, the tile ranges and the table upload
+// are segment_host.hpp's, shared with ragged_multi_guide.hip.
 #include <vector>
 
 #include "segment_host.hpp"
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(256) void ragged_local_attn_adapt_kernel(const uint
                                  guide + (long)item * D, g, lane, scale, ctx16 + (long)win * D);
 }
 
-// ---- 4: segmented global stream, one workgroup per work unit ----
+// ---- 4: segmented global stream, one workgroup per work unit (one row group: the item's nh rows) ----
 struct RaggedStreamParams {
     SegStreamParams c;
     const uint16_t* x;      // [sum N_i][E]
@@ -82,7 +84,8 @@ __global__ __launch_bounds__(256, 2) void ragged_global_stream_kernel(RaggedStre
     constexpr int E = NB * 128;
     const int4 u = p.units[blockIdx.x];
     const int N = p.items[u.x].N, tok0 = p.items[u.x].tok0, soff = p.items[u.x].score_off;
-    stream_segment<NB>(p.c, p.x + (long)tok0 * E, N, u.y, u.z, u.x, p.scores + (long)soff * 16, (long)((N + 15) / 16 * 16), (long)u.w);
+    stream_segment<NB, 1>(p.c, p.x + (long)tok0 * E, N, u.y, u.z, 0, p.c.rows, (long)u.x * p.c.rows, p.scores + (long)soff * 16, (long)((N + 15) / 16 * 16),
+                          (long)u.w, 0);
 }
 
 // ---- 5: merge per (item, head), grid = (rows, B), LDS sized for the longest item ----
@@ -127,23 +130,12 @@ namespace {
 
 constexpr const char* kWho = "compressor_ragged";
 
-// work units of an item with `ntiles` tiles: its share of 2 #CUs by tile count, rounded to nearest (a function of ntiles, the call's
-// tile total and #CUs only: permuting the items permutes the division); `chunks` > 0 overrides the share
-int ragged_chunks(long ntiles, long ntiles_sum, int chunks, int ncu) {
-    long c = chunks > 0 ? chunks : (2L * ncu * ntiles + ntiles_sum / 2) / ntiles_sum;
-    if (c > ntiles) c = ntiles;
-    if (c > kSegMaxChunks) c = kSegMaxChunks;
-    return (int)(c < 1 ? 1 : c);
-}
-
 struct RaggedLayout {
     long items, units, win_item, row_item, table_bytes;     // the table region, in front of the step's own regions
     SegLayout s;
     long rows, ntiles_sum;
     int max_T, wps;
 };
-
-inline long item_windows(const hicom_ragged_item& it, int wps) { return (long)(it.T / it.kt) * wps; }
 
 // ad: the k / v adaptors of the local stage, NULL for the plain recipe (hicom_compressor_ragged_*)
 RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
@@ -162,7 +154,7 @@ RaggedLayout ragged_layout(const hicom_compressor_ragged_args* a, const SegAdapt
         if (it.T > l.max_T) l.max_T = it.T;
     }
     const int ncu = a->chunks > 0 ? 0 : num_cus();
-    for (int i = 0; i < a->B; ++i) n.slots += ragged_chunks((a->items[i].T * HW + 15) / 16, l.ntiles_sum, a->chunks, ncu);
+    for (int i = 0; i < a->B; ++i) n.slots += seg_share_chunks((a->items[i].T * HW + 15) / 16, l.ntiles_sum, a->chunks, ncu);
     n.rows = (long)a->B * a->nh;
     n.part_rows = n.slots * 16;
     long off = 0;
@@ -183,22 +175,10 @@ int ragged_check(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP, "compressor_ragged: needs an exact window partition (H=%d W=%d, windows %dx%d)",
                   a->H, a->W, a->ks, a->ks);
-    const int wps = (a->H / a->ks) * (a->W / a->ks);
-    long tokens = 0;
-    int max_T = 0;
-    for (int i = 0; i < a->B; ++i) {
-        const hicom_ragged_item& it = a->items[i];
-        HICOM_REQUIRE(it.T > 0 && it.kt > 0 && it.n_global_rows > 0 && it.nl_group >= 0 && it.nl_count >= 0, HICOM_EINVAL, "compressor_ragged: item %d: bad shape", i);
-        HICOM_REQUIRE(it.T % it.kt == 0, HICOM_EUNSUP, "compressor_ragged: item %d needs an exact window partition (T=%d, temporal window %d)", i, it.T, it.kt);
-        HICOM_REQUIRE(it.kt * a->ks * a->ks <= 64, HICOM_EUNSUP, "compressor_ragged: item %d: windows of %d tokens (<= 64)", i, it.kt * a->ks * a->ks);
-        HICOM_REQUIRE((long)it.T * a->H * a->W < (1L << 27), HICOM_EUNSUP, "compressor_ragged: item %d: too many tokens", i);
-        const long w = item_windows(it, wps);
-        HICOM_REQUIRE(!it.nl_group || w % it.nl_group == 0, HICOM_EINVAL, "compressor_ragged: item %d: output layout", i);
-        HICOM_REQUIRE(it.nl_count == 0 || (it.nl_step > 0 && it.nl_first >= 0 && it.nl_first + (long)(it.nl_count - 1) * it.nl_step < w + it.nl_count),
-                      HICOM_EINVAL, "compressor_ragged: item %d: newline rows", i);
-        tokens += (long)it.T * a->H * a->W;
-        if (it.T > max_T) max_T = it.T;
-    }
+    long tokens;
+    int max_T;
+    st = seg_check_ragged_items(kWho, a, tokens, max_T, [](int) { return HICOM_OK; });
+    if (st != HICOM_OK) return st;
     // (item offsets and the logits' offsets, 16 floats per token and one padded tile per item, are ints on the device)
     HICOM_REQUIRE(tokens + 16L * a->B < (1L << 27), HICOM_EUNSUP, "compressor_ragged: too many tokens in one call");
     st = seg_check_merge_lds(kWho, a, max_T);
@@ -229,26 +209,21 @@ int ragged_prepare(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
     for (int i = 0; i < a->B; ++i) {
         const hicom_ragged_item& h = a->items[i];
         const long N = h.T * HW, w = item_windows(h, l.wps), ntiles = (N + 15) / 16;
-        const int chunks = ragged_chunks(ntiles, l.ntiles_sum, a->chunks, ncu);
+        const int chunks = seg_share_chunks(ntiles, l.ntiles_sum, a->chunks, ncu);
         RaggedItem& d = items[i];
         d.tok0 = (int)tok; d.N = (int)N; d.T = h.T; d.kt = h.kt; d.win0 = (int)win; d.slot0 = (int)slot; d.chunks = chunks;
         d.score_off = (int)score; d.row0 = (int)row; d.global_row0 = (int)(w + h.nl_count);
         d.nl_group = h.nl_group; d.nl_count = h.nl_count; d.nl_first = h.nl_first; d.nl_step = h.nl_step > 0 ? h.nl_step : 1;
         for (int c = 0; c < chunks; ++c) {
             int* u = units + 4 * (slot + c);
-            u[0] = i; u[1] = (int)(ntiles * c / chunks); u[2] = (int)(ntiles * (c + 1) / chunks); u[3] = (int)(slot + c);
+            u[0] = i; u[1] = seg_tile_at(ntiles, c, chunks); u[2] = seg_tile_at(ntiles, c + 1, chunks); u[3] = (int)(slot + c);
         }
         const long rows = w + h.nl_count + h.n_global_rows;
         for (long k = 0; k < w; ++k) win_item[win + k] = i;
         for (long k = 0; k < rows; ++k) row_item[row + k] = i;
         tok += N; win += w; row += rows; score += ntiles * 16; slot += chunks;
     }
-    hipStream_t s = (hipStream_t)a->stream;
-    if (hipMemcpyAsync(a->ws, tab.data(), (size_t)l.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_error("compressor_ragged: writing the table region: %s", hipGetErrorString(hipGetLastError()));
-        return HICOM_ELAUNCH;
-    }
-    return HICOM_OK;
+    return seg_upload_tables(kWho, a, tab.data(), l.table_bytes);
 }
 
 // the four launches that look their item up in the table region (segment_host.hpp: seg_step)
@@ -281,10 +256,10 @@ struct RaggedItems {
         p.units = (const int4*)(ws() + l.units); p.items = items();
         static bool attr_set = false;
         if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(ragged_global_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, kSegStreamSmem);
+            hipFuncSetAttribute(reinterpret_cast<const void*>(ragged_global_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, seg_stream_smem(1));
             attr_set = true;
         }
-        HICOM_LAUNCH(ragged_global_stream_kernel<9>, dim3((unsigned)l.s.n.slots), dim3(256), kSegStreamSmem, s(), p);
+        HICOM_LAUNCH(ragged_global_stream_kernel<9>, dim3((unsigned)l.s.n.slots), dim3(256), seg_stream_smem(1), s(), p);
         return seg_check_launch(kWho, "global stream");
     }
 

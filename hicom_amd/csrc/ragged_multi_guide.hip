@@ -5,16 +5,17 @@
 // the common checks are segment_host.hpp's with M pairs as its items (twelve launches, whatever B, the Q_i and the mix are):
 //    1-2  q_proj and the fold with M rows: the nh folded rows of pair p are rows nh p .. nh p + nh - 1
 //    3    rmg_local_kernel: one wave per window of the STACKED tensor (window -> item lookup as in ragged.hip); the wave walks its item's
-//         guides in groups of kGuideGroup through multi_window_ctx16 (multi_window.hpp), so every key row and every value row is loaded
+//         guides in groups of kGuideGroup (multi_window.hpp: multi_window_guides_ctx16), so every key row and every value row is loaded
 //         once per group; fp16 contexts go out pair-major: pair p of item i owns rows [ctx_row0_p, + windows_i)
-//    4    rmg_stream_kernel: the segmented stream in a two-row-group form, 32 densely packed folded rows of ONE item per workgroup, one
-//         workgroup per work unit {item, first tile, last tile, row pass, partial-state slot}
+//    4    rmg_stream_kernel: stream_segment (segment_item.hpp: the one body of the segmented stream) with two row groups, 32 densely packed
+//         folded rows of ONE item per workgroup, one workgroup per work unit {item, first tile, last tile, row pass, partial-state slot}
 //    5    merge_segments (segment_item.hpp) per (pair, head)
 //    6-11 the global tail with M rows, the local readout as one GEMM pair over all pairs' window contexts
 //   12    place_row with item = pair, the layout integers those of the pair's item
 // Only launches 3 and 4 know that several pairs alias one item's tokens.  This file holds the kernels, the table region
 // (hicom_compressor_ragged_multiguide_prepare derives it on the host, once per plan; hicom_amd/ragged_multi_guide.py: plan_tables restates
-// it), the chunk policy and the step's own limits.
+// it) and the step's own limits; the walk over the item descriptors (per-item requirements, chunk share by tiles x passes, tile ranges,
+// table upload) is segment_host.hpp's, shared with ragged.hip.
 //
 // Row space of an item: guide q owns rows nh q .. nh q + nh - 1, rows_i = nh Q_i in all; pass p of the stream carries rows [32 p, 32 p + 32),
 // its row group g (waves 4 g .. 4 g + 3) rows [32 p + 16 g, + 16).  Partial-state slots (16 rows each) are ordered
@@ -65,215 +66,13 @@ __global__ __launch_bounds__(256) void rmg_local_kernel(const uint16_t* key, con
     const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
     const int wi = (it.T / it.kt) * ay.nwin * ax.nwin;          // windows of the item = context rows of one pair
     const WindowGeom g(at, ay, ax, win - it.win0);
-    const long first = (long)it.tok0 * D, plane = (long)wi * D;
-    const uint16_t *k = key + first, *v = value + first;
-    for (int g0 = 0; g0 < it.Q; g0 += kGuideGroup) {
-        const uint16_t* q = guide + (long)(it.pair0 + g0) * D;
-        _Float16* o = ctx16 + ((long)it.ctx_row0 + (long)g0 * wi + (win - it.win0)) * D;
-        switch (it.Q - g0 < kGuideGroup ? it.Q - g0 : kGuideGroup) {      // (wave-uniform)
-            case 1: multi_window_ctx16<NV, 1>(k, v, q, g, lane, scale, o, plane); break;
-            case 2: multi_window_ctx16<NV, 2>(k, v, q, g, lane, scale, o, plane); break;
-            case 3: multi_window_ctx16<NV, 3>(k, v, q, g, lane, scale, o, plane); break;
-            default: multi_window_ctx16<NV, 4>(k, v, q, g, lane, scale, o, plane); break;
-        }
-    }
+    const long first = (long)it.tok0 * D;
+    multi_window_guides_ctx16<NV>(key + first, value + first, guide, it.pair0, it.Q, g, lane, scale,
+                                  ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)wi * D);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// 4: segmented many-row stream.  stream_segment (segment_item.hpp) in a two-row-group form: a 512-thread workgroup in which waves 0-3
-// and waves 4-7 are two copies of its four-wave machine on ONE double-buffered LDS tile, so an item's tokens come from HBM once per
-// 32 folded rows.  The tile is staged once per workgroup, its 1 KB pieces dealt round-robin to the eight waves; swizzle, the vmcnt(0) +
-// barrier discipline and the masked tail tile (the item's own last token again) are stream_segment's.  Each group has its own exchange
-// area, online softmax and accumulators, written as stream_segment writes them, in the same operations and the same order per row: a
-// row's result does not depend on its group, on the other rows of the pass or on how many of them are live.  A group without a live row
-// (rows >= nrows) stages and keeps the barriers only.  xi: the item's N tokens; row0: the pass's first row in the item's row space;
-// nrows: the item's rows; qrow0: the item's first row in the query planes; scores: the item's [..][score_stride] logits; slot: the
-// partial-state slot of group 0, group 1 `gslots` further.
-// ---------------------------------------------------------------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void stream_segment2(const SegStreamParams& p, const uint16_t* xi, int N, int tb, int te, int row0, int nrows, long qrow0,
-                                                float* scores, long score_stride, long slot, int gslots) {
-    constexpr int E = NB * 128;
-    constexpr int SLICE = E / 4;
-    constexpr int KSTEPS = SLICE / 32;
-    constexpr int CBLK = SLICE / 16;
-    constexpr int TILE_BYTES = NB * 4096;
-    constexpr int PIECES = NB * 4;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* tilebuf = smem;                                           // [2][TILE_BYTES]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave8 >> 2, wave = wave8 & 3;                   // row group; the wave inside its four-wave machine
-    float* red = reinterpret_cast<float*>(smem + 2 * TILE_BYTES) + grp * 1024;   // per group: [4 waves][16 rows][16 tokens]
-    const int r16 = lane & 15, kg = lane >> 4;
-    const int grow0 = row0 + 16 * grp;                              // the group's first row in the item's row space
-    const bool grp_on = grow0 < nrows;                              // (wave-uniform)
-    const bool row_ok = grow0 + r16 < nrows;
-    const long qrow = qrow0 + grow0 + r16;
-
-    // ---- A operand: the group's folded queries (rows >= nrows: zero), this wave's channel slice ----
-    bf16x8 ahi[KSTEPS], alo[KSTEPS];
-    {
-        const long off = qrow * E + SLICE * wave + 8 * kg;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            ahi[s] = row_ok ? *reinterpret_cast<const bf16x8*>(p.qhi + off + 32 * s) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            alo[s] = row_ok ? *reinterpret_cast<const bf16x8*>(p.qlo + off + 32 * s) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    }
-
-    f32x4 acc[CBLK];
-#pragma unroll
-    for (int cb = 0; cb < CBLK; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -1.0e30f, l_run = 0.f;
-
-    auto stage = [&](int tile, int buf) {
-        const int r = lane >> 4, cpos = lane & 15;
-#pragma unroll
-        for (int i = 0; i < (PIECES + 7) / 8; ++i) {
-            const int pi = wave8 + 8 * i;
-            if (pi < PIECES) {                                      // (wave-uniform: 36 pieces, waves 0-3 issue five, waves 4-7 four)
-                const int blk = pi >> 2, row = 4 * (pi & 3) + r;
-                int tok = tile * 16 + row;
-                tok = tok < N ? tok : N - 1;   // tail tile: the item's own last token again (masked below), never a neighbour's
-                const char* src = reinterpret_cast<const char*>(xi) + (long)tok * (E * 2) + blk * 256 + 16 * (cpos ^ bswz(row));
-                char* dst = tilebuf + buf * TILE_BYTES + pi * 1024;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),
-                                                 (__attribute__((address_space(3))) void*)(dst), 16, 0, 0);
-            }
-        }
-    };
-
-    const int q4 = (lane >> 2) & 3, pp = lane & 3;
-    const int trow = 4 * bsig(kg) + q4;
-    const int rd_row_off = r16 * 256, rd_swz = bswz(r16);
-    const int tr_row_off = trow * 256 + 8 * (pp & 1), tr_swz = bswz(trow);
-    const float* pa = (p.pos_a && row_ok) ? p.pos_a + qrow * p.pos_stride : nullptr;
-
-    // positional logit terms, one tile ahead; the token index is item-local: t restarts at 0 per item
-    float pt[4] = {0.f, 0.f, 0.f, 0.f}, py[4] = {0.f, 0.f, 0.f, 0.f}, px[4] = {0.f, 0.f, 0.f, 0.f};
-    auto fetch_pos = [&](int tile) {
-        if (pa) {
-            const int nb = tile * 16 + 4 * bsig(kg);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int n = nb + j;
-                n = n < N ? n : N - 1;
-                const unsigned un = (unsigned)n;
-                const unsigned t = un / (unsigned)p.HW, rem = un - t * (unsigned)p.HW;
-                const unsigned y = rem / (unsigned)p.W, xx = rem - y * (unsigned)p.W;
-                pt[j] = pa[p.t0i + t];
-                py[j] = pa[p.y0i + y];
-                px[j] = pa[p.x0i + xx];
-            }
-        }
-    };
-
-    if (tb < te) {
-        fetch_pos(tb);
-        stage(tb, 0);
-    }
-
-    for (int tile = tb; tile < te; ++tile) {
-        const int cur = (tile - tb) & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        float padd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) padd[j] = pt[j] + py[j] + px[j];
-        if (tile + 1 < te) {
-            fetch_pos(tile + 1);
-            stage(tile + 1, cur ^ 1);
-        }
-        const char* img = tilebuf + cur * TILE_BYTES;
-
-        if (grp_on) {
-            f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) {
-                const int ch0 = SLICE * wave + 32 * s;
-                const int blk = ch0 >> 7, cbase = (ch0 & 127) >> 3;
-                const bf16x8 b = *reinterpret_cast<const bf16x8*>(img + blk * 4096 + rd_row_off + 16 * ((cbase + kg) ^ rd_swz));
-                s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[s], b, s4, 0, 0, 0);
-                s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[s], b, s4, 0, 0, 0);
-            }
-            float* rw = red + wave * 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rw[(4 * kg + j) * 16 + r16] = s4[j];
-        }
-        lds_barrier();
-        if (!grp_on) continue;                                      // (wave-uniform; both barriers of the tile are behind this wave)
-
-        const float* rb = red + r16 * 16 + 4 * bsig(kg);
-        f32x4 lg = *reinterpret_cast<const f32x4*>(rb);
-        lg += *reinterpret_cast<const f32x4*>(rb + 256);
-        lg += *reinterpret_cast<const f32x4*>(rb + 512);
-        lg += *reinterpret_cast<const f32x4*>(rb + 768);
-        const int n0 = tile * 16 + 4 * bsig(kg);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) lg[j] += padd[j];
-        if (wave == 0 && row_ok) *reinterpret_cast<f32x4*>(scores + (long)(grow0 + r16) * score_stride + n0) = lg;
-
-        float tmax = -1.0e30f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tmax = (n0 + j < N) ? fmaxf(tmax, lg[j]) : tmax;
-        tmax = xrow4_max(tmax);
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = expf(m_run - m_new);
-        float pr[4], lsum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            pr[j] = (n0 + j < N) ? expf(lg[j] - m_new) : 0.f;
-            lsum += pr[j];
-        }
-        lsum = xrow4_sum(lsum);
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-        if (__any(alpha != 1.0f)) {
-            const float a0 = __shfl(alpha, 4 * kg + 0, 64), a1 = __shfl(alpha, 4 * kg + 1, 64);
-            const float a2 = __shfl(alpha, 4 * kg + 2, 64), a3 = __shfl(alpha, 4 * kg + 3, 64);
-#pragma unroll
-            for (int cb = 0; cb < CBLK; ++cb) {
-                acc[cb][0] *= a0; acc[cb][1] *= a1; acc[cb][2] *= a2; acc[cb][3] *= a3;
-            }
-        }
-        bf16x4 phi, plo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint16_t h, l;
-            split_bf16(pr[j], h, l);
-            phi[j] = (short)h;
-            plo[j] = (short)l;
-        }
-#pragma unroll
-        for (int cb = 0; cb < CBLK; ++cb) {
-            const int ch0 = SLICE * wave + 16 * cb;
-            const int blk = ch0 >> 7, c2 = (ch0 & 127) >> 3;
-            const char* a = img + blk * 4096 + tr_row_off + 16 * ((c2 + (pp >> 1)) ^ tr_swz);
-            const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a));
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(phi, b, acc[cb], 0, 0, 0);
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(plo, b, acc[cb], 0, 0, 0);
-        }
-    }
-
-    // ---- the group's partial state of this segment (rows >= nrows are not stored) ----
-    if (!grp_on) return;
-    const long prow = (slot + (long)grp * gslots) * 16;
-    if (wave == 0 && kg == 0 && row_ok) {
-        p.part_m[prow + r16] = m_run;
-        p.part_l[prow + r16] = l_run;
-    }
-#pragma unroll
-    for (int cb = 0; cb < CBLK; ++cb) {
-        float* o = p.part_acc + (prow + 4 * kg) * E + SLICE * wave + 16 * cb + r16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (grow0 + 4 * kg + j < nrows) o[(long)j * E] = acc[cb][j];
-    }
-}
-
+// ---- 4: segmented many-row stream, stream_segment (segment_item.hpp) with two row groups: 32 densely packed rows of ONE item per
+// workgroup, so the item's tokens come from HBM once per 32 folded rows ----
 struct RmgStreamParams {
     SegStreamParams c;
     const uint16_t* x;      // [sum N_i][E]
@@ -282,15 +81,13 @@ struct RmgStreamParams {
     const RmgItem* items;
 };
 
-constexpr int kRmgStreamSmem = 2 * 9 * 4096 + 2 * 4096;     // the double-buffered tile, one exchange area per row group
-
 template <int NB>
 __global__ __launch_bounds__(512, 1) void rmg_stream_kernel(RmgStreamParams p) {
     constexpr int E = NB * 128;
     const RmgUnit u = p.units[blockIdx.x];
     const RmgItem it = p.items[u.item];
-    stream_segment2<NB>(p.c, p.x + (long)it.tok0 * E, it.N, u.tb, u.te, 32 * u.pass, p.c.rows * it.Q, (long)it.pair0 * p.c.rows,
-                        p.scores + (long)it.score_off * 16, (long)((it.N + 15) / 16 * 16), (long)u.slot, it.chunks);
+    stream_segment<NB, 2>(p.c, p.x + (long)it.tok0 * E, it.N, u.tb, u.te, 32 * u.pass, p.c.rows * it.Q, (long)it.pair0 * p.c.rows,
+                          p.scores + (long)it.score_off * 16, (long)((it.N + 15) / 16 * 16), (long)u.slot, it.chunks);
 }
 
 // ---- 5: merge per (pair, head), grid = (heads, M), LDS sized for the longest item ----
@@ -344,17 +141,7 @@ constexpr int kPassRows = 32;               // folded rows of one pass of the st
 
 typedef hicom_compressor_ragged_multiguide_args Args;
 
-inline long item_windows(const hicom_ragged_item& it, int wps) { return (long)(it.T / it.kt) * wps; }
 inline long item_passes(const Args* a, int i) { return ((long)a->nh * a->guide_counts[i] + kPassRows - 1) / kPassRows; }
-
-// token chunks per pass of an item with `ntiles` tiles: its share of 2 #CUs work units by tiles x passes, rounded to nearest (for
-// Q_i = 1 everywhere: the ragged step's division); `chunks` > 0 overrides the share
-int rmg_chunks(long ntiles, long work_sum, int chunks, int ncu) {
-    long c = chunks > 0 ? chunks : (2L * ncu * ntiles + work_sum / 2) / work_sum;
-    if (c > ntiles) c = ntiles;
-    if (c > kSegMaxChunks) c = kSegMaxChunks;
-    return (int)(c < 1 ? 1 : c);
-}
 
 struct RmgLayout {
     long items, units, win_item, pairs, row_pair, table_bytes;      // the table region, in front of the step's own regions
@@ -382,7 +169,7 @@ RmgLayout rmg_layout(const Args* a) {
     }
     const int ncu = a->chunks > 0 ? 0 : num_cus();
     for (int i = 0; i < a->B; ++i) {
-        const long c = rmg_chunks((a->items[i].T * HW + 15) / 16, l.work_sum, a->chunks, ncu);
+        const long c = seg_share_chunks((a->items[i].T * HW + 15) / 16, l.work_sum, a->chunks, ncu);
         l.nunits += c * item_passes(a, i);
     }
     n.slots = 2 * l.nunits;
@@ -411,29 +198,21 @@ int rmg_check(const Args* a) {
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP,
                   "compressor_ragged_multiguide: needs an exact window partition (H=%d W=%d, windows %dx%d)", a->H, a->W, a->ks, a->ks);
-    const int wps = (a->H / a->ks) * (a->W / a->ks);
-    long tokens = 0, pairs = 0, products = 0, ctx_rows = 0;
-    int max_T = 0;
-    for (int i = 0; i < a->B; ++i) {
-        const hicom_ragged_item& it = a->items[i];
+    long tokens;
+    int max_T;
+    st = seg_check_ragged_items(kWho, a, tokens, max_T, [a](int i) -> int {        // item i's guide count in front of its shape
         const int Q = a->guide_counts[i];
         HICOM_REQUIRE(Q >= 1 && Q <= kMaxGuides, HICOM_EUNSUP, "compressor_ragged_multiguide: item %d: Q=%d guides (1 <= Q <= %d per item)", i, Q, kMaxGuides);
-        HICOM_REQUIRE(it.T > 0 && it.kt > 0 && it.n_global_rows > 0 && it.nl_group >= 0 && it.nl_count >= 0, HICOM_EINVAL,
-                      "compressor_ragged_multiguide: item %d: bad shape", i);
-        HICOM_REQUIRE(it.T % it.kt == 0, HICOM_EUNSUP, "compressor_ragged_multiguide: item %d needs an exact window partition (T=%d, temporal window %d)", i, it.T,
-                      it.kt);
-        HICOM_REQUIRE(it.kt * a->ks * a->ks <= 64, HICOM_EUNSUP, "compressor_ragged_multiguide: item %d: windows of %d tokens (<= 64)", i, it.kt * a->ks * a->ks);
-        const long N = (long)it.T * a->H * a->W;
-        HICOM_REQUIRE(N < (1L << 27), HICOM_EUNSUP, "compressor_ragged_multiguide: item %d: too many tokens", i);
-        const long w = item_windows(it, wps);
-        HICOM_REQUIRE(!it.nl_group || w % it.nl_group == 0, HICOM_EINVAL, "compressor_ragged_multiguide: item %d: output layout", i);
-        HICOM_REQUIRE(it.nl_count == 0 || (it.nl_step > 0 && it.nl_first >= 0 && it.nl_first + (long)(it.nl_count - 1) * it.nl_step < w + it.nl_count),
-                      HICOM_EINVAL, "compressor_ragged_multiguide: item %d: newline rows", i);
-        tokens += N;
+        return HICOM_OK;
+    });
+    if (st != HICOM_OK) return st;
+    const int wps = (a->H / a->ks) * (a->W / a->ks);
+    long pairs = 0, products = 0, ctx_rows = 0;
+    for (int i = 0; i < a->B; ++i) {
+        const long Q = a->guide_counts[i], N = (long)a->items[i].T * a->H * a->W;
         pairs += Q;
         products += Q * ((N + 15) / 16 * 16);
-        ctx_rows += Q * w;
-        if (it.T > max_T) max_T = it.T;
+        ctx_rows += Q * item_windows(a->items[i], wps);
     }
     HICOM_REQUIRE(pairs <= kSegMaxItems, HICOM_EUNSUP, "compressor_ragged_multiguide: %ld (item, guide) pairs (<= %d per call)", pairs, kSegMaxItems);
     // (item offsets, the logits' offsets -- counted in 16 floats, 32 rows per pass and token -- and the context rows are ints on the device)
@@ -461,7 +240,7 @@ int rmg_prepare(const Args* a) {
     for (int i = 0; i < a->B; ++i) {
         const hicom_ragged_item& h = a->items[i];
         const long N = h.T * HW, w = item_windows(h, l.wps), ntiles = (N + 15) / 16, passes = item_passes(a, i);
-        const int Q = a->guide_counts[i], chunks = rmg_chunks(ntiles, l.work_sum, a->chunks, ncu);
+        const int Q = a->guide_counts[i], chunks = seg_share_chunks(ntiles, l.work_sum, a->chunks, ncu);
         RmgItem& d = items[i];
         d.tok0 = (int)tok; d.N = (int)N; d.T = h.T; d.kt = h.kt; d.win0 = (int)win; d.slot0 = (int)slot; d.chunks = chunks;
         d.score_off = (int)score; d.pair0 = (int)pair; d.Q = Q; d.ctx_row0 = (int)ctx_row; d.global_row0 = (int)(w + h.nl_count);
@@ -469,7 +248,7 @@ int rmg_prepare(const Args* a) {
         for (long p = 0; p < passes; ++p)
             for (int c = 0; c < chunks; ++c) {
                 RmgUnit& u = units[unit++];
-                u.item = i; u.tb = (int)(ntiles * c / chunks); u.te = (int)(ntiles * (c + 1) / chunks); u.pass = (int)p;
+                u.item = i; u.tb = seg_tile_at(ntiles, c, chunks); u.te = seg_tile_at(ntiles, c + 1, chunks); u.pass = (int)p;
                 u.slot = (int)(slot + 2 * p * chunks + c);
             }
         for (long k = 0; k < w; ++k) win_item[win + k] = i;
@@ -481,12 +260,7 @@ int rmg_prepare(const Args* a) {
         }
         tok += N; win += w; row += Q * rows; score += passes * kPassRows * ntiles; slot += 2 * passes * chunks; pair += Q; ctx_row += Q * w;
     }
-    hipStream_t s = (hipStream_t)a->stream;
-    if (hipMemcpyAsync(a->ws, tab.data(), (size_t)l.table_bytes, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        set_error("compressor_ragged_multiguide: writing the table region: %s", hipGetErrorString(hipGetLastError()));
-        return HICOM_ELAUNCH;
-    }
-    return HICOM_OK;
+    return seg_upload_tables(kWho, a, tab.data(), l.table_bytes);
 }
 
 // the four launches that look their pair or item up in the table region (segment_host.hpp: seg_step)
@@ -514,10 +288,10 @@ struct PairItems {
         p.units = (const RmgUnit*)(ws() + l.units); p.items = items();
         static bool attr_set = false;
         if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(rmg_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, kRmgStreamSmem);
+            hipFuncSetAttribute(reinterpret_cast<const void*>(rmg_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, seg_stream_smem(2));
             attr_set = true;
         }
-        HICOM_LAUNCH(rmg_stream_kernel<9>, dim3((unsigned)l.nunits), dim3(512), kRmgStreamSmem, s(), p);
+        HICOM_LAUNCH(rmg_stream_kernel<9>, dim3((unsigned)l.nunits), dim3(512), seg_stream_smem(2), s(), p);
         return seg_check_launch(kWho, "global stream");
     }
 

@@ -1,7 +1,9 @@
-// Host side of a many-item compressor step, shared by the equal-shape step (batch.hip), the ragged step (ragged.hip) and the multi-guide
-// step (multi_guide.hip, whose items are the guides of one clip): the limits, the k / v adaptors of the local stage, the checks, the
-// workspace layout and the launch sequence that do not depend on how a wave finds its item.  The three files keep their kernels, the code
-// that launches them, their chunk policy and their own layout checks.  The shared functions are templates over the argument block
+// Host side of a many-item compressor step, shared by the equal-shape step (batch.hip), the ragged step (ragged.hip), the multi-guide
+// step (multi_guide.hip, whose items are the guides of one clip) and the ragged multi-guide step (ragged_multi_guide.hip, whose items
+// are (item, guide) pairs): the limits, the k / v adaptors of the local stage, the checks, the workspace layout and the launch sequence
+// that do not depend on how a wave finds its item, and the walk over hicom_ragged_item descriptors of the two ragged steps (per-item
+// requirements, chunk share, tile ranges, table upload).  The files keep their kernels, the code that launches them, their table
+// structs and their own layout checks.  The shared functions are templates over the argument block
 // (hicom_compressor_batch_args / _ragged_args / _multiguide_args name every common field alike; the item count is B or Q: seg_items) and
 // read `a->field` directly; `who` is the message prefix ("compressor_batch" / "compressor_ragged" / "compressor_multiguide").
 #pragma once
@@ -22,7 +24,6 @@ inline int num_cus() {
 
 constexpr int kSegMaxItems = 4096;       // items per call (grid y of the merge kernels, far below the limit)
 constexpr int kSegMaxChunks = 64;        // workgroups per item of the segmented stream
-constexpr int kSegStreamSmem = 2 * 9 * 4096 + 4096;
 
 // ---- k / v adaptors of the local stage, shared by the two many-item steps (NULL: the plain recipe) ------------------------------------
 struct SegAdapt {
@@ -176,6 +177,59 @@ inline int seg_check_equal_rows(const char* who, const A* a, int wpi) {
     // every local row of an item is a token row or a newline row
     HICOM_REQUIRE(a->global_row0 == (long)wpi + a->nl_count, HICOM_EINVAL, "%s: %ld local rows for %d tokens + %d newline rows", who, (long)a->global_row0,
                   wpi, a->nl_count);
+    return HICOM_OK;
+}
+
+// ---- the ragged item walk, shared by the two steps whose items come as hicom_ragged_item (ragged.hip, ragged_multi_guide.hip) ----------------
+inline long item_windows(const hicom_ragged_item& it, int wps) { return (long)(it.T / it.kt) * wps; }
+
+// tile `c` of `chunks` equal shares of an item's `ntiles` tiles: chunk c walks [seg_tile_at(c), seg_tile_at(c + 1))
+inline int seg_tile_at(long ntiles, int c, int chunks) { return (int)(ntiles * c / chunks); }
+
+// token chunks of an item with `ntiles` tiles: its share of 2 #CUs work units by `work` (ragged: tiles, work_sum the call's tile total;
+// multi-guide: tiles x passes), rounded to nearest -- a function of ntiles, work_sum and #CUs only: permuting the items permutes the
+// division; `chunks` > 0 overrides the share
+inline int seg_share_chunks(long ntiles, long work_sum, int chunks, int ncu) {
+    long c = chunks > 0 ? chunks : (2L * ncu * ntiles + work_sum / 2) / work_sum;
+    if (c > ntiles) c = ntiles;
+    if (c > kSegMaxChunks) c = kSegMaxChunks;
+    return (int)(c < 1 ? 1 : c);
+}
+
+// the per-item requirements, item by item; first(i) runs in front of item i's (the step's own requirement on the item: its status, not
+// HICOM_OK, ends the walk).  Adds up the call's tokens and finds the longest item's frames.
+template <class A, class First>
+inline int seg_check_ragged_items(const char* who, const A* a, long& tokens, int& max_T, First&& first) {
+    const int wps = (a->H / a->ks) * (a->W / a->ks);
+    tokens = 0;
+    max_T = 0;
+    for (int i = 0; i < a->B; ++i) {
+        const int st = first(i);
+        if (st != HICOM_OK) return st;
+        const hicom_ragged_item& it = a->items[i];
+        HICOM_REQUIRE(it.T > 0 && it.kt > 0 && it.n_global_rows > 0 && it.nl_group >= 0 && it.nl_count >= 0, HICOM_EINVAL, "%s: item %d: bad shape", who, i);
+        HICOM_REQUIRE(it.T % it.kt == 0, HICOM_EUNSUP, "%s: item %d needs an exact window partition (T=%d, temporal window %d)", who, i, it.T, it.kt);
+        HICOM_REQUIRE(it.kt * a->ks * a->ks <= 64, HICOM_EUNSUP, "%s: item %d: windows of %d tokens (<= 64)", who, i, it.kt * a->ks * a->ks);
+        const long N = (long)it.T * a->H * a->W;
+        HICOM_REQUIRE(N < (1L << 27), HICOM_EUNSUP, "%s: item %d: too many tokens", who, i);
+        const long w = item_windows(it, wps);
+        HICOM_REQUIRE(!it.nl_group || w % it.nl_group == 0, HICOM_EINVAL, "%s: item %d: output layout", who, i);
+        HICOM_REQUIRE(it.nl_count == 0 || (it.nl_step > 0 && it.nl_first >= 0 && it.nl_first + (long)(it.nl_count - 1) * it.nl_step < w + it.nl_count),
+                      HICOM_EINVAL, "%s: item %d: newline rows", who, i);
+        tokens += N;
+        if (it.T > max_T) max_T = it.T;
+    }
+    return HICOM_OK;
+}
+
+// the table region, derived on the host, to the head of the workspace (synchronises the stream)
+template <class A>
+inline int seg_upload_tables(const char* who, const A* a, const void* tab, long bytes) {
+    hipStream_t s = (hipStream_t)a->stream;
+    if (hipMemcpyAsync(a->ws, tab, (size_t)bytes, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("%s: writing the table region: %s", who, hipGetErrorString(hipGetLastError()));
+        return HICOM_ELAUNCH;
+    }
     return HICOM_OK;
 }
 

@@ -1,6 +1,7 @@
 // What one wave / workgroup does for ONE item of a many-item compressor step, shared by the equal-shape step (batch.hip: the item
 // comes from a constant stride) and the ragged step (ragged.hip: the item comes from a device table); the multi-guide step
-// (multi_guide.hip: the item is a guide) takes the placement.  Each function gets the item's own pointers, token count and layout
+// (multi_guide.hip: the item is a guide) takes the placement, the ragged multi-guide step (ragged_multi_guide.hip: the item is an
+// (item, guide) pair) the segmented stream with two row groups, the merge and the placement.  Each function gets the item's own pointers, token count and layout
 // integers from its caller and indexes nothing outside them, so the callers round identically: an item's result does not depend on
 // which of the steps ran it.
 #pragma once
@@ -121,14 +122,14 @@ __device__ __forceinline__ void local_window_adapt_ctx16(const uint16_t* kx, con
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Segmented global stream.  Tile staging, swizzle, MFMA operand layouts and the per-tile order of operations are those of
 // global_stream_kernel (global_stream.hip); see there for the CDNA4 mapping.  A workgroup walks the 16-token tiles [tb, te) of ONE
-// item, counted from the item's first token.
+// item, counted from the item's first token, for one or two groups of 16 folded rows of that item.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct SegStreamParams {
     const uint16_t* qhi;    // [items * rows][E] folded queries, item-major
     const uint16_t* qlo;
     const float* pos_a;     // [items * rows][pos_stride]
     int pos_stride;
-    int rows;               // folded rows per item (heads), <= 16
+    int rows;               // folded rows per item and guide (heads), <= 16
     int H, W, HW;
     int t0i, y0i, x0i;
     float* part_m;          // [slots][16]
@@ -139,29 +140,44 @@ struct SegStreamParams {
 __device__ __forceinline__ int bswz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 __device__ __forceinline__ int bsig(int g) { return ((g & 1) << 1) | (g >> 1); }
 
-// xi: the item's N tokens [N][E]; item: its index (query rows item * rows ..); scores: its [16][score_stride] logits; slot: where this
-// workgroup's partial state (m, l, ACC) goes.  Everything but the lane-dependent parts must be wave-uniform.
-template <int NB>
-__device__ __forceinline__ void stream_segment(const SegStreamParams& p, const uint16_t* xi, int N, int tb, int te, int item, float* scores,
-                                               long score_stride, long slot) {
+// One body for one or two ROW GROUPS of 16 folded rows: a workgroup of 64 * 4 * GROUPS threads in which waves 4 g .. 4 g + 3 are the
+// four-wave machine of group g, all groups on ONE double-buffered LDS tile (staged once per workgroup, its 1 KB pieces dealt round-robin
+// to all waves), so an item's tokens come from HBM once per 16 * GROUPS rows.  Each group has its own exchange area, online softmax and
+// accumulators, in the same operations and the same order per row: a row's result does not depend on GROUPS, on its group, on the
+// other rows of the workgroup or on how many of them are live.  A group without a live row (rows >= nrows) stages and keeps the
+// barriers only.  GROUPS == 1 (batch.hip, ragged.hip: row0 = 0, nrows = p.rows, gslots = 0): the group index and everything derived
+// from it are compile-time zero and the guards fold away.
+// xi: the item's N tokens [N][E]; row0: the workgroup's first row in the item's row space, nrows: the item's rows; qrow0: the item's
+// first row in the query planes; scores: the item's [nrows][score_stride] logits; slot: where group 0's partial state (m, l, ACC) goes,
+// group g `g * gslots` slots further.  Everything but the lane-dependent parts must be wave-uniform.
+template <int NB, int GROUPS>
+__device__ __forceinline__ void stream_segment(const SegStreamParams& p, const uint16_t* xi, int N, int tb, int te, int row0, int nrows, long qrow0,
+                                               float* scores, long score_stride, long slot, int gslots) {
     constexpr int E = NB * 128;
     constexpr int SLICE = E / 4;
     constexpr int KSTEPS = SLICE / 32;
     constexpr int CBLK = SLICE / 16;
     constexpr int TILE_BYTES = NB * 4096;
     constexpr int PIECES = NB * 4;
+    constexpr int WAVES = 4 * GROUPS;
+    static_assert(GROUPS == 1 || GROUPS == 2, "one or two row groups");
+    static_assert(GROUPS != 1 || PIECES % 4 == 0, "pieces are dealt round-robin to the 4 waves");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* tilebuf = smem;                                           // [2][TILE_BYTES]
-    float* red = reinterpret_cast<float*>(smem + 2 * TILE_BYTES);  // [4 waves][16 rows][16 tokens]
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave_wg = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = GROUPS == 1 ? 0 : wave_wg >> 2;                 // row group
+    const int wave = GROUPS == 1 ? wave_wg : wave_wg & 3;           // the wave inside its four-wave machine
+    float* red = reinterpret_cast<float*>(smem + 2 * TILE_BYTES) + grp * 1024;   // per group: [4 waves][16 rows][16 tokens]
     const int r16 = lane & 15, kg = lane >> 4;
-    const bool row_ok = r16 < p.rows;
-    const long qrow = (long)item * p.rows + r16;
+    const int grow0 = row0 + 16 * grp;                              // the group's first row in the item's row space
+    const bool grp_on = GROUPS == 1 || grow0 < nrows;               // (wave-uniform)
+    const bool row_ok = grow0 + r16 < nrows;
+    const long qrow = qrow0 + grow0 + r16;
 
-    // ---- A operand: the item's folded queries (rows >= p.rows: zero), this wave's channel slice ----
+    // ---- A operand: the group's folded queries (rows >= nrows: zero), this wave's channel slice ----
     bf16x8 ahi[KSTEPS], alo[KSTEPS];
     {
         const long off = qrow * E + SLICE * wave + 8 * kg;
@@ -179,17 +195,18 @@ __device__ __forceinline__ void stream_segment(const SegStreamParams& p, const u
 
     auto stage = [&](int tile, int buf) {
         const int r = lane >> 4, cpos = lane & 15;
-        static_assert(PIECES % 4 == 0, "pieces are dealt round-robin to the 4 waves");
 #pragma unroll
-        for (int i = 0; i < PIECES / 4; ++i) {
-            const int pi = wave + 4 * i;
-            const int blk = pi >> 2, row = 4 * (pi & 3) + r;
-            int tok = tile * 16 + row;
-            tok = tok < N ? tok : N - 1;   // tail tile: the item's own last token again (masked below), never a neighbour's
-            const char* src = reinterpret_cast<const char*>(xi) + (long)tok * (E * 2) + blk * 256 + 16 * (cpos ^ bswz(row));
-            char* dst = tilebuf + buf * TILE_BYTES + pi * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),
-                                             (__attribute__((address_space(3))) void*)(dst), 16, 0, 0);
+        for (int i = 0; i < (PIECES + WAVES - 1) / WAVES; ++i) {
+            const int pi = wave_wg + WAVES * i;
+            if (PIECES % WAVES == 0 || pi < PIECES) {               // (wave-uniform; two groups: 36 pieces, waves 0-3 issue five, waves 4-7 four)
+                const int blk = pi >> 2, row = 4 * (pi & 3) + r;
+                int tok = tile * 16 + row;
+                tok = tok < N ? tok : N - 1;   // tail tile: the item's own last token again (masked below), never a neighbour's
+                const char* src = reinterpret_cast<const char*>(xi) + (long)tok * (E * 2) + blk * 256 + 16 * (cpos ^ bswz(row));
+                char* dst = tilebuf + buf * TILE_BYTES + pi * 1024;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),
+                                                 (__attribute__((address_space(3))) void*)(dst), 16, 0, 0);
+            }
         }
     };
 
@@ -236,19 +253,22 @@ __device__ __forceinline__ void stream_segment(const SegStreamParams& p, const u
         }
         const char* img = tilebuf + cur * TILE_BYTES;
 
-        f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (grp_on) {
+            f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const int ch0 = SLICE * wave + 32 * s;
-            const int blk = ch0 >> 7, cbase = (ch0 & 127) >> 3;
-            const bf16x8 b = *reinterpret_cast<const bf16x8*>(img + blk * 4096 + rd_row_off + 16 * ((cbase + kg) ^ rd_swz));
-            s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[s], b, s4, 0, 0, 0);
-            s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[s], b, s4, 0, 0, 0);
+            for (int s = 0; s < KSTEPS; ++s) {
+                const int ch0 = SLICE * wave + 32 * s;
+                const int blk = ch0 >> 7, cbase = (ch0 & 127) >> 3;
+                const bf16x8 b = *reinterpret_cast<const bf16x8*>(img + blk * 4096 + rd_row_off + 16 * ((cbase + kg) ^ rd_swz));
+                s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[s], b, s4, 0, 0, 0);
+                s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[s], b, s4, 0, 0, 0);
+            }
+            float* rw = red + wave * 256;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rw[(4 * kg + j) * 16 + r16] = s4[j];
         }
-        float* rw = red + wave * 256;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rw[(4 * kg + j) * 16 + r16] = s4[j];
         lds_barrier();
+        if (!grp_on) continue;                                      // (wave-uniform; both barriers of the tile are behind this wave)
 
         const float* rb = red + r16 * 16 + 4 * bsig(kg);
         f32x4 lg = *reinterpret_cast<const f32x4*>(rb);
@@ -258,7 +278,7 @@ __device__ __forceinline__ void stream_segment(const SegStreamParams& p, const u
         const int n0 = tile * 16 + 4 * bsig(kg);
 #pragma unroll
         for (int j = 0; j < 4; ++j) lg[j] += padd[j];
-        if (wave == 0 && row_ok) *reinterpret_cast<f32x4*>(scores + r16 * score_stride + n0) = lg;
+        if (wave == 0 && row_ok) *reinterpret_cast<f32x4*>(scores + (long)(grow0 + r16) * score_stride + n0) = lg;
 
         float tmax = -1.0e30f;
 #pragma unroll
@@ -302,8 +322,9 @@ __device__ __forceinline__ void stream_segment(const SegStreamParams& p, const u
         }
     }
 
-    // ---- this segment's partial state ----
-    const long prow = slot * 16;
+    // ---- the group's partial state of this segment (rows >= nrows are not stored) ----
+    if (!grp_on) return;
+    const long prow = (slot + (long)grp * gslots) * 16;
     if (wave == 0 && kg == 0 && row_ok) {
         p.part_m[prow + r16] = m_run;
         p.part_l[prow + r16] = l_run;
@@ -313,9 +334,12 @@ __device__ __forceinline__ void stream_segment(const SegStreamParams& p, const u
         float* o = p.part_acc + (prow + 4 * kg) * E + SLICE * wave + 16 * cb + r16;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (4 * kg + j < p.rows) o[(long)j * E] = acc[cb][j];
+            if (grow0 + 4 * kg + j < nrows) o[(long)j * E] = acc[cb][j];
     }
 }
+
+// LDS of a stream_segment<9, groups> workgroup: the double-buffered tile, one exchange area per row group
+constexpr int seg_stream_smem(int groups) { return 2 * 9 * 4096 + groups * 4096; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Merge of one (item, head) row: ctx = sum_p e^(m_p - M) ACC_p / L + sum_s marg[s] pe[s], marg = the row's softmax weights summed

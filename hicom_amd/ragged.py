@@ -31,26 +31,31 @@ def item_chunks(ntiles: int, ntiles_sum: int, chunks: int, n_cus: int) -> int:
     return max(1, min(c, ntiles, MAX_CHUNKS))
 
 
+def prefix(v):
+    """Exclusive prefix sums of a list of ints."""
+    return [int(x) for x in np.concatenate([[0], np.cumsum(v)[:-1]])] if v else []
+
+
+def item_geometry(items, H: int, W: int, ks: int):
+    """What the item descriptors and the grid alone decide, per item: tokens N, 16-token tiles, windows, packed rows (of one guide),
+    the rows in front of the global rows, the first token and the first window in the stack."""
+    wps = (H // ks) * (W // ks)
+    N = [it[0] * H * W for it in items]
+    windows = [(it[0] // it[1]) * wps for it in items]
+    return SimpleNamespace(N=N, ntiles=[(n + 15) // 16 for n in N], windows=windows, rows=[w + it[3] + it[6] for w, it in zip(windows, items)],
+                           global_row0=[w + it[3] for w, it in zip(windows, items)], tok0=prefix(N), win0=prefix(windows), items=items)
+
+
 def plan_tables(items, H: int, W: int, ks: int, n_cus: int, chunks: int = 0):
     """items: sequences (T, kt, nl_group, nl_count, nl_first, nl_step, n_global_rows), the fields of hicom_ragged_item.
     Returns the per-item offsets (tokens, windows, rows, logits, partial-state slots), the work units (item, first tile, last tile,
     slot) and the window -> item / row -> item lookups, as hicom_compressor_ragged_prepare lays them out."""
-    wps = (H // ks) * (W // ks)
-    N = [it[0] * H * W for it in items]
-    ntiles = [(n + 15) // 16 for n in N]
-    windows = [(it[0] // it[1]) * wps for it in items]
-    rows = [w + it[3] + it[6] for w, it in zip(windows, items)]
-    nchunks = [item_chunks(t, sum(ntiles), chunks, n_cus) for t in ntiles]
-
-    def prefix(v):
-        return [int(x) for x in np.concatenate([[0], np.cumsum(v)[:-1]])] if v else []
-    t = SimpleNamespace(N=N, ntiles=ntiles, windows=windows, rows=rows, chunks=nchunks, tok0=prefix(N), win0=prefix(windows), row0=prefix(rows),
-                        score_off=prefix([16 * x for x in ntiles]), slot0=prefix(nchunks),
-                        global_row0=[w + it[3] for w, it in zip(windows, items)])
-    t.units = [(i, nt * c // nc, nt * (c + 1) // nc, s0 + c) for i, (nt, nc, s0) in enumerate(zip(ntiles, nchunks, t.slot0)) for c in range(nc)]
-    t.win_item = np.repeat(np.arange(len(items), dtype=np.int32), windows)
-    t.row_item = np.repeat(np.arange(len(items), dtype=np.int32), rows)
-    t.items = items
+    t = item_geometry(items, H, W, ks)
+    t.chunks = [item_chunks(n, sum(t.ntiles), chunks, n_cus) for n in t.ntiles]
+    t.row0, t.score_off, t.slot0 = prefix(t.rows), prefix([16 * x for x in t.ntiles]), prefix(t.chunks)
+    t.units = [(i, nt * c // nc, nt * (c + 1) // nc, s0 + c) for i, (nt, nc, s0) in enumerate(zip(t.ntiles, t.chunks, t.slot0)) for c in range(nc)]
+    t.win_item = np.repeat(np.arange(len(items), dtype=np.int32), t.windows)
+    t.row_item = np.repeat(np.arange(len(items), dtype=np.int32), t.rows)
     return t
 
 
@@ -66,26 +71,39 @@ def table_image(t) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
+def check_splits(what, ff, split_sizes, modals, guide_counts=None, check_counts=None):
+    """Raises unless split_sizes are positive ints that add up to the stacked frames and modals name a modality per item (one string
+    stands for all).  guide_counts (forward_ragged_multi_guide) are converted with the sizes and handed to check_counts(B, guide_counts)
+    between the two.  Returns (split_sizes, modals, guide_counts) as tuples."""
+    try:
+        split_sizes = tuple(int(t) for t in split_sizes)
+        if guide_counts is not None:
+            guide_counts = tuple(int(q) for q in guide_counts)
+    except TypeError:
+        seqs = "split_sizes is a sequence" if guide_counts is None else "split_sizes and guide_counts are sequences"
+        raise ValueError(f"{what}: {seqs} of positive ints, one per item") from None
+    B = len(split_sizes)
+    if B == 0 or any(t <= 0 for t in split_sizes):
+        raise ValueError(f"{what}: split_sizes is a sequence of positive ints, one per item (got {split_sizes})")
+    if sum(split_sizes) != ff.shape[0]:
+        raise ValueError(f"{what}: sum(split_sizes) = {sum(split_sizes)} vs {ff.shape[0]} stacked frames")
+    if check_counts is not None:
+        check_counts(B, guide_counts)
+    modals = (modals,) * B if isinstance(modals, str) else tuple(modals)
+    if len(modals) != B:
+        raise ValueError(f"{what}: {len(modals)} modals for {B} items (one string, or one per item)")
+    if any(m not in ("image", "video") for m in modals):
+        raise ValueError(f"{what}: modals are 'image' or 'video' (got {modals})")
+    return split_sizes, modals, guide_counts
+
+
 def _scope(proj, ff, fe, guides, split_sizes, modals, nl):
     """Raises for everything outside the ragged step's scope that does not need the per-item geometry; returns (B, H, W, E,
     split_sizes, modals) with the last two as tuples."""
     def count_items():
         nonlocal split_sizes, modals
-        try:
-            split_sizes = tuple(int(t) for t in split_sizes)
-        except TypeError:
-            raise ValueError("forward_ragged: split_sizes is a sequence of positive ints, one per item") from None
-        B = len(split_sizes)
-        if B == 0 or any(t <= 0 for t in split_sizes):
-            raise ValueError(f"forward_ragged: split_sizes is a sequence of positive ints, one per item (got {split_sizes})")
-        if sum(split_sizes) != ff.shape[0]:
-            raise ValueError(f"forward_ragged: sum(split_sizes) = {sum(split_sizes)} vs {ff.shape[0]} stacked frames")
-        modals = (modals,) * B if isinstance(modals, str) else tuple(modals)
-        if len(modals) != B:
-            raise ValueError(f"forward_ragged: {len(modals)} modals for {B} items (one string, or one per item)")
-        if any(m not in ("image", "video") for m in modals):
-            raise ValueError(f"forward_ragged: modals are 'image' or 'video' (got {modals})")
-        return B
+        split_sizes, modals, _ = check_splits("forward_ragged", ff, split_sizes, modals)
+        return len(split_sizes)
     B, E = seg.check_inputs("forward_ragged", "ragged", proj, ff, fe, guides, nl, 4, "the stacked [sum T_i, H, W, E] tensor", count_items)
     for i, (t, m) in enumerate(zip(split_sizes, modals)):
         if m == "image" and t != 1:
@@ -93,12 +111,13 @@ def _scope(proj, ff, fe, guides, split_sizes, modals, nl):
     return B, ff.shape[1], ff.shape[2], E, split_sizes, modals
 
 
-def item_descriptors(proj, split_sizes, modals, H, W, has_newline):
+def item_descriptors(proj, split_sizes, modals, H, W, has_newline, what="forward_ragged"):
     """The fields of hicom_ragged_item per item, (T, kt, nl_group, nl_count, nl_first, nl_step, n_global_rows), and the spatial
-    window ks: LocalCompressor.tilings and HIComProjector._layout on every item alone."""
+    window ks: LocalCompressor.tilings and HIComProjector._layout on every item alone.  Raises, under the name `what`, unless every
+    item's windows partition its grid exactly, with square spatial windows."""
     items, ks = [], None
     for i, (T, modal) in enumerate(zip(split_sizes, modals)):
-        at, ay, ax = seg.exact_tilings("forward_ragged", proj, T, H, W, modal, f"item {i}: ")
+        at, ay, ax = seg.exact_tilings(what, proj, T, H, W, modal, f"item {i}: ")
         ks = ay.k
         lay = proj._layout((at.nwin, ay.nwin, ax.nwin), modal, has_newline, False)
         nlr = lay.newline_rows

@@ -13,7 +13,6 @@ pairs' row counts from it, and the tests hold the device's table region against 
 from __future__ import annotations
 
 import ctypes as C
-from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -48,31 +47,22 @@ def plan_tables(items, guide_counts, H: int, W: int, ks: int, nh: int, n_cus: in
     work units (item, first tile, last tile, pass, slot of row group 0), the pair table (item, guide, first context row, first output
     row) and the window -> item / row -> pair lookups, as hicom_compressor_ragged_multiguide_prepare lays them out.  Partial-state
     slots are ordered [item][pass][row group][chunk]."""
-    Q = [int(q) for q in guide_counts]
-    wps = (H // ks) * (W // ks)
-    N = [it[0] * H * W for it in items]
-    ntiles = [(n + 15) // 16 for n in N]
-    windows = [(it[0] // it[1]) * wps for it in items]
-    rows = [w + it[3] + it[6] for w, it in zip(windows, items)]                  # of ONE pair of the item
-    passes = [item_passes(nh, q) for q in Q]
-    work_sum = sum(t * p for t, p in zip(ntiles, passes))
-    nchunks = [item_chunks(t, work_sum, chunks, n_cus) for t in ntiles]
-
-    def prefix(v):
-        return [int(x) for x in np.concatenate([[0], np.cumsum(v)[:-1]])] if v else []
-    t = SimpleNamespace(N=N, ntiles=ntiles, windows=windows, rows=rows, Q=Q, passes=passes, chunks=nchunks, tok0=prefix(N), win0=prefix(windows),
-                        pair0=prefix(Q), ctx_row0=prefix([q * w for q, w in zip(Q, windows)]), row0=prefix([q * r for q, r in zip(Q, rows)]),
-                        score_off=prefix([p * PASS_ROWS * x for p, x in zip(passes, ntiles)]),
-                        slot0=prefix([2 * p * c for p, c in zip(passes, nchunks)]),
-                        global_row0=[w + it[3] for w, it in zip(windows, items)])
+    prefix = ragged.prefix
+    t = ragged.item_geometry(items, H, W, ks)                   # (t.rows: of ONE pair of the item)
+    t.Q = [int(q) for q in guide_counts]
+    t.passes = [item_passes(nh, q) for q in t.Q]
+    work_sum = sum(n * p for n, p in zip(t.ntiles, t.passes))
+    t.chunks = [item_chunks(n, work_sum, chunks, n_cus) for n in t.ntiles]
+    t.pair0, t.ctx_row0, t.row0 = prefix(t.Q), prefix([q * w for q, w in zip(t.Q, t.windows)]), prefix([q * r for q, r in zip(t.Q, t.rows)])
+    t.score_off = prefix([p * PASS_ROWS * x for p, x in zip(t.passes, t.ntiles)])
+    t.slot0 = prefix([2 * p * c for p, c in zip(t.passes, t.chunks)])
     t.units = [(i, nt * c // nc, nt * (c + 1) // nc, p, s0 + 2 * p * nc + c)
-               for i, (nt, nc, s0, np_) in enumerate(zip(ntiles, nchunks, t.slot0, passes)) for p in range(np_) for c in range(nc)]
-    t.pairs = [(i, q, t.ctx_row0[i] + q * windows[i], t.row0[i] + q * rows[i]) for i in range(len(items)) for q in range(Q[i])]
-    t.pair_rows = [rows[i] for i, _, _, _ in t.pairs]
-    t.win_item = np.repeat(np.arange(len(items), dtype=np.int32), windows)
+               for i, (nt, nc, s0, np_) in enumerate(zip(t.ntiles, t.chunks, t.slot0, t.passes)) for p in range(np_) for c in range(nc)]
+    t.pairs = [(i, q, t.ctx_row0[i] + q * t.windows[i], t.row0[i] + q * t.rows[i]) for i in range(len(items)) for q in range(t.Q[i])]
+    t.pair_rows = [t.rows[i] for i, _, _, _ in t.pairs]
+    t.win_item = np.repeat(np.arange(len(items), dtype=np.int32), t.windows)
     t.row_pair = np.repeat(np.arange(len(t.pairs), dtype=np.int32), t.pair_rows)
-    t.slots = sum(2 * p * c for p, c in zip(passes, nchunks))
-    t.items = items
+    t.slots = sum(2 * p * c for p, c in zip(t.passes, t.chunks))
     return t
 
 
@@ -98,32 +88,20 @@ def check_inputs(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl):
     # the items are described as forward_ragged's; the guide rows are counted here, so the shared check sees M = sum Q_i rows
     counted = {}
 
+    def check_counts(B, counts):
+        if len(counts) != B:
+            raise ValueError(f"{WHAT}: {len(counts)} guide counts for {B} items (one per item)")
+        if any(not 1 <= q <= MAX_GUIDES for q in counts):
+            raise ValueError(f"{WHAT}: guide_counts {counts}: 1 <= Q_i <= {MAX_GUIDES} guides per item")
+
     def count_pairs():
         nonlocal split_sizes, modals, guide_counts
-        try:
-            split_sizes = tuple(int(t) for t in split_sizes)
-            guide_counts = tuple(int(q) for q in guide_counts)
-        except TypeError:
-            raise ValueError(f"{WHAT}: split_sizes and guide_counts are sequences of positive ints, one per item") from None
-        B = len(split_sizes)
-        if B == 0 or any(t <= 0 for t in split_sizes):
-            raise ValueError(f"{WHAT}: split_sizes is a sequence of positive ints, one per item (got {split_sizes})")
-        if sum(split_sizes) != ff.shape[0]:
-            raise ValueError(f"{WHAT}: sum(split_sizes) = {sum(split_sizes)} vs {ff.shape[0]} stacked frames")
-        if len(guide_counts) != B:
-            raise ValueError(f"{WHAT}: {len(guide_counts)} guide counts for {B} items (one per item)")
-        if any(not 1 <= q <= MAX_GUIDES for q in guide_counts):
-            raise ValueError(f"{WHAT}: guide_counts {guide_counts}: 1 <= Q_i <= {MAX_GUIDES} guides per item")
-        modals = (modals,) * B if isinstance(modals, str) else tuple(modals)
-        if len(modals) != B:
-            raise ValueError(f"{WHAT}: {len(modals)} modals for {B} items (one string, or one per item)")
-        if any(m not in ("image", "video") for m in modals):
-            raise ValueError(f"{WHAT}: modals are 'image' or 'video' (got {modals})")
+        split_sizes, modals, guide_counts = ragged.check_splits(WHAT, ff, split_sizes, modals, guide_counts, check_counts)
         E = ff.shape[-1]
         if not isinstance(guides, torch.Tensor) or guides.ndim != 2 or guides.shape[1] != E or guides.shape[0] != sum(guide_counts):
             raise ValueError(f"{WHAT}: guide_embeds is [sum Q_i, E] = [{sum(guide_counts)}, {E}], the guides of item i in the rows "
                              f"[sum_(j<i) Q_j, + Q_i) (got {tuple(guides.shape) if isinstance(guides, torch.Tensor) else None})")
-        counted["B"] = B
+        counted["B"] = len(split_sizes)
         return sum(guide_counts)
     _, E = seg.check_inputs(WHAT, "ragged multi-guide", proj, ff, fe, guides, nl, 4, "the stacked [sum T_i, H, W, E] tensor", count_pairs)
     for i, (t, m) in enumerate(zip(split_sizes, modals)):
@@ -132,42 +110,16 @@ def check_inputs(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl):
     return counted["B"], ff.shape[1], ff.shape[2], E, split_sizes, guide_counts, modals
 
 
-def exact_tilings(proj, split_sizes, modals, H, W, has_newline):
-    """ragged.item_descriptors under this step's name: the fields of hicom_ragged_item per item and the spatial window ks; raises unless
-    every item's windows partition its grid exactly, with square spatial windows."""
-    items, ks = [], None
-    for i, (T, modal) in enumerate(zip(split_sizes, modals)):
-        at, ay, ax = seg.exact_tilings(WHAT, proj, T, H, W, modal, f"item {i}: ")
-        ks = ay.k
-        lay = proj._layout((at.nwin, ay.nwin, ax.nwin), modal, has_newline, False)
-        nlr = lay.newline_rows
-        items.append((T, at.k, lay.nl_group, len(nlr), nlr[0] if nlr else 0, (nlr[1] - nlr[0]) if len(nlr) > 1 else 1,
-                      proj.global_compressor.num_queries))
-    return items, ks
-
-
-def new_args(proj):
-    return seg.new_args(proj, nv.CompressorRaggedMultiGuideArgs, None)          # (no adaptor recipe: check_inputs refuses it)
-
-
-def fill_common(a, proj, split_sizes, H, W, dev, out_dtype, chunks, ptr):
-    return seg.fill_common(a, proj, max(split_sizes), H, W, dev, out_dtype, chunks, ptr)
-
-
-def alloc_workspace(args, a, dev):
-    return seg.alloc_workspace(args, a, nv.compressor_ragged_multiguide_workspace, dev)
-
-
 def _build(proj, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev, stream):
-    desc, ks = exact_tilings(proj, split_sizes, modals, H, W, nl is not None)
+    desc, ks = ragged.item_descriptors(proj, split_sizes, modals, H, W, nl is not None, WHAT)
     items = (nv.RaggedItem * len(desc))(*[nv.RaggedItem(*d) for d in desc])
     counts = (C.c_int32 * len(guide_counts))(*guide_counts)
-    args, a, keep, ptr = new_args(proj)
+    args, a, keep, ptr = seg.new_args(proj, nv.CompressorRaggedMultiGuideArgs, None)       # (no adaptor recipe: check_inputs refuses it)
     a.B, a.E, a.ks, a.items = len(desc), E, ks, items
     a.guide_counts, a.n_guide_counts = counts, len(guide_counts)
-    refresh = fill_common(a, proj, split_sizes, H, W, dev, out_dtype, chunks, ptr)
+    refresh = seg.fill_common(a, proj, max(split_sizes), H, W, dev, out_dtype, chunks, ptr)
     a.stream = stream
-    ws, _ = alloc_workspace(args, a, dev)                       # (the kernels' limits raise here, in front of any launch)
+    ws, _ = seg.alloc_workspace(args, a, nv.compressor_ragged_multiguide_workspace, dev)     # (the kernels' limits raise here, in front of any launch)
     nv.compressor_ragged_multiguide_prepare(args)               # the device tables, once per plan (synchronises the stream)
     tables = plan_tables(desc, guide_counts, H, W, ks, a.nh, torch.cuda.get_device_properties(dev).multi_processor_count, a.chunks)
     plan = seg.SegPlan(args, ws, tables.pair_rows, a.hidden, (items, counts), tables)
@@ -175,27 +127,15 @@ def _build(proj, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chun
     return plan
 
 
-def call_inputs(proj, ff, fe, guides, nl):
-    return seg.call_inputs(proj, WHAT, ff, fe, guides, nl)
-
-
-def patch_io(a, ff, fe, guides, nl, out, stream):
-    seg.patch_io(a, ff, fe, guides, nl, out, stream)            # (the newline pointer whenever given: items differ in their newline rows)
-
-
-def cached_plan(proj, key, build):
-    return seg.cached_plan(proj, STORE, key, build)
-
-
 def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None):
     B, H, W, E, split_sizes, guide_counts, modals = check_inputs(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl)
-    dev, ff, fe, guides, nl, out_dtype, stream = call_inputs(proj, ff, fe, guides, nl)
+    dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, WHAT, ff, fe, guides, nl)
     key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
            seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v, guide_counts)
-    plan = cached_plan(proj, key, lambda: _build(proj, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev, stream))
+    plan = seg.cached_plan(proj, STORE, key, lambda: _build(proj, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev, stream))
     t = plan.tables
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
-    patch_io(plan.io, ff, fe, guides, nl, out, stream)
+    seg.patch_io(plan.io, ff, fe, guides, nl, out, stream)      # (the newline pointer whenever given: items differ in their newline rows)
     nv.compressor_ragged_multiguide_fwd(plan.args)
     # item i: its Q_i pairs' rows follow each other, all of one length -- a [Q_i, rows_i, hidden] view of the one storage
     return [v.view(q, r, plan.hidden) for v, q, r in zip(out.split([q * r for q, r in zip(t.Q, t.rows)]), t.Q, t.rows)]

@@ -6,6 +6,7 @@ As in tests/test_multi_guide_host.py: with chunks > 0 the workspace function and
 code, pointer fields are made-up aligned addresses that nothing reads before a launch, and every *_fwd / *_prepare case breaks one rule, so
 none launches or copies."""
 import ctypes
+import hashlib
 import os
 import re
 import shutil
@@ -148,6 +149,34 @@ def test_table_region_and_every_region_are_256_byte_aligned():
     assert sizes[1] - sizes[0] == _up(28 * 16 * 1152 * 4) - _up(14 * 16 * 1152 * 4) + 2 * (_up(28 * 64) - _up(14 * 64)) + _up(14 * 32) - _up(7 * 32)
 
 
+# ---- pinned values: the workspace function and the host mirror's table image, recorded before the host walk was shared -----------------
+PIN_CASES = {"mix6": (MIX6, (1, 3, 5, 2, 4)), "ones": (MIX6, (1,) * 5), "q32": ([CLIP4], (32,))}
+PIN_OVER = {"f32": dict(), "bf16_pos_h896": dict(out_dt=nv.DT_BF16, P=28, hidden=896)}
+# (case, chunks) -> workspace bytes (f32, bf16_pos_h896), ints of the table image, first 16 hex digits of its SHA-256 (little-endian int32)
+PINS = {
+    ("mix6", 1): (2766592, 3098624, 896, "c5f4793c21d15a17"),
+    ("mix6", 3): (4835072, 5167104, 1024, "d8c9328a93962cac"),
+    ("mix6", 18): (7937536, 8269568, 1216, "5caa2c7971c90e7d"),
+    ("ones", 1): (1365760, 1480704, 512, "f4cd85455c6790ad"),
+    ("ones", 3): (2843136, 2958080, 576, "a9d4d3826643cfc3"),
+    ("ones", 18): (5945600, 6060544, 768, "1cf94ec2c3837f3e"),
+    ("q32", 1): (4960000, 5613568, 1536, "e3406d3f95114e43"),
+    ("q32", 3): (7619328, 8272896, 1664, "3628efd9b0f678e2"),
+    ("q32", 18): (15597568, 16251136, 2112, "4369d903f742e8a7"),
+}
+
+
+@pytest.mark.parametrize("case,chunks", list(PINS))
+def test_workspace_bytes_and_table_image_are_pinned(case, chunks):
+    """chunks > 0, so no device count enters either figure."""
+    items, counts = PIN_CASES[case]
+    f32, bf16, ints, digest = PINS[case, chunks]
+    got = [call("workspace_bytes", block(items, counts, chunks=chunks, **over))[0] for over in PIN_OVER.values()]
+    assert got == [f32, bf16]
+    img = rmg.table_image(rmg.plan_tables(items, counts, 6, 6, 3, 9, N_CUS, chunks))
+    assert (img.size, hashlib.sha256(img.astype("<i4").tobytes()).hexdigest()[:16]) == (ints, digest)
+
+
 def projector(hidden=64, **over):
     return hicom_amd.build_vision_projector(SimpleNamespace(**{**cases.DEFAULT_CFG, "hidden_size": hidden, **over}))
 
@@ -156,7 +185,7 @@ def projector(hidden=64, **over):
 def test_single_guides_have_the_ragged_steps_units(chunks):
     proj = projector()
     splits, modals = [1, 4, 1, 8, 1], ["image", "video", "video", "video", "image"]
-    desc, ks = rmg.exact_tilings(proj, splits, modals, 6, 6, False)
+    desc, ks = ragged.item_descriptors(proj, splits, modals, 6, 6, False, "forward_ragged_multi_guide")
     assert (desc, ks) == ragged.item_descriptors(proj, splits, modals, 6, 6, False)
     t = rmg.plan_tables(desc, [1] * 5, 6, 6, ks, 9, N_CUS, chunks)
     r = ragged.plan_tables(desc, 6, 6, ks, N_CUS, chunks)
