@@ -25,6 +25,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .engine import patch_guide
 from .events import device_event
 
 
@@ -138,12 +139,11 @@ class _ShardSet:
     """One set of exchange buffers + argument blocks + workspaces (two sets alternate so that the all-gather of step i
     can still be reading its send buffer while step i+1 streams into the other one)."""
     __slots__ = ("mine", "everyone", "a_stream", "a_finish", "ws_stream", "ws_finish", "ev_stream", "ev_tok", "out", "fused", "r0", "direct_ag", "on_comm",
-                 "states_all", "tok_direct")
+                 "states_all", "tok_direct", "guide_slots")
 
 
 class _ShardPlan:
-    __slots__ = ("sets", "xs", "comm", "res", "lay", "pack", "nw", "hidden", "odt", "n_rows_total", "world", "rank", "sig",
-                 "guide_fields")
+    __slots__ = ("sets", "xs", "comm", "res", "lay", "pack", "nw", "hidden", "odt", "n_rows_total", "world", "rank", "sig")
 
     def set_inputs(self, st: _ShardSet, ff, fe, guide, out):
         """Patches this call's tensors into both argument blocks of a buffer set."""
@@ -151,10 +151,9 @@ class _ShardPlan:
             a.ff = ff.data_ptr()
             if fe is not None:
                 a.fe = fe.data_ptr()
-            if guide is not None:
-                for f in self.guide_fields:
-                    setattr(a, f, guide.data_ptr())
             a.out = out.data_ptr()
+        if guide is not None:
+            patch_guide(st.guide_slots, guide.data_ptr())
         if st.tok_direct:
             st.a_finish.ag_recv = out.data_ptr()       # (the token all-gather lands in the output's first world * nw rows)
 
@@ -267,20 +266,21 @@ def _shard_plan(projector, ff_shard, fe_shard, guide_embed, total_frames, image_
         st = _ShardSet()
         st.mine, st.everyone = mine, everyone
         state_mine, tok_mine = pack.state_view(st.mine), pack.tokens_view(st.mine, odt)
-        st.a_stream = engine.build_args(projector, ff_shard, fe_shard, guide_embed, "video", None, probe, None, t_offset=t0,
-                                        phases=nv.PHASE_STREAM, local_out=tok_mine, state_out=state_mine,
-                                        global_row0=lay.n_rows)
+        b_stream = engine.build_args(projector, ff_shard, fe_shard, guide_embed, "video", None, probe, None, t_offset=t0,
+                                     phases=nv.PHASE_STREAM, local_out=tok_mine, state_out=state_mine,
+                                     global_row0=lay.n_rows)
         # one workspace per buffer set AND plan: with MERGE_ON_NEXT the comm stream merges this set's partial states
         # while the main stream already runs the next step (on the other set, or of another plan)
+        st.a_stream = b_stream.block
         st.ws_stream = engine.attach_execution(st.a_stream, dev)
-        st.a_finish = engine.build_args(projector, ff_shard, fe_shard, guide_embed, "video", None, probe, None, t_offset=t0,
-                                        phases=nv.PHASE_FINISH, local_out=tok_mine, state_out=state_mine,
-                                        state_sets=st.everyone, state_set_stride=pack.set_stride_floats, nsets=world,
-                                        global_row0=lay.n_rows)
+        b_finish = engine.build_args(projector, ff_shard, fe_shard, guide_embed, "video", None, probe, None, t_offset=t0,
+                                     phases=nv.PHASE_FINISH, local_out=tok_mine, state_out=state_mine,
+                                     state_sets=st.everyone, state_set_stride=pack.set_stride_floats, nsets=world,
+                                     global_row0=lay.n_rows)
         # the FINISH phase runs on the comm stream (it reads only the gathered states)
+        st.a_finish = b_finish.block
         st.ws_finish = engine.attach_execution(st.a_finish, dev, main_stream=plan.comm, res=plan.res)
-        plan.guide_fields = st.a_stream._guide_ptr_fields
-        st.a_stream._keep = st.a_finish._keep = None
+        st.guide_slots = b_stream.guide_slots + b_finish.guide_slots      # (the borrowed tensors are not pinned: their pointers are patched per call)
         st.out = torch.empty((plan.n_rows_total, hidden), dtype=odt, device=dev)
         st.ev_stream, st.ev_tok = device_event(), torch.cuda.Event()      # (ev_stream: stream-to-stream on this device -- no system-scope fence, events.py)
         st.ev_stream.record(cur)                   # (hipEventRecord from C needs created events)

@@ -106,163 +106,206 @@ class Fp16NotFused(NotImplementedError):
     """fp16 tokens: this call does not take the fused release step (the fp16 projector then casts its inputs to bf16)."""
 
 
-def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, t_offset=0,
-               phases=nv.PHASE_STREAM | nv.PHASE_FINISH, local_out=None, state_out=None,
-               state_sets=None, state_set_stride=0, nsets=0, global_row0=None, stages=("local", "global"), local_row0=0,
-               tok16=False) -> nv.CompressorArgs:
-    """`stages` / `local_row0`: one SEGMENT of an anyres dict input (reference projector.py:679-689: the base image takes the local stage
-    only; the patch grid both, its rows behind the base image's) written into rows of a shared output.
-    tok16: fp16 frames_feature / frames_embed / guide (hicom_compressor_args.tok_dt; the release step only: Fp16NotFused otherwise)."""
-    from .projector import _require_bf16_cuda
+class BuiltArgs:
+    """What build_args returns: the filled argument block and everything that belongs to it on the Python side."""
+    __slots__ = ("block", "keep", "guide_slots", "queries", "producers")
 
-    def _require_tok(name, t):
-        if not tok16:
-            return _require_bf16_cuda(name, t)
-        if not t.is_cuda or t.dtype != torch.float16:
-            raise Fp16NotFused(f"{name}: fp16 tokens take fp16 CUDA tensors (got {t.dtype} on {t.device})")
-    lc = proj.local_compressor if "local" in stages else None
-    gc = proj.global_compressor if "global" in stages else None
-    a = nv.CompressorArgs()
-    _require_tok("frames_feature", ff)
-    a.tok_dt = nv.DT_F16 if tok16 else nv.DT_BF16
-    T, H, W, E = ff.shape
-    a.ff, a.T, a.H, a.W, a.E = ff.data_ptr(), T, H, W, E
-    a.fe = None
-    a.phases = phases
-    a.has_local, a.has_global = int(lc is not None), int(gc is not None)
-    a.hidden = (lc or gc).readout[2].out_features
-    keep = [ff]
-    a._guide_ptr_fields = ()            # argument fields that alias the caller's guide tensor (patched per call)
-    ext_l = ext_g = None
-    gptr = None if guide_embed is None else guide_embed.data_ptr()
-    if lc is not None:
-        lc._check_native()
+    def __init__(self):
+        self.block = nv.CompressorArgs()
+        self.keep = []              # borrowed tensors, alive until the call is enqueued (a plan drops them: their pointers are patched per call)
+        self.guide_slots = []       # (struct, field) pairs that alias the caller's guide tensor: patch_guide() per call
+        self.queries = None         # producer of per-call query rows (coarse / fine injection, query adaptors), or None
+        self.producers = []         # (cached producer of a weight-derived device table, its arguments) per table the block points at
+
+    def take(self, producer, *args):
+        """The table(s) of a cached, weight-derived producer; the call is what refresh() repeats."""
+        self.producers.append((producer, args))
+        return producer(*args)
+
+    def refresh(self):
+        """After the weights changed in place: re-runs the producers, which rebuild their tables into the buffers the block points at."""
+        for producer, args in self.producers:
+            producer(*args)
+
+
+def patch_guide(slots, ptr):
+    """Enters this call's guide address into every field that aliases the guide (BuiltArgs.guide_slots)."""
+    for struct, field in slots:
+        setattr(struct, field, ptr)
+
+
+def adaptor_streams(lc):
+    """(field of the argument block, MLP, LayerNorm, alpha) per adapted stream of the local compressor."""
+    return [s for on, s in ((lc.adapt_k, ("ak", lc.k_proj, lc.k_norm, lc.k_alpha)), (lc.adapt_v, ("av", lc.v_proj, lc.v_norm, lc.v_alpha))) if on]
+
+
+def _require_tok(tok16, name, t):
+    from .projector import _require_bf16_cuda
+    if not tok16:
+        return _require_bf16_cuda(name, t)
+    if not t.is_cuda or t.dtype != torch.float16:
+        raise Fp16NotFused(f"{name}: fp16 tokens take fp16 CUDA tensors (got {t.dtype} on {t.device})")
+
+
+def _fill_local_queries(b, lc, ls, ff, guide_embed, tok16):
+    """Where the local stage's per-window queries come from.  Returns the (rows, pooling scratch) buffers of queries made in front of
+    every call, or None."""
+    a, E = b.block, ff.shape[-1]
+    if lc.inject_in_call:
+        # coarse / fine injection into the pooled queries, run by the executor itself (hicom_compressor_args.inj_l)
+        if ls is not None:
+            raise NotImplementedError("the one-call executor takes injected local queries without clip-scale")
+        a.lq = None
+        inj_l = a.inj_l                                               # (a view of the block's memory, taken once)
+        _fill_injector(inj_l, lc.guide_injector, lc.use_guide, guide_embed, None, b.keep)
+        b.guide_slots.append((inj_l, "guide"))
+    elif lc.external_queries:
+        # coarse / fine injection, adapt_q, an adapted guide (ref :539-542): pooling + adaptor + injector run in front of every call
+        # (_query_producer) and leave f32 rows in buffers this plan owns
+        if ls is not None:
+            raise NotImplementedError("the one-call executor takes injected / adapted local queries without clip-scale")
+        grid = (a.at.nwin, a.ay.nwin, a.ax.nwin)
+        rows = 1 if lc.use_guide == "direct" else grid[0] * grid[1] * grid[2]
+        ext_l = (torch.empty((rows, E), dtype=torch.float32, device=ff.device),
+                 torch.empty((*grid, E), dtype=torch.float32, device=ff.device))
+        a.lq, a.lq_dt, a.lq_stride = ext_l[0].data_ptr(), nv.DT_F32, 0 if rows == 1 else E
+        return ext_l
+    elif lc.use_guide == "direct":
+        g = guide_embed
+        _require_tok(tok16, "guide_embed", g)
+        if g.ndim != 1 or g.shape[0] != E:
+            raise ValueError("direct guide injection takes a [D] guide embedding")
+        a.lq, a.lq_dt, a.lq_stride = g.data_ptr(), nv._dt(g), 0
+        b.guide_slots.append((a, "lq"))
+        b.keep.append(g)
+    else:
+        a.lq = None                                                   # pooled per-window query, made natively
+    return None
+
+
+def _fill_local(b, proj, lc, ff, fe, guide_embed, modal, tok16):
+    """The local stage: tilings, logit scale, queries, readout, k / v adaptors.  Returns _fill_local_queries' buffers."""
+    from . import injector as inj
+    from .projector import _require_bf16_cuda
+    a = b.block
+    lc._check_native()
+    if fe is not None:
+        _require_tok(tok16, "frames_embed", fe)
+        if fe.shape != ff.shape:
+            raise ValueError("frames_embed must have the shape of frames_feature")
+        a.fe = fe.data_ptr()
+        b.keep.append(fe)
+    a.at, a.ay, a.ax = (nv.Axis(t.n, t.k, t.nwin, t.nfull) for t in lc.tilings(*ff.shape[:3], modal))
+    ls = proj.local_logit
+    a.l2norm = 0
+    if ls is not None:                                                # ref :527-529, :549
+        a.l_scale, a.l_bias = math.exp(ls[0]), ls[1]
         if fe is not None:
-            _require_tok("frames_embed", fe)
-            if fe.shape != ff.shape:
-                raise ValueError("frames_embed must have the shape of frames_feature")
-            a.fe = fe.data_ptr()
-            keep.append(fe)
-        at, ay, ax = lc.tilings(T, H, W, modal)
-        a.at, a.ay, a.ax = (nv.Axis(t.n, t.k, t.nwin, t.nfull) for t in (at, ay, ax))
-        ls = proj.local_logit
-        a.l2norm = 0
-        if ls is not None:                                            # ref :527-529, :549
-            a.l_scale, a.l_bias = math.exp(ls[0]), ls[1]
-            if fe is not None:
-                a.l2norm = 1 | (2 if lc.use_guide == "direct" else 0)
-        else:
-            a.l_scale, a.l_bias = 1.0 / math.sqrt(lc.qk_dim), 0.0      # ref :551
-        if lc.inject_in_call:
-            # coarse / fine injection into the pooled queries, run by the executor itself (hicom_compressor_args.inj_l)
-            if ls is not None:
-                raise NotImplementedError("the one-call executor takes injected local queries without clip-scale")
-            a.lq = None
-            _fill_injector(a.inj_l, lc.guide_injector, lc.use_guide, guide_embed, None, keep)
-            a._guide_ptr_fields += ("inj_l.guide",)
-        elif lc.external_queries:
-            # coarse / fine injection, adapt_q, an adapted guide (ref :539-542): pooling + adaptor + injector run in front of every call
-            # (`_queries` below) and leave f32 rows in buffers this plan owns
-            if ls is not None:
-                raise NotImplementedError("the one-call executor takes injected / adapted local queries without clip-scale")
-            nw = at.nwin * ay.nwin * ax.nwin
-            rows = 1 if lc.use_guide == "direct" else nw
-            ext_l = (torch.empty((rows, E), dtype=torch.float32, device=ff.device),
-                     torch.empty((at.nwin, ay.nwin, ax.nwin, E), dtype=torch.float32, device=ff.device))
-            a.lq, a.lq_dt, a.lq_stride = ext_l[0].data_ptr(), nv.DT_F32, 0 if rows == 1 else E
-        elif lc.use_guide == "direct":
-            g = guide_embed
-            _require_tok("guide_embed", g)
-            if g.ndim != 1 or g.shape[0] != E:
-                raise ValueError("direct guide injection takes a [D] guide embedding")
-            a.lq, a.lq_dt, a.lq_stride = g.data_ptr(), nv._dt(g), 0
-            a._guide_ptr_fields += ("lq",)
-            keep.append(g)
-        else:
-            a.lq = None                                               # pooled per-window query, made natively
-        a.lw0, a.lb0 = _w(lc.readout[0])
-        a.lw2, a.lb2 = _w(lc.readout[2])
-        w0_16, w2_16 = lc.readout_f16()                               # fp16 copies, cached per weight version
-        a.lw0_f16, a.lw2_f16 = w0_16.data_ptr(), w2_16.data_ptr()
-        keep += [w0_16, w2_16]
-        if lc.adapt_k or lc.adapt_v:                                  # k / v adaptors (ref :431-457, :533-534)
-            from . import injector as inj
-            if ls is not None:
-                raise NotImplementedError("the one-call executor takes k / v adaptors without clip-scale")
-            for on, dst, mlp, norm, alpha in ((lc.adapt_k, a.ak, lc.k_proj, lc.k_norm, lc.k_alpha), (lc.adapt_v, a.av, lc.v_proj, lc.v_norm, lc.v_alpha)):
-                if not on:
-                    continue
-                dst.w0, dst.b0 = _w(mlp[0])
-                w2_16a = inj._f16_weight(mlp[2])
-                dst.w2_f16, dst.b2 = w2_16a.data_ptr(), mlp[2].bias.data_ptr()
-                _require_bf16_cuda("adaptor norm", norm.weight)
-                dst.gamma, dst.beta, dst.alpha = norm.weight.data_ptr(), norm.bias.data_ptr(), alpha.data_ptr()
-                a.adapt_alpha_dt, a.adapt_eps = nv._dt(alpha), norm.eps
-                keep.append(w2_16a)
-    if gc is not None:
-        gc._check_native(None)
-        if proj.global_logit is not None:
-            raise NotImplementedError("the one-call executor has no clip-scale global stage (use forward_stepwise)")
-        if gc.inject_in_call:
-            q_in, n_rows = gc.query.detach(), gc.num_queries                # injected by the executor itself (hicom_compressor_args.inj_g)
-            _require_bf16_cuda("global_compressor.query", q_in)
-            _fill_injector(a.inj_g, gc.guide_injector, gc.use_guide, guide_embed, q_in, keep)
-            a._guide_ptr_fields += ("inj_g.guide",)
-            a.gq_dt = nv.DT_BF16
-            keep.append(q_in)
-        elif gc.external_queries:
-            # injected through coarse / fine / an adapted guide (ref :642 with :369-397): f32 rows in a buffer this plan owns, refilled per call
-            q_in, n_rows = gc.injected_queries(guide_embed)
-            ext_g = torch.empty((q_in.shape[0], E), dtype=torch.float32, device=ff.device)
-            q_in = ext_g
-            a.gq_dt = nv.DT_F32
-        elif tok16:
-            # (the fp16 release step: the injected query row IS the fp16 guide -- direct mode through a plain injector)
-            if not (gc.use_guide == "direct" and gc.is_plain and guide_embed is not None):
-                raise Fp16NotFused("fp16 tokens: the global stage takes the direct guide")
-            _require_tok("guide_embed", guide_embed)
-            q_in, n_rows = guide_embed.reshape(1, -1), gc.num_queries
-            a.gq_dt = nv.DT_F16
-            keep.append(q_in)
-        else:
-            q_in, n_rows = gc.injected_queries(guide_embed)
-            a.gq_dt = nv.DT_BF16
-            keep.append(q_in)
-        att = gc.attn_layer
-        a.gq, a.nq, a.nh, a.n_global_rows = q_in.data_ptr(), q_in.shape[0], att.num_heads, n_rows
-        if gptr is not None and q_in.data_ptr() == gptr:
-            a._guide_ptr_fields += ("gq",)
-        a.wq, a.bq = _w(att.q_proj)
-        a.wk, _ = _w(att.k_proj)
-        a.wv, a.bv = _w(att.v_proj)
-        a.wo, a.bo = _w(att.out_proj)
-        a.gw0, a.gb0 = _w(gc.readout[0])
-        a.gw2, a.gb2 = _w(gc.readout[2])
-        a.gc0 = None
-        if gc.use_guide == "direct" and q_in.shape[0] == 1 and gc.readout[0].bias is not None and att.out_proj.bias is not None:
-            c0 = gc.readout_over_out_proj()                           # weight-only product: the five-launch step of the release recipe
-            a.gc0 = c0.data_ptr()
-            keep.append(c0)
-        if gc.use_pos_emb:
-            pe, kpe, cap = gc.pos_and_kpe(t_offset + T, H, W, ff.device)
-            pe_hi, pe_lo = gc.pos_planes(t_offset + T, H, W, ff.device, torch.float16 if tok16 else torch.bfloat16)
-            a.pe, a.kpe, a.P = pe.data_ptr(), kpe.data_ptr(), pe.shape[0]
-            a.pe_hi, a.pe_lo = pe_hi.data_ptr(), pe_lo.data_ptr()
-            a.t_index0, a.y_index0, a.x_index0 = t_offset, cap, cap + H
-            keep += [pe, kpe, pe_hi, pe_lo]
-            a.vpe_f16, a.marg_slots = None, 0
-            if a.gc0 and lc is not None and t_offset == 0 and state_out is None and os.environ.get("HICOM_RING_MARG", "0") == "1":
-                # release step, opt-in (measured a net loss, DESIGN.md §10): the value-side pos-emb in the merge role (v_proj . pe^T,
-                # weight-only) instead of behind the ring's token stream.  The table is only built -- and rebuilt by every training
-                # step's refresh -- when the switch is on.
-                vpe = gc.vpe_f16(T, H, W, ff.device)
-                if vpe is not None:
-                    a.vpe_f16, a.marg_slots = vpe.data_ptr(), vpe.shape[1]
-                    keep.append(vpe)
-        else:
-            a.pe = a.kpe = a.pe_hi = a.pe_lo = None
-            a.P = 0
-            a.vpe_f16, a.marg_slots = None, 0
+            a.l2norm = 1 | (2 if lc.use_guide == "direct" else 0)
+    else:
+        a.l_scale, a.l_bias = 1.0 / math.sqrt(lc.qk_dim), 0.0          # ref :551
+    ext_l = _fill_local_queries(b, lc, ls, ff, guide_embed, tok16)
+    a.lw0, a.lb0 = _w(lc.readout[0])
+    a.lw2, a.lb2 = _w(lc.readout[2])
+    w0_16, w2_16 = b.take(lc.readout_f16)                             # fp16 copies, cached per weight version
+    a.lw0_f16, a.lw2_f16 = w0_16.data_ptr(), w2_16.data_ptr()
+    b.keep += [w0_16, w2_16]
+    streams = adaptor_streams(lc)                                     # k / v adaptors (ref :431-457, :533-534)
+    if streams and ls is not None:
+        raise NotImplementedError("the one-call executor takes k / v adaptors without clip-scale")
+    for field, mlp, norm, alpha in streams:
+        dst = getattr(a, field)
+        dst.w0, dst.b0 = _w(mlp[0])
+        w2_16a = b.take(inj._f16_weight, mlp[2])
+        dst.w2_f16, dst.b2 = w2_16a.data_ptr(), mlp[2].bias.data_ptr()
+        _require_bf16_cuda("adaptor norm", norm.weight)
+        dst.gamma, dst.beta, dst.alpha = norm.weight.data_ptr(), norm.bias.data_ptr(), alpha.data_ptr()
+        a.adapt_alpha_dt, a.adapt_eps = nv._dt(alpha), norm.eps
+        b.keep.append(w2_16a)
+    return ext_l
+
+
+def _fill_global_queries(b, gc, ff, guide_embed, tok16):
+    """Where the global stage's injected queries come from.  Returns (query rows handed to the block, output rows, the buffer of rows made
+    in front of every call or None)."""
+    from .projector import _require_bf16_cuda
+    a, ext_g = b.block, None
+    if gc.inject_in_call:
+        q_in, n_rows = gc.query.detach(), gc.num_queries                # injected by the executor itself (hicom_compressor_args.inj_g)
+        _require_bf16_cuda("global_compressor.query", q_in)
+        inj_g = a.inj_g
+        _fill_injector(inj_g, gc.guide_injector, gc.use_guide, guide_embed, q_in, b.keep)
+        b.guide_slots.append((inj_g, "guide"))
+        a.gq_dt = nv.DT_BF16
+        b.keep.append(q_in)
+    elif gc.external_queries:
+        # injected through coarse / fine / an adapted guide (ref :642 with :369-397): f32 rows in a buffer this plan owns, refilled per call
+        q_in, n_rows = gc.injected_queries(guide_embed)
+        q_in = ext_g = torch.empty((q_in.shape[0], ff.shape[-1]), dtype=torch.float32, device=ff.device)
+        a.gq_dt = nv.DT_F32
+    elif tok16:
+        # (the fp16 release step: the injected query row IS the fp16 guide -- direct mode through a plain injector)
+        if not (gc.use_guide == "direct" and gc.is_plain and guide_embed is not None):
+            raise Fp16NotFused("fp16 tokens: the global stage takes the direct guide")
+        _require_tok(tok16, "guide_embed", guide_embed)
+        q_in, n_rows = guide_embed.reshape(1, -1), gc.num_queries
+        a.gq_dt = nv.DT_F16
+        b.keep.append(q_in)
+    else:
+        q_in, n_rows = gc.injected_queries(guide_embed)
+        a.gq_dt = nv.DT_BF16
+        b.keep.append(q_in)
+    return q_in, n_rows, ext_g
+
+
+def _fill_global(b, proj, gc, ff, guide_embed, t_offset, release_tail, tok16):
+    """The global stage: queries, attention and readout weights, positional tables.  release_tail: the call may take the release step's
+    opt-in merge-role form (a local stage, the whole clip, no state output).  Returns _fill_global_queries' buffer."""
+    a = b.block
+    T, H, W, _ = ff.shape
+    gc._check_native(None)
+    if proj.global_logit is not None:
+        raise NotImplementedError("the one-call executor has no clip-scale global stage (use forward_stepwise)")
+    q_in, n_rows, ext_g = _fill_global_queries(b, gc, ff, guide_embed, tok16)
+    att = gc.attn_layer
+    a.gq, a.nq, a.nh, a.n_global_rows = q_in.data_ptr(), q_in.shape[0], att.num_heads, n_rows
+    if guide_embed is not None and q_in.data_ptr() == guide_embed.data_ptr():
+        b.guide_slots.append((a, "gq"))
+    a.wq, a.bq = _w(att.q_proj)
+    a.wk, _ = _w(att.k_proj)
+    a.wv, a.bv = _w(att.v_proj)
+    a.wo, a.bo = _w(att.out_proj)
+    a.gw0, a.gb0 = _w(gc.readout[0])
+    a.gw2, a.gb2 = _w(gc.readout[2])
+    a.gc0 = None
+    if gc.use_guide == "direct" and q_in.shape[0] == 1 and gc.readout[0].bias is not None and att.out_proj.bias is not None:
+        c0 = b.take(gc.readout_over_out_proj)                         # weight-only product: the five-launch step of the release recipe
+        a.gc0 = c0.data_ptr()
+        b.keep.append(c0)
+    a.pe = a.kpe = a.pe_hi = a.pe_lo = None
+    a.P = 0
+    a.vpe_f16, a.marg_slots = None, 0
+    if gc.use_pos_emb:
+        pe, kpe, cap = b.take(gc.pos_and_kpe, t_offset + T, H, W, ff.device)
+        pe_hi, pe_lo = gc.pos_planes(t_offset + T, H, W, ff.device, torch.float16 if tok16 else torch.bfloat16)
+        a.pe, a.kpe, a.P = pe.data_ptr(), kpe.data_ptr(), pe.shape[0]
+        a.pe_hi, a.pe_lo = pe_hi.data_ptr(), pe_lo.data_ptr()
+        a.t_index0, a.y_index0, a.x_index0 = t_offset, cap, cap + H
+        b.keep += [pe, kpe, pe_hi, pe_lo]
+        if a.gc0 and release_tail and os.environ.get("HICOM_RING_MARG", "0") == "1":
+            # release step, opt-in (measured a net loss, DESIGN.md §10): the value-side pos-emb in the merge role (v_proj . pe^T,
+            # weight-only) instead of behind the ring's token stream.  The table is only built -- and rebuilt by every training
+            # step's refresh -- when the switch is on.
+            vpe = b.take(gc.vpe_f16, T, H, W, ff.device)
+            if vpe is not None:
+                a.vpe_f16, a.marg_slots = vpe.data_ptr(), vpe.shape[1]
+                b.keep.append(vpe)
+    return ext_g
+
+
+def _fill_output(b, out, layout, image_newline, local_row0, global_row0, local_out, state_out, state_sets, state_set_stride, nsets):
+    """Output rows, newline rows and the state fields of a sharded phase."""
+    a = b.block
     a.out, a.out_dt, a.ldo = out.data_ptr(), nv._dt(out), out.shape[-1]
     a.local_row0 = local_row0
     a.nl_group = layout.nl_group if layout is not None else 0
@@ -270,41 +313,72 @@ def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, 
     a.nl_count = 0
     if layout is not None and layout.newline_rows:
         nl = image_newline
-        keep.append(nl)
+        b.keep.append(nl)
         a.newline, a.newline_dt = nl.data_ptr(), nv._dt(nl)
         a.nl_first = layout.newline_rows[0] + local_row0
         a.nl_step = layout.newline_rows[1] - layout.newline_rows[0] if len(layout.newline_rows) > 1 else 1
         a.nl_count = len(layout.newline_rows)
     a.local_out, a.state_out = _p(local_out), _p(state_out)
     a.state_sets, a.state_set_stride, a.nsets = _p(state_sets), state_set_stride, nsets
-    a._keep = keep                      # keeps borrowed tensors alive until the call is enqueued
-    a._queries = None
-    if ext_l is not None or ext_g is not None:
-        grid = (a.at.nwin, a.ay.nwin, a.ax.nwin) if lc is not None else None
 
-        def queries(ff, guide, res=None, lc=lc, gc=gc, ext_l=ext_l, ext_g=ext_g, grid=grid, a=a):
-            """Fills the plan's query rows for this call.  The global rows on the current stream (the stream kernel needs them first);
-            the local rows -- pooling, adaptor, injector: up to ~10 launches, two of them GEMMs over all windows -- on `res.inj` beside
-            the global stage's stream kernel, the executor waiting for `res.ev_lq` in front of the window kernel.  res=None (graph
-            capture): everything on the current stream."""
-            if ext_g is not None:
-                gc.make_queries(guide, ext_g)
-            a.ev_queries = None
-            if ext_l is not None:
-                if res is None or gc is None:
+
+def _query_producer(a, lc, gc, ext_l, ext_g):
+    """The per-call producer of the query rows a.lq / a.gq point into (the closure owns those buffers)."""
+    grid = (a.at.nwin, a.ay.nwin, a.ax.nwin) if lc is not None else None
+
+    def queries(ff, guide, res=None):
+        """Fills the plan's query rows for this call.  The global rows on the current stream (the stream kernel needs them first);
+        the local rows -- pooling, adaptor, injector: up to ~10 launches, two of them GEMMs over all windows -- on `res.inj` beside
+        the global stage's stream kernel, the executor waiting for `res.ev_lq` in front of the window kernel.  res=None (graph
+        capture): everything on the current stream."""
+        if ext_g is not None:
+            gc.make_queries(guide, ext_g)
+        a.ev_queries = None
+        if ext_l is not None:
+            if res is None or gc is None:
+                lc.make_queries(ff, guide, grid, ext_l[1], ext_l[0])
+            else:
+                main = torch.cuda.current_stream(ff.device)
+                res.inj.wait_stream(main)          # (inputs ready; the previous call's readers of the rows are done)
+                with torch.cuda.stream(res.inj):
                     lc.make_queries(ff, guide, grid, ext_l[1], ext_l[0])
-                else:
-                    main = torch.cuda.current_stream(ff.device)
-                    res.inj.wait_stream(main)          # (inputs ready; the previous call's readers of the rows are done)
-                    with torch.cuda.stream(res.inj):
-                        lc.make_queries(ff, guide, grid, ext_l[1], ext_l[0])
-                        res.ev_lq.record(res.inj)
-                    ff.record_stream(res.inj)
-                    if guide is not None:
-                        guide.record_stream(res.inj)
-                    a.ev_queries = res.ev_lq.cuda_event
-        a._queries = queries            # (the closure owns the buffers a.lq / a.gq point into)
-    return a
+                    res.ev_lq.record(res.inj)
+                ff.record_stream(res.inj)
+                if guide is not None:
+                    guide.record_stream(res.inj)
+                a.ev_queries = res.ev_lq.cuda_event
+    return queries
+
+
+def build_args(proj, ff, fe, guide_embed, modal, image_newline, out, layout, *, t_offset=0,
+               phases=nv.PHASE_STREAM | nv.PHASE_FINISH, local_out=None, state_out=None,
+               state_sets=None, state_set_stride=0, nsets=0, global_row0=None, stages=("local", "global"), local_row0=0,
+               tok16=False) -> BuiltArgs:
+    """`stages` / `local_row0`: one SEGMENT of an anyres dict input (reference projector.py:679-689: the base image takes the local stage
+    only; the patch grid both, its rows behind the base image's) written into rows of a shared output.
+    tok16: fp16 frames_feature / frames_embed / guide (hicom_compressor_args.tok_dt; the release step only: Fp16NotFused otherwise)."""
+    lc = proj.local_compressor if "local" in stages else None
+    gc = proj.global_compressor if "global" in stages else None
+    b = BuiltArgs()
+    a = b.block
+    _require_tok(tok16, "frames_feature", ff)
+    a.tok_dt = nv.DT_F16 if tok16 else nv.DT_BF16
+    T, H, W, E = ff.shape
+    a.ff, a.T, a.H, a.W, a.E = ff.data_ptr(), T, H, W, E
+    a.fe = None
+    a.phases = phases
+    a.has_local, a.has_global = int(lc is not None), int(gc is not None)
+    a.hidden = (lc or gc).readout[2].out_features
+    b.keep.append(ff)
+    ext_l = ext_g = None
+    if lc is not None:
+        ext_l = _fill_local(b, proj, lc, ff, fe, guide_embed, modal, tok16)
+    if gc is not None:
+        ext_g = _fill_global(b, proj, gc, ff, guide_embed, t_offset, lc is not None and t_offset == 0 and state_out is None, tok16)
+    _fill_output(b, out, layout, image_newline, local_row0, global_row0, local_out, state_out, state_sets, state_set_stride, nsets)
+    if ext_l is not None or ext_g is not None:
+        b.queries = _query_producer(a, lc, gc, ext_l, ext_g)
+    return b
 
 
 def attach_execution(a: nv.CompressorArgs, device, main_stream=None, res=None) -> torch.Tensor:
@@ -330,22 +404,62 @@ def attach_execution(a: nv.CompressorArgs, device, main_stream=None, res=None) -
 class _Plan:
     """A filled argument block for one (projector state, problem shape) combination and the workspace it owns, plus --
     in graph mode -- the captured hipGraph of its launch sequence and the static buffer it writes."""
-    __slots__ = ("args", "ws", "rows", "hidden", "graph", "static_out", "hits", "fused", "sig", "guide_fields", "res", "fresh", "refresh",
+    __slots__ = ("args", "ws", "rows", "hidden", "graph", "static_out", "hits", "fused", "sig", "guide_slots", "res", "fresh", "refresh",
                  "queries")
 
-    def __init__(self, args, ws, rows, hidden, sig, res):
-        self.args, self.ws, self.rows, self.hidden, self.sig, self.res = args, ws, rows, hidden, sig, res
+    def __init__(self, built: BuiltArgs, ws, rows, hidden, res):
+        args = self.args = built.block
+        self.ws, self.rows, self.hidden, self.res = ws, rows, hidden, res
         self.fused = nv.compressor_is_fused(args)
-        self.guide_fields = args._guide_ptr_fields
+        self.guide_slots, self.queries = built.guide_slots, built.queries
+        built.keep = None          # the plan does not pin the caller's tensors: their pointers are patched per call
         self.graph = None
         self.static_out = None
         self.hits = 0
-        self.fresh = None          # weight CONTENT state (versions, epoch) the derived device caches were last built from
-        self.refresh = None        # callable that rebuilds them in place
-        self.queries = getattr(args, "_queries", None)     # producer of per-call query rows (coarse / fine injection, query adaptors), or None
+        self.sig = self.fresh = None       # (cached_plan) what the plan has baked in as addresses; the weight CONTENT state its tables were built from
+
+        def refresh():
+            built.refresh()
+            args.reuse_queries = 0         # guide off: the folded learnable queries are weight-derived too
+        self.refresh = refresh
+
+    def release(self):
+        """On eviction: the workspace may still be read by a deferred call's side stream, and the caching allocator must not hand the
+        block to another stream before that work has drained."""
+        self.ws.record_stream(self.res.side)
 
 
-_MAX_PLANS = 16      # per projector; plans live ON the module (they point into its cached device tables)
+MAX_PLANS = 16       # per store; plans live ON the module (they point into its cached device tables)
+
+
+def cached_plan(proj, store, key, build):
+    """THE plan-cache protocol of the package.  The plan of `key` in the module's store `store` ("_engine_plans", "_batch_plans", ...), built
+    by build() when there is none or the module's parameters were replaced (a build() that raises leaves no plan behind); weights changed
+    in place -- an optimizer step: every address still valid -- are followed by the plan's refresh(), which re-runs the producers of the
+    weight-derived tables into their buffers.  The oldest plan makes room for the seventeenth (its release(), if any).  Counts the use."""
+    plans = proj.__dict__.setdefault(store, {})
+    plan = plans.get(key)
+    sig = plan_sig(proj)
+    if plan is not None and plan.sig == sig:
+        fresh = content_sig(proj)
+        if plan.fresh != fresh:
+            plan.refresh()
+            sig = plan_sig(proj)                 # (a table that had to be reallocated bumps the cache generation)
+            plan.fresh = fresh
+    if plan is not None and plan.sig != sig:
+        plans.pop(key)
+        plan = None
+    if plan is None:
+        plan = build()
+        plan.sig = plan_sig(proj)                # (building may have (re)built the cached positional tables)
+        plan.fresh = content_sig(proj)
+        if len(plans) >= MAX_PLANS:
+            release = getattr(plans.pop(next(iter(plans))), "release", None)
+            if release is not None:
+                release()
+        plans[key] = plan
+    plan.hits += 1
+    return plan
 
 
 def _param_list(proj):
@@ -393,17 +507,6 @@ def weights_sig(proj):
         acc += p.data_ptr() + p._version * 1000003
     gc = proj.global_compressor
     return (id(proj), gen, acc, nv.weights_epoch(), 0 if gc is None else gc._cache_gen, proj.local_logit, proj.global_logit)
-
-
-def _evict_one(plans: dict):
-    """Drops the oldest plan.  Its workspace may still be read by a deferred call's side stream: the caching allocator
-    must not hand the block to another stream before that work has drained."""
-    k = next(iter(plans))
-    old = plans.pop(k)
-    res = getattr(old, "res", None)
-    ws = getattr(old, "ws", None)
-    if res is not None and ws is not None:
-        ws.record_stream(res.side)
 
 
 def last_window_contexts(proj, ff, modal):
@@ -492,22 +595,8 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
            ll is not None,
            None if adapt_y is None else tuple(t is not None for t in adapt_y),     # (supplied adaptor outputs: the workspace has no regions for them)
            seg_key, ff.dtype)
-    plans = proj.__dict__.setdefault("_engine_plans", {})
-    plan = plans.get(key)
-    sig = plan_sig(proj)
-    if plan is not None and plan.sig == sig:
-        fresh = content_sig(proj)
-        if plan.fresh != fresh:
-            # the weights changed under a plan whose addresses are all still valid (an optimizer step): re-run the producers of
-            # the weight-derived tables into their existing buffers instead of rebuilding the plan
-            plan.refresh()
-            plan.args.reuse_queries = 0            # guide off: the folded learnable queries are weight-derived too
-            sig = plan_sig(proj)                   # (a table that had to be reallocated bumps the cache generation)
-            plan.fresh = fresh
-    if plan is not None and plan.sig != sig:
-        plans.pop(key)
-        plan = None
-    if plan is None:
+
+    def build():
         T, H, W, _ = ff.shape
         layout = None
         n_local = 0
@@ -519,7 +608,8 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
         hidden = (lc or gc).readout[2].out_features
         row0 = segment["row0"] if segment is not None else 0
         probe = segment["out"] if segment is not None else torch.empty((n_local + n_global, hidden), dtype=out_dtype, device=dev)
-        a = build_args(proj, ff, fe, guide, modal, nl, probe, layout, global_row0=row0 + n_local, stages=stages, local_row0=row0, tok16=tok16)
+        built = build_args(proj, ff, fe, guide, modal, nl, probe, layout, global_row0=row0 + n_local, stages=stages, local_row0=row0, tok16=tok16)
+        a = built.block
         if tok16 and not nv.compressor_is_fused(a):
             raise Fp16NotFused("fp16 tokens: this geometry / recipe does not run on the fused release step")
         if adapt_y is not None:             # (before the workspace is sized: make_layout skips the regions of supplied outputs)
@@ -530,33 +620,8 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
             if not nv.compressor_is_fused(a):
                 raise NotImplementedError("local_logits=: this geometry does not run on the fused stream kernel (windows must "
                                           "partition the grid; see hicom_fused_stream_fwd in include/hicom_hip.h)")
-        ws = attach_execution(a, dev, res=res)
-        a._keep = None                 # the plan does not pin the caller's tensors: their pointers are patched per call
-        sig = plan_sig(proj)           # (build_args may have (re)built the cached positional tables)
-        if len(plans) >= _MAX_PLANS:
-            _evict_one(plans)
-        plan = plans[key] = _Plan(a, ws, n_local + n_global, hidden, sig, res)
-        plan.fresh = content_sig(proj)
-        use_gc0 = bool(a.gc0)
-        use_vpe = bool(a.vpe_f16)
-
-        def refresh(lc=lc, gc=gc, T=T, H=H, W=W, dev=dev, use_gc0=use_gc0, use_vpe=use_vpe):
-            if lc is not None:
-                lc.readout_f16()
-                if lc.adapt_k or lc.adapt_v:
-                    from . import injector as inj
-                    for on, mlp in ((lc.adapt_k, lc.k_proj), (lc.adapt_v, lc.v_proj)):
-                        if on:
-                            inj._f16_weight(mlp[2])
-            if gc is not None:
-                if gc.use_pos_emb:
-                    gc.pos_and_kpe(T, H, W, dev)
-                    if use_vpe:
-                        gc.vpe_f16(T, H, W, dev)
-                if use_gc0:
-                    gc.readout_over_out_proj()
-        plan.refresh = refresh
-    plan.hits += 1
+        return _Plan(built, attach_execution(a, dev, res=res), n_local + n_global, hidden, res)
+    plan = cached_plan(proj, "_engine_plans", key, build)
     a = plan.args
     # per-call pointers
     a.ff = ff.data_ptr()
@@ -567,10 +632,7 @@ def run_dense(proj, ff, fe, guide_embed, modal, image_newline, out_dtype, deferr
     a.ak.y = adapt_y[0].data_ptr() if adapt_y is not None and adapt_y[0] is not None else None
     a.av.y = adapt_y[1].data_ptr() if adapt_y is not None and adapt_y[1] is not None else None
     if guide is not None:
-        gp = guide.data_ptr()
-        for f in plan.guide_fields:
-            obj, _, leaf = f.rpartition(".")
-            setattr(getattr(a, obj) if obj else a, leaf, gp)
+        patch_guide(plan.guide_slots, guide.data_ptr())
     if nl is not None and a.nl_count > 0:
         a.newline = nl.data_ptr()
     if plan.queries is not None and deferred:

@@ -1,12 +1,13 @@
 """What HIComProjector.forward_batch (batch.py), forward_ragged (ragged.py) and forward_multi_guide (multi_guide.py) share on the Python
 side: the scope rule, the input checks, the plan (filled argument block + the workspace it owns), the fields of the argument block that
-come from the module alone, the plan builder of the two steps whose items share one shape, the call prologue, the per-call pointer patch
-and the plan-cache protocol.  The modules keep what depends on how items are described: one (T, H, W) shape and B or Q, or split sizes,
-modals and the table arithmetic.
+come from the module alone, the plan builder of the two steps whose items share one shape, the call prologue and the per-call pointer
+patch.  The modules keep what depends on how items are described: one (T, H, W) shape and B or Q, or split sizes, modals and the table
+arithmetic.
 
-Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`, `proj._multi_guide_plans`: at most MAX_PLANS each),
-like engine.run_dense's; the input / output pointers are patched per call.  forward_ragged_multi_guide (ragged_multi_guide.py: the product
-of the last two, `proj._ragged_multi_guide_plans`) is built on the same functions."""
+Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`, `proj._multi_guide_plans`: at most MAX_PLANS each)
+through engine.cached_plan, the ONE plan-cache protocol of the package: engine.run_dense's plans go through the same function.  The input /
+output pointers are patched per call.  forward_ragged_multi_guide (ragged_multi_guide.py: the product of the last two,
+`proj._ragged_multi_guide_plans`) is built on the same functions."""
 from __future__ import annotations
 
 import math
@@ -16,7 +17,7 @@ import torch
 from . import engine
 from . import native as nv
 
-MAX_PLANS = 16
+cached_plan, MAX_PLANS = engine.cached_plan, engine.MAX_PLANS       # (the steps' modules and the tests reach them here)
 
 
 class SegPlan:
@@ -42,18 +43,13 @@ def seg_recipe(proj):
     return "adaptkv" if (lc.adapt_k or lc.adapt_v) else "plain"
 
 
-def adaptor_streams(lc):
-    """(field of the argument block, MLP, LayerNorm, alpha) per adapted stream of the local compressor."""
-    return [s for on, s in ((lc.adapt_k, ("ak", lc.k_proj, lc.k_norm, lc.k_alpha)), (lc.adapt_v, ("av", lc.v_proj, lc.v_norm, lc.v_alpha))) if on]
-
-
 def fill_adaptors(a, lc, what, ptr):
     """The adaptor descriptors of a Compressor{Batch,Ragged}AdaptArgs block from the local compressor's parameters; `ptr` registers a
     tensor with the plan and returns its address.  The fp16 copy of the second layer's weight is the cached one of
     injector._f16_weight (range-checked when first built, refreshed in place: the plan holds its address)."""
     from . import injector as inj
     from .projector import _linear_params, _require_bf16_cuda
-    for field, mlp, norm, alpha in adaptor_streams(lc):
+    for field, mlp, norm, alpha in engine.adaptor_streams(lc):
         d = getattr(a, field)
         (w0, b0), (w2, b2) = _linear_params(mlp[0]), _linear_params(mlp[2])
         if w0.shape[0] % 64 or w0.shape[1] % 64 or w2.shape[0] % 64 or w0.shape != w2.shape:
@@ -68,7 +64,7 @@ def fill_adaptors(a, lc, what, ptr):
 def refresh_adaptors(lc):
     """Rebuilds, in place, the cached fp16 weight copies the adaptor descriptors point at (a no-op while the weights have not moved)."""
     from . import injector as inj
-    for _, mlp, _, _ in adaptor_streams(lc):
+    for _, mlp, _, _ in engine.adaptor_streams(lc):
         inj._f16_weight(mlp[2])
 
 
@@ -223,29 +219,3 @@ def patch_io(a, ff, fe, guides, nl, out, stream):
     a.newline = nl.data_ptr() if nl is not None else None
     a.out = out.data_ptr()
     a.stream = stream
-
-
-def cached_plan(proj, store, key, build):
-    """The plan of `key` in the module's store `store` ("_batch_plans" / "_ragged_plans"), built by build() when there is none or the
-    module's parameters were replaced; weights changed in place are followed by the plan's refresh().  Counts the use."""
-    plans = proj.__dict__.setdefault(store, {})
-    plan = plans.get(key)
-    sig = engine.plan_sig(proj)
-    if plan is not None and plan.sig == sig:
-        fresh = engine.content_sig(proj)
-        if plan.fresh != fresh:              # the weights changed in place: rebuild the weight-derived tables into their buffers
-            plan.refresh()
-            sig = engine.plan_sig(proj)
-            plan.fresh = fresh
-    if plan is not None and plan.sig != sig:
-        plans.pop(key)
-        plan = None
-    if plan is None:
-        plan = build()
-        plan.sig = engine.plan_sig(proj)     # (building may have (re)built the cached positional tables)
-        plan.fresh = engine.content_sig(proj)
-        if len(plans) >= MAX_PLANS:
-            plans.pop(next(iter(plans)))
-        plans[key] = plan
-    plan.hits += 1
-    return plan

@@ -362,6 +362,39 @@ def test_inplace_weight_update_refreshes_derived_tables_under_the_same_plan():
             assert torch.equal(got, want), (step, float((got.float() - want.float()).abs().max()))
 
 
+@pytest.mark.parametrize("name,names", [
+    ("G5_adaptkv", ("local_compressor.k_proj.2.weight", "local_compressor.v_proj.2.weight", "local_compressor.readout.0.weight")),
+    ("G6_coarse", ("local_compressor.guide_injector.coarse_proj.0.weight", "global_compressor.guide_injector.coarse_proj.2.weight",
+                   "global_compressor.attn_layer.k_proj.weight"))])
+def test_inplace_weight_update_under_the_same_plan_adaptor_and_injector_recipes(name, names):
+    """The recipes the test above does not reach.  G5_adaptkv: the fp16 copies of the k / v adaptors' second layers are entries of the
+    plan's refresh list beside the readout copies.  G6_coarse: the executor runs the guide injectors itself (their weights are read per
+    call, nothing derived) beside a refreshed kpe, and the caller's guide is aliased by the two nested injector blocks.  After an in-place
+    update the plan is the same object and the output is that of a freshly built module holding the updated weights; a second call with
+    another guide TENSOR (new address, other values) equals the fresh module on that guide -- the per-call guide patch.
+    Comparison: torch.equal, which the commit in front of the one-protocol refactor satisfies as well (both recipes, both calls)."""
+    m, _, case = _module_and_sd(name)
+    ff, fe, g = dev_bf16(case.ff), dev_bf16(case.fe), dev_bf16(case.g)
+    g2 = (g.float() * -0.5).to(g.dtype)
+    assert g2.data_ptr() != g.data_ptr()
+    params = dict(m.named_parameters())
+    with torch.no_grad():
+        before = m(ff, fe, g, case.modal, None).clone()
+        plan = next(iter(m.__dict__["_engine_plans"].values()))
+        for n in names:
+            params[n].copy_((params[n].float() * 1.25).to(torch.bfloat16))
+        got = m(ff, fe, g, case.modal, None).clone()
+        got2 = m(ff, fe, g2, case.modal, None).clone()
+        assert list(m.__dict__["_engine_plans"].values()) == [plan] and plan.hits == 3
+        fresh = build_module(cases.build_case(name))
+        fresh.load_state_dict({k: v.detach().clone() for k, v in m.state_dict().items()})
+        want, want2 = fresh(ff, fe, g, case.modal, None).clone(), fresh(ff, fe, g2, case.modal, None).clone()
+    for tag, a, b in (("updated", got, want), ("other guide", got2, want2)):
+        print(f"{name} {tag}: max-abs {float((a.float() - b.float()).abs().max()):.3e} equal {torch.equal(a, b)}")
+    assert not torch.equal(got, before) and not torch.equal(got2, got)
+    assert torch.equal(got, want) and torch.equal(got2, want2)
+
+
 def test_guide_off_reuses_folded_learnable_queries_until_the_weights_change():
     """Guide off: the injected queries are the learnable `query` parameter (IdentityMap, reference projector.py:586-587), so q_proj +
     fold are weight-only work; the executor keeps them in the plan's workspace (hicom_compressor_args.reuse_queries) and redoes them

@@ -314,3 +314,62 @@ def test_cached_plan_protocol(monkeypatch):
     assert list(proj._batch_plans) == [f"k{i}" for i in range(1, 17)]
     other = segments.cached_plan(proj, "_ragged_plans", "k0", build)                           # the stores are separate
     assert list(proj._ragged_plans) == ["k0"] and other.hits == 1 and len(proj._batch_plans) == 16
+
+
+def test_cached_plan_eviction_releases_and_a_failed_build_stores_nothing(monkeypatch):
+    """engine.cached_plan on the executor's store: the seventeenth key evicts the oldest plan and calls its release() exactly once, a plan
+    without release() goes silently, and a build() that raises leaves no plan behind and the other plans alone."""
+    monkeypatch.setattr(engine, "plan_sig", lambda proj: "sig")
+    monkeypatch.setattr(engine, "content_sig", lambda proj: "content")
+    proj = SimpleNamespace()
+    released = []
+
+    class Fake:
+        def __init__(self, tag):
+            self.tag, self.hits, self.sig, self.fresh, self.refresh = tag, 0, None, None, None
+
+    class Releasing(Fake):
+        def release(self):
+            released.append(self.tag)
+
+    def get(key, cls=Releasing):
+        return engine.cached_plan(proj, "_engine_plans", key, lambda: cls(key))
+    assert engine.cached_plan is segments.cached_plan and engine.MAX_PLANS == segments.MAX_PLANS == 16
+    first = get("k0")
+    get("k1", Fake)
+    for i in range(2, 16):
+        get(f"k{i}")
+    assert get("k0") is first and first.hits == 2 and not released and len(proj._engine_plans) == 16
+
+    def failing():
+        raise NotImplementedError("refused in front of the workspace")
+    before = dict(proj._engine_plans)
+    with pytest.raises(NotImplementedError):
+        engine.cached_plan(proj, "_engine_plans", "bad", failing)
+    assert proj._engine_plans == before and list(proj._engine_plans) == list(before) and not released      # nothing stored, nothing evicted
+    get("k16")
+    assert released == ["k0"] and list(proj._engine_plans) == [f"k{i}" for i in range(1, 17)]
+    get("k17")                                                                                 # k1 has no release(): evicted silently
+    assert released == ["k0"] and list(proj._engine_plans) == [f"k{i}" for i in range(2, 18)]
+    get("k18")
+    assert released == ["k0", "k2"]
+    # a stale plan whose rebuild is refused is gone, the others stay
+    monkeypatch.setattr(engine, "plan_sig", lambda proj: "sig2")
+    with pytest.raises(NotImplementedError):
+        engine.cached_plan(proj, "_engine_plans", "k5", failing)
+    assert list(proj._engine_plans) == [f"k{i}" for i in range(3, 19) if i != 5] and released == ["k0", "k2"]
+
+
+def test_patch_guide_reaches_the_nested_injector_blocks():
+    """engine.patch_guide on a bare argument block: slots on a top-level field and on `guide` of the nested inj_l / inj_g views, taken once
+    as build_args takes them -- ctypes views of a nested structure alias the parent's memory, so the block reads every address back."""
+    a = nv.CompressorArgs()
+    slots = [(a, "lq"), (a.inj_l, "guide"), (a, "gq"), (a.inj_g, "guide")]
+
+    def read():
+        return a.lq, a.inj_l.guide, a.gq, a.inj_g.guide
+    assert read() == (None,) * 4
+    for addr in (ADDR, ADDR + 0x2000):
+        engine.patch_guide(slots, addr)
+        assert read() == (addr,) * 4
+    assert (a.inj_l.visual, a.inj_g.visual, a.ff, a.fe) == (None,) * 4                       # ... and nothing beside them moved
