@@ -15,6 +15,10 @@
 // Launches 1-2 and 6-11, the workspace regions and the common checks are segment_host.hpp's, with M = Q; this file holds the local kernel,
 // the four launches that know a guide, the chunk policy and the step's own limits.  The packed-row layout integers are those of the batched
 // step and hold for every guide.
+//
+// Prepared clips: for the k / v adaptor recipe hicom_clip_adapt_prepare_fwd runs the adaptor MLPs over a clip's tokens
+// once, into planes the caller keeps; hicom_compressor_multiguide_adapt_fwd is the sequence above with launch 3 replaced by
+// multi_guide_local_adapt_kernel, which blends LayerNorm of those planes into the rows it loads.  Same launch count, same workspace.
 #include "multi_window.hpp"
 #include "segment_host.hpp"
 
@@ -31,6 +35,23 @@ __global__ __launch_bounds__(256) void multi_guide_local_kernel(const uint16_t* 
     if (win >= nwin) return;
     const WindowGeom g(at, ay, ax, win);
     multi_window_guides_ctx16<NV>(key, value, guide, 0, Q, g, lane, scale, ctx16 + (long)win * D, (long)nwin * D);
+}
+
+// The same grid and wave -> window map for the k / v adaptor recipe on a clip's PREPARED planes (multi_window.hpp:
+// multi_window_guides_adapt_ctx16; ad.ky / ad.vy: y = MLP(x) fp16 [tokens][D], indexed like the tokens).  Nothing here writes the planes.
+// kAdaptGuideGroup = 4 guides per walk under the 256-thread launch bound alone: 233 VGPRs, no scratch, two waves per SIMD (DESIGN.md §3.10
+// has the table: a group of 2 held to the 128 registers of four waves per SIMD spills 22 registers to scratch, and every no-scratch
+// form of a smaller group was slower at Q = 4, the time being the number of walks).
+template <int NV>
+__global__ __launch_bounds__(256) void multi_guide_local_adapt_kernel(const uint16_t* key, const uint16_t* value, const uint16_t* guide, SegAdaptParams ad,
+                                                                      hicom_axis at, hicom_axis ay, hicom_axis ax, int Q, int nwin, float scale,
+                                                                      _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const WindowGeom g(at, ay, ax, win);
+    multi_window_guides_adapt_ctx16<NV, kAdaptGuideGroup>(key, value, ad, guide, 0, Q, g, lane, scale, ctx16 + (long)win * D, (long)nwin * D);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -113,6 +134,7 @@ struct GuideItems {
     const Args* a;
     const MgLayout& l;
     bool marg;              // in-kernel positional marginals (clips), the logit tensor otherwise
+    const SegAdaptParams* prepared;     // the adaptor recipe on a clip's prepared planes (hicom_compressor_multiguide_adapt_fwd), NULL: plain
     char* ws() const { return (char*)a->ws; }
     float* f32(long off) const { return (float*)(ws() + off); }
     float* pos_a() const { return a->pe ? f32(l.s.pos_a) : nullptr; }
@@ -120,8 +142,12 @@ struct GuideItems {
     int local(const uint16_t* key_x, const SegAdaptParams*) const {
         const hicom_axis at{a->T, a->kt, a->T / a->kt, a->T / a->kt};
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
-        HICOM_LAUNCH(multi_guide_local_kernel<3>, dim3((unsigned)((l.wpi + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x, (const uint16_t*)a->ff,
-                     (const uint16_t*)a->guide, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
+        if (prepared)
+            HICOM_LAUNCH(multi_guide_local_adapt_kernel<3>, dim3((unsigned)((l.wpi + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x,
+                         (const uint16_t*)a->ff, (const uint16_t*)a->guide, *prepared, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
+        else
+            HICOM_LAUNCH(multi_guide_local_kernel<3>, dim3((unsigned)((l.wpi + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x, (const uint16_t*)a->ff,
+                         (const uint16_t*)a->guide, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
         return seg_check_launch(kWho, "local stage");
     }
 
@@ -147,7 +173,9 @@ struct GuideItems {
     int place(const SegPlaceParams& c) const { return seg_place_equal(kWho, multi_guide_place_kernel, a, c, l.wpi); }
 };
 
-int mg_fwd(const Args* a) {
+// prepared: the local stage's adaptor parameters with the caller's planes, NULL for the plain recipe.  seg_step runs as for the plain recipe
+// (no adaptor MLP, no adaptor region in the workspace): only the local hook differs.
+int mg_fwd(const Args* a, const SegAdaptParams* prepared = nullptr) {
     int st = mg_check(a);
     if (st != HICOM_OK) return st;
     const MgLayout l = mg_layout(a);
@@ -156,7 +184,37 @@ int mg_fwd(const Args* a) {
     st = seg_check_equal_rows(kWho, a, l.wpi);
     if (st != HICOM_OK) return st;
     const bool marg = a->pe && hicom_global_stream_has_marg(l.N, a->E, l.rows_pad, a->H, a->W, l.nparts) == 1;
-    return seg_step(a, nullptr, l.s, GuideItems{a, l, marg});
+    return seg_step(a, nullptr, l.s, GuideItems{a, l, marg, prepared});
+}
+
+// ---- the k / v adaptor recipe on prepared planes ------------------------------------------------------------------------------------------
+typedef hicom_compressor_multiguide_adapt_args AdaptArgs;
+
+// what the adaptor block adds to the plain checks; a stream is adapted when its plane is given
+int mga_check(const AdaptArgs* a) {
+    HICOM_REQUIRE(a->ky || a->vy, HICOM_EINVAL, "%s: neither stream has a prepared plane (the plain entry point runs that recipe)", kWho);
+    HICOM_REQUIRE((uintptr_t)a->ky % 16 == 0 && (uintptr_t)a->vy % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned planes", kWho);
+    HICOM_REQUIRE(a->alpha_dt == HICOM_DT_BF16 || a->alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", kWho, a->alpha_dt);
+    HICOM_REQUIRE((!a->ky || (a->ak.gamma && a->ak.beta && a->ak.alpha)) && (!a->vy || (a->av.gamma && a->av.beta && a->av.alpha)), HICOM_EINVAL,
+                  "%s: adaptor weights", kWho);
+    return HICOM_OK;
+}
+
+// ---- y = MLP(x) planes of a clip (hicom_clip_adapt_prepare_*) ---------------------------------------------------------------------------------
+constexpr const char* kWhoPrepare = "clip_adapt_prepare";
+
+// The workspace holds the fp16 [N, E] hidden plane of layer 1 per adapted stream (k first), each rounded up to 256 bytes: the y planes
+// are the caller's.  hid_v: where the value stream's begins.
+int prepare_check(int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, SegAdapt* ad, long* hid_v, long* total) {
+    HICOM_REQUIRE(ak && av, HICOM_EINVAL, "%s: NULL arguments", kWhoPrepare);
+    HICOM_REQUIRE(N > 0 && E > 0, HICOM_EINVAL, "%s: bad shape", kWhoPrepare);
+    *ad = SegAdapt{ak, av, HICOM_DT_BF16, 0.f};            // (the MLPs read neither alpha nor eps)
+    const int st = seg_adapt_check(kWhoPrepare, ad, N, E);
+    if (st != HICOM_OK) return st;
+    const long plane = ((long)N * E * 2 + 255) / 256 * 256;
+    *hid_v = ad->k() ? plane : 0;
+    *total = *hid_v + (ad->v() ? plane : 0);
+    return HICOM_OK;
 }
 
 }  // namespace
@@ -168,3 +226,45 @@ extern "C" int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compr
 }
 
 extern "C" int hicom_compressor_multiguide_fwd(const hicom_compressor_multiguide_args* a) { return mg_fwd(a); }
+
+// The planes are the caller's: the workspace is the plain entry point's for the same arguments.
+extern "C" int64_t hicom_compressor_multiguide_adapt_workspace_bytes(const hicom_compressor_multiguide_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", kWho);
+    return hicom_compressor_multiguide_workspace_bytes(&a->base);
+}
+
+extern "C" int hicom_compressor_multiguide_adapt_fwd(const hicom_compressor_multiguide_adapt_args* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", kWho);
+    int st = mg_check(&a->base);
+    if (st != HICOM_OK) return st;
+    st = mga_check(a);
+    if (st != HICOM_OK) return st;
+    SegAdaptParams p;
+    p.ky = (const _Float16*)a->ky; p.kgamma = (const uint16_t*)a->ak.gamma; p.kbeta = (const uint16_t*)a->ak.beta; p.kalpha = a->ak.alpha;
+    p.vy = (const _Float16*)a->vy; p.vgamma = (const uint16_t*)a->av.gamma; p.vbeta = (const uint16_t*)a->av.beta; p.valpha = a->av.alpha;
+    p.alpha_f32 = a->alpha_dt == HICOM_DT_F32;
+    p.eps = a->eps;
+    return mg_fwd(&a->base, &p);
+}
+
+extern "C" int64_t hicom_clip_adapt_prepare_workspace_bytes(int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av) {
+    SegAdapt ad;
+    long hid_v = 0, total = 0;
+    const int st = prepare_check(N, E, ak, av, &ad, &hid_v, &total);
+    return st != HICOM_OK ? st : total;
+}
+
+extern "C" int hicom_clip_adapt_prepare_fwd(const void* key_x, const void* ff, int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av,
+                                            void* ky, void* vy, void* ws, int64_t ws_bytes, void* stream) {
+    SegAdapt ad;
+    long hid_v = 0, total = 0;
+    const int st = prepare_check(N, E, ak, av, &ad, &hid_v, &total);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(key_x && ff && (!ad.k() || ky) && (!ad.v() || vy), HICOM_EINVAL, "%s: NULL pointer", kWhoPrepare);
+    for (const hicom_seg_adaptor* s : {ak, av})
+        if (s->w0) HICOM_REQUIRE(s->w2_f16, HICOM_EINVAL, "%s: adaptor weights", kWhoPrepare);
+    HICOM_REQUIRE(ws && ws_bytes >= total && (uintptr_t)ws % 256 == 0, HICOM_EINVAL, "%s: workspace of %ld bytes, 256-byte aligned", kWhoPrepare, total);
+    HICOM_REQUIRE((uintptr_t)key_x % 16 == 0 && (uintptr_t)ff % 16 == 0 && (uintptr_t)ky % 16 == 0 && (uintptr_t)vy % 16 == 0, HICOM_EINVAL,
+                  "%s: 16-byte aligned tokens and planes", kWhoPrepare);
+    return seg_adapt_mlps(ad, key_x, ff, N, E, ws, (char*)ws + hid_v, ky, vy, stream);
+}

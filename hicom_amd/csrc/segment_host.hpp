@@ -67,25 +67,26 @@ inline int seg_adapt_check_weights(const char* who, const SegAdapt* ad) {
 
 // y = MLP(x) of the adapted streams over all `tokens` of the call: two launches.  Both adaptors with matching biases: each layer of the
 // two MLPs is one paired launch; otherwise (one adaptor: two launches as well) the single-problem entry point per layer.
-inline int seg_adapt_mlps(const SegAdapt& ad, const void* key_x, const void* ff, long tokens, int E, char* ws, const SegAdaptLayout& l, void* stream) {
+// hid_k / hid_v: the fp16 hidden planes of layer 1 (temporaries), ky / vy: the fp16 y planes; those of a stream without adaptor are not read.
+inline int seg_adapt_mlps(const SegAdapt& ad, const void* key_x, const void* ff, long tokens, int E, void* hid_k, void* hid_v, void* ky, void* vy, void* stream) {
     const hicom_seg_adaptor &k = *ad.ak, &v = *ad.av;
     const int M = (int)tokens;
     if (ad.k() && ad.v() && !k.b0 == !v.b0 && !k.b2 == !v.b2) {
-        const int st = hicom_dense16_gemm_pair_fwd(key_x, k.w0, k.b0, ws + l.hid_k, nullptr, ff, v.w0, v.b0, ws + l.hid_v, nullptr, E, E, HICOM_DT_BF16,
+        const int st = hicom_dense16_gemm_pair_fwd(key_x, k.w0, k.b0, hid_k, nullptr, ff, v.w0, v.b0, hid_v, nullptr, E, E, HICOM_DT_BF16,
                                                    HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, E, E, 0, stream);
         if (st != HICOM_OK) return st;
-        return hicom_dense16_gemm_pair_fwd(ws + l.hid_k, k.w2_f16, k.b2, ws + l.ky, nullptr, ws + l.hid_v, v.w2_f16, v.b2, ws + l.vy, nullptr, E, E,
+        return hicom_dense16_gemm_pair_fwd(hid_k, k.w2_f16, k.b2, ky, nullptr, hid_v, v.w2_f16, v.b2, vy, nullptr, E, E,
                                            HICOM_DT_F16, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, E, E, 0, stream);
     }
-    auto mlp = [&](const hicom_seg_adaptor& a, const void* x, long hid, long y) -> int {
-        const int st = hicom_dense16_gemm_fwd(x, E, a.w0, E, HICOM_DT_BF16, a.b0, HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, ws + hid, E, E, nullptr, 0, nullptr,
+    auto mlp = [&](const hicom_seg_adaptor& a, const void* x, void* hid, void* y) -> int {
+        const int st = hicom_dense16_gemm_fwd(x, E, a.w0, E, HICOM_DT_BF16, a.b0, HICOM_DT_BF16, M, E, E, HICOM_ACT_GELU, hid, E, E, nullptr, 0, nullptr,
                                               0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
         if (st != HICOM_OK) return st;
-        return hicom_dense16_gemm_fwd(ws + hid, E, a.w2_f16, E, HICOM_DT_F16, a.b2, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, ws + y, E, E, nullptr, 0, nullptr,
+        return hicom_dense16_gemm_fwd(hid, E, a.w2_f16, E, HICOM_DT_F16, a.b2, HICOM_DT_BF16, M, E, E, HICOM_ACT_NONE, y, E, E, nullptr, 0, nullptr,
                                       0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, nullptr, stream);
     };
-    if (ad.k()) { const int st = mlp(k, key_x, l.hid_k, l.ky); if (st != HICOM_OK) return st; }
-    if (ad.v()) { const int st = mlp(v, ff, l.hid_v, l.vy); if (st != HICOM_OK) return st; }
+    if (ad.k()) { const int st = mlp(k, key_x, hid_k, ky); if (st != HICOM_OK) return st; }
+    if (ad.v()) { const int st = mlp(v, ff, hid_v, vy); if (st != HICOM_OK) return st; }
     return HICOM_OK;
 }
 
@@ -329,7 +330,7 @@ inline int seg_step(const A* a, const SegAdapt* ad, const SegLayout& l, const It
     {
         const uint16_t* key_x = (const uint16_t*)(a->fe ? a->fe : a->ff);
         if (ad) {
-            st = seg_adapt_mlps(*ad, key_x, a->ff, l.n.tokens, E, ws, l.ad, a->stream);
+            st = seg_adapt_mlps(*ad, key_x, a->ff, l.n.tokens, E, ws + l.ad.hid_k, ws + l.ad.hid_v, ws + l.ad.ky, ws + l.ad.vy, a->stream);
             if (st != HICOM_OK) return st;
             const hicom::SegAdaptParams p = seg_adapt_params(*ad, ws, l.ad);
             st = item.local(key_x, &p);

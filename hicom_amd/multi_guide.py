@@ -16,26 +16,33 @@ MAX_GUIDES = 32         # 9 heads x 32 guides = 288 folded rows, the row count t
 STORE = "_multi_guide_plans"
 
 
+def count_guides(what, guides, E):
+    """Q of guide_embeds [Q, E]; raises unless 1 <= Q <= MAX_GUIDES."""
+    if not isinstance(guides, torch.Tensor) or guides.ndim != 2 or guides.shape[1] != E:
+        raise ValueError(f"{what}: guide_embeds is [Q, E] = [Q, {E}], one instruction per row "
+                         f"(got {tuple(guides.shape) if isinstance(guides, torch.Tensor) else None})")
+    if not 1 <= guides.shape[0] <= MAX_GUIDES:
+        raise ValueError(f"{what}: Q={guides.shape[0]} guides (1 <= Q <= {MAX_GUIDES} per call)")
+    return guides.shape[0]
+
+
+def clip_scope(what, step, proj, ff, fe, guides, modal, nl):
+    """The checks of a step on ONE clip with Q guides (this one and forward_prepared, prepared.py) behind the caller's rule on the recipe;
+    returns (Q, T, H, W, E, tilings)."""
+    Q, E = seg.check_inputs(what, step, proj, ff, fe, guides, nl, 4, "[T, H, W, E]", lambda: count_guides(what, guides, ff.shape[-1]))
+    T, H, W, _ = ff.shape
+    if modal == "image" and T != 1:
+        raise ValueError(f"{what}: image modality expects a single frame [1, H, W, E]")
+    return Q, T, H, W, E, seg.exact_tilings(what, proj, T, H, W, modal)
+
+
 def _scope(proj, ff, fe, guides, modal, nl):
     """Raises for everything outside the step's scope; returns (Q, T, H, W, E, tilings)."""
     what = "forward_multi_guide"
     if not isinstance(ff, dict) and not isinstance(fe, dict) and seg.seg_recipe(proj) != "plain":
         raise NotImplementedError(f"{what} is built for the plain release recipe only (local + global compressor, use_guide='direct', no "
                                   "adaptors, no clip scale); the adaptor recipe and everything else go through forward() per guide")
-
-    def count_guides():
-        E = ff.shape[-1]
-        if not isinstance(guides, torch.Tensor) or guides.ndim != 2 or guides.shape[1] != E:
-            raise ValueError(f"{what}: guide_embeds is [Q, E] = [Q, {E}], one instruction per row "
-                             f"(got {tuple(guides.shape) if isinstance(guides, torch.Tensor) else None})")
-        if not 1 <= guides.shape[0] <= MAX_GUIDES:
-            raise ValueError(f"{what}: Q={guides.shape[0]} guides (1 <= Q <= {MAX_GUIDES} per call)")
-        return guides.shape[0]
-    Q, E = seg.check_inputs(what, "multi-guide", proj, ff, fe, guides, nl, 4, "[T, H, W, E]", count_guides)
-    T, H, W, _ = ff.shape
-    if modal == "image" and T != 1:
-        raise ValueError(f"{what}: image modality expects a single frame [1, H, W, E]")
-    return Q, T, H, W, E, seg.exact_tilings(what, proj, T, H, W, modal)
+    return clip_scope(what, "multi-guide", proj, ff, fe, guides, modal, nl)
 
 
 def run_multi_guide(proj, ff, fe, guides, modal, nl, chunks=None):

@@ -46,6 +46,8 @@ EXPORTS = (
     "hicom_compressor_ragged_adapt_fwd", "hicom_compressor_ragged_adapt_workspace_bytes", "hicom_compressor_ragged_adapt_prepare",
     "hicom_compressor_multiguide_fwd", "hicom_compressor_multiguide_workspace_bytes",
     "hicom_compressor_ragged_multiguide_fwd", "hicom_compressor_ragged_multiguide_workspace_bytes", "hicom_compressor_ragged_multiguide_prepare",
+    "hicom_clip_adapt_prepare_fwd", "hicom_clip_adapt_prepare_workspace_bytes",
+    "hicom_compressor_multiguide_adapt_fwd", "hicom_compressor_multiguide_adapt_workspace_bytes",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -214,6 +216,13 @@ class CompressorMultiGuideArgs(C.Structure):
     _fields_ = [(("Q" if name == "B" else name), ctype) for name, ctype in CompressorBatchArgs._fields_]
 
 
+class CompressorMultiGuideAdaptArgs(C.Structure):
+    """hicom_compressor_multiguide_adapt_args (include/hicom_hip.h): the plain block first, then the two adaptors (gamma / beta / alpha are
+    read), the prepared y planes of a clip (NULL: that stream is not adapted), the alpha dtype and the LayerNorm eps."""
+    _fields_ = [("base", CompressorMultiGuideArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("ky", C.c_void_p), ("vy", C.c_void_p),
+                ("alpha_dt", C.c_int32), ("eps", C.c_float)]
+
+
 class CompressorRaggedMultiGuideArgs(C.Structure):
     """hicom_compressor_ragged_multiguide_args (include/hicom_hip.h): the fields of hicom_compressor_ragged_args with the HOST array of the
     items' guide counts and its length behind `items` -- field order and types must match the header."""
@@ -335,6 +344,10 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
     L.hicom_compressor_multiguide_fwd.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
     L.hicom_compressor_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
+    L.hicom_compressor_multiguide_adapt_fwd.argtypes = [C.POINTER(CompressorMultiGuideAdaptArgs)]
+    L.hicom_compressor_multiguide_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorMultiGuideAdaptArgs)]
+    L.hicom_clip_adapt_prepare_workspace_bytes.argtypes = [i64, i32, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor)]
+    L.hicom_clip_adapt_prepare_fwd.argtypes = [vp, vp, i64, i32, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), vp, vp, vp, i64, vp]
     L.hicom_compressor_ragged_multiguide_fwd.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
     L.hicom_compressor_ragged_multiguide_prepare.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
     L.hicom_compressor_ragged_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
@@ -351,6 +364,8 @@ def lib() -> C.CDLL:
     L.hicom_compressor_batch_adapt_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_adapt_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_multiguide_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_multiguide_adapt_workspace_bytes.restype = C.c_int64
+    L.hicom_clip_adapt_prepare_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_multiguide_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
@@ -678,7 +693,7 @@ def compressor_fwd(args: CompressorArgs):
 
 def _adapt(args) -> bool:
     """True for the argument blocks of the adaptor recipe (the plain block is their first member)."""
-    return isinstance(args, (CompressorBatchAdaptArgs, CompressorRaggedAdaptArgs))
+    return isinstance(args, (CompressorBatchAdaptArgs, CompressorRaggedAdaptArgs, CompressorMultiGuideAdaptArgs))
 
 
 def _seg_call(args, step, fn, py_name=None):
@@ -717,12 +732,28 @@ def compressor_ragged_fwd(args):
     _seg_call(args, "ragged", "fwd")
 
 
-def compressor_multiguide_workspace(args: CompressorMultiGuideArgs) -> int:
-    return _seg_call(args, "multiguide", "workspace_bytes", "forward_multi_guide")
+def compressor_multiguide_workspace(args) -> int:
+    """args: CompressorMultiGuideArgs or CompressorMultiGuideAdaptArgs (as for compressor_multiguide_fwd)."""
+    return _seg_call(args, "multiguide", "workspace_bytes", "forward_prepared" if _adapt(args) else "forward_multi_guide")
 
 
-def compressor_multiguide_fwd(args: CompressorMultiGuideArgs):
+def compressor_multiguide_fwd(args):
     _seg_call(args, "multiguide", "fwd")
+
+
+def clip_adapt_prepare_workspace(N: int, E: int, ak: SegAdaptor, av: SegAdaptor) -> int:
+    n = lib().hicom_clip_adapt_prepare_workspace_bytes(N, E, C.byref(ak), C.byref(av))
+    if n < 0:
+        msg = lib().hicom_last_error().decode(errors="replace")
+        if n == -2:
+            raise NotImplementedError(f"prepare_clip: {msg}")
+        raise HicomNativeError(f"hicom_clip_adapt_prepare_workspace_bytes failed ({n}): {msg}")
+    return int(n)
+
+
+def clip_adapt_prepare_fwd(key_x: int, ff: int, N: int, E: int, ak: SegAdaptor, av: SegAdaptor, ky, vy, ws: int, ws_bytes: int, stream: int):
+    """Addresses in, launches out: y = MLP(x) of the adapted streams into the caller's fp16 planes ky / vy (None: not adapted)."""
+    _check(lib().hicom_clip_adapt_prepare_fwd(key_x, ff, N, E, C.byref(ak), C.byref(av), ky, vy, ws, ws_bytes, stream), "hicom_clip_adapt_prepare_fwd")
 
 
 def compressor_ragged_multiguide_workspace(args: CompressorRaggedMultiGuideArgs) -> int:

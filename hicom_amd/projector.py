@@ -822,6 +822,8 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_ragged_plans", None)
         self.__dict__.pop("_multi_guide_plans", None)
         self.__dict__.pop("_ragged_multi_guide_plans", None)
+        self.__dict__.pop("_prepared_plans", None)
+        self.__dict__.pop("_prepare_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1107,6 +1109,35 @@ class HIComProjector(nn.Module):
         thirteen-launch sequence); from four guides up this call wins, 1.2 x at Q = 6 and 1.75 x at Q = 16 on 64 frames."""
         from . import multi_guide
         return multi_guide.run_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
+
+    def prepare_clip(self, frames_feature, frames_embed, modal):
+        """Once per video: the guide-independent work of the k / v adaptor recipe.  frames_feature / frames_embed bf16 [T, H, W, E] as for
+        forward() (frames_embed may be None), modal "image" / "video".  Runs both layers of each adaptor MLP over the clip's tokens (the
+        dense GEMMs of forward_batch's adaptor recipe) and returns a PreparedClip (hicom_amd/prepared.py) that owns the fp16 planes
+        y_k / y_v [T H W, E] -- 2304 bytes per token and adapted stream; the module's shape-keyed prepare plan holds as much again for the
+        hidden planes of layer 1, shared by all clips of one shape -- and serves any number of forward_prepared calls.
+        The clip keeps REFERENCES to frames_feature / frames_embed (contiguous ones: no copy): every later call reads them in place, so
+        the caller must not overwrite them while the clip is in use.
+        A plain-recipe module (`local43_global32`) gets a clip without planes, so one code path in a caller serves both released recipes.
+        Scope as forward_prepared; everything else raises NotImplementedError / ValueError in front of the first launch."""
+        from . import prepared
+        return prepared.prepare_clip(self, frames_feature, frames_embed, modal)
+
+    def forward_prepared(self, clip, guide_embeds, image_newline=None, *, chunks=None):
+        """Q instructions about a prepared clip in one native call: guide_embeds bf16 [Q, E], 1 <= Q <= 32.  Returns [Q, rows, hidden];
+        out[q] is laid out as forward(frames_feature, frames_embed, guide_embeds[q], modal, image_newline) on the clip's tokens and equals
+        it to the kernels' rounding.  The call is the multi-guide step (forward_multi_guide, DESIGN.md §3.8: 13 launches on a clip, 14 on
+        an image) with the adaptor blends fused into its local kernel (§3.10): it runs no adaptor MLP, never writes the clip's planes,
+        allocates nothing token-sized and does not synchronise the host.
+        RuntimeError ("stale") when the adaptor MLP weights moved since prepare_clip -- clip.refresh() recomputes the planes in place;
+        every other weight (readout, global stage, the adaptors' LayerNorm and alpha) is read at call time and followed as by every plan.
+        A call on another stream than the clip's waits for the clip's event on the device.
+        The two release recipes (adapt_k and / or adapt_v on the local stage; a plain-recipe module's clip goes to forward_multi_guide
+        unchanged), bf16 module and inputs, E = 1152, hidden % 64 == 0, exact window partition with square windows of <= 64 tokens, no
+        anyres dicts, inference only: everything else raises NotImplementedError / ValueError in front of the first launch.
+        Which path when: DESIGN.md §3.10 has the measured table against the loop of forward()."""
+        from . import prepared
+        return prepared.run_prepared(self, clip, guide_embeds, image_newline, chunks)
 
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):

@@ -7,7 +7,8 @@ arithmetic.
 Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plans`, `proj._multi_guide_plans`: at most MAX_PLANS each)
 through engine.cached_plan, the ONE plan-cache protocol of the package: engine.run_dense's plans go through the same function.  The input /
 output pointers are patched per call.  forward_ragged_multi_guide (ragged_multi_guide.py: the product of the last two,
-`proj._ragged_multi_guide_plans`) is built on the same functions."""
+`proj._ragged_multi_guide_plans`) is built on the same functions, and so are prepare_clip / forward_prepared (prepared.py:
+`proj._prepare_plans`, `proj._prepared_plans`)."""
 from __future__ import annotations
 
 import math
@@ -68,10 +69,8 @@ def refresh_adaptors(lc):
         inj._f16_weight(mlp[2])
 
 
-def check_inputs(what, step, proj, ff, fe, guides, nl, ndim, ff_layout, count_items):
-    """The input checks of `what` ("forward_batch" / "forward_ragged", the `step` "batched" / "ragged"): raises for a module or tensors
-    outside the step's scope.  frames_feature has `ndim` axes (`ff_layout` says which); count_items() is called once frames_feature and
-    frames_embed have passed, checks what describes the items and returns B.  Returns (B, E)."""
+def check_tokens(what, step, proj, ff, fe, ndim, ff_layout):
+    """The part of check_inputs that knows no guide: the module's scope and dtype, frames_feature and frames_embed.  Returns E."""
     from .projector import _require_bf16_cuda
     if isinstance(ff, dict) or isinstance(fe, dict):
         raise NotImplementedError(f"{what}: anyres dict inputs have no {step} path (call forward() per image)")
@@ -89,6 +88,15 @@ def check_inputs(what, step, proj, ff, fe, guides, nl, ndim, ff_layout, count_it
         _require_bf16_cuda("frames_embed", fe)
         if tuple(fe.shape) != tuple(ff.shape):
             raise ValueError(f"{what}: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
+    return E
+
+
+def check_inputs(what, step, proj, ff, fe, guides, nl, ndim, ff_layout, count_items):
+    """The input checks of `what` ("forward_batch" / "forward_ragged", the `step` "batched" / "ragged"): raises for a module or tensors
+    outside the step's scope.  frames_feature has `ndim` axes (`ff_layout` says which); count_items() is called once frames_feature and
+    frames_embed have passed, checks what describes the items and returns B.  Returns (B, E)."""
+    from .projector import _require_bf16_cuda
+    E = check_tokens(what, step, proj, ff, fe, ndim, ff_layout)
     B = count_items()
     if not isinstance(guides, torch.Tensor) or tuple(guides.shape) != (B, E):
         raise ValueError(f"{what}: guide_embeds is [B, E] = [{B}, {E}], one instruction per item "

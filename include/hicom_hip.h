@@ -1021,6 +1021,39 @@ typedef struct hicom_compressor_multiguide_args {
 int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compressor_multiguide_args* args);
 int hicom_compressor_multiguide_fwd(const hicom_compressor_multiguide_args* args);
 
+/* ---- prepared clips: the k / v adaptor recipe with the adaptor MLPs run ONCE per clip, Q guides per call ----------
+ * key = (1 - a_k) x + a_k LN(MLP_k(x)) depends on the tokens only; the guide enters as the query.  hicom_clip_adapt_prepare_fwd runs
+ * both layers of each adaptor MLP over the clip's N tokens -- the launches of the adaptor steps above: one hicom_dense16_gemm_pair_fwd per
+ * layer with both adaptors, hicom_dense16_gemm_fwd per layer with one -- and leaves y = MLP(x) as fp16 [N, E] planes the CALLER owns.
+ *   key_x, ff : bf16 [N, E]: what the k adaptor resp. the v adaptor reads (key_x = fe, or ff without frames_embed)
+ *   ak, av    : w0 == NULL: that stream is not adapted (at least one is); gamma / beta / alpha are not read here
+ *   ky, vy    : fp16 [N, E] out, 16-byte aligned (not read for a stream without adaptor)
+ *   ws        : hicom_clip_adapt_prepare_workspace_bytes(N, E, ak, av) bytes, 256-byte aligned: the fp16 hidden plane of layer 1 per
+ *               adapted stream, a temporary
+ * E % 64 == 0 and N E < 2^32 (the dense GEMM's operand limit), HICOM_EUNSUP otherwise.  Only launches.
+ *
+ * hicom_compressor_multiguide_adapt_fwd is hicom_compressor_multiguide_fwd with the local stage reading those planes: the same launch
+ * sequence (no adaptor MLP runs), the same workspace (hicom_compressor_multiguide_adapt_workspace_bytes equals the plain function on
+ * `base`), the planes are read only.
+ *   base      : the plain block; ff / fe are the tokens the planes were made from
+ *   ak, av    : gamma / beta / alpha of the adapted streams are read (w0 .. b2 are not)
+ *   ky, vy    : the prepared planes; NULL: that stream is not adapted and is read as in the plain step.  Not both NULL (HICOM_EINVAL)
+ *   alpha_dt  : dtype of the two alpha scalars (HICOM_DT_BF16 | HICOM_DT_F32); eps: the LayerNorms' epsilon
+ * Guide q of the output equals hicom_compressor_batch_adapt_fwd on the clip with guide row q alone: bit for bit on the local rows. */
+int64_t hicom_clip_adapt_prepare_workspace_bytes(int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av);
+int hicom_clip_adapt_prepare_fwd(const void* key_x, const void* ff, int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av,
+                                 void* ky, void* vy, void* ws, int64_t ws_bytes, void* stream);
+typedef struct hicom_compressor_multiguide_adapt_args {
+    hicom_compressor_multiguide_args base;
+    hicom_seg_adaptor ak, av;
+    const void* ky;
+    const void* vy;
+    int32_t alpha_dt;
+    float eps;
+} hicom_compressor_multiguide_adapt_args;
+int64_t hicom_compressor_multiguide_adapt_workspace_bytes(const hicom_compressor_multiguide_adapt_args* args);
+int hicom_compressor_multiguide_adapt_fwd(const hicom_compressor_multiguide_adapt_args* args);
+
 /* ---- ragged multi-guide compressor step: B items of unequal length, item i with its own Q_i instructions -----------
  * The product of the ragged and the multi-guide step: a Video-MME evaluation batch (several videos x 3 questions), or a batch of
  * multi-question items through hicom/model/hicom_arch.py:146-180.  A PAIR is one (item, guide); pairs are numbered item-major, then
