@@ -75,23 +75,91 @@ def token_axes(N, H, W):
     return n // (H * W), (n // W) % H, n % W
 
 
+def stream_terms(q, x, pos, pe=None, H=1, W=1, t0i=0, y0i=0, x0i=0, axes=(True, True, True), t_of=None):
+    """The score tile of the stream kernels and the rows their values stand for:
+        dot[r, n] = q_r . x_n + pos[r, t0i + t] + pos[r, y0i + y] + pos[r, x0i + x],   val_n = x_n + pe[t0i + t] + pe[y0i + y] + pe[x0i + x]
+    (pos [rows, P] or None; pe [P, E] or None: val = x).  Returns (dot, abs terms of dot, val, |x| + |pe rows|).
+    axes / t_of (the frame the score side takes each token for) are the defects tests/test_global_stream_power.py plants: a dropped
+    positional term, a wrong frame index.  The value side always uses the token's own frame."""
+    N = x.shape[0]
+    dot, ab = q @ x.t(), q.abs() @ x.abs().t()
+    val, vabs = x, x.abs()
+    if pos is not None or pe is not None:
+        t, y, xx = token_axes(N, H, W)
+        if pos is not None:
+            for on, c in zip(axes, (t0i + (t if t_of is None else t_of), y0i + y, x0i + xx)):
+                if on:
+                    dot, ab = dot + pos[:, c], ab + pos[:, c].abs()
+        if pe is not None:
+            val = x + pe[t0i + t] + pe[y0i + y] + pe[x0i + xx]
+            vabs = x.abs() + pe[t0i + t].abs() + pe[y0i + y].abs() + pe[x0i + xx].abs()
+    return dot, ab, val, vabs
+
+
 def clip_attention_ref(q, x, inv, row_const, pos_a=None, pe=None, H=1, W=1, t0i=0, y0i=0, x0i=0):
     """logit[r, n] = (q_r . x_n + pos_a[r, t0i + t] + pos_a[r, y0i + y] + pos_a[r, x0i + x] + row_const[r]) * inv[n];
     ctx_r = sum_n softmax_n(logit[r, :]) (x_n + pe[t0i + t] + pe[y0i + y] + pe[x0i + x]).
     Returns (logit, ctx, abs terms of logit, sum_n p (|x_n| + |pe rows|): the value-side terms are summed separately)."""
-    N = x.shape[0]
-    dot, ab = q @ x.t(), q.abs() @ x.abs().t()
-    val = vabs = x
-    if pos_a is not None:
-        t, y, xx = token_axes(N, H, W)
-        pos = pos_a[:, t0i + t] + pos_a[:, y0i + y] + pos_a[:, x0i + xx]
-        dot, ab = dot + pos, ab + pos_a[:, t0i + t].abs() + pos_a[:, y0i + y].abs() + pos_a[:, x0i + xx].abs()
-        val = x + pe[t0i + t] + pe[y0i + y] + pe[x0i + xx]
-        vabs = x.abs() + pe[t0i + t].abs() + pe[y0i + y].abs() + pe[x0i + xx].abs()
+    dot, ab, val, vabs = stream_terms(q, x, pos_a, pe if pos_a is not None else None, H, W, t0i, y0i, x0i)
     S = (dot + row_const[:, None]) * inv[None, :]
     ab = (ab + row_const.abs()[:, None]) * inv[None, :]
     p = torch.softmax(S, dim=1)
-    return S, p @ val, ab, p @ vabs.abs()
+    return S, p @ val, ab, p @ vabs
+
+
+# ---- the two global-stage stream kernels (hicom_global_stream_fwd / _marg_fwd / _bwd) and the merge behind them ---------------
+def axis_marginals(w, H, W, t_of=None):
+    """The t / y / x marginals of w [rows, N] over the token grid (T, H, W), N = T H W: ([rows, T], [rows, H], [rows, W]).
+    t_of: the frame each token is counted under (a planted defect; default its own)."""
+    rows, N = w.shape
+    t, y, xx = token_axes(N, H, W)
+    t = t if t_of is None else t_of
+    return tuple(torch.zeros(rows, n, dtype=w.dtype).index_add_(1, ax, w) for ax, n in ((t, N // (H * W)), (y, H), (xx, W)))
+
+
+def global_stream_ref(q, x, pos_a=None, pe=None, H=1, W=1, t0i=0, y0i=0, x0i=0, scale=1.0, axes=(True, True, True), t_of=None, lost=()):
+    """What hicom_global_stream_fwd / _marg_fwd and the merge behind them stand for, in float64:
+        S[r, n] = q_r . x_n + pos_a[r, t0i + t] + pos_a[r, y0i + y] + pos_a[r, x0i + x],  (M, L) and lse = M + log L per row,
+        p = softmax_n S,  ctx_r = sum_n p[r, n] x_n + mt_r . pe[t0i + .] + my_r . pe[y0i + .] + mx_r . pe[x0i + .]
+    with (mt, my, mx) the t / y / x marginals of p: the form the merge uses, equal to sum_n p (x_n + pe rows of n).  pos_a and pe
+    None: no positional part (H, W unused).  scale / axes / t_of / lost (tokens left out of the softmax) plant defects.
+    Returns a dict; `*_ab` is the same expression on absolute values; ctx_x is the token part of ctx alone."""
+    N = x.shape[0]
+    dot, ab, _, vabs = stream_terms(q, x, pos_a, pe, H, W, t0i, y0i, x0i, axes, t_of)
+    S, S_ab = scale * dot, abs(scale) * ab
+    Sk = S.clone()
+    Sk[:, list(lost)] = -math.inf
+    M = Sk.max(1).values
+    e = torch.exp(Sk - M[:, None])
+    L = e.sum(1)
+    p = e / L[:, None]
+    o = {"S": S, "S_ab": S_ab, "M": M, "L": L, "lse": M + torch.log(L), "p": p, "ctx_x": p @ x, "ctx_x_ab": p @ x.abs(), "vabs": vabs}
+    o["ctx"], o["ctx_ab"] = o["ctx_x"], p @ vabs
+    if pe is not None:
+        T = N // (H * W)
+        o["marg"] = axis_marginals(p, H, W, t_of)
+        for m, c0, n in zip(o["marg"], (t0i, y0i, x0i), (T, H, W)):
+            o["ctx"] = o["ctx"] + m @ pe[c0:c0 + n]
+    return o
+
+
+def global_stream_bwd_ref(g, x, pos_b, S, ml, delta, H=1, W=1, t0i=0, y0i=0, x0i=0, scale=1.0, axes=(True, True, True), t_of=None,
+                          lost=(), use_delta=True):
+    """hicom_global_stream_bwd in float64: dP[r, n] = g_r . x_n + pos_b[r, t0i + t] + pos_b[r, y0i + y] + pos_b[r, x0i + x],
+        dS = exp(S - M) / L (dP - delta),   dSx_r = sum_n dS[r, n] x_n,   (mt, my, mx) = the t / y / x marginals of dS
+    S [rows, >= N] the forward's logits, ml [rows, 2] = (M, L), delta [rows].  pos_b None: no positional part, no marginals.
+    scale (of dP) / axes / t_of / lost (tokens whose dS is dropped) / use_delta plant defects.  Returns a dict with `*_ab` companions."""
+    rows, N = g.shape[0], x.shape[0]
+    dP, dP_ab, _, _ = stream_terms(g, x, pos_b, None, H, W, t0i, y0i, x0i, axes, t_of)
+    dP, dP_ab = scale * dP, abs(scale) * dP_ab
+    p = torch.exp(S[:rows, :N] - ml[:, 0:1]) / ml[:, 1:2]
+    d = delta[:, None] if use_delta else torch.zeros(rows, 1, dtype=torch.float64)
+    dS, dS_ab = p * (dP - d), p * (dP_ab + d.abs())
+    dS[:, list(lost)] = 0
+    o = {"p": p, "dP": dP, "dP_ab": dP_ab, "dS": dS, "dS_ab": dS_ab, "dSx": dS @ x, "dSx_ab": dS.abs() @ x.abs()}
+    if pos_b is not None:
+        o["marg"], o["marg_ab"] = axis_marginals(dS, H, W, t_of), axis_marginals(dS.abs(), H, W, t_of)
+    return o
 
 
 # ---- row operators over the token stream ------------------------------------------------------------------------------------

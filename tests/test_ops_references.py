@@ -151,6 +151,51 @@ def test_clip_attention_reference_positional_terms():
     assert _maxabs(S, want_S) <= 1e-12 and _maxabs(ctx, torch.softmax(want_S, 1) @ xp) <= 1e-12
 
 
+@pytest.mark.parametrize("T,H,W,rows,t0", [(3, 2, 4, 5, 0), (2, 3, 3, 1, 2), (1, 4, 2, 3, 1)])
+def test_global_stream_references_equal_autograd_through_attention_over_x_plus_pos(T, H, W, rows, t0):
+    """f = sum_r ctx_r . g_r with ctx_r = sum_n softmax_n(qt_r . (x_n + pos_n)) (x_n + pos_n): the forward reference restates it, and
+    the backward reference's outputs assemble its gradients: d f / d qt = sum_n dS x_n + marginals(dS) @ PE, d f / d S = dS, with the
+    score-side tables pos_a = qt PE^T, pos_b = g PE^T and delta_r = g_r . ctx_r."""
+    gen = torch.Generator().manual_seed(T * 100 + H * 10 + W)
+    rnd = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)
+    E, N = 12, T * H * W
+    cap = t0 + T + 2
+    y0, x0 = cap, cap + H
+    pe, x, g = rnd(cap + H + W + 3, E), rnd(N, E), rnd(rows, E)
+    qt = (0.6 * rnd(rows, E)).requires_grad_(True)
+    t, y, xx = R.token_axes(N, H, W)
+    xp = x + pe[t0 + t] + pe[y0 + y] + pe[x0 + xx]                       # attention over x + pos, written out
+    S_plain = qt @ xp.t()
+    ctx_plain = torch.softmax(S_plain, 1) @ xp
+    (dqt,) = torch.autograd.grad((ctx_plain * g).sum(), qt)
+    qd = qt.detach()
+    fw = R.global_stream_ref(qd, x, qd @ pe.t(), pe, H, W, t0, y0, x0)
+    assert _maxabs(fw["S"], S_plain.detach()) <= TOL and _maxabs(fw["ctx"], ctx_plain.detach()) <= TOL
+    assert _maxabs(fw["lse"], torch.logsumexp(S_plain.detach(), 1)) <= TOL
+    assert _maxabs(fw["ctx"] - fw["ctx_x"], torch.softmax(S_plain.detach(), 1) @ (xp - x)) <= TOL      # the positional part alone
+    assert bool((fw["S_ab"] >= fw["S"].abs() - 1e-12).all()) and bool((fw["ctx_ab"] >= fw["ctx"].abs() - 1e-12).all())
+    for m in fw["marg"]:
+        assert _maxabs(m.sum(1), torch.ones(rows, dtype=torch.float64)) <= TOL
+    ml = torch.stack([fw["M"], fw["L"]], 1)
+    delta = (g * fw["ctx"]).sum(1)
+    pad = torch.full((rows, 5), float("nan"), dtype=torch.float64)      # columns beyond N do not matter
+    bw = R.global_stream_bwd_ref(g, x, g @ pe.t(), torch.cat([fw["S"], pad], 1), ml, delta, H, W, t0, y0, x0)
+    mt, my, mx = bw["marg"]
+    assert _maxabs(bw["dSx"] + mt @ pe[t0:t0 + T] + my @ pe[y0:y0 + H] + mx @ pe[x0:x0 + W], dqt) <= TOL
+    # the gradient with respect to the logits themselves
+    S_leaf = fw["S"].clone().requires_grad_(True)
+    (dS,) = torch.autograd.grad(((torch.softmax(S_leaf, 1) @ xp) * g).sum(), S_leaf)
+    assert _maxabs(bw["dS"], dS) <= TOL and float(bw["dS"].abs().max()) > 1e-3
+    assert _maxabs(bw["dS"].sum(1), torch.zeros(rows, dtype=torch.float64)) <= TOL          # the true delta: every row of dS sums to zero
+    assert bool((bw["dS_ab"] >= bw["dS"].abs() - 1e-12).all()) and bool((bw["dSx_ab"] >= bw["dSx"].abs() - 1e-12).all())
+    # without the positional tables both references are the plain folded attention of global_attention_backward_ref
+    S0, ml0, dS0, delta0 = R.global_attention_backward_ref(qd, x, g)
+    f0 = R.global_stream_ref(qd, x)
+    assert _maxabs(f0["S"], S0) <= TOL and _maxabs(torch.stack([f0["M"], f0["L"]], 1), ml0) <= TOL and "marg" not in f0
+    b0 = R.global_stream_bwd_ref(g, x, None, S0, ml0, delta0)
+    assert _maxabs(b0["dS"], dS0) <= TOL and "marg" not in b0
+
+
 def test_window_index_and_sequential_sum():
     win = R.window_of_token(4, 4, 6, 2, 2)
     assert int(win.max()) + 1 == 2 * 2 * 3 and bool((torch.bincount(win) == 8).all())
