@@ -20,6 +20,11 @@
 // Row space of an item: guide q owns rows nh q .. nh q + nh - 1, rows_i = nh Q_i in all; pass p of the stream carries rows [32 p, 32 p + 32),
 // its row group g (waves 4 g .. 4 g + 3) rows [32 p + 16 g, + 16).  Partial-state slots (16 rows each) are ordered
 // [item][pass][row group][chunk]: every 16-row group has its chunks in consecutive slots, which is what merge_segments walks.
+//
+// Prepared clips (hicom_compressor_clips_multiguide_*): the same step over B clips that live at their own addresses, each
+// with its own y planes for the k / v adaptor recipe.  Launches 3 and 4 are clips_local_kernel / clips_local_adapt_kernel and
+// clips_stream_kernel, which take an item's base pointers from a [B][4] device table the caller fills per call; checks, layout, table
+// region and every other launch are the functions of this file on the base block.
 #include <vector>
 
 #include "multi_window.hpp"
@@ -87,6 +92,76 @@ __global__ __launch_bounds__(512, 1) void rmg_stream_kernel(RmgStreamParams p) {
     const RmgUnit u = p.units[blockIdx.x];
     const RmgItem it = p.items[u.item];
     stream_segment<NB, 2>(p.c, p.x + (long)it.tok0 * E, it.N, u.tb, u.te, 32 * u.pass, p.c.rows * it.Q, (long)it.pair0 * p.c.rows,
+                          p.scores + (long)it.score_off * 16, (long)((it.N + 15) / 16 * 16), (long)u.slot, it.chunks);
+}
+
+// ---- 3 and 4 over PREPARED CLIPS: every item lives at its own addresses ----
+// One row of the caller's device table per item (hicom_compressor_clips_multiguide_args.item_ptrs): where the item's key tokens, value
+// tokens and y planes begin.  ky / vy are NULL for a stream without adaptor.  The kernels only read through these pointers.
+struct ClipPtrs {
+    const uint16_t* key_x;      // frames_embed, or frames_feature without it: [N_i][E]
+    const uint16_t* value_x;    // frames_feature [N_i][E]: the values of the local stage, the tokens of the global stream
+    const _Float16* ky;         // MLP_k(key_x) fp16 [N_i][E]
+    const _Float16* vy;         // MLP_v(value_x) fp16 [N_i][E]
+};
+static_assert(sizeof(ClipPtrs) == 32, "a table row is four 64-bit addresses");
+
+// rmg_local_kernel with the item's base pointers from the table instead of key + tok0 D: the window list, the wave -> window map, the
+// device function and the pair-major context rows are the same, so a plain-recipe call has the bits of the ragged multi-guide step.
+// The lookups are wave-uniform (win is); nothing is stored through what they return.
+template <int NV>
+__global__ __launch_bounds__(256) void clips_local_kernel(const ClipPtrs* clips, const uint16_t* guide, const RmgItem* items, const int* win_item,
+                                                          hicom_axis ay, hicom_axis ax, int nwin, float scale, _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const int item = win_item[win];
+    const RmgItem it = items[item];
+    const ClipPtrs c = clips[item];
+    const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+    const int wi = (it.T / it.kt) * ay.nwin * ax.nwin;
+    const WindowGeom g(at, ay, ax, win - it.win0);
+    multi_window_guides_ctx16<NV>(c.key_x, c.value_x, guide, it.pair0, it.Q, g, lane, scale, ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D,
+                                  (long)wi * D);
+}
+
+// The same for the k / v adaptor recipe: the window of multi_guide_local_adapt_kernel (multi_window.hpp: groups of kAdaptGuideGroup guides)
+// on the item's own tokens and planes.  ad: gamma / beta / alpha / eps of the call; its ky / vy are replaced by the item's.
+template <int NV>
+__global__ __launch_bounds__(256) void clips_local_adapt_kernel(const ClipPtrs* clips, const uint16_t* guide, SegAdaptParams ad, const RmgItem* items,
+                                                                const int* win_item, hicom_axis ay, hicom_axis ax, int nwin, float scale,
+                                                                _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const int item = win_item[win];
+    const RmgItem it = items[item];
+    const ClipPtrs c = clips[item];
+    ad.ky = c.ky;
+    ad.vy = c.vy;
+    const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+    const int wi = (it.T / it.kt) * ay.nwin * ax.nwin;
+    const WindowGeom g(at, ay, ax, win - it.win0);
+    multi_window_guides_adapt_ctx16<NV, kAdaptGuideGroup>(c.key_x, c.value_x, ad, guide, it.pair0, it.Q, g, lane, scale,
+                                                          ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)wi * D);
+}
+
+// rmg_stream_kernel with the unit's tokens at the item's value_x: work units, passes, slots and scores are the same
+struct ClipsStreamParams {
+    SegStreamParams c;
+    const ClipPtrs* clips;
+    float* scores;
+    const RmgUnit* units;
+    const RmgItem* items;
+};
+
+template <int NB>
+__global__ __launch_bounds__(512, 1) void clips_stream_kernel(ClipsStreamParams p) {
+    const RmgUnit u = p.units[blockIdx.x];
+    const RmgItem it = p.items[u.item];
+    stream_segment<NB, 2>(p.c, p.clips[u.item].value_x, it.N, u.tb, u.te, 32 * u.pass, p.c.rows * it.Q, (long)it.pair0 * p.c.rows,
                           p.scores + (long)it.score_off * 16, (long)((it.N + 15) / 16 * 16), (long)u.slot, it.chunks);
 }
 
@@ -263,10 +338,19 @@ int rmg_prepare(const Args* a) {
     return seg_upload_tables(kWho, a, tab.data(), l.table_bytes);
 }
 
+// the clips step (hicom_compressor_clips_multiguide_fwd): the caller's device table and the local stage's adaptor parameters (their ky / vy
+// come from the table per item)
+struct ClipsCall {
+    const ClipPtrs* ptrs;
+    bool adapted;
+    SegAdaptParams ad;
+};
+
 // the four launches that look their pair or item up in the table region (segment_host.hpp: seg_step)
 struct PairItems {
     const Args* a;
     const RmgLayout& l;
+    const ClipsCall* clips;     // the items are prepared clips at their own addresses; NULL: the stacked tensor a->ff / a->fe
     char* ws() const { return (char*)a->ws; }
     hipStream_t s() const { return (hipStream_t)a->stream; }
     const RmgItem* items() const { return (const RmgItem*)(ws() + l.items); }
@@ -274,13 +358,38 @@ struct PairItems {
 
     int local(const uint16_t* key_x, const SegAdaptParams*) const {
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
-        HICOM_LAUNCH(rmg_local_kernel<3>, dim3((unsigned)((l.item_windows + 3) / 4)), dim3(256), 0, s(), key_x, (const uint16_t*)a->ff,
-                     (const uint16_t*)a->guide, items(), (const int*)(ws() + l.win_item), ay, ax, (int)l.item_windows, a->l_scale,
-                     (_Float16*)(ws() + l.s.ctx16));
+        const dim3 grid((unsigned)((l.item_windows + 3) / 4));
+        const int* win_item = (const int*)(ws() + l.win_item);
+        _Float16* ctx16 = (_Float16*)(ws() + l.s.ctx16);
+        if (clips && clips->adapted)
+            HICOM_LAUNCH(clips_local_adapt_kernel<3>, grid, dim3(256), 0, s(), clips->ptrs, (const uint16_t*)a->guide, clips->ad, items(), win_item, ay, ax,
+                         (int)l.item_windows, a->l_scale, ctx16);
+        else if (clips)
+            HICOM_LAUNCH(clips_local_kernel<3>, grid, dim3(256), 0, s(), clips->ptrs, (const uint16_t*)a->guide, items(), win_item, ay, ax,
+                         (int)l.item_windows, a->l_scale, ctx16);
+        else
+            HICOM_LAUNCH(rmg_local_kernel<3>, grid, dim3(256), 0, s(), key_x, (const uint16_t*)a->ff, (const uint16_t*)a->guide, items(), win_item, ay, ax,
+                         (int)l.item_windows, a->l_scale, ctx16);
         return seg_check_launch(kWho, "local stage");
     }
 
+    int stream_clips(const SegStreamParams& c) const {
+        ClipsStreamParams p;
+        p.c = c;
+        p.clips = clips->ptrs;
+        p.scores = (float*)(ws() + l.s.scores);
+        p.units = (const RmgUnit*)(ws() + l.units); p.items = items();
+        static bool attr_set = false;
+        if (!attr_set) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(clips_stream_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, seg_stream_smem(2));
+            attr_set = true;
+        }
+        HICOM_LAUNCH(clips_stream_kernel<9>, dim3((unsigned)l.nunits), dim3(512), seg_stream_smem(2), s(), p);
+        return seg_check_launch(kWho, "global stream");
+    }
+
     int stream(const SegStreamParams& c) const {
+        if (clips) return stream_clips(c);
         RmgStreamParams p;
         p.c = c;
         p.x = (const uint16_t*)a->ff;
@@ -314,11 +423,13 @@ struct PairItems {
     }
 };
 
-int rmg_fwd(const Args* a) {
+// clips: the items are prepared clips at their own addresses (clips_fwd); every check runs as for the stacked tensor, only a->ff / a->fe
+// are not looked at
+int rmg_fwd(const Args* a, const ClipsCall* clips = nullptr) {
     int st = rmg_check(a);
     if (st != HICOM_OK) return st;
     const RmgLayout l = rmg_layout(a);
-    st = seg_check_fwd(kWho, a, nullptr, l.s.total);
+    st = seg_check_fwd(kWho, a, nullptr, l.s.total, clips != nullptr);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->ldo >= a->hidden, HICOM_EINVAL, "compressor_ragged_multiguide: output layout");
     for (int i = 0; i < a->B; ++i)
@@ -326,7 +437,36 @@ int rmg_fwd(const Args* a) {
                       "compressor_ragged_multiguide: item %d has newline rows and there is no newline token", i);
     Args pairs = *a;            // the shared host sees the pairs as its items: M guide rows, M global tokens, all pairs' window contexts
     pairs.B = l.M;
-    return seg_step(&pairs, nullptr, l.s, PairItems{a, l});
+    return seg_step(&pairs, nullptr, l.s, PairItems{a, l, clips});
+}
+
+// ---- prepared clips, Q_i guides each (hicom_compressor_clips_multiguide_*) -----------------------------------------------------------------
+constexpr const char* kWhoClips = "compressor_clips_multiguide";
+typedef hicom_compressor_clips_multiguide_args ClipsArgs;
+
+// what the block adds to the checks of its base block (which run behind these, under the base step's name)
+int clips_check(const ClipsArgs* a) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", kWhoClips);
+    HICOM_REQUIRE(!a->base.ff && !a->base.fe, HICOM_EINVAL, "%s: the clips' tokens come through item_ptrs: base.ff and base.fe must be NULL", kWhoClips);
+    if (a->ak.w0 || a->av.w0)
+        HICOM_REQUIRE(a->alpha_dt == HICOM_DT_BF16 || a->alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", kWhoClips, a->alpha_dt);
+    return rmg_check(&a->base);
+}
+
+int clips_fwd(const ClipsArgs* a) {
+    int st = clips_check(a);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(a->item_ptrs && (uintptr_t)a->item_ptrs % 16 == 0, HICOM_EINVAL, "%s: item_ptrs is a 16-byte aligned DEVICE table [B][4]", kWhoClips);
+    for (const hicom_seg_adaptor* s : {&a->ak, &a->av})
+        if (s->w0) HICOM_REQUIRE(s->gamma && s->beta && s->alpha, HICOM_EINVAL, "%s: adaptor weights", kWhoClips);
+    ClipsCall c;
+    c.ptrs = (const ClipPtrs*)a->item_ptrs;
+    c.adapted = a->ak.w0 || a->av.w0;
+    c.ad.ky = nullptr; c.ad.kgamma = (const uint16_t*)a->ak.gamma; c.ad.kbeta = (const uint16_t*)a->ak.beta; c.ad.kalpha = a->ak.alpha;
+    c.ad.vy = nullptr; c.ad.vgamma = (const uint16_t*)a->av.gamma; c.ad.vbeta = (const uint16_t*)a->av.beta; c.ad.valpha = a->av.alpha;
+    c.ad.alpha_f32 = a->alpha_dt == HICOM_DT_F32;
+    c.ad.eps = a->eps;
+    return rmg_fwd(&a->base, &c);
 }
 
 }  // namespace
@@ -340,3 +480,18 @@ extern "C" int64_t hicom_compressor_ragged_multiguide_workspace_bytes(const hico
 extern "C" int hicom_compressor_ragged_multiguide_prepare(const hicom_compressor_ragged_multiguide_args* a) { return rmg_prepare(a); }
 
 extern "C" int hicom_compressor_ragged_multiguide_fwd(const hicom_compressor_ragged_multiguide_args* a) { return rmg_fwd(a); }
+
+// The planes and the tokens are the caller's: the workspace and its table region are the ragged multi-guide step's for the base block.
+extern "C" int64_t hicom_compressor_clips_multiguide_workspace_bytes(const hicom_compressor_clips_multiguide_args* a) {
+    const int st = clips_check(a);
+    if (st != HICOM_OK) return st;
+    return rmg_layout(&a->base).s.total;
+}
+
+extern "C" int hicom_compressor_clips_multiguide_prepare(const hicom_compressor_clips_multiguide_args* a) {
+    const int st = clips_check(a);
+    if (st != HICOM_OK) return st;
+    return rmg_prepare(&a->base);
+}
+
+extern "C" int hicom_compressor_clips_multiguide_fwd(const hicom_compressor_clips_multiguide_args* a) { return clips_fwd(a); }

@@ -151,16 +151,17 @@ inline int seg_check_ws(const char* who, const A* a, long total) {
     return HICOM_OK;
 }
 
-// what a *_fwd call checks on top of its shape checks, in front of the first launch
+// what a *_fwd call checks on top of its shape checks, in front of the first launch; tokens_elsewhere: the step finds its tokens through a
+// table of its own (ragged_multi_guide.hip: the clips step), ff / fe are not looked at
 template <class A>
-inline int seg_check_fwd(const char* who, const A* a, const SegAdapt* ad, long ws_total) {
-    HICOM_REQUIRE(a->ff && a->guide && a->out, HICOM_EINVAL, "%s: NULL pointer", who);
+inline int seg_check_fwd(const char* who, const A* a, const SegAdapt* ad, long ws_total, bool tokens_elsewhere = false) {
+    HICOM_REQUIRE((a->ff || tokens_elsewhere) && a->guide && a->out, HICOM_EINVAL, "%s: NULL pointer", who);
     HICOM_REQUIRE(a->lw0_f16 && a->lw2_f16 && a->wq && a->wk && a->wv && a->wo && a->gw0 && a->gw2, HICOM_EINVAL, "%s: NULL weight", who);
     int st = seg_adapt_check_weights(who, ad);
     if (st != HICOM_OK) return st;
     st = seg_check_ws(who, a, ws_total);
     if (st != HICOM_OK) return st;
-    HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (!a->fe || (uintptr_t)a->fe % 16 == 0) && (uintptr_t)a->guide % 16 == 0, HICOM_EINVAL,
+    HICOM_REQUIRE((tokens_elsewhere || ((uintptr_t)a->ff % 16 == 0 && (!a->fe || (uintptr_t)a->fe % 16 == 0))) && (uintptr_t)a->guide % 16 == 0, HICOM_EINVAL,
                   "%s: 16-byte aligned inputs", who);
     return HICOM_OK;
 }

@@ -48,6 +48,7 @@ EXPORTS = (
     "hicom_compressor_ragged_multiguide_fwd", "hicom_compressor_ragged_multiguide_workspace_bytes", "hicom_compressor_ragged_multiguide_prepare",
     "hicom_clip_adapt_prepare_fwd", "hicom_clip_adapt_prepare_workspace_bytes",
     "hicom_compressor_multiguide_adapt_fwd", "hicom_compressor_multiguide_adapt_workspace_bytes",
+    "hicom_compressor_clips_multiguide_fwd", "hicom_compressor_clips_multiguide_workspace_bytes", "hicom_compressor_clips_multiguide_prepare",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -231,6 +232,14 @@ class CompressorRaggedMultiGuideArgs(C.Structure):
                                     if name == "items" else []))]
 
 
+class CompressorClipsMultiGuideArgs(C.Structure):
+    """hicom_compressor_clips_multiguide_args (include/hicom_hip.h): the ragged multi-guide block first (its ff / fe stay NULL), then the two
+    adaptors (w0 NULL: not adapted; gamma / beta / alpha are read), the alpha dtype, the LayerNorm eps and the address of the DEVICE table
+    [B][4] of 64-bit addresses {key_x, value_x, ky, vy} per item."""
+    _fields_ = [("base", CompressorRaggedMultiGuideArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("alpha_dt", C.c_int32), ("eps", C.c_float),
+                ("item_ptrs", C.c_void_p)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -351,6 +360,9 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_multiguide_fwd.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
     L.hicom_compressor_ragged_multiguide_prepare.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
     L.hicom_compressor_ragged_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
+    L.hicom_compressor_clips_multiguide_fwd.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
+    L.hicom_compressor_clips_multiguide_prepare.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
+    L.hicom_compressor_clips_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -367,6 +379,7 @@ def lib() -> C.CDLL:
     L.hicom_compressor_multiguide_adapt_workspace_bytes.restype = C.c_int64
     L.hicom_clip_adapt_prepare_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_multiguide_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_clips_multiguide_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -766,6 +779,18 @@ def compressor_ragged_multiguide_prepare(args: CompressorRaggedMultiGuideArgs):
 
 def compressor_ragged_multiguide_fwd(args: CompressorRaggedMultiGuideArgs):
     _seg_call(args, "ragged_multiguide", "fwd")
+
+
+def compressor_clips_multiguide_workspace(args: CompressorClipsMultiGuideArgs) -> int:
+    return _seg_call(args, "clips_multiguide", "workspace_bytes", "forward_prepared_many")
+
+
+def compressor_clips_multiguide_prepare(args: CompressorClipsMultiGuideArgs):
+    _seg_call(args, "clips_multiguide", "prepare")
+
+
+def compressor_clips_multiguide_fwd(args: CompressorClipsMultiGuideArgs):
+    _seg_call(args, "clips_multiguide", "fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -1139,6 +1139,27 @@ class HIComProjector(nn.Module):
         from . import prepared
         return prepared.run_prepared(self, clip, guide_embeds, image_newline, chunks)
 
+    def forward_prepared_many(self, clips, guide_embeds, guide_counts, image_newline=None, *, chunks=None):
+        """B prepared clips, clip i with its own Q_i instructions, in one native call -- a server with B videos in flight and a few
+        pending questions about each.  clips: a sequence of what prepare_clip returned, each with its own storage, frame count and
+        modality (images, clips of unequal length and 1-frame "videos" side by side; a clip may appear more than once); guide_counts the B
+        ints Q_i, 1 <= Q_i <= 32; guide_embeds bf16 [sum Q_i, E], the guides of clip i in the rows [sum_(j<i) Q_j, + Q_i).  Returns the
+        list of B tensors [Q_i, rows_i, hidden], views that tile ONE storage in item-major, then guide-major order; out[i][q] is laid out
+        as forward() on clip i alone with its guide q and equals it to the kernels' rounding.
+        The clips are read where they live: the twelve launches of forward_ragged_multi_guide, the two that read tokens taking each
+        clip's addresses from a per-plan device table (csrc/ragged_multi_guide.hip).  No adaptor MLP runs and nothing
+        token-sized is allocated or copied.  A plain-recipe module's clips carry no planes: the call is then forward_ragged_multi_guide
+        over separately allocated tensors, bit for bit.  Plans are keyed by the mix of shapes, not by the clips.
+        Scope as forward_prepared and forward_ragged_multi_guide (the two release recipes, bf16, E = 1152, hidden % 64 == 0, one H x W
+        per call, exact window partition, inference only); in addition ValueError for a clip of another module, clips that disagree on
+        H, W, E or on having frames_embed, and planes that do not match the module's adaptors; RuntimeError naming the clip for a
+        stale one (clip.refresh()).  Every refusal comes in front of the first launch.
+        A clip made on another stream is waited for on the device.  The call may wait on the host for its own stream while it writes
+        the table (a call with the clips of the call before writes nothing).
+        Which path when: DESIGN.md §3.11 has the measured table (tools/prepared_many_bench.py)."""
+        from . import prepared_many
+        return prepared_many.run_prepared_many(self, clips, guide_embeds, guide_counts, image_newline, chunks)
+
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):
         """B items of UNEQUAL length and mixed modality, item i with its own Q_i instructions, in one native call -- a Video-MME style

@@ -110,21 +110,35 @@ def check_inputs(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl):
     return counted["B"], ff.shape[1], ff.shape[2], E, split_sizes, guide_counts, modals
 
 
-def _build(proj, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev, stream):
-    desc, ks = ragged.item_descriptors(proj, split_sizes, modals, H, W, nl is not None, WHAT)
+def build_plan(proj, what, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev, stream, block=nv.CompressorRaggedMultiGuideArgs,
+               workspace=nv.compressor_ragged_multiguide_workspace, prepare=nv.compressor_ragged_multiguide_prepare, fill=None):
+    """The plan of a step over B items with Q_i guides each: this module's, or forward_prepared_many's (prepared_many.py: `block` holds the
+    ragged multi-guide block as `base`; fill(args, ptr) enters what it adds in front of the workspace call).  The item walk, the common
+    fields, the workspace, the device tables (once per plan) and their Python restatement are one function for both."""
+    desc, ks = ragged.item_descriptors(proj, split_sizes, modals, H, W, nl is not None, what)
     items = (nv.RaggedItem * len(desc))(*[nv.RaggedItem(*d) for d in desc])
     counts = (C.c_int32 * len(guide_counts))(*guide_counts)
-    args, a, keep, ptr = seg.new_args(proj, nv.CompressorRaggedMultiGuideArgs, None)       # (no adaptor recipe: check_inputs refuses it)
+    args, a, keep, ptr = seg.new_args(proj, block, block)
     a.B, a.E, a.ks, a.items = len(desc), E, ks, items
     a.guide_counts, a.n_guide_counts = counts, len(guide_counts)
     refresh = seg.fill_common(a, proj, max(split_sizes), H, W, dev, out_dtype, chunks, ptr)
     a.stream = stream
-    ws, _ = seg.alloc_workspace(args, a, nv.compressor_ragged_multiguide_workspace, dev)     # (the kernels' limits raise here, in front of any launch)
-    nv.compressor_ragged_multiguide_prepare(args)               # the device tables, once per plan (synchronises the stream)
+    if fill is not None:
+        fill(args, ptr)
+    nbytes = workspace(args)                                    # (the kernels' limits raise here, in front of any launch)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+    prepare(args)                                               # the device tables, once per plan (synchronises the stream)
     tables = plan_tables(desc, guide_counts, H, W, ks, a.nh, torch.cuda.get_device_properties(dev).multi_processor_count, a.chunks)
     plan = seg.SegPlan(args, ws, tables.pair_rows, a.hidden, (items, counts), tables)
     plan.keep, plan.refresh = keep, refresh
     return plan
+
+
+def pair_views(plan, out):
+    """Item i's Q_i pairs' rows follow each other, all of one length: a [Q_i, rows_i, hidden] view of the one storage per item."""
+    t = plan.tables
+    return [v.view(q, r, plan.hidden) for v, q, r in zip(out.split([q * r for q, r in zip(t.Q, t.rows)]), t.Q, t.rows)]
 
 
 def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None):
@@ -132,10 +146,9 @@ def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, moda
     dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, WHAT, ff, fe, guides, nl)
     key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
            seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v, guide_counts)
-    plan = seg.cached_plan(proj, STORE, key, lambda: _build(proj, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev, stream))
-    t = plan.tables
+    plan = seg.cached_plan(proj, STORE, key, lambda: build_plan(proj, WHAT, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev,
+                                                                stream))       # (no adaptor recipe: check_inputs refuses it)
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
     seg.patch_io(plan.io, ff, fe, guides, nl, out, stream)      # (the newline pointer whenever given: items differ in their newline rows)
     nv.compressor_ragged_multiguide_fwd(plan.args)
-    # item i: its Q_i pairs' rows follow each other, all of one length -- a [Q_i, rows_i, hidden] view of the one storage
-    return [v.view(q, r, plan.hidden) for v, q, r in zip(out.split([q * r for q, r in zip(t.Q, t.rows)]), t.Q, t.rows)]
+    return pair_views(plan, out)

@@ -1108,6 +1108,36 @@ int64_t hicom_compressor_ragged_multiguide_workspace_bytes(const hicom_compresso
 int hicom_compressor_ragged_multiguide_prepare(const hicom_compressor_ragged_multiguide_args* args);
 int hicom_compressor_ragged_multiguide_fwd(const hicom_compressor_ragged_multiguide_args* args);
 
+/* ---- prepared clips, Q_i instructions each: the ragged multi-guide step over clips at their own addresses ---------
+ * B prepared clips (hicom_clip_adapt_prepare_fwd; or plain token tensors for the plain recipe) that were made at different times live
+ * at different addresses, each with its own y planes.  This is hicom_compressor_ragged_multiguide_fwd with launch 3 (local windows) and
+ * launch 4 (segmented stream) taking an item's base pointers from a device table instead of ff + tok0 E: the same twelve launches, no
+ * adaptor MLP, nothing token-sized in the workspace.  One entry point serves both release recipes.
+ *   base      : the ragged multi-guide block.  ff and fe are not used and must be NULL (HICOM_EINVAL); items, guide_counts, guide,
+ *               chunks, out, ws as there
+ *   ak, av    : w0 == NULL: that stream is not adapted; both NULL: the plain recipe (the plain window runs).  Of an adapted stream
+ *               gamma / beta / alpha are read (w0 .. b2 are not), as in hicom_compressor_multiguide_adapt_args
+ *   alpha_dt  : dtype of the two alpha scalars (HICOM_DT_BF16 | HICOM_DT_F32); eps: the LayerNorms' epsilon
+ *   item_ptrs : DEVICE table [B][4] of 64-bit addresses {key_x, value_x, ky, vy} per item, 16-byte aligned.  key_x: the clip's
+ *               frames_embed, or its frames_feature when there is none; value_x: its frames_feature (bf16 [T_i H W, E] each, 16-byte
+ *               aligned); ky / vy: its fp16 [T_i H W, E] planes, 0 for a stream without adaptor.  The kernels only read through them.
+ *               The table is the CALLER's to fill, per call, on `stream` in front of the call: stream order protects it against the
+ *               previous call's kernels.  The host cannot look at device-resident addresses: the caller checks them.
+ * hicom_compressor_clips_multiguide_workspace_bytes equals hicom_compressor_ragged_multiguide_workspace_bytes on `base` (the tokens and
+ * the planes are the caller's); hicom_compressor_clips_multiguide_prepare writes the same table region, once per plan (tok0 stays in the
+ * item table and is not used for addressing); hicom_compressor_clips_multiguide_fwd then only launches: no copy, no synchronisation, no
+ * allocation.  Limits and error codes are those of the base step; its checks report under its name. */
+typedef struct hicom_compressor_clips_multiguide_args {
+    hicom_compressor_ragged_multiguide_args base;
+    hicom_seg_adaptor ak, av;
+    int32_t alpha_dt;
+    float eps;
+    const uint64_t* item_ptrs;                      /* DEVICE memory, B x 4 entries */
+} hicom_compressor_clips_multiguide_args;
+int64_t hicom_compressor_clips_multiguide_workspace_bytes(const hicom_compressor_clips_multiguide_args* args);
+int hicom_compressor_clips_multiguide_prepare(const hicom_compressor_clips_multiguide_args* args);
+int hicom_compressor_clips_multiguide_fwd(const hicom_compressor_clips_multiguide_args* args);
+
 #ifdef __cplusplus
 }
 #endif
