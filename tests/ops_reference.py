@@ -290,6 +290,67 @@ def sequential_f32_sum(parts):
     return s
 
 
+# ---- dense 16-bit GEMM (hicom_dense16_gemm_fwd, hicom_dense16_tn_fwd) -----------------------------------------------------------
+def slice_sums(v):
+    """Sums of v [M, N] over the 64-column slices [64 s, min(64 s + 64, N)) -> [ceil(N / 64), M] (the layout of ssq / row_dot)."""
+    M, N = v.shape
+    S = (N + 63) // 64
+    pad = torch.zeros(M, 64 * S, dtype=v.dtype)
+    pad[:, :N] = v
+    return pad.reshape(M, S, 64).sum(-1).t().contiguous()
+
+
+def dense16_ref(a, w, b, *, K, tab=None, geom=None, act="none", res=None, dot_vec=None, t_of=None, swap_yx=False, tab_pitch=None,
+                row_of=None, tab_at="pre", pre_has_tab=True, pad_cols_in_ssq=False, slices_swapped=False):
+    """hicom_dense16_gemm_fwd in float64 on the exactly widened operands: a [M, >= K], w [N, >= K], b [N] or None,
+        pre = a[:, :K] . w[:, :K]^T + table + b,   val = act(pre),   y = val + res,
+        ssq[s, m] = sum of pre^2 over slice s (columns [64 s, min(64 s + 64, N))),   rdot[s, m] = sum of dot_vec . y over slice s,
+    table[m, n] = tab[t0 + m // (H W), n] + tab[y0 + (m // W) % H, n] + tab[x0 + m % W, n] for n < N, geom = (H, W, t0, y0, x0),
+    tab [P, tab_ld >= N].  act: "none" | "gelu" (erf) | "gelu_tanh".  Returns a dict (rdot only with dot_vec).
+    The remaining keywords plant the defects of tests/test_dense16_power.py:
+      t_of [M]         the frame row m is taken for;   swap_yx: y = rem % H, x = rem // H
+      tab_pitch        the table read as a flat array with this pitch in place of tab_ld
+      row_of [M]       the row whose (t, y, x) row m takes
+      tab_at           "pre" (right) | "after_ssq": ssq is taken without the table | "after_act": the table is added to act(acc + b)
+      pre_has_tab      False: the `pre` output alone lacks the table
+      pad_cols_in_ssq  every padded column of the last slice adds b[N - 1]^2;   slices_swapped: slices 0 and 1 of ssq / rdot exchanged"""
+    M, N = a.shape[0], w.shape[0]
+    acc = a[:, :K] @ w[:, :K].t()
+    bias = torch.zeros(N, dtype=torch.float64) if b is None else b
+    term = torch.zeros(M, N, dtype=torch.float64)
+    if tab is not None:
+        H, W, t0, y0, x0 = geom
+        m = torch.arange(M) if row_of is None else row_of
+        t, rem = (m // (H * W) if t_of is None else t_of), m % (H * W)
+        y, x = (rem % H, rem // H) if swap_yx else (rem // W, rem % W)
+        flat, pitch, cols = tab.reshape(-1), (tab.shape[1] if tab_pitch is None else tab_pitch), torch.arange(N)
+        rows = lambda r: flat[r[:, None] * pitch + cols[None, :]]
+        term = rows(t0 + t) + rows(y0 + y) + rows(x0 + x)
+    plain = acc + bias
+    full = plain + term
+    f = {"none": lambda h: h, "gelu": lambda h: gelu_ref(h)[0], "gelu_tanh": lambda h: torch.nn.functional.gelu(h, approximate="tanh")}[act]
+    val = f(plain) + term if tab_at == "after_act" else f(full)
+    sq_of = full if tab_at == "pre" else plain
+    o = {"pre": full if (pre_has_tab and tab_at != "after_act") else plain, "val": val, "y": val if res is None else val + res}
+    o["ssq"] = slice_sums(sq_of * sq_of)
+    if pad_cols_in_ssq:
+        o["ssq"][-1] += (64 * o["ssq"].shape[0] - N) * bias[N - 1] ** 2
+    if dot_vec is not None:
+        o["rdot"] = slice_sums(o["y"] * dot_vec[None, :])
+    if slices_swapped:
+        for k in ("ssq", "rdot"):
+            if k in o:
+                o[k] = o[k][[1, 0] + list(range(2, o[k].shape[0]))]
+    return o
+
+
+def dense16_tn_ref(a, b, M, N, k_rows=None):
+    """hicom_dense16_tn_fwd (all splits summed) in float64: a[:, :M]^T . b[:, :N] over the rows of a [Kt, >= M] and b [Kt, >= N].
+    k_rows (a slice of the contraction rows that are kept) plants a dropped split."""
+    k_rows = slice(None) if k_rows is None else k_rows
+    return a[k_rows, :M].t() @ b[k_rows, :N]
+
+
 # ---- fused local + global stream (hicom_fused_stream_fwd) and its query producer (hicom_query_prep_fwd) -----------------------
 def ring_partitions(NW, nparts):
     """Partition of every window: the contiguous window-major ranges [p wpw, min((p + 1) wpw, NW)), wpw = ceil(NW / nparts)."""

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import make_golden_head as mh
+import ops_reference as R
 from hicom_amd import native as nv
 from oracle import hicom_oracle as orc
 
@@ -94,6 +95,8 @@ def test_dense16_gemm_matches_torch(M, N, K, dt):
     assert float((o16[:, :N].double() - act).abs().max()) <= 2 ** -11 * scale + 1e-6
     assert float(o16[:, N:].abs().max()) == 0.0 if npad > N else True
     assert float((ssq.sum(0).double() - (ref ** 2).sum(1)).abs().max()) <= 1e-4 * float((ref ** 2).sum(1).max())
+    per_slice = R.slice_sums(ref.cpu() ** 2)                          # [ceil(N / 64), M]: every slice on its own, not only their sum
+    assert ssq.shape == per_slice.shape and float((ssq.cpu().double() - per_slice).abs().max()) <= 1e-4 * float(per_slice.max())
 
 
 @pytest.mark.parametrize("act,approx", [(nv.ACT_GELU_TANH, "tanh"), (nv.ACT_GELU, "none")])
@@ -156,6 +159,9 @@ def test_dense16_row_dot_epilogue(M, N, K, with_y, vec_dt):
     scale = float((ref.abs() @ vec.double().abs()).max())
     assert float((out.double() - want).abs().max()) <= 2e-6 * scale
     assert float((parts.sum(0).double() - want).abs().max()) <= 2e-6 * scale
+    per_slice = R.slice_sums(ref.cpu() * vec.double().cpu())         # [ceil(N / 64), M]: every slice on its own, not only their sum
+    slice_scale = float(R.slice_sums(ref.cpu().abs() * vec.double().cpu().abs()).max())
+    assert parts.shape == per_slice.shape and float((parts.cpu().double() - per_slice).abs().max()) <= 2e-6 * slice_scale
     if with_y:
         assert float((y.double() - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
     with pytest.raises(nv.HicomNativeError):

@@ -399,3 +399,66 @@ def test_ring_defect_query_lo_plane_dropped_is_reported():
             best = max(best, _ratio(i, ref, b, bad, _GLOBAL))
     print(f"RING_DEFECT query_lo_dropped ratio={best:.3e}")
     assert best >= 2.0
+
+
+# ---- dense 16-bit GEMM references ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T,H,W,N,offs", [(3, 4, 5, 136, (0, 3, 7)), (2, 3, 7, 132, (5, 9, 14)), (1, 6, 6, 64, (0, 1, 7))])
+def test_dense16_reference_is_the_projection_of_tokens_plus_a_separable_positional_embedding(T, H, W, N, offs):
+    """The identity the clip-scale global stage rests on (csrc/dense16.hip, DenseParams::tab): with a separable positional embedding
+    pos(m) = PE[t0 + t] + PE[y0 + y] + PE[x0 + x] and tab = PE W^T, (x + pos) W^T + b = x W^T + tab[t0 + t] + tab[y0 + y] + tab[x0 + x] + b,
+    and the per-slice sums of squares add up to the squared row norm of that product."""
+    g = torch.Generator().manual_seed(T * 100 + N)
+    M, K, P, ld = T * H * W, 24, 24, N + 8
+    x, w, b = (torch.randn(s, dtype=torch.float64, generator=g) for s in ((M, K + 5), (N, K), (N,)))
+    pe = torch.randn(P, K, dtype=torch.float64, generator=g)
+    tab = torch.full((P, ld), float("nan"), dtype=torch.float64)             # a pitch above N: the pad columns are never read
+    tab[:, :N] = pe @ w.t()
+    t0, y0, x0 = offs
+    m = torch.arange(M)
+    pos = pe[t0 + m // (H * W)] + pe[y0 + (m // W) % H] + pe[x0 + m % W]
+    direct = (x[:, :K] + pos) @ w.t() + b
+    res, vec = torch.randn(M, N, dtype=torch.float64, generator=g), torch.randn(N, dtype=torch.float64, generator=g)
+    o = R.dense16_ref(x, w, b, K=K, tab=tab, geom=(H, W, t0, y0, x0), act="gelu", res=res, dot_vec=vec)
+    assert _maxabs(o["pre"], direct) <= 1e-12
+    assert o["ssq"].shape == ((N + 63) // 64, M) and _maxabs(o["ssq"].sum(0), (direct ** 2).sum(1)) <= 1e-12 * float((direct ** 2).sum(1).max())
+    gelu = torch.nn.functional.gelu(direct)
+    assert _maxabs(o["val"], gelu) <= 1e-12 and _maxabs(o["y"], gelu + res) <= 1e-12
+    assert _maxabs(o["rdot"].sum(0), (gelu + res) @ vec) <= 1e-11
+    plain = R.dense16_ref(x, w, None, K=K, act="gelu_tanh")
+    assert _maxabs(plain["pre"], x[:, :K] @ w.t()) <= 1e-12 and _maxabs(plain["y"], torch.nn.functional.gelu(plain["pre"], approximate="tanh")) <= 1e-12
+    assert "rdot" not in plain
+
+
+@pytest.mark.parametrize("N", [136, 132])
+def test_dense16_reference_slice_boundaries_by_hand_built_columns(N):
+    """One row, a = e_0, w[n, 0] = the column's value: columns 0 .. 63 carry 1, 64 .. 127 carry 2, the last N - 128 carry 3."""
+    a = torch.zeros(1, 8, dtype=torch.float64)
+    a[0, 0] = 1.0
+    w = torch.zeros(N, 8, dtype=torch.float64)
+    w[:64, 0], w[64:128, 0], w[128:, 0] = 1.0, 2.0, 3.0
+    vec = torch.ones(N, dtype=torch.float64)
+    o = R.dense16_ref(a, w, None, K=8, dot_vec=vec)
+    assert o["ssq"].shape == (3, 1) and o["ssq"][:, 0].tolist() == [64.0, 256.0, 9.0 * (N - 128)]
+    assert o["rdot"][:, 0].tolist() == [64.0, 128.0, 3.0 * (N - 128)]
+    # one column at a time: column n lands in slice n // 64 and nowhere else
+    for n in (0, 63, 64, 127, 128, N - 1):
+        w1 = torch.zeros(N, 8, dtype=torch.float64)
+        w1[n, 0] = 5.0
+        s = R.dense16_ref(a, w1, None, K=8)["ssq"][:, 0]
+        assert float(s[n // 64]) == 25.0 and float(s.sum()) == 25.0
+    # the planted slice faults do what they say
+    b = torch.zeros(N, dtype=torch.float64)
+    b[N - 1] = 0.5
+    good, pad = R.dense16_ref(a, w, b, K=8), R.dense16_ref(a, w, b, K=8, pad_cols_in_ssq=True)
+    assert float(pad["ssq"][2, 0] - good["ssq"][2, 0]) == (192 - N) * 0.25 and torch.equal(pad["ssq"][:2], good["ssq"][:2])
+    assert R.dense16_ref(a, w, None, K=8, dot_vec=vec, slices_swapped=True)["ssq"][:, 0].tolist() == [256.0, 64.0, 9.0 * (N - 128)]
+
+
+def test_dense16_tn_reference_and_slice_sums():
+    g = torch.Generator().manual_seed(9)
+    a, b = torch.randn(11, 16, dtype=torch.float64, generator=g), torch.randn(11, 24, dtype=torch.float64, generator=g)
+    want = sum(torch.outer(a[k, :8], b[k, :16]) for k in range(11))
+    assert _maxabs(R.dense16_tn_ref(a, b, 8, 16), want) <= 1e-13
+    assert _maxabs(R.dense16_tn_ref(a, b, 8, 16, k_rows=slice(0, 4)), sum(torch.outer(a[k, :8], b[k, :16]) for k in range(4))) <= 1e-13
+    v = torch.arange(2 * 70, dtype=torch.float64).reshape(2, 70)
+    assert R.slice_sums(v).tolist() == [[float(v[0, :64].sum()), float(v[1, :64].sum())], [float(v[0, 64:].sum()), float(v[1, 64:].sum())]]
