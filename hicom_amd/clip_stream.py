@@ -1,0 +1,285 @@
+"""HIComProjector.open_stream: ONE video that arrives in chunks, compressed as it arrives (csrc/clip_stream.hip).
+
+The vision tower runs over a few frames at a time; forward() and every many-item step want the whole [T, H, W, E] pair resident before
+the first launch.  A ClipStream takes the guide up front and the frames in pieces of whole window groups (Tc % kt == 0):
+
+    s = proj.open_stream(guide_embed, H, W, max_frames, image_newline)
+    rows = s.push(frames_feature[Tc, H, W, E], frames_embed or None)      # any number of times; the chunk may be freed afterwards
+    out = s.finish()                                                      # [local rows so far + 32, hidden]
+
+Why it is exact (hicom_amd/dist.py has the same split over GPUs): local windows never straddle a group of kt frames, so a chunk's local rows
+are final when the chunk has been read; the global softmax state (M, L, ACC[rows, E]) of disjoint frame ranges merges exactly when the
+positional terms use absolute frame numbers, and the positional tables are indexed by absolute frame (sized for max_frames at open, so the
+y / x offsets never move); in `direct` mode both stages' queries are the guide, so nothing depends on the final T.
+
+One push is one host call (hicom_compressor_stream_push): the fused ring kernel on the chunk with t_index0 = frames pushed so far, the fold of
+its partials into the carried state (hicom_stream_state_fold_fwd), the two readout GEMMs writing the chunk's rows at their packed offset in the
+stream's output buffer (+ the chunk's `grid` / `frame` newline rows).  finish() runs GlobalCompressor.finish on the carried state as one set
+and does not consume it: more pushes and another finish() give the longer clip's result.
+
+Nothing token-sized is allocated: the output buffer (for max_frames), the state, the query operands and the positional tables at open; the
+per-chunk workspace (partials, the fp16 context and hidden planes of ONE chunk) with the plan, on first use of a chunk length.  Plans are cached
+on the module (`proj._clip_stream_plans`) per (Tc, H, W, E, has frames_embed, newline, out dtype, stream) through segments.cached_plan; the
+frame offset, the row offset and everything that belongs to a stream (queries, tables, state, output) are patched per push, so a stream of
+equal chunks builds one plan and two streams of one module share it.  Everything runs on the caller's current stream.
+
+Scope: that of forward_multi_guide (the plain release recipe, a bf16 module with bf16 CUDA inputs, inference only) on the geometry the fused
+ring kernel takes (H % ks == W % ks == 0, 16 <= kt ks ks <= 64, E == 1152, at most 12 folded rows, hidden % 64 == 0)."""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import native as nv
+from . import segments as seg
+
+STORE = "_clip_stream_plans"
+WHAT = "open_stream"
+
+
+def _require_bf16_cuda(name, t):
+    from .projector import _require_bf16_cuda as check
+    check(name, t)
+
+
+def prefix_layout(proj, groups, gh, gw, has_newline):
+    """(row at which a chunk behind `groups` window groups starts, HIComProjector._layout of that prefix).  The rows of a prefix that depend
+    on the whole clip -- the `one_token` newline row behind the last token: a layout with newline rows but no interleaving -- belong to
+    finish(), so they do not count."""
+    lay = proj._layout((groups, gh, gw), "video", has_newline, False)
+    tail = len(lay.newline_rows) if lay.nl_group == 0 else 0
+    return lay.n_rows - tail, lay
+
+
+def chunk_rows(proj, groups0, groups, gh, gw, has_newline):
+    """Where the chunk of `groups` window groups behind `groups0` lands: (row0, nl_group, its chunk-local newline rows as absolute rows, the
+    row behind it).  All of it from _layout of the two prefixes."""
+    row0, _ = prefix_layout(proj, groups0, gh, gw, has_newline)
+    row1, lay = prefix_layout(proj, groups0 + groups, gh, gw, has_newline)
+    newline = [r for r in lay.newline_rows if row0 <= r < row1] if lay.nl_group else []
+    return row0, lay.nl_group, newline, row1
+
+
+def stream_scope(proj, guide, H, W, max_frames, nl):
+    """Raises for everything outside the scope of a clip stream, in front of any device work; returns (E, kt, ks, hidden, heads)."""
+    if seg.seg_recipe(proj) != "plain":
+        raise NotImplementedError(f"{WHAT} is built for the plain release recipe only (local + global compressor, use_guide='direct', no "
+                                  "adaptors, no clip scale); everything else goes through forward() on the whole clip")
+    lc, gc = proj.local_compressor, proj.global_compressor
+    wdt = lc.readout[0].weight.dtype
+    if wdt != torch.bfloat16:
+        raise NotImplementedError(f"{WHAT}: a {wdt} projector; the clip stream takes a bfloat16 module and bfloat16 inputs")
+    E, hidden, nh = gc.embed_dim, lc.readout[2].out_features, gc.attn_layer.num_heads
+    if not isinstance(guide, torch.Tensor) or tuple(guide.shape) != (E,):
+        raise ValueError(f"{WHAT}: guide_embed is [E] = [{E}], the one instruction of the stream "
+                         f"(got {tuple(guide.shape) if isinstance(guide, torch.Tensor) else None})")
+    if guide.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{WHAT}: guide_embed dtype {guide.dtype}; the clip stream takes bfloat16 inputs")
+    kt, ks = lc.temporal_kernel_size, lc.spatial_kernel_size
+    if E != 1152 or nh > 12 or hidden % 64:
+        raise NotImplementedError(f"{WHAT}: E={E}, {nh} heads, hidden={hidden} (the fused ring kernel takes E == 1152 and <= 12 folded rows, "
+                                  "the fp16 readout planes hidden % 64 == 0)")
+    if not all(isinstance(v, int) and v > 0 for v in (H, W, max_frames)):
+        raise ValueError(f"{WHAT}: H, W and max_frames are positive ints (got {H}, {W}, {max_frames})")
+    if H % ks or W % ks or not 16 <= kt * ks * ks <= 64:
+        raise NotImplementedError(f"{WHAT}: the windows must partition the grid exactly, 16 .. 64 tokens each (H={H} W={W}, windows "
+                                  f"{kt}x{ks}x{ks}); such clips go through forward()")
+    if max_frames % kt:
+        raise ValueError(f"{WHAT}: max_frames={max_frames} (a multiple of the temporal window, {kt} frames)")
+    if nl is not None:
+        if not isinstance(nl, torch.Tensor) or tuple(nl.shape) != (hidden,):
+            raise ValueError(f"{WHAT}: image_newline is [hidden] = [{hidden}]")
+        if nl.dtype != torch.bfloat16:
+            raise NotImplementedError(f"{WHAT}: image_newline dtype {nl.dtype}; the clip stream takes bfloat16 inputs")
+    proj._layout((max_frames // kt, H // ks, W // ks), "video", nl is not None, False)       # (ValueError: a packing that needs image_newline)
+    return E, kt, ks, hidden, nh
+
+
+class StreamPlan:
+    """What one chunk shape needs: the argument block with the module's fields filled and the workspace of ONE chunk."""
+    __slots__ = ("args", "ws", "sig", "fresh", "refresh", "hits", "keep")
+
+    def __init__(self, args, ws, keep, refresh):
+        self.args, self.ws, self.keep, self.refresh = args, ws, keep, refresh
+        self.sig = self.fresh = None
+        self.hits = 0
+
+
+class ClipStream:
+    """The object HIComProjector.open_stream returns (module docstring).  Attributes: `frames` pushed so far, `rows` local rows so far
+    (the whole-clip newline row of `one_token` included once finish() has written it), `out` the output buffer."""
+
+    def __init__(self, proj, guide_embed, H, W, max_frames, image_newline=None):
+        from .projector import _out_dtype, _refuse_grad
+        self.E, self.kt, self.ks, self.hidden, self.nh = stream_scope(proj, guide_embed, H, W, max_frames, image_newline)
+        _refuse_grad(proj, f"HIComProjector.{WHAT}")
+        _require_bf16_cuda("guide_embed", guide_embed)
+        if image_newline is not None:
+            _require_bf16_cuda("image_newline", image_newline)
+        self.proj, self.H, self.W, self.max_frames = proj, H, W, max_frames
+        self.gh, self.gw = H // self.ks, W // self.ks
+        self.newline = None if image_newline is None else image_newline.contiguous()
+        self.device, self.out_dtype = guide_embed.device, _out_dtype(proj)
+        self.has_fe = None                        # decided by the first push; every chunk of a clip agrees
+        self.frames = 0
+        self.n_pushes = 0
+        max_rows = proj._layout((max_frames // self.kt, self.gh, self.gw), "video", image_newline is not None, False).n_rows
+        self.n_global = proj.global_compressor.num_queries
+        self._allocate(max_rows + self.n_global)
+        self._prepare(guide_embed)
+
+    # -- device work: three methods, so that the host logic around them can be exercised without a device ---------------------------------
+    def _allocate(self, rows):
+        dev, E, gc = self.device, self.E, self.proj.global_compressor
+        self.out = torch.empty((rows, self.hidden), dtype=self.out_dtype, device=dev)
+        self.state_ml = torch.empty((2, self.nh, 2), dtype=torch.float32, device=dev)      # (M, L) ping-pong: read one, write the other
+        self.state_acc = torch.empty((1, self.nh, E), dtype=torch.float32, device=dev)
+        self.q_hi = torch.zeros((16, E), dtype=torch.bfloat16, device=dev)
+        self.q_lo = torch.zeros_like(self.q_hi)
+        self.qp_state = nv.query_prep_state(E, dev)
+        self.pos_a = self.pe_hi = self.pe_lo = None
+        self.P = self.y0 = self.x0 = 0
+        if gc.use_pos_emb:
+            # sized for max_frames: the y / x table offsets (cap, cap + H) never move while the stream lives; the stream keeps the tables
+            _, self.kpe, cap = gc.pos_and_kpe(self.max_frames, self.H, self.W, dev)
+            self.pe_hi, self.pe_lo = gc.pos_planes(self.max_frames, self.H, self.W, dev)
+            self.P, self.y0, self.x0 = self.pe_hi.shape[0], cap, cap + self.H
+            self.pos_a = torch.zeros((16, self.P), dtype=torch.float32, device=dev)
+
+    def _prepare(self, guide):
+        """Everything that depends on the guide alone: q_proj, the fold, the score-side positional table and the local query rows in one
+        launch (hicom_query_prep_fwd), and the empty state.  Once per open_stream / reset, not per push."""
+        from .projector import _linear_params
+        gc = self.proj.global_compressor
+        att = gc.attn_layer
+        self.guide = guide.contiguous()
+        wq, bq = _linear_params(att.q_proj)
+        wk, _ = _linear_params(att.k_proj)
+        if gc.use_pos_emb:
+            gc.pos_and_kpe(self.max_frames, self.H, self.W, self.device)                   # (follows k_proj.weight in place)
+        nv.query_prep(self.guide, self.guide, wq, bq, wk, self.kpe if gc.use_pos_emb else None, self.nh, att.scale, self.q_hi, self.q_lo,
+                      self.pos_a, self.qp_state)
+        nv.stream_state_clear(self.state_ml, self.state_acc)
+        self.cur = 0
+
+    def _build_plan(self, Tc, has_fe):
+        from .projector import _linear_params
+        lc = self.proj.local_compressor
+        nw = (Tc // self.kt) * self.gh * self.gw
+        nparts = nv.fused_stream_nparts(nw)
+        E, hidden, dev = self.E, self.hidden, self.device
+
+        def up(n):
+            return (n + 255) // 256 * 256
+        sizes = [up(nparts * 16 * 4), up(nparts * 16 * 4), up(nparts * 16 * E * 4), up(nw * E * 2), up(nw * hidden * 2)]
+        ws = torch.empty((sum(sizes),), dtype=torch.uint8, device=dev)
+        offs = [sum(sizes[:i]) for i in range(len(sizes))]
+        a = nv.StreamPushArgs()
+        a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.rows, a.hidden, a.nparts = Tc, self.H, self.W, E, self.kt, self.ks, self.nh, hidden, nparts
+        a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
+        a.part_m, a.part_l, a.part_acc, a.ctx_f16, a.hid_f16 = (ws.data_ptr() + o for o in offs)
+        w0h, w2h = lc.readout_f16()
+        b0, b2 = _linear_params(lc.readout[0])[1], _linear_params(lc.readout[2])[1]
+        a.lw0_f16, a.lw2_f16, a.lb0, a.lb2 = w0h.data_ptr(), w2h.data_ptr(), b0.data_ptr(), b2.data_ptr()
+        a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
+        a.ldo = hidden
+        return StreamPlan(a, ws, [w0h, w2h, b0, b2], lc.readout_f16)
+
+    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
+        a = plan.args
+        a.ff, a.fe, a.t0 = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), t0
+        a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
+        a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
+        a.pe_hi = self.pe_hi.data_ptr() if self.pe_hi is not None else None
+        a.pe_lo = self.pe_lo.data_ptr() if self.pe_lo is not None else None
+        a.P, a.y_index0, a.x_index0 = self.P, self.y0, self.x0
+        a.state_ml_in, a.state_ml_out = self.state_ml[self.cur].data_ptr(), self.state_ml[self.cur ^ 1].data_ptr()
+        a.state_acc = self.state_acc.data_ptr()
+        a.out, a.row0, a.nl_group = self.out.data_ptr(), row0, nl_group
+        a.nl_count = len(newline_rows)
+        a.newline = self.newline.data_ptr() if newline_rows else None
+        if newline_rows:
+            a.nl_first = newline_rows[0]
+            a.nl_step = newline_rows[1] - newline_rows[0] if len(newline_rows) > 1 else 1
+        a.stream = stream
+        nv.compressor_stream_push(a)
+
+    # -- the public surface ---------------------------------------------------------------------------------------------------------------
+    @property
+    def rows(self):
+        """Local rows of the frames pushed so far, as forward() on them would lay them out."""
+        return self.proj._layout((self.frames // self.kt, self.gh, self.gw), "video", self.newline is not None, False).n_rows
+
+    def _check_chunk(self, ff, fe):
+        from .projector import _refuse_grad
+        what = "ClipStream.push"
+        if isinstance(ff, dict) or isinstance(fe, dict):
+            raise NotImplementedError(f"{what}: anyres dict inputs have no clip-stream path (call forward() per image)")
+        if seg.seg_recipe(self.proj) != "plain" or self.proj.local_compressor.readout[0].weight.dtype != torch.bfloat16:
+            raise NotImplementedError(f"{what}: the module left the scope of {WHAT} (the plain release recipe, bfloat16) since the stream was opened")
+        if not isinstance(ff, torch.Tensor) or ff.ndim != 4:
+            raise ValueError(f"{what}: frames_feature is [Tc, H, W, E]")
+        Tc = ff.shape[0]
+        if tuple(ff.shape[1:]) != (self.H, self.W, self.E):
+            raise ValueError(f"{what}: a chunk of {tuple(ff.shape)}; the stream was opened for [Tc, {self.H}, {self.W}, {self.E}]")
+        if Tc <= 0 or Tc % self.kt:
+            raise ValueError(f"{what}: Tc={Tc} frames; a chunk is a positive number of whole window groups of {self.kt} frames")
+        if self.frames + Tc > self.max_frames:
+            raise ValueError(f"{what}: {self.frames} + {Tc} frames exceed max_frames={self.max_frames} of {WHAT}")
+        for name, t in (("frames_feature", ff), ("frames_embed", fe)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16):
+                raise NotImplementedError(f"{what}: {name} dtype {getattr(t, 'dtype', type(t))}; the clip stream takes bfloat16 tokens")
+        if fe is not None and tuple(fe.shape) != tuple(ff.shape):
+            raise ValueError(f"{what}: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
+        if self.has_fe is not None and (fe is not None) != self.has_fe:
+            raise ValueError(f"{what}: this clip's chunks came {'with' if self.has_fe else 'without'} frames_embed so far")
+        _refuse_grad(self.proj, "ClipStream.push")
+        _require_bf16_cuda("frames_feature", ff)
+        if fe is not None:
+            _require_bf16_cuda("frames_embed", fe)
+        return Tc
+
+    def push(self, frames_feature, frames_embed=None):
+        """The next Tc frames of the clip (bf16 [Tc, H, W, E], Tc a positive multiple of kt; frames_embed None: the keys are
+        frames_feature).  Returns a view of this chunk's local output rows in their final place in the stream's output buffer, complete
+        on the caller's stream; the chunk is not referenced afterwards."""
+        Tc = self._check_chunk(frames_feature, frames_embed)
+        ff = frames_feature.contiguous()
+        fe = frames_embed.contiguous() if frames_embed is not None else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        key = (Tc, self.H, self.W, self.E, fe is not None, None if self.newline is None else tuple(self.newline.shape), self.out_dtype, stream)
+        plan = seg.cached_plan(self.proj, STORE, key, lambda: self._build_plan(Tc, fe is not None))
+        row0, nl_group, newline_rows, row1 = chunk_rows(self.proj, self.frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
+        self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
+        self.cur ^= 1
+        self.has_fe = fe is not None
+        self.frames += Tc
+        self.n_pushes += 1
+        return self.out[row0:row1]
+
+    def finish(self):
+        """[local rows so far + 32, hidden]: the rows that depend on the whole clip (a `one_token` newline row, the global rows) written
+        behind the local rows pushed so far.  A view of the stream's buffer; the state is not consumed."""
+        from .projector import _refuse_grad
+        if self.frames == 0:
+            raise ValueError("ClipStream.finish: nothing has been pushed")
+        _refuse_grad(self.proj, "ClipStream.finish")
+        row0, lay = prefix_layout(self.proj, self.frames // self.kt, self.gh, self.gw, self.newline is not None)
+        if lay.n_rows > row0:                                                              # whole-clip newline rows (`one_token`)
+            nv.scatter_rows(self.newline.view(1, -1), self.out, row0, lay.n_rows - row0)
+        gc = self.proj.global_compressor
+        gc.finish(self.state_ml[self.cur:self.cur + 1], self.state_acc, self.guide.view(1, -1), self.out, lay.n_rows, self.n_global)
+        return self.out[:lay.n_rows + self.n_global]
+
+    def reset(self, guide_embed=None):
+        """A new clip on the same buffers, with the same or a new guide: the query preparation runs again (it follows the weights) and the
+        state is emptied on the caller's stream."""
+        from .projector import _refuse_grad
+        guide = self.guide if guide_embed is None else guide_embed
+        if guide_embed is not None:
+            stream_scope(self.proj, guide, self.H, self.W, self.max_frames, self.newline)
+            _require_bf16_cuda("guide_embed", guide)
+        _refuse_grad(self.proj, "ClipStream.reset")
+        self.frames, self.n_pushes, self.has_fe = 0, 0, None
+        self._prepare(guide)

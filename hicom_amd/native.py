@@ -49,6 +49,7 @@ EXPORTS = (
     "hicom_clip_adapt_prepare_fwd", "hicom_clip_adapt_prepare_workspace_bytes",
     "hicom_compressor_multiguide_adapt_fwd", "hicom_compressor_multiguide_adapt_workspace_bytes",
     "hicom_compressor_clips_multiguide_fwd", "hicom_compressor_clips_multiguide_workspace_bytes", "hicom_compressor_clips_multiguide_prepare",
+    "hicom_stream_state_clear_fwd", "hicom_stream_state_fold_fwd", "hicom_compressor_stream_push",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -240,6 +241,19 @@ class CompressorClipsMultiGuideArgs(C.Structure):
                 ("item_ptrs", C.c_void_p)]
 
 
+class StreamPushArgs(C.Structure):
+    """hicom_stream_push_args (include/hicom_hip.h): one push of a clip stream -- field order and types must match the header."""
+    _fields_ = [("ff", C.c_void_p), ("fe", C.c_void_p), ("Tc", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("E", C.c_int32),
+                ("kt", C.c_int32), ("ks", C.c_int32), ("t0", C.c_int32), ("rows", C.c_int32), ("q_hi", C.c_void_p), ("q_lo", C.c_void_p),
+                ("pos_a", C.c_void_p), ("pe_hi", C.c_void_p), ("pe_lo", C.c_void_p), ("P", C.c_int32), ("y_index0", C.c_int32),
+                ("x_index0", C.c_int32), ("l_scale", C.c_float), ("part_m", C.c_void_p), ("part_l", C.c_void_p), ("part_acc", C.c_void_p),
+                ("ctx_f16", C.c_void_p), ("hid_f16", C.c_void_p), ("nparts", C.c_int32), ("hidden", C.c_int32),
+                ("state_ml_in", C.c_void_p), ("state_ml_out", C.c_void_p), ("state_acc", C.c_void_p), ("lw0_f16", C.c_void_p),
+                ("lb0", C.c_void_p), ("lw2_f16", C.c_void_p), ("lb2", C.c_void_p), ("out", C.c_void_p), ("out_dt", C.c_int32),
+                ("nl_group", C.c_int32), ("ldo", C.c_int64), ("row0", C.c_int64), ("newline", C.c_void_p), ("nl_first", C.c_int64),
+                ("nl_step", C.c_int64), ("nl_count", C.c_int32), ("reserved_", C.c_int32), ("stream", C.c_void_p)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -363,6 +377,9 @@ def lib() -> C.CDLL:
     L.hicom_compressor_clips_multiguide_fwd.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
     L.hicom_compressor_clips_multiguide_prepare.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
     L.hicom_compressor_clips_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
+    L.hicom_stream_state_clear_fwd.argtypes = [vp, i32, vp, i64, vp]
+    L.hicom_stream_state_fold_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.hicom_compressor_stream_push.argtypes = [C.POINTER(StreamPushArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -791,6 +808,24 @@ def compressor_clips_multiguide_prepare(args: CompressorClipsMultiGuideArgs):
 
 def compressor_clips_multiguide_fwd(args: CompressorClipsMultiGuideArgs):
     _seg_call(args, "clips_multiguide", "fwd")
+
+
+def stream_state_clear(state_ml, state_acc, stream=None):
+    """The empty state of a clip stream: (M, L) = (-inf, 0) in every pair of state_ml [..., 2], zeros in state_acc (one launch)."""
+    _check(lib().hicom_stream_state_clear_fwd(_ptr(state_ml), state_ml.numel() // 2, _ptr(state_acc), state_acc.numel(),
+                                              _stream() if stream is None else stream), "hicom_stream_state_clear_fwd")
+
+
+def stream_state_fold(part_m, part_l, part_acc, rows, ml_in, ml_out, acc):
+    """Folds the partials part_m / part_l f32 [nparts, rows_pad], part_acc f32 [nparts, rows_pad, E] into the carried state: (M, L) from
+    ml_in [rows, 2] to ml_out [rows, 2] (two different blocks), acc [rows, E] in place (hicom_stream_state_fold_fwd)."""
+    nparts, rows_pad = part_m.shape
+    _check(lib().hicom_stream_state_fold_fwd(_ptr(part_m), _ptr(part_l), _ptr(part_acc), nparts, rows, rows_pad, part_acc.shape[-1],
+                                             _ptr(ml_in), _ptr(ml_out), _ptr(acc), _stream()), "hicom_stream_state_fold_fwd")
+
+
+def compressor_stream_push(args: StreamPushArgs):
+    _check(lib().hicom_compressor_stream_push(C.byref(args)), "hicom_compressor_stream_push")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

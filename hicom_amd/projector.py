@@ -824,6 +824,7 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_ragged_multi_guide_plans", None)
         self.__dict__.pop("_prepared_plans", None)
         self.__dict__.pop("_prepare_plans", None)
+        self.__dict__.pop("_clip_stream_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1159,6 +1160,27 @@ class HIComProjector(nn.Module):
         Which path when: DESIGN.md §3.11 has the measured table (tools/prepared_many_bench.py)."""
         from . import prepared_many
         return prepared_many.run_prepared_many(self, clips, guide_embeds, guide_counts, image_newline, chunks)
+
+    def open_stream(self, guide_embed, H, W, max_frames, image_newline=None):
+        """ONE video that arrives in chunks, the guide known up front: returns a ClipStream (hicom_amd/clip_stream.py).
+            s = proj.open_stream(guide_embed, H, W, max_frames, image_newline)       # guide_embed bf16 [E]; modal is "video"
+            rows = s.push(frames_feature, frames_embed)   # bf16 [Tc, H, W, E], Tc a positive multiple of the temporal window; frames_embed may
+                                                          # be None; any number of times, sum Tc <= max_frames; returns this chunk's local rows
+            out = s.finish()                              # [local rows so far + 32, hidden], laid out as forward() on the concatenation and equal to
+                                                          # it to the kernels' rounding; does not consume the state: push on, finish again
+            s.reset(guide_embed=None)                     # the same buffers for a new clip (and optionally a new guide)
+        Each chunk is read once, by one host call (the fused ring kernel with the absolute frame offset, the fold of its partials into ONE
+        carried softmax state, the two readout GEMMs), and may be freed when push returns.  open_stream allocates the output buffer for
+        max_frames, the state and the positional tables; a chunk length allocates its partials workspace on first use; push allocates
+        nothing.  Everything runs on the caller's current stream.
+        The plain release recipe only (local + global compressor, use_guide="direct", no adaptors, no clip scale, bf16 module and inputs),
+        H % ks == W % ks == 0, windows of 16 .. 64 tokens, E == 1152, hidden % 64 == 0: everything else raises NotImplementedError /
+        ValueError in front of the first launch, a push past max_frames and finish() on an empty stream included.  Inference only.
+        Which path when (DESIGN.md §3.12, 27 x 27 grid, hidden 896): a push of 8 or 16 frames takes about 150 us (launch-bound), finish() 24 us; 512
+        frames in chunks of 8 take 9.8 ms against 0.51 ms for forward() on the resident clip, with 73 MB of device memory against 3.4 GB.  A
+        clip that is already resident belongs to forward()."""
+        from . import clip_stream
+        return clip_stream.ClipStream(self, guide_embed, H, W, max_frames, image_newline)
 
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):

@@ -1138,6 +1138,70 @@ int64_t hicom_compressor_clips_multiguide_workspace_bytes(const hicom_compressor
 int hicom_compressor_clips_multiguide_prepare(const hicom_compressor_clips_multiguide_args* args);
 int hicom_compressor_clips_multiguide_fwd(const hicom_compressor_clips_multiguide_args* args);
 
+/* ---- clip stream: a video that arrives in chunks of whole window groups, one carried softmax state ----------------
+ * The carried state of the global stage is the un-normalised online-softmax triple of everything pushed so far, in the layout
+ * hicom_global_combine_fwd reads as ONE set:  state_ml f32 [rows][2] = (M, L),  state_acc f32 [rows][E].  Empty: M = -inf, L = 0, ACC = 0
+ * (hicom_stream_state_clear_fwd writes that into ml_rows (M, L) pairs and acc_floats floats: a launch on `stream`).
+ *
+ * hicom_stream_state_fold_fwd folds the `nparts` partials of one chunk, as hicom_fused_stream_fwd writes them with pe_hi / pe_lo given
+ * (part_m, part_l f32 [nparts][rows_pad], part_acc f32 [nparts][rows_pad][E]: the value-side positional term is inside part_acc), into it:
+ *     M' = max(M, max_p m_p)     L' = e^(M - M') L + sum_p e^(m_p - M') l_p     ACC' = e^(M - M') ACC + sum_p e^(m_p - M') acc_p
+ * A term whose max is -inf has weight 0 (no -inf - -inf): from the empty state the result is the merge of the partials alone.  Rows >= rows
+ * of the padded partials are not read.  ACC is updated in place (every element is read and written by one lane).  (M, L) is read by every
+ * workgroup of a row, so it is NOT updated in place: state_ml_in and state_ml_out are two different [rows][2] blocks and the caller swaps
+ * them from push to push.  E % 4 == 0; part_acc and state_acc 16-byte aligned, state_ml_* 8-byte aligned. */
+int hicom_stream_state_clear_fwd(float* state_ml, int32_t ml_rows, float* state_acc, int64_t acc_floats, void* stream);
+int hicom_stream_state_fold_fwd(const float* part_m, const float* part_l, const float* part_acc, int32_t nparts, int32_t rows,
+                                int32_t rows_pad, int32_t E, const float* state_ml_in, float* state_ml_out, float* state_acc, void* stream);
+
+/* One push of a clip stream in ONE host call: hicom_fused_stream_fwd on the chunk (t_index0 = t0, f32 partials, the fp16 context plane),
+ * hicom_stream_state_fold_fwd, the two hicom_readout16_gemm_fwd launches of the local readout writing the chunk's rows at row0 (packed with
+ * nl_group), and -- nl_count > 0 -- the chunk's newline rows (hicom_scatter_rows_fwd).  Nothing is allocated, copied or synchronised.
+ * The block is built once per chunk shape; ff, fe, t0, row0, nl_first, state_ml_in / state_ml_out, out and stream change from push to push.
+ *   ff, fe      : bf16 [Tc, H, W, E] (fe NULL: the keys are frames_feature); Tc % kt == H % ks == W % ks == 0, 16 <= kt ks ks <= 64, E == 1152
+ *   t0          : absolute number of the chunk's first frame: the frame rows of pos_a / pe_hi / pe_lo are read at t0 + t, so the state of
+ *                 disjoint frame ranges merges exactly; t0 + Tc <= y_index0 (the tables' frame capacity), x_index0 + W <= P
+ *   q_hi .. pe_lo, rows, l_scale : hicom_fused_stream_fwd's operands of the same names (guide-only: made once per stream)
+ *   part_*      : the chunk's partials, nparts = hicom_fused_stream_nparts(windows of the chunk); ctx_f16 fp16 [windows, E]; hid_f16 fp16
+ *                 [windows, hidden]
+ *   lw0_f16 .. lb2 : the local readout (fp16 weight copies, bf16 biases); hidden % 64 == 0
+ *   out         : the stream's output buffer (out_dt HICOM_DT_F32 | HICOM_DT_BF16, row length ldo >= hidden)
+ *   newline     : bf16 [hidden], rows nl_first + i nl_step, i < nl_count (absolute rows of `out`), or nl_count = 0 */
+typedef struct hicom_stream_push_args {
+    const void* ff;
+    const void* fe;
+    int32_t Tc, H, W, E, kt, ks;
+    int32_t t0, rows;
+    const void* q_hi;
+    const void* q_lo;
+    const float* pos_a;
+    const void* pe_hi;
+    const void* pe_lo;
+    int32_t P, y_index0, x_index0;
+    float l_scale;
+    float* part_m;
+    float* part_l;
+    float* part_acc;
+    void* ctx_f16;
+    void* hid_f16;
+    int32_t nparts, hidden;
+    const float* state_ml_in;
+    float* state_ml_out;
+    float* state_acc;
+    const void* lw0_f16;
+    const void* lb0;
+    const void* lw2_f16;
+    const void* lb2;
+    void* out;
+    int32_t out_dt, nl_group;
+    int64_t ldo, row0;
+    const void* newline;
+    int64_t nl_first, nl_step;
+    int32_t nl_count, reserved_;
+    void* stream;
+} hicom_stream_push_args;
+int hicom_compressor_stream_push(const hicom_stream_push_args* args);
+
 #ifdef __cplusplus
 }
 #endif
