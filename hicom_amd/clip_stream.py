@@ -24,7 +24,10 @@ frame offset, the row offset and everything that belongs to a stream (queries, t
 equal chunks builds one plan and two streams of one module share it.  Everything runs on the caller's current stream.
 
 Scope: that of forward_multi_guide (the plain release recipe, a bf16 module with bf16 CUDA inputs, inference only) on the geometry the fused
-ring kernel takes (H % ks == W % ks == 0, 16 <= kt ks ks <= 64, E == 1152, at most 12 folded rows, hidden % 64 == 0)."""
+ring kernel takes (H % ks == W % ks == 0, 16 <= kt ks ks <= 64, E == 1152, at most 12 folded rows, hidden % 64 == 0).
+
+HIComProjector.open_stream_multi (ClipStreamMulti, at the end of this file) is the same stream for Q guides known up front:
+every chunk is read once for all of them."""
 from __future__ import annotations
 
 import math
@@ -61,8 +64,9 @@ def chunk_rows(proj, groups0, groups, gh, gw, has_newline):
     return row0, lay.nl_group, newline, row1
 
 
-def stream_scope(proj, guide, H, W, max_frames, nl):
-    """Raises for everything outside the scope of a clip stream, in front of any device work; returns (E, kt, ks, hidden, heads)."""
+def stream_scope(proj, guide, H, W, max_frames, nl, WHAT=WHAT, multi=False):
+    """Raises for everything outside the scope of a clip stream, in front of any device work; returns (E, kt, ks, hidden, heads).  multi: the
+    guide is the [Q, E] block of open_stream_multi (WHAT names the entry in the messages)."""
     if seg.seg_recipe(proj) != "plain":
         raise NotImplementedError(f"{WHAT} is built for the plain release recipe only (local + global compressor, use_guide='direct', no "
                                   "adaptors, no clip scale); everything else goes through forward() on the whole clip")
@@ -71,7 +75,10 @@ def stream_scope(proj, guide, H, W, max_frames, nl):
     if wdt != torch.bfloat16:
         raise NotImplementedError(f"{WHAT}: a {wdt} projector; the clip stream takes a bfloat16 module and bfloat16 inputs")
     E, hidden, nh = gc.embed_dim, lc.readout[2].out_features, gc.attn_layer.num_heads
-    if not isinstance(guide, torch.Tensor) or tuple(guide.shape) != (E,):
+    if multi:
+        from .multi_guide import count_guides
+        count_guides(WHAT, guide, E)
+    elif not isinstance(guide, torch.Tensor) or tuple(guide.shape) != (E,):
         raise ValueError(f"{WHAT}: guide_embed is [E] = [{E}], the one instruction of the stream "
                          f"(got {tuple(guide.shape) if isinstance(guide, torch.Tensor) else None})")
     if guide.dtype != torch.bfloat16:
@@ -109,6 +116,7 @@ class StreamPlan:
 class ClipStream:
     """The object HIComProjector.open_stream returns (module docstring).  Attributes: `frames` pushed so far, `rows` local rows so far
     (the whole-clip newline row of `one_token` included once finish() has written it), `out` the output buffer."""
+    NAME, WHAT = "ClipStream", WHAT                  # what the messages call the object and the entry that opens it
 
     def __init__(self, proj, guide_embed, H, W, max_frames, image_newline=None):
         from .projector import _out_dtype, _refuse_grad
@@ -213,7 +221,7 @@ class ClipStream:
 
     def _check_chunk(self, ff, fe):
         from .projector import _refuse_grad
-        what = "ClipStream.push"
+        what, WHAT = f"{self.NAME}.push", self.WHAT
         if isinstance(ff, dict) or isinstance(fe, dict):
             raise NotImplementedError(f"{what}: anyres dict inputs have no clip-stream path (call forward() per image)")
         if seg.seg_recipe(self.proj) != "plain" or self.proj.local_compressor.readout[0].weight.dtype != torch.bfloat16:
@@ -234,7 +242,7 @@ class ClipStream:
             raise ValueError(f"{what}: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
         if self.has_fe is not None and (fe is not None) != self.has_fe:
             raise ValueError(f"{what}: this clip's chunks came {'with' if self.has_fe else 'without'} frames_embed so far")
-        _refuse_grad(self.proj, "ClipStream.push")
+        _refuse_grad(self.proj, what)
         _require_bf16_cuda("frames_feature", ff)
         if fe is not None:
             _require_bf16_cuda("frames_embed", fe)
@@ -283,3 +291,209 @@ class ClipStream:
         _refuse_grad(self.proj, "ClipStream.reset")
         self.frames, self.n_pushes, self.has_fe = 0, 0, None
         self._prepare(guide)
+
+
+# =================================================================================================================================
+# several guides per stream (HIComProjector.open_stream_multi)
+# =================================================================================================================================
+STORE_MULTI = "_clip_stream_multi_plans"
+MAX_PARTS = 256                                  # token chunks of the many-row global stream (csrc/clip_stream.hip: kMaxStreamParts)
+
+
+def multi_chunk_limits(what, Tc, H, W, use_pos_emb):
+    """The LDS limits of the merge kernels (csrc/merge.hip) applied to ONE chunk of Tc frames, with the largest number of token chunks a plan
+    may choose: NotImplementedError in front of any device work (hicom_compressor_stream_push_multi checks the same with the plan's own)."""
+    if not use_pos_emb:
+        return
+    if H + W > 1024 or not ((H <= 32 and W <= 32) or (H * W + H + 4) * 4 <= 60000):
+        raise NotImplementedError(f"{what}: a {H}x{W} grid: the merge keeps a frame of logits in LDS")
+    if (MAX_PARTS + 2 * Tc + H + W + 64 * (H + W + 2) + 16 * 64 + 4) * 4 > 60000:
+        raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the merge keeps the row's Tc + H + W weights and 64 frames of "
+                                  "marginals in LDS; push shorter chunks")
+
+
+class ClipStreamMulti(ClipStream):
+    """The object HIComProjector.open_stream_multi returns: ONE video that arrives in chunks, Q guides known up front.
+
+        s = proj.open_stream_multi(guide_embeds[Q, E], H, W, max_frames, image_newline)        # 1 <= Q <= 32
+        rows = s.push(frames_feature[Tc, H, W, E], frames_embed or None)     # [Q, chunk rows, hidden]; the chunk may be freed afterwards
+        out = s.finish()                                                     # [Q, local rows so far + 32, hidden]
+
+    out[q] is what forward() gives for the concatenation of everything pushed with guide q (to the kernels' rounding).  finish() does not
+    consume the state.  The output buffer `out` is [Q, cap_rows + 32, hidden] with cap_rows = the local rows of max_frames frames: the
+    views push() and finish() return are STRIDED over q (a row range of every guide's block; `.contiguous()` copies), valid until the rows
+    are written again (reset, or a later finish() for the rows behind the local ones).
+
+    One push is one host call (hicom_compressor_stream_push_multi): the multi-guide local kernel on the chunk's windows, the many-row
+    global stream over the chunk's tokens at the absolute frame offset, its merge into ONE un-normalised set of R = heads x Q rows, the fold
+    of that set into the carried state (hicom_stream_state_fold_set_fwd), the readout GEMM pair over Q x windows rows and the placement.
+    The tokens of a chunk are read once for all Q guides by the local stage and once per 32 folded rows by the global stage.
+
+    Per stream (open and reset): q_proj over the Q guides, the fold into the hi / lo query planes and the score-side positional table (sized
+    for max_frames: the y / x offsets never move), the empty state.  Per plan -- (Q, Tc, H, W, E, has frames_embed, newline, out dtype,
+    stream), cached on the module as `proj._clip_stream_multi_plans` -- the workspace of ONE chunk; push allocates nothing.
+
+    Scope: that of open_stream (plain release recipe, bf16 module and inputs, inference only, exact window partition, E == 1152,
+    hidden % 64 == 0; windows of <= 64 tokens) with 1 <= Q <= 32 and the merge kernels' LDS limits on a chunk (multi_chunk_limits)."""
+    NAME, WHAT = "ClipStreamMulti", "open_stream_multi"
+
+    def __init__(self, proj, guide_embeds, H, W, max_frames, image_newline=None):
+        from .projector import _out_dtype, _refuse_grad
+        self.E, self.kt, self.ks, self.hidden, self.nh = stream_scope(proj, guide_embeds, H, W, max_frames, image_newline, self.WHAT, True)
+        multi_chunk_limits(self.WHAT, self.kt, H, W, proj.global_compressor.use_pos_emb)      # (the shortest chunk must fit)
+        _refuse_grad(proj, f"HIComProjector.{self.WHAT}")
+        _require_bf16_cuda("guide_embeds", guide_embeds)
+        if image_newline is not None:
+            _require_bf16_cuda("image_newline", image_newline)
+        self.proj, self.H, self.W, self.max_frames = proj, H, W, max_frames
+        self.Q = guide_embeds.shape[0]
+        self.R = self.Q * self.nh                                            # folded rows: guide q's heads are rows nh q .. nh q + nh - 1
+        self.rows_pad = (self.R + 31) // 32 * 32                             # whole 32-row passes of the many-row stream kernel
+        self.gh, self.gw = H // self.ks, W // self.ks
+        self.newline = None if image_newline is None else image_newline.contiguous()
+        self.device, self.out_dtype = guide_embeds.device, _out_dtype(proj)
+        self.has_fe = None
+        self.frames = 0
+        self.n_pushes = 0
+        self.cap_rows = proj._layout((max_frames // self.kt, self.gh, self.gw), "video", image_newline is not None, False).n_rows
+        self.n_global = proj.global_compressor.num_queries
+        self._allocate(self.cap_rows + self.n_global)
+        self._prepare(guide_embeds)
+
+    # -- device work ------------------------------------------------------------------------------------------------------------------------
+    def _allocate(self, rows):
+        dev, E, Q, R, RP, gc = self.device, self.E, self.Q, self.R, self.rows_pad, self.proj.global_compressor
+
+        def f32(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        self.out = torch.empty((Q, rows, self.hidden), dtype=self.out_dtype, device=dev)
+        self.state_ml = f32(2, R, 2)                                         # (M, L) ping-pong: read one block, write the other
+        self.state_acc = f32(1, R, E)
+        self.qp = f32(Q, E)
+        self.q_hi = torch.zeros((RP, E), dtype=torch.bfloat16, device=dev)   # rows >= R stay zero (the fold does not write them)
+        self.q_lo = torch.zeros_like(self.q_hi)
+        # finish(): the combined contexts and the global tail with M = Q
+        self.fin = (f32(R, E), f32(Q, E), f32(Q, E), f32(Q, gc.readout[0].out_features), f32(Q, gc.readout[2].out_features))
+        self.pos_a = self.pe = self.kpe = None
+        self.P = self.y0 = self.x0 = 0
+        if gc.use_pos_emb:
+            # sized for max_frames: the y / x table offsets (cap, cap + H) never move while the stream lives; the stream keeps the tables
+            self.pe, self.kpe, cap = gc.pos_and_kpe(self.max_frames, self.H, self.W, dev)
+            self.P, self.y0, self.x0 = self.pe.shape[0], cap, cap + self.H
+            self.pos_a = torch.zeros((RP, self.P), dtype=torch.float32, device=dev)
+
+    def _prepare(self, guides):
+        """Everything that depends on the guides alone: q_proj with M = Q, the fold into the query planes and the score-side positional
+        table, the empty state.  Once per open_stream_multi / reset, not per push."""
+        from .projector import _linear_params
+        gc = self.proj.global_compressor
+        att = gc.attn_layer
+        self.guides = guides.contiguous()
+        wq, bq = _linear_params(att.q_proj)
+        wk, _ = _linear_params(att.k_proj)
+        if gc.use_pos_emb:
+            gc.pos_and_kpe(self.max_frames, self.H, self.W, self.device)                   # (follows k_proj.weight in place)
+        nv.linear(self.guides, wq, bq, self.qp)
+        nv.fold_query_split(self.qp, wk, self.kpe, self.nh, att.scale, self.q_hi, self.q_lo, self.pos_a)
+        nv.stream_state_clear(self.state_ml, self.state_acc)
+        self.cur = 0
+
+    def _build_plan(self, Tc, has_fe):
+        from .projector import _linear_params
+        lc, gc = self.proj.local_compressor, self.proj.global_compressor
+        E, hidden, dev, H, W, Q, R, RP = self.E, self.hidden, self.device, self.H, self.W, self.Q, self.R, self.rows_pad
+        nw = (Tc // self.kt) * self.gh * self.gw
+        N = Tc * H * W
+        ntiles = (N + 15) // 16
+        nparts = max(1, min(nv.global_stream_nparts(N, RP), ntiles, MAX_PARTS))
+        marg = bool(gc.use_pos_emb) and nv.global_stream_has_marg(N, E, RP, H, W, nparts)      # the form, once per plan
+        stride = ntiles * 16
+        odt = 4 if self.out_dtype == torch.float32 else 2
+
+        def up(n):
+            return (n + 255) // 256 * 256
+        scores = max(RP * stride, nparts * RP * nv.global_stream_marg_width(H, W))
+        sizes = [up(nparts * RP * 4), up(nparts * RP * 4), up(nparts * RP * E * 4), up(scores * 4), up(RP * Tc * (H + W + 2) * 4), up(R * 2 * 4),
+                 up(R * E * 4), up(Q * nw * E * 2), up(Q * nw * hidden * 2), up(Q * nw * hidden * odt)]
+        ws = torch.empty((sum(sizes),), dtype=torch.uint8, device=dev)
+        offs = [sum(sizes[:i]) for i in range(len(sizes))]
+        a = nv.StreamPushMultiArgs()
+        a.Q, a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.nparts = Q, Tc, H, W, E, self.kt, self.ks, self.nh, hidden, nparts
+        a.marg, a.score_stride = int(marg), stride
+        a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
+        (a.part_m, a.part_l, a.part_acc, a.scores, a.scratch, a.set_ml, a.set_acc, a.ctx_f16, a.hid_f16, a.loc) = (ws.data_ptr() + o for o in offs)
+        w0h, w2h = lc.readout_f16()
+        b0, b2 = _linear_params(lc.readout[0])[1], _linear_params(lc.readout[2])[1]
+        a.lw0_f16, a.lw2_f16, a.lb0, a.lb2 = w0h.data_ptr(), w2h.data_ptr(), b0.data_ptr(), b2.data_ptr()
+        a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
+        a.ldo = hidden
+        return StreamPlan(a, ws, [w0h, w2h, b0, b2], lc.readout_f16)
+
+    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
+        a = plan.args
+        a.ff, a.fe, a.guide, a.t0 = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr(), t0
+        a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
+        a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
+        a.pe = self.pe.data_ptr() if self.pe is not None else None
+        a.P, a.y_index0, a.x_index0 = self.P, self.y0, self.x0
+        a.state_ml_in, a.state_ml_out = self.state_ml[self.cur].data_ptr(), self.state_ml[self.cur ^ 1].data_ptr()
+        a.state_acc = self.state_acc.data_ptr()
+        a.out, a.row0, a.nl_group, a.q_stride = self.out.data_ptr(), row0, nl_group, self.out.stride(0)
+        a.nl_count = len(newline_rows)
+        a.newline = self.newline.data_ptr() if newline_rows else None
+        a.nl_first, a.nl_step = 0, 1
+        if newline_rows:
+            a.nl_first = newline_rows[0]
+            a.nl_step = newline_rows[1] - newline_rows[0] if len(newline_rows) > 1 else nl_group + 1
+        a.stream = stream
+        nv.compressor_stream_push_multi(a)
+
+    def _finish_device(self, row0, tail):
+        self.proj.global_compressor.finish_guides(self.state_ml[self.cur:self.cur + 1], self.state_acc, self.guides, self.fin)
+        nv.stream_place_global(self.fin[4], self.newline, tail, self.n_global, self.out, row0)
+
+    # -- the public surface ---------------------------------------------------------------------------------------------------------------
+    def push(self, frames_feature, frames_embed=None):
+        """The next Tc frames of the clip (bf16 [Tc, H, W, E], Tc a positive multiple of kt; frames_embed None: the keys are
+        frames_feature).  Returns the view [Q, chunk rows, hidden] of this chunk's local output rows in their final place in the stream's
+        output buffer (strided over q), complete on the caller's stream; the chunk is not referenced afterwards."""
+        Tc = self._check_chunk(frames_feature, frames_embed)
+        multi_chunk_limits(f"{self.NAME}.push", Tc, self.H, self.W, self.proj.global_compressor.use_pos_emb)
+        ff = frames_feature.contiguous()
+        fe = frames_embed.contiguous() if frames_embed is not None else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        key = (self.Q, Tc, self.H, self.W, self.E, fe is not None, None if self.newline is None else tuple(self.newline.shape), self.out_dtype,
+               stream)
+        plan = seg.cached_plan(self.proj, STORE_MULTI, key, lambda: self._build_plan(Tc, fe is not None))
+        row0, nl_group, newline_rows, row1 = chunk_rows(self.proj, self.frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
+        self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
+        self.cur ^= 1
+        self.has_fe = fe is not None
+        self.frames += Tc
+        self.n_pushes += 1
+        return self.out[:, row0:row1]
+
+    def finish(self):
+        """[Q, local rows so far + 32, hidden]: the rows that depend on the whole clip (a `one_token` newline row, the 32 global rows of every
+        guide) written behind the local rows pushed so far.  A view of the stream's buffer, strided over q; the state is not consumed."""
+        from .projector import _refuse_grad
+        if self.frames == 0:
+            raise ValueError(f"{self.NAME}.finish: nothing has been pushed")
+        _refuse_grad(self.proj, f"{self.NAME}.finish")
+        row0, lay = prefix_layout(self.proj, self.frames // self.kt, self.gh, self.gw, self.newline is not None)
+        self._finish_device(row0, lay.n_rows - row0)
+        return self.out[:, :lay.n_rows + self.n_global]
+
+    def reset(self, guides=None):
+        """A new clip on the same buffers, with the same or Q new guides (another Q: ValueError -- open another stream): the query
+        preparation runs again (it follows the weights) and the state is emptied on the caller's stream."""
+        from .projector import _refuse_grad
+        new = self.guides if guides is None else guides
+        if guides is not None:
+            stream_scope(self.proj, new, self.H, self.W, self.max_frames, self.newline, self.WHAT, True)
+            if new.shape[0] != self.Q:
+                raise ValueError(f"{self.NAME}.reset: {new.shape[0]} guides on a stream opened for Q={self.Q} (the buffers are sized by Q)")
+            _require_bf16_cuda("guide_embeds", new)
+        _refuse_grad(self.proj, f"{self.NAME}.reset")
+        self.frames, self.n_pushes, self.has_fe = 0, 0, None
+        self._prepare(new)

@@ -73,6 +73,13 @@ constexpr int kMaxStreamChunks = 256;
 
 typedef hicom_compressor_multiguide_args Args;
 
+// the plain local stage: one wave per window, four windows per workgroup (the step's launch 3 and hicom_multi_guide_local_fwd)
+void launch_local_plain(const uint16_t* key, const uint16_t* value, const uint16_t* guide, hicom_axis at, hicom_axis ay, hicom_axis ax, int Q, int nwin,
+                        float scale, _Float16* ctx16, void* stream) {
+    HICOM_LAUNCH(multi_guide_local_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, (hipStream_t)stream, key, value, guide, at, ay, ax, Q, nwin,
+                 scale, ctx16);
+}
+
 // token chunks of the global stream
 int mg_chunks(const Args* a, long N, int rows_pad) {
     const long ntiles = (N + 15) / 16;
@@ -146,8 +153,8 @@ struct GuideItems {
             HICOM_LAUNCH(multi_guide_local_adapt_kernel<3>, dim3((unsigned)((l.wpi + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x,
                          (const uint16_t*)a->ff, (const uint16_t*)a->guide, *prepared, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
         else
-            HICOM_LAUNCH(multi_guide_local_kernel<3>, dim3((unsigned)((l.wpi + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x, (const uint16_t*)a->ff,
-                         (const uint16_t*)a->guide, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
+            launch_local_plain(key_x, (const uint16_t*)a->ff, (const uint16_t*)a->guide, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16),
+                               a->stream);
         return seg_check_launch(kWho, "local stage");
     }
 
@@ -218,6 +225,25 @@ int prepare_check(int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom
 }
 
 }  // namespace
+
+// The local stage alone, for a caller that runs the other stages itself (clip_stream.hip: a chunk of a streamed clip; windows do not
+// depend on the frame offset).  Checks everything in front of the launch.
+extern "C" int hicom_multi_guide_local_fwd(const void* key, const void* value, const void* guide, int32_t Q, int32_t T, int32_t H, int32_t W, int32_t E,
+                                           int32_t kt, int32_t ks, float scale, void* ctx_f16, void* stream) {
+    HICOM_REQUIRE(key && value && guide && ctx_f16, HICOM_EINVAL, "multi_guide_local: NULL pointer");
+    HICOM_REQUIRE(Q >= 1 && Q <= kMaxGuides, HICOM_EUNSUP, "multi_guide_local: Q=%d guides (1 <= Q <= %d per call)", Q, kMaxGuides);
+    HICOM_REQUIRE(T > 0 && H > 0 && W > 0 && kt > 0 && ks > 0, HICOM_EINVAL, "multi_guide_local: bad shape");
+    HICOM_REQUIRE(E == 1152, HICOM_EUNSUP, "multi_guide_local: E=%d (only 1152)", E);
+    HICOM_REQUIRE(T % kt == 0 && H % ks == 0 && W % ks == 0 && kt * ks * ks <= 64, HICOM_EUNSUP,
+                  "multi_guide_local: needs an exact partition into windows of <= 64 tokens (T=%d H=%d W=%d, windows %dx%dx%d)", T, H, W, kt, ks, ks);
+    const long nwin = (long)(T / kt) * (H / ks) * (W / ks);
+    HICOM_REQUIRE((long)T * H * W < (1L << 31) / 16 && nwin * Q < (1L << 31) / 16, HICOM_EUNSUP, "multi_guide_local: too many tokens in one call");
+    HICOM_REQUIRE((uintptr_t)key % 16 == 0 && (uintptr_t)value % 16 == 0 && (uintptr_t)guide % 16 == 0 && (uintptr_t)ctx_f16 % 16 == 0, HICOM_EINVAL,
+                  "multi_guide_local: 16-byte aligned inputs");
+    const hicom_axis at{T, kt, T / kt, T / kt}, ay{H, ks, H / ks, H / ks}, ax{W, ks, W / ks, W / ks};
+    launch_local_plain((const uint16_t*)key, (const uint16_t*)value, (const uint16_t*)guide, at, ay, ax, Q, (int)nwin, scale, (_Float16*)ctx_f16, stream);
+    return seg_check_launch("multi_guide_local", "local stage");
+}
 
 extern "C" int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compressor_multiguide_args* a) {
     const int st = mg_check(a);

@@ -50,6 +50,7 @@ EXPORTS = (
     "hicom_compressor_multiguide_adapt_fwd", "hicom_compressor_multiguide_adapt_workspace_bytes",
     "hicom_compressor_clips_multiguide_fwd", "hicom_compressor_clips_multiguide_workspace_bytes", "hicom_compressor_clips_multiguide_prepare",
     "hicom_stream_state_clear_fwd", "hicom_stream_state_fold_fwd", "hicom_compressor_stream_push",
+    "hicom_stream_state_fold_set_fwd", "hicom_multi_guide_local_fwd", "hicom_stream_place_rows_fwd", "hicom_compressor_stream_push_multi",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -254,6 +255,21 @@ class StreamPushArgs(C.Structure):
                 ("nl_step", C.c_int64), ("nl_count", C.c_int32), ("reserved_", C.c_int32), ("stream", C.c_void_p)]
 
 
+class StreamPushMultiArgs(C.Structure):
+    """hicom_stream_push_multi_args (include/hicom_hip.h): one push of a multi-guide clip stream -- field order and types must match the header."""
+    _fields_ = [("ff", C.c_void_p), ("fe", C.c_void_p), ("guide", C.c_void_p), ("Q", C.c_int32), ("Tc", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("E", C.c_int32), ("kt", C.c_int32), ("ks", C.c_int32), ("nh", C.c_int32), ("t0", C.c_int32),
+                ("marg", C.c_int32), ("q_hi", C.c_void_p), ("q_lo", C.c_void_p), ("pos_a", C.c_void_p), ("pe", C.c_void_p), ("P", C.c_int32),
+                ("y_index0", C.c_int32), ("x_index0", C.c_int32), ("l_scale", C.c_float), ("part_m", C.c_void_p), ("part_l", C.c_void_p),
+                ("part_acc", C.c_void_p), ("scores", C.c_void_p), ("scratch", C.c_void_p), ("set_ml", C.c_void_p), ("set_acc", C.c_void_p),
+                ("ctx_f16", C.c_void_p), ("hid_f16", C.c_void_p), ("loc", C.c_void_p), ("nparts", C.c_int32), ("hidden", C.c_int32),
+                ("score_stride", C.c_int64), ("state_ml_in", C.c_void_p), ("state_ml_out", C.c_void_p), ("state_acc", C.c_void_p),
+                ("lw0_f16", C.c_void_p), ("lb0", C.c_void_p), ("lw2_f16", C.c_void_p), ("lb2", C.c_void_p), ("out", C.c_void_p),
+                ("out_dt", C.c_int32), ("nl_group", C.c_int32), ("ldo", C.c_int64), ("q_stride", C.c_int64), ("row0", C.c_int64),
+                ("newline", C.c_void_p), ("nl_first", C.c_int64), ("nl_step", C.c_int64), ("nl_count", C.c_int32), ("reserved_", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -380,6 +396,10 @@ def lib() -> C.CDLL:
     L.hicom_stream_state_clear_fwd.argtypes = [vp, i32, vp, i64, vp]
     L.hicom_stream_state_fold_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.hicom_compressor_stream_push.argtypes = [C.POINTER(StreamPushArgs)]
+    L.hicom_stream_state_fold_set_fwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    L.hicom_multi_guide_local_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]
+    L.hicom_stream_place_rows_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp, i32, i64, i64, i64, vp]
+    L.hicom_compressor_stream_push_multi.argtypes = [C.POINTER(StreamPushMultiArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -826,6 +846,27 @@ def stream_state_fold(part_m, part_l, part_acc, rows, ml_in, ml_out, acc):
 
 def compressor_stream_push(args: StreamPushArgs):
     _check(lib().hicom_compressor_stream_push(C.byref(args)), "hicom_compressor_stream_push")
+
+
+def stream_state_fold_set(set_ml, set_acc, ml_in, ml_out, acc, rows=None):
+    """Folds ONE un-normalised set (set_ml [rows, 2] = interleaved (M, L), set_acc [rows, E]: a merge with normalize = 0) into the carried
+    state: (M, L) from ml_in to ml_out (two different blocks), acc in place (hicom_stream_state_fold_set_fwd)."""
+    _check(lib().hicom_stream_state_fold_set_fwd(_ptr(set_ml), _ptr(set_acc), set_acc.shape[0] if rows is None else rows, set_acc.shape[-1],
+                                                 _ptr(ml_in), _ptr(ml_out), _ptr(acc), _stream()), "hicom_stream_state_fold_set_fwd")
+
+
+def stream_place_global(tok, newline, tail_newline, n_rows, out, row0):
+    """finish() of a multi-guide clip stream: behind guide q's local rows (out [Q, rows, hidden], at row0) the whole-clip newline rows
+    (tail_newline: 0 or 1) and n_rows copies of its global row tok[q] (f32 [Q, hidden]) (hicom_stream_place_rows_fwd)."""
+    Q, cap, hidden = out.shape
+    rows = tail_newline + n_rows
+    _check(lib().hicom_stream_place_rows_fwd(None, _ptr(tok), _ptr(newline) if tail_newline else None, Q, 0, hidden, 0, tail_newline, 0, 1, rows,
+                                             tail_newline, _ptr(out), _dt(out), hidden, cap * hidden, row0, _stream()),
+           "hicom_stream_place_rows_fwd")
+
+
+def compressor_stream_push_multi(args: StreamPushMultiArgs):
+    _check(lib().hicom_compressor_stream_push_multi(C.byref(args)), "hicom_compressor_stream_push_multi")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -771,6 +771,25 @@ class GlobalCompressor(_TrackedWeights, nn.Module):
         nv.linear(hid, w2, b2, tok)
         nv.scatter_rows(tok, out, row0, n_rows)
 
+    def finish_guides(self, ml_set, acc_set, guides, work):
+        """finish() for Q guides whose folded rows lie in ONE un-normalised set (a multi-guide clip stream, clip_stream.ClipStreamMulti):
+        ml_set [1, R, 2], acc_set [1, R, E] with R = heads x Q, guide q's heads in rows heads q .. ; guides bf16 [Q, E].  The combine over
+        the set as it is, then the global tail with M = Q (v_proj per head, out_proj + the guide as residual, the readout): four
+        hicom_linear_fwd.  work = (ctx [R, E], o [Q, E], pre [Q, E], hid [Q, .], tok [Q, hidden]) f32, the caller's; the global rows
+        are left in tok (one per guide) for the caller to place."""
+        att = self.attn_layer
+        ctx, o, pre, hid, tok = work
+        nv.global_combine(ml_set, acc_set, ctx)
+        wv, bv = _linear_params(att.v_proj)
+        wo, bo = _linear_params(att.out_proj)
+        nv.linear(ctx, wv, bv, o, head_rows=att.num_heads, head_dim=att.head_dim)
+        nv.linear(o, wo, bo, pre, res=guides)                              # (the bf16 guide as the residual, ref :646)
+        w0, b0 = _linear_params(self.readout[0])
+        w2, b2 = _linear_params(self.readout[2])
+        nv.linear(pre, w0, b0, hid, act=nv.ACT_GELU)
+        nv.linear(hid, w2, b2, tok)
+        return tok
+
     def forward_into(self, frames_feature, guide_embed, logit_scale, out, row0: int, logit_bias=None):
         self._check_native(logit_scale)
         q_in, n_rows = self.injected_queries(guide_embed)
@@ -825,6 +844,7 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_prepared_plans", None)
         self.__dict__.pop("_prepare_plans", None)
         self.__dict__.pop("_clip_stream_plans", None)
+        self.__dict__.pop("_clip_stream_multi_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1181,6 +1201,26 @@ class HIComProjector(nn.Module):
         clip that is already resident belongs to forward()."""
         from . import clip_stream
         return clip_stream.ClipStream(self, guide_embed, H, W, max_frames, image_newline)
+
+    def open_stream_multi(self, guide_embeds, H, W, max_frames, image_newline=None):
+        """ONE video that arrives in chunks, Q guides known up front -- the questions of a Video-MME style loop about a streamed video:
+        returns a ClipStreamMulti (hicom_amd/clip_stream.py).
+            s = proj.open_stream_multi(guide_embeds, H, W, max_frames, image_newline)    # guide_embeds bf16 [Q, E], 1 <= Q <= 32
+            rows = s.push(frames_feature, frames_embed)   # as ClipStream.push; returns the view [Q, chunk rows, hidden] of this chunk's local rows
+            out = s.finish()                              # [Q, local rows so far + 32, hidden]; out[q] is laid out as forward() on the
+                                                          # concatenation with guide q and equals it to the kernels' rounding; the state is not consumed
+            s.reset(guide_embeds=None)                    # the same buffers for a new clip (and optionally Q new guides; another Q raises ValueError)
+        The output buffer is [Q, rows of max_frames + 32, hidden]: the returned views are STRIDED over q.  Each chunk is read by one host
+        call (hicom_compressor_stream_push_multi: the multi-guide local kernel, the many-row global stream at the absolute frame offset and
+        its merge into one un-normalised set of heads x Q rows, the fold of the set into the carried state, the readout GEMM pair over Q x
+        windows rows, the placement: eight launches whatever Q is) and may be freed when push returns.  open_stream_multi allocates the output
+        buffer, the state, the query planes and the positional tables; a chunk length its workspace on first use; push and finish nothing.
+        The scope of open_stream with 1 <= Q <= 32 and the merge kernels' LDS limits on a chunk; everything else raises NotImplementedError /
+        ValueError in front of the first launch.  Inference only.
+        Which path when (DESIGN.md §3.13, 27 x 27 grid, hidden 896, chunks of 8 frames): a push takes 115 / 122 / 194 / 353 us at Q = 1 / 3 / 6 /
+        16 against 149 / 441 / 880 / 2331 us for Q single-guide streams pushed one after the other; finish() 23 .. 38 us.  It wins from Q = 1."""
+        from . import clip_stream
+        return clip_stream.ClipStreamMulti(self, guide_embeds, H, W, max_frames, image_newline)
 
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):

@@ -1202,6 +1202,97 @@ typedef struct hicom_stream_push_args {
 } hicom_stream_push_args;
 int hicom_compressor_stream_push(const hicom_stream_push_args* args);
 
+/* ---- clip stream for several instructions: one chunked video, Q guides ---------------------------------------------
+ * The carried state is ONE un-normalised set of R = nh Q rows (guide q's heads are rows nh q .. nh q + nh - 1, as the multi-guide step
+ * packs them), state_ml f32 [R][2], state_acc f32 [R][E]: what hicom_global_combine_fwd reads as one set.
+ *
+ * hicom_stream_state_fold_set_fwd folds ONE un-normalised set as hicom_global_merge_fwd / hicom_global_merge_marg_fwd write it with
+ * normalize = 0 (set_ml f32 [rows][2] = interleaved (M, L), set_acc f32 [rows][E]) into the carried state, with the arithmetic of
+ * hicom_stream_state_fold_fwd (one kernel body): an empty term weighs 0 by test, expf, ACC in place, (M, L) from state_ml_in to
+ * state_ml_out (two blocks that must not overlap).  From the empty state the result is the set.  Any row count (288 = 9 heads x 32 guides).
+ * E % 4 == 0; set_acc and state_acc 16-byte aligned, set_ml and state_ml_* 8-byte aligned. */
+int hicom_stream_state_fold_set_fwd(const float* set_ml, const float* set_acc, int32_t rows, int32_t E, const float* state_ml_in,
+                                    float* state_ml_out, float* state_acc, void* stream);
+
+/* The local stage of the multi-guide step alone (multi_guide.hip's kernel: one wave per window, every row of the window loaded once per
+ * group of guides): key / value bf16 [T, H, W, E] (E == 1152), guide bf16 [Q, E], fp16 contexts ctx_f16 [Q][windows][E], window order
+ * (t1, h1, w1).  Exact window partition, kt ks ks <= 64 tokens, 1 <= Q <= 32.  Windows do not depend on a frame offset. */
+int hicom_multi_guide_local_fwd(const void* key, const void* value, const void* guide, int32_t Q, int32_t T, int32_t H, int32_t W, int32_t E,
+                                int32_t kt, int32_t ks, float scale, void* ctx_f16, void* stream);
+
+/* Placement of `rows` packed rows per guide into a [Q][.][ldo] output whose guides lie q_stride ELEMENTS apart (byte work; the row body is
+ * that of every many-item step): out[q][row0 + r], r < rows, is
+ *   r >= global_row0                      : tok[q] (f32 [Q][hidden], rounded once) -- the global rows of finish();
+ *   r = nl_first + i nl_step, i < nl_count: newline (bf16 [hidden]); nl_first is relative to row0;
+ *   otherwise                             : row q windows + m of loc ([Q][windows][hidden], the output dtype), m = r - r / (nl_group + 1)
+ *                                           (nl_group = 0: m = r).
+ * A push places a chunk (global_row0 = rows = windows + nl_count, tok NULL); finish() the rows behind the local rows (loc NULL, windows = 0,
+ * global_row0 = nl_count = the whole-clip newline rows, 0 or 1).  Grid Q x rows. */
+int hicom_stream_place_rows_fwd(const void* loc, const float* tok, const void* newline, int32_t Q, int32_t windows, int32_t hidden,
+                                int32_t nl_group, int32_t nl_count, int64_t nl_first, int64_t nl_step, int64_t rows, int64_t global_row0,
+                                void* out, int32_t out_dt, int64_t ldo, int64_t q_stride, int64_t row0, void* stream);
+
+/* One push of a multi-guide clip stream in ONE host call, eight launches (nine in the logit-tensor form): hicom_multi_guide_local_fwd on the
+ * chunk; the many-row global stream over the chunk's tokens with t_index0 = t0 (hicom_global_stream_marg_fwd when marg != 0, else
+ * hicom_global_stream_fwd) and its merge (hicom_global_merge_marg_fwd / hicom_global_merge_fwd) with normalize = 0 and t_index0 = t0 into
+ * (set_ml, set_acc); hicom_stream_state_fold_set_fwd; the two hicom_readout16_gemm_fwd launches over M = Q x windows rows into `loc`;
+ * hicom_stream_place_rows_fwd.  Every shape, pointer, alignment and table bound is checked in front of the first launch.  Nothing is
+ * allocated, copied or synchronised.  The block is built once per (Q, chunk shape); ff, fe, guide, t0, row0, nl_first, the stream's
+ * operands (q_hi .. pe, P, y_index0, x_index0, state_*, out, q_stride, newline) and stream change from push to push.
+ *   ff, fe     : bf16 [Tc, H, W, E] (fe NULL: the keys are frames_feature); Tc % kt == H % ks == W % ks == 0, kt ks ks <= 64, E == 1152
+ *   guide      : bf16 [Q, E], 1 <= Q <= 32: the local queries;  nh heads: rows = nh Q folded rows, rows_pad = rows rounded up to 32
+ *   q_hi, q_lo : bf16 [rows_pad, E] (hicom_fold_query_split_fwd over the Q guides; rows >= rows zero); pos_a f32 [rows_pad, P] or NULL
+ *   pe         : f32 [P, E], the table the merge reads, NULL iff pos_a is NULL; frames at t0 + t: t0 + Tc <= y_index0, y_index0 + H <=
+ *                x_index0, x_index0 + W <= P
+ *   marg       : the form, chosen once per plan: 1 needs pe and hicom_global_stream_has_marg(Tc H W, E, rows_pad, H, W, nparts) == 1
+ *   part_*     : the chunk's partials [nparts][rows_pad] / [nparts][rows_pad][E], 1 <= nparts <= min(tiles of 16 tokens, 256)
+ *   scores     : marg: f32 [nparts][rows_pad][hicom_global_stream_marg_width(H, W)]; else the logits f32 [rows_pad][score_stride],
+ *                score_stride >= Tc H W rounded up to 16 and % 4 == 0.  16-byte aligned
+ *   scratch    : f32 [rows_pad Tc (H + W + 2)] (pe given); set_ml f32 [rows][2], set_acc f32 [rows][E]
+ *   ctx_f16    : fp16 [Q windows, E]; hid_f16 fp16 [Q windows, hidden]; loc [Q windows, hidden] of the output dtype; hidden % 64 == 0
+ *   out        : guide q's rows start q_stride elements apart, row length ldo >= hidden; the chunk's rows go to rows row0 .. of each guide;
+ *                nl_first: ABSOLUTE row of the chunk's first newline row (>= row0), as in hicom_stream_push_args */
+typedef struct hicom_stream_push_multi_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t Q, Tc, H, W, E, kt, ks, nh;
+    int32_t t0, marg;
+    const void* q_hi;
+    const void* q_lo;
+    const float* pos_a;
+    const float* pe;
+    int32_t P, y_index0, x_index0;
+    float l_scale;
+    float* part_m;
+    float* part_l;
+    float* part_acc;
+    float* scores;
+    float* scratch;
+    float* set_ml;
+    float* set_acc;
+    void* ctx_f16;
+    void* hid_f16;
+    void* loc;
+    int32_t nparts, hidden;
+    int64_t score_stride;
+    const float* state_ml_in;
+    float* state_ml_out;
+    float* state_acc;
+    const void* lw0_f16;
+    const void* lb0;
+    const void* lw2_f16;
+    const void* lb2;
+    void* out;
+    int32_t out_dt, nl_group;
+    int64_t ldo, q_stride, row0;
+    const void* newline;
+    int64_t nl_first, nl_step;
+    int32_t nl_count, reserved_;
+    void* stream;
+} hicom_stream_push_multi_args;
+int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_args* args);
+
 #ifdef __cplusplus
 }
 #endif
