@@ -26,8 +26,9 @@ equal chunks builds one plan and two streams of one module share it.  Everything
 Scope: that of forward_multi_guide (the plain release recipe, a bf16 module with bf16 CUDA inputs, inference only) on the geometry the fused
 ring kernel takes (H % ks == W % ks == 0, 16 <= kt ks ks <= 64, E == 1152, at most 12 folded rows, hidden % 64 == 0).
 
-HIComProjector.open_stream_multi (ClipStreamMulti, at the end of this file) is the same stream for Q guides known up front:
-every chunk is read once for all of them."""
+HIComProjector.open_stream_multi (ClipStreamMulti, behind ClipStream in this file) is the same stream for Q guides known up
+front: every chunk is read once for all of them.  HIComProjector.open_stream_adapt (ClipStreamAdapt, at the end of this file)
+is that stream for the k / v adaptor recipe: the adaptor MLPs run once per chunk for all Q guides."""
 from __future__ import annotations
 
 import math
@@ -64,10 +65,15 @@ def chunk_rows(proj, groups0, groups, gh, gw, has_newline):
     return row0, lay.nl_group, newline, row1
 
 
-def stream_scope(proj, guide, H, W, max_frames, nl, WHAT=WHAT, multi=False):
+def stream_scope(proj, guide, H, W, max_frames, nl, WHAT=WHAT, multi=False, recipe="plain"):
     """Raises for everything outside the scope of a clip stream, in front of any device work; returns (E, kt, ks, hidden, heads).  multi: the
-    guide is the [Q, E] block of open_stream_multi (WHAT names the entry in the messages)."""
-    if seg.seg_recipe(proj) != "plain":
+    guide is the [Q, E] block of open_stream_multi (WHAT names the entry in the messages).  recipe: the segments.seg_recipe the entry is
+    built for ("adaptkv": open_stream_adapt)."""
+    if seg.seg_recipe(proj) != recipe:
+        if recipe == "adaptkv":
+            raise NotImplementedError(f"{WHAT} is built for the two release recipes only (local + global compressor, use_guide='direct', no "
+                                      "adaptors but adapt_k / adapt_v on the local stage, no clip scale); everything else goes through "
+                                      "forward() on the whole clip")
         raise NotImplementedError(f"{WHAT} is built for the plain release recipe only (local + global compressor, use_guide='direct', no "
                                   "adaptors, no clip scale); everything else goes through forward() on the whole clip")
     lc, gc = proj.local_compressor, proj.global_compressor
@@ -117,6 +123,7 @@ class ClipStream:
     """The object HIComProjector.open_stream returns (module docstring).  Attributes: `frames` pushed so far, `rows` local rows so far
     (the whole-clip newline row of `one_token` included once finish() has written it), `out` the output buffer."""
     NAME, WHAT = "ClipStream", WHAT                  # what the messages call the object and the entry that opens it
+    RECIPE, RECIPE_WORDS = "plain", "the plain release recipe"       # segments.seg_recipe of the modules the stream takes
 
     def __init__(self, proj, guide_embed, H, W, max_frames, image_newline=None):
         from .projector import _out_dtype, _refuse_grad
@@ -224,8 +231,8 @@ class ClipStream:
         what, WHAT = f"{self.NAME}.push", self.WHAT
         if isinstance(ff, dict) or isinstance(fe, dict):
             raise NotImplementedError(f"{what}: anyres dict inputs have no clip-stream path (call forward() per image)")
-        if seg.seg_recipe(self.proj) != "plain" or self.proj.local_compressor.readout[0].weight.dtype != torch.bfloat16:
-            raise NotImplementedError(f"{what}: the module left the scope of {WHAT} (the plain release recipe, bfloat16) since the stream was opened")
+        if seg.seg_recipe(self.proj) != self.RECIPE or self.proj.local_compressor.readout[0].weight.dtype != torch.bfloat16:
+            raise NotImplementedError(f"{what}: the module left the scope of {WHAT} ({self.RECIPE_WORDS}, bfloat16) since the stream was opened")
         if not isinstance(ff, torch.Tensor) or ff.ndim != 4:
             raise ValueError(f"{what}: frames_feature is [Tc, H, W, E]")
         Tc = ff.shape[0]
@@ -336,11 +343,20 @@ class ClipStreamMulti(ClipStream):
     Scope: that of open_stream (plain release recipe, bf16 module and inputs, inference only, exact window partition, E == 1152,
     hidden % 64 == 0; windows of <= 64 tokens) with 1 <= Q <= 32 and the merge kernels' LDS limits on a chunk (multi_chunk_limits)."""
     NAME, WHAT = "ClipStreamMulti", "open_stream_multi"
+    STORE = STORE_MULTI
+
+    def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
+        """stream_scope of the class and the limits of the shortest chunk: (E, kt, ks, hidden, heads)."""
+        dims = stream_scope(proj, guide_embeds, H, W, max_frames, image_newline, self.WHAT, True, self.RECIPE)
+        multi_chunk_limits(self.WHAT, dims[1], H, W, proj.global_compressor.use_pos_emb)      # (the shortest chunk must fit)
+        return dims
+
+    def _plan_key(self, Tc, has_fe, stream):
+        return (self.Q, Tc, self.H, self.W, self.E, has_fe, None if self.newline is None else tuple(self.newline.shape), self.out_dtype, stream)
 
     def __init__(self, proj, guide_embeds, H, W, max_frames, image_newline=None):
         from .projector import _out_dtype, _refuse_grad
-        self.E, self.kt, self.ks, self.hidden, self.nh = stream_scope(proj, guide_embeds, H, W, max_frames, image_newline, self.WHAT, True)
-        multi_chunk_limits(self.WHAT, self.kt, H, W, proj.global_compressor.use_pos_emb)      # (the shortest chunk must fit)
+        self.E, self.kt, self.ks, self.hidden, self.nh = self._scope(proj, guide_embeds, H, W, max_frames, image_newline)
         _refuse_grad(proj, f"HIComProjector.{self.WHAT}")
         _require_bf16_cuda("guide_embeds", guide_embeds)
         if image_newline is not None:
@@ -399,6 +415,14 @@ class ClipStreamMulti(ClipStream):
         self.cur = 0
 
     def _build_plan(self, Tc, has_fe):
+        a = nv.StreamPushMultiArgs()
+        ws, _, keep = self._fill_block(a, Tc)
+        return StreamPlan(a, ws, keep, self.proj.local_compressor.readout_f16)
+
+    def _fill_block(self, a, Tc, extra=()):
+        """The fields of the push block `a` that the module and the chunk shape decide, and the workspace of ONE chunk with its regions
+        entered into `a`.  extra: byte sizes of further regions behind them (0: none).  Returns (workspace, the addresses of the extra
+        regions -- None for an empty one --, the tensors the block points at)."""
         from .projector import _linear_params
         lc, gc = self.proj.local_compressor, self.proj.global_compressor
         E, hidden, dev, H, W, Q, R, RP = self.E, self.hidden, self.device, self.H, self.W, self.Q, self.R, self.rows_pad
@@ -414,23 +438,27 @@ class ClipStreamMulti(ClipStream):
             return (n + 255) // 256 * 256
         scores = max(RP * stride, nparts * RP * nv.global_stream_marg_width(H, W))
         sizes = [up(nparts * RP * 4), up(nparts * RP * 4), up(nparts * RP * E * 4), up(scores * 4), up(RP * Tc * (H + W + 2) * 4), up(R * 2 * 4),
-                 up(R * E * 4), up(Q * nw * E * 2), up(Q * nw * hidden * 2), up(Q * nw * hidden * odt)]
+                 up(R * E * 4), up(Q * nw * E * 2), up(Q * nw * hidden * 2), up(Q * nw * hidden * odt)] + [up(n) for n in extra]
         ws = torch.empty((sum(sizes),), dtype=torch.uint8, device=dev)
         offs = [sum(sizes[:i]) for i in range(len(sizes))]
-        a = nv.StreamPushMultiArgs()
         a.Q, a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.nparts = Q, Tc, H, W, E, self.kt, self.ks, self.nh, hidden, nparts
         a.marg, a.score_stride = int(marg), stride
         a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
-        (a.part_m, a.part_l, a.part_acc, a.scores, a.scratch, a.set_ml, a.set_acc, a.ctx_f16, a.hid_f16, a.loc) = (ws.data_ptr() + o for o in offs)
+        (a.part_m, a.part_l, a.part_acc, a.scores, a.scratch, a.set_ml, a.set_acc, a.ctx_f16, a.hid_f16, a.loc) = (ws.data_ptr() + o for o in offs[:10])
         w0h, w2h = lc.readout_f16()
         b0, b2 = _linear_params(lc.readout[0])[1], _linear_params(lc.readout[2])[1]
         a.lw0_f16, a.lw2_f16, a.lb0, a.lb2 = w0h.data_ptr(), w2h.data_ptr(), b0.data_ptr(), b2.data_ptr()
         a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
         a.ldo = hidden
-        return StreamPlan(a, ws, [w0h, w2h, b0, b2], lc.readout_f16)
+        return ws, [ws.data_ptr() + o if n else None for o, n in zip(offs[10:], extra)], [w0h, w2h, b0, b2]
 
     def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
-        a = plan.args
+        self._patch(plan.args, ff, fe, t0, row0, nl_group, newline_rows, stream)
+        nv.compressor_stream_push_multi(plan.args)
+
+    def _patch(self, a, ff, fe, t0, row0, nl_group, newline_rows, stream):
+        """What changes from push to push in the plain push block `a`: the chunk, its frame and row offsets, its newline rows and everything
+        that belongs to this stream (a plan serves every stream of the module)."""
         a.ff, a.fe, a.guide, a.t0 = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr(), t0
         a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
         a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
@@ -446,7 +474,6 @@ class ClipStreamMulti(ClipStream):
             a.nl_first = newline_rows[0]
             a.nl_step = newline_rows[1] - newline_rows[0] if len(newline_rows) > 1 else nl_group + 1
         a.stream = stream
-        nv.compressor_stream_push_multi(a)
 
     def _finish_device(self, row0, tail):
         self.proj.global_compressor.finish_guides(self.state_ml[self.cur:self.cur + 1], self.state_acc, self.guides, self.fin)
@@ -462,9 +489,7 @@ class ClipStreamMulti(ClipStream):
         ff = frames_feature.contiguous()
         fe = frames_embed.contiguous() if frames_embed is not None else None
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        key = (self.Q, Tc, self.H, self.W, self.E, fe is not None, None if self.newline is None else tuple(self.newline.shape), self.out_dtype,
-               stream)
-        plan = seg.cached_plan(self.proj, STORE_MULTI, key, lambda: self._build_plan(Tc, fe is not None))
+        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(Tc, fe is not None, stream), lambda: self._build_plan(Tc, fe is not None))
         row0, nl_group, newline_rows, row1 = chunk_rows(self.proj, self.frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
         self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
         self.cur ^= 1
@@ -490,10 +515,96 @@ class ClipStreamMulti(ClipStream):
         from .projector import _refuse_grad
         new = self.guides if guides is None else guides
         if guides is not None:
-            stream_scope(self.proj, new, self.H, self.W, self.max_frames, self.newline, self.WHAT, True)
+            self._scope(self.proj, new, self.H, self.W, self.max_frames, self.newline)
             if new.shape[0] != self.Q:
                 raise ValueError(f"{self.NAME}.reset: {new.shape[0]} guides on a stream opened for Q={self.Q} (the buffers are sized by Q)")
             _require_bf16_cuda("guide_embeds", new)
         _refuse_grad(self.proj, f"{self.NAME}.reset")
         self.frames, self.n_pushes, self.has_fe = 0, 0, None
         self._prepare(new)
+
+
+# =================================================================================================================================
+# several guides per stream on the k / v adaptor recipe (HIComProjector.open_stream_adapt)
+# =================================================================================================================================
+STORE_ADAPT = "_clip_stream_adapt_plans"
+
+
+def adaptor_widths(what, lc):
+    """The width condition of segments.fill_adaptors, from the parameters' shapes alone: in front of any device work."""
+    from . import engine
+    for _, mlp, _, _ in engine.adaptor_streams(lc):
+        w0, w2 = mlp[0].weight, mlp[2].weight
+        if w0.shape[0] % 64 or w0.shape[1] % 64 or w2.shape[0] % 64 or w0.shape != w2.shape:
+            raise NotImplementedError(f"{what}: adaptor widths must be multiples of 64")
+
+
+def adapt_chunk_limit(what, Tc, H, W, E):
+    """The operand limit of the adaptor MLPs' dense GEMMs on ONE chunk (hicom_clip_adapt_prepare_fwd checks the same)."""
+    if Tc * H * W * E >= 1 << 32:
+        raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the adaptor GEMMs take operands below 2^32 elements; push shorter chunks")
+
+
+class ClipStreamAdapt(ClipStreamMulti):
+    """The object HIComProjector.open_stream_adapt returns for a module of the k / v adaptor recipe (`local43_adaptkv_global32`; adapt_k
+    and / or adapt_v on the local compressor): ClipStreamMulti's surface, state, output buffer, finish() and reset().
+
+    The adaptors sit on the local stage only and the adaptor MLPs do not know the guide, so only the local stage of a push differs
+    (hicom_compressor_stream_push_multi_adapt): both layers of each adaptor MLP over the chunk's Tc H W tokens ONCE for all Q guides, into
+    fp16 planes ky / vy [Tc H W, E] that live for that push; the multi-guide local kernel that blends LayerNorm of those planes into the
+    rows it loads (the kernel of forward_prepared); then the launches of the plain push.  Without frames_embed the k adaptor reads
+    frames_feature, as the keys do.
+
+    Per plan -- ClipStreamMulti's key plus the adaptor set, cached on the module as `proj._clip_stream_adapt_plans` -- the workspace of ONE
+    chunk: the parent's regions, the two planes and the hidden planes of layer 1 (4 x 2304 bytes per token of a chunk with both adaptors).
+    The planes are written and read inside one push, in stream order, so two streams of one module share a plan.  push allocates nothing.
+    The plan follows the weights as every plan does: its refresh rebuilds the cached fp16 copies of the adaptors' second layers.
+
+    Scope: that of open_stream_multi with the adaptor recipe in the place of the plain one, adaptor widths % 64 == 0 and Tc H W E < 2^32
+    per chunk."""
+    NAME, WHAT = "ClipStreamAdapt", "open_stream_adapt"
+    RECIPE, RECIPE_WORDS = "adaptkv", "the k / v adaptor release recipe"
+    STORE = STORE_ADAPT
+
+    def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
+        dims = super()._scope(proj, guide_embeds, H, W, max_frames, image_newline)
+        adaptor_widths(self.WHAT, proj.local_compressor)
+        adapt_chunk_limit(self.WHAT, dims[1], H, W, dims[0])
+        return dims
+
+    def _plan_key(self, Tc, has_fe, stream):
+        lc = self.proj.local_compressor
+        return super()._plan_key(Tc, has_fe, stream) + (bool(lc.adapt_k), bool(lc.adapt_v))
+
+    def _build_plan(self, Tc, has_fe):
+        lc = self.proj.local_compressor
+        args = nv.StreamPushMultiAdaptArgs()
+        keep = []
+
+        def ptr(t):
+            if t is None:
+                return None
+            keep.append(t)
+            return t.data_ptr()
+        seg.fill_adaptors(args, lc, self.WHAT, ptr)
+        N = Tc * self.H * self.W
+        hid_bytes = nv.clip_adapt_prepare_workspace(N, self.E, args.ak, args.av, self.WHAT)     # (the GEMM's operand limit raises here)
+        plane = N * self.E * 2
+        ws, (args.ky, args.vy, args.adapt_ws), readout = self._fill_block(args.base, Tc, (plane if lc.adapt_k else 0, plane if lc.adapt_v else 0,
+                                                                                         hid_bytes))
+        args.adapt_ws_bytes = hid_bytes
+
+        def refresh():
+            lc.readout_f16()
+            seg.refresh_adaptors(lc)
+        return StreamPlan(args, ws, keep + readout, refresh)
+
+    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
+        self._patch(plan.args.base, ff, fe, t0, row0, nl_group, newline_rows, stream)
+        nv.compressor_stream_push_multi_adapt(plan.args)
+
+    def push(self, frames_feature, frames_embed=None):
+        """ClipStreamMulti.push on the adaptor recipe (the class docstring has what differs)."""
+        if isinstance(frames_feature, torch.Tensor) and frames_feature.ndim == 4:
+            adapt_chunk_limit(f"{self.NAME}.push", frames_feature.shape[0], self.H, self.W, self.E)
+        return super().push(frames_feature, frames_embed)

@@ -8,9 +8,13 @@
 // multi-guide local kernel, the many-row global stream with t_index0 and its merge with normalize = 0 over time, with two kernels of this
 // file: the fold of ONE merged set into the state (the body of the fold above) and the placement of Q x rows packed rows (place_row of
 // segment_item.hpp), which finish() uses again for every guide's global rows.
+//
+// The k / v adaptor recipe: hicom_compressor_stream_push_multi_adapt is the same push with another local stage -- the adaptor
+// MLPs over the chunk's tokens (hicom_clip_adapt_prepare_fwd) and the adapt local kernel (hicom_multi_guide_local_adapt_fwd) -- on one body,
+// push_multi, which holds the checks and launches 2 ... for both entry points.
 #include <math.h>
 
-#include "segment_item.hpp"
+#include "segment_host.hpp"
 
 namespace hicom {
 
@@ -239,8 +243,13 @@ extern "C" int hicom_stream_place_rows_fwd(const void* loc, const float* tok, co
                         ldo, q_stride, row0, stream);
 }
 
-extern "C" int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_args* a) {
-    constexpr const char* who = "compressor_stream_push_multi";
+namespace {
+
+// One push of a multi-guide stream, the body of both entry points: every check of the block, the entry's own checks (`more_checks`), then
+// `local` -- the launches that leave the chunk's fp16 contexts in ctx_f16 -- and launches 2 ... of the plain push.  Nothing is launched
+// before every check has passed.
+template <class Checks, class Local>
+int push_multi(const char* who, const hicom_stream_push_multi_args* a, Checks&& more_checks, Local&& local) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", who);
     HICOM_REQUIRE(a->Q >= 1 && a->Q <= kMaxStreamGuides, HICOM_EUNSUP, "%s: Q=%d guides (1 <= Q <= %d per stream)", who, a->Q, kMaxStreamGuides);
     HICOM_REQUIRE(a->Tc > 0 && a->H > 0 && a->W > 0 && a->kt > 0 && a->ks > 0 && a->hidden > 0 && a->nh > 0 && a->nparts > 0, HICOM_EINVAL, "%s: bad shape", who);
@@ -293,9 +302,11 @@ extern "C" int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_
     int st = place_check(who, a->loc, nullptr, a->newline, a->Q, (int)nw, a->hidden, a->nl_group, a->nl_count, a->nl_count ? a->nl_first - a->row0 : 0,
                          a->nl_step, chunk_rows, chunk_rows, a->out, a->out_dt, a->ldo, a->q_stride, a->row0);
     if (st != HICOM_OK) return st;
+    st = more_checks();
+    if (st != HICOM_OK) return st;
 
-    // 1: local stage (no frames_embed: the keys are frames_feature, reference projector.py:532)
-    st = hicom_multi_guide_local_fwd(a->fe ? a->fe : a->ff, a->ff, a->guide, a->Q, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->l_scale, a->ctx_f16, a->stream);
+    // 1: local stage
+    st = local();
     if (st != HICOM_OK) return st;
     // 2-3: the many-row global stream at the chunk's absolute frame offset and its merge into ONE un-normalised set
     if (a->marg) {
@@ -326,4 +337,38 @@ extern "C" int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_
     // 7: guide q's packed rows and the chunk's newline rows to out[q][row0 ..]
     return place_launch(who, a->loc, nullptr, a->newline, a->Q, (int)nw, a->hidden, a->nl_group, a->nl_count, a->nl_count ? a->nl_first - a->row0 : 0, a->nl_step,
                         chunk_rows, chunk_rows, a->out, a->out_dt, a->ldo, a->q_stride, a->row0, a->stream);
+}
+
+}  // namespace
+
+extern "C" int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_args* a) {
+    // (no frames_embed: the keys are frames_feature, reference projector.py:532)
+    return push_multi("compressor_stream_push_multi", a, [] { return (int)HICOM_OK; }, [a] {
+        return hicom_multi_guide_local_fwd(a->fe ? a->fe : a->ff, a->ff, a->guide, a->Q, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->l_scale, a->ctx_f16, a->stream);
+    });
+}
+
+// ---- the k / v adaptor recipe: the adaptor MLPs over the chunk's tokens, then the adapt local stage, in front of launches 2 ...
+extern "C" int hicom_compressor_stream_push_multi_adapt(const hicom_stream_push_multi_adapt_args* x) {
+    constexpr const char* who = "compressor_stream_push_multi_adapt";
+    HICOM_REQUIRE(x, HICOM_EINVAL, "%s: NULL arguments", who);
+    const hicom_stream_push_multi_args* a = &x->base;
+    const void* key_x = a->fe ? a->fe : a->ff;             // (no frames_embed: the k adaptor reads frames_feature, as the keys do)
+    const long N = (long)a->Tc * a->H * a->W;
+    return push_multi(
+        who, a,
+        [&] {
+            HICOM_REQUIRE((x->ky != nullptr) == (x->ak.w0 != nullptr) && (x->vy != nullptr) == (x->av.w0 != nullptr), HICOM_EINVAL,
+                          "%s: a plane and its adaptor come together (ky with ak.w0, vy with av.w0)", who);
+            const int st = hicom_host::multi_guide_local_adapt_args_check(key_x, a->ff, a->guide, x->ky, x->vy, &x->ak, &x->av, x->alpha_dt, a->Q, a->Tc, a->H,
+                                                                          a->W, a->E, a->kt, a->ks, a->ctx_f16);
+            if (st != HICOM_OK) return st;
+            return hicom_host::clip_adapt_prepare_args_check(key_x, a->ff, N, a->E, &x->ak, &x->av, x->ky, x->vy, x->adapt_ws, x->adapt_ws_bytes, nullptr);
+        },
+        [&] {
+            const int st = hicom_clip_adapt_prepare_fwd(key_x, a->ff, N, a->E, &x->ak, &x->av, x->ky, x->vy, x->adapt_ws, x->adapt_ws_bytes, a->stream);
+            if (st != HICOM_OK) return st;
+            return hicom_multi_guide_local_adapt_fwd(key_x, a->ff, a->guide, x->ky, x->vy, &x->ak, &x->av, x->alpha_dt, x->eps, a->Q, a->Tc, a->H, a->W, a->E,
+                                                     a->kt, a->ks, a->l_scale, a->ctx_f16, a->stream);
+        });
 }

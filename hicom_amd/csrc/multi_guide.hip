@@ -19,6 +19,7 @@
 // Prepared clips: for the k / v adaptor recipe hicom_clip_adapt_prepare_fwd runs the adaptor MLPs over a clip's tokens
 // once, into planes the caller keeps; hicom_compressor_multiguide_adapt_fwd is the sequence above with launch 3 replaced by
 // multi_guide_local_adapt_kernel, which blends LayerNorm of those planes into the rows it loads.  Same launch count, same workspace.
+// hicom_multi_guide_local_adapt_fwd is that launch alone, for a clip stream's chunk.
 #include "multi_window.hpp"
 #include "segment_host.hpp"
 
@@ -78,6 +79,13 @@ void launch_local_plain(const uint16_t* key, const uint16_t* value, const uint16
                         float scale, _Float16* ctx16, void* stream) {
     HICOM_LAUNCH(multi_guide_local_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, (hipStream_t)stream, key, value, guide, at, ay, ax, Q, nwin,
                  scale, ctx16);
+}
+
+// the same grid for the adaptor recipe on prepared planes (the step's launch 3 and hicom_multi_guide_local_adapt_fwd)
+void launch_local_adapt(const uint16_t* key, const uint16_t* value, const uint16_t* guide, const SegAdaptParams& ad, hicom_axis at, hicom_axis ay, hicom_axis ax,
+                        int Q, int nwin, float scale, _Float16* ctx16, void* stream) {
+    HICOM_LAUNCH(multi_guide_local_adapt_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, (hipStream_t)stream, key, value, guide, ad, at, ay, ax, Q,
+                 nwin, scale, ctx16);
 }
 
 // token chunks of the global stream
@@ -150,8 +158,8 @@ struct GuideItems {
         const hicom_axis at{a->T, a->kt, a->T / a->kt, a->T / a->kt};
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
         if (prepared)
-            HICOM_LAUNCH(multi_guide_local_adapt_kernel<3>, dim3((unsigned)((l.wpi + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x,
-                         (const uint16_t*)a->ff, (const uint16_t*)a->guide, *prepared, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
+            launch_local_adapt(key_x, (const uint16_t*)a->ff, (const uint16_t*)a->guide, *prepared, at, ay, ax, a->Q, l.wpi, a->l_scale,
+                               (_Float16*)(ws() + l.s.ctx16), a->stream);
         else
             launch_local_plain(key_x, (const uint16_t*)a->ff, (const uint16_t*)a->guide, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16),
                                a->stream);
@@ -197,14 +205,24 @@ int mg_fwd(const Args* a, const SegAdaptParams* prepared = nullptr) {
 // ---- the k / v adaptor recipe on prepared planes ------------------------------------------------------------------------------------------
 typedef hicom_compressor_multiguide_adapt_args AdaptArgs;
 
-// what the adaptor block adds to the plain checks; a stream is adapted when its plane is given
-int mga_check(const AdaptArgs* a) {
-    HICOM_REQUIRE(a->ky || a->vy, HICOM_EINVAL, "%s: neither stream has a prepared plane (the plain entry point runs that recipe)", kWho);
-    HICOM_REQUIRE((uintptr_t)a->ky % 16 == 0 && (uintptr_t)a->vy % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned planes", kWho);
-    HICOM_REQUIRE(a->alpha_dt == HICOM_DT_BF16 || a->alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", kWho, a->alpha_dt);
-    HICOM_REQUIRE((!a->ky || (a->ak.gamma && a->ak.beta && a->ak.alpha)) && (!a->vy || (a->av.gamma && a->av.beta && a->av.alpha)), HICOM_EINVAL,
-                  "%s: adaptor weights", kWho);
+// what prepared planes add to the plain checks; a stream is adapted when its plane is given
+int planes_check(const char* who, const void* ky, const void* vy, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int alpha_dt) {
+    HICOM_REQUIRE(ky || vy, HICOM_EINVAL, "%s: neither stream has a prepared plane (the plain entry point runs that recipe)", who);
+    HICOM_REQUIRE((uintptr_t)ky % 16 == 0 && (uintptr_t)vy % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned planes", who);
+    HICOM_REQUIRE(alpha_dt == HICOM_DT_BF16 || alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", who, alpha_dt);
+    HICOM_REQUIRE((!ky || (ak->gamma && ak->beta && ak->alpha)) && (!vy || (av->gamma && av->beta && av->alpha)), HICOM_EINVAL, "%s: adaptor weights", who);
     return HICOM_OK;
+}
+
+int mga_check(const AdaptArgs* a) { return planes_check(kWho, a->ky, a->vy, &a->ak, &a->av, a->alpha_dt); }
+
+SegAdaptParams planes_params(const void* ky, const void* vy, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int alpha_dt, float eps) {
+    SegAdaptParams p;
+    p.ky = (const _Float16*)ky; p.kgamma = (const uint16_t*)ak->gamma; p.kbeta = (const uint16_t*)ak->beta; p.kalpha = ak->alpha;
+    p.vy = (const _Float16*)vy; p.vgamma = (const uint16_t*)av->gamma; p.vbeta = (const uint16_t*)av->beta; p.valpha = av->alpha;
+    p.alpha_f32 = alpha_dt == HICOM_DT_F32;
+    p.eps = eps;
+    return p;
 }
 
 // ---- y = MLP(x) planes of a clip (hicom_clip_adapt_prepare_*) ---------------------------------------------------------------------------------
@@ -226,23 +244,57 @@ int prepare_check(int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom
 
 }  // namespace
 
-// The local stage alone, for a caller that runs the other stages itself (clip_stream.hip: a chunk of a streamed clip; windows do not
-// depend on the frame offset).  Checks everything in front of the launch.
+// ---- the local stage alone, for a caller that runs the other stages itself (clip_stream.hip: a chunk of a streamed clip; windows do not
+// depend on the frame offset).  Everything is checked in front of the launch.
+namespace {
+
+int local_check(const char* who, const void* key, const void* value, const void* guide, int Q, int T, int H, int W, int E, int kt, int ks, const void* ctx_f16) {
+    HICOM_REQUIRE(key && value && guide && ctx_f16, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE(Q >= 1 && Q <= kMaxGuides, HICOM_EUNSUP, "%s: Q=%d guides (1 <= Q <= %d per call)", who, Q, kMaxGuides);
+    HICOM_REQUIRE(T > 0 && H > 0 && W > 0 && kt > 0 && ks > 0, HICOM_EINVAL, "%s: bad shape", who);
+    HICOM_REQUIRE(E == 1152, HICOM_EUNSUP, "%s: E=%d (only 1152)", who, E);
+    HICOM_REQUIRE(T % kt == 0 && H % ks == 0 && W % ks == 0 && kt * ks * ks <= 64, HICOM_EUNSUP,
+                  "%s: needs an exact partition into windows of <= 64 tokens (T=%d H=%d W=%d, windows %dx%dx%d)", who, T, H, W, kt, ks, ks);
+    const long nwin = (long)(T / kt) * (H / ks) * (W / ks);
+    HICOM_REQUIRE((long)T * H * W < (1L << 31) / 16 && nwin * Q < (1L << 31) / 16, HICOM_EUNSUP, "%s: too many tokens in one call", who);
+    HICOM_REQUIRE((uintptr_t)key % 16 == 0 && (uintptr_t)value % 16 == 0 && (uintptr_t)guide % 16 == 0 && (uintptr_t)ctx_f16 % 16 == 0, HICOM_EINVAL,
+                  "%s: 16-byte aligned inputs", who);
+    return HICOM_OK;
+}
+
+constexpr const char* kWhoLocalAdapt = "multi_guide_local_adapt";
+
+}  // namespace
+
 extern "C" int hicom_multi_guide_local_fwd(const void* key, const void* value, const void* guide, int32_t Q, int32_t T, int32_t H, int32_t W, int32_t E,
                                            int32_t kt, int32_t ks, float scale, void* ctx_f16, void* stream) {
-    HICOM_REQUIRE(key && value && guide && ctx_f16, HICOM_EINVAL, "multi_guide_local: NULL pointer");
-    HICOM_REQUIRE(Q >= 1 && Q <= kMaxGuides, HICOM_EUNSUP, "multi_guide_local: Q=%d guides (1 <= Q <= %d per call)", Q, kMaxGuides);
-    HICOM_REQUIRE(T > 0 && H > 0 && W > 0 && kt > 0 && ks > 0, HICOM_EINVAL, "multi_guide_local: bad shape");
-    HICOM_REQUIRE(E == 1152, HICOM_EUNSUP, "multi_guide_local: E=%d (only 1152)", E);
-    HICOM_REQUIRE(T % kt == 0 && H % ks == 0 && W % ks == 0 && kt * ks * ks <= 64, HICOM_EUNSUP,
-                  "multi_guide_local: needs an exact partition into windows of <= 64 tokens (T=%d H=%d W=%d, windows %dx%dx%d)", T, H, W, kt, ks, ks);
+    const int st = local_check("multi_guide_local", key, value, guide, Q, T, H, W, E, kt, ks, ctx_f16);
+    if (st != HICOM_OK) return st;
     const long nwin = (long)(T / kt) * (H / ks) * (W / ks);
-    HICOM_REQUIRE((long)T * H * W < (1L << 31) / 16 && nwin * Q < (1L << 31) / 16, HICOM_EUNSUP, "multi_guide_local: too many tokens in one call");
-    HICOM_REQUIRE((uintptr_t)key % 16 == 0 && (uintptr_t)value % 16 == 0 && (uintptr_t)guide % 16 == 0 && (uintptr_t)ctx_f16 % 16 == 0, HICOM_EINVAL,
-                  "multi_guide_local: 16-byte aligned inputs");
     const hicom_axis at{T, kt, T / kt, T / kt}, ay{H, ks, H / ks, H / ks}, ax{W, ks, W / ks, W / ks};
     launch_local_plain((const uint16_t*)key, (const uint16_t*)value, (const uint16_t*)guide, at, ay, ax, Q, (int)nwin, scale, (_Float16*)ctx_f16, stream);
     return seg_check_launch("multi_guide_local", "local stage");
+}
+
+// segment_host.hpp declares the two *_args_check functions: the checks of an entry point without its launches
+int hicom_host::multi_guide_local_adapt_args_check(const void* key, const void* value, const void* guide, const void* ky, const void* vy,
+                                                   const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int alpha_dt, int Q, int T, int H, int W, int E,
+                                                   int kt, int ks, const void* ctx_f16) {
+    HICOM_REQUIRE(ak && av, HICOM_EINVAL, "%s: NULL arguments", kWhoLocalAdapt);
+    const int st = local_check(kWhoLocalAdapt, key, value, guide, Q, T, H, W, E, kt, ks, ctx_f16);
+    return st != HICOM_OK ? st : planes_check(kWhoLocalAdapt, ky, vy, ak, av, alpha_dt);
+}
+
+extern "C" int hicom_multi_guide_local_adapt_fwd(const void* key, const void* value, const void* guide, const void* ky, const void* vy,
+                                                 const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int32_t alpha_dt, float eps, int32_t Q, int32_t T,
+                                                 int32_t H, int32_t W, int32_t E, int32_t kt, int32_t ks, float scale, void* ctx_f16, void* stream) {
+    const int st = multi_guide_local_adapt_args_check(key, value, guide, ky, vy, ak, av, alpha_dt, Q, T, H, W, E, kt, ks, ctx_f16);
+    if (st != HICOM_OK) return st;
+    const long nwin = (long)(T / kt) * (H / ks) * (W / ks);
+    const hicom_axis at{T, kt, T / kt, T / kt}, ay{H, ks, H / ks, H / ks}, ax{W, ks, W / ks, W / ks};
+    launch_local_adapt((const uint16_t*)key, (const uint16_t*)value, (const uint16_t*)guide, planes_params(ky, vy, ak, av, alpha_dt, eps), at, ay, ax, Q,
+                       (int)nwin, scale, (_Float16*)ctx_f16, stream);
+    return seg_check_launch(kWhoLocalAdapt, "local stage");
 }
 
 extern "C" int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compressor_multiguide_args* a) {
@@ -265,11 +317,7 @@ extern "C" int hicom_compressor_multiguide_adapt_fwd(const hicom_compressor_mult
     if (st != HICOM_OK) return st;
     st = mga_check(a);
     if (st != HICOM_OK) return st;
-    SegAdaptParams p;
-    p.ky = (const _Float16*)a->ky; p.kgamma = (const uint16_t*)a->ak.gamma; p.kbeta = (const uint16_t*)a->ak.beta; p.kalpha = a->ak.alpha;
-    p.vy = (const _Float16*)a->vy; p.vgamma = (const uint16_t*)a->av.gamma; p.vbeta = (const uint16_t*)a->av.beta; p.valpha = a->av.alpha;
-    p.alpha_f32 = a->alpha_dt == HICOM_DT_F32;
-    p.eps = a->eps;
+    const SegAdaptParams p = planes_params(a->ky, a->vy, &a->ak, &a->av, a->alpha_dt, a->eps);
     return mg_fwd(&a->base, &p);
 }
 
@@ -280,8 +328,8 @@ extern "C" int64_t hicom_clip_adapt_prepare_workspace_bytes(int64_t N, int32_t E
     return st != HICOM_OK ? st : total;
 }
 
-extern "C" int hicom_clip_adapt_prepare_fwd(const void* key_x, const void* ff, int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av,
-                                            void* ky, void* vy, void* ws, int64_t ws_bytes, void* stream) {
+int hicom_host::clip_adapt_prepare_args_check(const void* key_x, const void* ff, long N, int E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av,
+                                              const void* ky, const void* vy, const void* ws, long ws_bytes, long* hid_v_out) {
     SegAdapt ad;
     long hid_v = 0, total = 0;
     const int st = prepare_check(N, E, ak, av, &ad, &hid_v, &total);
@@ -292,5 +340,15 @@ extern "C" int hicom_clip_adapt_prepare_fwd(const void* key_x, const void* ff, i
     HICOM_REQUIRE(ws && ws_bytes >= total && (uintptr_t)ws % 256 == 0, HICOM_EINVAL, "%s: workspace of %ld bytes, 256-byte aligned", kWhoPrepare, total);
     HICOM_REQUIRE((uintptr_t)key_x % 16 == 0 && (uintptr_t)ff % 16 == 0 && (uintptr_t)ky % 16 == 0 && (uintptr_t)vy % 16 == 0, HICOM_EINVAL,
                   "%s: 16-byte aligned tokens and planes", kWhoPrepare);
+    if (hid_v_out) *hid_v_out = hid_v;
+    return HICOM_OK;
+}
+
+extern "C" int hicom_clip_adapt_prepare_fwd(const void* key_x, const void* ff, int64_t N, int32_t E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av,
+                                            void* ky, void* vy, void* ws, int64_t ws_bytes, void* stream) {
+    long hid_v = 0;
+    const int st = clip_adapt_prepare_args_check(key_x, ff, N, E, ak, av, ky, vy, ws, ws_bytes, &hid_v);
+    if (st != HICOM_OK) return st;
+    const SegAdapt ad{ak, av, HICOM_DT_BF16, 0.f};            // (the MLPs read neither alpha nor eps)
     return seg_adapt_mlps(ad, key_x, ff, N, E, ws, (char*)ws + hid_v, ky, vy, stream);
 }

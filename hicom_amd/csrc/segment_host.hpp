@@ -109,6 +109,14 @@ inline auto seg_with_adapt(const char* who, const AdaptArgs* a, F&& f) -> declty
     return f(&a->base, &ad);
 }
 
+// multi_guide.hip: every argument check of hicom_clip_adapt_prepare_fwd and of hicom_multi_guide_local_adapt_fwd without their launches, for a
+// host call that runs several entry points and checks all of them in front of its first launch (clip_stream.hip).  hid_v_out (may be NULL):
+// where the value stream's hidden plane begins in the workspace.
+int clip_adapt_prepare_args_check(const void* key_x, const void* ff, long N, int E, const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, const void* ky,
+                                  const void* vy, const void* ws, long ws_bytes, long* hid_v_out);
+int multi_guide_local_adapt_args_check(const void* key, const void* value, const void* guide, const void* ky, const void* vy, const hicom_seg_adaptor* ak,
+                                       const hicom_seg_adaptor* av, int alpha_dt, int Q, int T, int H, int W, int E, int kt, int ks, const void* ctx_f16);
+
 // items of the call: B of a batch / ragged block, Q (guides) of a multi-guide block
 template <class A>
 inline auto seg_items(const A* a) -> decltype(a->B) { return a->B; }

@@ -51,6 +51,7 @@ EXPORTS = (
     "hicom_compressor_clips_multiguide_fwd", "hicom_compressor_clips_multiguide_workspace_bytes", "hicom_compressor_clips_multiguide_prepare",
     "hicom_stream_state_clear_fwd", "hicom_stream_state_fold_fwd", "hicom_compressor_stream_push",
     "hicom_stream_state_fold_set_fwd", "hicom_multi_guide_local_fwd", "hicom_stream_place_rows_fwd", "hicom_compressor_stream_push_multi",
+    "hicom_multi_guide_local_adapt_fwd", "hicom_compressor_stream_push_multi_adapt",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -270,6 +271,13 @@ class StreamPushMultiArgs(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class StreamPushMultiAdaptArgs(C.Structure):
+    """hicom_stream_push_multi_adapt_args (include/hicom_hip.h): the plain push block first, then the two adaptors, the fp16 planes of ONE
+    chunk (NULL: that stream is not adapted), the workspace of the adaptor MLPs' hidden planes, the alpha dtype and the LayerNorm eps."""
+    _fields_ = [("base", StreamPushMultiArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("ky", C.c_void_p), ("vy", C.c_void_p),
+                ("adapt_ws", C.c_void_p), ("adapt_ws_bytes", C.c_int64), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -400,6 +408,9 @@ def lib() -> C.CDLL:
     L.hicom_multi_guide_local_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]
     L.hicom_stream_place_rows_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp, i32, i64, i64, i64, vp]
     L.hicom_compressor_stream_push_multi.argtypes = [C.POINTER(StreamPushMultiArgs)]
+    L.hicom_multi_guide_local_adapt_fwd.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32, i32, i32,
+                                                    i32, f32, vp, vp]
+    L.hicom_compressor_stream_push_multi_adapt.argtypes = [C.POINTER(StreamPushMultiAdaptArgs)]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -791,12 +802,12 @@ def compressor_multiguide_fwd(args):
     _seg_call(args, "multiguide", "fwd")
 
 
-def clip_adapt_prepare_workspace(N: int, E: int, ak: SegAdaptor, av: SegAdaptor) -> int:
+def clip_adapt_prepare_workspace(N: int, E: int, ak: SegAdaptor, av: SegAdaptor, what: str = "prepare_clip") -> int:
     n = lib().hicom_clip_adapt_prepare_workspace_bytes(N, E, C.byref(ak), C.byref(av))
     if n < 0:
         msg = lib().hicom_last_error().decode(errors="replace")
         if n == -2:
-            raise NotImplementedError(f"prepare_clip: {msg}")
+            raise NotImplementedError(f"{what}: {msg}")
         raise HicomNativeError(f"hicom_clip_adapt_prepare_workspace_bytes failed ({n}): {msg}")
     return int(n)
 
@@ -867,6 +878,18 @@ def stream_place_global(tok, newline, tail_newline, n_rows, out, row0):
 
 def compressor_stream_push_multi(args: StreamPushMultiArgs):
     _check(lib().hicom_compressor_stream_push_multi(C.byref(args)), "hicom_compressor_stream_push_multi")
+
+
+def multi_guide_local_adapt(key_x: int, ff: int, guide: int, ky, vy, ak: SegAdaptor, av: SegAdaptor, alpha_dt: int, eps: float, Q: int, T: int, H: int,
+                            W: int, E: int, kt: int, ks: int, scale: float, ctx_f16: int, stream: int):
+    """Addresses in, one launch out: the local stage of forward_prepared alone (hicom_multi_guide_local_adapt_fwd), fp16 contexts
+    [Q][windows][E] from the tokens and the prepared planes ky / vy (None: that stream is not adapted)."""
+    _check(lib().hicom_multi_guide_local_adapt_fwd(key_x, ff, guide, ky, vy, C.byref(ak), C.byref(av), alpha_dt, eps, Q, T, H, W, E, kt, ks, scale, ctx_f16,
+                                                   stream), "hicom_multi_guide_local_adapt_fwd")
+
+
+def compressor_stream_push_multi_adapt(args: StreamPushMultiAdaptArgs):
+    _check(lib().hicom_compressor_stream_push_multi_adapt(C.byref(args)), "hicom_compressor_stream_push_multi_adapt")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -845,6 +845,7 @@ class HIComProjector(nn.Module):
         self.__dict__.pop("_prepare_plans", None)
         self.__dict__.pop("_clip_stream_plans", None)
         self.__dict__.pop("_clip_stream_multi_plans", None)
+        self.__dict__.pop("_clip_stream_adapt_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1221,6 +1222,28 @@ class HIComProjector(nn.Module):
         16 against 149 / 441 / 880 / 2331 us for Q single-guide streams pushed one after the other; finish() 23 .. 38 us.  It wins from Q = 1."""
         from . import clip_stream
         return clip_stream.ClipStreamMulti(self, guide_embeds, H, W, max_frames, image_newline)
+
+    def open_stream_adapt(self, guide_embeds, H, W, max_frames, image_newline=None):
+        """open_stream_multi for the k / v adaptor recipe (`local43_adaptkv_global32`: adapt_k and / or adapt_v on the local compressor):
+        returns a ClipStreamAdapt (hicom_amd/clip_stream.py) with the surface of ClipStreamMulti --
+            s = proj.open_stream_adapt(guide_embeds, H, W, max_frames, image_newline)    # guide_embeds bf16 [Q, E], 1 <= Q <= 32
+            rows = s.push(frames_feature, frames_embed)   # [Q, chunk rows, hidden]
+            out = s.finish()                              # [Q, local rows so far + 32, hidden]; out[q] equals forward() on the concatenation with
+                                                          # guide q to the kernels' rounding
+            s.reset(guide_embeds=None)
+        The adaptor MLPs are per token and do not know the guide: a push runs both layers of each over the chunk's tokens ONCE for all Q
+        guides, into fp16 planes of one chunk that the plan owns (nothing per token outlives the push, unlike prepare_clip's planes of
+        the whole video), then the multi-guide local kernel of forward_prepared on those planes and the launches of open_stream_multi's
+        push: one host call (hicom_compressor_stream_push_multi_adapt), ten launches whatever Q is.  The global stage of the recipe is
+        the plain one, so the carried state, finish() and reset() are ClipStreamMulti's.  Without frames_embed the k adaptor reads
+        frames_feature, as the keys do.
+        A plain-recipe module gets open_stream_multi's object, so one entry serves both released recipes (as forward_prepared does).
+        The scope of open_stream_multi with the adaptor recipe in the place of the plain one, adaptor widths % 64 == 0 and Tc H W E < 2^32
+        per chunk; everything else raises NotImplementedError / ValueError in front of the first launch.  Inference only."""
+        from . import clip_stream
+        if clip_stream.seg.seg_recipe(self) == "plain":
+            return self.open_stream_multi(guide_embeds, H, W, max_frames, image_newline)
+        return clip_stream.ClipStreamAdapt(self, guide_embeds, H, W, max_frames, image_newline)
 
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):

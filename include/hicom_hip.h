@@ -1293,6 +1293,43 @@ typedef struct hicom_stream_push_multi_args {
 } hicom_stream_push_multi_args;
 int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_args* args);
 
+/* ---- clip stream for several instructions on the k / v adaptor recipe ----------------------------------------------
+ * The adaptors sit on the local stage only, so the carried state, its fold, finish() and the placement are those above; a push differs
+ * in its local stage alone: the adaptor MLPs run over the chunk's tokens once for all Q guides, into planes that live for one push.
+ *
+ * hicom_multi_guide_local_adapt_fwd is the local stage of hicom_compressor_multiguide_adapt_fwd alone (its kernel, its launch): key / value
+ * bf16 [T, H, W, E], the fp16 planes ky / vy [T H W, E] of hicom_clip_adapt_prepare_fwd (NULL: that stream is not adapted; not both NULL,
+ * HICOM_EINVAL; 16-byte aligned), gamma / beta / alpha of the two adaptors (of an adapted stream; w0 .. b2 are not read), alpha_dt and
+ * eps as in hicom_compressor_multiguide_adapt_args; fp16 contexts ctx_f16 [Q][windows][E].  Shapes, limits and checks of
+ * hicom_multi_guide_local_fwd.  Windows do not depend on a frame offset. */
+int hicom_multi_guide_local_adapt_fwd(const void* key, const void* value, const void* guide, const void* ky, const void* vy,
+                                      const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int32_t alpha_dt, float eps, int32_t Q, int32_t T,
+                                      int32_t H, int32_t W, int32_t E, int32_t kt, int32_t ks, float scale, void* ctx_f16, void* stream);
+
+/* One push of a multi-guide clip stream on the adaptor recipe in ONE host call, ten launches (eleven in the logit-tensor form) whatever Q
+ * is: hicom_clip_adapt_prepare_fwd on the chunk's N = Tc H W tokens (layer 1 and layer 2 of the adaptor MLPs, a GEMM pair each with both
+ * adaptors) into ky / vy; hicom_multi_guide_local_adapt_fwd on the chunk; then launches 2 ... of hicom_compressor_stream_push_multi
+ * unchanged.  Every check of that entry point and of the two parts runs in front of the first launch.  Nothing is allocated, copied or
+ * synchronised.
+ *   base         : the plain block, every field as there.  The k adaptor reads fe (ff when fe is NULL), the v adaptor ff
+ *   ak, av       : w0 == NULL: that stream is not adapted (at least one is); every field of an adapted stream is read
+ *   ky, vy       : fp16 [N, E] planes of ONE chunk, 16-byte aligned, written and read by this call; NULL exactly for a stream without
+ *                  adaptor (HICOM_EINVAL otherwise)
+ *   adapt_ws     : hicom_clip_adapt_prepare_workspace_bytes(N, E, ak, av) bytes, 256-byte aligned (the hidden planes of layer 1)
+ *   alpha_dt, eps: as in hicom_compressor_multiguide_adapt_args
+ * E % 64 == 0 and N E < 2^32 per chunk (the dense GEMM's operand limit), HICOM_EUNSUP otherwise. */
+typedef struct hicom_stream_push_multi_adapt_args {
+    hicom_stream_push_multi_args base;
+    hicom_seg_adaptor ak, av;
+    void* ky;
+    void* vy;
+    void* adapt_ws;
+    int64_t adapt_ws_bytes;
+    int32_t alpha_dt;
+    float eps;
+} hicom_stream_push_multi_adapt_args;
+int hicom_compressor_stream_push_multi_adapt(const hicom_stream_push_multi_adapt_args* args);
+
 #ifdef __cplusplus
 }
 #endif
