@@ -580,15 +580,17 @@ static int check_window_call(const char* who, int D, hicom_axis at, hicom_axis a
     return HICOM_OK;
 }
 
-// the forward's and the plain backward's limits on a window and on the grid
-static int check_window_limits(const char* who, long win, long nwin) {
+// LDS of a window kernel: n_arrays per-token float arrays of the window, then the [4][D] slab of partial rows
+static size_t window_smem(long win, int D, int n_arrays) { return n_arrays * (((size_t)win + 3) & ~(size_t)3) * 4 + 4 * (size_t)D * 4; }
+
+// the forward's and the plain backward's limits on a window and on the grid.  smem: the caller's window_smem -- the kernels take it as
+// dynamic LDS and nothing here raises the 64-KB default, so it stays under the bound merge.hip uses for its dynamic LDS.
+static int check_window_limits(const char* who, long win, long nwin, size_t smem) {
     HICOM_REQUIRE(win <= 4096, HICOM_EUNSUP, "%s: window of %ld tokens is too large", who, win);
+    HICOM_REQUIRE(smem <= 60000, HICOM_EUNSUP, "%s: window of %ld tokens needs %zu bytes of LDS (at most 60000)", who, win, smem);
     HICOM_REQUIRE(nwin < (1L << 31), HICOM_EINVAL, "%s: too many windows", who);
     return HICOM_OK;
 }
-
-// LDS of a window kernel: n_arrays per-token float arrays of the window, then the [4][D] slab of partial rows
-static size_t window_smem(long win, int D, int n_arrays) { return n_arrays * (((size_t)win + 3) & ~(size_t)3) * 4 + 4 * (size_t)D * 4; }
 
 // kernel<NV> for D = NV * 384 (D was checked: 1152 or 768)
 #define LAUNCH_BY_WIDTH(kernel, D, grid, smem, stream, ...)                                                \
@@ -607,7 +609,7 @@ extern "C" int hicom_local_attn_fwd(const void* key, int32_t key_dt, const void*
     HICOM_REQUIRE(key_dt >= 0 && key_dt <= 2 && value_dt >= 0 && value_dt <= 2, HICOM_EINVAL, "local_attn: stream dtype");
     long win, nwin;
     if (int rc = check_window_call("local_attn", D, at, ay, ax, false, win, nwin)) return rc;
-    if (int rc = check_window_limits("local_attn", win, nwin)) return rc;
+    if (int rc = check_window_limits("local_attn", win, nwin, window_smem(win, D, 1))) return rc;
     LocalParams p{key, value, key_dt, value_dt, query, query_dt == HICOM_DT_F32,
                   (long)query_stride, at, ay, ax, scale, bias, l2norm, ctx, (_Float16*)ctx_f16};
     LAUNCH_BY_WIDTH(local_attn_kernel, D, dim3((unsigned)nwin), window_smem(win, D, 1), (hipStream_t)stream, p);
@@ -626,7 +628,7 @@ extern "C" int hicom_local_attn_adapt_fwd(const void* key_x, const void* key_y, 
     HICOM_REQUIRE(alpha_dt == HICOM_DT_BF16 || alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "local_attn_adapt: alpha dtype");
     long win, nwin;
     if (int rc = check_window_call("local_attn_adapt", D, at, ay, ax, false, win, nwin)) return rc;
-    if (int rc = check_window_limits("local_attn_adapt", win, nwin)) return rc;
+    if (int rc = check_window_limits("local_attn_adapt", win, nwin, window_smem(win, D, 1))) return rc;
     LocalAdaptParams p{(const uint16_t*)key_x, (const _Float16*)key_y, (const uint16_t*)k_gamma, (const uint16_t*)k_beta, k_alpha,
                        (const uint16_t*)value_x, (const _Float16*)value_y, (const uint16_t*)v_gamma, (const uint16_t*)v_beta, v_alpha,
                        alpha_dt == HICOM_DT_F32, eps, query, query_dt == HICOM_DT_F32, (long)query_stride, at, ay, ax, scale, bias, ctx};
@@ -643,7 +645,7 @@ extern "C" int hicom_local_attn_bwd(const void* key, const void* value, int32_t 
     HICOM_REQUIRE(query_dt == HICOM_DT_BF16 || query_dt == HICOM_DT_F32, HICOM_EINVAL, "local_attn_bwd: query dtype");
     long win, nwin;
     if (int rc = check_window_call("local_attn_bwd", D, at, ay, ax, false, win, nwin)) return rc;
-    if (int rc = check_window_limits("local_attn_bwd", win, nwin)) return rc;
+    if (int rc = check_window_limits("local_attn_bwd", win, nwin, window_smem(win, D, 5))) return rc;
     LocalBwdParams p{(const uint16_t*)key, (const uint16_t*)value, query, query_dt == HICOM_DT_F32, (long)query_stride, at, ay, ax,
                      scale, bias, dctx, dq, (uint16_t*)dkey, l2norm_key ? 1 : 0, dls, (uint16_t*)dvalue, value_is_key ? 1 : 0, 0, 0, 0};
     HICOM_REQUIRE(!(value_is_key && dkey), HICOM_EINVAL, "local_attn_bwd: value_is_key writes the summed gradient to dvalue (dkey must be NULL)");

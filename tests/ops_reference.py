@@ -450,3 +450,188 @@ def query_prep_ref(guide, w_q, b_q, w_k, kpe, nh, scale, g_w0, g_b0, b_o):
     if g_w0 is not None:
         r0, r0_ab = g_w0 @ (b_o + guide) + g_b0, g_w0.abs() @ (b_o.abs() + guide.abs()) + g_b0.abs()
     return (qt, pa, r0), (qt_ab, pa_ab, r0_ab)
+
+
+# ---- window attention (hicom_local_attn_fwd / _adapt_fwd / _bwd) and the pooled per-window queries ------------------------------
+def window_axis(n, k):
+    """(k, nwin, nfull) of one axis, restated from the balance rule the kernels are handed: n a multiple of k: n / k full windows;
+    otherwise ceil(n / k) windows of which the first nfull = n mod nwin (or all) are full and every other one shares ONE element with
+    its predecessor.  (n < k: one short window.)"""
+    if n % k == 0:
+        return k, n // k, n // k
+    if n < k:
+        return n, 1, 1
+    nwin = -(-n // k)
+    nfull = n % nwin or nwin
+    assert nfull * k + (nwin - nfull) * (k - 1) == n, (n, k)
+    return k, nwin, nfull
+
+
+def window_axis_starts(n, k, wrong_overlap=False):
+    """Start of every window of an axis (csrc/window_rows.hpp, axis_start): i k for i < nfull, else nfull k + (i - nfull)(k - 1) - 1.
+    wrong_overlap plants the `- 1` dropped."""
+    k, nwin, nfull = window_axis(n, k)
+    return [i * k if i < nfull else nfull * k + (i - nfull) * (k - 1) - (0 if wrong_overlap else 1) for i in range(nwin)]
+
+
+def window_tokens(T, H, W, kt, ks, wrong_overlap=False):
+    """tok [NW, WIN]: token index of position i of window w; windows t-major over (t1, h1, w1), positions t-major over (t2, h2, w2),
+    the flat index ((t0 + t2) H + y0 + h2) W + x0 + w2 as WindowGeom::token_of forms it.  Second value: the windows' (t1, h1, w1)
+    [NW, 3].  (With wrong_overlap the last window runs one element off its axis; the flat index is kept below T H W.)"""
+    axes = [(window_axis(n, k)[0], window_axis_starts(n, k, wrong_overlap)) for n, k in ((T, kt), (H, ks), (W, ks))]
+    (ktt, st), (ky, sy), (kx, sx) = axes
+    t2, h2, w2 = torch.meshgrid(torch.arange(ktt), torch.arange(ky), torch.arange(kx), indexing="ij")
+    t2, h2, w2 = t2.reshape(-1), h2.reshape(-1), w2.reshape(-1)
+    tok, idx = [], []
+    for a, t0 in enumerate(st):
+        for b, y0 in enumerate(sy):
+            for c, x0 in enumerate(sx):
+                tok.append(((t0 + t2) * H + (y0 + h2)) * W + (x0 + w2))
+                idx.append((a, b, c))
+    return torch.stack(tok).clamp_(max=T * H * W - 1), torch.tensor(idx)
+
+
+def window_launch_classes(T, H, W, kt, ks):
+    """Launch order of the backward's per-token outputs: None for an exact partition (one launch, plain stores); otherwise the list
+    of window-index tensors per launch, parity class val = 0 .. 7 of (t1 & 1) | (h1 & 1) << 1 | (w1 & 1) << 2 restricted to the axes
+    that overlap (windows of one class share no token)."""
+    mask = sum(1 << a for a, (n, k) in enumerate(((T, kt), (H, ks), (W, ks))) if window_axis(n, k)[1] * window_axis(n, k)[0] != n)
+    if not mask:
+        return None
+    _, idx = window_tokens(T, H, W, kt, ks)
+    cls = ((idx[:, 0] & 1) | ((idx[:, 1] & 1) << 1) | ((idx[:, 2] & 1) << 2)) & mask
+    return [torch.nonzero(cls == val).reshape(-1) for val in range(8) if not (val & ~mask)]
+
+
+def _window_softmax(s, lost, stats_limit):
+    s = s.clone()
+    s[:, list(lost)] = -math.inf
+    n = s.shape[1] if stats_limit is None else min(stats_limit, s.shape[1])
+    mx = s[:, :n].max(1, keepdim=True).values
+    e = torch.exp(s - mx)
+    return e / e[:, :n].sum(1, keepdim=True), mx
+
+
+def window_attention_ref(key, value, query, geom, scale, bias, l2norm=0, lost=(), stats_limit=None, wrong_overlap=False,
+                         key_ab=None, value_ab=None):
+    """hicom_local_attn_fwd (and, on blend_rows' rows, hicom_local_attn_adapt_fwd) in float64.  key, value [N, D] per token, already
+    up-cast; query [NW, D] per window (a shared query repeated); geom = (T, H, W, kt, ks).
+        s[w, i] = scale (q_w . k_n) / (|k_n| if l2norm & 1) / (|q_w| if l2norm & 2) + bias,  n = tok[w, i];   p = softmax_i s;
+        ctx_w = sum_i p[w, i] v_n.
+    key_ab / value_ab: the rows' absolute terms where a row is itself a sum (the adaptor blend); default |key|, |value|.
+    lost (window positions out of the softmax), stats_limit (maximum and sum over the first n positions only) and wrong_overlap
+    plant the defects of tests/test_window_attn_power.py.  Returns a dict: ctx, p, s, tok, and the absolute-term sums s_ab (of
+    s - bias) and ctx_ab."""
+    tok, _ = window_tokens(*geom, wrong_overlap=wrong_overlap)
+    K, V = key[tok], value[tok]                                                  # [NW, WIN, D]
+    Kab = K.abs() if key_ab is None else key_ab[tok]
+    Vab = V.abs() if value_ab is None else value_ab[tok]
+    den = torch.ones(tok.shape, dtype=torch.float64)
+    if l2norm & 1:
+        den = den * K.norm(dim=2)
+    if l2norm & 2:
+        den = den * query.norm(dim=1, keepdim=True)
+    s = scale * torch.einsum("wid,wd->wi", K, query) / den + bias
+    s_ab = abs(scale) * torch.einsum("wid,wd->wi", Kab, query.abs()) / den
+    p, mx = _window_softmax(s, lost, stats_limit)
+    return {"tok": tok, "s": s, "s_ab": s_ab, "p": p, "mx": mx, "ctx": torch.einsum("wi,wid->wd", p, V),
+            "ctx_ab": torch.einsum("wi,wid->wd", p, Vab)}
+
+
+def window_attention_bwd_ref(key, value, query, dctx, geom, scale, bias, l2norm_key=False, value_is_key=False, use_delta=True,
+                             drop_kc=False, overwrite_shared=False, lost=(), key_grad_in_dvalue=True, stats_limit=None, wrong_overlap=False):
+    """hicom_local_attn_bwd in closed form (the kernel's header comment), float64.  Per window, khat_i = k_i / |k_i| with l2norm_key
+    (else k_i), r_i = 1 / |k_i| (else 1):
+        s_i = scale q . khat_i + bias,  p = softmax(s),  dP_i = dctx_w . v_i,  delta = sum_j p_j dP_j,  dS_i = p_i (dP_i - delta)
+        dq_w = scale sum_i dS_i khat_i,    dls_w = sum_i dS_i (s_i - bias)
+        dk_i = dsk_i q - kc_i k_i,  dsk_i = scale dS_i r_i,  kc_i = dsk_i (q . khat_i) r_i  (0 without l2norm_key)
+        dv_i = p_i dctx_w  (+ dk_i with value_is_key)
+    dkey / dvalue [N, D] sum the windows that hold a token.  `steps`: the per-token contributions in launch order -- one entry per
+    launch (window_launch_classes; a single one for an exact partition) with the tokens it writes (each once) and the rows it adds,
+    and their absolute terms -- which the bf16 read-modify-write bound needs.
+    use_delta, drop_kc, overwrite_shared (a shared token keeps only its last contribution), lost (window positions out of the
+    softmax: no contribution anywhere), key_grad_in_dvalue, stats_limit and wrong_overlap (as in the forward) plant defects."""
+    T, H, W, kt, ks = geom
+    N, D = key.shape
+    tok, _ = window_tokens(*geom, wrong_overlap=wrong_overlap)
+    NW, WIN = tok.shape
+    K, V = key[tok], value[tok]
+    r = 1.0 / K.norm(dim=2) if l2norm_key else torch.ones(NW, WIN, dtype=torch.float64)
+    sraw = torch.einsum("wid,wd->wi", K, query) * r
+    sraw_ab = torch.einsum("wid,wd->wi", K.abs(), query.abs()) * r
+    s = scale * sraw + bias
+    p, mx = _window_softmax(s, lost, stats_limit)
+    dP, dP_ab = torch.einsum("wid,wd->wi", V, dctx), torch.einsum("wid,wd->wi", V.abs(), dctx.abs())
+    delta = (p * dP).sum(1, keepdim=True) if use_delta else torch.zeros(NW, 1, dtype=torch.float64)
+    dS = p * (dP - delta)
+    dsk = scale * dS * r
+    kc = torch.zeros_like(dsk) if (not l2norm_key or drop_kc) else dsk * sraw * r
+    o = {"tok": tok, "s": s, "s_ab": abs(scale) * sraw_ab, "sraw": sraw, "sraw_ab": sraw_ab, "r": r, "p": p, "mx": mx, "dP": dP,
+         "dP_ab": dP_ab, "delta": delta, "dS": dS, "dsk": dsk, "kc": kc}
+    o["dq"], o["dq_ab"] = torch.einsum("wi,wid->wd", dsk, K), torch.einsum("wi,wid->wd", dsk.abs(), K.abs())
+    o["dls"], o["dls_ab"] = (dS * (s - bias)).sum(1), (dS * (s - bias)).abs().sum(1)
+    dk = dsk[:, :, None] * query[:, None, :] - kc[:, :, None] * K
+    dk_ab = dsk.abs()[:, :, None] * query.abs()[:, None, :] + kc.abs()[:, :, None] * K.abs()
+    dv, dv_ab = p[:, :, None] * dctx[:, None, :], p[:, :, None] * dctx.abs()[:, None, :]
+    if value_is_key and key_grad_in_dvalue:
+        dv, dv_ab = dv + dk, dv_ab + dk_ab
+    o["dk_rows"], o["dv_rows"] = dk, dv
+    classes = window_launch_classes(*geom)
+    launches = [torch.arange(NW)] if classes is None else classes
+    o["steps"] = []
+    o["dkey"], o["dvalue"] = torch.zeros(N, D, dtype=torch.float64), torch.zeros(N, D, dtype=torch.float64)
+    for ws in launches:
+        if ws.numel() == 0:
+            continue
+        t = tok[ws].reshape(-1)
+        assert wrong_overlap or t.unique().numel() == t.numel(), "windows of one launch share a token"
+        step = {"tok": t, "win": ws, "dk": dk[ws].reshape(-1, D), "dk_ab": dk_ab[ws].reshape(-1, D), "dv": dv[ws].reshape(-1, D),
+                "dv_ab": dv_ab[ws].reshape(-1, D)}
+        o["steps"].append(step)
+        for name, rows in (("dkey", step["dk"]), ("dvalue", step["dv"])):
+            if overwrite_shared:
+                o[name][t] = rows
+            else:
+                o[name].index_add_(0, t, rows)
+    return o
+
+
+def _pool_taps(n_in, n_out):
+    """PyTorch's align_corners=False source index (area_pixel_compute_source_index), clamped at 0: (i0, i1, lam) per output index."""
+    src = ((torch.arange(n_out, dtype=torch.float64) + 0.5) * (n_in / n_out) - 0.5).clamp_min(0.0)
+    i0 = src.floor().long().clamp_max(n_in - 1)
+    i1 = (i0 + 1).clamp_max(n_in - 1)
+    return i0, i1, src - i0
+
+
+def trilinear_pool_ref(x, To, Ho, Wo, second_tap_is_first=False):
+    """hicom_trilinear_pool_fwd in float64: x [T, H, W, D] -> [To, Ho, Wo, D], taps and lerp nested t, then h, then w.  Also returns
+    the same expression on absolute values, and per axis |upper neighbour - tap 0| + |tap 0 - lower neighbour| of the partially
+    interpolated field (what an error of that axis' source index is multiplied by, on whichever side of an integer it falls).
+    second_tap_is_first plants a defect (tests/test_window_attn_power.py)."""
+    def lerp(v, dim, n_out):
+        n_in = v.shape[dim]
+        i0, i1, lam = _pool_taps(n_in, n_out)
+        if second_tap_is_first:
+            i1 = i0
+        shape = [1] * v.dim()
+        shape[dim] = n_out
+        lam = lam.reshape(shape)
+        a, b = v.index_select(dim, i0), v.index_select(dim, i1)
+        return a * (1 - lam) + b * lam
+
+    def absl(v, dim, n_out):
+        return lerp(v.abs(), dim, n_out)
+
+    def slope(v, dim, n_out):
+        n_in = v.shape[dim]
+        i0, _, _ = _pool_taps(n_in, n_out)
+        a = v.index_select(dim, i0)
+        return (v.index_select(dim, (i0 + 1).clamp_max(n_in - 1)) - a).abs() + (a - v.index_select(dim, (i0 - 1).clamp_min(0))).abs()
+
+    out = lerp(lerp(lerp(x, 0, To), 1, Ho), 2, Wo)
+    ab = absl(absl(absl(x, 0, To), 1, Ho), 2, Wo)
+    sl_t = absl(absl(slope(x, 0, To), 1, Ho), 2, Wo)
+    sl_h = absl(slope(lerp(x, 0, To), 1, Ho), 2, Wo)
+    sl_w = slope(lerp(lerp(x, 0, To), 1, Ho), 2, Wo)
+    return out, ab, (sl_t, sl_h, sl_w)

@@ -462,3 +462,101 @@ def test_dense16_tn_reference_and_slice_sums():
     assert _maxabs(R.dense16_tn_ref(a, b, 8, 16, k_rows=slice(0, 4)), sum(torch.outer(a[k, :8], b[k, :16]) for k in range(4))) <= 1e-13
     v = torch.arange(2 * 70, dtype=torch.float64).reshape(2, 70)
     assert R.slice_sums(v).tolist() == [[float(v[0, :64].sum()), float(v[1, :64].sum())], [float(v[0, 64:].sum()), float(v[1, 64:].sum())]]
+
+
+# ---- window attention and the pooled queries (tests/test_gpu_window_attn.py) --------------------------------------------------
+def _gathered_window_attention(key, value, q, tok, scale, bias, l2norm_key):
+    """Autograd's view: gather the windows' rows, softmax per window, contexts; returns (ctx, s)."""
+    K, V = key[tok], value[tok]
+    if l2norm_key:
+        K = K / K.norm(dim=2, keepdim=True)
+    s = scale * torch.einsum("wid,wd->wi", K, q) + bias
+    return torch.einsum("wi,wid->wd", torch.softmax(s, 1), V), s
+
+
+@pytest.mark.parametrize("l2norm_key", [False, True])
+@pytest.mark.parametrize("geom,shared,value_is_key", [((3, 7, 5, 2, 3), True, False), ((3, 7, 5, 2, 3), False, True),
+                                                      ((4, 4, 6, 2, 2), False, False), ((4, 4, 6, 2, 2), True, True)])
+def test_window_attention_references_equal_autograd_through_a_gathered_window_softmax(geom, shared, value_is_key, l2norm_key):
+    """One overlapping geometry (every axis) and one exact one: contexts, dq, dkey, dvalue (also with the key-side gradient added) and
+    dls against float64 autograd, <= 1e-12 relative."""
+    T, H, W, kt, ks = geom
+    D, bias = 12, 0.25
+    g = torch.Generator().manual_seed(T * 10 + H + int(l2norm_key))
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    N = T * H * W
+    tok, idx = R.window_tokens(*geom)
+    NW = tok.shape[0]
+    # the restated geometry: every token covered, shared planes only where an axis is not divided
+    assert sorted(set(tok.reshape(-1).tolist())) == list(range(N))
+    assert (tok.numel() == N) == (T % kt == 0 and H % ks == 0 and W % ks == 0)
+    key, q0, dctx = rnd(N, D).requires_grad_(True), rnd(1 if shared else NW, D), rnd(NW, D)
+    value = key if value_is_key else rnd(N, D).requires_grad_(True)
+    q = q0.expand(NW, D).clone().requires_grad_(True)
+    ls = torch.tensor(math.log(3.0) if l2norm_key else math.log(0.3), dtype=torch.float64, requires_grad=True)
+    ctx, s = _gathered_window_attention(key, value, q, tok, torch.exp(ls), bias, l2norm_key)
+    (ctx * dctx).sum().backward()
+    scale = float(torch.exp(ls.detach()))
+    rel = lambda a, b: _maxabs(a, b) / max(1.0, float(b.abs().max()))
+    fw = R.window_attention_ref(key.detach(), value.detach(), q.detach(), geom, scale, bias, l2norm=1 if l2norm_key else 0)
+    assert rel(fw["ctx"], ctx.detach()) <= 1e-12 and rel(fw["s"], s.detach()) <= 1e-12
+    assert bool((fw["s_ab"] + abs(bias) >= fw["s"].abs() - 1e-12).all()) and bool((fw["ctx_ab"] >= fw["ctx"].abs() - 1e-12).all())
+    bw = R.window_attention_bwd_ref(key.detach(), value.detach(), q.detach(), dctx, geom, scale, bias, l2norm_key=l2norm_key,
+                                    value_is_key=value_is_key)
+    assert rel(bw["dq"], q.grad) <= 1e-12
+    assert rel(bw["dls"].sum(), ls.grad) <= 1e-12                      # d s / d ls = s - bias, summed over the windows
+    if value_is_key:
+        assert rel(bw["dvalue"], key.grad) <= 1e-12                    # the key-side gradient of the same rows is added in
+    else:
+        assert rel(bw["dkey"], key.grad) <= 1e-12 and rel(bw["dvalue"], value.grad) <= 1e-12
+    # the contribution list sums to the outputs, one launch for an exact partition, parity classes otherwise
+    exact = tok.numel() == N
+    assert len(bw["steps"]) == (1 if exact else 8)
+    tot = torch.zeros(N, D, dtype=torch.float64)
+    for st in bw["steps"]:
+        tot.index_add_(0, st["tok"], st["dk"])
+    assert _maxabs(tot, bw["dkey"]) <= 1e-12
+    # the forward's other l2norm bit and the planted switches do what they say
+    f2 = R.window_attention_ref(key.detach(), value.detach(), q.detach(), geom, scale, bias, l2norm=2)
+    qn = q.detach() / q.detach().norm(dim=1, keepdim=True)
+    assert rel(f2["ctx"], R.window_attention_ref(key.detach(), value.detach(), qn, geom, scale, bias)["ctx"]) <= 1e-12
+    assert rel(R.window_attention_ref(key.detach(), value.detach(), q.detach(), geom, scale, bias + 95.0, l2norm=int(l2norm_key))["ctx"],
+               fw["ctx"]) <= 1e-9                                       # invariant to the bias
+    lost = R.window_attention_ref(key.detach(), value.detach(), q.detach(), geom, scale, bias, l2norm=int(l2norm_key), lost=(0,))
+    assert float(lost["p"][:, 0].abs().max()) == 0.0 and _maxabs(lost["p"].sum(1), torch.ones(NW, dtype=torch.float64)) <= 1e-12
+    lim = R.window_attention_ref(key.detach(), value.detach(), q.detach(), geom, scale, bias, l2norm=int(l2norm_key), stats_limit=5)
+    assert _maxabs(lim["p"][:, :5].sum(1), torch.ones(NW, dtype=torch.float64)) <= 1e-12 and float(lim["p"].sum(1).min()) > 1.0
+    if not exact:
+        assert not torch.equal(R.window_tokens(*geom, wrong_overlap=True)[0], tok)
+
+
+def test_window_geometry_restated():
+    assert R.window_axis(7, 3) == (3, 3, 1) and R.window_axis_starts(7, 3) == [0, 2, 4]
+    assert R.window_axis(8, 3) == (3, 3, 2) and R.window_axis_starts(8, 3) == [0, 3, 5]
+    assert R.window_axis(7, 4) == (4, 2, 1) and R.window_axis_starts(7, 4) == [0, 3]
+    assert R.window_axis_starts(7, 3, wrong_overlap=True) == [0, 3, 5]
+    assert R.window_axis(6, 3) == (3, 2, 2) and R.window_axis(2, 3) == (2, 1, 1)
+    tok, idx = R.window_tokens(2, 4, 4, 1, 2)
+    assert tok[0].tolist() == [0, 1, 4, 5] and tok[1].tolist() == [2, 3, 6, 7] and tok[4].tolist() == [16, 17, 20, 21]
+    assert idx[5].tolist() == [1, 0, 1]
+    assert torch.equal(R.window_of_token(2, 4, 4, 1, 2)[tok], torch.arange(8)[:, None].expand(8, 4))
+    cls = R.window_launch_classes(7, 7, 5, 4, 3)
+    assert len(cls) == 8 and sorted(torch.cat(cls).tolist()) == list(range(12)) and R.window_launch_classes(8, 6, 6, 4, 3) is None
+    assert [c.tolist() for c in R.window_launch_classes(4, 8, 3, 4, 3)] == [[0, 2], [1]]            # only y overlaps: classes 0 and 2
+
+
+@pytest.mark.parametrize("shape,out", [((7, 7, 5), (2, 3, 2)), ((4, 27, 27), (1, 9, 9)), ((8, 6, 6), (8, 6, 6)), ((1, 6, 6), (1, 2, 2)),
+                                       ((5, 3, 2), (2, 1, 1))])
+def test_trilinear_pool_reference_equals_torch_interpolate(shape, out):
+    g = torch.Generator().manual_seed(sum(shape))
+    x = torch.randn(*shape, 8, generator=g, dtype=torch.float64)
+    want = torch.nn.functional.interpolate(x.permute(3, 0, 1, 2)[None], size=out, mode="trilinear", align_corners=False)[0].permute(1, 2, 3, 0)
+    got, ab, slopes = R.trilinear_pool_ref(x, *out)
+    assert _maxabs(got, want) <= 1e-12
+    assert bool((ab >= got.abs() - 1e-12).all()) and all(s.shape == got.shape for s in slopes)
+    if shape == out:
+        assert torch.equal(got, x)
+    # the planted defect shows wherever a second tap has weight ((1, 6, 6) -> (1, 2, 2): every source index is a grid point)
+    on_grid = all(float(R._pool_taps(n, m)[2].abs().max()) == 0.0 for n, m in zip(shape, out))
+    assert on_grid == (shape in ((8, 6, 6), (1, 6, 6)))
+    assert (_maxabs(R.trilinear_pool_ref(x, *out, second_tap_is_first=True)[0], got) > 0.1) == (not on_grid)
