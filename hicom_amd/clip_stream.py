@@ -19,16 +19,21 @@ and does not consume it: more pushes and another finish() give the longer clip's
 
 Nothing token-sized is allocated: the output buffer (for max_frames), the state, the query operands and the positional tables at open; the
 per-chunk workspace (partials, the fp16 context and hidden planes of ONE chunk) with the plan, on first use of a chunk length.  Plans are cached
-on the module (`proj._clip_stream_plans`) per (Tc, H, W, E, has frames_embed, newline, out dtype, stream) through segments.cached_plan; the
+on the module (`proj._clip_stream_plans`) per (Q, Tc, H, W, E, has frames_embed, newline, out dtype, stream) through segments.cached_plan; the
 frame offset, the row offset and everything that belongs to a stream (queries, tables, state, output) are patched per push, so a stream of
 equal chunks builds one plan and two streams of one module share it.  Everything runs on the caller's current stream.
 
 Scope: that of forward_multi_guide (the plain release recipe, a bf16 module with bf16 CUDA inputs, inference only) on the geometry the fused
 ring kernel takes (H % ks == W % ks == 0, 16 <= kt ks ks <= 64, E == 1152, at most 12 folded rows, hidden % 64 == 0).
 
-HIComProjector.open_stream_multi (ClipStreamMulti, behind ClipStream in this file) is the same stream for Q guides known up
-front: every chunk is read once for all of them.  HIComProjector.open_stream_adapt (ClipStreamAdapt, at the end of this file)
-is that stream for the k / v adaptor recipe: the adaptor MLPs run once per chunk for all Q guides."""
+HIComProjector.open_stream_multi (ClipStreamMulti) is the same stream for Q guides known up front: every chunk is read once
+for all of them.  HIComProjector.open_stream_adapt (ClipStreamAdapt, at the end of this file) is that stream for the
+k / v adaptor recipe: the adaptor MLPs run once per chunk for all Q guides.
+
+Who holds what: ClipStreamBase has the host side of all three once -- the open sequence, the chunk checks, push, finish, reset, `rows`,
+the plan key and store, and the fields of the push block that every native push takes (_fill_common per plan, _patch_common per push).
+A class names itself (NAME, WHAT, STORE, RECIPE, RECIPE_WORDS, MULTI, GUIDE) and holds its device side: _allocate, _prepare, _build_plan,
+_launch, _finish_device, and the limits of a chunk (_chunk_limits)."""
 from __future__ import annotations
 
 import math
@@ -39,7 +44,9 @@ from . import native as nv
 from . import segments as seg
 
 STORE = "_clip_stream_plans"
-WHAT = "open_stream"
+STORE_MULTI = "_clip_stream_multi_plans"
+STORE_ADAPT = "_clip_stream_adapt_plans"
+MAX_PARTS = 256                                  # token chunks of the many-row global stream (csrc/clip_stream.hip: kMaxStreamParts)
 
 
 def _require_bf16_cuda(name, t):
@@ -65,12 +72,14 @@ def chunk_rows(proj, groups0, groups, gh, gw, has_newline):
     return row0, lay.nl_group, newline, row1
 
 
-def stream_scope(proj, guide, H, W, max_frames, nl, WHAT=WHAT, multi=False, recipe="plain"):
-    """Raises for everything outside the scope of a clip stream, in front of any device work; returns (E, kt, ks, hidden, heads).  multi: the
-    guide is the [Q, E] block of open_stream_multi (WHAT names the entry in the messages).  recipe: the segments.seg_recipe the entry is
-    built for ("adaptkv": open_stream_adapt)."""
-    if seg.seg_recipe(proj) != recipe:
-        if recipe == "adaptkv":
+def stream_scope(proj, guide, H, W, max_frames, nl, cls=None):
+    """Raises for everything outside the scope of a clip stream, in front of any device work; returns (E, kt, ks, hidden, heads).  cls: the
+    stream class (None: ClipStream) -- its WHAT names the entry in the messages, MULTI says that the guide is the [Q, E] block of
+    open_stream_multi, RECIPE is the segments.seg_recipe the entry is built for ("adaptkv": open_stream_adapt)."""
+    cls = cls or ClipStream
+    WHAT = cls.WHAT
+    if seg.seg_recipe(proj) != cls.RECIPE:
+        if cls.RECIPE == "adaptkv":
             raise NotImplementedError(f"{WHAT} is built for the two release recipes only (local + global compressor, use_guide='direct', no "
                                       "adaptors but adapt_k / adapt_v on the local stage, no clip scale); everything else goes through "
                                       "forward() on the whole clip")
@@ -81,7 +90,7 @@ def stream_scope(proj, guide, H, W, max_frames, nl, WHAT=WHAT, multi=False, reci
     if wdt != torch.bfloat16:
         raise NotImplementedError(f"{WHAT}: a {wdt} projector; the clip stream takes a bfloat16 module and bfloat16 inputs")
     E, hidden, nh = gc.embed_dim, lc.readout[2].out_features, gc.attn_layer.num_heads
-    if multi:
+    if cls.MULTI:
         from .multi_guide import count_guides
         count_guides(WHAT, guide, E)
     elif not isinstance(guide, torch.Tensor) or tuple(guide.shape) != (E,):
@@ -109,6 +118,33 @@ def stream_scope(proj, guide, H, W, max_frames, nl, WHAT=WHAT, multi=False, reci
     return E, kt, ks, hidden, nh
 
 
+def multi_chunk_limits(what, Tc, H, W, use_pos_emb):
+    """The LDS limits of the merge kernels (csrc/merge.hip) applied to ONE chunk of Tc frames, with the largest number of token chunks a plan
+    may choose: NotImplementedError in front of any device work (hicom_compressor_stream_push_multi checks the same with the plan's own)."""
+    if not use_pos_emb:
+        return
+    if H + W > 1024 or not ((H <= 32 and W <= 32) or (H * W + H + 4) * 4 <= 60000):
+        raise NotImplementedError(f"{what}: a {H}x{W} grid: the merge keeps a frame of logits in LDS")
+    if (MAX_PARTS + 2 * Tc + H + W + 64 * (H + W + 2) + 16 * 64 + 4) * 4 > 60000:
+        raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the merge keeps the row's Tc + H + W weights and 64 frames of "
+                                  "marginals in LDS; push shorter chunks")
+
+
+def adaptor_widths(what, lc):
+    """The width condition of segments.fill_adaptors, from the parameters' shapes alone: in front of any device work."""
+    from . import engine
+    for _, mlp, _, _ in engine.adaptor_streams(lc):
+        w0, w2 = mlp[0].weight, mlp[2].weight
+        if w0.shape[0] % 64 or w0.shape[1] % 64 or w2.shape[0] % 64 or w0.shape != w2.shape:
+            raise NotImplementedError(f"{what}: adaptor widths must be multiples of 64")
+
+
+def adapt_chunk_limit(what, Tc, H, W, E):
+    """The operand limit of the adaptor MLPs' dense GEMMs on ONE chunk (hicom_clip_adapt_prepare_fwd checks the same)."""
+    if Tc * H * W * E >= 1 << 32:
+        raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the adaptor GEMMs take operands below 2^32 elements; push shorter chunks")
+
+
 class StreamPlan:
     """What one chunk shape needs: the argument block with the module's fields filled and the workspace of ONE chunk."""
     __slots__ = ("args", "ws", "sig", "fresh", "refresh", "hits", "keep")
@@ -119,106 +155,86 @@ class StreamPlan:
         self.hits = 0
 
 
-class ClipStream:
-    """The object HIComProjector.open_stream returns (module docstring).  Attributes: `frames` pushed so far, `rows` local rows so far
-    (the whole-clip newline row of `one_token` included once finish() has written it), `out` the output buffer."""
-    NAME, WHAT = "ClipStream", WHAT                  # what the messages call the object and the entry that opens it
+class ClipStreamBase:
+    """The host side of the three clip streams (module docstring: who holds what).  Attributes: `frames` pushed so far, `rows` local rows so
+    far (the whole-clip newline row of `one_token` included once finish() has written it), `out` the output buffer for `cap_rows` local
+    rows + the global rows, `Q` guides (1: ClipStream), `guide` / `guides`, `n_pushes`, `has_fe`, `cur` (the (M, L) block a push reads)."""
+    NAME = WHAT = STORE = None                       # what the messages call the object and the entry that opens it; the plan store
     RECIPE, RECIPE_WORDS = "plain", "the plain release recipe"       # segments.seg_recipe of the modules the stream takes
+    MULTI, GUIDE = False, "guide_embed"              # the guide is [E] (kept as `guide`) / the [Q, E] block (`guides`); the argument's name
 
-    def __init__(self, proj, guide_embed, H, W, max_frames, image_newline=None):
+    def __init__(self, proj, guide, H, W, max_frames, image_newline=None):
         from .projector import _out_dtype, _refuse_grad
-        self.E, self.kt, self.ks, self.hidden, self.nh = stream_scope(proj, guide_embed, H, W, max_frames, image_newline)
-        _refuse_grad(proj, f"HIComProjector.{WHAT}")
-        _require_bf16_cuda("guide_embed", guide_embed)
+        self.E, self.kt, self.ks, self.hidden, self.nh = self._scope(proj, guide, H, W, max_frames, image_newline)
+        _refuse_grad(proj, f"HIComProjector.{self.WHAT}")
+        _require_bf16_cuda(self.GUIDE, guide)
         if image_newline is not None:
             _require_bf16_cuda("image_newline", image_newline)
         self.proj, self.H, self.W, self.max_frames = proj, H, W, max_frames
+        self.Q = guide.shape[0] if self.MULTI else 1
         self.gh, self.gw = H // self.ks, W // self.ks
         self.newline = None if image_newline is None else image_newline.contiguous()
-        self.device, self.out_dtype = guide_embed.device, _out_dtype(proj)
+        self.device, self.out_dtype = guide.device, _out_dtype(proj)
         self.has_fe = None                        # decided by the first push; every chunk of a clip agrees
         self.frames = 0
         self.n_pushes = 0
-        max_rows = proj._layout((max_frames // self.kt, self.gh, self.gw), "video", image_newline is not None, False).n_rows
+        self.cap_rows = proj._layout((max_frames // self.kt, self.gh, self.gw), "video", image_newline is not None, False).n_rows
         self.n_global = proj.global_compressor.num_queries
-        self._allocate(max_rows + self.n_global)
-        self._prepare(guide_embed)
+        self._allocate(self.cap_rows + self.n_global)
+        self._prepare(guide)
 
-    # -- device work: three methods, so that the host logic around them can be exercised without a device ---------------------------------
-    def _allocate(self, rows):
-        dev, E, gc = self.device, self.E, self.proj.global_compressor
-        self.out = torch.empty((rows, self.hidden), dtype=self.out_dtype, device=dev)
-        self.state_ml = torch.empty((2, self.nh, 2), dtype=torch.float32, device=dev)      # (M, L) ping-pong: read one, write the other
-        self.state_acc = torch.empty((1, self.nh, E), dtype=torch.float32, device=dev)
-        self.q_hi = torch.zeros((16, E), dtype=torch.bfloat16, device=dev)
-        self.q_lo = torch.zeros_like(self.q_hi)
-        self.qp_state = nv.query_prep_state(E, dev)
-        self.pos_a = self.pe_hi = self.pe_lo = None
-        self.P = self.y0 = self.x0 = 0
-        if gc.use_pos_emb:
-            # sized for max_frames: the y / x table offsets (cap, cap + H) never move while the stream lives; the stream keeps the tables
-            _, self.kpe, cap = gc.pos_and_kpe(self.max_frames, self.H, self.W, dev)
-            self.pe_hi, self.pe_lo = gc.pos_planes(self.max_frames, self.H, self.W, dev)
-            self.P, self.y0, self.x0 = self.pe_hi.shape[0], cap, cap + self.H
-            self.pos_a = torch.zeros((16, self.P), dtype=torch.float32, device=dev)
+    def _scope(self, proj, guide, H, W, max_frames, image_newline):
+        """stream_scope of the class and the limits of the shortest chunk: (E, kt, ks, hidden, heads)."""
+        dims = stream_scope(proj, guide, H, W, max_frames, image_newline, type(self))
+        self._chunk_limits(self.WHAT, proj, dims[1], H, W, dims[0])
+        return dims
 
-    def _prepare(self, guide):
-        """Everything that depends on the guide alone: q_proj, the fold, the score-side positional table and the local query rows in one
-        launch (hicom_query_prep_fwd), and the empty state.  Once per open_stream / reset, not per push."""
-        from .projector import _linear_params
-        gc = self.proj.global_compressor
-        att = gc.attn_layer
-        self.guide = guide.contiguous()
-        wq, bq = _linear_params(att.q_proj)
-        wk, _ = _linear_params(att.k_proj)
-        if gc.use_pos_emb:
-            gc.pos_and_kpe(self.max_frames, self.H, self.W, self.device)                   # (follows k_proj.weight in place)
-        nv.query_prep(self.guide, self.guide, wq, bq, wk, self.kpe if gc.use_pos_emb else None, self.nh, att.scale, self.q_hi, self.q_lo,
-                      self.pos_a, self.qp_state)
-        nv.stream_state_clear(self.state_ml, self.state_acc)
-        self.cur = 0
+    def _chunk_limits(self, what, proj, Tc, H, W, E):
+        """Hook: NotImplementedError for a chunk of Tc frames that the class's kernels do not take (at open: the shortest chunk)."""
 
-    def _build_plan(self, Tc, has_fe):
+    def _plan_key(self, Tc, has_fe, stream):
+        return (self.Q, Tc, self.H, self.W, self.E, has_fe, None if self.newline is None else tuple(self.newline.shape), self.out_dtype, stream)
+
+    def _fill_common(self, a, Tc, nparts, sizes):
+        """The fields that every push block has and the module and the chunk shape decide -- the geometry, the local scale, the readout
+        and the output's form -- and the workspace of ONE chunk: regions of `sizes` bytes, each rounded up to 256.  Returns (workspace, the
+        regions' addresses, the tensors the block points at)."""
         from .projector import _linear_params
         lc = self.proj.local_compressor
-        nw = (Tc // self.kt) * self.gh * self.gw
-        nparts = nv.fused_stream_nparts(nw)
-        E, hidden, dev = self.E, self.hidden, self.device
-
-        def up(n):
-            return (n + 255) // 256 * 256
-        sizes = [up(nparts * 16 * 4), up(nparts * 16 * 4), up(nparts * 16 * E * 4), up(nw * E * 2), up(nw * hidden * 2)]
-        ws = torch.empty((sum(sizes),), dtype=torch.uint8, device=dev)
-        offs = [sum(sizes[:i]) for i in range(len(sizes))]
-        a = nv.StreamPushArgs()
-        a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.rows, a.hidden, a.nparts = Tc, self.H, self.W, E, self.kt, self.ks, self.nh, hidden, nparts
+        offs, at = [], 0
+        for n in sizes:
+            offs.append(at)
+            at += (n + 255) // 256 * 256
+        ws = torch.empty((at,), dtype=torch.uint8, device=self.device)
+        a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.hidden, a.nparts = Tc, self.H, self.W, self.E, self.kt, self.ks, self.hidden, nparts
         a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
-        a.part_m, a.part_l, a.part_acc, a.ctx_f16, a.hid_f16 = (ws.data_ptr() + o for o in offs)
         w0h, w2h = lc.readout_f16()
         b0, b2 = _linear_params(lc.readout[0])[1], _linear_params(lc.readout[2])[1]
         a.lw0_f16, a.lw2_f16, a.lb0, a.lb2 = w0h.data_ptr(), w2h.data_ptr(), b0.data_ptr(), b2.data_ptr()
         a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
-        a.ldo = hidden
-        return StreamPlan(a, ws, [w0h, w2h, b0, b2], lc.readout_f16)
+        a.ldo = self.hidden
+        return ws, [ws.data_ptr() + o for o in offs], [w0h, w2h, b0, b2]
 
-    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
-        a = plan.args
+    def _patch_common(self, a, ff, fe, t0, row0, nl_group, newline_rows, stream):
+        """What changes from push to push in every push block: the chunk, its frame and row offsets, its newline rows and what belongs to
+        this stream (a plan serves every stream of the module)."""
         a.ff, a.fe, a.t0 = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), t0
         a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
         a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
-        a.pe_hi = self.pe_hi.data_ptr() if self.pe_hi is not None else None
-        a.pe_lo = self.pe_lo.data_ptr() if self.pe_lo is not None else None
         a.P, a.y_index0, a.x_index0 = self.P, self.y0, self.x0
         a.state_ml_in, a.state_ml_out = self.state_ml[self.cur].data_ptr(), self.state_ml[self.cur ^ 1].data_ptr()
         a.state_acc = self.state_acc.data_ptr()
         a.out, a.row0, a.nl_group = self.out.data_ptr(), row0, nl_group
         a.nl_count = len(newline_rows)
         a.newline = self.newline.data_ptr() if newline_rows else None
+        # Plans are shared, so both fields are set on every push.  Without newline rows nothing reads them: hicom_compressor_stream_push
+        # returns in front of hicom_scatter_rows_fwd and place_check / place_row stop at nl_count == 0.  With ONE row the step is
+        # nl_group + 1, which place_check asks for; the scatter kernel multiplies it by the row's index, 0, and its check wants it > 0.
+        a.nl_first, a.nl_step = 0, 1
         if newline_rows:
             a.nl_first = newline_rows[0]
-            a.nl_step = newline_rows[1] - newline_rows[0] if len(newline_rows) > 1 else 1
+            a.nl_step = newline_rows[1] - newline_rows[0] if len(newline_rows) > 1 else nl_group + 1
         a.stream = stream
-        nv.compressor_stream_push(a)
 
     # -- the public surface ---------------------------------------------------------------------------------------------------------------
     @property
@@ -253,73 +269,120 @@ class ClipStream:
         _require_bf16_cuda("frames_feature", ff)
         if fe is not None:
             _require_bf16_cuda("frames_embed", fe)
+        self._chunk_limits(what, self.proj, Tc, self.H, self.W, self.E)
         return Tc
 
     def push(self, frames_feature, frames_embed=None):
         """The next Tc frames of the clip (bf16 [Tc, H, W, E], Tc a positive multiple of kt; frames_embed None: the keys are
-        frames_feature).  Returns a view of this chunk's local output rows in their final place in the stream's output buffer, complete
-        on the caller's stream; the chunk is not referenced afterwards."""
+        frames_feature).  Returns a view of this chunk's local output rows in their final place in the stream's output buffer
+        ([chunk rows, hidden]; [Q, chunk rows, hidden], strided over q, for Q guides), complete on the caller's stream; the chunk is not
+        referenced afterwards."""
         Tc = self._check_chunk(frames_feature, frames_embed)
         ff = frames_feature.contiguous()
         fe = frames_embed.contiguous() if frames_embed is not None else None
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        key = (Tc, self.H, self.W, self.E, fe is not None, None if self.newline is None else tuple(self.newline.shape), self.out_dtype, stream)
-        plan = seg.cached_plan(self.proj, STORE, key, lambda: self._build_plan(Tc, fe is not None))
+        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(Tc, fe is not None, stream), lambda: self._build_plan(Tc, fe is not None))
         row0, nl_group, newline_rows, row1 = chunk_rows(self.proj, self.frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
         self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
         self.cur ^= 1
         self.has_fe = fe is not None
         self.frames += Tc
         self.n_pushes += 1
-        return self.out[row0:row1]
+        return self.out[:, row0:row1] if self.MULTI else self.out[row0:row1]
 
     def finish(self):
-        """[local rows so far + 32, hidden]: the rows that depend on the whole clip (a `one_token` newline row, the global rows) written
-        behind the local rows pushed so far.  A view of the stream's buffer; the state is not consumed."""
+        """[local rows so far + 32, hidden] ([Q, ...] for Q guides): the rows that depend on the whole clip (a `one_token` newline row, the
+        32 global rows of every guide) written behind the local rows pushed so far.  A view of the stream's buffer (strided over q); the
+        state is not consumed."""
         from .projector import _refuse_grad
         if self.frames == 0:
-            raise ValueError("ClipStream.finish: nothing has been pushed")
-        _refuse_grad(self.proj, "ClipStream.finish")
+            raise ValueError(f"{self.NAME}.finish: nothing has been pushed")
+        _refuse_grad(self.proj, f"{self.NAME}.finish")
         row0, lay = prefix_layout(self.proj, self.frames // self.kt, self.gh, self.gw, self.newline is not None)
-        if lay.n_rows > row0:                                                              # whole-clip newline rows (`one_token`)
-            nv.scatter_rows(self.newline.view(1, -1), self.out, row0, lay.n_rows - row0)
-        gc = self.proj.global_compressor
-        gc.finish(self.state_ml[self.cur:self.cur + 1], self.state_acc, self.guide.view(1, -1), self.out, lay.n_rows, self.n_global)
-        return self.out[:lay.n_rows + self.n_global]
+        self._finish_device(row0, lay.n_rows - row0)
+        n = lay.n_rows + self.n_global
+        return self.out[:, :n] if self.MULTI else self.out[:n]
 
-    def reset(self, guide_embed=None):
-        """A new clip on the same buffers, with the same or a new guide: the query preparation runs again (it follows the weights) and the
-        state is emptied on the caller's stream."""
+    def reset(self, guide=None):
+        """A new clip on the same buffers, with the same or a new guide (Q new guides; another Q: ValueError -- open another stream): the
+        query preparation runs again (it follows the weights) and the state is emptied on the caller's stream."""
         from .projector import _refuse_grad
-        guide = self.guide if guide_embed is None else guide_embed
-        if guide_embed is not None:
-            stream_scope(self.proj, guide, self.H, self.W, self.max_frames, self.newline)
-            _require_bf16_cuda("guide_embed", guide)
-        _refuse_grad(self.proj, "ClipStream.reset")
+        new = guide if guide is not None else self.guides if self.MULTI else self.guide
+        if guide is not None:
+            self._scope(self.proj, new, self.H, self.W, self.max_frames, self.newline)
+            if self.MULTI and new.shape[0] != self.Q:
+                raise ValueError(f"{self.NAME}.reset: {new.shape[0]} guides on a stream opened for Q={self.Q} (the buffers are sized by Q)")
+            _require_bf16_cuda(self.GUIDE, new)
+        _refuse_grad(self.proj, f"{self.NAME}.reset")
         self.frames, self.n_pushes, self.has_fe = 0, 0, None
-        self._prepare(guide)
+        self._prepare(new)
+
+
+class ClipStream(ClipStreamBase):
+    """The object HIComProjector.open_stream returns (module docstring): one guide, the fused ring kernel per chunk."""
+    NAME, WHAT, STORE = "ClipStream", "open_stream", STORE
+
+    # -- device work: methods of their own, so that the host logic around them can be exercised without a device ---------------------------
+    def _allocate(self, rows):
+        dev, E, gc = self.device, self.E, self.proj.global_compressor
+        self.out = torch.empty((rows, self.hidden), dtype=self.out_dtype, device=dev)
+        self.state_ml = torch.empty((2, self.nh, 2), dtype=torch.float32, device=dev)      # (M, L) ping-pong: read one, write the other
+        self.state_acc = torch.empty((1, self.nh, E), dtype=torch.float32, device=dev)
+        self.q_hi = torch.zeros((16, E), dtype=torch.bfloat16, device=dev)
+        self.q_lo = torch.zeros_like(self.q_hi)
+        self.qp_state = nv.query_prep_state(E, dev)
+        self.pos_a = self.pe_hi = self.pe_lo = None
+        self.P = self.y0 = self.x0 = 0
+        if gc.use_pos_emb:
+            # sized for max_frames: the y / x table offsets (cap, cap + H) never move while the stream lives; the stream keeps the tables
+            _, self.kpe, cap = gc.pos_and_kpe(self.max_frames, self.H, self.W, dev)
+            self.pe_hi, self.pe_lo = gc.pos_planes(self.max_frames, self.H, self.W, dev)
+            self.P, self.y0, self.x0 = self.pe_hi.shape[0], cap, cap + self.H
+            self.pos_a = torch.zeros((16, self.P), dtype=torch.float32, device=dev)
+
+    def _prepare(self, guide):
+        """Everything that depends on the guide alone: q_proj, the fold, the score-side positional table and the local query rows in one
+        launch (hicom_query_prep_fwd), and the empty state.  Once per open_stream / reset, not per push."""
+        from .projector import _linear_params
+        gc = self.proj.global_compressor
+        att = gc.attn_layer
+        self.guide = guide.contiguous()
+        wq, bq = _linear_params(att.q_proj)
+        wk, _ = _linear_params(att.k_proj)
+        if gc.use_pos_emb:
+            gc.pos_and_kpe(self.max_frames, self.H, self.W, self.device)                   # (follows k_proj.weight in place)
+        nv.query_prep(self.guide, self.guide, wq, bq, wk, self.kpe if gc.use_pos_emb else None, self.nh, att.scale, self.q_hi, self.q_lo,
+                      self.pos_a, self.qp_state)
+        nv.stream_state_clear(self.state_ml, self.state_acc)
+        self.cur = 0
+
+    def _build_plan(self, Tc, has_fe):
+        nw = (Tc // self.kt) * self.gh * self.gw
+        nparts = nv.fused_stream_nparts(nw)
+        a = nv.StreamPushArgs()
+        ws, (a.part_m, a.part_l, a.part_acc, a.ctx_f16, a.hid_f16), keep = self._fill_common(
+            a, Tc, nparts, [nparts * 16 * 4, nparts * 16 * 4, nparts * 16 * self.E * 4, nw * self.E * 2, nw * self.hidden * 2])
+        a.rows = self.nh
+        return StreamPlan(a, ws, keep, self.proj.local_compressor.readout_f16)
+
+    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
+        a = plan.args
+        self._patch_common(a, ff, fe, t0, row0, nl_group, newline_rows, stream)
+        a.pe_hi = self.pe_hi.data_ptr() if self.pe_hi is not None else None
+        a.pe_lo = self.pe_lo.data_ptr() if self.pe_lo is not None else None
+        nv.compressor_stream_push(a)
+
+    def _finish_device(self, row0, tail):
+        if tail:                                                                           # whole-clip newline rows (`one_token`)
+            nv.scatter_rows(self.newline.view(1, -1), self.out, row0, tail)
+        gc = self.proj.global_compressor
+        gc.finish(self.state_ml[self.cur:self.cur + 1], self.state_acc, self.guide.view(1, -1), self.out, row0 + tail, self.n_global)
 
 
 # =================================================================================================================================
 # several guides per stream (HIComProjector.open_stream_multi, DESIGN.md §3.13)
 # =================================================================================================================================
-STORE_MULTI = "_clip_stream_multi_plans"
-MAX_PARTS = 256                                  # token chunks of the many-row global stream (csrc/clip_stream.hip: kMaxStreamParts)
-
-
-def multi_chunk_limits(what, Tc, H, W, use_pos_emb):
-    """The LDS limits of the merge kernels (csrc/merge.hip) applied to ONE chunk of Tc frames, with the largest number of token chunks a plan
-    may choose: NotImplementedError in front of any device work (hicom_compressor_stream_push_multi checks the same with the plan's own)."""
-    if not use_pos_emb:
-        return
-    if H + W > 1024 or not ((H <= 32 and W <= 32) or (H * W + H + 4) * 4 <= 60000):
-        raise NotImplementedError(f"{what}: a {H}x{W} grid: the merge keeps a frame of logits in LDS")
-    if (MAX_PARTS + 2 * Tc + H + W + 64 * (H + W + 2) + 16 * 64 + 4) * 4 > 60000:
-        raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the merge keeps the row's Tc + H + W weights and 64 frames of "
-                                  "marginals in LDS; push shorter chunks")
-
-
-class ClipStreamMulti(ClipStream):
+class ClipStreamMulti(ClipStreamBase):
     """The object HIComProjector.open_stream_multi returns: ONE video that arrives in chunks, Q guides known up front.
 
         s = proj.open_stream_multi(guide_embeds[Q, E], H, W, max_frames, image_newline)        # 1 <= Q <= 32
@@ -342,39 +405,13 @@ class ClipStreamMulti(ClipStream):
 
     Scope: that of open_stream (plain release recipe, bf16 module and inputs, inference only, exact window partition, E == 1152,
     hidden % 64 == 0; windows of <= 64 tokens) with 1 <= Q <= 32 and the merge kernels' LDS limits on a chunk (multi_chunk_limits)."""
-    NAME, WHAT = "ClipStreamMulti", "open_stream_multi"
-    STORE = STORE_MULTI
+    NAME, WHAT, STORE = "ClipStreamMulti", "open_stream_multi", STORE_MULTI
+    MULTI, GUIDE = True, "guide_embeds"
+    R = property(lambda self: self.Q * self.nh)                     # folded rows: guide q's heads are rows nh q .. nh q + nh - 1
+    rows_pad = property(lambda self: (self.R + 31) // 32 * 32)      # whole 32-row passes of the many-row stream kernel
 
-    def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
-        """stream_scope of the class and the limits of the shortest chunk: (E, kt, ks, hidden, heads)."""
-        dims = stream_scope(proj, guide_embeds, H, W, max_frames, image_newline, self.WHAT, True, self.RECIPE)
-        multi_chunk_limits(self.WHAT, dims[1], H, W, proj.global_compressor.use_pos_emb)      # (the shortest chunk must fit)
-        return dims
-
-    def _plan_key(self, Tc, has_fe, stream):
-        return (self.Q, Tc, self.H, self.W, self.E, has_fe, None if self.newline is None else tuple(self.newline.shape), self.out_dtype, stream)
-
-    def __init__(self, proj, guide_embeds, H, W, max_frames, image_newline=None):
-        from .projector import _out_dtype, _refuse_grad
-        self.E, self.kt, self.ks, self.hidden, self.nh = self._scope(proj, guide_embeds, H, W, max_frames, image_newline)
-        _refuse_grad(proj, f"HIComProjector.{self.WHAT}")
-        _require_bf16_cuda("guide_embeds", guide_embeds)
-        if image_newline is not None:
-            _require_bf16_cuda("image_newline", image_newline)
-        self.proj, self.H, self.W, self.max_frames = proj, H, W, max_frames
-        self.Q = guide_embeds.shape[0]
-        self.R = self.Q * self.nh                                            # folded rows: guide q's heads are rows nh q .. nh q + nh - 1
-        self.rows_pad = (self.R + 31) // 32 * 32                             # whole 32-row passes of the many-row stream kernel
-        self.gh, self.gw = H // self.ks, W // self.ks
-        self.newline = None if image_newline is None else image_newline.contiguous()
-        self.device, self.out_dtype = guide_embeds.device, _out_dtype(proj)
-        self.has_fe = None
-        self.frames = 0
-        self.n_pushes = 0
-        self.cap_rows = proj._layout((max_frames // self.kt, self.gh, self.gw), "video", image_newline is not None, False).n_rows
-        self.n_global = proj.global_compressor.num_queries
-        self._allocate(self.cap_rows + self.n_global)
-        self._prepare(guide_embeds)
+    def _chunk_limits(self, what, proj, Tc, H, W, E):
+        multi_chunk_limits(what, Tc, H, W, proj.global_compressor.use_pos_emb)
 
     # -- device work ------------------------------------------------------------------------------------------------------------------------
     def _allocate(self, rows):
@@ -423,9 +460,8 @@ class ClipStreamMulti(ClipStream):
         """The fields of the push block `a` that the module and the chunk shape decide, and the workspace of ONE chunk with its regions
         entered into `a`.  extra: byte sizes of further regions behind them (0: none).  Returns (workspace, the addresses of the extra
         regions -- None for an empty one --, the tensors the block points at)."""
-        from .projector import _linear_params
-        lc, gc = self.proj.local_compressor, self.proj.global_compressor
-        E, hidden, dev, H, W, Q, R, RP = self.E, self.hidden, self.device, self.H, self.W, self.Q, self.R, self.rows_pad
+        gc = self.proj.global_compressor
+        E, hidden, H, W, Q, R, RP = self.E, self.hidden, self.H, self.W, self.Q, self.R, self.rows_pad
         nw = (Tc // self.kt) * self.gh * self.gw
         N = Tc * H * W
         ntiles = (N + 15) // 16
@@ -433,118 +469,31 @@ class ClipStreamMulti(ClipStream):
         marg = bool(gc.use_pos_emb) and nv.global_stream_has_marg(N, E, RP, H, W, nparts)      # the form, once per plan
         stride = ntiles * 16
         odt = 4 if self.out_dtype == torch.float32 else 2
-
-        def up(n):
-            return (n + 255) // 256 * 256
         scores = max(RP * stride, nparts * RP * nv.global_stream_marg_width(H, W))
-        sizes = [up(nparts * RP * 4), up(nparts * RP * 4), up(nparts * RP * E * 4), up(scores * 4), up(RP * Tc * (H + W + 2) * 4), up(R * 2 * 4),
-                 up(R * E * 4), up(Q * nw * E * 2), up(Q * nw * hidden * 2), up(Q * nw * hidden * odt)] + [up(n) for n in extra]
-        ws = torch.empty((sum(sizes),), dtype=torch.uint8, device=dev)
-        offs = [sum(sizes[:i]) for i in range(len(sizes))]
-        a.Q, a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.nparts = Q, Tc, H, W, E, self.kt, self.ks, self.nh, hidden, nparts
-        a.marg, a.score_stride = int(marg), stride
-        a.l_scale = 1.0 / math.sqrt(lc.qk_dim)
-        (a.part_m, a.part_l, a.part_acc, a.scores, a.scratch, a.set_ml, a.set_acc, a.ctx_f16, a.hid_f16, a.loc) = (ws.data_ptr() + o for o in offs[:10])
-        w0h, w2h = lc.readout_f16()
-        b0, b2 = _linear_params(lc.readout[0])[1], _linear_params(lc.readout[2])[1]
-        a.lw0_f16, a.lw2_f16, a.lb0, a.lb2 = w0h.data_ptr(), w2h.data_ptr(), b0.data_ptr(), b2.data_ptr()
-        a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
-        a.ldo = hidden
-        return ws, [ws.data_ptr() + o if n else None for o, n in zip(offs[10:], extra)], [w0h, w2h, b0, b2]
+        ws, at, keep = self._fill_common(a, Tc, nparts, [nparts * RP * 4, nparts * RP * 4, nparts * RP * E * 4, scores * 4, RP * Tc * (H + W + 2) * 4, R * 2 * 4,
+                                                         R * E * 4, Q * nw * E * 2, Q * nw * hidden * 2, Q * nw * hidden * odt, *extra])
+        a.Q, a.nh, a.marg, a.score_stride = Q, self.nh, int(marg), stride
+        (a.part_m, a.part_l, a.part_acc, a.scores, a.scratch, a.set_ml, a.set_acc, a.ctx_f16, a.hid_f16, a.loc) = at[:10]
+        return ws, [p if n else None for p, n in zip(at[10:], extra)], keep
 
     def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
         self._patch(plan.args, ff, fe, t0, row0, nl_group, newline_rows, stream)
         nv.compressor_stream_push_multi(plan.args)
 
     def _patch(self, a, ff, fe, t0, row0, nl_group, newline_rows, stream):
-        """What changes from push to push in the plain push block `a`: the chunk, its frame and row offsets, its newline rows and everything
-        that belongs to this stream (a plan serves every stream of the module)."""
-        a.ff, a.fe, a.guide, a.t0 = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr(), t0
-        a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
-        a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
+        """_patch_common on the plain push block `a`, and what only the multi-guide block has."""
+        self._patch_common(a, ff, fe, t0, row0, nl_group, newline_rows, stream)
+        a.guide, a.q_stride = self.guides.data_ptr(), self.out.stride(0)
         a.pe = self.pe.data_ptr() if self.pe is not None else None
-        a.P, a.y_index0, a.x_index0 = self.P, self.y0, self.x0
-        a.state_ml_in, a.state_ml_out = self.state_ml[self.cur].data_ptr(), self.state_ml[self.cur ^ 1].data_ptr()
-        a.state_acc = self.state_acc.data_ptr()
-        a.out, a.row0, a.nl_group, a.q_stride = self.out.data_ptr(), row0, nl_group, self.out.stride(0)
-        a.nl_count = len(newline_rows)
-        a.newline = self.newline.data_ptr() if newline_rows else None
-        a.nl_first, a.nl_step = 0, 1
-        if newline_rows:
-            a.nl_first = newline_rows[0]
-            a.nl_step = newline_rows[1] - newline_rows[0] if len(newline_rows) > 1 else nl_group + 1
-        a.stream = stream
 
     def _finish_device(self, row0, tail):
         self.proj.global_compressor.finish_guides(self.state_ml[self.cur:self.cur + 1], self.state_acc, self.guides, self.fin)
         nv.stream_place_global(self.fin[4], self.newline, tail, self.n_global, self.out, row0)
 
-    # -- the public surface ---------------------------------------------------------------------------------------------------------------
-    def push(self, frames_feature, frames_embed=None):
-        """The next Tc frames of the clip (bf16 [Tc, H, W, E], Tc a positive multiple of kt; frames_embed None: the keys are
-        frames_feature).  Returns the view [Q, chunk rows, hidden] of this chunk's local output rows in their final place in the stream's
-        output buffer (strided over q), complete on the caller's stream; the chunk is not referenced afterwards."""
-        Tc = self._check_chunk(frames_feature, frames_embed)
-        multi_chunk_limits(f"{self.NAME}.push", Tc, self.H, self.W, self.proj.global_compressor.use_pos_emb)
-        ff = frames_feature.contiguous()
-        fe = frames_embed.contiguous() if frames_embed is not None else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(Tc, fe is not None, stream), lambda: self._build_plan(Tc, fe is not None))
-        row0, nl_group, newline_rows, row1 = chunk_rows(self.proj, self.frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
-        self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
-        self.cur ^= 1
-        self.has_fe = fe is not None
-        self.frames += Tc
-        self.n_pushes += 1
-        return self.out[:, row0:row1]
-
-    def finish(self):
-        """[Q, local rows so far + 32, hidden]: the rows that depend on the whole clip (a `one_token` newline row, the 32 global rows of every
-        guide) written behind the local rows pushed so far.  A view of the stream's buffer, strided over q; the state is not consumed."""
-        from .projector import _refuse_grad
-        if self.frames == 0:
-            raise ValueError(f"{self.NAME}.finish: nothing has been pushed")
-        _refuse_grad(self.proj, f"{self.NAME}.finish")
-        row0, lay = prefix_layout(self.proj, self.frames // self.kt, self.gh, self.gw, self.newline is not None)
-        self._finish_device(row0, lay.n_rows - row0)
-        return self.out[:, :lay.n_rows + self.n_global]
-
-    def reset(self, guides=None):
-        """A new clip on the same buffers, with the same or Q new guides (another Q: ValueError -- open another stream): the query
-        preparation runs again (it follows the weights) and the state is emptied on the caller's stream."""
-        from .projector import _refuse_grad
-        new = self.guides if guides is None else guides
-        if guides is not None:
-            self._scope(self.proj, new, self.H, self.W, self.max_frames, self.newline)
-            if new.shape[0] != self.Q:
-                raise ValueError(f"{self.NAME}.reset: {new.shape[0]} guides on a stream opened for Q={self.Q} (the buffers are sized by Q)")
-            _require_bf16_cuda("guide_embeds", new)
-        _refuse_grad(self.proj, f"{self.NAME}.reset")
-        self.frames, self.n_pushes, self.has_fe = 0, 0, None
-        self._prepare(new)
-
 
 # =================================================================================================================================
 # several guides per stream on the k / v adaptor recipe (HIComProjector.open_stream_adapt, DESIGN.md §3.14)
 # =================================================================================================================================
-STORE_ADAPT = "_clip_stream_adapt_plans"
-
-
-def adaptor_widths(what, lc):
-    """The width condition of segments.fill_adaptors, from the parameters' shapes alone: in front of any device work."""
-    from . import engine
-    for _, mlp, _, _ in engine.adaptor_streams(lc):
-        w0, w2 = mlp[0].weight, mlp[2].weight
-        if w0.shape[0] % 64 or w0.shape[1] % 64 or w2.shape[0] % 64 or w0.shape != w2.shape:
-            raise NotImplementedError(f"{what}: adaptor widths must be multiples of 64")
-
-
-def adapt_chunk_limit(what, Tc, H, W, E):
-    """The operand limit of the adaptor MLPs' dense GEMMs on ONE chunk (hicom_clip_adapt_prepare_fwd checks the same)."""
-    if Tc * H * W * E >= 1 << 32:
-        raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the adaptor GEMMs take operands below 2^32 elements; push shorter chunks")
-
-
 class ClipStreamAdapt(ClipStreamMulti):
     """The object HIComProjector.open_stream_adapt returns for a module of the k / v adaptor recipe (`local43_adaptkv_global32`; adapt_k
     and / or adapt_v on the local compressor): ClipStreamMulti's surface, state, output buffer, finish() and reset().
@@ -562,15 +511,17 @@ class ClipStreamAdapt(ClipStreamMulti):
 
     Scope: that of open_stream_multi with the adaptor recipe in the place of the plain one, adaptor widths % 64 == 0 and Tc H W E < 2^32
     per chunk."""
-    NAME, WHAT = "ClipStreamAdapt", "open_stream_adapt"
+    NAME, WHAT, STORE = "ClipStreamAdapt", "open_stream_adapt", STORE_ADAPT
     RECIPE, RECIPE_WORDS = "adaptkv", "the k / v adaptor release recipe"
-    STORE = STORE_ADAPT
 
     def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
         dims = super()._scope(proj, guide_embeds, H, W, max_frames, image_newline)
         adaptor_widths(self.WHAT, proj.local_compressor)
-        adapt_chunk_limit(self.WHAT, dims[1], H, W, dims[0])
         return dims
+
+    def _chunk_limits(self, what, proj, Tc, H, W, E):
+        super()._chunk_limits(what, proj, Tc, H, W, E)
+        adapt_chunk_limit(what, Tc, H, W, E)
 
     def _plan_key(self, Tc, has_fe, stream):
         lc = self.proj.local_compressor
@@ -602,9 +553,3 @@ class ClipStreamAdapt(ClipStreamMulti):
     def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
         self._patch(plan.args.base, ff, fe, t0, row0, nl_group, newline_rows, stream)
         nv.compressor_stream_push_multi_adapt(plan.args)
-
-    def push(self, frames_feature, frames_embed=None):
-        """ClipStreamMulti.push on the adaptor recipe (the class docstring has what differs)."""
-        if isinstance(frames_feature, torch.Tensor) and frames_feature.ndim == 4:
-            adapt_chunk_limit(f"{self.NAME}.push", frames_feature.shape[0], self.H, self.W, self.E)
-        return super().push(frames_feature, frames_embed)

@@ -11,7 +11,8 @@
 //
 // The k / v adaptor recipe: hicom_compressor_stream_push_multi_adapt is the same push with another local stage -- the adaptor
 // MLPs over the chunk's tokens (hicom_clip_adapt_prepare_fwd) and the adapt local kernel (hicom_multi_guide_local_adapt_fwd) -- on one body,
-// push_multi, which holds the checks and launches 2 ... for both entry points.
+// push_multi, which holds the checks and launches 2 ... for both entry points.  The host checks that the three pushes share are chunk_check; the
+// two fold entry points share fold_launch.
 #include <math.h>
 
 #include "segment_host.hpp"
@@ -113,87 +114,41 @@ extern "C" int hicom_stream_state_clear_fwd(float* state_ml, int32_t ml_rows, fl
     return hicom_host::check_launch("stream_state_clear");
 }
 
-extern "C" int hicom_stream_state_fold_fwd(const float* part_m, const float* part_l, const float* part_acc, int32_t nparts, int32_t rows,
-                                           int32_t rows_pad, int32_t E, const float* state_ml_in, float* state_ml_out, float* state_acc,
-                                           void* stream) {
-    HICOM_REQUIRE(part_m && part_l && part_acc && state_ml_in && state_ml_out && state_acc, HICOM_EINVAL, "stream_state_fold: NULL pointer");
-    HICOM_REQUIRE(nparts > 0 && rows > 0 && rows <= rows_pad && E > 0 && E % 4 == 0, HICOM_EINVAL,
-                  "stream_state_fold: bad shape (nparts=%d rows=%d rows_pad=%d E=%d; E %% 4)", nparts, rows, rows_pad, E);
-    HICOM_REQUIRE((uintptr_t)part_acc % 16 == 0 && (uintptr_t)state_acc % 16 == 0 && (uintptr_t)state_ml_in % 8 == 0 &&
-                      (uintptr_t)state_ml_out % 8 == 0, HICOM_EINVAL, "stream_state_fold: 16-byte aligned accumulators, 8-byte aligned (M, L)");
-    // every slice of a row reads the old (M, L): writing it back into the block being read would race between the row's workgroups
-    HICOM_REQUIRE(state_ml_in + 2 * (long)rows <= state_ml_out || state_ml_out + 2 * (long)rows <= state_ml_in, HICOM_EINVAL,
-                  "stream_state_fold: state_ml_in and state_ml_out overlap");
-    hipLaunchKernelGGL(stream_state_fold_kernel, dim3((unsigned)((E + 4 * kWave - 1) / (4 * kWave)), (unsigned)rows), dim3(kWave), 0,
-                       (hipStream_t)stream, part_m, part_l, part_acc, nparts, rows_pad, E, state_ml_in, state_ml_out, state_acc);
-    return hicom_host::check_launch("stream_state_fold");
-}
-
-extern "C" int hicom_compressor_stream_push(const hicom_stream_push_args* a) {
-    HICOM_REQUIRE(a, HICOM_EINVAL, "compressor_stream_push: NULL arguments");
-    HICOM_REQUIRE(a->Tc > 0 && a->H > 0 && a->W > 0 && a->kt > 0 && a->ks > 0 && a->hidden > 0 && a->rows > 0 && a->nparts > 0, HICOM_EINVAL,
-                  "compressor_stream_push: bad shape");
-    HICOM_REQUIRE(a->E == 1152, HICOM_EUNSUP, "compressor_stream_push: E=%d (only 1152)", a->E);
-    HICOM_REQUIRE(a->rows <= 12, HICOM_EUNSUP, "compressor_stream_push: %d folded rows (<= 12)", a->rows);
-    HICOM_REQUIRE(a->hidden % 64 == 0, HICOM_EUNSUP, "compressor_stream_push: hidden=%d (multiple of 64: fp16 readout planes)", a->hidden);
-    HICOM_REQUIRE(a->Tc % a->kt == 0 && a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP,
-                  "compressor_stream_push: needs an exact window partition (Tc=%d H=%d W=%d, windows %dx%dx%d)", a->Tc, a->H, a->W, a->kt, a->ks,
-                  a->ks);
-    const int win = a->kt * a->ks * a->ks;
-    HICOM_REQUIRE(win >= 16 && win <= 64, HICOM_EUNSUP, "compressor_stream_push: windows of %d tokens (16 .. 64)", win);
-    HICOM_REQUIRE(a->out_dt == HICOM_DT_F32 || a->out_dt == HICOM_DT_BF16, HICOM_EUNSUP, "compressor_stream_push: output dtype %d (bf16 | f32)",
-                  a->out_dt);
-    HICOM_REQUIRE(a->ff && a->q_hi && a->q_lo && a->part_m && a->part_l && a->part_acc && a->ctx_f16 && a->hid_f16 && a->state_ml_in &&
-                      a->state_ml_out && a->state_acc && a->out, HICOM_EINVAL, "compressor_stream_push: NULL pointer");
-    HICOM_REQUIRE(a->lw0_f16 && a->lb0 && a->lw2_f16 && a->lb2, HICOM_EINVAL, "compressor_stream_push: NULL weight");
-    HICOM_REQUIRE((a->pos_a != nullptr) == (a->pe_hi != nullptr) && (a->pe_hi != nullptr) == (a->pe_lo != nullptr), HICOM_EINVAL,
-                  "compressor_stream_push: pos_a, pe_hi and pe_lo come together");
-    HICOM_REQUIRE(a->t0 >= 0 && a->t0 % a->kt == 0, HICOM_EINVAL, "compressor_stream_push: t0=%d (whole window groups of %d frames)", a->t0, a->kt);
-    if (a->pos_a)
-        HICOM_REQUIRE((long)a->t0 + a->Tc <= a->y_index0 && a->y_index0 + a->H <= a->x_index0 && a->x_index0 + a->W <= a->P, HICOM_EINVAL,
-                      "compressor_stream_push: frames %d .. %d, grid %dx%d outside the positional tables (t < %d, y at %d, x at %d, %d rows)",
-                      a->t0, a->t0 + a->Tc, a->H, a->W, a->y_index0, a->y_index0, a->x_index0, a->P);
-    HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (uintptr_t)a->fe % 16 == 0, HICOM_EINVAL, "compressor_stream_push: 16-byte aligned inputs");
-    const long nw = (long)(a->Tc / a->kt) * (a->H / a->ks) * (a->W / a->ks);
-    HICOM_REQUIRE(nw <= INT32_MAX && a->ldo >= a->hidden && a->row0 >= 0 && a->nl_group >= 0 && (a->nl_group == 0 || nw % a->nl_group == 0),
-                  HICOM_EINVAL, "compressor_stream_push: output layout");
-    HICOM_REQUIRE(a->nl_count >= 0 && (a->nl_count == 0 || (a->newline && a->nl_first >= a->row0 && a->nl_step > 0)), HICOM_EINVAL,
-                  "compressor_stream_push: newline rows");
-    // (no frames_embed: the keys are frames_feature, reference projector.py:532 -- the ring kernel streams it as its key tensor too)
-    int st = hicom_fused_stream_fwd(a->ff, a->fe ? a->fe : a->ff, nullptr, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->q_hi, a->q_lo, a->rows, a->l_scale, 0.f,
-                                    a->pos_a, a->P, a->pe_hi, a->pe_lo, a->t0, a->y_index0, a->x_index0, a->part_m, a->part_l, a->part_acc,
-                                    a->nparts, nullptr, nullptr, nullptr, a->ctx_f16, nullptr, 0, nullptr, nullptr, 0, HICOM_DT_BF16, nullptr,
-                                    a->stream);
-    if (st != HICOM_OK) return st;
-    st = hicom_stream_state_fold_fwd(a->part_m, a->part_l, a->part_acc, a->nparts, a->rows, 16, a->E, a->state_ml_in, a->state_ml_out,
-                                     a->state_acc, a->stream);
-    if (st != HICOM_OK) return st;
-    st = hicom_readout16_gemm_fwd(a->ctx_f16, a->lw0_f16, a->lb0, HICOM_DT_BF16, (int32_t)nw, a->hidden, a->E, HICOM_ACT_GELU, a->hid_f16, nullptr, 0,
-                                  0, 0, 0, nullptr, a->stream);
-    if (st != HICOM_OK) return st;
-    st = hicom_readout16_gemm_fwd(a->hid_f16, a->lw2_f16, a->lb2, HICOM_DT_BF16, (int32_t)nw, a->hidden, a->hidden, HICOM_ACT_NONE, nullptr, a->out,
-                                  a->out_dt, a->ldo, a->row0, a->nl_group, nullptr, a->stream);
-    if (st != HICOM_OK || a->nl_count == 0) return st;
-    return hicom_scatter_rows_fwd(a->newline, HICOM_DT_BF16, 1, a->hidden, a->out, a->out_dt, a->ldo, a->nl_first, a->nl_step, 0, a->nl_count,
-                                  a->stream);
-}
-
-// ---- several guides per stream (DESIGN.md §3.13) ---------------------------------------------------------------------------------------------
-extern "C" int hicom_stream_state_fold_set_fwd(const float* set_ml, const float* set_acc, int32_t rows, int32_t E, const float* state_ml_in,
-                                               float* state_ml_out, float* state_acc, void* stream) {
-    HICOM_REQUIRE(set_ml && set_acc && state_ml_in && state_ml_out && state_acc, HICOM_EINVAL, "stream_state_fold_set: NULL pointer");
-    HICOM_REQUIRE(rows > 0 && rows <= 65535 && E > 0 && E % 4 == 0, HICOM_EINVAL, "stream_state_fold_set: bad shape (rows=%d E=%d; E %% 4)", rows, E);
-    HICOM_REQUIRE((uintptr_t)set_acc % 16 == 0 && (uintptr_t)state_acc % 16 == 0 && (uintptr_t)set_ml % 8 == 0 && (uintptr_t)state_ml_in % 8 == 0 &&
-                      (uintptr_t)state_ml_out % 8 == 0, HICOM_EINVAL, "stream_state_fold_set: 16-byte aligned accumulators, 8-byte aligned (M, L)");
-    // every slice of a row reads the old (M, L): writing it back into the block being read would race between the row's workgroups
-    HICOM_REQUIRE(state_ml_in + 2 * (long)rows <= state_ml_out || state_ml_out + 2 * (long)rows <= state_ml_in, HICOM_EINVAL,
-                  "stream_state_fold_set: state_ml_in and state_ml_out overlap");
-    hipLaunchKernelGGL(stream_state_fold_set_kernel, dim3((unsigned)((E + 4 * kWave - 1) / (4 * kWave)), (unsigned)rows), dim3(kWave), 0,
-                       (hipStream_t)stream, set_ml, set_acc, E, state_ml_in, state_ml_out, state_acc);
-    return hicom_host::check_launch("stream_state_fold_set");
-}
-
 namespace {
+
+// What the two fold entry points share behind their own NULL and shape checks: the alignment of the terms (`term_acc` their accumulators, `term_ml`
+// (M, L) pairs or NULL) and of the state, the (M, L) blocks apart, and the launch of `kernel(terms..., E, state_ml_in, state_ml_out, state_acc)`.
+template <class Kernel, class... Terms>
+int fold_launch(const char* who, Kernel kernel, const float* term_acc, const float* term_ml, int rows, int E, const float* state_ml_in, float* state_ml_out,
+                float* state_acc, void* stream, Terms... terms) {
+    HICOM_REQUIRE((uintptr_t)term_acc % 16 == 0 && (uintptr_t)state_acc % 16 == 0 && (uintptr_t)term_ml % 8 == 0 && (uintptr_t)state_ml_in % 8 == 0 &&
+                      (uintptr_t)state_ml_out % 8 == 0, HICOM_EINVAL, "%s: 16-byte aligned accumulators, 8-byte aligned (M, L)", who);
+    // every slice of a row reads the old (M, L): writing it back into the block being read would race between the row's workgroups
+    HICOM_REQUIRE(state_ml_in + 2 * (long)rows <= state_ml_out || state_ml_out + 2 * (long)rows <= state_ml_in, HICOM_EINVAL,
+                  "%s: state_ml_in and state_ml_out overlap", who);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((E + 4 * kWave - 1) / (4 * kWave)), (unsigned)rows), dim3(kWave), 0, (hipStream_t)stream, terms..., E,
+                       state_ml_in, state_ml_out, state_acc);
+    return hicom_host::check_launch(who);
+}
+
+// The checks of one chunk that all three pushes make, on the fields their argument blocks share by name (`heads`: the folded rows per guide;
+// `has_pos`: the positional tables are in play).  The limits on heads and windows, the pointers and the merge stay with the entry points.
+template <class Args>
+int chunk_check(const char* who, const Args* a, int heads, bool has_pos) {
+    HICOM_REQUIRE(a->Tc > 0 && a->H > 0 && a->W > 0 && a->kt > 0 && a->ks > 0 && a->hidden > 0 && heads > 0 && a->nparts > 0, HICOM_EINVAL, "%s: bad shape", who);
+    HICOM_REQUIRE(a->E == 1152, HICOM_EUNSUP, "%s: E=%d (only 1152)", who, a->E);
+    HICOM_REQUIRE(a->hidden % 64 == 0, HICOM_EUNSUP, "%s: hidden=%d (multiple of 64: fp16 readout planes)", who, a->hidden);
+    HICOM_REQUIRE(a->Tc % a->kt == 0 && a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP,
+                  "%s: needs an exact window partition (Tc=%d H=%d W=%d, windows %dx%dx%d)", who, a->Tc, a->H, a->W, a->kt, a->ks, a->ks);
+    HICOM_REQUIRE(a->out_dt == HICOM_DT_F32 || a->out_dt == HICOM_DT_BF16, HICOM_EUNSUP, "%s: output dtype %d (bf16 | f32)", who, a->out_dt);
+    HICOM_REQUIRE(a->lw0_f16 && a->lb0 && a->lw2_f16 && a->lb2, HICOM_EINVAL, "%s: NULL weight", who);
+    HICOM_REQUIRE(a->t0 >= 0 && a->t0 % a->kt == 0, HICOM_EINVAL, "%s: t0=%d (whole window groups of %d frames)", who, a->t0, a->kt);
+    if (has_pos)
+        HICOM_REQUIRE((long)a->t0 + a->Tc <= a->y_index0 && a->y_index0 + a->H <= a->x_index0 && a->x_index0 + a->W <= a->P, HICOM_EINVAL,
+                      "%s: frames %d .. %d, grid %dx%d outside the positional tables (t < %d, y at %d, x at %d, %d rows)", who, a->t0, a->t0 + a->Tc, a->H,
+                      a->W, a->y_index0, a->y_index0, a->x_index0, a->P);
+    return HICOM_OK;
+}
 
 constexpr int kMaxStreamGuides = 32;        // 9 heads x 32 guides = 288 rows: the row count the many-row stream kernel is proven at
 constexpr int kMaxStreamParts = 256;        // token chunks of the global stream (the merge keeps a weight per chunk in LDS)
@@ -233,6 +188,57 @@ int place_launch(const char* who, const void* loc, const float* tok, const void*
 
 }  // namespace
 
+extern "C" int hicom_stream_state_fold_fwd(const float* part_m, const float* part_l, const float* part_acc, int32_t nparts, int32_t rows, int32_t rows_pad,
+                                           int32_t E, const float* state_ml_in, float* state_ml_out, float* state_acc, void* stream) {
+    HICOM_REQUIRE(part_m && part_l && part_acc && state_ml_in && state_ml_out && state_acc, HICOM_EINVAL, "stream_state_fold: NULL pointer");
+    HICOM_REQUIRE(nparts > 0 && rows > 0 && rows <= rows_pad && E > 0 && E % 4 == 0, HICOM_EINVAL,
+                  "stream_state_fold: bad shape (nparts=%d rows=%d rows_pad=%d E=%d; E %% 4)", nparts, rows, rows_pad, E);
+    return fold_launch("stream_state_fold", stream_state_fold_kernel, part_acc, nullptr, rows, E, state_ml_in, state_ml_out, state_acc, stream, part_m, part_l,
+                       part_acc, (int)nparts, (int)rows_pad);
+}
+
+extern "C" int hicom_compressor_stream_push(const hicom_stream_push_args* a) {
+    constexpr const char* who = "compressor_stream_push";
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", who);
+    int st = chunk_check(who, a, a->rows, a->pos_a != nullptr);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(a->rows <= 12, HICOM_EUNSUP, "%s: %d folded rows (<= 12)", who, a->rows);
+    const int win = a->kt * a->ks * a->ks;
+    HICOM_REQUIRE(win >= 16 && win <= 64, HICOM_EUNSUP, "%s: windows of %d tokens (16 .. 64)", who, win);
+    HICOM_REQUIRE(a->ff && a->q_hi && a->q_lo && a->part_m && a->part_l && a->part_acc && a->ctx_f16 && a->hid_f16 && a->state_ml_in &&
+                      a->state_ml_out && a->state_acc && a->out, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE((a->pos_a != nullptr) == (a->pe_hi != nullptr) && (a->pe_hi != nullptr) == (a->pe_lo != nullptr), HICOM_EINVAL,
+                  "%s: pos_a, pe_hi and pe_lo come together", who);
+    HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (uintptr_t)a->fe % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned inputs", who);
+    const long nw = (long)(a->Tc / a->kt) * (a->H / a->ks) * (a->W / a->ks);
+    HICOM_REQUIRE(nw <= INT32_MAX && a->ldo >= a->hidden && a->row0 >= 0 && a->nl_group >= 0 && (a->nl_group == 0 || nw % a->nl_group == 0),
+                  HICOM_EINVAL, "%s: output layout", who);
+    HICOM_REQUIRE(a->nl_count >= 0 && (a->nl_count == 0 || (a->newline && a->nl_first >= a->row0 && a->nl_step > 0)), HICOM_EINVAL, "%s: newline rows", who);
+    // (no frames_embed: the keys are frames_feature, reference projector.py:532 -- the ring kernel streams it as its key tensor too)
+    st = hicom_fused_stream_fwd(a->ff, a->fe ? a->fe : a->ff, nullptr, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->q_hi, a->q_lo, a->rows, a->l_scale, 0.f,
+                                a->pos_a, a->P, a->pe_hi, a->pe_lo, a->t0, a->y_index0, a->x_index0, a->part_m, a->part_l, a->part_acc, a->nparts, nullptr, nullptr,
+                                nullptr, a->ctx_f16, nullptr, 0, nullptr, nullptr, 0, HICOM_DT_BF16, nullptr, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_stream_state_fold_fwd(a->part_m, a->part_l, a->part_acc, a->nparts, a->rows, 16, a->E, a->state_ml_in, a->state_ml_out, a->state_acc, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_readout16_gemm_fwd(a->ctx_f16, a->lw0_f16, a->lb0, HICOM_DT_BF16, (int32_t)nw, a->hidden, a->E, HICOM_ACT_GELU, a->hid_f16, nullptr, 0,
+                                  0, 0, 0, nullptr, a->stream);
+    if (st != HICOM_OK) return st;
+    st = hicom_readout16_gemm_fwd(a->hid_f16, a->lw2_f16, a->lb2, HICOM_DT_BF16, (int32_t)nw, a->hidden, a->hidden, HICOM_ACT_NONE, nullptr, a->out,
+                                  a->out_dt, a->ldo, a->row0, a->nl_group, nullptr, a->stream);
+    if (st != HICOM_OK || a->nl_count == 0) return st;
+    return hicom_scatter_rows_fwd(a->newline, HICOM_DT_BF16, 1, a->hidden, a->out, a->out_dt, a->ldo, a->nl_first, a->nl_step, 0, a->nl_count, a->stream);
+}
+
+// ---- several guides per stream (DESIGN.md §3.13) ---------------------------------------------------------------------------------------------
+extern "C" int hicom_stream_state_fold_set_fwd(const float* set_ml, const float* set_acc, int32_t rows, int32_t E, const float* state_ml_in,
+                                               float* state_ml_out, float* state_acc, void* stream) {
+    HICOM_REQUIRE(set_ml && set_acc && state_ml_in && state_ml_out && state_acc, HICOM_EINVAL, "stream_state_fold_set: NULL pointer");
+    HICOM_REQUIRE(rows > 0 && rows <= 65535 && E > 0 && E % 4 == 0, HICOM_EINVAL, "stream_state_fold_set: bad shape (rows=%d E=%d; E %% 4)", rows, E);
+    return fold_launch("stream_state_fold_set", stream_state_fold_set_kernel, set_acc, set_ml, rows, E, state_ml_in, state_ml_out, state_acc, stream, set_ml,
+                       set_acc);
+}
+
 extern "C" int hicom_stream_place_rows_fwd(const void* loc, const float* tok, const void* newline, int32_t Q, int32_t windows, int32_t hidden,
                                            int32_t nl_group, int32_t nl_count, int64_t nl_first, int64_t nl_step, int64_t rows, int64_t global_row0,
                                            void* out, int32_t out_dt, int64_t ldo, int64_t q_stride, int64_t row0, void* stream) {
@@ -252,14 +258,10 @@ template <class Checks, class Local>
 int push_multi(const char* who, const hicom_stream_push_multi_args* a, Checks&& more_checks, Local&& local) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", who);
     HICOM_REQUIRE(a->Q >= 1 && a->Q <= kMaxStreamGuides, HICOM_EUNSUP, "%s: Q=%d guides (1 <= Q <= %d per stream)", who, a->Q, kMaxStreamGuides);
-    HICOM_REQUIRE(a->Tc > 0 && a->H > 0 && a->W > 0 && a->kt > 0 && a->ks > 0 && a->hidden > 0 && a->nh > 0 && a->nparts > 0, HICOM_EINVAL, "%s: bad shape", who);
-    HICOM_REQUIRE(a->E == 1152, HICOM_EUNSUP, "%s: E=%d (only 1152)", who, a->E);
+    int st = chunk_check(who, a, a->nh, a->pe != nullptr);
+    if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->nh <= 16 && a->E % a->nh == 0, HICOM_EUNSUP, "%s: %d heads (<= 16 folded rows per guide)", who, a->nh);
-    HICOM_REQUIRE(a->hidden % 64 == 0, HICOM_EUNSUP, "%s: hidden=%d (multiple of 64: fp16 readout planes)", who, a->hidden);
-    HICOM_REQUIRE(a->Tc % a->kt == 0 && a->H % a->ks == 0 && a->W % a->ks == 0, HICOM_EUNSUP,
-                  "%s: needs an exact window partition (Tc=%d H=%d W=%d, windows %dx%dx%d)", who, a->Tc, a->H, a->W, a->kt, a->ks, a->ks);
     HICOM_REQUIRE(a->kt * a->ks * a->ks <= 64, HICOM_EUNSUP, "%s: windows of %d tokens (<= 64)", who, a->kt * a->ks * a->ks);
-    HICOM_REQUIRE(a->out_dt == HICOM_DT_F32 || a->out_dt == HICOM_DT_BF16, HICOM_EUNSUP, "%s: output dtype %d (bf16 | f32)", who, a->out_dt);
     const long N = (long)a->Tc * a->H * a->W, ntiles = (N + 15) / 16;
     const long nw = (long)(a->Tc / a->kt) * (a->H / a->ks) * (a->W / a->ks);
     const int rows = a->Q * a->nh, rows_pad = (rows + 31) / 32 * 32;
@@ -268,13 +270,7 @@ int push_multi(const char* who, const hicom_stream_push_multi_args* a, Checks&& 
                   ntiles, kMaxStreamParts);
     HICOM_REQUIRE(a->ff && a->guide && a->q_hi && a->q_lo && a->part_m && a->part_l && a->part_acc && a->scores && a->set_ml && a->set_acc && a->ctx_f16 &&
                       a->hid_f16 && a->loc && a->state_ml_in && a->state_ml_out && a->state_acc && a->out, HICOM_EINVAL, "%s: NULL pointer", who);
-    HICOM_REQUIRE(a->lw0_f16 && a->lb0 && a->lw2_f16 && a->lb2, HICOM_EINVAL, "%s: NULL weight", who);
     HICOM_REQUIRE((a->pos_a != nullptr) == (a->pe != nullptr) && (!a->pe || a->scratch), HICOM_EINVAL, "%s: pos_a, pe and scratch come together", who);
-    HICOM_REQUIRE(a->t0 >= 0 && a->t0 % a->kt == 0, HICOM_EINVAL, "%s: t0=%d (whole window groups of %d frames)", who, a->t0, a->kt);
-    if (a->pe)
-        HICOM_REQUIRE(a->P > 0 && (long)a->t0 + a->Tc <= a->y_index0 && a->y_index0 + a->H <= a->x_index0 && a->x_index0 + a->W <= a->P, HICOM_EINVAL,
-                      "%s: frames %d .. %d, grid %dx%d outside the positional tables (t < %d, y at %d, x at %d, %d rows)", who, a->t0, a->t0 + a->Tc, a->H,
-                      a->W, a->y_index0, a->y_index0, a->x_index0, a->P);
     HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (uintptr_t)a->fe % 16 == 0 && (uintptr_t)a->guide % 16 == 0 && (uintptr_t)a->q_hi % 16 == 0 &&
                       (uintptr_t)a->q_lo % 16 == 0 && (uintptr_t)a->scores % 16 == 0 && (uintptr_t)a->ctx_f16 % 16 == 0 && (uintptr_t)a->hid_f16 % 16 == 0 &&
                       (uintptr_t)a->loc % 16 == 0 && (uintptr_t)a->lw0_f16 % 16 == 0 && (uintptr_t)a->lw2_f16 % 16 == 0 && (uintptr_t)a->set_acc % 16 == 0 &&
@@ -299,8 +295,8 @@ int push_multi(const char* who, const hicom_stream_push_multi_args* a, Checks&& 
     // the chunk's rows in every guide's part of the output: the placement's own check, with the newline rows made chunk-local
     HICOM_REQUIRE(a->nl_count >= 0 && (a->nl_count == 0 || a->nl_first >= a->row0), HICOM_EINVAL, "%s: newline rows", who);
     const long chunk_rows = nw + a->nl_count;
-    int st = place_check(who, a->loc, nullptr, a->newline, a->Q, (int)nw, a->hidden, a->nl_group, a->nl_count, a->nl_count ? a->nl_first - a->row0 : 0,
-                         a->nl_step, chunk_rows, chunk_rows, a->out, a->out_dt, a->ldo, a->q_stride, a->row0);
+    st = place_check(who, a->loc, nullptr, a->newline, a->Q, (int)nw, a->hidden, a->nl_group, a->nl_count, a->nl_count ? a->nl_first - a->row0 : 0,
+                     a->nl_step, chunk_rows, chunk_rows, a->out, a->out_dt, a->ldo, a->q_stride, a->row0);
     if (st != HICOM_OK) return st;
     st = more_checks();
     if (st != HICOM_OK) return st;

@@ -430,14 +430,21 @@ class _Plan:
 
 
 MAX_PLANS = 16       # per store; plans live ON the module (they point into its cached device tables)
+STORES = "_plan_stores"     # on the module: the names of the stores cached_plan has made
 
 
 def cached_plan(proj, store, key, build):
     """THE plan-cache protocol of the package.  The plan of `key` in the module's store `store` ("_engine_plans", "_batch_plans", ...), built
     by build() when there is none or the module's parameters were replaced (a build() that raises leaves no plan behind); weights changed
     in place -- an optimizer step: every address still valid -- are followed by the plan's refresh(), which re-runs the producers of the
-    weight-derived tables into their buffers.  The oldest plan makes room for the seventeenth (its release(), if any).  Counts the use."""
-    plans = proj.__dict__.setdefault(store, {})
+    weight-derived tables into their buffers.  The oldest plan makes room for the seventeenth (its release(), if any).  Counts the use.
+    A store's name is recorded on the module (`proj._plan_stores`) when the store is made: HIComProjector._invalidate_plans drops every
+    recorded store, so a new caller has no list to add its store to."""
+    d = proj.__dict__
+    plans = d.get(store)
+    if plans is None:
+        plans = d[store] = {}
+        d.setdefault(STORES, set()).add(store)
     plan = plans.get(key)
     sig = plan_sig(proj)
     if plan is not None and plan.sig == sig:

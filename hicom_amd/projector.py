@@ -834,18 +834,13 @@ class HIComProjector(nn.Module):
         self.graph_replay = False    # True: capture each cached plan into a hipGraph and replay it
 
     def _invalidate_plans(self):
-        self.__dict__["_engine_params_gen"] = self.__dict__.get("_engine_params_gen", 0) + 1
-        self.__dict__.pop("_engine_plans", None)
-        self.__dict__.pop("_shard_plans", None)
-        self.__dict__.pop("_batch_plans", None)
-        self.__dict__.pop("_ragged_plans", None)
-        self.__dict__.pop("_multi_guide_plans", None)
-        self.__dict__.pop("_ragged_multi_guide_plans", None)
-        self.__dict__.pop("_prepared_plans", None)
-        self.__dict__.pop("_prepare_plans", None)
-        self.__dict__.pop("_clip_stream_plans", None)
-        self.__dict__.pop("_clip_stream_multi_plans", None)
-        self.__dict__.pop("_clip_stream_adapt_plans", None)
+        """Drops every plan of the module: the stores engine.cached_plan has made (it records their names), dist.py's shard plans, and the
+        cached parameter list (its generation)."""
+        d = self.__dict__
+        d["_engine_params_gen"] = d.get("_engine_params_gen", 0) + 1
+        for store in d.pop("_plan_stores", ()):
+            d.pop(store, None)
+        d.pop("_shard_plans", None)
 
     def _apply(self, fn, *args, **kwargs):           # .to() / .cuda() / .bfloat16() ...
         self._invalidate_plans()
@@ -1189,7 +1184,7 @@ class HIComProjector(nn.Module):
                                                           # be None; any number of times, sum Tc <= max_frames; returns this chunk's local rows
             out = s.finish()                              # [local rows so far + 32, hidden], laid out as forward() on the concatenation and equal to
                                                           # it to the kernels' rounding; does not consume the state: push on, finish again
-            s.reset(guide_embed=None)                     # the same buffers for a new clip (and optionally a new guide)
+            s.reset(guide=None)                           # the same buffers for a new clip (and optionally a new guide)
         Each chunk is read once, by one host call (the fused ring kernel with the absolute frame offset, the fold of its partials into ONE
         carried softmax state, the two readout GEMMs), and may be freed when push returns.  open_stream allocates the output buffer for
         max_frames, the state and the positional tables; a chunk length allocates its partials workspace on first use; push allocates
@@ -1210,7 +1205,7 @@ class HIComProjector(nn.Module):
             rows = s.push(frames_feature, frames_embed)   # as ClipStream.push; returns the view [Q, chunk rows, hidden] of this chunk's local rows
             out = s.finish()                              # [Q, local rows so far + 32, hidden]; out[q] is laid out as forward() on the
                                                           # concatenation with guide q and equals it to the kernels' rounding; the state is not consumed
-            s.reset(guide_embeds=None)                    # the same buffers for a new clip (and optionally Q new guides; another Q raises ValueError)
+            s.reset(guide=None)                           # the same buffers for a new clip (and optionally Q new guides; another Q raises ValueError)
         The output buffer is [Q, rows of max_frames + 32, hidden]: the returned views are STRIDED over q.  Each chunk is read by one host
         call (hicom_compressor_stream_push_multi: the multi-guide local kernel, the many-row global stream at the absolute frame offset and
         its merge into one un-normalised set of heads x Q rows, the fold of the set into the carried state, the readout GEMM pair over Q x
@@ -1230,7 +1225,7 @@ class HIComProjector(nn.Module):
             rows = s.push(frames_feature, frames_embed)   # [Q, chunk rows, hidden]
             out = s.finish()                              # [Q, local rows so far + 32, hidden]; out[q] equals forward() on the concatenation with
                                                           # guide q to the kernels' rounding
-            s.reset(guide_embeds=None)
+            s.reset(guide=None)
         The adaptor MLPs are per token and do not know the guide: a push runs both layers of each over the chunk's tokens ONCE for all Q
         guides, into fp16 planes of one chunk that the plan owns (nothing per token outlives the push, unlike prepare_clip's planes of
         the whole video), then the multi-guide local kernel of forward_prepared on those planes and the launches of open_stream_multi's

@@ -8,7 +8,8 @@ Plans are cached on the module by shape (`proj._batch_plans`, `proj._ragged_plan
 through engine.cached_plan, the ONE plan-cache protocol of the package: engine.run_dense's plans go through the same function.  The input /
 output pointers are patched per call.  forward_ragged_multi_guide (ragged_multi_guide.py: the product of the last two,
 `proj._ragged_multi_guide_plans`) is built on the same functions, and so are prepare_clip / forward_prepared (prepared.py:
-`proj._prepare_plans`, `proj._prepared_plans`)."""
+`proj._prepare_plans`, `proj._prepared_plans`).  No list of the stores is kept by hand: cached_plan records each store's name on the module,
+and HIComProjector._invalidate_plans drops what is recorded."""
 from __future__ import annotations
 
 import math
