@@ -242,9 +242,12 @@ class ClipStreamBase:
         """Local rows of the frames pushed so far, as forward() on them would lay them out."""
         return self.proj._layout((self.frames // self.kt, self.gh, self.gw), "video", self.newline is not None, False).n_rows
 
-    def _check_chunk(self, ff, fe):
+    def _check_chunk(self, ff, fe, counters=None):
+        """The chunk against the stream's scope and the clip's counters, in front of any device work; returns Tc.  counters: the (frames,
+        has_fe) pair the chunk continues (None: the stream's own; a ClipStreamGroup passes those of the chunk's slot)."""
         from .projector import _refuse_grad
         what, WHAT = f"{self.NAME}.push", self.WHAT
+        frames, has_fe = (self.frames, self.has_fe) if counters is None else counters
         if isinstance(ff, dict) or isinstance(fe, dict):
             raise NotImplementedError(f"{what}: anyres dict inputs have no clip-stream path (call forward() per image)")
         if seg.seg_recipe(self.proj) != self.RECIPE or self.proj.local_compressor.readout[0].weight.dtype != torch.bfloat16:
@@ -256,15 +259,15 @@ class ClipStreamBase:
             raise ValueError(f"{what}: a chunk of {tuple(ff.shape)}; the stream was opened for [Tc, {self.H}, {self.W}, {self.E}]")
         if Tc <= 0 or Tc % self.kt:
             raise ValueError(f"{what}: Tc={Tc} frames; a chunk is a positive number of whole window groups of {self.kt} frames")
-        if self.frames + Tc > self.max_frames:
-            raise ValueError(f"{what}: {self.frames} + {Tc} frames exceed max_frames={self.max_frames} of {WHAT}")
+        if frames + Tc > self.max_frames:
+            raise ValueError(f"{what}: {frames} + {Tc} frames exceed max_frames={self.max_frames} of {WHAT}")
         for name, t in (("frames_feature", ff), ("frames_embed", fe)):
             if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16):
                 raise NotImplementedError(f"{what}: {name} dtype {getattr(t, 'dtype', type(t))}; the clip stream takes bfloat16 tokens")
         if fe is not None and tuple(fe.shape) != tuple(ff.shape):
             raise ValueError(f"{what}: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
-        if self.has_fe is not None and (fe is not None) != self.has_fe:
-            raise ValueError(f"{what}: this clip's chunks came {'with' if self.has_fe else 'without'} frames_embed so far")
+        if has_fe is not None and (fe is not None) != has_fe:
+            raise ValueError(f"{what}: this clip's chunks came {'with' if has_fe else 'without'} frames_embed so far")
         _refuse_grad(self.proj, what)
         _require_bf16_cuda("frames_feature", ff)
         if fe is not None:

@@ -52,6 +52,8 @@ EXPORTS = (
     "hicom_stream_state_clear_fwd", "hicom_stream_state_fold_fwd", "hicom_compressor_stream_push",
     "hicom_stream_state_fold_set_fwd", "hicom_multi_guide_local_fwd", "hicom_stream_place_rows_fwd", "hicom_compressor_stream_push_multi",
     "hicom_multi_guide_local_adapt_fwd", "hicom_compressor_stream_push_multi_adapt",
+    "hicom_compressor_stream_group_workspace_bytes", "hicom_compressor_stream_group_prepare", "hicom_compressor_stream_group_push",
+    "hicom_stream_group_merge_fold_fwd",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -278,6 +280,22 @@ class StreamPushMultiAdaptArgs(C.Structure):
                 ("adapt_ws", C.c_void_p), ("adapt_ws_bytes", C.c_int64), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
 
 
+GROUP_MAX = 32                                   # slots per clip stream group and items per push (csrc/clip_stream_group.hip: kGroupMax)
+
+
+class StreamGroupPushArgs(C.Structure):
+    """hicom_stream_group_push_args (include/hicom_hip.h): one push of a clip stream group -- field order and types must match the header.
+    tc (per plan) and slot / t0 / row0 (per push) are fixed arrays of 32 ints: they reach the kernels by value."""
+    _fields_ = [("ff", C.c_void_p), ("fe", C.c_void_p), ("guide", C.c_void_p), ("B", C.c_int32), ("items", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("E", C.c_int32), ("kt", C.c_int32), ("ks", C.c_int32), ("nh", C.c_int32), ("hidden", C.c_int32),
+                ("chunks", C.c_int32), ("q_hi", C.c_void_p), ("q_lo", C.c_void_p), ("pos_a", C.c_void_p), ("pe", C.c_void_p), ("P", C.c_int32),
+                ("y_index0", C.c_int32), ("x_index0", C.c_int32), ("l_scale", C.c_float), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("state_ml", C.c_void_p), ("state_acc", C.c_void_p), ("lw0_f16", C.c_void_p), ("lb0", C.c_void_p), ("lw2_f16", C.c_void_p),
+                ("lb2", C.c_void_p), ("out", C.c_void_p), ("out_dt", C.c_int32), ("nl_group", C.c_int32), ("ldo", C.c_int64),
+                ("slot_stride", C.c_int64), ("slot_rows", C.c_int64), ("newline", C.c_void_p), ("tc", C.c_int32 * GROUP_MAX),
+                ("slot", C.c_int32 * GROUP_MAX), ("t0", C.c_int32 * GROUP_MAX), ("row0", C.c_int32 * GROUP_MAX), ("stream", C.c_void_p)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -411,6 +429,11 @@ def lib() -> C.CDLL:
     L.hicom_multi_guide_local_adapt_fwd.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32, i32, i32,
                                                     i32, f32, vp, vp]
     L.hicom_compressor_stream_push_multi_adapt.argtypes = [C.POINTER(StreamPushMultiAdaptArgs)]
+    L.hicom_compressor_stream_group_workspace_bytes.argtypes = [C.POINTER(StreamGroupPushArgs)]
+    L.hicom_compressor_stream_group_prepare.argtypes = [C.POINTER(StreamGroupPushArgs)]
+    L.hicom_compressor_stream_group_push.argtypes = [C.POINTER(StreamGroupPushArgs)]
+    L.hicom_stream_group_merge_fold_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32,
+                                                    vp, vp, vp]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -428,6 +451,7 @@ def lib() -> C.CDLL:
     L.hicom_clip_adapt_prepare_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_ragged_multiguide_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_clips_multiguide_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_stream_group_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -890,6 +914,32 @@ def multi_guide_local_adapt(key_x: int, ff: int, guide: int, ky, vy, ak: SegAdap
 
 def compressor_stream_push_multi_adapt(args: StreamPushMultiAdaptArgs):
     _check(lib().hicom_compressor_stream_push_multi_adapt(C.byref(args)), "hicom_compressor_stream_push_multi_adapt")
+
+
+def compressor_stream_group_workspace(args: StreamGroupPushArgs) -> int:
+    n = lib().hicom_compressor_stream_group_workspace_bytes(C.byref(args))
+    if n < 0:
+        _check(int(n), "hicom_compressor_stream_group_workspace_bytes")
+    return int(n)
+
+
+def compressor_stream_group_prepare(args: StreamGroupPushArgs):
+    _check(lib().hicom_compressor_stream_group_prepare(C.byref(args)), "hicom_compressor_stream_group_prepare")
+
+
+def compressor_stream_group_push(args: StreamGroupPushArgs):
+    _check(lib().hicom_compressor_stream_group_push(C.byref(args)), "hicom_compressor_stream_group_push")
+
+
+def stream_group_merge_fold(part_m, part_l, part_acc, scores, items, rows, Tc, H, W, pe, y0, x0, slots, t0s, state_ml, state_acc):
+    """The merge + fold kernel of a group push alone (hicom_stream_group_merge_fold_fwd): `items` chunks of Tc frames, part_m / part_l
+    [items nparts, 16], part_acc [items nparts, 16, E], scores [items, 16, ceil16(Tc H W)], folded in place into rows slots[i] of
+    state_ml [B, rows, 2] / state_acc [B, rows, E]."""
+    nparts = part_m.shape[0] // items
+    ia = (C.c_int32 * items)
+    _check(lib().hicom_stream_group_merge_fold_fwd(_ptr(part_m), _ptr(part_l), _ptr(part_acc), _ptr(scores), items, nparts, rows, part_acc.shape[-1], Tc, H, W,
+                                                   _ptr(pe), 0 if pe is None else pe.shape[0], y0, x0, ia(*slots), ia(*t0s), state_ml.shape[0],
+                                                   _ptr(state_ml), _ptr(state_acc), _stream()), "hicom_stream_group_merge_fold_fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

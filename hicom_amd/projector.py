@@ -1240,6 +1240,27 @@ class HIComProjector(nn.Module):
             return self.open_stream_multi(guide_embeds, H, W, max_frames, image_newline)
         return clip_stream.ClipStreamAdapt(self, guide_embeds, H, W, max_frames, image_newline)
 
+    def open_stream_group(self, guide_embeds, H, W, max_frames, image_newline=None):
+        """B live videos that arrive in chunks, one guide per video, pushed in ONE call per tick: returns a ClipStreamGroup
+        (hicom_amd/clip_stream_group.py).
+            g = proj.open_stream_group(guide_embeds, H, W, max_frames, image_newline)    # guide_embeds bf16 [B, E], 1 <= B <= 32 slots
+            views = g.push(frames_feature, frames_embed, split_sizes, slots=None)        # bf16 [sum Tc_i, H, W, E], the stacked tensor
+                                                          # forward_ragged reads; slots: the slot of each item (default range(B) for B items),
+                                                          # any non-empty subset in any order, a slot at most once; one view of local rows per item
+            out = g.finish(slot)                          # [local rows of the slot so far + 32, hidden]: forward() on the concatenation of the
+                                                          # slot's chunks with the slot's guide, to the kernels' rounding; the state is not consumed
+            g.reset(slot, guide=None)                     # a new clip (and optionally a new guide) in that slot; the others untouched
+            g.frames[slot], g.rows(slot)
+        One push is one host call (hicom_compressor_stream_group_push), six launches whatever B and the mix of chunk lengths are: the local
+        stage over all windows, the segmented global stream with each item's absolute frame offset, the merge of each item's partials
+        folded into its slot's carried state in place, the readout GEMM pair over all windows, the placement into each slot's part of ONE
+        [B, rows of max_frames + 32, hidden] storage.  Plans are keyed by the tuple of chunk lengths; slot, frame offset and output row
+        travel in the kernel arguments, so a push allocates nothing, copies nothing to the device and never synchronises.
+        The scope of open_stream (windows of <= 64 tokens) with 1 <= B <= 32; everything else raises NotImplementedError / ValueError in
+        front of the first launch.  Inference only.  Which path when: DESIGN.md §3.15 (tools/clip_stream_group_bench.py)."""
+        from . import clip_stream_group
+        return clip_stream_group.ClipStreamGroup(self, guide_embeds, H, W, max_frames, image_newline)
+
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):
         """B items of UNEQUAL length and mixed modality, item i with its own Q_i instructions, in one native call -- a Video-MME style

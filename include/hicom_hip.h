@@ -1330,6 +1330,74 @@ typedef struct hicom_stream_push_multi_adapt_args {
 } hicom_stream_push_multi_adapt_args;
 int hicom_compressor_stream_push_multi_adapt(const hicom_stream_push_multi_adapt_args* args);
 
+/* ---- clip stream group: B live videos, one guide and one carried state each, pushed in one call -------------------
+ * The group's state is state_ml f32 [B][nh][2] = (M, L) and state_acc f32 [B][nh][E]: slot s's slice is ONE set as
+ * hicom_global_combine_fwd reads it (empty: hicom_stream_state_clear_fwd).  The query operands are slot-major: q_hi / q_lo bf16
+ * [B nh][E], pos_a f32 [B nh][P] (hicom_linear_fwd + hicom_fold_query_split_fwd over the B guides), guide bf16 [B][E].
+ *
+ * One push takes `items` chunks (1 <= items <= B <= 32) of the stacked tensor ff / fe bf16 [sum tc_i, H, W, E] (fe NULL: the keys are
+ * ff), item i with tc[i] frames (a positive multiple of kt) for slot slot[i], at the absolute frame offset t0[i], its chunk rows --
+ * windows, with a newline row behind every nl_group of them when nl_group > 0 -- going to rows row0[i] .. of that slot's part of `out`
+ * (slot s starts slot_stride ELEMENTS behind slot 0 and has slot_rows rows of ldo elements).  Six launches whatever items and the mix of
+ * tc are: the local stage over all windows (the guide row of the item's slot), the segmented global stream (frame rows of pos_a at
+ * t0[i] + t, query rows slot[i] nh ..), the merge of the item's partials into its chunk's UN-normalised set folded into the slot's
+ * state IN PLACE (one workgroup per (item, head) row -- so a slot appears at most once per push), the two hicom_readout16_gemm_fwd
+ * launches over all windows and the placement.
+ *
+ * hicom_compressor_stream_group_workspace_bytes: the plan's workspace for the tuple (tc[0 .. items)), from B, items, tc, the geometry,
+ * hidden, out_dt, nl_group and chunks alone (a negative status on a refusal).  hicom_compressor_stream_group_prepare writes the static
+ * tables of that tuple (first token, token count, first window, work units, window -> item, row -> item) to the head of ws: one copy,
+ * synchronises `stream`; once per plan.  hicom_compressor_stream_group_push checks every shape, pointer, alignment, table bound and slot
+ * in front of the first launch -- t0[i] + tc[i] <= y_index0, row0[i] + chunk rows <= slot_rows, slots distinct and < B -- and only
+ * launches: slot, t0 and row0 travel by value in the kernel arguments, nothing is allocated, copied or synchronised.
+ *   chunks : work units per item of the segmented stream (0: every item its share of 2 x #CUs units by token count), as in
+ *            hicom_compressor_ragged_args; E == 1152, nh <= 16, hidden % 64 == 0, H % ks == W % ks == 0, kt ks ks <= 64 */
+typedef struct hicom_stream_group_push_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t B, items, H, W, E, kt, ks, nh;
+    int32_t hidden, chunks;
+    const void* q_hi;
+    const void* q_lo;
+    const float* pos_a;
+    const float* pe;
+    int32_t P, y_index0, x_index0;
+    float l_scale;
+    void* ws;
+    int64_t ws_bytes;
+    float* state_ml;
+    float* state_acc;
+    const void* lw0_f16;
+    const void* lb0;
+    const void* lw2_f16;
+    const void* lb2;
+    void* out;
+    int32_t out_dt, nl_group;
+    int64_t ldo, slot_stride, slot_rows;
+    const void* newline;
+    int32_t tc[32];
+    int32_t slot[32];
+    int32_t t0[32];
+    int32_t row0[32];
+    void* stream;
+} hicom_stream_group_push_args;
+int64_t hicom_compressor_stream_group_workspace_bytes(const hicom_stream_group_push_args* args);
+int hicom_compressor_stream_group_prepare(const hicom_stream_group_push_args* args);
+int hicom_compressor_stream_group_push(const hicom_stream_group_push_args* args);
+
+/* The merge + fold kernel of the push alone: `items` chunks of Tc frames, item i's nparts partials in the slots [i nparts, (i + 1) nparts)
+ * of part_m / part_l f32 [slots][16] and part_acc f32 [slots][16][E] (rows >= rows are not read), its logits f32 [16][ceil16(Tc H W)] at
+ * scores + i 16 ceil16(Tc H W) (read when pe is given).  With M_c the maximum of the item's m_p:
+ *     L_c = sum_p e^(m_p - M_c) l_p      ACC_c = sum_p e^(m_p - M_c) acc_p + sum_s marg_s pe[s]
+ * marg = the t / y / x marginals of e^(logit - M_c), the t rows of pe (f32 [P][E]) at t0[i] + t, the y / x rows at y_index0 / x_index0.
+ * The set is folded into rows slot[i] rows .. of state_ml [B][rows][2] / state_acc [B][rows][E] in place with the arithmetic of
+ * hicom_stream_state_fold_set_fwd (an empty term weighs 0).  slot / t0: HOST arrays of `items` ints; slots distinct and < B <= 32. */
+int hicom_stream_group_merge_fold_fwd(const float* part_m, const float* part_l, const float* part_acc, const float* scores, int32_t items,
+                                      int32_t nparts, int32_t rows, int32_t E, int32_t Tc, int32_t H, int32_t W, const float* pe, int32_t P,
+                                      int32_t y_index0, int32_t x_index0, const int32_t* slot, const int32_t* t0, int32_t B, float* state_ml,
+                                      float* state_acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
