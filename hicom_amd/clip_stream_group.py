@@ -144,8 +144,8 @@ class ClipStreamGroup(cs.ClipStreamBase):
 
     # -- the public surface ---------------------------------------------------------------------------------------------------------------
     def _slot(self, what, slot):
-        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.Q:
-            raise ValueError(f"{what}: slot {slot!r} (0 <= slot < B = {self.Q})")
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.B:
+            raise ValueError(f"{what}: slot {slot!r} (0 <= slot < B = {self.B})")
         return slot
 
     def rows(self, slot):
@@ -161,11 +161,11 @@ class ClipStreamGroup(cs.ClipStreamBase):
         if not isinstance(ff, torch.Tensor) or ff.ndim != 4:
             raise ValueError(f"{what}: frames_feature is [sum Tc, H, W, E], the stacked chunks of the call")
         tcs = tuple(int(n) for n in split_sizes)
-        if not 1 <= len(tcs) <= self.Q:
-            raise ValueError(f"{what}: {len(tcs)} items (1 .. B = {self.Q}: a slot appears at most once per push)")
-        slots = tuple(range(self.Q)) if slots is None and len(tcs) == self.Q else slots
+        if not 1 <= len(tcs) <= self.B:
+            raise ValueError(f"{what}: {len(tcs)} items (1 .. B = {self.B}: a slot appears at most once per push)")
+        slots = tuple(range(self.B)) if slots is None and len(tcs) == self.B else slots
         if slots is None or len(slots) != len(tcs):
-            raise ValueError(f"{what}: slots names the slot of each of the {len(tcs)} items (the default is range(B) for B = {self.Q} items)")
+            raise ValueError(f"{what}: slots names the slot of each of the {len(tcs)} items (the default is range(B) for B = {self.B} items)")
         slots = tuple(self._slot(what, s) for s in slots)
         if len(set(slots)) != len(slots):
             raise ValueError(f"{what}: slots {list(slots)}: a slot appears at most once per push (its state is updated in place)")

@@ -54,6 +54,8 @@ EXPORTS = (
     "hicom_multi_guide_local_adapt_fwd", "hicom_compressor_stream_push_multi_adapt",
     "hicom_compressor_stream_group_workspace_bytes", "hicom_compressor_stream_group_prepare", "hicom_compressor_stream_group_push",
     "hicom_stream_group_merge_fold_fwd",
+    "hicom_compressor_stream_group_multi_workspace_bytes", "hicom_compressor_stream_group_multi_prepare", "hicom_compressor_stream_group_multi_push",
+    "hicom_stream_group_multi_merge_fold_fwd", "hicom_stream_group_place_global_fwd",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -296,6 +298,20 @@ class StreamGroupPushArgs(C.Structure):
                 ("slot", C.c_int32 * GROUP_MAX), ("t0", C.c_int32 * GROUP_MAX), ("row0", C.c_int32 * GROUP_MAX), ("stream", C.c_void_p)]
 
 
+class StreamGroupMultiPushArgs(C.Structure):
+    """hicom_stream_group_multi_push_args (include/hicom_hip.h): one push of a clip stream group with several guides per slot -- field order
+    and types must match the header.  tc / q (per plan) and slot / t0 / row0 / pair0 (per push) are fixed arrays of 32 ints."""
+    _fields_ = [("ff", C.c_void_p), ("fe", C.c_void_p), ("guide", C.c_void_p), ("B", C.c_int32), ("M", C.c_int32), ("items", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("E", C.c_int32), ("kt", C.c_int32), ("ks", C.c_int32), ("nh", C.c_int32), ("hidden", C.c_int32),
+                ("chunks", C.c_int32), ("reserved_", C.c_int32), ("q_hi", C.c_void_p), ("q_lo", C.c_void_p), ("pos_a", C.c_void_p), ("pe", C.c_void_p),
+                ("P", C.c_int32), ("y_index0", C.c_int32), ("x_index0", C.c_int32), ("l_scale", C.c_float), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("state_ml", C.c_void_p), ("state_acc", C.c_void_p), ("lw0_f16", C.c_void_p), ("lb0", C.c_void_p), ("lw2_f16", C.c_void_p),
+                ("lb2", C.c_void_p), ("out", C.c_void_p), ("out_dt", C.c_int32), ("nl_group", C.c_int32), ("ldo", C.c_int64),
+                ("pair_stride", C.c_int64), ("pair_rows", C.c_int64), ("newline", C.c_void_p), ("tc", C.c_int32 * GROUP_MAX),
+                ("q", C.c_int32 * GROUP_MAX), ("slot", C.c_int32 * GROUP_MAX), ("t0", C.c_int32 * GROUP_MAX), ("row0", C.c_int32 * GROUP_MAX),
+                ("pair0", C.c_int32 * GROUP_MAX), ("stream", C.c_void_p)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -434,6 +450,12 @@ def lib() -> C.CDLL:
     L.hicom_compressor_stream_group_push.argtypes = [C.POINTER(StreamGroupPushArgs)]
     L.hicom_stream_group_merge_fold_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32,
                                                     vp, vp, vp]
+    L.hicom_compressor_stream_group_multi_workspace_bytes.argtypes = [C.POINTER(StreamGroupMultiPushArgs)]
+    L.hicom_compressor_stream_group_multi_prepare.argtypes = [C.POINTER(StreamGroupMultiPushArgs)]
+    L.hicom_compressor_stream_group_multi_push.argtypes = [C.POINTER(StreamGroupMultiPushArgs)]
+    L.hicom_stream_group_multi_merge_fold_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32),
+                                                          C.POINTER(i32), i32, vp, vp, vp]
+    L.hicom_stream_group_place_global_fwd.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.c_uint32, i32, i32, i32, vp, i32, i64, i64, i64, vp]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -452,6 +474,7 @@ def lib() -> C.CDLL:
     L.hicom_compressor_ragged_multiguide_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_clips_multiguide_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_stream_group_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_stream_group_multi_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -940,6 +963,48 @@ def stream_group_merge_fold(part_m, part_l, part_acc, scores, items, rows, Tc, H
     _check(lib().hicom_stream_group_merge_fold_fwd(_ptr(part_m), _ptr(part_l), _ptr(part_acc), _ptr(scores), items, nparts, rows, part_acc.shape[-1], Tc, H, W,
                                                    _ptr(pe), 0 if pe is None else pe.shape[0], y0, x0, ia(*slots), ia(*t0s), state_ml.shape[0],
                                                    _ptr(state_ml), _ptr(state_acc), _stream()), "hicom_stream_group_merge_fold_fwd")
+
+
+def compressor_stream_group_multi_workspace(args: StreamGroupMultiPushArgs) -> int:
+    n = lib().hicom_compressor_stream_group_multi_workspace_bytes(C.byref(args))
+    if n < 0:
+        _check(int(n), "hicom_compressor_stream_group_multi_workspace_bytes")
+    return int(n)
+
+
+def compressor_stream_group_multi_prepare(args: StreamGroupMultiPushArgs):
+    _check(lib().hicom_compressor_stream_group_multi_prepare(C.byref(args)), "hicom_compressor_stream_group_multi_prepare")
+
+
+def compressor_stream_group_multi_push(args: StreamGroupMultiPushArgs):
+    _check(lib().hicom_compressor_stream_group_multi_push(C.byref(args)), "hicom_compressor_stream_group_multi_push")
+
+
+def stream_group_multi_merge_fold(part_m, part_l, part_acc, scores, items, rows, Q, Tc, H, W, pe, y0, x0, pair0s, t0s, state_ml, state_acc):
+    """The merge + fold kernel of a group-multi push alone (hicom_stream_group_multi_merge_fold_fwd): `items` chunks of Tc frames with Q
+    guides each, part_m / part_l [items 2 passes nparts, 16], part_acc [.., 16, E], scores [items, 32 passes, ceil16(Tc H W)], folded in
+    place into the rows pair0s[i] rows + R of state_ml [M rows, 2] / state_acc [M rows, E]."""
+    passes = (rows * Q + 31) // 32
+    nparts = part_m.shape[0] // (items * 2 * passes)
+    ia = (C.c_int32 * items)
+    _check(lib().hicom_stream_group_multi_merge_fold_fwd(_ptr(part_m), _ptr(part_l), _ptr(part_acc), _ptr(scores), items, nparts, rows, Q, part_acc.shape[-1],
+                                                         Tc, H, W, _ptr(pe), 0 if pe is None else pe.shape[0], y0, x0, ia(*pair0s), ia(*t0s),
+                                                         state_ml.numel() // (2 * rows), _ptr(state_ml), _ptr(state_acc), _stream()),
+           "hicom_stream_group_multi_merge_fold_fwd")
+
+
+def stream_group_place_global(tok, newline, guide_counts, row0s, named, tail_newline, n_rows, out):
+    """The placement of ClipStreamGroupMulti.finish_many (hicom_stream_group_place_global_fwd): for every slot in `named` and each of its
+    guides, behind row row0s[slot] of the pair's part of out [M, rows, hidden]: tail_newline (0 | 1) newline rows, then n_rows copies of the
+    pair's row of tok (f32 [M, hidden])."""
+    B = len(guide_counts)
+    ia = (C.c_int32 * B)
+    mask = 0
+    for s in named:
+        mask |= 1 << s
+    _check(lib().hicom_stream_group_place_global_fwd(_ptr(tok), _ptr(newline) if tail_newline else None, B, ia(*guide_counts), ia(*row0s), mask, tail_newline,
+                                                     n_rows, out.shape[-1], _ptr(out), _dt(out), out.stride(1), out.stride(0), out.shape[1], _stream()),
+           "hicom_stream_group_place_global_fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -1261,6 +1261,28 @@ class HIComProjector(nn.Module):
         from . import clip_stream_group
         return clip_stream_group.ClipStreamGroup(self, guide_embeds, H, W, max_frames, image_newline)
 
+    def open_stream_group_multi(self, guide_embeds, guide_counts, H, W, max_frames, image_newline=None):
+        """B live videos that arrive in chunks, slot s with its own Q_s guides, pushed in ONE call per tick and finished in ONE launch
+        sequence: returns a ClipStreamGroupMulti (hicom_amd/clip_stream_group_multi.py).
+            g = proj.open_stream_group_multi(guide_embeds, guide_counts, H, W, max_frames, image_newline)
+                                                          # guide_counts: the B ints Q_s, 1 <= B <= 32, 1 <= Q_s <= 32; guide_embeds bf16
+                                                          # [sum Q_s, E], the guides of slot s in the rows [sum_(j<s) Q_j, + Q_s)
+            views = g.push(frames_feature, frames_embed, split_sizes, slots=None)        # as ClipStreamGroup.push; views[i]: [Q_slot_i, chunk rows, hidden]
+            out = g.finish(slot)                          # [Q_s, local rows of the slot so far + 32, hidden]; out[q] is forward() on the
+                                                          # concatenation of the slot's chunks with its guide q, to the kernels' rounding
+            outs = g.finish_many(slots=None)              # {slot: the same} for several slots (default: every slot with frames), ONE launch sequence
+            g.reset(slot, guides=None)                    # a new clip (and optionally Q_s new guides) in that slot; the others untouched
+            g.frames[slot], g.rows(slot), g.guide_counts
+        One push is one host call (hicom_compressor_stream_group_multi_push), six launches whatever B, the Q_s and the chunk lengths are:
+        every item's tokens are read once per 4 guides by the local stage and once per 32 folded rows by the global stream; the merge of
+        each folded row's partials is folded into the pair's carried state in place.  Plans are keyed by the tuple of (Tc_i, Q_i); first
+        pair, frame offset and output row travel in the kernel arguments, so a push allocates nothing, copies nothing to the device and
+        never synchronises.  finish_many is the combine over the whole state, four linear launches with sum Q_s rows and one placement.
+        The scope of open_stream_group; everything else raises NotImplementedError / ValueError in front of the first launch.  Inference
+        only.  Which path when: DESIGN.md §3.16 (tools/clip_stream_group_multi_bench.py)."""
+        from . import clip_stream_group_multi
+        return clip_stream_group_multi.ClipStreamGroupMulti(self, guide_embeds, guide_counts, H, W, max_frames, image_newline)
+
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):
         """B items of UNEQUAL length and mixed modality, item i with its own Q_i instructions, in one native call -- a Video-MME style

@@ -1398,6 +1398,82 @@ int hicom_stream_group_merge_fold_fwd(const float* part_m, const float* part_l, 
                                       int32_t y_index0, int32_t x_index0, const int32_t* slot, const int32_t* t0, int32_t B, float* state_ml,
                                       float* state_acc, void* stream);
 
+/* ---- clip stream group with several guides per slot -----------------------------------------------------------------
+ * Slot s has Q_s guides (1 <= Q_s <= 32); a PAIR is one (slot, guide), numbered slot-major then guide-major: slot s owns the pairs
+ * [pair0_s, pair0_s + Q_s), pair0_s = sum_{j<s} Q_j, M = sum Q_s pairs in all (hicom_compressor_ragged_multiguide_args' convention).
+ * Everything is pair-major: guide bf16 [M][E], q_hi / q_lo bf16 [>= M nh][E] and pos_a f32 [>= M nh][P] with row pair nh + h
+ * (hicom_linear_fwd + hicom_fold_query_split_fwd over the M guides), state_ml f32 [M nh][2], state_acc f32 [M nh][E] -- slot s's rows are
+ * contiguous -- and out: pair p starts pair_stride ELEMENTS behind pair 0 and has pair_rows rows of ldo elements.
+ *
+ * One push takes `items` chunks (1 <= items <= B <= 32) of the stacked tensor ff / fe bf16 [sum tc_i, H, W, E]; item i has tc[i] frames and
+ * the q[i] guides of slot slot[i], whose first pair is pair0[i]; its frames start at the absolute offset t0[i], its chunk rows go to rows
+ * row0[i] .. of each of its pairs.  Six launches whatever items, q and tc are: the local stage over the stack's windows (every guide of the
+ * item's slot, tokens loaded once per 4 guides), the segmented stream with two row groups (32 folded rows of one item per workgroup, one
+ * pass per 32 rows), the merge of every folded row's partials folded into the pair's state IN PLACE (one workgroup per (item, folded row):
+ * a slot appears at most once per push and the items' pair ranges do not meet), the two hicom_readout16_gemm_fwd launches over all pairs'
+ * window contexts and the placement.
+ *
+ * hicom_compressor_stream_group_multi_workspace_bytes: the plan's workspace for the tuple ((tc[i], q[i])), from B, M, items, tc, q, the
+ * geometry, hidden, out_dt, nl_group and chunks alone (a negative status on a refusal).  ..._prepare writes the static tables of that
+ * tuple to the head of ws: one copy, synchronises `stream`; once per plan.  ..._push checks every shape, pointer, alignment, table bound,
+ * slot and pair range in front of the first launch -- t0[i] + tc[i] <= y_index0, row0[i] + chunk rows <= pair_rows, slots distinct and
+ * < B, 1 <= q[i] <= 32, pair0[i] + q[i] <= M -- and only launches: pair0, t0 and row0 travel by value in the kernel arguments, nothing is
+ * allocated, copied or synchronised.  chunks: token chunks per item and pass (0: the item's share of 2 x #CUs work units by tiles x passes). */
+typedef struct hicom_stream_group_multi_push_args {
+    const void* ff;
+    const void* fe;
+    const void* guide;
+    int32_t B, M, items, H, W, E, kt, ks, nh, hidden, chunks, reserved_;
+    const void* q_hi;
+    const void* q_lo;
+    const float* pos_a;
+    const float* pe;
+    int32_t P, y_index0, x_index0;
+    float l_scale;
+    void* ws;
+    int64_t ws_bytes;
+    float* state_ml;
+    float* state_acc;
+    const void* lw0_f16;
+    const void* lb0;
+    const void* lw2_f16;
+    const void* lb2;
+    void* out;
+    int32_t out_dt, nl_group;
+    int64_t ldo, pair_stride, pair_rows;
+    const void* newline;
+    int32_t tc[32];
+    int32_t q[32];
+    int32_t slot[32];
+    int32_t t0[32];
+    int32_t row0[32];
+    int32_t pair0[32];
+    void* stream;
+} hicom_stream_group_multi_push_args;
+int64_t hicom_compressor_stream_group_multi_workspace_bytes(const hicom_stream_group_multi_push_args* args);
+int hicom_compressor_stream_group_multi_prepare(const hicom_stream_group_multi_push_args* args);
+int hicom_compressor_stream_group_multi_push(const hicom_stream_group_multi_push_args* args);
+
+/* The merge + fold kernel of that push alone: `items` chunks of Tc frames with Q guides each, rows = heads, R = rows Q folded rows per item in
+ * passes = ceil(R / 32) passes.  Item i's partials lie in the slots [i S, (i + 1) S), S = 2 passes nparts, ordered [pass][row group][chunk]
+ * (folded row R: row R % 16 of the slots i S + (R / 16) nparts + c, c < nparts) of part_m / part_l f32 [slots][16] and part_acc f32
+ * [slots][16][E]; its logits f32 [32 passes][ceil16(Tc H W)] at scores + i 32 passes ceil16(Tc H W) (read when pe is given).  The arithmetic
+ * is that of hicom_stream_group_merge_fold_fwd per folded row, into rows pair0[i] rows + R of state_ml [M rows][2] / state_acc [M rows][E] in
+ * place.  pair0 / t0: HOST arrays of `items` ints; the ranges [pair0[i], pair0[i] + Q) lie inside the M pairs and do not meet. */
+int hicom_stream_group_multi_merge_fold_fwd(const float* part_m, const float* part_l, const float* part_acc, const float* scores, int32_t items,
+                                            int32_t nparts, int32_t rows, int32_t Q, int32_t E, int32_t Tc, int32_t H, int32_t W, const float* pe,
+                                            int32_t P, int32_t y_index0, int32_t x_index0, const int32_t* pair0, const int32_t* t0, int32_t M,
+                                            float* state_ml, float* state_acc, void* stream);
+
+/* The placement of a batched finish alone: for every slot s < B with bit s of `named` set and every q < guide_counts[s], into pair
+ * pair0_s + q of out ([M][pair_rows][ldo], pairs pair_stride elements apart) at row row0[s]: `tail` (0 | 1) copies of newline (bf16
+ * [hidden]), then n_rows copies of tok[pair0_s + q] (f32 [M][hidden], rounded once: the copies are bit-identical).  Rows of tok that
+ * belong to slots not named are never read, their pairs never written.  guide_counts / row0: HOST arrays of B ints (row0 of a slot not
+ * named is not looked at). */
+int hicom_stream_group_place_global_fwd(const float* tok, const void* newline, int32_t B, const int32_t* guide_counts, const int32_t* row0,
+                                        uint32_t named, int32_t tail, int32_t n_rows, int32_t hidden, void* out, int32_t out_dt, int64_t ldo,
+                                        int64_t pair_stride, int64_t pair_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
