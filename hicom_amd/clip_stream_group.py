@@ -18,7 +18,9 @@ guide, to the kernels' rounding.
 
 Who holds what.  ClipStreamBase has the open sequence, the scope (stream_scope), the chunk checks (_check_chunk, with the slot's counters),
 the layout (prefix_layout, chunk_rows), the plan key and store (cached_plan with a store of its own) and the readout fields of the push
-block (_fill_common); this class has per-slot counters in the place of the base's single ones and the device side.  Per group, at open:
+block (_fill_common); this class has per-slot counters in the place of the base's single ones and the device side.  The device side is
+written pair-major, for slots of several guides (clip_stream_group_multi.py: ClipStreamGroupMulti supplies only its native entry points,
+its plane rows and field names); this class is its case guide_counts == (1,) * B, pair0 == range(B), M == B.  Per group, at open:
 the output storage [B, cap_rows + 32, hidden], state_ml [B, nh, 2] and state_acc [B, nh, E] (slot s's slices are the ONE set
 GlobalCompressor.finish reads), the slot-major query operands q_hi / q_lo [B nh, E] and pos_a [B nh, P], the positional tables for
 max_frames.  The query preparation (hicom_linear_fwd + hicom_fold_query_split_fwd) runs at open and per reset(slot) -- then only that
@@ -50,11 +52,15 @@ class ClipStreamGroup(cs.ClipStreamBase):
     """The object HIComProjector.open_stream_group returns (module docstring).  `frames` and `has_fe` are per-slot lists; `out` is
     [B, cap_rows + 32, hidden]; `guides` the [B, E] block, one row per slot."""
     NAME, WHAT, STORE = "ClipStreamGroup", "open_stream_group", STORE_GROUP
-    MULTI, GUIDE = True, "guide_embeds"          # the guides come as one [B, E] block: Q of the base is B, the slots
+    MULTI, GUIDE = True, "guide_embeds"          # the guides come as one [sum Q_s, E] block: Q of the base is M, the pairs
+    PAIRS = False                                # the push block has M, q and pair0 (ClipStreamGroupMulti); here a slot is its one pair
+    STRIDE, ROWS = "slot_stride", "slot_rows"    # the push block's fields for the output's stride and rows per slot / pair
 
     def __init__(self, proj, guide_embeds, H, W, max_frames, image_newline=None):
         super().__init__(proj, guide_embeds, H, W, max_frames, image_newline)
-        self.B = self.Q
+        if not self.PAIRS:
+            self.B = self.M = self.Q
+            self.guide_counts, self.pair0 = (1,) * self.B, list(range(self.B))
         self.frames = [0] * self.B
         self.has_fe = [None] * self.B            # per slot, decided by the slot's first push; every chunk of a clip agrees
         self._spans = {}
@@ -63,16 +69,26 @@ class ClipStreamGroup(cs.ClipStreamBase):
         if proj.global_compressor.use_pos_emb and (Tc * (H + W) + Tc + H + W) * 4 > 48 * 1024:
             raise NotImplementedError(f"{what}: Tc={Tc} frames of {H}x{W}: the merge keeps Tc (H + W) marginal sums in LDS; push shorter chunks")
 
-    # -- device work ------------------------------------------------------------------------------------------------------------------------
+    # -- what the two classes say of themselves ------------------------------------------------------------------------------------------
+    def _native(self):
+        """(the push block's class, workspace_bytes, prepare, push) of `nv` as the class's module sees it."""
+        return nv.StreamGroupPushArgs, nv.compressor_stream_group_workspace, nv.compressor_stream_group_prepare, nv.compressor_stream_group_push
+
+    def _row_shapes(self, M, nh):
+        """(the leading dimensions of state_ml / state_acc, the rows of the query planes) for M pairs."""
+        return (M, nh), M * nh
+
+    # -- device work, pair-major: pair p = pair0[slot] + q owns out[p], the state rows and the query rows [p nh, (p + 1) nh) ---------------------
     def _allocate(self, rows):
-        dev, E, B, nh, gc = self.device, self.E, self.Q, self.nh, self.proj.global_compressor
+        dev, E, M, nh, gc = self.device, self.E, self.Q, self.nh, self.proj.global_compressor
+        state, RP = self._row_shapes(M, nh)
 
         def f32(*shape):
             return torch.empty(shape, dtype=torch.float32, device=dev)
-        self.out = torch.empty((B, rows, self.hidden), dtype=self.out_dtype, device=dev)
-        self.state_ml, self.state_acc = f32(B, nh, 2), f32(B, nh, E)           # in place: one workgroup owns a row, no ping-pong
-        self.qp = f32(B, E)
-        self.q_hi = torch.zeros((B * nh, E), dtype=torch.bfloat16, device=dev)
+        self.out = torch.empty((M, rows, self.hidden), dtype=self.out_dtype, device=dev)
+        self.state_ml, self.state_acc = f32(*state, 2), f32(*state, E)         # in place: one workgroup owns a row, no ping-pong
+        self.qp = f32(M, E)
+        self.q_hi = torch.zeros((RP, E), dtype=torch.bfloat16, device=dev)     # (rows >= M nh stay zero)
         self.q_lo = torch.zeros_like(self.q_hi)
         self.pos_a = self.pe = self.kpe = None
         self.P = self.y0 = self.x0 = 0
@@ -80,67 +96,78 @@ class ClipStreamGroup(cs.ClipStreamBase):
             # sized for max_frames: the y / x table offsets (cap, cap + H) never move while the group lives; one set for all slots
             self.pe, self.kpe, cap = gc.pos_and_kpe(self.max_frames, self.H, self.W, dev)
             self.P, self.y0, self.x0 = self.pe.shape[0], cap, cap + self.H
-            self.pos_a = torch.zeros((B * nh, self.P), dtype=torch.float32, device=dev)
+            self.pos_a = torch.zeros((RP, self.P), dtype=torch.float32, device=dev)
         # staging planes of the query preparation (_prepare)
         self.stage = (torch.zeros_like(self.q_hi), torch.zeros_like(self.q_hi), None if self.pos_a is None else torch.zeros_like(self.pos_a))
 
+    def _pairs(self, slot):
+        return slice(self.pair0[slot], self.pair0[slot] + self.guide_counts[slot])
+
     def _prepare(self, guides, slot=None):
-        """Everything that depends on the guides alone, for every slot (open) or for `slot`'s rows only (reset): q_proj, the fold into the
+        """Everything that depends on the guides alone, for every slot (open) or for `slot`'s pairs only (reset): q_proj, the fold into the
         query planes and the score-side positional table, the empty state."""
         from .projector import _linear_params
         gc = self.proj.global_compressor
         att, nh = gc.attn_layer, self.nh
         if slot is None:
-            self.guides = guides.contiguous().clone()                          # the group's own block: reset(slot, guide) writes a row
-            s0, s1 = 0, self.Q
+            self.guides = guides.contiguous().clone()                          # the group's own block: reset(slot, guides) writes rows
+            pairs = slice(0, self.Q)
         else:
+            pairs = self._pairs(slot)
             if guides is not None:
-                self.guides[slot].copy_(guides)
-            s0, s1 = slot, slot + 1
+                self.guides[pairs].copy_(guides)
         wq, bq = _linear_params(att.q_proj)
         wk, _ = _linear_params(att.k_proj)
         if gc.use_pos_emb:
             gc.pos_and_kpe(self.max_frames, self.H, self.W, self.device)       # (follows k_proj.weight in place)
-        # The launch pair always runs over all B guides, into staging planes: both kernels choose their instantiation by the row count
+        # The launch pair always runs over all M guides, into staging planes: both kernels choose their instantiation by the row count
         # (one row takes another path and rounds differently), and a replay behind reset(slot) must be bit-equal to the slot's first
-        # run.  Only the rows of the slots being prepared are copied into the planes a push reads: the other slots keep theirs.
+        # run.  Only the rows of the pairs being prepared are copied into the planes a push reads: the other slots keep theirs.
         hi, lo, pos = self.stage
         nv.linear(self.guides, wq, bq, self.qp)
         nv.fold_query_split(self.qp, wk, self.kpe, nh, att.scale, hi, lo, pos)
-        rows = slice(s0 * nh, s1 * nh)
+        rows = slice(pairs.start * nh, pairs.stop * nh)
         self.q_hi[rows].copy_(hi[rows])
         self.q_lo[rows].copy_(lo[rows])
         if pos is not None:
             self.pos_a[rows].copy_(pos[rows])
-        nv.stream_state_clear(self.state_ml[s0:s1], self.state_acc[s0:s1])
+        nv.stream_state_clear(self.state_ml.view(-1, 2)[rows], self.state_acc.view(-1, self.E)[rows])
 
-    def _build_plan(self, tcs, has_fe, stream=None):
-        """The plan of one tuple of chunk lengths: the block with everything but the per-push fields, the workspace and its static tables."""
-        a = nv.StreamGroupPushArgs()
-        a.B, a.items, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.chunks = self.Q, len(tcs), self.H, self.W, self.E, self.kt, self.ks, self.nh, self.hidden, 0
+    def _build_plan(self, items, has_fe, stream=None):
+        """The plan of one tuple of chunk lengths (PAIRS: of (chunk length, guide count)): the block with everything but the per-push fields,
+        the workspace and its static tables."""
+        Args, workspace, prepare, _ = self._native()
+        a = Args()
+        a.B, a.items, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.chunks = self.B, len(items), self.H, self.W, self.E, self.kt, self.ks, self.nh, self.hidden, 0
         a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
         a.nl_group = self.proj._layout((self.max_frames // self.kt, self.gh, self.gw), "video", self.newline is not None, False).nl_group
-        for i, n in enumerate(tcs):
-            a.tc[i] = n
-        ws, (a.ws,), keep = self._fill_common(a, max(tcs), 0, [nv.compressor_stream_group_workspace(a)])
+        if self.PAIRS:
+            a.M, a.q[:len(items)], items = self.M, [q for _, q in items], [n for n, _ in items]
+        a.tc[:len(items)] = items
+        ws, (a.ws,), keep = self._fill_common(a, max(items), 0, [workspace(a)])
         a.ws_bytes, a.stream = ws.numel(), stream
-        nv.compressor_stream_group_prepare(a)
+        prepare(a)
         return cs.StreamPlan(a, ws, keep, self.proj.local_compressor.readout_f16)
 
     def _launch(self, plan, ff, fe, slots, t0s, row0s, stream):
         a = plan.args
+        a.B = self.B                             # of THIS group, as M and pair0: plans are shared by the groups of a module, and the C checks use them
         a.ff, a.fe, a.guide = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr()
         a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
         a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
         a.pe = self.pe.data_ptr() if self.pe is not None else None
         a.P, a.y_index0, a.x_index0 = self.P, self.y0, self.x0
         a.state_ml, a.state_acc = self.state_ml.data_ptr(), self.state_acc.data_ptr()
-        a.out, a.slot_stride, a.slot_rows = self.out.data_ptr(), self.out.stride(0), self.out.shape[1]
+        a.out = self.out.data_ptr()
+        setattr(a, self.STRIDE, self.out.stride(0))
+        setattr(a, self.ROWS, self.out.shape[1])
         a.newline = self.newline.data_ptr() if (self.newline is not None and a.nl_group) else None
         for i, (s, t0, row0) in enumerate(zip(slots, t0s, row0s)):
             a.slot[i], a.t0[i], a.row0[i] = s, t0, row0
+        if self.PAIRS:
+            a.M, a.pair0[:len(slots)] = self.M, [self.pair0[s] for s in slots]
         a.stream = stream
-        nv.compressor_stream_group_push(a)
+        self._native()[3](a)
 
     # -- the public surface ---------------------------------------------------------------------------------------------------------------
     def _slot(self, what, slot):
@@ -194,20 +221,22 @@ class ClipStreamGroup(cs.ClipStreamBase):
     def push(self, frames_feature, frames_embed=None, split_sizes=(), slots=None):
         """The next chunks of the slots named: frames_feature bf16 [sum Tc_i, H, W, E] (frames_embed None: the keys are frames_feature; all or
         none within a call), split_sizes the chunk lengths Tc_i (positive multiples of kt), slots the slot of each item (module docstring).
-        Returns one view per item: that chunk's local rows in their final place in the slot's part of the output storage, complete on the
-        caller's stream; the stack is not referenced afterwards."""
+        Returns one view per item: that chunk's local rows ([chunk rows, hidden]; PAIRS: of every guide of the slot, [Q_slot, chunk rows,
+        hidden]) in their final place in the output storage, complete on the caller's stream; the stack is not referenced afterwards."""
         tcs, slots = self._check_push(frames_feature, frames_embed, split_sizes, slots)
         ff = frames_feature.contiguous()
         fe = frames_embed.contiguous() if frames_embed is not None else None
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(tcs, fe is not None, stream), lambda: self._build_plan(tcs, fe is not None, stream))
+        # what an item gives the plan key: its length and, PAIRS, its guide count, which decides its work units
+        items = tuple((n, self.guide_counts[s]) for n, s in zip(tcs, slots)) if self.PAIRS else tcs
+        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(items, fe is not None, stream), lambda: self._build_plan(items, fe is not None, stream))
         spans = [self._span(self.frames[s], n) for n, s in zip(tcs, slots)]
         self._launch(plan, ff, fe, slots, [self.frames[s] for s in slots], [sp[0] for sp in spans], stream)
         for n, s in zip(tcs, slots):
             self.frames[s] += n
             self.has_fe[s] = fe is not None
         self.n_pushes += 1
-        return [self.out[s, sp[0]:sp[3]] for s, sp in zip(slots, spans)]
+        return [self.out[self._pairs(s) if self.PAIRS else s, sp[0]:sp[3]] for s, sp in zip(slots, spans)]
 
     def finish(self, slot):
         """[local rows of `slot` so far + 32, hidden]: the rows that depend on the whole clip (a `one_token` newline row, the 32 global rows)

@@ -18,8 +18,10 @@ contiguous: the one set GlobalCompressor.finish_guides reads), the query operand
 finish(slot)[q] is forward() on the concatenation of everything pushed into the slot with the slot's guide q, to the kernels' rounding;
 `slots` of a push as for ClipStreamGroup: a slot at most once, an absent slot is not touched.
 
-Who holds what.  ClipStreamGroup has the checks of a push, the per-slot counters and the spans; ClipStreamBase the scope, the layout and
-the readout fields of the push block.  This class has the pair-major device side.  The query preparation runs at open and per reset(slot),
+Who holds what.  ClipStreamGroup has the checks of a push, the per-slot counters, the spans and the pair-major device side (allocation,
+query preparation, plan, launch and push: one body, of which ClipStreamGroup itself is the case of one pair per slot); ClipStreamBase the
+scope, the layout and the readout fields of the push block.  This class has the counts, the plan key, what the body asks a class for (the
+native entry points, the rows of the planes, the names of two fields) and the batched finish.  The query preparation runs at open and per reset(slot),
 always over all M guides into staging planes -- only the prepared slot's rows are copied into the planes a push reads (ClipStreamGroup's
 rule: the kernels pick their instantiation by the row count, and a replay must be bit-equal to the first run).  Per plan, keyed by the
 TUPLE of (Tc_i, Q_i) of the call: the workspace and the static device tables.  Per push, by value in the kernel arguments: every item's
@@ -42,7 +44,6 @@ import torch
 from . import clip_stream as cs
 from . import clip_stream_group as csg
 from . import native as nv
-from . import segments as seg
 
 STORE_GROUP_MULTI = "_clip_stream_group_multi_plans"
 MAX_SLOTS = MAX_GUIDES = nv.GROUP_MAX
@@ -74,17 +75,15 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
     """The object HIComProjector.open_stream_group_multi returns (module docstring).  `frames` and `has_fe` are per-slot lists; `out` is
     [M, cap_rows + 32, hidden], pair-major; `guides` the [M, E] block; `pair0[s]` the first pair of slot s."""
     NAME, WHAT, STORE = "ClipStreamGroupMulti", "open_stream_group_multi", STORE_GROUP_MULTI
+    PAIRS, STRIDE, ROWS = True, "pair_stride", "pair_rows"
 
     def __init__(self, proj, guide_embeds, guide_counts, H, W, max_frames, image_newline=None):
         # the open sequence is ClipStreamBase's (scope, allocate, prepare); _scope takes the counts from here and sets B (the slots, what
         # ClipStreamGroup's checks read), M (the pairs; the base's Q, the guide rows, equals it) and pair0
         self._counts_arg = guide_counts
-        cs.ClipStreamBase.__init__(self, proj, guide_embeds, H, W, max_frames, image_newline)
+        super().__init__(proj, guide_embeds, H, W, max_frames, image_newline)
         del self._counts_arg
         assert self.Q == self.M
-        self.frames = [0] * self.B
-        self.has_fe = [None] * self.B
-        self._spans = {}
 
     def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
         """stream_scope on the guide block (its count is checked per slot here, not per call) and the counts: (E, kt, ks, hidden, heads)."""
@@ -106,109 +105,20 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
         so groups of one module with other guide counts share plans."""
         return (self.B, tcqs, self.H, self.W, self.E, has_fe, None if self.newline is None else tuple(self.newline.shape), self.out_dtype, stream)
 
-    # -- device work ------------------------------------------------------------------------------------------------------------------------
+    # -- what the class says of itself; the device work and push are ClipStreamGroup's -------------------------------------------------------
+    def _native(self):
+        return (nv.StreamGroupMultiPushArgs, nv.compressor_stream_group_multi_workspace, nv.compressor_stream_group_multi_prepare,
+                nv.compressor_stream_group_multi_push)
+
+    def _row_shapes(self, M, nh):
+        return (M * nh,), (M * nh + 31) // 32 * 32       # whole 32-row passes, as the ragged multi-guide step pads its planes
+
     def _allocate(self, rows):
-        dev, E, M, nh, gc = self.device, self.E, self.M, self.nh, self.proj.global_compressor
-        RP = (M * nh + 31) // 32 * 32            # whole 32-row passes, as the ragged multi-guide step pads its planes; rows >= M nh stay zero
-
-        def f32(*shape):
-            return torch.empty(shape, dtype=torch.float32, device=dev)
-        self.out = torch.empty((M, rows, self.hidden), dtype=self.out_dtype, device=dev)
-        self.state_ml, self.state_acc = f32(M * nh, 2), f32(M * nh, E)         # in place: one workgroup owns a row, no ping-pong
-        self.qp = f32(M, E)
-        self.q_hi = torch.zeros((RP, E), dtype=torch.bfloat16, device=dev)
-        self.q_lo = torch.zeros_like(self.q_hi)
-        self.pos_a = self.pe = self.kpe = None
-        self.P = self.y0 = self.x0 = 0
-        if gc.use_pos_emb:
-            # sized for max_frames: the y / x table offsets (cap, cap + H) never move while the group lives; one set for all slots
-            self.pe, self.kpe, cap = gc.pos_and_kpe(self.max_frames, self.H, self.W, dev)
-            self.P, self.y0, self.x0 = self.pe.shape[0], cap, cap + self.H
-            self.pos_a = torch.zeros((RP, self.P), dtype=torch.float32, device=dev)
-        # staging planes of the query preparation (_prepare)
-        self.stage = (torch.zeros_like(self.q_hi), torch.zeros_like(self.q_hi), None if self.pos_a is None else torch.zeros_like(self.pos_a))
+        super()._allocate(rows)
+        M, E, gc = self.M, self.E, self.proj.global_compressor
         # finish_many: the combined contexts and the global tail with M rows
-        self.fin = (f32(M * nh, E), f32(M, E), f32(M, E), f32(M, gc.readout[0].out_features), f32(M, gc.readout[2].out_features))
-
-    def _prepare(self, guides, slot=None):
-        """Everything that depends on the guides alone, for every slot (open) or for `slot`'s pairs only (reset): q_proj, the fold into the
-        query planes and the score-side positional table, the empty state."""
-        from .projector import _linear_params
-        gc = self.proj.global_compressor
-        att, nh = gc.attn_layer, self.nh
-        if slot is None:
-            self.guides = guides.contiguous().clone()                          # the group's own block: reset(slot, guides) writes rows
-            p0, p1 = 0, self.M
-        else:
-            p0, p1 = self.pair0[slot], self.pair0[slot] + self.guide_counts[slot]
-            if guides is not None:
-                self.guides[p0:p1].copy_(guides)
-        wq, bq = _linear_params(att.q_proj)
-        wk, _ = _linear_params(att.k_proj)
-        if gc.use_pos_emb:
-            gc.pos_and_kpe(self.max_frames, self.H, self.W, self.device)       # (follows k_proj.weight in place)
-        # always over all M guides, into staging planes; only the prepared pairs' rows are copied (ClipStreamGroup._prepare has the reason)
-        hi, lo, pos = self.stage
-        nv.linear(self.guides, wq, bq, self.qp)
-        nv.fold_query_split(self.qp, wk, self.kpe, nh, att.scale, hi, lo, pos)
-        rows = slice(p0 * nh, p1 * nh)
-        self.q_hi[rows].copy_(hi[rows])
-        self.q_lo[rows].copy_(lo[rows])
-        if pos is not None:
-            self.pos_a[rows].copy_(pos[rows])
-        nv.stream_state_clear(self.state_ml[rows], self.state_acc[rows])
-
-    def _build_plan(self, tcqs, has_fe, stream=None):
-        """The plan of one tuple of (chunk length, guide count): the block with everything but the per-push fields, the workspace and its
-        static tables."""
-        a = nv.StreamGroupMultiPushArgs()
-        a.B, a.M, a.items, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.chunks = (self.B, self.M, len(tcqs), self.H, self.W, self.E, self.kt, self.ks, self.nh,
-                                                                              self.hidden, 0)
-        a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
-        a.nl_group = self.proj._layout((self.max_frames // self.kt, self.gh, self.gw), "video", self.newline is not None, False).nl_group
-        for i, (n, q) in enumerate(tcqs):
-            a.tc[i], a.q[i] = n, q
-        ws, (a.ws,), keep = self._fill_common(a, max(n for n, _ in tcqs), 0, [nv.compressor_stream_group_multi_workspace(a)])
-        a.ws_bytes, a.stream = ws.numel(), stream
-        nv.compressor_stream_group_multi_prepare(a)
-        return cs.StreamPlan(a, ws, keep, self.proj.local_compressor.readout_f16)
-
-    def _launch(self, plan, ff, fe, slots, t0s, row0s, stream):
-        a = plan.args
-        a.B, a.M = self.B, self.M                # of THIS group: plans are shared by the groups of a module, and the C checks use both
-        a.ff, a.fe, a.guide = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr()
-        a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
-        a.pos_a = self.pos_a.data_ptr() if self.pos_a is not None else None
-        a.pe = self.pe.data_ptr() if self.pe is not None else None
-        a.P, a.y_index0, a.x_index0 = self.P, self.y0, self.x0
-        a.state_ml, a.state_acc = self.state_ml.data_ptr(), self.state_acc.data_ptr()
-        a.out, a.pair_stride, a.pair_rows = self.out.data_ptr(), self.out.stride(0), self.out.shape[1]
-        a.newline = self.newline.data_ptr() if (self.newline is not None and a.nl_group) else None
-        for i, (s, t0, row0) in enumerate(zip(slots, t0s, row0s)):
-            a.slot[i], a.t0[i], a.row0[i], a.pair0[i] = s, t0, row0, self.pair0[s]
-        a.stream = stream
-        nv.compressor_stream_group_multi_push(a)
-
-    # -- the public surface ---------------------------------------------------------------------------------------------------------------
-    def _pairs(self, slot):
-        return slice(self.pair0[slot], self.pair0[slot] + self.guide_counts[slot])
-
-    def push(self, frames_feature, frames_embed=None, split_sizes=(), slots=None):
-        """The next chunks of the slots named, as ClipStreamGroup.push.  Returns one view per item, [Q_slot, chunk rows, hidden]: that
-        chunk's local rows of every guide of the slot in their final place in the output storage, complete on the caller's stream."""
-        tcs, slots = self._check_push(frames_feature, frames_embed, split_sizes, slots)
-        ff = frames_feature.contiguous()
-        fe = frames_embed.contiguous() if frames_embed is not None else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        tcqs = tuple((n, self.guide_counts[s]) for n, s in zip(tcs, slots))     # an item's Q decides its work units: it belongs to the plan
-        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(tcqs, fe is not None, stream), lambda: self._build_plan(tcqs, fe is not None, stream))
-        spans = [self._span(self.frames[s], n) for n, s in zip(tcs, slots)]
-        self._launch(plan, ff, fe, slots, [self.frames[s] for s in slots], [sp[0] for sp in spans], stream)
-        for n, s in zip(tcs, slots):
-            self.frames[s] += n
-            self.has_fe[s] = fe is not None
-        self.n_pushes += 1
-        return [self.out[self._pairs(s), sp[0]:sp[3]] for s, sp in zip(slots, spans)]
+        self.fin = tuple(torch.empty(shape, dtype=torch.float32, device=self.device)
+                         for shape in ((M * self.nh, E), (M, E), (M, E), (M, gc.readout[0].out_features), (M, gc.readout[2].out_features)))
 
     def finish_many(self, slots=None):
         """{slot: [Q_s, local rows of the slot so far + 32, hidden]} for the slots named (default: every slot that holds frames), in ONE

@@ -282,7 +282,7 @@ class StreamPushMultiAdaptArgs(C.Structure):
                 ("adapt_ws", C.c_void_p), ("adapt_ws_bytes", C.c_int64), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
 
 
-GROUP_MAX = 32                                   # slots per clip stream group and items per push (csrc/clip_stream_group.hip: kGroupMax)
+GROUP_MAX = 32                                   # slots per clip stream group and items per push (csrc/stream_group_host.hpp: kGroupMax)
 
 
 class StreamGroupPushArgs(C.Structure):

@@ -355,3 +355,28 @@ def test_refusals_on_the_device_entry_launch_nothing():
         with pytest.raises(ValueError, match="nothing has been pushed"):
             open_group(key).finish(0)
     assert g.frames == [4, 4, 4]
+
+
+# the table region hicom_compressor_stream_group_prepare wrote for the host tests' push_block (three items of 4 / 8 / 4 frames, chunks = 2)
+# at commit 740012d on an MI355X, 256 ints: GroupItem x 3 | {item, first tile, last tile, partial slot} x 6 | window -> item | row -> item
+TABLE_REGION = ([0, 144, 4, 0, 0, 2, 0, 0, 4, 0, 0, 0, 144, 288, 8, 4, 2, 2, 144, 4, 8, 0, 0, 0, 432, 144, 4, 12, 4, 2, 432, 12, 4] + [0] * 31
+                + [0, 0, 4, 0, 0, 4, 9, 1, 1, 0, 9, 2, 1, 9, 18, 3, 2, 0, 4, 4, 2, 4, 9, 5] + [0] * 40
+                + [0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2] + [0] * 48
+                + [0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2] + [0] * 48)
+
+
+def check_table_region(block, workspace, prepare, want):
+    """prepare(block) on a real workspace filled with 0xff writes exactly `want` to its head: the ints behind it keep the fill."""
+    n = workspace(block)
+    ws = torch.full((n,), 255, dtype=torch.uint8, device="cuda")
+    block.ws, block.ws_bytes, block.stream = ws.data_ptr(), n, torch.cuda.current_stream().cuda_stream
+    prepare(block)
+    got = ws[:4 * (len(want) + 64)].view(torch.int32).tolist()
+    assert got[:len(want)] == want, [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
+    assert got[len(want):] == [-1] * 64, "the table region is longer than the parent's"
+
+
+def test_prepare_writes_the_parents_table_region():
+    from test_clip_stream_group_host import push_block
+    assert len(TABLE_REGION) == 256
+    check_table_region(push_block(), nv.compressor_stream_group_workspace, nv.compressor_stream_group_prepare, TABLE_REGION)

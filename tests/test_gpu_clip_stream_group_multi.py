@@ -313,3 +313,21 @@ def test_a_second_push_of_the_same_tuple_allocates_nothing_and_builds_no_plan():
         g.reset(2)
     push(g, key, ((2, 8),))
     assert len(plans) == 2
+
+
+# the table region hicom_compressor_stream_group_multi_prepare wrote for the host tests' push_block (three items of 4 / 8 / 4 frames with
+# 4 / 1 / 2 guides, chunks = 2) at commit 740012d on an MI355X, 256 ints: GmItem x 3 | GmUnit x 8 (item 0 has two passes) | window -> item |
+# row -> item
+TABLE_REGION = ([0, 144, 4, 0, 4, 0, 2, 0, 4, 0, 0, 4, 0, 0, 0, 0, 144, 288, 8, 4, 8, 8, 2, 576, 1, 16, 16, 8, 0, 0, 0, 0, 432, 144, 4, 12, 4, 12, 2, 1152, 2, 24, 24, 4]
+                + [0] * 20
+                + [0, 0, 4, 0, 0, 0, 0, 0, 0, 4, 9, 0, 1, 0, 0, 0, 0, 0, 4, 1, 4, 0, 0, 0, 0, 4, 9, 1, 5, 0, 0, 0, 1, 0, 9, 0, 8, 0, 0, 0, 1, 9, 18, 0, 9, 0, 0, 0,
+                   2, 0, 4, 0, 12, 0, 0, 0, 2, 4, 9, 0, 13] + [0] * 3
+                + [0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2] + [0] * 48
+                + [0] * 16 + [1] * 8 + [2] * 8 + [0] * 32)
+
+
+def test_prepare_writes_the_parents_table_region():
+    from test_clip_stream_group_multi_host import push_block
+    from test_gpu_clip_stream_group import check_table_region
+    assert len(TABLE_REGION) == 256
+    check_table_region(push_block(), nv.compressor_stream_group_multi_workspace, nv.compressor_stream_group_multi_prepare, TABLE_REGION)
