@@ -927,6 +927,12 @@ def compressor_stream_push_multi(args: StreamPushMultiArgs):
     _check(lib().hicom_compressor_stream_push_multi(C.byref(args)), "hicom_compressor_stream_push_multi")
 
 
+def multi_guide_local(key_x: int, ff: int, guide: int, Q: int, T: int, H: int, W: int, E: int, kt: int, ks: int, scale: float, ctx_f16: int, stream: int):
+    """Addresses in, one launch out: the plain local stage of forward_multi_guide alone (hicom_multi_guide_local_fwd), fp16 contexts
+    [Q][windows][E]."""
+    _check(lib().hicom_multi_guide_local_fwd(key_x, ff, guide, Q, T, H, W, E, kt, ks, scale, ctx_f16, stream), "hicom_multi_guide_local_fwd")
+
+
 def multi_guide_local_adapt(key_x: int, ff: int, guide: int, ky, vy, ak: SegAdaptor, av: SegAdaptor, alpha_dt: int, eps: float, Q: int, T: int, H: int,
                             W: int, E: int, kt: int, ks: int, scale: float, ctx_f16: int, stream: int):
     """Addresses in, one launch out: the local stage of forward_prepared alone (hicom_multi_guide_local_adapt_fwd), fp16 contexts

@@ -366,8 +366,13 @@ def forward_bounds(run, fw):
              yhat carries the LayerNorm statistics' error 2 D 2^-23 (|y| + |mu|) rstd (as in the adaptor backward's test), times
              a |gamma| p_i, and the blend of the two accumulators adds 6 roundings on ctx_ab.
       ctx16  the same, + one rounding to fp16 (2^-10 |ref|, 2^-24 in the subnormal range), of the value saturated at +-65504."""
-    c = build(run)
-    d_s = logit_tol(run, c, fw["s_ab"])
+    return forward_bounds_of(run, build(run), fw)
+
+
+def forward_bounds_of(run, c, fw, d_s_more=0.0):
+    """forward_bounds on tensors `c` of the caller's own (tests/multi_window_inputs.py: one guide of a multi-guide run); run: what
+    logit_tol reads (kernel, l2norm).  d_s_more: a further term of the logit bound, [NW, WIN]."""
+    d_s = logit_tol(run, c, fw["s_ab"]) + d_s_more
     rel = weight_rel(fw, d_s, c.WIN)
     tok = fw["tok"]
     if run.kernel == "adapt":
