@@ -137,20 +137,27 @@ class ClipStreamGroup(cs.ClipStreamBase):
         """The plan of one tuple of chunk lengths (PAIRS: of (chunk length, guide count)): the block with everything but the per-push fields,
         the workspace and its static tables."""
         Args, workspace, prepare, _ = self._native()
-        a = Args()
+        args = Args()
+        a = getattr(args, "base", args)              # (the block of the k / v adaptor recipe has the plain block first: clip_stream_group_adapt.py)
         a.B, a.items, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.chunks = self.B, len(items), self.H, self.W, self.E, self.kt, self.ks, self.nh, self.hidden, 0
         a.out_dt = nv.DT_F32 if self.out_dtype == torch.float32 else nv.DT_BF16
         a.nl_group = self.proj._layout((self.max_frames // self.kt, self.gh, self.gw), "video", self.newline is not None, False).nl_group
         if self.PAIRS:
             a.M, a.q[:len(items)], items = self.M, [q for _, q in items], [n for n, _ in items]
         a.tc[:len(items)] = items
-        ws, (a.ws,), keep = self._fill_common(a, max(items), 0, [workspace(a)])
+        more, refresh = self._fill_front(args)
+        ws, (a.ws,), keep = self._fill_common(a, max(items), 0, [workspace(args)])
         a.ws_bytes, a.stream = ws.numel(), stream
-        prepare(a)
-        return cs.StreamPlan(a, ws, keep, self.proj.local_compressor.readout_f16)
+        prepare(args)
+        return cs.StreamPlan(args, ws, keep + more, refresh)
+
+    def _fill_front(self, args):
+        """Hook: what the block has beyond the plain fields, entered in front of the workspace query: (the tensors those fields point at, the
+        plan's refresh).  Here nothing, and the plan follows the readout weights."""
+        return [], self.proj.local_compressor.readout_f16
 
     def _launch(self, plan, ff, fe, slots, t0s, row0s, stream):
-        a = plan.args
+        a = getattr(plan.args, "base", plan.args)
         a.B = self.B                             # of THIS group, as M and pair0: plans are shared by the groups of a module, and the C checks use them
         a.ff, a.fe, a.guide = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr()
         a.q_hi, a.q_lo = self.q_hi.data_ptr(), self.q_lo.data_ptr()
@@ -167,7 +174,7 @@ class ClipStreamGroup(cs.ClipStreamBase):
         if self.PAIRS:
             a.M, a.pair0[:len(slots)] = self.M, [self.pair0[s] for s in slots]
         a.stream = stream
-        self._native()[3](a)
+        self._native()[3](plan.args)
 
     # -- the public surface ---------------------------------------------------------------------------------------------------------------
     def _slot(self, what, slot):

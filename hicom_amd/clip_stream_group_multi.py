@@ -76,6 +76,7 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
     [M, cap_rows + 32, hidden], pair-major; `guides` the [M, E] block; `pair0[s]` the first pair of slot s."""
     NAME, WHAT, STORE = "ClipStreamGroupMulti", "open_stream_group_multi", STORE_GROUP_MULTI
     PAIRS, STRIDE, ROWS = True, "pair_stride", "pair_rows"
+    SLOT_GUIDES = _SlotGuides                    # what reset(slot, guides) tells stream_scope: the entry's name and the class's recipe
 
     def __init__(self, proj, guide_embeds, guide_counts, H, W, max_frames, image_newline=None):
         # the open sequence is ClipStreamBase's (scope, allocate, prepare); _scope takes the counts from here and sets B (the slots, what
@@ -168,7 +169,7 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
         what = f"{self.NAME}.reset"
         slot = self._slot(what, slot)
         if guides is not None:
-            cs.stream_scope(self.proj, guides, self.H, self.W, self.max_frames, self.newline, _SlotGuides)
+            cs.stream_scope(self.proj, guides, self.H, self.W, self.max_frames, self.newline, self.SLOT_GUIDES)
             if guides.shape[0] != self.guide_counts[slot]:
                 raise ValueError(f"{what}: {guides.shape[0]} guides for slot {slot}, which was opened with Q={self.guide_counts[slot]} (the buffers are "
                                  "sized by the counts: open another group)")

@@ -131,7 +131,7 @@ using namespace hicom_host;
 namespace {
 
 // one guide per slot: an item is one folded-row group of its slot, one pass, one work unit per token chunk
-struct Single {
+struct Single : GroupPlainFront<Single> {
     typedef hicom_stream_group_push_args Args;
     typedef GroupItem Item;
     typedef int4 Unit;

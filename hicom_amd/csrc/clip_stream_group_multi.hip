@@ -21,7 +21,9 @@
 // the 32 copies of its global row behind the slot's local rows; rows of other pairs are never read or written.
 //
 // This file has the kernels, their table entries, the description of the flavour (Multi) and the finish placement's entry; the host side of
-// the other entry points is stream_group_host.hpp, shared with clip_stream_group.hip.
+// the other entry points is stream_group_host.hpp, shared with clip_stream_group.hip.  At the foot: the same group on the k / v adaptor
+// recipe -- the flavour Adapt, which is Multi with a front of its own (the adaptor MLPs over the stacked tokens and
+// gm_local_adapt_kernel in the place of launch 1), its three entry points and the stand-alone entry of its local stage.
 #include "merge_fold.hpp"
 #include "multi_window.hpp"
 #include "stream_group_host.hpp"
@@ -70,6 +72,40 @@ __global__ __launch_bounds__(256) void gm_local_kernel(const uint16_t* key, cons
     const long first = (long)it.tok0 * D;
     multi_window_guides_ctx16<NV>(key + first, value + first, guide, push.pair0[item], it.Q, g, lane, scale,
                                   ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)it.wins * D);
+}
+
+// The same wave -> window map for the k / v adaptor recipe: launch 3 of the adaptor flavour's push, behind the adaptor MLPs
+// over the tick's STACKED tokens.  ad: gamma / beta / alpha / eps of the call and the fp16 planes y = MLP(x) of the whole stack (either may
+// be NULL, not both), indexed like the tokens: the by-value copy has them advanced to the item's first token, as clips_local_adapt_kernel
+// (ragged_multi_guide.hip) replaces them per item.  Contexts pair-major, exactly where gm_local_kernel puts them.  items NULL: the
+// stand-alone entry's uniform form -- every item has u_T frames and u_Q guides, tokens, planes and context rows packed item after item.
+// Every branch on `items` and every lookup is wave-uniform (win is); nothing is stored through what the lookups return.
+template <int NV>
+__global__ __launch_bounds__(256) void gm_local_adapt_kernel(const uint16_t* key, const uint16_t* value, const uint16_t* guide, SegAdaptParams ad,
+                                                             const GmItem* items, const int* win_item, hicom_axis ay, hicom_axis ax, int kt, int nwin,
+                                                             int u_T, int u_Q, float scale, _Float16* ctx16, GmPush push) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    int item, T, Q, win0, wins;
+    long tok0, ctx_row0;
+    if (items) {
+        item = win_item[win];
+        const GmItem it = items[item];
+        T = it.T; Q = it.Q; win0 = it.win0; wins = it.wins; tok0 = it.tok0; ctx_row0 = it.ctx_row0;
+    } else {
+        T = u_T; Q = u_Q; wins = (u_T / kt) * ay.nwin * ax.nwin;
+        item = win / wins;
+        win0 = item * wins; tok0 = (long)item * u_T * ay.n * ax.n; ctx_row0 = (long)item * u_Q * wins;
+    }
+    const hicom_axis at{T, kt, T / kt, T / kt};
+    const WindowGeom g(at, ay, ax, win - win0);
+    const long first = tok0 * D;
+    if (ad.ky) ad.ky += first;
+    if (ad.vy) ad.vy += first;
+    multi_window_guides_adapt_ctx16<NV, kAdaptGuideGroup>(key + first, value + first, ad, guide, push.pair0[item], Q, g, lane, scale,
+                                                          ctx16 + (ctx_row0 + (win - win0)) * D, (long)wins * D);
 }
 
 // ---- 2: segmented many-row stream: the item's frames count from its absolute offset, its query rows are its slot's pairs' ----
@@ -192,15 +228,21 @@ int gm_check_pairs(const char* who, const int32_t* pair0, const int32_t* q, int 
     return HICOM_OK;
 }
 
-// Q_i guides per item: nh Q_i folded rows in passes of 32 (two row groups per stream workgroup), one work unit per (pass, token chunk)
-struct Multi {
+// Q_i guides per item: nh Q_i folded rows in passes of 32 (two row groups per stream workgroup), one work unit per (pass, token chunk).
+// Names: the message prefixes (the adaptor flavour at the foot of this file is the same description under its own)
+struct MultiNames {
+    static constexpr const char *kWho = "compressor_stream_group_multi", *kFoldWho = "stream_group_multi_merge_fold";
+};
+
+template <class Names>
+struct MultiOf : GroupPlainFront<MultiOf<Names>> {
     typedef hicom_stream_group_multi_push_args Args;
     typedef GmItem Item;
     typedef GmUnit Unit;
     typedef GmStreamParams StreamParams;
     typedef GmMergeParams MergeParams;
     typedef GmPlaceParams PlaceParams;
-    static constexpr const char *kWho = "compressor_stream_group_multi", *kFoldWho = "stream_group_multi_merge_fold", *kUnit = "pair";
+    static constexpr const char *kWho = Names::kWho, *kFoldWho = Names::kFoldWho, *kUnit = "pair";
     static constexpr int kRowGroups = 2;
     static constexpr auto kStride = &Args::pair_stride, kRows = &Args::pair_rows;
     static constexpr auto kPlaceStride = &PlaceParams::pair_stride;
@@ -224,7 +266,7 @@ struct Multi {
     static int check_totals(const Args* a, int wps) {
         long products = 0, ctx_rows = 0;
         for (int i = 0; i < a->items; ++i) {
-            products += group_item_passes<Multi>(a, i) * 32 * (((long)a->tc[i] * a->H * a->W + 15) / 16);
+            products += group_item_passes<MultiOf>(a, i) * 32 * (((long)a->tc[i] * a->H * a->W + 15) / 16);
             ctx_rows += a->q[i] * group_item_win(a, i, wps);
         }
         HICOM_REQUIRE(products < (1L << 27), HICOM_EUNSUP, "%s: too many token x guide products in one push", kWho);
@@ -254,6 +296,8 @@ struct Multi {
     }
     static int check_fold_units(const char* who, const int32_t* pair0, int Q, int items, int M) { return gm_check_pairs(who, pair0, nullptr, Q, items, M); }
 };
+
+typedef MultiOf<MultiNames> Multi;
 
 }  // namespace
 
@@ -305,4 +349,107 @@ extern "C" int hicom_stream_group_place_global_fwd(const float* tok, const void*
     p.tail = tail; p.ldo = ldo; p.pair_stride = pair_stride;
     HICOM_LAUNCH(gm_place_global_kernel, dim3((unsigned)(tail + n_rows), (unsigned)max_Q, (unsigned)B), dim3(128), 0, (hipStream_t)stream, p);
     return seg_check_launch(who, "placement");
+}
+
+// ---- the k / v adaptor recipe ----------------------------------------------------------------------------------------------
+// The adaptors sit on the local stage only and the adaptor MLPs know neither the guide nor the slot, so a push differs in its front alone:
+// hicom_clip_adapt_prepare_fwd over the tick's sum N_i STACKED tokens (layer 1 and layer 2, one GEMM pair per layer with both adaptors)
+// into fp16 planes ky / vy [sum N_i, E] that live for that push, then gm_local_adapt_kernel; launches 2-6 of the plain push follow
+// unchanged: eight launches.  The planes and the hidden planes of layer 1 are regions of the plan's ONE workspace, behind `loc`.
+namespace {
+
+struct AdaptNames {
+    static constexpr const char *kWho = "compressor_stream_group_adapt", *kFoldWho = "stream_group_multi_merge_fold";
+};
+
+struct Adapt : MultiOf<AdaptNames> {
+    const hicom_stream_group_adapt_push_args* x;
+    explicit Adapt(const hicom_stream_group_adapt_push_args* x_) : x(x_) {}
+    SegAdapt adaptors() const { return SegAdapt{&x->ak, &x->av, x->alpha_dt, x->eps}; }
+    enum { kKy, kVy, kHid };                 // l.front[]: the two planes, the hidden planes of layer 1 (hicom_clip_adapt_prepare_workspace_bytes)
+
+    int check_shape(const Args* a, long tokens) const {
+        const SegAdapt ad = adaptors();
+        return seg_adapt_check(kWho, &ad, tokens, a->E);
+    }
+    template <class Take>
+    void regions(const Args* a, GroupLayout& l, Take&& take) const {
+        const SegAdapt ad = adaptors();
+        const long plane = l.tokens * a->E * 2;
+        const int64_t hid = hicom_clip_adapt_prepare_workspace_bytes(l.tokens, a->E, &x->ak, &x->av);
+        l.front[kKy] = ad.k() ? take(plane) : 0;
+        l.front[kVy] = ad.v() ? take(plane) : 0;
+        l.front[kHid] = take(hid > 0 ? hid : 0);
+    }
+    const void* key_x(const Args* a) const { return a->fe ? a->fe : a->ff; }      // (no frames_embed: the k adaptor reads frames_feature, as the keys do)
+    int check_push(const Args* a, const GroupLayout& l) const {
+        const SegAdapt ad = adaptors();
+        const int st = seg_adapt_check_weights(kWho, &ad);
+        if (st != HICOM_OK) return st;
+        char* ws = (char*)a->ws;
+        return clip_adapt_prepare_args_check(key_x(a), a->ff, l.tokens, a->E, &x->ak, &x->av, ad.k() ? ws + l.front[kKy] : nullptr,
+                                             ad.v() ? ws + l.front[kVy] : nullptr, ws + l.front[kHid], l.total - l.front[kHid], nullptr);
+    }
+    int front(const Args* a, const GroupLayout& l, const uint16_t* kx, const GroupPush& push) const {
+        const SegAdapt ad = adaptors();
+        char* ws = (char*)a->ws;
+        // 1-2: y = MLP(x) of the adapted streams over the whole stack
+        const int st = hicom_clip_adapt_prepare_fwd(kx, a->ff, l.tokens, a->E, &x->ak, &x->av, ad.k() ? ws + l.front[kKy] : nullptr,
+                                                    ad.v() ? ws + l.front[kVy] : nullptr, ws + l.front[kHid], l.total - l.front[kHid], a->stream);
+        if (st != HICOM_OK) return st;
+        // 3: local stage on the planes
+        SegAdaptLayout planes;
+        planes.ky = l.front[kKy]; planes.vy = l.front[kVy];
+        const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+        HICOM_LAUNCH(gm_local_adapt_kernel<3>, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, kx, (const uint16_t*)a->ff,
+                     (const uint16_t*)a->guide, seg_adapt_params(ad, ws, planes), (const GmItem*)(ws + l.items), (const int*)(ws + l.win_item), ay, ax,
+                     (int)a->kt, (int)l.windows, 0, 0, a->l_scale, (_Float16*)(ws + l.ctx16), push);
+        return seg_check_launch(kWho, "local stage");
+    }
+};
+
+}  // namespace
+
+extern "C" int64_t hicom_compressor_stream_group_adapt_workspace_bytes(const hicom_stream_group_adapt_push_args* x) {
+    HICOM_REQUIRE(x, HICOM_EINVAL, "%s: NULL arguments", Adapt::kWho);
+    return group_workspace_bytes<Adapt>(&x->base, Adapt(x));
+}
+extern "C" int hicom_compressor_stream_group_adapt_prepare(const hicom_stream_group_adapt_push_args* x) {
+    HICOM_REQUIRE(x, HICOM_EINVAL, "%s: NULL arguments", Adapt::kWho);
+    return group_prepare<Adapt>(&x->base, Adapt(x));
+}
+extern "C" int hicom_compressor_stream_group_adapt_push(const hicom_stream_group_adapt_push_args* x) {
+    HICOM_REQUIRE(x, HICOM_EINVAL, "%s: NULL arguments", Adapt::kWho);
+    return group_push<Adapt>(&x->base, Adapt(x));
+}
+
+// Launch 3 of that push alone: `items` chunks of Tc frames with Q guides each, packed one behind the other -- item i's tokens (and plane
+// rows) at i Tc H W, its contexts at ctx_f16 + i Q windows E, pair-major within the item -- with the guide rows pair0[i] .. pair0[i] + Q of
+// guide [M][E].  ky / vy: the planes of the whole stack, one of them may be NULL.
+extern "C" int hicom_stream_group_local_adapt_fwd(const void* key, const void* value, const void* guide, const void* ky, const void* vy,
+                                                  const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int32_t alpha_dt, float eps, int32_t items,
+                                                  int32_t Q, int32_t Tc, int32_t H, int32_t W, int32_t E, int32_t kt, int32_t ks, float scale,
+                                                  const int32_t* pair0, int32_t M, void* ctx_f16, void* stream) {
+    constexpr const char* who = "stream_group_local_adapt";
+    HICOM_REQUIRE(pair0, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE(items >= 1 && items <= kGmMax && M >= 1 && M <= kGmMax * kGmMax, HICOM_EINVAL, "%s: bad shape (items=%d M=%d)", who, items, M);
+    // the checks of the one-clip launch on an item's shape: pointers, Q, the window partition, E, alignment, the planes and their adaptors
+    int st = multi_guide_local_adapt_args_check(key, value, guide, ky, vy, ak, av, alpha_dt, Q, Tc, H, W, E, kt, ks, ctx_f16);
+    if (st != HICOM_OK) return st;
+    const long N = (long)Tc * H * W, wins = (long)(Tc / kt) * (H / ks) * (W / ks);
+    // (item offsets are ints on the device, as in a push)
+    HICOM_REQUIRE(N * items < (1L << 27) && wins * Q * items < (1L << 20), HICOM_EUNSUP, "%s: too many tokens in one call", who);
+    st = gm_check_pairs(who, pair0, nullptr, Q, items, M);
+    if (st != HICOM_OK) return st;
+    SegAdaptParams p;
+    p.ky = (const _Float16*)ky; p.kgamma = (const uint16_t*)ak->gamma; p.kbeta = (const uint16_t*)ak->beta; p.kalpha = ak->alpha;
+    p.vy = (const _Float16*)vy; p.vgamma = (const uint16_t*)av->gamma; p.vbeta = (const uint16_t*)av->beta; p.valpha = av->alpha;
+    p.alpha_f32 = alpha_dt == HICOM_DT_F32;
+    p.eps = eps;
+    const hicom_axis ay{H, ks, H / ks, H / ks}, ax{W, ks, W / ks, W / ks};
+    const long nwin = wins * items;
+    HICOM_LAUNCH(gm_local_adapt_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)key, (const uint16_t*)value,
+                 (const uint16_t*)guide, p, (const GmItem*)nullptr, (const int*)nullptr, ay, ax, (int)kt, (int)nwin, (int)Tc, (int)Q, scale, (_Float16*)ctx_f16,
+                 group_push_values(pair0, pair0, nullptr, items));       // (this launch reads pair0 alone: the frame offsets are not its business)
+    return seg_check_launch(who, "local stage");
 }

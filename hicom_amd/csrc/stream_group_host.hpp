@@ -1,8 +1,8 @@
 // Host side of the two clip stream group pushes, written once: the shape check, the workspace layout, the per-push
 // values, the slot check, workspace_bytes, prepare's item walk and upload, every check of a push in front of the first launch, the
-// six-launch sequence with its parameter fill, and the stand-alone merge + fold entry.  clip_stream_group.hip (one guide per slot) and
-// clip_stream_group_multi.hip (several) keep their kernels, their table structs and a flavour description F; the functions here are
-// templates over F and read `a->field` directly (the two argument blocks name every common field alike).  F says what truly differs:
+// six-launch sequence with its parameter fill (launch 1 behind a flavour hook), and the stand-alone merge + fold entry.
+// clip_stream_group.hip (one guide per slot) and clip_stream_group_multi.hip (several) keep their kernels, their table structs and a
+// flavour description F; the functions here are templates over F and read `a->field` directly (the two argument blocks name every common field alike).  F says what truly differs:
 //   Args, Item, Unit, StreamParams, MergeParams, PlaceParams; the kernels local, stream, merge, place
 //   kWho, kFoldWho: the message prefixes; kUnit: what owns one state and one part of the output ("slot" | "pair")
 //   kRowGroups: a stream workgroup has 256 kRowGroups threads and 16 kRowGroups folded rows, one pass of an item's row space
@@ -10,6 +10,12 @@
 //   guides(a, i); unit0(a): the per-item array of first units (slot | first pair); write(item, units, walk): an item's table entries
 //   check_group, check_item, check_totals, check_units, check_fold_shape, check_fold_units: the flavour's own requirements, each at its
 //   place in the order of the checks; uniform_guides(p, Q): the guide count of the stand-alone entry's items
+// A flavour is also an OBJECT (`f`, default-constructed for the two plain flavours), for what a push may put in FRONT of launch 2:
+//   f.regions(a, l, take): further workspace regions behind `loc` (l.front[]), so that every plain offset and total stays what it is
+//   f.check_shape(a, tokens), f.check_push(a, l): its requirements on the tuple (behind check_totals) and on a push (behind the plain
+//   checks, in front of the first launch); f.front(a, l, key_x, push): the launches that leave the fp16 contexts in ws + l.ctx16
+// GroupPlainFront<F> is the trivial form -- no region, no requirement, launch 1 = F::local -- which the two plain flavours inherit; the
+// k / v adaptor flavour (clip_stream_group_multi.hip) is Multi with the four of its own.
 #pragma once
 #include <vector>
 
@@ -35,7 +41,8 @@ using namespace hicom;
 struct GroupLayout {
     long items, units, win_item, row_item, table_bytes;     // the table region
     long scores, part_m, part_l, part_acc, ctx16, hid16, loc, total;
-    long windows, ctx_rows, rows, slots, nunits, work_sum, score16;
+    long front[3];                                          // the regions of the flavour's front step, behind loc (0: absent)
+    long windows, ctx_rows, rows, slots, nunits, work_sum, score16, tokens;
     int max_T, max_Q, wps;
 };
 
@@ -53,8 +60,28 @@ template <class F>
 inline long group_item_passes(const typename F::Args* a, int i) { return ((long)a->nh * F::guides(a, i) + 16 * F::kRowGroups - 1) / (16 * F::kRowGroups); }
 
 // everything that the tuple of the items and the geometry decide: the checks of workspace_bytes, prepare and push
+// The trivial form of a flavour's front (header comment): launch 1 is F::local over the stack's windows.
 template <class F>
-int group_check_shape(const typename F::Args* a) {
+struct GroupPlainFront {
+    template <class A, class Take>
+    void regions(const A*, GroupLayout&, Take&&) const {}
+    template <class A>
+    int check_shape(const A*, long) const { return HICOM_OK; }
+    template <class A>
+    int check_push(const A*, const GroupLayout&) const { return HICOM_OK; }
+    template <class A>
+    int front(const A* a, const GroupLayout& l, const uint16_t* key_x, const GroupPush& push) const {
+        const char* ws = (const char*)a->ws;
+        const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+        HICOM_LAUNCH(F::local, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, key_x, (const uint16_t*)a->ff,
+                     (const uint16_t*)a->guide, (const typename F::Item*)(ws + l.items), (const int*)(ws + l.win_item), ay, ax, (int)a->kt, (int)l.windows,
+                     a->l_scale, (_Float16*)(ws + l.ctx16), push);
+        return seg_check_launch(F::kWho, "local stage");
+    }
+};
+
+template <class F>
+int group_check_shape(const typename F::Args* a, const F& f = F()) {
     constexpr const char* who = F::kWho;
     HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", who);
     HICOM_REQUIRE(a->B >= 1 && a->B <= kGroupMax, HICOM_EUNSUP, "%s: B=%d slots (1 <= B <= %d per group)", who, a->B, kGroupMax);
@@ -88,18 +115,21 @@ int group_check_shape(const typename F::Args* a) {
     HICOM_REQUIRE(tokens + 16L * a->items < (1L << 27), HICOM_EUNSUP, "%s: too many tokens in one push", who);
     st = F::check_totals(a, wps);
     if (st != HICOM_OK) return st;
+    st = f.check_shape(a, tokens);
+    if (st != HICOM_OK) return st;
     return seg_check_merge_lds(who, a, max_T);
 }
 
 // The partial-state slots of an item are ordered [pass][row group][chunk]; its logits are [16 kRowGroups passes][ceil16(N)].
 template <class F>
-GroupLayout group_layout(const typename F::Args* a) {
+GroupLayout group_layout(const typename F::Args* a, const F& f = F()) {
     GroupLayout l{};
     const long HW = (long)a->H * a->W, E = a->E;
     l.wps = (a->H / a->ks) * (a->W / a->ks);
     for (int i = 0; i < a->items; ++i) {
         const long N = a->tc[i] * HW, w = group_item_win(a, i, l.wps), ntiles = (N + 15) / 16, Q = F::guides(a, i);
         l.windows += w;
+        l.tokens += N;
         l.ctx_rows += Q * w;
         l.rows += Q * (w + group_item_nl(a, i, l.wps));
         l.score16 += group_item_passes<F>(a, i) * 16 * F::kRowGroups * ntiles;
@@ -125,6 +155,7 @@ GroupLayout group_layout(const typename F::Args* a) {
     l.ctx16 = take(l.ctx_rows * E * 2);
     l.hid16 = take(l.ctx_rows * (long)a->hidden * 2);
     l.loc = take(l.ctx_rows * (long)a->hidden * odt);
+    f.regions(a, l, take);
     l.total = off;
     return l;
 }
@@ -151,17 +182,17 @@ inline int group_check_slots(const char* who, const int32_t* slot, int items, in
 }
 
 template <class F>
-int64_t group_workspace_bytes(const typename F::Args* a) {
-    const int st = group_check_shape<F>(a);
+int64_t group_workspace_bytes(const typename F::Args* a, const F& f = F()) {
+    const int st = group_check_shape<F>(a, f);
     if (st != HICOM_OK) return st;
-    return group_layout<F>(a).total;
+    return group_layout<F>(a, f).total;
 }
 
 template <class F>
-int group_prepare(const typename F::Args* a) {
-    int st = group_check_shape<F>(a);
+int group_prepare(const typename F::Args* a, const F& f = F()) {
+    int st = group_check_shape<F>(a, f);
     if (st != HICOM_OK) return st;
-    const GroupLayout l = group_layout<F>(a);
+    const GroupLayout l = group_layout<F>(a, f);
     st = seg_check_ws(F::kWho, a, l.total);
     if (st != HICOM_OK) return st;
     std::vector<int> tab((size_t)(l.table_bytes / 4), 0);
@@ -212,11 +243,11 @@ int group_merge_launch(const char* who, const typename F::MergeParams& p, int ma
 }
 
 template <class F>
-int group_push(const typename F::Args* a) {
+int group_push(const typename F::Args* a, const F& f = F()) {
     constexpr const char* who = F::kWho;
-    int st = group_check_shape<F>(a);
+    int st = group_check_shape<F>(a, f);
     if (st != HICOM_OK) return st;
-    const GroupLayout l = group_layout<F>(a);
+    const GroupLayout l = group_layout<F>(a, f);
     st = seg_check_ws(who, a, l.total);
     if (st != HICOM_OK) return st;
     const long unit_stride = a->*F::kStride, unit_rows = a->*F::kRows;
@@ -245,6 +276,8 @@ int group_push(const typename F::Args* a) {
                       i, a->row0[i], (long)a->row0[i] + rows, F::kUnit, unit_rows);
     }
     HICOM_REQUIRE(l.windows <= INT32_MAX && l.rows <= INT32_MAX && l.nunits <= INT32_MAX, HICOM_EUNSUP, "%s: too many windows in one push", who);
+    st = f.check_push(a, l);
+    if (st != HICOM_OK) return st;
 
     char* ws = (char*)a->ws;
     hipStream_t s = (hipStream_t)a->stream;
@@ -252,14 +285,9 @@ int group_push(const typename F::Args* a) {
     const typename F::Item* items = (const typename F::Item*)(ws + l.items);
     const uint16_t* key_x = (const uint16_t*)(a->fe ? a->fe : a->ff);      // (no frames_embed: the keys are frames_feature)
 
-    // 1: local stage
-    {
-        const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
-        HICOM_LAUNCH(F::local, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, s, key_x, (const uint16_t*)a->ff, (const uint16_t*)a->guide, items,
-                     (const int*)(ws + l.win_item), ay, ax, (int)a->kt, (int)l.windows, a->l_scale, (_Float16*)(ws + l.ctx16), push);
-        st = seg_check_launch(who, "local stage");
-        if (st != HICOM_OK) return st;
-    }
+    // 1: local stage (the flavour's front: F::local, or what a flavour runs in its place)
+    st = f.front(a, l, key_x, push);
+    if (st != HICOM_OK) return st;
     // 2: segmented global stream
     {
         constexpr int smem = hicom::seg_stream_smem(F::kRowGroups);

@@ -56,6 +56,8 @@ EXPORTS = (
     "hicom_stream_group_merge_fold_fwd",
     "hicom_compressor_stream_group_multi_workspace_bytes", "hicom_compressor_stream_group_multi_prepare", "hicom_compressor_stream_group_multi_push",
     "hicom_stream_group_multi_merge_fold_fwd", "hicom_stream_group_place_global_fwd",
+    "hicom_compressor_stream_group_adapt_workspace_bytes", "hicom_compressor_stream_group_adapt_prepare", "hicom_compressor_stream_group_adapt_push",
+    "hicom_stream_group_local_adapt_fwd",
 )
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
@@ -312,6 +314,12 @@ class StreamGroupMultiPushArgs(C.Structure):
                 ("pair0", C.c_int32 * GROUP_MAX), ("stream", C.c_void_p)]
 
 
+class StreamGroupAdaptPushArgs(C.Structure):
+    """hicom_stream_group_adapt_push_args (include/hicom_hip.h): the group-multi push block first, then the two adaptors, the alpha dtype and
+    the LayerNorm eps.  The planes and the adaptor MLPs' hidden planes are regions of base.ws."""
+    _fields_ = [("base", StreamGroupMultiPushArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -456,6 +464,11 @@ def lib() -> C.CDLL:
     L.hicom_stream_group_multi_merge_fold_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32),
                                                           C.POINTER(i32), i32, vp, vp, vp]
     L.hicom_stream_group_place_global_fwd.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.c_uint32, i32, i32, i32, vp, i32, i64, i64, i64, vp]
+    L.hicom_compressor_stream_group_adapt_workspace_bytes.argtypes = [C.POINTER(StreamGroupAdaptPushArgs)]
+    L.hicom_compressor_stream_group_adapt_prepare.argtypes = [C.POINTER(StreamGroupAdaptPushArgs)]
+    L.hicom_compressor_stream_group_adapt_push.argtypes = [C.POINTER(StreamGroupAdaptPushArgs)]
+    L.hicom_stream_group_local_adapt_fwd.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32, i32, i32,
+                                                     i32, i32, f32, C.POINTER(i32), i32, vp, vp]
     L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
     L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
@@ -475,6 +488,7 @@ def lib() -> C.CDLL:
     L.hicom_compressor_clips_multiguide_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_stream_group_workspace_bytes.restype = C.c_int64
     L.hicom_compressor_stream_group_multi_workspace_bytes.restype = C.c_int64
+    L.hicom_compressor_stream_group_adapt_workspace_bytes.restype = C.c_int64
     _LIB = L
     return L
 
@@ -1011,6 +1025,33 @@ def stream_group_place_global(tok, newline, guide_counts, row0s, named, tail_new
     _check(lib().hicom_stream_group_place_global_fwd(_ptr(tok), _ptr(newline) if tail_newline else None, B, ia(*guide_counts), ia(*row0s), mask, tail_newline,
                                                      n_rows, out.shape[-1], _ptr(out), _dt(out), out.stride(1), out.stride(0), out.shape[1], _stream()),
            "hicom_stream_group_place_global_fwd")
+
+
+def compressor_stream_group_adapt_workspace(args: StreamGroupAdaptPushArgs) -> int:
+    n = lib().hicom_compressor_stream_group_adapt_workspace_bytes(C.byref(args))
+    if n < 0:
+        _check(int(n), "hicom_compressor_stream_group_adapt_workspace_bytes")
+    return int(n)
+
+
+def compressor_stream_group_adapt_prepare(args: StreamGroupAdaptPushArgs):
+    _check(lib().hicom_compressor_stream_group_adapt_prepare(C.byref(args)), "hicom_compressor_stream_group_adapt_prepare")
+
+
+def compressor_stream_group_adapt_push(args: StreamGroupAdaptPushArgs):
+    _check(lib().hicom_compressor_stream_group_adapt_push(C.byref(args)), "hicom_compressor_stream_group_adapt_push")
+
+
+def stream_group_local_adapt(key_x, ff, guide, ky, vy, ak: SegAdaptor, av: SegAdaptor, alpha_dt: int, eps: float, items: int, Q: int, Tc: int, kt: int,
+                             ks: int, scale: float, pair0s, ctx_f16):
+    """The adaptor local stage of a group push alone (hicom_stream_group_local_adapt_fwd): `items` chunks of Tc frames with Q guides each,
+    packed one behind the other in key_x / ff bf16 [items Tc, H, W, E] and the fp16 planes ky / vy [items Tc H W, E] (None: that stream is
+    not adapted); guide bf16 [M, E], item i takes the rows pair0s[i] .. + Q; fp16 contexts ctx_f16 [>= items Q windows, E]."""
+    _, H, W, E = ff.shape
+    ia = (C.c_int32 * items)
+    _check(lib().hicom_stream_group_local_adapt_fwd(_ptr(key_x), _ptr(ff), _ptr(guide), _ptr(ky), _ptr(vy), C.byref(ak), C.byref(av), alpha_dt, eps, items, Q, Tc,
+                                                    H, W, E, kt, ks, scale, ia(*pair0s), guide.shape[0], _ptr(ctx_f16), _stream()),
+           "hicom_stream_group_local_adapt_fwd")
 
 
 def compressor_fwd2(first: CompressorArgs, second: CompressorArgs):

@@ -1283,6 +1283,31 @@ class HIComProjector(nn.Module):
         from . import clip_stream_group_multi
         return clip_stream_group_multi.ClipStreamGroupMulti(self, guide_embeds, guide_counts, H, W, max_frames, image_newline)
 
+    def open_stream_group_adapt(self, guide_embeds, guide_counts, H, W, max_frames, image_newline=None):
+        """open_stream_group_multi for the k / v adaptor recipe (`local43_adaptkv_global32`: adapt_k and / or adapt_v on the local
+        compressor): returns a ClipStreamGroupAdapt (hicom_amd/clip_stream_group_adapt.py) with the surface of
+        ClipStreamGroupMulti --
+            g = proj.open_stream_group_adapt(guide_embeds, guide_counts, H, W, max_frames, image_newline)
+                                                          # guide_counts: the B ints Q_s ((1,) * B: one guide per slot); guide_embeds bf16 [sum Q_s, E]
+            views = g.push(frames_feature, frames_embed, split_sizes, slots=None)        # views[i]: [Q_slot_i, chunk rows, hidden]
+            out = g.finish(slot);  outs = g.finish_many(slots=None);  g.reset(slot, guides=None)
+            g.frames[slot], g.rows(slot), g.guide_counts
+        The adaptor MLPs are per token and know neither the guide nor the slot: a push runs both layers of each over the tick's STACKED
+        tokens of all items once, one GEMM pair per layer, into fp16 planes that the plan owns and that live for that push, then the adaptor
+        local stage over the stack's windows (the guides of the item's slot in groups of 4) and launches 2-6 of open_stream_group_multi's
+        push: one host call (hicom_compressor_stream_group_adapt_push), eight launches whatever B, the Q_s and the chunk lengths are.  The
+        global stage of the recipe is the plain one, so the carried states, finish, finish_many and reset are ClipStreamGroupMulti's.
+        Without frames_embed the k adaptor reads frames_feature, as the keys do.  The plan's workspace grows by 4 x 2304 bytes per token of
+        a tick with both adaptors.
+        A plain-recipe module gets open_stream_group_multi's object, so one entry serves both released recipes (as open_stream_adapt does).
+        The scope of open_stream_group_multi with the adaptor recipe in the place of the plain one, adaptor widths % 64 == 0 and
+        (sum Tc_i) H W E < 2^32 per push; everything else raises NotImplementedError / ValueError in front of the first launch.  Inference
+        only.  Which path when: DESIGN.md §3.17 (tools/clip_stream_group_adapt_bench.py)."""
+        from . import clip_stream_group_adapt
+        if clip_stream_group_adapt.seg.seg_recipe(self) == "plain":
+            return self.open_stream_group_multi(guide_embeds, guide_counts, H, W, max_frames, image_newline)
+        return clip_stream_group_adapt.ClipStreamGroupAdapt(self, guide_embeds, guide_counts, H, W, max_frames, image_newline)
+
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
                                    chunks=None):
         """B items of UNEQUAL length and mixed modality, item i with its own Q_i instructions, in one native call -- a Video-MME style

@@ -1474,6 +1474,40 @@ int hicom_stream_group_place_global_fwd(const float* tok, const void* newline, i
                                         uint32_t named, int32_t tail, int32_t n_rows, int32_t hidden, void* out, int32_t out_dt, int64_t ldo,
                                         int64_t pair_stride, int64_t pair_rows, void* stream);
 
+/* ---- clip stream group on the k / v adaptor recipe -------------------------------------------------------------------
+ * The group above for a module with adapt_k and / or adapt_v on the local stage.  The adaptor MLPs know neither the guide nor the slot,
+ * so one tick's tokens of all items go through them ONCE: a push is eight launches whatever items, q and tc are --
+ * hicom_clip_adapt_prepare_fwd over the sum N_i STACKED tokens (two launches: layer 1 and layer 2, a GEMM pair each with both adaptors)
+ * into fp16 planes ky / vy [sum N_i, E], the adaptor local stage over the stack's windows (item i reads its tokens and its plane rows at
+ * its first token, the guides of its slot in groups of 4), then launches 2-6 of hicom_compressor_stream_group_multi_push unchanged.  The
+ * k adaptor reads fe (ff when fe is NULL), the v adaptor ff.
+ *   base         : the plain block, every field as there; its ws also holds the two planes and the hidden planes of layer 1
+ *                  (hicom_clip_adapt_prepare_workspace_bytes(sum N_i, E, ak, av)) BEHIND the plain regions, whose offsets do not move:
+ *                  4 x 2 E bytes per token of a push with both adaptors
+ *   ak, av       : w0 == NULL: that stream is not adapted (at least one is, HICOM_EINVAL); every field of an adapted stream is read
+ *   alpha_dt, eps: as in hicom_compressor_multiguide_adapt_args
+ * ..._workspace_bytes / ..._prepare / ..._push as for the plain group, with (sum N_i) E < 2^32 (the dense GEMM's operand limit over the
+ * stack, HICOM_EUNSUP) and the checks of hicom_clip_adapt_prepare_fwd, all in front of the first launch. */
+typedef struct hicom_stream_group_adapt_push_args {
+    hicom_stream_group_multi_push_args base;
+    hicom_seg_adaptor ak, av;
+    int32_t alpha_dt;
+    float eps;
+} hicom_stream_group_adapt_push_args;
+int64_t hicom_compressor_stream_group_adapt_workspace_bytes(const hicom_stream_group_adapt_push_args* args);
+int hicom_compressor_stream_group_adapt_prepare(const hicom_stream_group_adapt_push_args* args);
+int hicom_compressor_stream_group_adapt_push(const hicom_stream_group_adapt_push_args* args);
+
+/* The adaptor local stage of that push alone: `items` chunks of Tc frames with Q guides each, packed one behind the other.  key / value bf16
+ * [items Tc, H, W, E]; ky / vy fp16 [items Tc H W, E], the planes of the whole stack (one of them may be NULL: that stream is not adapted);
+ * guide bf16 [M][E], item i takes the rows pair0[i] .. pair0[i] + Q (pair0: a HOST array; the ranges lie inside the M pairs and do not
+ * meet); fp16 contexts ctx_f16 [items][Q][windows of a chunk][E].  Per item the arithmetic, shapes, limits and checks of
+ * hicom_multi_guide_local_adapt_fwd on that chunk with its own rows of the planes. */
+int hicom_stream_group_local_adapt_fwd(const void* key, const void* value, const void* guide, const void* ky, const void* vy,
+                                       const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int32_t alpha_dt, float eps, int32_t items,
+                                       int32_t Q, int32_t Tc, int32_t H, int32_t W, int32_t E, int32_t kt, int32_t ks, float scale,
+                                       const int32_t* pair0, int32_t M, void* ctx_f16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
