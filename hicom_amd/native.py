@@ -3,6 +3,10 @@
 The HIP library is the product: there is NO CPU or PyTorch fallback.  `lib()` raises if the
 shared object is missing or was built for a different ABI version; every wrapper raises
 `HicomNativeError` on a non-zero status, with the library's own message.
+
+What a C function looks like is said ONCE, in `SIGNATURES` below the struct mirrors.  A new entry point is: its declaration in the header,
+one row of that table, a wrapper below `lib()`, and -- if it takes a new struct -- the mirror here and a row of STRUCTS in tests/test_abi.py,
+which holds every row and every mirror against the header.
 """
 from __future__ import annotations
 
@@ -20,45 +24,6 @@ ABI_VERSION = 16
 
 DT_BF16, DT_F32, DT_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_GELU_TANH = 0, 1, 2
-
-EXPORTS = (
-    "hicom_abi_version", "hicom_last_error", "hicom_local_attn_fwd", "hicom_local_attn_bwd", "hicom_trilinear_pool_fwd",
-    "hicom_linear_fwd", "hicom_fold_query_fwd", "hicom_split_bf16_fwd", "hicom_split16_fwd", "hicom_global_stream_fwd",
-    "hicom_global_stream_nparts", "hicom_global_merge_fwd", "hicom_global_combine_fwd",
-    "hicom_readout_gemm_fwd", "hicom_scatter_rows_fwd", "hicom_fold_query_split_fwd",
-    "hicom_global_combine_strided_fwd", "hicom_compressor_workspace_bytes", "hicom_compressor_zero_prefix_bytes", "hicom_compressor_is_fused",
-    "hicom_compressor_fwd2", "hicom_compressor_takes_shard4", "hicom_compressor_handoff_failures", "hicom_cast16_fwd", "hicom_global_dx_fwd",
-    "hicom_compressor_fwd", "hicom_linear_to_rows_fwd", "hicom_fused_stream_fwd", "hicom_fused_stream_nparts",
-    "hicom_planes_gemm_fwd", "hicom_row_ln_fwd", "hicom_small_mha_fwd", "hicom_place_blocks_fwd",
-    "hicom_global_stream_bwd", "hicom_readout16_gemm_fwd", "hicom_to_f16_fwd", "hicom_merge_vproj_fwd",
-    "hicom_dense16_gemm_fwd", "hicom_ln_stream_fwd", "hicom_to_f16_padded_fwd", "hicom_clip_query_prep_fwd", "hicom_inv_norm_fwd",
-    "hicom_global_stream_clip_fwd", "hicom_splice_rows_fwd", "hicom_splice_labels_fwd",
-    "hicom_query_prep_fwd", "hicom_query_prep_state_bytes", "hicom_partials_sum_fwd", "hicom_l2norm_stream_fwd", "hicom_local_attn_adapt_fwd",
-    "hicom_small_mha_scaled_fwd", "hicom_merge_vproj_fixed_fwd", "hicom_dense16_tn_fwd", "hicom_dense16_tn_splits",
-    "hicom_local_attn_adapt_bwd", "hicom_adapt_dy_fwd", "hicom_gelu_split_fwd", "hicom_gelu_bwd_fwd", "hicom_colsum_fwd",
-    "hicom_global_stream_marg_fwd", "hicom_global_stream_marg_width", "hicom_global_stream_has_marg", "hicom_global_merge_marg_fwd",
-    "hicom_act_rows_fwd", "hicom_act_bwd_rows_fwd", "hicom_readout16_gemm_role_fwd", "hicom_r16_chain_state_bytes", "hicom_dense16_gemm_pair_fwd", "hicom_gemv_chain_fwd",
-    "hicom_merge_vproj_sets_fwd", "hicom_readout_tail_fwd", "hicom_readout_tail_state_bytes",
-    "hicom_compressor_ctx16_offset",
-    "hicom_compressor_batch_fwd", "hicom_compressor_batch_workspace_bytes",
-    "hicom_compressor_ragged_fwd", "hicom_compressor_ragged_workspace_bytes", "hicom_compressor_ragged_prepare",
-    "hicom_compressor_batch_adapt_fwd", "hicom_compressor_batch_adapt_workspace_bytes",
-    "hicom_compressor_ragged_adapt_fwd", "hicom_compressor_ragged_adapt_workspace_bytes", "hicom_compressor_ragged_adapt_prepare",
-    "hicom_compressor_multiguide_fwd", "hicom_compressor_multiguide_workspace_bytes",
-    "hicom_compressor_ragged_multiguide_fwd", "hicom_compressor_ragged_multiguide_workspace_bytes", "hicom_compressor_ragged_multiguide_prepare",
-    "hicom_clip_adapt_prepare_fwd", "hicom_clip_adapt_prepare_workspace_bytes",
-    "hicom_compressor_multiguide_adapt_fwd", "hicom_compressor_multiguide_adapt_workspace_bytes",
-    "hicom_compressor_clips_multiguide_fwd", "hicom_compressor_clips_multiguide_workspace_bytes", "hicom_compressor_clips_multiguide_prepare",
-    "hicom_stream_state_clear_fwd", "hicom_stream_state_fold_fwd", "hicom_compressor_stream_push",
-    "hicom_stream_state_fold_set_fwd", "hicom_multi_guide_local_fwd", "hicom_stream_place_rows_fwd", "hicom_compressor_stream_push_multi",
-    "hicom_multi_guide_local_adapt_fwd", "hicom_compressor_stream_push_multi_adapt",
-    "hicom_compressor_stream_group_workspace_bytes", "hicom_compressor_stream_group_prepare", "hicom_compressor_stream_group_push",
-    "hicom_stream_group_merge_fold_fwd",
-    "hicom_compressor_stream_group_multi_workspace_bytes", "hicom_compressor_stream_group_multi_prepare", "hicom_compressor_stream_group_multi_push",
-    "hicom_stream_group_multi_merge_fold_fwd", "hicom_stream_group_place_global_fwd",
-    "hicom_compressor_stream_group_adapt_workspace_bytes", "hicom_compressor_stream_group_adapt_prepare", "hicom_compressor_stream_group_adapt_push",
-    "hicom_stream_group_local_adapt_fwd",
-)
 
 PHASE_STREAM, PHASE_FINISH, PHASE_MERGE_ON_NEXT, PHASE_NEXT_IS_MAIN = 1, 2, 4, 8
 
@@ -320,6 +285,141 @@ class StreamGroupAdaptPushArgs(C.Structure):
     _fields_ = [("base", StreamGroupMultiPushArgs), ("ak", SegAdaptor), ("av", SegAdaptor), ("alpha_dt", C.c_int32), ("eps", C.c_float)]
 
 
+vp, i32, i64, f32, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32
+
+# The C ABI, one row per entry point of include/hicom_hip.h: name -> (restype, argtypes).  lib() applies it; tests/test_abi.py holds every
+# row, and every ctypes.Structure above, against the header.
+SIGNATURES = {
+    "hicom_abi_version": (C.c_int, []),
+    "hicom_last_error": (C.c_char_p, []),
+    "hicom_local_attn_fwd": (C.c_int, [vp, i32, vp, i32, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, i32, vp, vp, vp]),
+    "hicom_local_attn_bwd": (C.c_int, [vp, vp, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, vp, vp, vp, i32, vp, vp, i32, vp]),
+    "hicom_trilinear_pool_fwd": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "hicom_linear_fwd": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "hicom_fold_query_fwd": (C.c_int, [vp, vp, i32, i32, i32, f32, vp, vp]),
+    "hicom_split_bf16_fwd": (C.c_int, [vp, i32, i32, i32, vp, vp, vp]),
+    "hicom_split16_fwd": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
+    "hicom_global_stream_fwd": (C.c_int, [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp]),
+    "hicom_global_stream_nparts": (C.c_int, [i64, i32]),
+    "hicom_global_merge_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, i64, i64, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "hicom_global_combine_fwd": (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
+    "hicom_readout_gemm_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]),
+    "hicom_scatter_rows_fwd": (C.c_int, [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]),
+    "hicom_fold_query_split_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, i32, vp]),
+    "hicom_global_combine_strided_fwd": (C.c_int, [vp, vp, i64, i32, i32, i32, vp, vp]),
+    "hicom_compressor_workspace_bytes": (i64, [C.POINTER(CompressorArgs)]),
+    "hicom_compressor_zero_prefix_bytes": (i64, [C.POINTER(CompressorArgs)]),
+    "hicom_compressor_is_fused": (C.c_int, [C.POINTER(CompressorArgs)]),
+    "hicom_compressor_fwd2": (C.c_int, [C.POINTER(CompressorArgs), C.POINTER(CompressorArgs)]),
+    "hicom_compressor_takes_shard4": (C.c_int, [C.POINTER(CompressorArgs)]),
+    "hicom_compressor_handoff_failures": (C.c_int, [C.POINTER(CompressorArgs), C.POINTER(C.c_int32), vp]),
+    "hicom_cast16_fwd": (C.c_int, [vp, i32, vp, i32, i64, vp]),
+    "hicom_global_dx_fwd": (C.c_int, [vp, vp, i64, vp, vp, vp, i32, i64, i32, vp, i32, vp]),
+    "hicom_compressor_fwd": (C.c_int, [C.POINTER(CompressorArgs)]),
+    "hicom_linear_to_rows_fwd": (C.c_int, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]),
+    "hicom_fused_stream_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp,
+                                         i32, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]),
+    "hicom_fused_stream_nparts": (C.c_int, [i32]),
+    "hicom_planes_gemm_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i64, i64, i32, vp]),
+    "hicom_row_ln_fwd": (C.c_int, [vp, i32, i64, vp, i64, vp, i64, vp, vp, i32, vp, i32, i64, vp, i32, f32, vp, i32, i64, i32, i32, vp]),
+    "hicom_small_mha_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "hicom_place_blocks_fwd": (C.c_int, [vp, i32, i32, i64, i32, vp, i64, i64, i32, vp]),
+    "hicom_global_stream_bwd": (C.c_int, [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
+    "hicom_readout16_gemm_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, C.POINTER(AuxGemv), vp]),
+    "hicom_to_f16_fwd": (C.c_int, [vp, i32, vp, i64, vp]),
+    "hicom_merge_vproj_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "hicom_dense16_gemm_fwd": (C.c_int, [vp, i64, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp, i64, vp, i32, i64, vp, i64, vp, vp,
+                                         i64, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
+    "hicom_ln_stream_fwd": (C.c_int, [vp, i32, i64, vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, vp]),
+    "hicom_to_f16_padded_fwd": (C.c_int, [vp, i32, i64, i64, vp, i64, vp]),
+    "hicom_clip_query_prep_fwd": (C.c_int, [vp, vp, i32, i32, i32, f32, vp, vp]),
+    "hicom_inv_norm_fwd": (C.c_int, [vp, i32, i64, vp, vp]),
+    "hicom_global_stream_clip_fwd": (C.c_int, [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, i32,
+                                               vp]),
+    "hicom_splice_rows_fwd": (C.c_int, [vp, i64, i32, vp, vp]),
+    "hicom_splice_labels_fwd": (C.c_int, [vp, vp, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp]),
+    "hicom_query_prep_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+    "hicom_query_prep_state_bytes": (i64, [i32]),
+    "hicom_partials_sum_fwd": (C.c_int, [vp, i32, i64, vp, vp]),
+    "hicom_l2norm_stream_fwd": (C.c_int, [vp, vp, i64, i32, vp]),
+    "hicom_local_attn_adapt_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, vp,
+                                             vp]),
+    "hicom_small_mha_scaled_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "hicom_merge_vproj_fixed_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "hicom_dense16_tn_fwd": (C.c_int, [vp, i64, vp, i64, i32, i64, i32, i32, vp, i64, i32, vp]),
+    "hicom_dense16_tn_splits": (C.c_int, [i32, i32, i64]),
+    "hicom_local_attn_adapt_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, vp, vp,
+                                             vp, vp, vp, vp, vp, vp]),
+    "hicom_adapt_dy_fwd": (C.c_int, [vp, vp, vp, i32, i64, vp, vp, i32, f32, i32, Axis, Axis, Axis, vp, vp, vp, i32, vp]),
+    "hicom_gelu_split_fwd": (C.c_int, [vp, vp, vp, i64, vp]),
+    "hicom_gelu_bwd_fwd": (C.c_int, [vp, vp, i64, i32, vp, i32, vp]),
+    "hicom_colsum_fwd": (C.c_int, [vp, i64, i32, vp, i32, vp]),
+    "hicom_global_stream_marg_fwd": (C.c_int, [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
+    "hicom_global_stream_marg_width": (C.c_int, [i32, i32]),
+    "hicom_global_stream_has_marg": (C.c_int, [i64, i32, i32, i32, i32, i32]),
+    "hicom_global_merge_marg_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "hicom_act_rows_fwd": (C.c_int, [vp, i64, i64, i32, i32, vp, vp]),
+    "hicom_act_bwd_rows_fwd": (C.c_int, [vp, vp, i64, i64, i32, i32, vp]),
+    "hicom_readout16_gemm_role_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, C.POINTER(R16Role), vp]),
+    "hicom_r16_chain_state_bytes": (i64, [i32]),
+    "hicom_dense16_gemm_pair_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, i64, i32, i64, vp]),
+    "hicom_gemv_chain_fwd": (C.c_int, [C.POINTER(R16Role), vp]),
+    "hicom_merge_vproj_sets_fwd": (C.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "hicom_readout_tail_fwd": (C.c_int, [C.POINTER(R16Gemm), C.POINTER(R16Gemm), C.POINTER(R16Role), C.POINTER(R16Role), vp, vp]),
+    "hicom_readout_tail_state_bytes": (i64, []),
+    "hicom_compressor_ctx16_offset": (i64, [C.POINTER(CompressorArgs)]),
+    "hicom_compressor_batch_fwd": (C.c_int, [C.POINTER(CompressorBatchArgs)]),
+    "hicom_compressor_batch_workspace_bytes": (i64, [C.POINTER(CompressorBatchArgs)]),
+    "hicom_compressor_ragged_fwd": (C.c_int, [C.POINTER(CompressorRaggedArgs)]),
+    "hicom_compressor_ragged_workspace_bytes": (i64, [C.POINTER(CompressorRaggedArgs)]),
+    "hicom_compressor_ragged_prepare": (C.c_int, [C.POINTER(CompressorRaggedArgs)]),
+    "hicom_compressor_batch_adapt_fwd": (C.c_int, [C.POINTER(CompressorBatchAdaptArgs)]),
+    "hicom_compressor_batch_adapt_workspace_bytes": (i64, [C.POINTER(CompressorBatchAdaptArgs)]),
+    "hicom_compressor_ragged_adapt_fwd": (C.c_int, [C.POINTER(CompressorRaggedAdaptArgs)]),
+    "hicom_compressor_ragged_adapt_workspace_bytes": (i64, [C.POINTER(CompressorRaggedAdaptArgs)]),
+    "hicom_compressor_ragged_adapt_prepare": (C.c_int, [C.POINTER(CompressorRaggedAdaptArgs)]),
+    "hicom_compressor_multiguide_fwd": (C.c_int, [C.POINTER(CompressorMultiGuideArgs)]),
+    "hicom_compressor_multiguide_workspace_bytes": (i64, [C.POINTER(CompressorMultiGuideArgs)]),
+    "hicom_compressor_ragged_multiguide_fwd": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs)]),
+    "hicom_compressor_ragged_multiguide_workspace_bytes": (i64, [C.POINTER(CompressorRaggedMultiGuideArgs)]),
+    "hicom_compressor_ragged_multiguide_prepare": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs)]),
+    "hicom_clip_adapt_prepare_fwd": (C.c_int, [vp, vp, i64, i32, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), vp, vp, vp, i64, vp]),
+    "hicom_clip_adapt_prepare_workspace_bytes": (i64, [i64, i32, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor)]),
+    "hicom_compressor_multiguide_adapt_fwd": (C.c_int, [C.POINTER(CompressorMultiGuideAdaptArgs)]),
+    "hicom_compressor_multiguide_adapt_workspace_bytes": (i64, [C.POINTER(CompressorMultiGuideAdaptArgs)]),
+    "hicom_compressor_clips_multiguide_fwd": (C.c_int, [C.POINTER(CompressorClipsMultiGuideArgs)]),
+    "hicom_compressor_clips_multiguide_workspace_bytes": (i64, [C.POINTER(CompressorClipsMultiGuideArgs)]),
+    "hicom_compressor_clips_multiguide_prepare": (C.c_int, [C.POINTER(CompressorClipsMultiGuideArgs)]),
+    "hicom_stream_state_clear_fwd": (C.c_int, [vp, i32, vp, i64, vp]),
+    "hicom_stream_state_fold_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "hicom_compressor_stream_push": (C.c_int, [C.POINTER(StreamPushArgs)]),
+    "hicom_stream_state_fold_set_fwd": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "hicom_multi_guide_local_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "hicom_stream_place_rows_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp, i32, i64, i64, i64, vp]),
+    "hicom_compressor_stream_push_multi": (C.c_int, [C.POINTER(StreamPushMultiArgs)]),
+    "hicom_multi_guide_local_adapt_fwd": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32,
+                                                    i32, i32, i32, f32, vp, vp]),
+    "hicom_compressor_stream_push_multi_adapt": (C.c_int, [C.POINTER(StreamPushMultiAdaptArgs)]),
+    "hicom_compressor_stream_group_workspace_bytes": (i64, [C.POINTER(StreamGroupPushArgs)]),
+    "hicom_compressor_stream_group_prepare": (C.c_int, [C.POINTER(StreamGroupPushArgs)]),
+    "hicom_compressor_stream_group_push": (C.c_int, [C.POINTER(StreamGroupPushArgs)]),
+    "hicom_stream_group_merge_fold_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32),
+                                                    C.POINTER(i32), i32, vp, vp, vp]),
+    "hicom_compressor_stream_group_multi_workspace_bytes": (i64, [C.POINTER(StreamGroupMultiPushArgs)]),
+    "hicom_compressor_stream_group_multi_prepare": (C.c_int, [C.POINTER(StreamGroupMultiPushArgs)]),
+    "hicom_compressor_stream_group_multi_push": (C.c_int, [C.POINTER(StreamGroupMultiPushArgs)]),
+    "hicom_stream_group_multi_merge_fold_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32),
+                                                          C.POINTER(i32), i32, vp, vp, vp]),
+    "hicom_stream_group_place_global_fwd": (C.c_int, [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), u32, i32, i32, i32, vp, i32, i64, i64, i64, vp]),
+    "hicom_compressor_stream_group_adapt_workspace_bytes": (i64, [C.POINTER(StreamGroupAdaptPushArgs)]),
+    "hicom_compressor_stream_group_adapt_prepare": (C.c_int, [C.POINTER(StreamGroupAdaptPushArgs)]),
+    "hicom_compressor_stream_group_adapt_push": (C.c_int, [C.POINTER(StreamGroupAdaptPushArgs)]),
+    "hicom_stream_group_local_adapt_fwd": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32,
+                                                     i32, i32, i32, i32, f32, C.POINTER(i32), i32, vp, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -339,156 +439,9 @@ def lib() -> C.CDLL:
     L.hicom_last_error.restype = C.c_char_p
     if L.hicom_abi_version() != ABI_VERSION:
         raise HicomNativeError(f"ABI mismatch: library {L.hicom_abi_version()} vs binding {ABI_VERSION}; rebuild")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    L.hicom_local_attn_fwd.argtypes = [vp, i32, vp, i32, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, i32, vp, vp, vp]
-    L.hicom_local_attn_bwd.argtypes = [vp, vp, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, vp, vp, vp, i32, vp, vp, i32, vp]
-    L.hicom_global_dx_fwd.argtypes = [vp, vp, i64, vp, vp, vp, i32, i64, i32, vp, i32, vp]
-    L.hicom_trilinear_pool_fwd.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-    L.hicom_linear_fwd.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-    L.hicom_fold_query_fwd.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
-    L.hicom_split_bf16_fwd.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-    L.hicom_split16_fwd.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
-    L.hicom_global_stream_fwd.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64,
-                                          vp, vp, vp, i32, vp]
-    L.hicom_global_stream_nparts.argtypes = [i64, i32]
-    L.hicom_global_stream_marg_fwd.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64,
-                                               vp, vp, vp, vp, i32, vp]
-    L.hicom_global_stream_marg_width.argtypes = [i32, i32]
-    L.hicom_global_stream_has_marg.argtypes = [i64, i32, i32, i32, i32, i32]
-    L.hicom_global_merge_marg_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp]
-    L.hicom_global_stream_bwd.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp, vp,
-                                          vp, vp, vp, i32, vp]
-    L.hicom_global_merge_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i64, i64, i32, i32, vp, i32, i32, i32,
-                                         vp, vp, vp, i32, vp]
-    L.hicom_linear_to_rows_fwd.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
-    L.hicom_fused_stream_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, vp, i32, vp, vp, i32, i32, i32,
-                                         vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
-    L.hicom_readout16_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, C.POINTER(AuxGemv), vp]
-    L.hicom_readout16_gemm_role_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, C.POINTER(R16Role), vp]
-    L.hicom_r16_chain_state_bytes.argtypes = [i32]
-    L.hicom_gemv_chain_fwd.argtypes = [C.POINTER(R16Role), vp]
-    L.hicom_merge_vproj_sets_fwd.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.hicom_r16_chain_state_bytes.restype = i64
-    L.hicom_readout_tail_fwd.argtypes = [C.POINTER(R16Gemm), C.POINTER(R16Gemm), C.POINTER(R16Role), C.POINTER(R16Role), vp, vp]
-    L.hicom_readout_tail_state_bytes.argtypes = []
-    L.hicom_readout_tail_state_bytes.restype = i64
-    L.hicom_compressor_ctx16_offset.argtypes = [C.POINTER(CompressorArgs)]
-    L.hicom_compressor_ctx16_offset.restype = i64
-    L.hicom_to_f16_fwd.argtypes = [vp, i32, vp, i64, vp]
-    L.hicom_splice_rows_fwd.argtypes = [vp, i64, i32, vp, vp]
-    L.hicom_splice_labels_fwd.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp]
-    L.hicom_to_f16_padded_fwd.argtypes = [vp, i32, i64, i64, vp, i64, vp]
-    L.hicom_dense16_gemm_fwd.argtypes = [vp, i64, vp, i64, i32, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp, i64, vp, i32, i64, vp, i64, vp,
-                                         vp, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp]
-    L.hicom_dense16_gemm_pair_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, i64, i32, i64, vp]
-    L.hicom_partials_sum_fwd.argtypes = [vp, i32, i64, vp, vp]
-    L.hicom_dense16_tn_splits.argtypes = [i32, i32, i64]
-    L.hicom_dense16_tn_fwd.argtypes = [vp, i64, vp, i64, i32, i64, i32, i32, vp, i64, i32, vp]
-    L.hicom_l2norm_stream_fwd.argtypes = [vp, vp, i64, i32, vp]
-    L.hicom_local_attn_adapt_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32, vp, vp]
-    L.hicom_local_attn_adapt_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, Axis, Axis, Axis, vp, i32, i64, f32, f32,
-                                             vp, vp, vp, vp, vp, vp, vp, vp]
-    L.hicom_adapt_dy_fwd.argtypes = [vp, vp, vp, i32, i64, vp, vp, i32, f32, i32, Axis, Axis, Axis, vp, vp, vp, i32, vp]
-    L.hicom_gelu_split_fwd.argtypes = [vp, vp, vp, i64, vp]
-    L.hicom_gelu_bwd_fwd.argtypes = [vp, vp, i64, i32, vp, i32, vp]
-    L.hicom_act_rows_fwd.argtypes = [vp, i64, i64, i32, i32, vp, vp]
-    L.hicom_act_bwd_rows_fwd.argtypes = [vp, vp, i64, i64, i32, i32, vp]
-    L.hicom_colsum_fwd.argtypes = [vp, i64, i32, vp, i32, vp]
-    L.hicom_clip_query_prep_fwd.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp]
-    L.hicom_inv_norm_fwd.argtypes = [vp, i32, i64, vp, vp]
-    L.hicom_global_stream_clip_fwd.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64,
-                                               vp, vp, vp, i32, vp]
-    L.hicom_ln_stream_fwd.argtypes = [vp, i32, i64, vp, vp, vp, vp, i32, f32, vp, i32, i32, i32, vp]
-    L.hicom_merge_vproj_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.hicom_merge_vproj_fixed_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.hicom_fused_stream_nparts.argtypes = [i32]
-    L.hicom_query_prep_state_bytes.argtypes = [i32]
-    L.hicom_query_prep_state_bytes.restype = i64
-    L.hicom_query_prep_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
-    L.hicom_planes_gemm_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i64, i64, i32, vp]
-    L.hicom_row_ln_fwd.argtypes = [vp, i32, i64, vp, i64, vp, i64, vp, vp, i32, vp, i32, i64, vp, i32, f32, vp, i32, i64,
-                                   i32, i32, vp]
-    L.hicom_small_mha_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.hicom_small_mha_scaled_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]
-    L.hicom_fold_query_split_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, i32, vp]
-    L.hicom_global_combine_strided_fwd.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp]
-    ap = C.POINTER(CompressorArgs)
-    L.hicom_compressor_workspace_bytes.argtypes = [ap]
-    L.hicom_compressor_zero_prefix_bytes.argtypes = [ap]
-    L.hicom_compressor_is_fused.argtypes = [ap]
-    L.hicom_compressor_fwd2.argtypes = [ap, ap]
-    L.hicom_cast16_fwd.argtypes = [vp, i32, vp, i32, i64, vp]
-    L.hicom_compressor_takes_shard4.argtypes = [ap]
-    L.hicom_compressor_handoff_failures.argtypes = [ap, C.POINTER(C.c_int32), vp]
-    L.hicom_compressor_fwd.argtypes = [ap]
-    L.hicom_compressor_batch_fwd.argtypes = [C.POINTER(CompressorBatchArgs)]
-    L.hicom_compressor_batch_workspace_bytes.argtypes = [C.POINTER(CompressorBatchArgs)]
-    L.hicom_compressor_ragged_fwd.argtypes = [C.POINTER(CompressorRaggedArgs)]
-    L.hicom_compressor_ragged_prepare.argtypes = [C.POINTER(CompressorRaggedArgs)]
-    L.hicom_compressor_ragged_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedArgs)]
-    L.hicom_compressor_batch_adapt_fwd.argtypes = [C.POINTER(CompressorBatchAdaptArgs)]
-    L.hicom_compressor_batch_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorBatchAdaptArgs)]
-    L.hicom_compressor_ragged_adapt_fwd.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
-    L.hicom_compressor_ragged_adapt_prepare.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
-    L.hicom_compressor_ragged_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedAdaptArgs)]
-    L.hicom_compressor_multiguide_fwd.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
-    L.hicom_compressor_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorMultiGuideArgs)]
-    L.hicom_compressor_multiguide_adapt_fwd.argtypes = [C.POINTER(CompressorMultiGuideAdaptArgs)]
-    L.hicom_compressor_multiguide_adapt_workspace_bytes.argtypes = [C.POINTER(CompressorMultiGuideAdaptArgs)]
-    L.hicom_clip_adapt_prepare_workspace_bytes.argtypes = [i64, i32, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor)]
-    L.hicom_clip_adapt_prepare_fwd.argtypes = [vp, vp, i64, i32, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), vp, vp, vp, i64, vp]
-    L.hicom_compressor_ragged_multiguide_fwd.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
-    L.hicom_compressor_ragged_multiguide_prepare.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
-    L.hicom_compressor_ragged_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorRaggedMultiGuideArgs)]
-    L.hicom_compressor_clips_multiguide_fwd.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
-    L.hicom_compressor_clips_multiguide_prepare.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
-    L.hicom_compressor_clips_multiguide_workspace_bytes.argtypes = [C.POINTER(CompressorClipsMultiGuideArgs)]
-    L.hicom_stream_state_clear_fwd.argtypes = [vp, i32, vp, i64, vp]
-    L.hicom_stream_state_fold_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.hicom_compressor_stream_push.argtypes = [C.POINTER(StreamPushArgs)]
-    L.hicom_stream_state_fold_set_fwd.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
-    L.hicom_multi_guide_local_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]
-    L.hicom_stream_place_rows_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp, i32, i64, i64, i64, vp]
-    L.hicom_compressor_stream_push_multi.argtypes = [C.POINTER(StreamPushMultiArgs)]
-    L.hicom_multi_guide_local_adapt_fwd.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32, i32, i32,
-                                                    i32, f32, vp, vp]
-    L.hicom_compressor_stream_push_multi_adapt.argtypes = [C.POINTER(StreamPushMultiAdaptArgs)]
-    L.hicom_compressor_stream_group_workspace_bytes.argtypes = [C.POINTER(StreamGroupPushArgs)]
-    L.hicom_compressor_stream_group_prepare.argtypes = [C.POINTER(StreamGroupPushArgs)]
-    L.hicom_compressor_stream_group_push.argtypes = [C.POINTER(StreamGroupPushArgs)]
-    L.hicom_stream_group_merge_fold_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32,
-                                                    vp, vp, vp]
-    L.hicom_compressor_stream_group_multi_workspace_bytes.argtypes = [C.POINTER(StreamGroupMultiPushArgs)]
-    L.hicom_compressor_stream_group_multi_prepare.argtypes = [C.POINTER(StreamGroupMultiPushArgs)]
-    L.hicom_compressor_stream_group_multi_push.argtypes = [C.POINTER(StreamGroupMultiPushArgs)]
-    L.hicom_stream_group_multi_merge_fold_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, C.POINTER(i32),
-                                                          C.POINTER(i32), i32, vp, vp, vp]
-    L.hicom_stream_group_place_global_fwd.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.c_uint32, i32, i32, i32, vp, i32, i64, i64, i64, vp]
-    L.hicom_compressor_stream_group_adapt_workspace_bytes.argtypes = [C.POINTER(StreamGroupAdaptPushArgs)]
-    L.hicom_compressor_stream_group_adapt_prepare.argtypes = [C.POINTER(StreamGroupAdaptPushArgs)]
-    L.hicom_compressor_stream_group_adapt_push.argtypes = [C.POINTER(StreamGroupAdaptPushArgs)]
-    L.hicom_stream_group_local_adapt_fwd.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32, i32, i32,
-                                                     i32, i32, f32, C.POINTER(i32), i32, vp, vp]
-    L.hicom_global_combine_fwd.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.hicom_readout_gemm_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i64, i64, i32, vp]
-    L.hicom_scatter_rows_fwd.argtypes = [vp, i32, i32, i32, vp, i32, i64, i64, i64, i32, i32, vp]
-    L.hicom_place_blocks_fwd.argtypes = [vp, i32, i32, i64, i32, vp, i64, i64, i32, vp]
-    for name in EXPORTS[2:]:
-        getattr(L, name).restype = C.c_int
-    L.hicom_compressor_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_zero_prefix_bytes.restype = C.c_int64
-    L.hicom_compressor_batch_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_ragged_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_batch_adapt_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_ragged_adapt_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_multiguide_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_multiguide_adapt_workspace_bytes.restype = C.c_int64
-    L.hicom_clip_adapt_prepare_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_ragged_multiguide_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_clips_multiguide_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_stream_group_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_stream_group_multi_workspace_bytes.restype = C.c_int64
-    L.hicom_compressor_stream_group_adapt_workspace_bytes.restype = C.c_int64
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 

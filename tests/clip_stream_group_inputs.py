@@ -43,6 +43,7 @@ import numpy as np
 import torch
 
 import clip_stream_inputs as ci
+from global_stream_inputs import EPS23, TRANS
 from hicom_amd import geometry as geo
 from hicom_amd import synth
 from oracle import hicom_oracle as orc
@@ -252,3 +253,46 @@ def group_ref(key, schedule, with_fe=True, mutant=None, nslots=B):
 
 def region_errors(got, want):
     return ci.region_errors(got, want)
+
+
+# ---- the merge + fold kernels alone: the shapes of their tests, the float64 reference and its bounds -----------------------------------------
+# =============================================================================================================================
+# the merge + fold kernel alone
+# =============================================================================================================================
+ITEMS, R, RP, E, TC, H, W = 3, 9, 16, 1152, 4, 6, 6
+N = TC * H * W
+Y0, X0, P = 16, 22, 28
+SLOTS, T0S, NSLOTS = (2, 0, 1), (8, 0, 4), 4             # a fourth slot is absent
+
+
+def merge_fold_ref(nparts, pm, pl, pacc, s, pe, ml, acc):
+    """float64 (M', L', ACC') per item and the bounds of L' and ACC' (clip_stream_group_inputs' docstring)."""
+    out = []
+    f = lambda x: np.asarray(x, dtype=np.float64)
+    for i, (slot, t0) in enumerate(zip(SLOTS, T0S)):
+        m, l, a = (f(x[i * nparts:(i + 1) * nparts, :R]) for x in (pm, pl, pacc))           # [nparts, R], [nparts, R, E]
+        Mc = m.max(axis=0)
+        u = np.exp(m - Mc)
+        Lc, Lc_arg = (u * l).sum(0), (u * EPS23 * np.abs(m - Mc) * l).sum(0)
+        A, A_abs = (u[..., None] * a).sum(0), (u[..., None] * np.abs(a)).sum(0)
+        D_c = ((u * EPS23 * np.abs(m - Mc))[..., None] * np.abs(a)).sum(0)
+        e = np.exp(f(s[i, :R]) - Mc[:, None]).reshape(R, TC, H, W)
+        ea = e * EPS23 * np.abs(f(s[i, :R]).reshape(R, TC, H, W) - Mc[:, None, None, None])
+        rows = np.concatenate([f(pe[t0:t0 + TC]), f(pe[Y0:Y0 + H]), f(pe[X0:X0 + W])])        # [T + H + W, E]
+        marg = lambda w: np.concatenate([w.sum((2, 3)), w.sum((1, 3)), w.sum((1, 2))], axis=1)     # [R, T + H + W]
+        Bc, B_abs, G_c = marg(e) @ rows, marg(e) @ np.abs(rows), marg(ea) @ np.abs(rows)
+        M, L, ACC = f(ml[slot, :, 0]), f(ml[slot, :, 1]), f(acc[slot])
+        Mn = np.maximum(M, Mc)
+        with np.errstate(invalid="ignore"):
+            w_o = np.where(np.isinf(M), 0.0, np.exp(M - Mn))
+            arg_o = np.where(np.isinf(M), 0.0, np.abs(M - Mn))
+        w_c, arg_c = np.exp(Mc - Mn), np.abs(Mc - Mn)
+        Ln, An = w_o * L + w_c * Lc, w_o[:, None] * ACC + w_c[:, None] * (A + Bc)
+        rel = 8 * EPS23 + 2 * TRANS
+        k_m, k_p = (nparts + 8) * EPS23 + TRANS, (N + TC + H + W + 8) * EPS23 + TRANS
+        l_tol = rel * (w_o * L + w_c * Lc) + EPS23 * (arg_o * w_o * L + arg_c * w_c * Lc) + w_c * (k_m * Lc + Lc_arg)
+        a_mag = w_c[:, None] * (A_abs + B_abs)
+        a_tol = (rel * (w_o[:, None] * np.abs(ACC) + a_mag) + EPS23 * (arg_o[:, None] * w_o[:, None] * np.abs(ACC) + arg_c[:, None] * a_mag)
+                 + w_c[:, None] * (k_m * A_abs + D_c + k_p * B_abs + G_c))
+        out.append((slot, Mn, Ln, An, l_tol, a_tol))
+    return out

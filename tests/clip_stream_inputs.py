@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 import cases
+from global_stream_inputs import EPS23, TRANS
 from hicom_amd import geometry as geo
 from hicom_amd import synth
 from oracle import hicom_oracle as orc
@@ -175,3 +176,22 @@ def chunked_ref(key, chunking, with_fe=True, mutant=None, guide2=False):
     att = Wo @ (O / L[:, None]).reshape(D) + bo
     out[lay.n_rows:] = _mlp((g + att)[None], sd, "global_compressor.readout")
     return out
+
+
+# ---- the fold kernel alone: float64 reference and bounds (tests/test_gpu_clip_stream.py has the derivation) ---------------------------------
+def fold_ref(pm, pl, pacc, M, L, A):
+    """float64 (M', L', ACC') and the bounds of L' and ACC' (module docstring)."""
+    R = M.shape[0]
+    nparts = pm.shape[0]
+    m = np.concatenate([M[None].astype(np.float64), pm[:, :R].astype(np.float64)])            # [1 + nparts, R]
+    l = np.concatenate([L[None].astype(np.float64), pl[:, :R].astype(np.float64)])
+    a = np.concatenate([A[None].astype(np.float64), pacc[:, :R].astype(np.float64)])          # [1 + nparts, R, E]
+    Mn = m.max(axis=0)
+    with np.errstate(invalid="ignore"):
+        w = np.where(np.isinf(m), 0.0, np.exp(m - Mn))
+        arg = np.where(np.isinf(m), 0.0, np.abs(m - Mn))
+    rel = (nparts + 8) * EPS23 + 2 * TRANS
+    Ln, An = (w * l).sum(0), (w[..., None] * a).sum(0)
+    l_tol = rel * (w * np.abs(l)).sum(0) + (w * EPS23 * arg * np.abs(l)).sum(0)
+    a_tol = rel * (w[..., None] * np.abs(a)).sum(0) + ((w * EPS23 * arg)[..., None] * np.abs(a)).sum(0)
+    return Mn, Ln, An, l_tol, a_tol

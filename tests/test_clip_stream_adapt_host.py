@@ -8,10 +8,6 @@ As in tests/test_clip_stream_multi_host.py the push-time checks and the plan cac
 the device methods replaced by recorders and `nv` as clip_stream sees it replaced by an object that fails the test when any native function
 is called."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import pytest
@@ -22,93 +18,11 @@ import hicom_amd
 from hicom_amd import clip_stream as cs
 from hicom_amd import native as nv
 from hicom_amd import segments as seg
-from test_clip_stream_host import NoNative, module, tokens
-from test_clip_stream_multi_host import C_REFUSALS as PLAIN_REFUSALS
-from test_clip_stream_multi_host import guides
-from test_clip_stream_multi_host import push_block as plain_block
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("hicom_multi_guide_local_adapt_fwd", "hicom_compressor_stream_push_multi_adapt")
-EINVAL, EUNSUP = -1, -2
-ADDR = 0x7F0000001000
-ADAPTKV = "local43_adaptkv_global32"
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-        assert getattr(L, name).restype is ctypes.c_int
-    assert "typedef struct hicom_stream_push_multi_adapt_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16                            # additive: the version stays
-    for entry in ("open_stream_adapt", "open_stream_multi", "open_stream"):
-        assert hasattr(hicom_amd.HIComProjector, entry)
-    assert issubclass(cs.ClipStreamAdapt, cs.ClipStreamMulti)
-
-
-def test_adapt_block_layout_matches_the_header_and_the_old_blocks_keep_their_size(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    A = nv.StreamPushMultiAdaptArgs
-    names = [n for n, _ in A._fields_]
-    old = (("hicom_stream_push_multi_args", nv.StreamPushMultiArgs), ("hicom_stream_push_args", nv.StreamPushArgs),
-           ("hicom_seg_adaptor", nv.SegAdaptor), ("hicom_compressor_multiguide_adapt_args", nv.CompressorMultiGuideAdaptArgs))
-    src = tmp_path / "abi.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hicom_hip.h"\nint main(void) {\n'
-                   '    printf("%d %zu", HICOM_ABI_VERSION, sizeof(hicom_stream_push_multi_adapt_args));\n'
-                   + "".join(f'    printf(" %zu", offsetof(hicom_stream_push_multi_adapt_args, {n}));\n' for n in names)
-                   + "".join(f'    printf(" %zu", sizeof({c}));\n' for c, _ in old)
-                   + '    printf("\\n");\n    return 0;\n}\n')
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    ver, size, *rest = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    offs, old_sizes = rest[:len(names)], rest[len(names):]
-    assert ver == 16 and size == ctypes.sizeof(A)
-    assert offs == [getattr(A, n).offset for n in names]
-    assert names[0] == "base" and A.base.offset == 0 and names[-2:] == ["alpha_dt", "eps"]
-    assert old_sizes == [ctypes.sizeof(t) for _, t in old]
-    assert old_sizes[:3] == [344, 280, 56], "the blocks of the earlier entry points keep their sizes"
+from host_util import ADDR, EINVAL, EUNSUP, NoNative, module, tokens
+from stream_blocks import ADAPTKV, ADAPT_REFUSALS, MULTI_REFUSALS as PLAIN_REFUSALS, adapt_block, adaptor, guides, multi_push_block as plain_block
 
 
 # ---- C refusals: none launches ----------------------------------------------------------------------------------------------------------
-def adaptor(**over):
-    d = nv.SegAdaptor()
-    for f, _ in nv.SegAdaptor._fields_:
-        setattr(d, f, ADDR)
-    for k, v in over.items():
-        setattr(d, k, v)
-    return d
-
-
-def adapt_block(base=None, **over):
-    """The chunk of test_clip_stream_multi_host.push_block (4 frames of 6 x 6, Q = 3, hidden 64) with both adaptors: 144 tokens, planes and
-    hidden planes of 144 x 1152 x 2 = 331776 bytes each."""
-    x = nv.StreamPushMultiAdaptArgs()
-    x.base = plain_block(**(base or {}))
-    x.ak, x.av = adaptor(), adaptor()
-    x.ky, x.vy, x.adapt_ws, x.adapt_ws_bytes, x.alpha_dt, x.eps = ADDR, ADDR, ADDR, 2 * 331776, nv.DT_BF16, 1e-6
-    for k, v in over.items():
-        setattr(x, k, v)
-    return x
-
-
-ADAPT_REFUSALS = {
-    "both planes NULL": (dict(ky=None, vy=None, ak=adaptor(w0=None), av=adaptor(w0=None)), EINVAL, "neither stream has a prepared plane"),
-    "a plane without its adaptor": (dict(av=adaptor(w0=None)), EINVAL, "come together"),
-    "an adaptor without its plane": (dict(ky=None), EINVAL, "come together"),
-    "workspace one byte short": (dict(adapt_ws_bytes=2 * 331776 - 1), EINVAL, "workspace of 663552 bytes"),
-    "NULL workspace": (dict(adapt_ws=None), EINVAL, "workspace of"),
-    "workspace off its 256 bytes": (dict(adapt_ws=ADDR + 128), EINVAL, "256-byte aligned"),
-    "misaligned key plane": (dict(ky=ADDR + 8), EINVAL, "16-byte aligned planes"),
-    "misaligned value plane": (dict(vy=ADDR + 2), EINVAL, "16-byte aligned planes"),
-    "alpha dtype": (dict(alpha_dt=nv.DT_F16), EINVAL, "alpha dtype"),
-    "NULL LayerNorm weight": (dict(ak=adaptor(gamma=None)), EINVAL, "adaptor weights"),
-    "NULL alpha": (dict(av=adaptor(alpha=None)), EINVAL, "adaptor weights"),
-    "NULL second layer": (dict(av=adaptor(w2_f16=None)), EINVAL, "adaptor weights"),
-}
 
 
 @pytest.mark.parametrize("name", list(ADAPT_REFUSALS))

@@ -4,10 +4,6 @@ new block as the host C compiler sees it and the unchanged sizes of the earlier 
 C entry points with made-up aligned addresses that nothing reads before a launch, of the Python object with `nv` replaced by an object that
 fails the test when a native function is called -- the plan key and the store."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import pytest
@@ -15,21 +11,14 @@ import torch
 
 import cases
 import hicom_amd
-import test_clip_stream_group_multi_host as gmh
 from hicom_amd import clip_stream as cs
 from hicom_amd import clip_stream_group as csg
 from hicom_amd import clip_stream_group_adapt as cga
 from hicom_amd import clip_stream_group_multi as cgm
 from hicom_amd import native as nv
-from test_clip_stream_adapt_host import adaptor
-from test_clip_stream_host import ADDR, EINVAL, EUNSUP, NoNative, module, tokens
+from host_util import ADDR, EINVAL, EUNSUP, NoNative, module, tokens
+from stream_blocks import ADAPTKV, adaptor, group_multi as gmh, guides
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADAPTKV = "local43_adaptkv_global32"
-SYMBOLS = ("hicom_compressor_stream_group_adapt_workspace_bytes", "hicom_compressor_stream_group_adapt_prepare",
-           "hicom_compressor_stream_group_adapt_push", "hicom_stream_group_local_adapt_fwd")
-EARLIER = {**gmh.EARLIER, "hicom_stream_group_multi_push_args": nv.StreamGroupMultiPushArgs, "hicom_seg_adaptor": nv.SegAdaptor}
-EARLIER_SIZES = {**gmh.EARLIER_SIZES, "hicom_stream_group_multi_push_args": 1008, "hicom_seg_adaptor": 56}
 PLANE = (4 + 8 + 4) * 36 * 1152 * 2          # one fp16 plane over the 576 stacked tokens of gmh.push_block()
 
 
@@ -37,44 +26,6 @@ def test_the_feature_is_there():
     assert hasattr(hicom_amd.HIComProjector, "open_stream_group_adapt")
     assert issubclass(cga.ClipStreamGroupAdapt, cgm.ClipStreamGroupMulti) and cga.ClipStreamGroupAdapt.RECIPE == "adaptkv"
     assert cga.ClipStreamGroupAdapt.RECIPE_WORDS == "the k / v adaptor release recipe"
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-    assert declared == set(nv.EXPORTS), "header and native.EXPORTS name the same entry points"
-    assert L.hicom_compressor_stream_group_adapt_workspace_bytes.restype is ctypes.c_int64
-    assert L.hicom_compressor_stream_group_adapt_push.restype is ctypes.c_int
-    assert "typedef struct hicom_stream_group_adapt_push_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16
-
-
-def test_push_args_layout_matches_the_header_and_the_earlier_blocks_keep_their_sizes(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    A = nv.StreamGroupAdaptPushArgs
-    names = [n for n, _ in A._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hicom_hip.h"\nint main(void) {\n'
-                   '    printf("%d %zu", HICOM_ABI_VERSION, sizeof(hicom_stream_group_adapt_push_args));\n'
-                   + "".join(f'    printf(" %zu", sizeof({n}));\n' for n in EARLIER)
-                   + "".join(f'    printf(" %zu", offsetof(hicom_stream_group_adapt_push_args, {n}));\n' for n in names)
-                   + '    printf("\\n");\n    return 0;\n}\n')
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    ver, size, *rest = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    earlier, offs = rest[:len(EARLIER)], rest[len(EARLIER):]
-    assert ver == nv.ABI_VERSION == 16
-    assert size == ctypes.sizeof(A)
-    assert offs == [getattr(A, n).offset for n in names]
-    assert names == ["base", "ak", "av", "alpha_dt", "eps"] and A.base.offset == 0
-    for (name, struct), got in zip(EARLIER.items(), earlier):
-        assert got == ctypes.sizeof(struct), name
-        assert got == EARLIER_SIZES[name], f"{name} changed its size"
 
 
 # ---- C refusals: none launches ----------------------------------------------------------------------------------------------------------
@@ -170,7 +121,6 @@ def test_local_adapt_refusals_in_front_of_any_device_call():
 
 # ---- Python refusals, the plan key and the store, without a device -------------------------------------------------------------------------
 COUNTS = (1, 2, 5)
-guides = gmh.guides
 
 
 @pytest.fixture

@@ -3,106 +3,19 @@ the new symbols and the unchanged ABI version, the layout of the push block as t
 device work -- of the C entry points with made-up aligned addresses that nothing reads before a launch, of the Python object with `nv`
 replaced by an object that fails the test when a native function is called -- and the plan cache keyed by the tuple of chunk lengths."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import pytest
 import torch
 
-import cases
-import hicom_amd
 from hicom_amd import clip_stream as cs
 from hicom_amd import clip_stream_group as csg
 from hicom_amd import native as nv
-from test_clip_stream_host import ADDR, EINVAL, EUNSUP, NoNative, module, tokens
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("hicom_compressor_stream_group_workspace_bytes", "hicom_compressor_stream_group_prepare", "hicom_compressor_stream_group_push",
-           "hicom_stream_group_merge_fold_fwd")
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-    assert declared == set(nv.EXPORTS), "header and native.EXPORTS name the same entry points"
-    assert L.hicom_compressor_stream_group_workspace_bytes.restype is ctypes.c_int64
-    assert "typedef struct hicom_stream_group_push_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16
-    assert hasattr(hicom_amd.HIComProjector, "open_stream_group")
-
-
-def test_push_args_layout_matches_the_header_field_for_field(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    names = [n for n, _ in nv.StreamGroupPushArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hicom_hip.h"\nint main(void) {\n'
-                   '    printf("%d %zu", HICOM_ABI_VERSION, sizeof(hicom_stream_group_push_args));\n'
-                   + "".join(f'    printf(" %zu", offsetof(hicom_stream_group_push_args, {n}));\n' for n in names)
-                   + '    printf("\\n");\n    return 0;\n}\n')
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    ver, size, *offs = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    assert ver == nv.ABI_VERSION == 16
-    assert size == ctypes.sizeof(nv.StreamGroupPushArgs)
-    assert offs == [getattr(nv.StreamGroupPushArgs, n).offset for n in names]
-    assert names[-1] == "stream" and nv.StreamGroupPushArgs.tc.size == 4 * nv.GROUP_MAX == 128
+from host_util import ADDR, EINVAL, EUNSUP, NoNative, module, tokens
+from stream_blocks import GROUP_REFUSALS as C_REFUSALS, group_push_block as push_block, guides
 
 
 # ---- C refusals: none launches ----------------------------------------------------------------------------------------------------------
-def push_block(over=None):
-    """Three items (4, 8, 4 frames) of a 6 x 6 grid for the slots (2, 0, 1) of a group of 3; `over`: fields, or (array, index) -> value."""
-    a = nv.StreamGroupPushArgs()
-    a.B, a.items, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.hidden, a.chunks = 3, 3, 6, 6, 1152, 4, 3, 9, 64, 2
-    for f in ("ff", "fe", "guide", "q_hi", "q_lo", "pos_a", "pe", "ws", "state_ml", "state_acc", "lw0_f16", "lb0", "lw2_f16", "lb2", "out"):
-        setattr(a, f, ADDR)
-    a.P, a.y_index0, a.x_index0, a.l_scale, a.out_dt, a.ldo, a.slot_rows, a.slot_stride = 28, 16, 22, 0.03, nv.DT_F32, 64, 48, 64 * 48
-    for i, (tc, slot, t0, row0) in enumerate(((4, 2, 0, 0), (8, 0, 4, 4), (4, 1, 8, 8))):
-        a.tc[i], a.slot[i], a.t0[i], a.row0[i] = tc, slot, t0, row0
-    a.ws_bytes = 1 << 30
-    for k, v in (over or {}).items():
-        if isinstance(k, tuple):
-            getattr(a, k[0])[k[1]] = v
-        else:
-            setattr(a, k, v)
-    return a
-
-
-C_REFUSALS = {
-    "B = 0": ({"B": 0}, EUNSUP, "1 <= B <= 32"),
-    "B = 33": ({"B": 33}, EUNSUP, "1 <= B <= 32"),
-    "more items than slots": ({"items": 4}, EINVAL, "a slot appears at most once"),
-    "E = 768": ({"E": 768}, EUNSUP, "only 1152"),
-    "17 heads": ({"nh": 17}, EUNSUP, "<= 16 folded rows"),
-    "hidden = 100": ({"hidden": 100}, EUNSUP, "multiple of 64"),
-    "Tc % kt": ({("tc", 1): 6}, EUNSUP, "item 1 needs an exact window partition"),
-    "H % ks": ({"H": 7}, EUNSUP, "exact window partition"),
-    "window of 72 tokens": ({"kt": 8, ("tc", 0): 8, ("tc", 2): 8}, EUNSUP, "<= 64"),
-    "output dtype": ({"out_dt": nv.DT_F16}, EUNSUP, "output dtype"),
-    "workspace too small": ({"ws_bytes": 4096}, EINVAL, "workspace of"),
-    "NULL ff": ({"ff": None}, EINVAL, "NULL pointer"),
-    "NULL state": ({"state_acc": None}, EINVAL, "NULL pointer"),
-    "NULL weight": ({"lw2_f16": None}, EINVAL, "NULL weight"),
-    "pe without pos_a": ({"pos_a": None}, EINVAL, "come together"),
-    "unaligned ff": ({"ff": ADDR + 8}, EINVAL, "16-byte aligned"),
-    "duplicate slot": ({("slot", 2): 0}, EINVAL, "slot 0 appears twice"),
-    "slot out of range": ({("slot", 0): 3}, EINVAL, "0 <= slot < B = 3"),
-    "negative slot": ({("slot", 0): -1}, EINVAL, "0 <= slot < B = 3"),
-    "t0 inside a window group": ({("t0", 1): 2}, EINVAL, "whole window groups"),
-    "frames past the tables": ({("t0", 1): 12}, EINVAL, "item 1: frames 12 .. 20, grid 6x6 outside the positional tables"),
-    "rows past the slot's buffer": ({("row0", 1): 41}, EINVAL, "item 1: rows 41 .. 49 outside the slot's buffer of 48 rows"),
-    "negative row": ({("row0", 0): -1}, EINVAL, "outside the slot's buffer"),
-    "slots closer than their rows": ({"slot_stride": 64 * 47}, EINVAL, "output layout"),
-    "ldo < hidden": ({"ldo": 63}, EINVAL, "output layout"),
-    "newline rows without a pointer": ({"nl_group": 2}, EINVAL, "no newline token"),
-}
 
 
 @pytest.mark.parametrize("name", list(C_REFUSALS))
@@ -156,10 +69,6 @@ def host(monkeypatch):
     monkeypatch.setattr(G, "_launch", lambda self, plan, ff, fe, slots, t0s, row0s, stream: launches.append((tuple(slots), tuple(t0s), tuple(row0s))))
     monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: SimpleNamespace(cuda_stream=0))
     return SimpleNamespace(launches=launches, built=built)
-
-
-def guides(B):
-    return torch.zeros((B, cases.D), dtype=torch.bfloat16)
 
 
 def test_open_refusals_come_before_any_native_call(monkeypatch):

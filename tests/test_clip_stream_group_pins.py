@@ -23,14 +23,13 @@ import torch
 
 import cases
 import hicom_amd
-import test_clip_stream_group_host as single
-import test_clip_stream_group_multi_host as multi
 from hicom_amd import clip_stream as cs
 from hicom_amd import clip_stream_group as csg
 from hicom_amd import clip_stream_group_multi as cgm
 from hicom_amd import native as nv
+from host_util import ADDR, module, tokens
+from stream_blocks import group as single, group_multi as multi
 
-ADDR = single.ADDR
 FLAVOURS = {"group": (single, "hicom_compressor_stream_group"), "group_multi": (multi, "hicom_compressor_stream_group_multi")}
 
 
@@ -337,10 +336,10 @@ def recorded(monkeypatch, kind):
         self.P, self.y0, self.x0 = 28, 16, 22
     monkeypatch.setattr(G, "_allocate", allocate)
     monkeypatch.setattr(G, "_prepare", lambda self, guides, slot=None: setattr(self, "guides", guides))
-    m = single.module(mm_newline_position="grid")
+    m = module(mm_newline_position="grid")
     lc = m.local_compressor
     tensors.update({"readout_f16()[0]": t(4), "readout_f16()[1]": t(4), "readout[0].bias": lc.readout[0].bias, "readout[2].bias": lc.readout[2].bias,
-                    "ff": single.tokens(16), "fe": single.tokens(16)})
+                    "ff": tokens(16), "fe": tokens(16)})
     monkeypatch.setattr(type(lc), "readout_f16", lambda self: (tensors["readout_f16()[0]"], tensors["readout_f16()[1]"]))
     nl = t(64, dtype=torch.bfloat16)
     with torch.no_grad():

@@ -6,87 +6,19 @@ The push-time checks and the plan cache need a stream object and no device: `hos
 ClipStream (_allocate, _prepare, _launch) and the plan's workspace replaced by recorders, and `nv` as clip_stream sees it replaced by an object
 that fails the test when any native function is called."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import pytest
 import torch
 
 import cases
-import hicom_amd
 from hicom_amd import clip_stream as cs
 from hicom_amd import native as nv
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("hicom_stream_state_clear_fwd", "hicom_stream_state_fold_fwd", "hicom_compressor_stream_push")
-EINVAL, EUNSUP = -1, -2
-ADDR = 0x7F0000001000
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-        assert getattr(L, name).restype is ctypes.c_int
-    assert "typedef struct hicom_stream_push_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16
-    assert hasattr(hicom_amd.HIComProjector, "open_stream")
-
-
-def test_push_args_layout_matches_the_header_field_for_field(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    names = [n for n, _ in nv.StreamPushArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hicom_hip.h"\nint main(void) {\n'
-                   '    printf("%d %zu", HICOM_ABI_VERSION, sizeof(hicom_stream_push_args));\n'
-                   + "".join(f'    printf(" %zu", offsetof(hicom_stream_push_args, {n}));\n' for n in names)
-                   + '    printf("\\n");\n    return 0;\n}\n')
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    ver, size, *offs = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    assert ver == nv.ABI_VERSION == 16
-    assert size == ctypes.sizeof(nv.StreamPushArgs)
-    assert offs == [getattr(nv.StreamPushArgs, n).offset for n in names]
-    assert names[-1] == "stream"
+from host_util import ADDR, EINVAL, NoNative, module, tokens
+from stream_blocks import SINGLE_REFUSALS as C_REFUSALS, single_push_block as push_block
 
 
 # ---- C refusals: none launches ----------------------------------------------------------------------------------------------------------
-def push_block(**over):
-    a = nv.StreamPushArgs()
-    a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.t0, a.rows, a.hidden, a.nparts = 4, 6, 6, 1152, 4, 3, 0, 9, 64, 1
-    for f in ("ff", "fe", "q_hi", "q_lo", "pos_a", "pe_hi", "pe_lo", "part_m", "part_l", "part_acc", "ctx_f16", "hid_f16", "state_ml_in", "state_acc",
-              "lw0_f16", "lb0", "lw2_f16", "lb2", "out"):
-        setattr(a, f, ADDR)
-    a.state_ml_out = ADDR + 4096
-    a.P, a.y_index0, a.x_index0, a.l_scale, a.out_dt, a.ldo = 28, 16, 22, 0.03, nv.DT_F32, 64
-    for k, v in over.items():
-        setattr(a, k, v)
-    return a
-
-
-C_REFUSALS = {
-    "E = 768": (dict(E=768), EUNSUP, "only 1152"),
-    "13 rows": (dict(rows=13), EUNSUP, "<= 12"),
-    "hidden = 100": (dict(hidden=100), EUNSUP, "multiple of 64"),
-    "Tc % kt": (dict(Tc=6), EUNSUP, "exact window partition"),
-    "window of 72 tokens": (dict(Tc=8, kt=8), EUNSUP, "16 .. 64"),
-    "output dtype": (dict(out_dt=nv.DT_F16), EUNSUP, "output dtype"),
-    "NULL ff": (dict(ff=None), EINVAL, "NULL pointer"),
-    "NULL weight": (dict(lw2_f16=None), EINVAL, "NULL weight"),
-    "pe without pos_a": (dict(pos_a=None), EINVAL, "come together"),
-    "t0 inside a window group": (dict(t0=2), EINVAL, "whole window groups"),
-    "frames past the tables": (dict(t0=16), EINVAL, "outside the positional tables"),
-    "unaligned ff": (dict(ff=ADDR + 8), EINVAL, "16-byte aligned"),
-    "ldo < hidden": (dict(ldo=63), EINVAL, "output layout"),
-    "newline rows without a pointer": (dict(nl_count=2, nl_first=2, nl_step=3), EINVAL, "newline rows"),
-}
 
 
 @pytest.mark.parametrize("name", list(C_REFUSALS))
@@ -110,9 +42,6 @@ def test_c_fold_refusals_in_front_of_any_device_call():
 
 
 # ---- row offsets ----------------------------------------------------------------------------------------------------------------------------
-def module(ptype="local43_global32", use_guide="direct", dtype=torch.bfloat16, **cfg_over):
-    cfg = SimpleNamespace(**{**cases.DEFAULT_CFG, "hidden_size": 64, "mm_projector_type": ptype, "use_guide": use_guide, **cfg_over})
-    return hicom_amd.build_vision_projector(cfg).to(dtype).eval()
 
 
 @pytest.mark.parametrize("pos", ["grid", "frame", "one_token", "no_token"])
@@ -145,17 +74,6 @@ def test_chunk_rows_concatenated_are_the_layout_of_the_whole_clip(pos, has_nl, g
 
 
 # ---- Python refusals and the plan cache without a device -------------------------------------------------------------------------------
-class NoNative:
-    """`nv` as clip_stream sees it during a host test: the constants and classes of the real module; any function call fails the test."""
-
-    def __getattr__(self, name):
-        real = getattr(nv, name)
-        if isinstance(real, type) or not callable(real):
-            return real
-
-        def refuse(*a, **k):
-            pytest.fail(f"native call nv.{name} in a host test")
-        return refuse
 
 
 @pytest.fixture
@@ -170,10 +88,6 @@ def host(monkeypatch):
     monkeypatch.setattr(cs.ClipStream, "_launch", lambda self, plan, ff, fe, t0, row0, nl_group, nl_rows, stream: launches.append((t0, row0, nl_group, nl_rows)))
     monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: SimpleNamespace(cuda_stream=0))
     return launches
-
-
-def tokens(Tc, H=6, W=6, E=cases.D, dtype=torch.bfloat16):
-    return torch.zeros((Tc, H, W, E), dtype=dtype)
 
 
 GUIDE = torch.zeros((cases.D,), dtype=torch.bfloat16)

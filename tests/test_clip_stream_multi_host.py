@@ -7,111 +7,19 @@ As in tests/test_clip_stream_host.py the push-time checks and the plan cache nee
 device methods of ClipStreamMulti (_allocate, _prepare, _build_plan, _launch) replaced by recorders, and `nv` as clip_stream sees it replaced
 by an object that fails the test when any native function is called."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import pytest
 import torch
 
 import cases
-import hicom_amd
 from hicom_amd import clip_stream as cs
 from hicom_amd import native as nv
-from test_clip_stream_host import NoNative, module, tokens
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("hicom_stream_state_fold_set_fwd", "hicom_multi_guide_local_fwd", "hicom_stream_place_rows_fwd", "hicom_compressor_stream_push_multi")
-EINVAL, EUNSUP = -1, -2
-ADDR = 0x7F0000001000
-
-
-def guides(Q, dtype=torch.bfloat16):
-    return torch.zeros((Q, cases.D), dtype=dtype)
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-        assert getattr(L, name).restype is ctypes.c_int
-    assert "typedef struct hicom_stream_push_multi_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16                            # additive: the version stays
-    assert hasattr(hicom_amd.HIComProjector, "open_stream_multi") and hasattr(hicom_amd.HIComProjector, "open_stream")
-
-
-def test_push_multi_args_layout_matches_the_header_field_for_field(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    names = [n for n, _ in nv.StreamPushMultiArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hicom_hip.h"\nint main(void) {\n'
-                   '    printf("%zu", sizeof(hicom_stream_push_multi_args));\n'
-                   + "".join(f'    printf(" %zu", offsetof(hicom_stream_push_multi_args, {n}));\n' for n in names)
-                   + '    printf("\\n");\n    return 0;\n}\n')
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, *offs = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    assert size == ctypes.sizeof(nv.StreamPushMultiArgs)
-    assert offs == [getattr(nv.StreamPushMultiArgs, n).offset for n in names]
-    assert names[-1] == "stream"
-    assert ctypes.sizeof(nv.StreamPushArgs) != size                                 # (the single-guide block is another struct, untouched)
+from host_util import ADDR, EINVAL, EUNSUP, NoNative, module, tokens
+from stream_blocks import MULTI_REFUSALS as C_REFUSALS, guides, multi_push_block as push_block
 
 
 # ---- C refusals: none launches ----------------------------------------------------------------------------------------------------------
-POINTERS = ("ff", "fe", "guide", "q_hi", "q_lo", "pos_a", "pe", "part_m", "part_l", "part_acc", "scores", "scratch", "set_ml", "set_acc", "ctx_f16",
-            "hid_f16", "loc", "state_ml_in", "state_acc", "lw0_f16", "lb0", "lw2_f16", "lb2", "out")
-
-
-def push_block(**over):
-    """A chunk of 4 frames of 6 x 6 for Q = 3 guides at hidden 64: 4 windows, 27 folded rows; tables for 16 frames."""
-    a = nv.StreamPushMultiArgs()
-    a.Q, a.Tc, a.H, a.W, a.E, a.kt, a.ks, a.nh, a.t0, a.hidden, a.nparts, a.marg = 3, 4, 6, 6, 1152, 4, 3, 9, 0, 64, 2, 0
-    for f in POINTERS:
-        setattr(a, f, ADDR)
-    a.state_ml_out = ADDR + 4096
-    a.P, a.y_index0, a.x_index0, a.l_scale, a.out_dt, a.ldo, a.score_stride = 28, 16, 22, 0.03, nv.DT_F32, 64, 144
-    a.q_stride, a.row0 = 64 * 48, 0
-    for k, v in over.items():
-        setattr(a, k, v)
-    return a
-
-
-C_REFUSALS = {
-    "Q = 33": (dict(Q=33), EUNSUP, "1 <= Q <= 32"),
-    "Q = 0": (dict(Q=0), EUNSUP, "1 <= Q <= 32"),
-    "E = 768": (dict(E=768), EUNSUP, "only 1152"),
-    "17 heads": (dict(nh=17), EUNSUP, "<= 16 folded rows"),
-    "hidden = 100": (dict(hidden=100), EUNSUP, "multiple of 64"),
-    "Tc % kt": (dict(Tc=6), EUNSUP, "exact window partition"),
-    "window of 72 tokens": (dict(Tc=8, kt=8), EUNSUP, "<= 64"),
-    "output dtype": (dict(out_dt=nv.DT_F16), EUNSUP, "output dtype"),
-    "more chunks than tiles": (dict(nparts=10), EINVAL, "token chunks"),
-    "NULL ff": (dict(ff=None), EINVAL, "NULL pointer"),
-    "NULL guide": (dict(guide=None), EINVAL, "NULL pointer"),
-    "NULL set": (dict(set_acc=None), EINVAL, "NULL pointer"),
-    "NULL state": (dict(state_acc=None), EINVAL, "NULL pointer"),
-    "NULL weight": (dict(lw2_f16=None), EINVAL, "NULL weight"),
-    "pe without pos_a": (dict(pos_a=None), EINVAL, "come together"),
-    "t0 inside a window group": (dict(t0=2), EINVAL, "whole window groups"),
-    "frames past the tables": (dict(t0=16), EINVAL, "outside the positional tables"),
-    "last frame past the tables": (dict(t0=12, Tc=8), EINVAL, "outside the positional tables"),
-    "x rows past the tables": (dict(P=27), EINVAL, "outside the positional tables"),
-    "unaligned ff": (dict(ff=ADDR + 8), EINVAL, "aligned"),
-    "(M, L) blocks overlap: the same block": (dict(state_ml_out=ADDR), EINVAL, "overlap"),
-    "(M, L) blocks overlap: 27 rows need 216 bytes": (dict(state_ml_out=ADDR + 208), EINVAL, "overlap"),
-    "marginal form without pos-emb": (dict(marg=1, pe=None, pos_a=None), EUNSUP, "no in-kernel marginals"),
-    "short score stride": (dict(score_stride=128), EINVAL, "score_stride"),
-    "ldo < hidden": (dict(ldo=63), EINVAL, "output layout"),
-    "guides closer than their rows": (dict(row0=46), EINVAL, "output layout"),
-    "newline rows without a pointer": (dict(nl_group=2, nl_count=2, nl_first=2, nl_step=3, newline=None), EINVAL, "newline rows"),
-    "newline rows off the packing": (dict(nl_group=2, nl_count=2, nl_first=1, nl_step=3, newline=ADDR), EINVAL, "newline rows"),
-}
 
 
 @pytest.mark.parametrize("name", list(C_REFUSALS))

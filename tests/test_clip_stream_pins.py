@@ -21,14 +21,12 @@ import torch
 
 import cases
 import hicom_amd
-import test_clip_stream_adapt_host as adapt
-import test_clip_stream_host as single
-import test_clip_stream_multi_host as multi
 from hicom_amd import clip_stream as cs
 from hicom_amd import engine, multi_guide, native as nv, prepared, prepared_many, ragged_multi_guide
 from hicom_amd import segments as seg
+from host_util import ADDR, module, tokens
+from stream_blocks import ADAPTKV, adapt, multi, single
 
-ADDR = 0x7F0000001000                # a made-up address, 4096-byte aligned
 
 
 # ---- refusals in front of the first launch -----------------------------------------------------------------------------------------------
@@ -257,13 +255,13 @@ def recorded(monkeypatch, kind):
         self.cur = 0
     monkeypatch.setattr(base, "_allocate", allocate)
     monkeypatch.setattr(base, "_prepare", prepare)
-    m = single.module("local43_global32" if kind != "adapt" else adapt.ADAPTKV, mm_newline_position="grid")
+    m = module("local43_global32" if kind != "adapt" else ADAPTKV, mm_newline_position="grid")
     lc = m.local_compressor
     w0h, w2h = t(4), t(4)
     monkeypatch.setattr(type(lc), "readout_f16", lambda self: (w0h, w2h))
     nl = t(64, dtype=torch.bfloat16)
     guide = t(cases.D, dtype=torch.bfloat16) if kind == "single" else t(3, cases.D, dtype=torch.bfloat16)
-    ff, fe = single.tokens(4), single.tokens(4)
+    ff, fe = tokens(4), tokens(4)
     with torch.no_grad():
         s = getattr(m, {"single": "open_stream", "multi": "open_stream_multi", "adapt": "open_stream_adapt"}[kind])(guide, 6, 6, 16, nl)
         s.device = "cpu"
@@ -384,7 +382,7 @@ def test_invalidate_plans_drops_every_store_cached_plan_was_handed(monkeypatch):
                  if "STORE" in k and isinstance(v, str)]
     assert {cs.STORE, cs.STORE_MULTI, cs.STORE_ADAPT, "_prepared_many_plans", "_prepare_plans"} <= set(constants) and len(constants) == 8
     stores = ["_a_store_no_list_names", "_engine_plans", "_batch_plans", "_ragged_plans"] + constants
-    m = single.module()
+    m = module()
     for store in stores:
         plan = engine.cached_plan(m, store, "k", Fake)
         assert m.__dict__[store] == {"k": plan}                       # the stores stay where they were

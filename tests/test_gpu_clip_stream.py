@@ -24,7 +24,7 @@ import pytest
 import torch
 
 import clip_stream_inputs as ci
-from global_stream_inputs import EPS23, TRANS
+from clip_stream_inputs import fold_ref
 from gpu_util import build_module, dev_bf16
 from hicom_amd import native as nv
 
@@ -57,24 +57,6 @@ def fold_inputs(nparts, carried, seed):
         L = rng.uniform(1.0, 40.0, R).astype(np.float32)
         A = rng.normal(0.0, 5.0, (R, E)).astype(np.float32)
     return pm, pl, pacc, M, L, A
-
-
-def fold_ref(pm, pl, pacc, M, L, A):
-    """float64 (M', L', ACC') and the bounds of L' and ACC' (module docstring)."""
-    R = M.shape[0]
-    nparts = pm.shape[0]
-    m = np.concatenate([M[None].astype(np.float64), pm[:, :R].astype(np.float64)])            # [1 + nparts, R]
-    l = np.concatenate([L[None].astype(np.float64), pl[:, :R].astype(np.float64)])
-    a = np.concatenate([A[None].astype(np.float64), pacc[:, :R].astype(np.float64)])          # [1 + nparts, R, E]
-    Mn = m.max(axis=0)
-    with np.errstate(invalid="ignore"):
-        w = np.where(np.isinf(m), 0.0, np.exp(m - Mn))
-        arg = np.where(np.isinf(m), 0.0, np.abs(m - Mn))
-    rel = (nparts + 8) * EPS23 + 2 * TRANS
-    Ln, An = (w * l).sum(0), (w[..., None] * a).sum(0)
-    l_tol = rel * (w * np.abs(l)).sum(0) + (w * EPS23 * arg * np.abs(l)).sum(0)
-    a_tol = rel * (w[..., None] * np.abs(a)).sum(0) + ((w * EPS23 * arg)[..., None] * np.abs(a)).sum(0)
-    return Mn, Ln, An, l_tol, a_tol
 
 
 @pytest.mark.parametrize("nparts", [1, 3, 7])

@@ -29,10 +29,9 @@ import clip_stream_group_adapt_inputs as gi
 import multi_window_inputs as mw
 import ops_reference as R
 import window_attn_inputs as wi
-from gpu_util import build_module, dev_bf16
+from gpu_util import DEV, build_module, check, dev_bf16, guarded, ptr, stream
 from hicom_amd import native as nv
 from ops_reference import up
-from test_gpu_multi_window import DEV, check, guarded, ptr, stream
 
 pytestmark = pytest.mark.gpu
 

@@ -24,9 +24,10 @@ import pytest
 import torch
 
 import clip_stream_group_multi_inputs as mi
-from gpu_util import build_module, dev_bf16
+from clip_stream_group_inputs import E, H, ITEMS, N, NSLOTS, P, R, SLOTS, T0S, TC, W, X0, Y0, merge_fold_ref
+from gpu_util import build_module, check_table_region, dev_bf16
 from hicom_amd import native as nv
-from test_gpu_clip_stream_group import E, H, ITEMS, N, NSLOTS, P, R, SLOTS, T0S, TC, W, X0, Y0, merge_fold_ref
+from stream_blocks import group_multi_push_block
 
 pytestmark = pytest.mark.gpu
 
@@ -327,7 +328,5 @@ TABLE_REGION = ([0, 144, 4, 0, 4, 0, 2, 0, 4, 0, 0, 4, 0, 0, 0, 0, 144, 288, 8, 
 
 
 def test_prepare_writes_the_parents_table_region():
-    from test_clip_stream_group_multi_host import push_block
-    from test_gpu_clip_stream_group import check_table_region
     assert len(TABLE_REGION) == 256
-    check_table_region(push_block(), nv.compressor_stream_group_multi_workspace, nv.compressor_stream_group_multi_prepare, TABLE_REGION)
+    check_table_region(group_multi_push_block(), nv.compressor_stream_group_multi_workspace, nv.compressor_stream_group_multi_prepare, TABLE_REGION)

@@ -24,10 +24,10 @@ import torch
 
 import clip_stream_inputs as ci
 import clip_stream_multi_inputs as cm
+from clip_stream_inputs import fold_ref
 from gpu_util import build_module, dev_bf16
 from hicom_amd import clip_stream as cs
 from hicom_amd import native as nv
-from test_gpu_clip_stream import fold_ref
 
 pytestmark = pytest.mark.gpu
 

@@ -12,23 +12,12 @@ import torch
 
 import make_golden_head as mh
 import ops_reference as R
+from gpu_util import SiglipHead as _Head
 from hicom_amd import native as nv
 from oracle import hicom_oracle as orc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class _Head(torch.nn.Module):
-    """Stand-in with the attribute names of HF's SiglipMultiheadAttentionPoolingHead that encoder.py:284-285 touches."""
-    def __init__(self, sd):
-        super().__init__()
-        D, I = mh.D, mh.INTER
-        self.layernorm = torch.nn.LayerNorm(D, eps=1e-6)
-        self.mlp = torch.nn.Module()
-        self.mlp.fc1 = torch.nn.Linear(D, I)
-        self.mlp.fc2 = torch.nn.Linear(I, D)
-        self.load_state_dict({k[len("head."):]: torch.from_numpy(v.copy()) for k, v in sd.items()})
 
 
 @pytest.fixture(scope="module")

@@ -43,48 +43,16 @@ import torch
 import cases
 import multi_window_inputs as mw
 import ops_reference as R
-import window_attn_inputs as wi
-from gpu_util import build_module
+from gpu_util import DEV, build_module, check, guarded, ptr, stream
 from hicom_amd import native as nv
 from hicom_amd import synth
-from ops_reference import up
 from oracle import hicom_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
-DEV = "cuda"
 D = mw.D
 EINVAL, EUNSUP = -1, -2
-
-
-def check(name, got, ref, tol):
-    """|got - ref| <= tol elementwise (float64 on the CPU); the figures are printed first."""
-    got, ref, tol = up(got), ref.double(), tol.double()
-    assert got.shape == ref.shape == tol.shape, (name, got.shape, ref.shape, tol.shape)
-    assert bool(torch.isfinite(got).all()), f"{name}: non-finite values in the result"
-    err = (got - ref).abs()
-    ratio = err / tol.clamp_min(1e-300)
-    i = int(ratio.argmax())
-    print(f"MULTI_WINDOW {name} err={float(err.max()):.3e} bound={float(tol.reshape(-1)[i]):.3e} ratio={float(ratio.reshape(-1)[i]):.3e}")
-    assert bool((err <= tol).all()), f"{name}: error {float(err.reshape(-1)[i]):.3e} over its bound {float(tol.reshape(-1)[i]):.3e}"
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def guarded(t):
-    """t [rows, D] as an interior view of a device buffer with a NaN row in front and behind (2304 bytes: 16-byte aligned); None stays."""
-    if t is None:
-        return None
-    v = wi.guard_rows(t, DEV)
-    assert v.data_ptr() % 16 == 0
-    return v
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def out_planes(Q, NW):

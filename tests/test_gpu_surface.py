@@ -133,7 +133,7 @@ def test_guide_injector_forward(name, mode, shape, vis_dtype):
 def test_c4_chain_head_compressor_splice_matches_oracle_chain():
     import make_golden_head as mh
     from hicom_amd import prepare_inputs_labels_for_multimodal, siglip_head_embed, synth
-    from test_gpu_head import _Head
+    from gpu_util import SiglipHead as _Head
     T, HID, S, V = 32, 3584, 2048, 4096
     head_sd = mh.head_state_dict()
     head = _Head(head_sd).to(torch.bfloat16).cuda().eval()

@@ -8,21 +8,14 @@ As in tests/test_seg_host_pins.py: with chunks > 0 the workspace function and ev
 code, pointer fields are made-up aligned addresses that nothing reads before a launch, and every *_fwd case breaks one rule, so none
 launches."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
 from hicom_amd import native as nv
+from host_util import ADDR, EINVAL, EUNSUP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDR = 0x7F0000001000                # a made-up address, 4096-byte aligned
-EINVAL, EUNSUP = -1, -2
 POINTERS = ("ff", "fe", "guide", "out", "newline", "lw0_f16", "lb0", "lw2_f16", "lb2", "wq", "bq", "wk", "wv", "bv", "wo", "bo", "gw0", "gb0", "gw2", "gb2",
             "pe", "kpe")
-SYMBOLS = ("hicom_compressor_multiguide_fwd", "hicom_compressor_multiguide_workspace_bytes")
 
 
 def block(fwd=False, **over):
@@ -44,48 +37,6 @@ def block(fwd=False, **over):
 def call(fn, a):
     r = getattr(nv.lib(), f"hicom_compressor_multiguide_{fn}")(None if a is None else ctypes.byref(a))
     return int(r), nv.lib().hicom_last_error().decode()
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-    assert L.hicom_compressor_multiguide_fwd.restype is ctypes.c_int
-    assert L.hicom_compressor_multiguide_workspace_bytes.restype is ctypes.c_int64
-    assert "typedef struct hicom_compressor_multiguide_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16
-
-
-SRC = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "hicom_hip.h"
-int main(void) {
-    printf("%d %zu %zu %zu %zu\n", HICOM_ABI_VERSION, sizeof(hicom_compressor_multiguide_args), offsetof(hicom_compressor_multiguide_args, Q),
-           offsetof(hicom_compressor_multiguide_args, nl_first), offsetof(hicom_compressor_multiguide_args, stream));
-    return 0;
-}
-"""
-
-
-def test_args_layout_matches_the_header(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    src = tmp_path / "abi.c"
-    src.write_text(SRC)
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    ver, size, off_q, off_nl, off_stream = (int(v) for v in subprocess.check_output([str(exe)]).split())
-    A = nv.CompressorMultiGuideArgs
-    assert ver == nv.ABI_VERSION == 16
-    assert size == ctypes.sizeof(A)
-    assert off_q == A.Q.offset
-    assert off_nl == A.nl_first.offset
-    assert off_stream == A.stream.offset and A._fields_[-1][0] == "stream"          # the last field
-    assert not hasattr(A, "B")
 
 
 def _up(n):

@@ -207,7 +207,7 @@ def test_window_index_and_sequential_sum():
 # ---- hicom_fused_stream_fwd / hicom_query_prep_fwd: the references of tests/test_gpu_fused_ring.py ---------------------------
 from types import SimpleNamespace
 
-import test_gpu_fused_ring as G                                          # (its inputs, limits and tolerances need no GPU)
+import fused_ring_inputs as G                                            # (the inputs, limits and tolerances of tests/test_gpu_fused_ring.py)
 
 
 def _small_ring(seed, rows=3, with_pos=True):

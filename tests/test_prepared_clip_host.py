@@ -7,77 +7,18 @@ As in tests/test_multi_guide_host.py: with chunks > 0 the workspace functions an
 code, pointer fields are made-up aligned addresses that nothing reads before a launch, and every *_fwd case breaks one rule, so none
 launches."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
-from types import SimpleNamespace
 
 import pytest
 import torch
 
 import cases
-import hicom_amd
+import host_util
 from hicom_amd import native as nv
+from host_util import ADDR, EINVAL, EUNSUP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ADDR = 0x7F0000001000                # a made-up address, 4096-byte aligned
-EINVAL, EUNSUP = -1, -2
-NEW = ("hicom_clip_adapt_prepare_workspace_bytes", "hicom_clip_adapt_prepare_fwd", "hicom_compressor_multiguide_adapt_workspace_bytes",
-       "hicom_compressor_multiguide_adapt_fwd")
 POINTERS = ("ff", "fe", "guide", "out", "newline", "lw0_f16", "lb0", "lw2_f16", "lb2", "wq", "bq", "wk", "wv", "bv", "wo", "bo", "gw0", "gb0", "gw2", "gb2",
             "pe", "kpe")
 STORES = ("_prepared_plans", "_prepare_plans", "_multi_guide_plans")
-
-
-def test_symbols_are_declared_listed_and_bound():
-    header = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", header))
-    L = nv.lib()
-    for name in NEW:
-        assert name in declared and name in nv.EXPORTS and hasattr(L, name)
-    assert L.hicom_compressor_multiguide_adapt_workspace_bytes.restype is ctypes.c_int64
-    assert L.hicom_clip_adapt_prepare_workspace_bytes.restype is ctypes.c_int64
-    assert L.hicom_compressor_multiguide_adapt_fwd.restype is ctypes.c_int and L.hicom_clip_adapt_prepare_fwd.restype is ctypes.c_int
-    assert len(L.hicom_compressor_multiguide_adapt_fwd.argtypes) == 1 and len(L.hicom_clip_adapt_prepare_fwd.argtypes) == 11
-    assert len(L.hicom_clip_adapt_prepare_workspace_bytes.argtypes) == 4
-    assert "typedef struct hicom_compressor_multiguide_adapt_args" in header
-    assert nv.ABI_VERSION == L.hicom_abi_version() == 16
-
-
-FIELDS = ("base", "ak", "av", "ky", "vy", "alpha_dt", "eps")
-SRC = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "hicom_hip.h"
-#define A hicom_compressor_multiguide_adapt_args
-int main(void) {
-    A a;
-    printf("%d %zu %zu %zu\n", HICOM_ABI_VERSION, sizeof(hicom_compressor_multiguide_args), sizeof(hicom_seg_adaptor), sizeof(A));
-    printf("%zu %zu %zu %zu %zu %zu %zu\n", offsetof(A, base), offsetof(A, ak), offsetof(A, av), offsetof(A, ky), offsetof(A, vy), offsetof(A, alpha_dt),
-           offsetof(A, eps));
-    printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(a.base), sizeof(a.ak), sizeof(a.av), sizeof(a.ky), sizeof(a.vy), sizeof(a.alpha_dt), sizeof(a.eps));
-    return 0;
-}
-"""
-
-
-def test_args_layout_matches_the_ctypes_mirror_field_for_field(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    src, exe = tmp_path / "abi.c", tmp_path / "abi"
-    src.write_text(SRC)
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    head, offsets, sizes = ([int(v) for v in line.split()] for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    A = nv.CompressorMultiGuideAdaptArgs
-    assert head == [16, ctypes.sizeof(nv.CompressorMultiGuideArgs), ctypes.sizeof(nv.SegAdaptor), ctypes.sizeof(A)]
-    assert tuple(n for n, _ in A._fields_) == FIELDS
-    assert offsets == [getattr(A, f).offset for f in FIELDS]
-    assert sizes == [getattr(A, f).size for f in FIELDS]
-    assert A.base.offset == 0 and A.ak.offset == ctypes.sizeof(nv.CompressorMultiGuideArgs)        # the plain block first, untouched
-    z = A()
-    assert z.ky is None and z.vy is None and z.ak.w0 is None and z.av.w0 is None                  # a zeroed block adapts neither stream
 
 
 def block(fwd=False, ky=ADDR, vy=ADDR, **over):
@@ -200,8 +141,7 @@ def test_prepare_refusals_in_front_of_any_device_call():
 
 # ---- Python refusals that need no device ------------------------------------------------------------------------------------------------
 def module(ptype="local43_adaptkv_global32", use_guide="direct", dtype=torch.bfloat16):
-    cfg = SimpleNamespace(**{**cases.DEFAULT_CFG, "hidden_size": 896, "mm_projector_type": ptype, "use_guide": use_guide})
-    return hicom_amd.build_vision_projector(cfg).to(dtype).eval()
+    return host_util.module(ptype, use_guide, dtype, hidden_size=896)
 
 
 def no_plans(m):

@@ -7,79 +7,21 @@ As in tests/test_ragged_multi_guide_host.py: with chunks > 0 the workspace funct
 host code, pointer fields are made-up aligned addresses that nothing reads before a launch, and every *_fwd / *_prepare case breaks one
 rule, so none launches or copies."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
-from types import SimpleNamespace
 
 import pytest
 import torch
 
 import cases
-import hicom_amd
+import host_util
 from hicom_amd import native as nv
 from hicom_amd import prepared, prepared_many
-from hicom_amd.projector import HIComProjector
+from host_util import ADDR, EINVAL, EUNSUP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-ADDR = 0x7F0000001000                # a made-up address, 4096-byte aligned
-EINVAL, EUNSUP = -1, -2
-NEW = ("hicom_compressor_clips_multiguide_workspace_bytes", "hicom_compressor_clips_multiguide_prepare", "hicom_compressor_clips_multiguide_fwd")
 POINTERS = ("guide", "out", "newline", "lw0_f16", "lb0", "lw2_f16", "lb2", "wq", "bq", "wk", "wv", "bv", "wo", "bo", "gw0", "gb0", "gw2", "gb2", "pe", "kpe")
 STORE = "_prepared_many_plans"
 IMAGE, CLIP4, CLIP8 = (1, 1, 0, 0, 0, 1, 32), (4, 4, 0, 0, 0, 1, 32), (8, 4, 0, 0, 0, 1, 32)
 MIX6 = ([IMAGE, CLIP4, IMAGE, CLIP8, IMAGE], (1, 3, 5, 2, 4), 6)
 MIX9 = ([IMAGE, CLIP4], (4, 8), 9)
-
-
-def test_symbols_are_declared_listed_and_bound():
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", HEADER))
-    raw = ctypes.CDLL(nv.LIB_PATH)
-    for name in NEW:
-        assert name in declared and name in nv.EXPORTS and hasattr(raw, name)
-        assert len(getattr(nv.lib(), name).argtypes) == 1
-    assert nv.lib().hicom_compressor_clips_multiguide_workspace_bytes.restype is ctypes.c_int64
-    assert nv.lib().hicom_compressor_clips_multiguide_fwd.restype is ctypes.c_int
-    assert nv.lib().hicom_compressor_clips_multiguide_prepare.restype is ctypes.c_int
-    assert "typedef struct hicom_compressor_clips_multiguide_args" in HEADER
-    assert nv.ABI_VERSION == nv.lib().hicom_abi_version() == 16 and "#define HICOM_ABI_VERSION 16" in HEADER
-    assert callable(getattr(HIComProjector, "forward_prepared_many"))
-
-
-FIELDS = ("base", "ak", "av", "alpha_dt", "eps", "item_ptrs")
-SRC = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "hicom_hip.h"
-#define A hicom_compressor_clips_multiguide_args
-int main(void) {
-    A a;
-    printf("%d %zu %zu %zu\n", HICOM_ABI_VERSION, sizeof(hicom_compressor_ragged_multiguide_args), sizeof(hicom_seg_adaptor), sizeof(A));
-    printf("%zu %zu %zu %zu %zu %zu\n", offsetof(A, base), offsetof(A, ak), offsetof(A, av), offsetof(A, alpha_dt), offsetof(A, eps), offsetof(A, item_ptrs));
-    printf("%zu %zu %zu %zu %zu %zu\n", sizeof(a.base), sizeof(a.ak), sizeof(a.av), sizeof(a.alpha_dt), sizeof(a.eps), sizeof(a.item_ptrs));
-    return 0;
-}
-"""
-
-
-def test_args_layout_matches_the_ctypes_mirror_field_for_field(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    src, exe = tmp_path / "abi.c", tmp_path / "abi"
-    src.write_text(SRC)
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    head, offsets, sizes = ([int(v) for v in line.split()] for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    A = nv.CompressorClipsMultiGuideArgs
-    assert head == [16, ctypes.sizeof(nv.CompressorRaggedMultiGuideArgs), ctypes.sizeof(nv.SegAdaptor), ctypes.sizeof(A)]
-    assert tuple(n for n, _ in A._fields_) == FIELDS
-    assert offsets == [getattr(A, f).offset for f in FIELDS]
-    assert sizes == [getattr(A, f).size for f in FIELDS]
-    assert A.base.offset == 0 and A.ak.offset == ctypes.sizeof(nv.CompressorRaggedMultiGuideArgs)        # the base block first, untouched
-    z = A()
-    assert z.item_ptrs is None and z.ak.w0 is None and z.av.w0 is None and z.base.ff is None              # a zeroed block: the plain recipe
 
 
 def block(mix=MIX6, fwd=False, adapt=(True, True), item_ptrs=ADDR, **over):
@@ -189,8 +131,7 @@ def test_a_limit_of_the_kernels_is_not_implemented_error_under_the_python_name()
 
 # ---- Python refusals that need no device ------------------------------------------------------------------------------------------------
 def module(ptype="local43_adaptkv_global32", use_guide="direct", dtype=torch.bfloat16):
-    cfg = SimpleNamespace(**{**cases.DEFAULT_CFG, "hidden_size": 896, "mm_projector_type": ptype, "use_guide": use_guide})
-    return hicom_amd.build_vision_projector(cfg).to(dtype).eval()
+    return host_util.module(ptype, use_guide, dtype, hidden_size=896)
 
 
 def cpu_clip(m, T=4, h=6, w=6, fe=True, modal="video", planes=(True, True)):

@@ -7,10 +7,6 @@ code, pointer fields are made-up aligned addresses that nothing reads before a l
 none launches or copies."""
 import ctypes
 import hashlib
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import pytest
@@ -21,13 +17,8 @@ import hicom_amd
 from hicom_amd import native as nv
 from hicom_amd import ragged
 from hicom_amd import ragged_multi_guide as rmg
-from hicom_amd.projector import HIComProjector
+from host_util import ADDR, EINVAL, EUNSUP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "hicom_hip.h")).read()
-ADDR = 0x7F0000001000                # a made-up address, 4096-byte aligned
-EINVAL, EUNSUP = -1, -2
-SYMBOLS = ("hicom_compressor_ragged_multiguide_workspace_bytes", "hicom_compressor_ragged_multiguide_prepare", "hicom_compressor_ragged_multiguide_fwd")
 N_CUS = 256
 IMAGE, CLIP4, CLIP8 = (1, 1, 0, 0, 0, 1, 32), (4, 4, 0, 0, 0, 1, 32), (8, 4, 0, 0, 0, 1, 32)
 MIX6 = [IMAGE, CLIP4, IMAGE, CLIP8, IMAGE]
@@ -49,53 +40,6 @@ def block(items=MIX6, counts=(1, 3, 5, 2, 4), n_counts=None, **over):
 def call(fn, a):
     r = getattr(nv.lib(), f"hicom_compressor_ragged_multiguide_{fn}")(None if a is None else ctypes.byref(a))
     return int(r), nv.lib().hicom_last_error().decode()
-
-
-def test_symbols_are_declared_listed_and_bound():
-    declared = set(re.findall(r"\b(hicom_[a-z0-9_]+)\s*\(", HEADER))
-    raw = ctypes.CDLL(nv.LIB_PATH)
-    for name in SYMBOLS:
-        assert name in declared and name in nv.EXPORTS and hasattr(raw, name)
-        assert len(getattr(nv.lib(), name).argtypes) == 1
-    assert nv.lib().hicom_compressor_ragged_multiguide_workspace_bytes.restype is ctypes.c_int64
-    assert nv.lib().hicom_compressor_ragged_multiguide_fwd.restype is ctypes.c_int
-    assert nv.lib().hicom_compressor_ragged_multiguide_prepare.restype is ctypes.c_int
-    assert nv.ABI_VERSION == nv.lib().hicom_abi_version() == 16 and "#define HICOM_ABI_VERSION 16" in HEADER
-    assert callable(getattr(HIComProjector, "forward_ragged_multi_guide"))
-
-
-SRC = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "hicom_hip.h"
-#define A hicom_compressor_ragged_multiguide_args
-int main(void) {
-    printf("%d %zu %zu %zu\n", HICOM_ABI_VERSION, sizeof(A), sizeof(hicom_ragged_item), sizeof(hicom_compressor_ragged_args));
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", offsetof(A, B), offsetof(A, items), offsetof(A, guide_counts), offsetof(A, n_guide_counts),
-           offsetof(A, lw0_f16), offsetof(A, ldo), offsetof(A, ws_bytes), offsetof(A, stream));
-    return 0;
-}
-"""
-
-
-def test_args_layout_matches_the_header(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no host C compiler")
-    src = tmp_path / "abi.c"
-    src.write_text(SRC)
-    exe = tmp_path / "abi"
-    subprocess.check_call([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    head, offs = ([int(v) for v in line.split()] for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    A = nv.CompressorRaggedMultiGuideArgs
-    assert head == [16, ctypes.sizeof(A), 28, ctypes.sizeof(nv.CompressorRaggedArgs)]           # hicom_ragged_item stays 28 bytes
-    assert ctypes.sizeof(A) == ctypes.sizeof(nv.CompressorRaggedArgs) + 16
-    assert offs == [f.offset for f in (A.B, A.items, A.guide_counts, A.n_guide_counts, A.lw0_f16, A.ldo, A.ws_bytes, A.stream)]
-    assert A._fields_[-1][0] == "stream"
-    # every field of the ragged block, in its order, with the guide counts behind `items`
-    names = [n for n, _ in A._fields_]
-    assert [n for n in names if n not in ("guide_counts", "n_guide_counts", "reserved_")] == [n for n, _ in nv.CompressorRaggedArgs._fields_]
-    assert names[names.index("items") + 1:names.index("items") + 4] == ["guide_counts", "n_guide_counts", "reserved_"]
 
 
 # ---- workspace --------------------------------------------------------------------------------------------------------------------------
