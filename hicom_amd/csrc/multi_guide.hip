@@ -20,6 +20,10 @@
 // once, into planes the caller keeps; hicom_compressor_multiguide_adapt_fwd is the sequence above with launch 3 replaced by
 // multi_guide_local_adapt_kernel, which blends LayerNorm of those planes into the rows it loads.  Same launch count, same workspace.
 // hicom_multi_guide_local_adapt_fwd is that launch alone, for a clip stream's chunk.
+//
+// Logits form: hicom_compressor_multiguide_logits_fwd is the plain sequence with launch 3 replaced by
+// multi_guide_local_logits_kernel, which takes the local logits of every guide precomputed (hicom_head_scores_multi_fwd) and reads the
+// value rows only.  Same launch count, same workspace; frames_embed is not read.  hicom_multi_guide_local_logits_fwd is that launch alone.
 #include "multi_window.hpp"
 #include "segment_host.hpp"
 
@@ -55,6 +59,19 @@ __global__ __launch_bounds__(256) void multi_guide_local_adapt_kernel(const uint
     multi_window_guides_adapt_ctx16<NV, kAdaptGuideGroup>(key, value, ad, guide, 0, Q, g, lane, scale, ctx16 + (long)win * D, (long)nwin * D);
 }
 
+// The same grid and wave -> window map with the local logits given (multi_window.hpp: multi_window_guides_logits_ctx16; logits f32
+// [Q][tokens], guide q's plane q_stride floats behind guide 0's).  No key row is read.
+template <int NV>
+__global__ __launch_bounds__(256) void multi_guide_local_logits_kernel(const uint16_t* value, const float* logits, long q_stride, hicom_axis at, hicom_axis ay,
+                                                                       hicom_axis ax, int Q, int nwin, float scale, _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const WindowGeom g(at, ay, ax, win);
+    multi_window_guides_logits_ctx16<NV>(value, logits, q_stride, Q, g, lane, scale, ctx16 + (long)win * D, (long)nwin * D);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Placement of every guide's packed rows (segment_item.hpp: place_equal_row, item = guide): grid = Q * item_rows, one output row per
 // workgroup.
@@ -87,6 +104,19 @@ void launch_local_adapt(const uint16_t* key, const uint16_t* value, const uint16
     HICOM_LAUNCH(multi_guide_local_adapt_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, (hipStream_t)stream, key, value, guide, ad, at, ay, ax, Q,
                  nwin, scale, ctx16);
 }
+
+// the same grid with the local logits given (the logits step's launch 3 and hicom_multi_guide_local_logits_fwd)
+void launch_local_logits(const uint16_t* value, const float* logits, long q_stride, hicom_axis at, hicom_axis ay, hicom_axis ax, int Q, int nwin, float scale,
+                         _Float16* ctx16, void* stream) {
+    HICOM_LAUNCH(multi_guide_local_logits_kernel<3>, dim3((unsigned)((nwin + 3) / 4)), dim3(256), 0, (hipStream_t)stream, value, logits, q_stride, at, ay, ax,
+                 Q, nwin, scale, ctx16);
+}
+
+// the local logits of the logits step: f32 [Q][T H W], guide q's plane q_stride floats behind guide 0's; p NULL: the keyed forms
+struct LocalLogits {
+    const float* p;
+    long q_stride;
+};
 
 // token chunks of the global stream
 int mg_chunks(const Args* a, long N, int rows_pad) {
@@ -150,6 +180,7 @@ struct GuideItems {
     const MgLayout& l;
     bool marg;              // in-kernel positional marginals (clips), the logit tensor otherwise
     const SegAdaptParams* prepared;     // the adaptor recipe on a clip's prepared planes (hicom_compressor_multiguide_adapt_fwd), NULL: plain
+    LocalLogits logits;                 // the logits form (hicom_compressor_multiguide_logits_fwd): no key row is read
     char* ws() const { return (char*)a->ws; }
     float* f32(long off) const { return (float*)(ws() + off); }
     float* pos_a() const { return a->pe ? f32(l.s.pos_a) : nullptr; }
@@ -157,7 +188,9 @@ struct GuideItems {
     int local(const uint16_t* key_x, const SegAdaptParams*) const {
         const hicom_axis at{a->T, a->kt, a->T / a->kt, a->T / a->kt};
         const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
-        if (prepared)
+        if (logits.p)
+            launch_local_logits((const uint16_t*)a->ff, logits.p, logits.q_stride, at, ay, ax, a->Q, l.wpi, a->l_scale, (_Float16*)(ws() + l.s.ctx16), a->stream);
+        else if (prepared)
             launch_local_adapt(key_x, (const uint16_t*)a->ff, (const uint16_t*)a->guide, *prepared, at, ay, ax, a->Q, l.wpi, a->l_scale,
                                (_Float16*)(ws() + l.s.ctx16), a->stream);
         else
@@ -189,8 +222,8 @@ struct GuideItems {
 };
 
 // prepared: the local stage's adaptor parameters with the caller's planes, NULL for the plain recipe.  seg_step runs as for the plain recipe
-// (no adaptor MLP, no adaptor region in the workspace): only the local hook differs.
-int mg_fwd(const Args* a, const SegAdaptParams* prepared = nullptr) {
+// (no adaptor MLP, no adaptor region in the workspace): only the local hook differs.  logits: the logits form, likewise.
+int mg_fwd(const Args* a, const SegAdaptParams* prepared = nullptr, LocalLogits logits = LocalLogits{nullptr, 0}) {
     int st = mg_check(a);
     if (st != HICOM_OK) return st;
     const MgLayout l = mg_layout(a);
@@ -199,7 +232,7 @@ int mg_fwd(const Args* a, const SegAdaptParams* prepared = nullptr) {
     st = seg_check_equal_rows(kWho, a, l.wpi);
     if (st != HICOM_OK) return st;
     const bool marg = a->pe && hicom_global_stream_has_marg(l.N, a->E, l.rows_pad, a->H, a->W, l.nparts) == 1;
-    return seg_step(a, nullptr, l.s, GuideItems{a, l, marg, prepared});
+    return seg_step(a, nullptr, l.s, GuideItems{a, l, marg, prepared, logits});
 }
 
 // ---- the k / v adaptor recipe on prepared planes ------------------------------------------------------------------------------------------
@@ -276,6 +309,24 @@ extern "C" int hicom_multi_guide_local_fwd(const void* key, const void* value, c
     return seg_check_launch("multi_guide_local", "local stage");
 }
 
+extern "C" int hicom_multi_guide_local_logits_fwd(const void* value, const float* logits, int64_t q_stride, hicom_axis at, hicom_axis ay, hicom_axis ax,
+                                                  int32_t Q, int32_t nwin, float scale, void* ctx_f16, void* stream) {
+    const char* who = "multi_guide_local_logits";
+    HICOM_REQUIRE(value && logits && ctx_f16, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE(Q >= 1 && Q <= kMaxGuides, HICOM_EUNSUP, "%s: Q=%d guides (1 <= Q <= %d per call)", who, Q, kMaxGuides);
+    for (const hicom_axis* x : {&at, &ay, &ax})
+        HICOM_REQUIRE(x->n > 0 && x->k > 0 && x->nwin > 0 && x->nwin * x->k == x->n && x->nfull == x->nwin, HICOM_EUNSUP,
+                      "%s: needs an exact window partition (an axis of %d in %d windows of %d)", who, x->n, x->nwin, x->k);
+    HICOM_REQUIRE(ay.k == ax.k && at.k * ay.k * ax.k <= 64, HICOM_EUNSUP, "%s: square spatial windows of <= 64 tokens (%dx%dx%d)", who, at.k, ay.k, ax.k);
+    const long N = (long)at.n * ay.n * ax.n;
+    HICOM_REQUIRE(nwin == (long)at.nwin * ay.nwin * ax.nwin, HICOM_EINVAL, "%s: nwin=%d for a grid of %dx%dx%d windows", who, nwin, at.nwin, ay.nwin, ax.nwin);
+    HICOM_REQUIRE(N < (1L << 31) / 16 && (long)nwin * Q < (1L << 31) / 16, HICOM_EUNSUP, "%s: too many tokens in one call", who);
+    HICOM_REQUIRE(Q == 1 || q_stride >= N, HICOM_EINVAL, "%s: q_stride=%ld floats between the guides' planes of %ld tokens", who, (long)q_stride, N);
+    HICOM_REQUIRE((uintptr_t)value % 16 == 0 && (uintptr_t)logits % 4 == 0 && (uintptr_t)ctx_f16 % 16 == 0, HICOM_EINVAL, "%s: aligned inputs", who);
+    launch_local_logits((const uint16_t*)value, logits, q_stride, at, ay, ax, Q, nwin, scale, (_Float16*)ctx_f16, stream);
+    return seg_check_launch(who, "local stage");
+}
+
 // segment_host.hpp declares the two *_args_check functions: the checks of an entry point without its launches
 int hicom_host::multi_guide_local_adapt_args_check(const void* key, const void* value, const void* guide, const void* ky, const void* vy,
                                                    const hicom_seg_adaptor* ak, const hicom_seg_adaptor* av, int alpha_dt, int Q, int T, int H, int W, int E,
@@ -304,6 +355,15 @@ extern "C" int64_t hicom_compressor_multiguide_workspace_bytes(const hicom_compr
 }
 
 extern "C" int hicom_compressor_multiguide_fwd(const hicom_compressor_multiguide_args* a) { return mg_fwd(a); }
+
+// The logits form: a->fe is not read (the workspace and its size function are the plain entry point's).
+extern "C" int hicom_compressor_multiguide_logits_fwd(const hicom_compressor_multiguide_args* a, const float* local_logits, int64_t q_stride) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", kWho);
+    HICOM_REQUIRE(local_logits && (uintptr_t)local_logits % 4 == 0, HICOM_EINVAL, "%s: local_logits is f32 [Q][T H W]", kWho);
+    HICOM_REQUIRE(a->Q <= 1 || q_stride >= (int64_t)a->T * a->H * a->W, HICOM_EINVAL, "%s: q_stride=%ld floats between the guides' logit planes", kWho,
+                  (long)q_stride);
+    return mg_fwd(a, nullptr, LocalLogits{local_logits, (long)q_stride});
+}
 
 // The planes are the caller's: the workspace is the plain entry point's for the same arguments.
 extern "C" int64_t hicom_compressor_multiguide_adapt_workspace_bytes(const hicom_compressor_multiguide_adapt_args* a) {

@@ -80,6 +80,60 @@ __device__ __forceinline__ void multi_window_guides_ctx16(const uint16_t* key, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The logits form: the raw dot products key_n . guide_q come precomputed, logits f32 [Q][tokens] with guide q's
+// plane q_stride floats behind guide 0's (hicom_head_scores_multi_fwd writes them).  No key row is read and there is no dot product
+// over the channels: lane i of the wave fetches the logit of the window's token i, `scale` and the softmax follow as in
+// multi_window_ctx16, and every value row of the window is loaded once per group of NG guides into NG accumulators.  lrows: the
+// group's first logit plane.
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <int NV, int NG>
+__device__ __forceinline__ void multi_window_logits_ctx16(const uint16_t* value, const float* lrows, long q_stride, const WindowGeom& g, int lane,
+                                                          float scale, _Float16* o, long plane) {
+    constexpr int D = NV * 384;
+    const long mine = g.token_of(lane < g.WIN ? lane : 0);
+    float pw[NG];
+#pragma unroll
+    for (int u = 0; u < NG; ++u) {
+        const float sc = lane < g.WIN ? lrows[(long)u * q_stride + mine] * scale : -3.0e38f;
+        const float mx = wave_max_fast(sc);
+        const float e = lane < g.WIN ? expf(sc - mx) : 0.f;
+        pw[u] = e / wave_sum_fast(e);
+    }
+    float acc[NG][NV][6];
+#pragma unroll
+    for (int u = 0; u < NG; ++u) row_zero<NV>(acc[u]);
+    for (int i = 0; i < g.WIN; ++i) {
+        float v[NV][6];
+        load_row<NV>(value + g.token_of(i) * D, lane, v);
+#pragma unroll
+        for (int u = 0; u < NG; ++u) row_axpy<NV>(__shfl(pw[u], i, 64), v, acc[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < NG; ++u)
+#pragma unroll
+        for (int s = 0; s < NV; ++s)
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                o[(long)u * plane + 384 * s + 6 * lane + j] = (_Float16)fminf(fmaxf(acc[u][s][j], -65504.f), 65504.f);
+}
+
+// All Q guides of one window in groups of kGuideGroup, as multi_window_guides_ctx16 walks them; logits: guide q0's plane.
+template <int NV>
+__device__ __forceinline__ void multi_window_guides_logits_ctx16(const uint16_t* value, const float* logits, long q_stride, int Q, const WindowGeom& g,
+                                                                 int lane, float scale, _Float16* o, long plane) {
+    for (int g0 = 0; g0 < Q; g0 += kGuideGroup) {
+        const float* l = logits + (long)g0 * q_stride;
+        _Float16* og = o + (long)g0 * plane;
+        switch (Q - g0 < kGuideGroup ? Q - g0 : kGuideGroup) {
+            case 1: multi_window_logits_ctx16<NV, 1>(value, l, q_stride, g, lane, scale, og, plane); break;
+            case 2: multi_window_logits_ctx16<NV, 2>(value, l, q_stride, g, lane, scale, og, plane); break;
+            case 3: multi_window_logits_ctx16<NV, 3>(value, l, q_stride, g, lane, scale, og, plane); break;
+            default: multi_window_logits_ctx16<NV, 4>(value, l, q_stride, g, lane, scale, og, plane); break;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // The same for the k / v adaptor recipe on PREPARED planes (multi_guide.hip: multi_guide_local_adapt_kernel): the window of
 // local_window_adapt_ctx16 (segment_item.hpp) for NG guides in one walk.  ky / vy are the y = MLP(x) planes a clip keeps
 // (hicom_clip_adapt_prepare_fwd); either may be NULL (that stream is not adapted and takes blend_dot's plain path), not both.

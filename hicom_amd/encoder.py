@@ -192,11 +192,35 @@ def siglip_head_scores(last_hidden_state: torch.Tensor, head, guide_embed: torch
     return (logits, out) if return_embed else logits
 
 
-def _head_chain(last_hidden_state, head, hidden_act, out_dtype, guide, want_embed, keep=None):
+def siglip_head_scores_multi(last_hidden_state: torch.Tensor, head, guide_embeds: torch.Tensor, hidden_act: str = None) -> torch.Tensor:
+    """[..., D] bf16 tokens, guides [Q, D] bf16 (1 <= Q <= 32) -> fp32 [Q, ...] raw local logits  guide_q . (x_n + head.mlp(head.layernorm(x_n)))
+    in front of the 1/sqrt(D) scale (the convention of siglip_head_scores), for `HIComProjector.forward_multi_guide(frames_feature, None,
+    guide_embeds, modal, local_logits=...)`.  The score is linear in frames_embed, so the second head GEMM is not run: with
+    U_q = fc2.weight^T guide_q and c_q = guide_q . fc2.bias the logits are  guide_q . x_n + U_q . hid_n + c_q  from ONE pass over x and the
+    hidden layer for all guides (csrc/head_scores.hip).  U is made from the live bf16 weight on every call (it depends on
+    the guides): no weight-derived cache beyond fc1's fp16 copy (_head_cache).  Inference only."""
+    from .multi_guide import count_guides
     from .projector import _require_bf16_cuda
     x = last_hidden_state
     _require_bf16_cuda("last_hidden_state", x)
-    if guide is not None and torch.is_grad_enabled() and any(p.requires_grad for p in _head_params(head)):
+    Q = count_guides("siglip_head_scores_multi", guide_embeds, x.shape[-1])
+    _require_bf16_cuda("guide_embeds", guide_embeds)
+    nv.begin_inference()
+    x2, hid, kpad, _ = _head_hidden(x, head, hidden_act, True)
+    fc2 = head.mlp.fc2
+    guides = guide_embeds.contiguous()
+    u_hi, u_lo, u_scale, c = nv.head_guide_fold(fc2.weight.detach().contiguous(), fc2.bias.detach(), guides, nv.head_fold_ldu(kpad))
+    logits = torch.empty((Q, x2.shape[0]), dtype=torch.float32, device=x.device)
+    nv.head_scores_multi(x2, hid, kpad, guides, u_hi, u_lo, u_scale, c, logits)
+    return logits.view((Q,) + tuple(x.shape[:-1]))
+
+
+def _head_hidden(x, head, hidden_act, scores, keep=None):
+    """The first half of the head: checks, LayerNorm -> fp16, fc1 + activation -> the fp16 hidden plane [M, ld], zero from column inter to
+    kpad.  Returns (x as [M, D], hid, kpad, fc2's fp16 weight copy).  scores: the caller builds no autograd graph."""
+    from .projector import _require_bf16_cuda
+    _require_bf16_cuda("last_hidden_state", x)
+    if scores and torch.is_grad_enabled() and any(p.requires_grad for p in _head_params(head)):
         raise RuntimeError("siglip_head_scores builds no autograd graph (inference path): call it under torch.no_grad(); "
                            "siglip_head_embed is the differentiable form")
     ln, fc1, fc2 = head.layernorm, head.mlp.fc1, head.mlp.fc2
@@ -217,6 +241,14 @@ def _head_chain(last_hidden_state, head, hidden_act, out_dtype, guide, want_embe
     if keep is not None and fc1.weight.shape[0] % 8 == 0:              # training forward: fc1's value before the activation as well
         pre = keep["h1"] = torch.empty((M, ld), dtype=torch.float16, device=x.device)
     nv.dense16_gemm(a16, w1, fc1.bias.detach(), act=_ACTS[hidden_act], out_f16=hid, n_store=kpad, pre_f16=pre)
+    return x2, hid, kpad, w2
+
+
+def _head_chain(last_hidden_state, head, hidden_act, out_dtype, guide, want_embed, keep=None):
+    x = last_hidden_state
+    x2, hid, kpad, w2 = _head_hidden(x, head, hidden_act, guide is not None, keep)
+    M, D = x2.shape
+    fc2 = head.mlp.fc2
     out = torch.empty((M, D), dtype=out_dtype or x.dtype, device=x.device) if want_embed else None
     parts = torch.empty(((D + 63) // 64, M), dtype=torch.float32, device=x.device) if guide is not None else None
     nv.dense16_gemm(hid, w2, fc2.bias.detach(), N=D, K=kpad, y=out, res=x2, row_dot=(guide, parts) if guide is not None else None)

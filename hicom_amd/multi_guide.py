@@ -4,7 +4,11 @@ The reference's Video-MME driver asks every question of a video with its own pro
 (hicom/eval/video/inference_video_mcqa_videomme.py:268-303).  The guide is only the query of the two stages, so here the visual tokens
 are streamed once for all Q guides: the local stage loads each window row once per group of guides, the global stage runs the 9 Q folded
 rows through the many-row stream kernel of the guide-off recipe.  Scope rule, input checks, plan and plan cache are segments.py's, shared
-with forward_batch and forward_ragged; the plain release recipe only.  Plans are keyed by shape, Q included."""
+with forward_batch and forward_ragged; the plain release recipe only.  Plans are keyed by shape, Q included.
+
+Logits form: with `local_logits` = fp32 [Q, T, H, W] from `siglip_head_scores_multi` the local stage takes its scores
+from that tensor and reads the value rows only (hicom_compressor_multiguide_logits_fwd: the same sequence, another launch 3); frames_embed
+is None, as for forward(..., local_logits=).  The two forms do not share a plan: the key carries the form."""
 from __future__ import annotations
 
 import torch
@@ -45,15 +49,47 @@ def _scope(proj, ff, fe, guides, modal, nl):
     return clip_scope(what, "multi-guide", proj, ff, fe, guides, modal, nl)
 
 
-def run_multi_guide(proj, ff, fe, guides, modal, nl, chunks=None):
+def _require_f32_cuda(name, t):
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: float32 expected, got {t.dtype} (siglip_head_scores_multi returns it)")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: a device tensor expected (got {t.device})")
+
+
+def check_logits(what, ll, fe, Q, grid):
+    """The checks of local_logits behind the scope checks of the keyed call and in front of any device work: frames_embed must be None
+    (forward(..., local_logits=) has the same rule), fp32 device [Q, T, H, W]."""
+    if fe is not None:
+        raise ValueError(f"{what}: local_logits replaces frames_embed: pass frames_embed=None")
+    if not isinstance(ll, torch.Tensor) or ll.ndim != 4 or tuple(ll.shape[1:]) != tuple(grid):
+        raise ValueError(f"{what}: local_logits is [Q, T, H, W] = [{Q}, {', '.join(map(str, grid))}], one plane of raw dot products per guide "
+                         f"(got {tuple(ll.shape) if isinstance(ll, torch.Tensor) else None})")
+    if ll.shape[0] != Q:
+        raise ValueError(f"{what}: local_logits holds {ll.shape[0]} guides, guide_embeds {Q}")
+    _require_f32_cuda("local_logits", ll)
+
+
+def plan_key(Q, T, H, W, E, has_fe, modal, nl, out_dtype, stream, chunks, logits=False):
+    """The key of a plan; the keyed form's is what it was before the logits form (so its plans and their order in the store do not change)."""
+    key = (Q, T, H, W, E, has_fe, modal, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0))
+    return key + ("logits",) if logits else key
+
+
+def run_multi_guide(proj, ff, fe, guides, modal, nl, chunks=None, local_logits=None):
     Q, T, H, W, E, tiles = _scope(proj, ff, fe, guides, modal, nl)
+    if local_logits is not None:
+        check_logits("forward_multi_guide", local_logits, fe, Q, (T, H, W))
     dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, "forward_multi_guide", ff, fe, guides, nl)
-    key = (Q, T, H, W, E, fe is not None, modal, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0))
+    key = plan_key(Q, T, H, W, E, fe is not None, modal, nl, out_dtype, stream, chunks, local_logits is not None)
     plan = seg.cached_plan(proj, STORE, key, lambda: seg.build_equal_plan(
         proj, "forward_multi_guide", nv.CompressorMultiGuideArgs, None, "Q", (Q, T, H, W, E), tiles, modal, nl, out_dtype, chunks, dev,
         nv.compressor_multiguide_workspace))                                         # (no adaptor recipe: _scope refuses it)
     a = plan.io
     out = torch.empty((Q, plan.rows, plan.hidden), dtype=out_dtype, device=dev)
     seg.patch_io(a, ff, fe, guides, nl if a.nl_count > 0 else None, out, stream)
-    nv.compressor_multiguide_fwd(plan.args)
+    if local_logits is not None:
+        ll = local_logits.contiguous()
+        nv.compressor_multiguide_logits_fwd(plan.args, ll.data_ptr(), T * H * W)
+    else:
+        nv.compressor_multiguide_fwd(plan.args)
     return out

@@ -416,6 +416,10 @@ SIGNATURES = {
     "hicom_compressor_stream_group_adapt_push": (C.c_int, [C.POINTER(StreamGroupAdaptPushArgs)]),
     "hicom_stream_group_local_adapt_fwd": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(SegAdaptor), C.POINTER(SegAdaptor), i32, f32, i32, i32, i32, i32,
                                                      i32, i32, i32, i32, f32, C.POINTER(i32), i32, vp, vp]),
+    "hicom_head_guide_fold_fwd": (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "hicom_head_scores_multi_fwd": (C.c_int, [vp, vp, i64, i64, i32, i32, vp, vp, vp, i64, vp, vp, i32, vp, i64, vp]),
+    "hicom_multi_guide_local_logits_fwd": (C.c_int, [vp, vp, i64, Axis, Axis, Axis, i32, i32, f32, vp, vp]),
+    "hicom_compressor_multiguide_logits_fwd": (C.c_int, [C.POINTER(CompressorMultiGuideArgs), vp, i64]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -814,6 +818,51 @@ def compressor_multiguide_workspace(args) -> int:
 
 def compressor_multiguide_fwd(args):
     _seg_call(args, "multiguide", "fwd")
+
+
+def compressor_multiguide_logits_fwd(args: CompressorMultiGuideArgs, local_logits: int, q_stride: int):
+    """The plain multi-guide step with the local logits given (address of f32 [Q][q_stride]); args.fe is not read."""
+    _check(lib().hicom_compressor_multiguide_logits_fwd(C.byref(args), local_logits, q_stride), "hicom_compressor_multiguide_logits_fwd")
+
+
+def multi_guide_local_logits(value: int, logits: int, q_stride: int, at: Axis, ay: Axis, ax: Axis, Q: int, nwin: int, scale: float, ctx_f16: int,
+                             stream: int):
+    """Addresses in, one launch out: the local stage of the logits step alone (hicom_multi_guide_local_logits_fwd), fp16 contexts
+    [Q][nwin][1152]."""
+    _check(lib().hicom_multi_guide_local_logits_fwd(value, logits, q_stride, at, ay, ax, Q, nwin, scale, ctx_f16, stream),
+           "hicom_multi_guide_local_logits_fwd")
+
+
+HEAD_FOLD_SLICES = 16       # slices of D in hicom_head_guide_fold_fwd: its workspace holds 16 Q ldu floats
+
+
+def head_fold_ldu(kpad: int) -> int:
+    """Row pitch of the U planes hicom_head_scores_multi_fwd reads: kpad rounded up to its 128-channel blocks."""
+    return (kpad + 127) // 128 * 128
+
+
+def head_guide_fold(w2, b2, guides, ldu: int):
+    """U = W2^T g_q as an fp16 hi + lo pair at a power of two per row, and c = g_q . b2 (hicom_head_guide_fold_fwd): w2 bf16 [D, inter],
+    b2 bf16 [D] or None, guides bf16 [Q, D].  Returns (u_hi, u_lo fp16 [Qpad, ldu], u_scale, c f32 [Qpad])."""
+    D, inter = w2.shape
+    Q = guides.shape[0]
+    qpad = (Q + 15) // 16 * 16
+    dev = guides.device
+    u = torch.empty((2, qpad, ldu), dtype=torch.float16, device=dev)
+    sc = torch.empty((2, qpad), dtype=torch.float32, device=dev)
+    ws = torch.empty((HEAD_FOLD_SLICES * Q * ldu,), dtype=torch.float32, device=dev)
+    _check(lib().hicom_head_guide_fold_fwd(_ptr(w2), _ptr(b2), D, inter, _ptr(guides), Q, _ptr(u[0]), _ptr(u[1]), ldu, _ptr(sc[0]), _ptr(sc[1]), _ptr(ws),
+                                           ws.numel() * 4, _stream()), "hicom_head_guide_fold_fwd")
+    return u[0], u[1], sc[0], sc[1]
+
+
+def head_scores_multi(x2, hid, kpad: int, guides, u_hi, u_lo, u_scale, c, logits):
+    """logits f32 [Q, M] = the raw local logits of every guide (hicom_head_scores_multi_fwd): x2 bf16 [M, D], hid fp16 [M, ld], the planes of
+    head_guide_fold."""
+    M, D = x2.shape
+    Q = guides.shape[0]
+    _check(lib().hicom_head_scores_multi_fwd(_ptr(x2), _ptr(hid), hid.shape[1], M, D, kpad, _ptr(guides), _ptr(u_hi), _ptr(u_lo), u_hi.shape[1], _ptr(u_scale),
+                                             _ptr(c), Q, _ptr(logits), logits.shape[1], _stream()), "hicom_head_scores_multi_fwd")
 
 
 def clip_adapt_prepare_workspace(N: int, E: int, ak: SegAdaptor, av: SegAdaptor, what: str = "prepare_clip") -> int:

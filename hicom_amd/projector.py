@@ -1110,7 +1110,7 @@ class HIComProjector(nn.Module):
         from . import ragged
         return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
 
-    def forward_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None):
+    def forward_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None, local_logits=None):
         """ONE image or clip, Q instructions in one native call: frames_feature / frames_embed bf16 [T, H, W, E] as for forward()
         (frames_embed may be None), guide_embeds bf16 [Q, E], 1 <= Q <= 32 -- the questions a Video-MME style loop asks about one video
         (reference inference_video_mcqa_videomme.py:268-303).  Returns [Q, rows, hidden]; out[q] is laid out as forward(frames_feature,
@@ -1123,9 +1123,12 @@ class HIComProjector(nn.Module):
         `chunks`: token chunks of the global stream (None: the stream kernel's own choice).
         Which path when (DESIGN.md §3.8, 27 x 27 grid): the crossover against a loop of forward() is Q = 3 -- 230 against 226 us on a
         64-frame clip, 133 against 136 us on 8 frames.  One or two guides belong to forward() (Q = 1: 178 against 77 us, the step is a
-        thirteen-launch sequence); from four guides up this call wins, 1.2 x at Q = 6 and 1.75 x at Q = 16 on 64 frames."""
+        thirteen-launch sequence); from four guides up this call wins, 1.2 x at Q = 6 and 1.75 x at Q = 16 on 64 frames.
+        `local_logits` = fp32 [Q, T, H, W] raw dot products frames_embed_n . guide_q from `hicom_amd.siglip_head_scores_multi`, passed
+        with frames_embed=None (the rule of forward(..., local_logits=)): the local stage then reads frames_feature and Q floats per
+        token, frames_embed is never made, and the head's second GEMM is not run.  The global rows do not change."""
         from . import multi_guide
-        return multi_guide.run_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
+        return multi_guide.run_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks, local_logits)
 
     def prepare_clip(self, frames_feature, frames_embed, modal):
         """Once per video: the guide-independent work of the k / v adaptor recipe.  frames_feature / frames_embed bf16 [T, H, W, E] as for

@@ -1508,6 +1508,38 @@ int hicom_stream_group_local_adapt_fwd(const void* key, const void* value, const
                                        int32_t Q, int32_t Tc, int32_t H, int32_t W, int32_t E, int32_t kt, int32_t ks, float scale,
                                        const int32_t* pair0, int32_t M, void* ctx_f16, void* stream);
 
+/* ---- multi-guide step without frames_embed: the local logits of Q guides from the SigLIP head's hidden layer -----------
+ * frames_embed = x + fc2(hid) + b2 enters the plain release recipe only through g_q . frames_embed[n], which is linear in it:
+ *     g_q . frames_embed[n] = g_q . x[n] + U[q] . hid[n] + c[q],     U[q] = W2^T g_q,  c[q] = g_q . b2.
+ * The second head GEMM is not run and frames_embed is never written (csrc/head_scores.hip).
+ *
+ * hicom_head_guide_fold_fwd (two launches): w2 bf16 [D][inter] (fc2.weight), b2 bf16 [D] or NULL, guides bf16 [Q][D], 1 <= Q <= 32,
+ * D <= 2048.  U in fp32, split into an fp16 pair at a power of two per row: u_hi + u_lo = U[q] 2^s with max |U[q]| 2^s in [2^14, 2^15),
+ * fp16 [Qpad][ldu], Qpad = Q rounded up to 16, zero from column inter on and in the rows behind Q; u_scale [Qpad] = 2^-s, c [Qpad].
+ * ldu >= inter, a multiple of 8 (hicom_head_scores_multi_fwd wants kpad rounded up to 128).  ws: 16 Q ldu floats, nothing to zero.
+ *
+ * hicom_head_scores_multi_fwd (one launch): x bf16 [M][D], hid fp16 [M][ld] of which columns [0, kpad) are read (the fp16 hidden plane
+ * hicom_dense16_gemm_fwd stores with n_store = kpad: zero from column inter on; the pitch gap behind kpad is never read), the planes of
+ * the fold.  logits[q q_stride + n] = g_q . x[n] + 2^-s (u_hi + u_lo)[q] . hid[n] + c[q] for q < Q, n < M, fp32 accumulation: the raw
+ * dot products in front of the 1 / sqrt(D) scale.  D % 128 == 0, kpad % 64 == 0, ld % 8 == 0, any M. */
+int hicom_head_guide_fold_fwd(const void* w2, const void* b2, int32_t D, int32_t inter, const void* guides, int32_t Q, void* u_hi, void* u_lo,
+                              int64_t ldu, float* u_scale, float* c, void* ws, int64_t ws_bytes, void* stream);
+int hicom_head_scores_multi_fwd(const void* x, const void* hid, int64_t ld, int64_t M, int32_t D, int32_t kpad, const void* guides,
+                                const void* u_hi, const void* u_lo, int64_t ldu, const float* u_scale, const float* c, int32_t Q, float* logits,
+                                int64_t q_stride, void* stream);
+
+/* The local stage of the multi-guide step with the logits given: value bf16 [T, H, W, 1152], logits f32, guide q's [T H W] plane q_stride
+ * floats behind guide 0's; at / ay / ax describe an exact window partition (n = nwin k, nfull = nwin) with square spatial windows of at most
+ * 64 tokens, nwin = their product.  Per window and guide: softmax(scale logits) over the window's tokens, every value row loaded once per
+ * group of guides; fp16 contexts ctx_f16 [Q][nwin][1152] as hicom_multi_guide_local_fwd writes them.  No key row is read.
+ *
+ * hicom_compressor_multiguide_logits_fwd is hicom_compressor_multiguide_fwd with that launch as its local stage: the same launch count,
+ * the same workspace (hicom_compressor_multiguide_workspace_bytes); args->fe is not read and may be NULL.  local_logits f32 [Q][q_stride],
+ * q_stride >= T H W. */
+int hicom_multi_guide_local_logits_fwd(const void* value, const float* logits, int64_t q_stride, hicom_axis at, hicom_axis ay, hicom_axis ax,
+                                       int32_t Q, int32_t nwin, float scale, void* ctx_f16, void* stream);
+int hicom_compressor_multiguide_logits_fwd(const hicom_compressor_multiguide_args* args, const float* local_logits, int64_t q_stride);
+
 #ifdef __cplusplus
 }
 #endif
