@@ -6,7 +6,8 @@
 //     guide row of item w / windows_per_item (batch_local_attn_kernel, batch_local_attn_adapt_kernel: one wave per window);
 //   * global stage: batch_global_stream_kernel with blockIdx.y = item.  A workgroup walks a contiguous range of 16-token tiles of ONE
 //     item (chunk blockIdx.x of `chunks`), so a partial state (m, l, ACC) never mixes tokens of two items; batch_merge_kernel merges the
-//     chunks of each (item, head) row;
+//     chunks of each (item, head) row.  The stream itself is stream_segment (stream_body.hpp): the one body of the four-wave machine,
+//     the same text hicom_global_stream_fwd's narrow kernel runs; this file holds only the wrapper that finds the item;
 //   * placement: batch_place_kernel, output row / item_rows = item;
 //   * the chunk policy (B x chunks fills the chip twice over) and the checks of the one item shape and its packed-row layout.
 #include "segment_host.hpp"
@@ -43,8 +44,8 @@ __global__ __launch_bounds__(256) void batch_local_attn_adapt_kernel(const uint1
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Segmented global stream: grid = (chunks, B), workgroup (part, item) walks chunk `part` of the item's tiles (segment_item.hpp:
-// stream_segment).
+// Segmented global stream: grid = (chunks, B), workgroup (part, item) walks chunk `part` of the item's tiles (stream_body.hpp:
+// stream_segment, one row group, row0 = 0, every row of the item).
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct BatchStreamParams {
     SegStreamParams c;

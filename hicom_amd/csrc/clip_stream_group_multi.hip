@@ -4,7 +4,7 @@
 // (forward_ragged_multi_guide's convention).  One push is six launches whatever B, the Q_s and the mix of chunk lengths are:
 //    1  gm_local_kernel: one wave per window of the STACKED tensor, the wave walks the guides of the item's SLOT in groups of kGuideGroup
 //       (multi_window.hpp: multi_window_guides_ctx16), fp16 contexts pair-major within the call as in rmg_local_kernel
-//    2  gm_stream_kernel: stream_segment<9, 2> (segment_item.hpp), 32 densely packed folded rows of ONE item per workgroup, the frame rows of
+//    2  gm_stream_kernel: stream_segment<9, 2> (stream_body.hpp), 32 densely packed folded rows of ONE item per workgroup, the frame rows of
 //       the score-side table at the item's absolute offset, the query rows from pair0_slot nh
 //    3  gm_merge_fold_kernel: merge_fold_row (merge_fold.hpp) per (item, folded row R < nh Q_item), IN PLACE into state row pair0_slot nh + R
 //  4-5  the readout GEMM pair over all pairs' window contexts

@@ -2,28 +2,16 @@
 //
 // Replaces MultiheadAttention.forward (reference projector.py:166-228) as used by
 // GlobalCompressor.forward (:634-646).  k_proj / v_proj are folded into the queries on the
-// host side of the ABI (hicom_fold_query_fwd), so this kernel consumes the RAW bf16 tokens:
-//     S[r, n]   = qt[r, :] . x[n, :]  (+ separable positional terms a_t + a_y + a_x)
-//     ACC[r, :] = sum_n exp(S[r, n] - m_r) x[n, :]          (online softmax, fp32)
-// and never materialises K, V or x + pos.  x is read from HBM exactly once per row group.
+// host side of the ABI (hicom_fold_query_fwd), so the kernels consume the RAW bf16 tokens and
+// never materialise K, V or x + pos.  x is read from HBM exactly once per row group.
 //
-// CDNA4 mapping
-//   * workgroup = 4 waves, 2 workgroups per CU (80 KiB LDS, <=256 VGPR each); a workgroup walks
-//     a contiguous range of 16-token tiles with running (m, l, ACC) in registers.
-//   * tile staging: global_load_lds_dwordx4 (LDS-DMA, 1 KiB per wave instruction, whole 256-B
-//     row segments) into a double-buffered [E/128][16 rows][256 B] image with the
-//     chunk ^ rot(row) swizzle, so that BOTH the row read (ds_read_b128: B operand of the
-//     score MFMA) and the transposed read (ds_read_b64_tr_b16: B operand of the P.x MFMA)
-//     of the same image are bank-conflict free / 2-way.
-//   * scores: v_mfma_f32_16x16x32_bf16, A = folded queries as bf16 hi + lo pairs (two MFMAs
-//     into one accumulator -> fp32-grade logits), each wave contracts its own E/4 channel
-//     slice and the four partial 16x16 tiles are summed through LDS.
-//   * softmax fused at wavefront level: lane (row, token-quad) owns 4 logits, row max / row sum
-//     are two cross-lane shuffles; P is split hi/lo and is already in A-fragment order.
-//   * P.x: v_mfma_f32_16x16x16_bf16, each wave owns E/4 output channels (72 accumulator VGPRs).
+// Who holds what: the narrow (four-wave, one-row-group) machine is stream_segment in stream_body.hpp -- the CDNA4 mapping is
+// described there -- and global_stream_kernel below only derives a workgroup's tile range and row group from blockIdx for it; the
+// many-item steps call the same body from their own kernels.  This file holds the wide (many-row) machine, the wide / narrow choice
+// and the C entry points of the single-item stream, forward and backward.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "stream_body.hpp"
 
 namespace hicom {
 
@@ -44,11 +32,11 @@ struct StreamParams {
     int rows_pad;
     int rows;      // rows < rows_pad that carry real queries; padded rows are never stored
     int ntiles;
-    // backward mode (global_stream_kernel<NB, true>): softmax state and scores of the forward pass
+    // backward mode (StreamMode::Bwd, global_stream_wide_kernel<NB, true>): softmax state and scores of the forward pass
     const float* s_in;     // [rows_pad][score_stride] raw logits S written by the forward pass
     const float* ml;       // [rows][2] (M, L) of the forward softmax
     const float* delta;    // [rows] dctx_r . ctx_r
-    // clip-scale variant (forward): logit = (qt . x + pos + row_const[r]) * inv_norm[n]
+    // clip-scale variant (StreamMode::FwdClip): logit = (qt . x + pos + row_const[r]) * inv_norm[n]
     const float* inv_norm; // [N] or NULL
     const float* row_const;// [rows_pad] or NULL
     // wide forward only: un-normalised positional marginals of the softmax weights of each token chunk, relative to the chunk's
@@ -58,246 +46,17 @@ struct StreamParams {
     int marg_stride;
 };
 
-// bit rotation of the row index used as the 16-byte-chunk swizzle (bijective on 0..15)
-__device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-// token-quad permutation: MFMA k-group g <-> tile rows 4*sig(g)..4*sig(g)+3, so that the two
-// 4-row blocks a 32-lane half reads with ds_read_b64_tr_b16 sit 8 rows apart (conflict-free)
-__device__ __forceinline__ int sig(int g) { return ((g & 1) << 1) | (g >> 1); }
-
-// BWD = false: forward (above).  BWD = true: attention backward over the same stream (reference autograd through
-// projector.py:197-215): the "queries" are the upstream gradients dctx_r of the per-head contexts, so the MFMA score
-// tile is dP[r, n] = dctx_r . (x_n + pos_n); with the forward's logits S and softmax state (M, L) the lane forms
-//     dS[r, n] = exp(S[r, n] - M_r) / L_r * (dP[r, n] - delta_r),      delta_r = dctx_r . ctx_r
-// writes it to `scores` (the positional marginals are taken from it afterwards) and accumulates
-//     ACC[r, :] += dS[r, n] x[n, :]        ( = the x part of d q~_r )
-// through the same hi/lo P.x MFMAs.  No running max: the state is known.
-template <int NB, bool BWD = false>
+// The narrow form: workgroup (part, rg) of the grid (nparts, rows_pad / 16) runs stream_segment with one row group over its share of
+// the clip's tiles, for rows 16 rg .. 16 rg + 15 of the one "item" the call has; partial state [part][rows_pad] = slot part *
+// rows_pad / 16 + rg.  Rows >= p.rows are masked by the body.
+template <int NB, StreamMode MODE = StreamMode::Fwd>
 __global__ __launch_bounds__(256, 2) void global_stream_kernel(StreamParams p) {
-    constexpr int E = NB * 128;
-    constexpr int SLICE = E / 4;          // channels owned by one wave
-    constexpr int KSTEPS = SLICE / 32;    // score MFMAs (K = 32 channels) per wave per pass
-    constexpr int CBLK = SLICE / 16;      // 16-channel output blocks per wave
-    constexpr int TILE_BYTES = NB * 4096;
-    constexpr int PIECES = NB * 4;        // 1 KiB LDS-DMA pieces per tile
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* tilebuf = smem;                                           // [2][TILE_BYTES]
-    float* red = reinterpret_cast<float*>(smem + 2 * TILE_BYTES);  // [4 waves][16 rows][16 tokens]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, kg = lane >> 4;
     const int part = blockIdx.x, rg = blockIdx.y, nparts = gridDim.x;
     const int tb = (int)(((long)p.ntiles * part) / nparts);
     const int te = (int)(((long)p.ntiles * (part + 1)) / nparts);
-    const long row_glob = (long)rg * 16 + r16;
-
-    // ---- A operand: folded queries, this wave's channel slice, hi and lo parts ----------------
-    bf16x8 ahi[KSTEPS], alo[KSTEPS];
-    {
-        const long off = row_glob * E + SLICE * wave + 8 * kg;
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            ahi[s] = *reinterpret_cast<const bf16x8*>(p.qhi + off + 32 * s);
-            alo[s] = *reinterpret_cast<const bf16x8*>(p.qlo + off + 32 * s);
-        }
-    }
-
-    f32x4 acc[CBLK];
-#pragma unroll
-    for (int cb = 0; cb < CBLK; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -1.0e30f, l_run = 0.f;   // online-softmax state of row r16 (replicated over kg, waves)
-
-    // ---- LDS-DMA staging of one 16-token tile ------------------------------------------------
-    auto stage = [&](int tile, int buf) {
-        const int r = lane >> 4, cpos = lane & 15;
-        static_assert(PIECES % 4 == 0, "pieces are dealt round-robin to the 4 waves");
-#pragma unroll
-        for (int i = 0; i < PIECES / 4; ++i) {
-            const int pi = wave + 4 * i;
-            const int blk = pi >> 2, row = 4 * (pi & 3) + r;
-            long tok = (long)tile * 16 + row;
-            tok = tok < p.N ? tok : p.N - 1;   // tail tile: re-read a valid row (masked later)
-            const char* src = reinterpret_cast<const char*>(p.x) + tok * (long)(E * 2) + blk * 256 +
-                              16 * (cpos ^ swz(row));
-            char* dst = tilebuf + buf * TILE_BYTES + pi * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),
-                                             (__attribute__((address_space(3))) void*)(dst), 16, 0, 0);
-        }
-    };
-
-    // per-lane LDS byte offsets inside a tile image
-    const int q4 = (lane >> 2) & 3, pp = lane & 3;
-    const int trow = 4 * sig(kg) + q4;                // row this lane addresses in transposed reads
-    const int rd_row_off = r16 * 256, rd_swz = swz(r16);
-    const int tr_row_off = trow * 256 + 8 * (pp & 1), tr_swz = swz(trow);
-    const float* pa = p.pos_a ? p.pos_a + row_glob * p.pos_stride : nullptr;
-
-    // positional logit terms are fetched ONE TILE AHEAD: vmcnt retires in order, so consuming an
-    // ordinary load issued after the LDS-DMA of the next tile would drain that prefetch.
-    float pt[4] = {0.f, 0.f, 0.f, 0.f}, py[4] = {0.f, 0.f, 0.f, 0.f}, px[4] = {0.f, 0.f, 0.f, 0.f};
-    auto fetch_pos = [&](int tile) {
-        if (pa) {
-            const long nb = (long)tile * 16 + 4 * sig(kg);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                long n = nb + j;
-                n = n < p.N ? n : p.N - 1;
-                const unsigned un = (unsigned)n;
-                const unsigned t = un / (unsigned)p.HW, rem = un - t * (unsigned)p.HW;
-                const unsigned y = rem / (unsigned)p.W, xx = rem - y * (unsigned)p.W;
-                pt[j] = pa[p.t0i + t];
-                py[j] = pa[p.y0i + y];
-                px[j] = pa[p.x0i + xx];
-            }
-        }
-    };
-
-    // backward: the forward's logits of (row r16, tokens 4*sig(kg)..+3), fetched one tile ahead like the positional terms
-    f32x4 s_next = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bw_m = 0.f, bw_linv = 0.f, bw_delta = 0.f;
-    const float crow = (!BWD && p.row_const) ? p.row_const[row_glob] : 0.f;
-    auto fetch_s = [&](int tile) {
-        if constexpr (BWD) {
-            s_next = *reinterpret_cast<const f32x4*>(p.s_in + row_glob * p.score_stride + (long)tile * 16 + 4 * sig(kg));
-        } else if (p.inv_norm) {        // per-token key norms of this lane's 4 tokens (tail tile: clamped, masked later)
-            const long nb = (long)tile * 16 + 4 * sig(kg);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s_next[j] = p.inv_norm[nb + j < p.N ? nb + j : p.N - 1];
-        }
-    };
-    if constexpr (BWD) {
-        if (row_glob < p.rows) {
-            bw_m = p.ml[2 * row_glob];
-            bw_linv = 1.0f / p.ml[2 * row_glob + 1];
-            bw_delta = p.delta[row_glob];
-        }
-    }
-
-    if (tb < te) {
-        fetch_pos(tb);
-        fetch_s(tb);
-        stage(tb, 0);
-    }
-
-    for (int tile = tb; tile < te; ++tile) {
-        const int cur = (tile - tb) & 1;
-        // [A] every wave's LDS-DMA pieces of tile `tile` have landed (explicit drain: hipcc does
-        //     not order LDS-DMA against the barrier by itself), and every wave is done reading the
-        //     other buffer and the reduction scratch
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        float padd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) padd[j] = pt[j] + py[j] + px[j];
-        const f32x4 s_cur = s_next;
-        if (tile + 1 < te) {
-            fetch_pos(tile + 1);
-            fetch_s(tile + 1);
-            stage(tile + 1, cur ^ 1);
-        }
-        const char* img = tilebuf + cur * TILE_BYTES;
-
-        // ---- partial scores over this wave's channel slice: S = qt_hi.x^T + qt_lo.x^T -------
-        f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const int ch0 = SLICE * wave + 32 * s;
-            const int blk = ch0 >> 7, cbase = (ch0 & 127) >> 3;
-            const bf16x8 b = *reinterpret_cast<const bf16x8*>(img + blk * 4096 + rd_row_off +
-                                                              16 * ((cbase + kg) ^ rd_swz));
-            s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[s], b, s4, 0, 0, 0);
-            s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[s], b, s4, 0, 0, 0);
-        }
-        // C layout: lane holds rows 4*kg + j (j = 0..3) of token column r16
-        float* rw = red + wave * 256;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rw[(4 * kg + j) * 16 + r16] = s4[j];
-        lds_barrier();   // [B] LDS only: the next tile's LDS-DMA stays in flight
-
-        // ---- full logits of (row r16, tokens 4*sig(kg) .. +3) -----------------------------------
-        const float* rb = red + r16 * 16 + 4 * sig(kg);
-        f32x4 lg = *reinterpret_cast<const f32x4*>(rb);
-        lg += *reinterpret_cast<const f32x4*>(rb + 256);
-        lg += *reinterpret_cast<const f32x4*>(rb + 512);
-        lg += *reinterpret_cast<const f32x4*>(rb + 768);
-        const long n0 = (long)tile * 16 + 4 * sig(kg);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) lg[j] += padd[j];
-        if (!BWD && p.inv_norm) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) lg[j] = (lg[j] + crow) * s_cur[j];
-        }
-        float pr[4];
-        if constexpr (BWD) {
-            // dS = softmax weight x (dP - delta); padded rows (state 0, 0, 0) and tail tokens contribute nothing
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                pr[j] = (n0 + j < p.N && row_glob < p.rows) ? expf(s_cur[j] - bw_m) * bw_linv * (lg[j] - bw_delta) : 0.f;
-            if (wave == 0) *reinterpret_cast<f32x4*>(p.scores + row_glob * p.score_stride + n0) = f32x4{pr[0], pr[1], pr[2], pr[3]};
-        } else {
-        if (wave == 0) *reinterpret_cast<f32x4*>(p.scores + row_glob * p.score_stride + n0) = lg;
-
-        // ---- online softmax for row r16 (lanes r16, r16+16, r16+32, r16+48 share the row) -------
-        float tmax = -1.0e30f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tmax = (n0 + j < p.N) ? fmaxf(tmax, lg[j]) : tmax;
-        tmax = xrow4_max(tmax);                          // (the row's four lanes r16 + 16 kg: gfx950 row swaps, no LDS round trip)
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = expf(m_run - m_new);
-        float lsum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            pr[j] = (n0 + j < p.N) ? expf(lg[j] - m_new) : 0.f;
-            lsum += pr[j];
-        }
-        lsum = xrow4_sum(lsum);
-        l_run = l_run * alpha + lsum;
-        m_run = m_new;
-        // rescale the running context when any row's max moved (wave-uniform branch)
-        if (__any(alpha != 1.0f)) {
-            const float a0 = __shfl(alpha, 4 * kg + 0, 64), a1 = __shfl(alpha, 4 * kg + 1, 64);
-            const float a2 = __shfl(alpha, 4 * kg + 2, 64), a3 = __shfl(alpha, 4 * kg + 3, 64);
-#pragma unroll
-            for (int cb = 0; cb < CBLK; ++cb) {
-                acc[cb][0] *= a0; acc[cb][1] *= a1; acc[cb][2] *= a2; acc[cb][3] *= a3;
-            }
-        }
-        }
-        bf16x4 phi, plo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint16_t h, l;
-            split_bf16(pr[j], h, l);
-            phi[j] = (short)h;
-            plo[j] = (short)l;
-        }
-
-        // ---- ACC += P . x over this wave's output channels ----------------------------------------
-#pragma unroll
-        for (int cb = 0; cb < CBLK; ++cb) {
-            const int ch0 = SLICE * wave + 16 * cb;
-            const int blk = ch0 >> 7, c2 = (ch0 & 127) >> 3;
-            const char* a = img + blk * 4096 + tr_row_off + 16 * ((c2 + (pp >> 1)) ^ tr_swz);
-            const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(a));
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(phi, b, acc[cb], 0, 0, 0);
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(plo, b, acc[cb], 0, 0, 0);
-        }
-    }
-
-    // ---- partial results of this token chunk ----------------------------------------------------
-    const long prow = (long)part * p.rows_pad + rg * 16;
-    if (!BWD && wave == 0 && kg == 0 && rg * 16 + r16 < p.rows) {
-        p.part_m[prow + r16] = m_run;
-        p.part_l[prow + r16] = l_run;
-    }
-#pragma unroll
-    for (int cb = 0; cb < CBLK; ++cb) {
-        float* o = p.part_acc + (prow + 4 * kg) * E + SLICE * wave + 16 * cb + r16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (rg * 16 + 4 * kg + j < p.rows) o[(long)j * E] = acc[cb][j];
-    }
+    const SegStreamParams c{p.qhi, p.qlo, p.pos_a, p.pos_stride, p.rows, p.H, p.W, p.HW, p.t0i, p.y0i, p.x0i, p.part_m, p.part_l, p.part_acc};
+    stream_segment<NB, 1, MODE>(c, p.x, (int)p.N, tb, te, 16 * rg, p.rows, 0, p.scores, p.score_stride, (long)part * (p.rows_pad / 16) + rg, 0,
+                                StreamModeArgs{p.inv_norm, p.row_const, p.s_in, p.ml, p.delta});
 }
 
 // Dev-only phase sums of the many-row kernel (tools/wide_trace.py builds a second library with -DHICOM_WTRACE): lane 0 of every wave
@@ -342,7 +101,7 @@ constexpr int kWideMargBlocks = 2;  // 16-column marginal blocks per wave (x 4 w
 // (LDS exchange -> lookups -> DPP reductions -> exp -> LDS hand-over -> transposed reads -> MFMAs, ~5k clocks per 16 tokens, both
 // waves of a SIMD in the same phase): two tiles per barrier interval would overlap two such chains, and 160 KB of LDS hold four
 // 36-KB tiles, not the six that needs.
-// BWD = true: the attention backward over the same stream (see global_stream_kernel<NB, true>): the "queries" are the upstream
+// BWD = true: the attention backward over the same stream (see StreamMode::Bwd, stream_body.hpp): the "queries" are the upstream
 // gradients dctx_r, the score tile is dP, the quarter-of-the-rows step forms dS = exp(S - M) / L (dP - delta) from the forward's logits
 // (fetched one tile ahead by an asm load the end-of-iteration wait covers: the loading waves' counted LDS-DMA and compiler-counted
 // loads do not mix), dS goes through the same P hand-over into the dS . x MFMAs, no running max, no rescale.  The positional
@@ -713,6 +472,13 @@ extern "C" int hicom_global_stream_marg_width(int32_t H, int32_t W) {
     return 16 * (1 + (H + 15) / 16 + (W + 15) / 16);
 }
 
+// HICOM_GLOBAL_NARROW=1, dev / test switch: always take the one-row-group kernel.  Read on every call: the tests set and clear it
+// inside a running process.
+static bool force_narrow() {
+    const char* v = getenv("HICOM_GLOBAL_NARROW");
+    return v && v[0] == '1';
+}
+
 static bool wide_ok(int64_t N, int32_t E, int32_t rows_pad, int32_t H, int32_t W, int32_t nparts) {
     const bool pos = H > 0 && W > 0;
     const long ntiles = (N + 15) / 16, HW = pos ? (long)H * W : 1;
@@ -725,8 +491,7 @@ static bool wide_ok(int64_t N, int32_t E, int32_t rows_pad, int32_t H, int32_t W
 // positional marginals) and a grid whose [frames | rows | columns] fit its 8 marginal blocks of 16 columns
 extern "C" int hicom_global_stream_has_marg(int64_t N, int32_t E, int32_t rows_pad, int32_t H, int32_t W, int32_t nparts) {
     if (N <= 0 || nparts <= 0 || rows_pad <= 0 || H <= 0 || W <= 0) return HICOM_EINVAL;
-    const char* force_narrow = getenv("HICOM_GLOBAL_NARROW");      // dev / test switch: always take the one-row-group kernel
-    if (force_narrow && force_narrow[0] == '1') return 0;
+    if (force_narrow()) return 0;
     const char* no_marg = getenv("HICOM_GLOBAL_NO_MARG");          // dev / A-B switch: logit tensor + marginal pass (the round-3 path)
     if (no_marg && no_marg[0] == '1') return 0;
     // (the merge behind it keeps its weight record -- 2 + nparts + T + H + W floats per row -- in the head of the row's scratch region of
@@ -735,6 +500,73 @@ extern "C" int hicom_global_stream_has_marg(int64_t N, int32_t E, int32_t rows_p
     const long T = N / ((long)H * W);
     if (2 + (long)nparts + T + H + W > T * (H + W + 2)) return 0;
     return (wide_ok(N, E, rows_pad, H, W, nparts) && 1 + (H + 15) / 16 + (W + 15) / 16 <= 4 * kWideMargBlocks) ? 1 : 0;
+}
+
+// The fields every entry fills alike.  q_hi / q_lo / pos: the forward's qt_* / pos_a, the backward's dctx_* / pos_b; scores: the
+// forward's logits, the backward's ds_out.  The mode fields and the partial softmax state start NULL.
+static StreamParams stream_params(const void* x, int64_t N, const void* q_hi, const void* q_lo, int32_t rows, int32_t rows_pad,
+                                  const float* pos, int32_t pos_stride, int32_t H, int32_t W, int32_t t_index0, int32_t y_index0,
+                                  int32_t x_index0, float* scores, int64_t score_stride, float* part_acc) {
+    StreamParams p{};
+    p.x = (const uint16_t*)x; p.N = N; p.qhi = (const uint16_t*)q_hi; p.qlo = (const uint16_t*)q_lo;
+    p.pos_a = pos; p.pos_stride = pos_stride; p.H = H; p.W = W; p.HW = H * W;
+    p.t0i = t_index0; p.y0i = y_index0; p.x0i = x_index0;
+    p.scores = scores; p.score_stride = score_stride;
+    p.part_acc = part_acc; p.rows_pad = rows_pad; p.rows = rows;
+    p.ntiles = (int)((N + 15) / 16);
+    return p;
+}
+
+template <int NB, StreamMode MODE>
+static void narrow_launch_nb(const StreamParams& p, int nparts, hipStream_t s) {
+    constexpr int smem = stream_smem(NB, 1);
+    static bool attr_set = false;
+    if (smem > 64 * 1024 && !attr_set) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(global_stream_kernel<NB, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((global_stream_kernel<NB, MODE>), dim3((unsigned)nparts, (unsigned)(p.rows_pad / 16)), dim3(256), smem, s, p);
+}
+
+template <StreamMode MODE>
+static void narrow_launch(const StreamParams& p, int E, int nparts, hipStream_t s) {
+    if (E == 1152) narrow_launch_nb<9, MODE>(p, nparts, s);
+    else narrow_launch_nb<6, MODE>(p, nparts, s);
+}
+
+// The wide / narrow choice and the launch, for the checked arguments of a forward (BWD = false) or backward entry.  Many rows: the wide
+// form (two row groups per workgroup, three-deep ring, half the passes over the tokens) when its limits hold; with part_marg the
+// positional marginals (of the softmax weights, in the backward of dS) come out of the kernel and `scores` may be NULL.  Else the
+// narrow form, clip scale as an instantiation of its own (p.inv_norm given).
+template <bool BWD>
+static int stream_launch(StreamParams p, int32_t E, int32_t nparts, float* part_marg, void* stream) {
+    const char* who = BWD ? "global_stream_bwd" : "global_stream";
+    const bool pos = p.pos_a != nullptr;
+    const bool wide = !p.inv_norm && !force_narrow() && wide_ok(p.N, E, p.rows_pad, pos ? p.H : 0, pos ? p.W : 0, nparts);
+    HICOM_REQUIRE(!part_marg || (wide && pos && hicom_global_stream_has_marg(p.N, E, p.rows_pad, p.H, p.W, nparts) == 1), HICOM_EUNSUP,
+                  "%s: no in-kernel marginals for this shape (hicom_global_stream_has_marg)", who);
+    HICOM_REQUIRE(wide || p.scores, HICOM_EINVAL, "%s", BWD ? "global_stream_bwd: ds_out is NULL" : "global_stream: scores is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    if (wide) {
+        const int S = kWideFrames + (pos ? p.H + p.W : 0);
+        const size_t smem = (size_t)3 * 9 * 4096 + 2 * (size_t)kWideRG * 4 * 1024 + 128 + (size_t)kWideRG * (1024 + 64) + (size_t)kWideRG * 16 * S * 4;
+        static bool wide_attr = false;
+        if (!wide_attr) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(global_stream_wide_kernel<9, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+            wide_attr = true;
+        }
+        p.part_marg = part_marg;
+        p.marg_stride = part_marg ? hicom_global_stream_marg_width(p.H, p.W) : 0;
+        if (!pos) { p.H = 1; p.W = 1; p.HW = 1; }
+        hipLaunchKernelGGL((global_stream_wide_kernel<9, BWD>), dim3((unsigned)nparts, (unsigned)(p.rows_pad / (16 * kWideRG))), dim3(512), smem, s, p);
+    } else if (BWD) {
+        narrow_launch<StreamMode::Bwd>(p, E, nparts, s);
+    } else if (p.inv_norm) {
+        narrow_launch<StreamMode::FwdClip>(p, E, nparts, s);
+    } else {
+        narrow_launch<StreamMode::Fwd>(p, E, nparts, s);
+    }
+    return hicom_host::check_launch(who);
 }
 
 static int global_stream_launch(const void* x, int64_t N, int32_t E,
@@ -756,51 +588,10 @@ static int global_stream_launch(const void* x, int64_t N, int32_t E,
                       ((uintptr_t)scores % 16 == 0),
                   HICOM_EINVAL, "global_stream: pointers must be 16-byte aligned");
     if (pos_a) HICOM_REQUIRE(H > 0 && W > 0 && pos_stride > 0, HICOM_EINVAL, "global_stream: pos geometry");
-    StreamParams p;
-    p.x = (const uint16_t*)x; p.N = N; p.qhi = (const uint16_t*)qt_hi; p.qlo = (const uint16_t*)qt_lo;
-    p.pos_a = pos_a; p.pos_stride = pos_stride; p.H = H; p.W = W; p.HW = H * W;
-    p.t0i = t_index0; p.y0i = y_index0; p.x0i = x_index0;
-    p.scores = scores; p.score_stride = score_stride;
-    p.part_m = part_m; p.part_l = part_l; p.part_acc = part_acc; p.rows_pad = rows_pad; p.rows = rows;
-    p.ntiles = (int)((N + 15) / 16);
-    p.s_in = nullptr; p.ml = nullptr; p.delta = nullptr;
+    StreamParams p = stream_params(x, N, qt_hi, qt_lo, rows, rows_pad, pos_a, pos_stride, H, W, t_index0, y_index0, x_index0, scores, score_stride, part_acc);
+    p.part_m = part_m; p.part_l = part_l;
     p.inv_norm = inv_norm; p.row_const = row_const;
-    p.part_marg = pos_a ? part_marg : nullptr;
-    p.marg_stride = pos_a ? hicom_global_stream_marg_width(H, W) : 0;
-    dim3 grid((unsigned)nparts, (unsigned)(rows_pad / 16));
-    hipStream_t s = (hipStream_t)stream;
-    // many rows: the wide form (two row groups per workgroup, three-deep ring) when its limits hold
-    const char* force_narrow = getenv("HICOM_GLOBAL_NARROW");      // dev / test switch: always take the one-row-group kernel
-    const bool wide = !inv_norm && !(force_narrow && force_narrow[0] == '1') && wide_ok(N, E, rows_pad, pos_a ? H : 0, pos_a ? W : 0, nparts);
-    HICOM_REQUIRE(!part_marg || (wide && hicom_global_stream_has_marg(N, E, rows_pad, H, W, nparts) == 1), HICOM_EUNSUP,
-                  "global_stream: no in-kernel marginals for this shape (hicom_global_stream_has_marg)");
-    HICOM_REQUIRE(scores || part_marg, HICOM_EINVAL, "global_stream: scores is NULL");
-    if (wide) {
-        const int S = kWideFrames + (pos_a ? H + W : 0);
-        const size_t smem = (size_t)3 * 9 * 4096 + 2 * (size_t)kWideRG * 4 * 1024 + 128 + (size_t)kWideRG * (1024 + 64) + (size_t)kWideRG * 16 * S * 4;
-        static bool wide_attr = false;
-        if (!wide_attr) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(global_stream_wide_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-            wide_attr = true;
-        }
-        if (!pos_a) { p.H = 1; p.W = 1; p.HW = 1; }
-        hipLaunchKernelGGL(global_stream_wide_kernel<9>, dim3((unsigned)nparts, (unsigned)(rows_pad / (16 * kWideRG))), dim3(512), smem, s, p);
-        return hicom_host::check_launch("global_stream");
-    }
-    if (E == 1152) {
-        constexpr int smem = 2 * 9 * 4096 + 4096;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(global_stream_kernel<9>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(global_stream_kernel<9>, grid, dim3(256), smem, s, p);
-    } else {
-        constexpr int smem = 2 * 6 * 4096 + 4096;
-        hipLaunchKernelGGL(global_stream_kernel<6>, grid, dim3(256), smem, s, p);
-    }
-    return hicom_host::check_launch("global_stream");
+    return stream_launch<false>(p, E, nparts, part_marg, stream);
 }
 
 extern "C" int hicom_global_stream_fwd(const void* x, int64_t N, int32_t E,
@@ -860,48 +651,7 @@ extern "C" int hicom_global_stream_bwd(const void* x, int64_t N, int32_t E, cons
                       ((uintptr_t)s_in % 16 == 0) && ((uintptr_t)ds_out % 16 == 0), HICOM_EINVAL, "global_stream_bwd: alignment");
     HICOM_REQUIRE(rows_pad % 16 == 0, HICOM_EINVAL, "global_stream_bwd: rows_pad");
     if (pos_b) HICOM_REQUIRE(H > 0 && W > 0 && pos_stride > 0, HICOM_EINVAL, "global_stream_bwd: pos geometry");
-    StreamParams p;
-    p.x = (const uint16_t*)x; p.N = N; p.qhi = (const uint16_t*)dctx_hi; p.qlo = (const uint16_t*)dctx_lo;
-    p.pos_a = pos_b; p.pos_stride = pos_stride; p.H = H; p.W = W; p.HW = H * W;
-    p.t0i = t_index0; p.y0i = y_index0; p.x0i = x_index0;
-    p.scores = ds_out; p.score_stride = score_stride;
-    p.part_m = nullptr; p.part_l = nullptr; p.part_acc = part_acc; p.rows_pad = rows_pad; p.rows = rows;
-    p.ntiles = (int)((N + 15) / 16);
-    p.s_in = s_in; p.ml = ml; p.delta = delta; p.inv_norm = nullptr; p.row_const = nullptr; p.part_marg = nullptr; p.marg_stride = 0;
-    dim3 grid((unsigned)nparts, (unsigned)(rows_pad / 16));
-    hipStream_t s = (hipStream_t)stream;
-    // many rows: the wide form (two row groups per workgroup, half the passes over the tokens; with part_marg the positional marginals
-    // of dS come out of the kernel and ds_out may be NULL)
-    const char* force_narrow = getenv("HICOM_GLOBAL_NARROW");
-    const bool wide = !(force_narrow && force_narrow[0] == '1') && wide_ok(N, E, rows_pad, pos_b ? H : 0, pos_b ? W : 0, nparts);
-    HICOM_REQUIRE(!part_marg || (wide && pos_b && hicom_global_stream_has_marg(N, E, rows_pad, H, W, nparts) == 1), HICOM_EUNSUP,
-                  "global_stream_bwd: no in-kernel marginals for this shape (hicom_global_stream_has_marg)");
-    HICOM_REQUIRE(wide || ds_out, HICOM_EINVAL, "global_stream_bwd: ds_out is NULL");
-    if (wide) {
-        const int S = kWideFrames + (pos_b ? H + W : 0);
-        const size_t smem = (size_t)3 * 9 * 4096 + 2 * (size_t)kWideRG * 4 * 1024 + 128 + (size_t)kWideRG * (1024 + 64) + (size_t)kWideRG * 16 * S * 4;
-        static bool wide_attr = false;
-        if (!wide_attr) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(global_stream_wide_kernel<9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-            wide_attr = true;
-        }
-        p.part_marg = part_marg;
-        p.marg_stride = part_marg ? hicom_global_stream_marg_width(H, W) : 0;
-        if (!pos_b) { p.H = 1; p.W = 1; p.HW = 1; }
-        hipLaunchKernelGGL((global_stream_wide_kernel<9, true>), dim3((unsigned)nparts, (unsigned)(rows_pad / (16 * kWideRG))), dim3(512), smem, s, p);
-        return hicom_host::check_launch("global_stream_bwd");
-    }
-    if (E == 1152) {
-        constexpr int smem = 2 * 9 * 4096 + 4096;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(global_stream_kernel<9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((global_stream_kernel<9, true>), grid, dim3(256), smem, s, p);
-    } else {
-        constexpr int smem = 2 * 6 * 4096 + 4096;
-        hipLaunchKernelGGL((global_stream_kernel<6, true>), grid, dim3(256), smem, s, p);
-    }
-    return hicom_host::check_launch("global_stream_bwd");
+    StreamParams p = stream_params(x, N, dctx_hi, dctx_lo, rows, rows_pad, pos_b, pos_stride, H, W, t_index0, y_index0, x_index0, ds_out, score_stride, part_acc);
+    p.s_in = s_in; p.ml = ml; p.delta = delta;
+    return stream_launch<true>(p, E, nparts, part_marg, stream);
 }

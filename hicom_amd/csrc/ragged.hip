@@ -13,7 +13,8 @@
 // The stacked tensor is not one window grid (kt differs between neighbours), so the local stage builds each window's geometry from its
 // item's own (T, kt) and offsets the token index by the item's first token.  The four lookups are wave-uniform loads through a
 // kernel-argument pointer with a uniform index: they land in SGPRs.  hicom_compressor_ragged_fwd only launches.  The stream is
-// stream_segment (segment_item.hpp) with one row group; the per-item requirements, the chunk share, the tile ranges and the table upload
+// stream_segment (stream_body.hpp: the one body of the four-wave stream machine, also behind hicom_global_stream_fwd's narrow kernel)
+// with one row group; the per-item requirements, the chunk share, the tile ranges and the table upload
 // are segment_host.hpp's, shared with ragged_multi_guide.hip.
 #include <vector>
 

@@ -7,7 +7,7 @@
 //    3    rmg_local_kernel: one wave per window of the STACKED tensor (window -> item lookup as in ragged.hip); the wave walks its item's
 //         guides in groups of kGuideGroup (multi_window.hpp: multi_window_guides_ctx16), so every key row and every value row is loaded
 //         once per group; fp16 contexts go out pair-major: pair p of item i owns rows [ctx_row0_p, + windows_i)
-//    4    rmg_stream_kernel: stream_segment (segment_item.hpp: the one body of the segmented stream) with two row groups, 32 densely packed
+//    4    rmg_stream_kernel: stream_segment (stream_body.hpp: the one body of the four-wave stream machine) with two row groups, 32 densely packed
 //         folded rows of ONE item per workgroup, one workgroup per work unit {item, first tile, last tile, row pass, partial-state slot}
 //    5    merge_segments (segment_item.hpp) per (pair, head)
 //    6-11 the global tail with M rows, the local readout as one GEMM pair over all pairs' window contexts
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void rmg_local_kernel(const uint16_t* key, con
                                   ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)wi * D);
 }
 
-// ---- 4: segmented many-row stream, stream_segment (segment_item.hpp) with two row groups: 32 densely packed rows of ONE item per
+// ---- 4: segmented many-row stream, stream_segment (stream_body.hpp) with two row groups: 32 densely packed rows of ONE item per
 // workgroup, so the item's tokens come from HBM once per 32 folded rows ----
 struct RmgStreamParams {
     SegStreamParams c;

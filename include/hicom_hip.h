@@ -238,6 +238,9 @@ int hicom_split16_fwd(const float* x, int32_t rows, int32_t rows_pad, int32_t E,
  *   part_m/l     : f32 [nparts, rows_pad]; part_acc : f32 [nparts, rows_pad, E]
  *   nparts       : number of token chunks (= workgroups per row group); returned layout is
  *                  consumed by hicom_global_merge_fwd.
+ *   N            : 0 < N < 2^31, else HICOM_EINVAL (all four entries below and hicom_global_stream_bwd).  The narrow (one-row-group)
+ *                  kernel indexes tokens with a 32-bit int, as the many-item steps do: the last tile's 16 * tile + 15 <= 2^31 - 1
+ *                  still is one.  No such N fits device memory at E >= 768.
  */
 int hicom_global_stream_fwd(const void* x, int64_t N, int32_t E,
                             const void* qt_hi, const void* qt_lo, int32_t rows, int32_t rows_pad,

@@ -32,8 +32,8 @@ positional rows by more than 10 bounds; the marginal form with and without the l
 bit for bit.  Backward: ds_out elementwise, part_acc.sum(0) against sum dS x, in the marginal form the t / y / x marginals gathered as
 hicom_amd/autograd.py gathers them, and ds_out = None leaves part_acc / part_marg bit-identical.
 Every output starts as NaN.  include/hicom_hip.h promises that rows >= `rows` "produce no output": rows >= R of part_m / part_l /
-part_acc / part_marg must still be NaN.  The kernels do store rows >= R of `scores` / ds_out (inside the [rows_pad, stride] allocation);
-those rows are overwritten with NaN before the merge runs, which proves the consumer does not read them, and in the backward they
+part_acc / part_marg must still be NaN.  The wide kernel does store rows >= R of `scores` / ds_out (inside the [rows_pad, stride]
+allocation; the narrow one masks them); those rows are overwritten with NaN before the merge runs, which proves the consumer does not read them, and in the backward they
 must be zero or untouched.  The padding columns of part_marg (frames past the 8-frame block's use, H and W up to 16) are zero or
 untouched, and no consumer column lies in them.
 
