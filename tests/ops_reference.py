@@ -635,3 +635,109 @@ def trilinear_pool_ref(x, To, Ho, Wo, second_tap_is_first=False):
     sl_h = absl(slope(lerp(x, 0, To), 1, Ho), 2, Wo)
     sl_w = slope(lerp(lerp(x, 0, To), 1, Ho), 2, Wo)
     return out, ab, (sl_t, sl_h, sl_w)
+
+
+# ---- merge of streaming partials, cross-shard combine, merge + v_proj (csrc/merge.hip, csrc/merge_item.hpp) ---------------------
+def merge_ref(part_m, part_l, part_acc, rows, scores=None, N=0, H=1, W=1, pe=None, t0i=0, y0i=0, x0i=0, normalize=False, absolute=False,
+              lose_last_partial=False, lose_partial_batch=False, frame_max_unscaled=False, lose_frames_from_64=False,
+              lose_pos_from_128=False, ignore_t0=False, swap_yx=False, neighbour_record=False, pad_leak=False, unnormalised_L=False):
+    """hicom_global_merge_fwd / hicom_global_merge_marg_fwd as include/hicom_hip.h states them, in float64:
+        M_r = max_p m_p,   L_r = sum_p e^(m_p - M_r) l_p,
+        ACC[r, :] = sum_p e^(m_p - M_r) acc_p[r, :] + sum_n e^(s_n - M_r) (pe[t0i + t] + pe[y0i + y] + pe[x0i + x]),   (/ L_r with normalize)
+    part_m, part_l [nparts, rows_pad], part_acc [nparts, rows_pad, E], scores [rows_pad, >= N] (or None: no positional term), pe [P, E].
+    The positional term is taken token by token from the logits; no marginal is formed.  Returns (M, L, acc) of the first `rows` rows.
+    absolute: acc is the same expression on absolute values, un-normalised (what an fp32 summation error is proportional to).
+    The remaining keywords plant the faults of tests/test_merge_power.py (see its docstring)."""
+    nparts = part_m.shape[0]
+    nrow = rows + 1 if pad_leak else rows
+
+    def weights(rsel):
+        m, l = part_m[:, rsel], part_l[:, rsel]
+        M = m.max(0).values
+        w = torch.exp(m - M[None, :])
+        wl = w.clone()
+        if lose_last_partial:
+            wl[nparts - 1] = 0
+        wa = wl.clone()
+        if lose_partial_batch and nparts >= 225:
+            wa[:256] = 0
+        wn = None
+        if scores is not None and pe is not None:
+            s = scores[rsel, :N]
+            t, y, x = token_axes(N, H, W)
+            wn = torch.exp(s - M[:, None])
+            if frame_max_unscaled:
+                fmax = _seg_max(s, t, N // (H * W))
+                wn = torch.exp(s - fmax[:, t])
+            if lose_frames_from_64:
+                wn = wn * (t < 64)
+        return M, (wl * l).sum(0), wa, wn, l.sum(0)
+
+    sel = torch.arange(nrow)
+    M, L, wa, wn, lsum = weights(sel)
+    if neighbour_record:
+        nb = (torch.arange(rows) + 1) % rows
+        nb = torch.cat([nb, sel[rows:]])
+        _, Lr, wa, wn, lsum = weights(nb)
+    else:
+        Lr = L
+    vals = part_acc[:, :nrow].abs() if absolute else part_acc[:, :nrow]
+    acc = (wa[:, :, None] * vals).sum(0)
+    if wn is not None:
+        T = N // (H * W)
+        t, y, x = token_axes(N, H, W)
+        ty, tx = (x % H, y % W) if swap_yx else (y, x)
+        rows_of = ((0 if ignore_t0 else t0i) + t, y0i + ty, x0i + tx)
+        keep = (t < 128, T + ty < 128, T + H + tx < 128) if lose_pos_from_128 else (None, None, None)
+        pos = None                                                   # [N, E]: the positional rows of every token, summed in place
+        for idx, k in zip(rows_of, keep):
+            term = pe[idx]
+            if absolute:
+                term.abs_()
+            if k is not None:
+                term[~k] = 0
+            pos = term if pos is None else pos.add_(term)
+        acc = acc + wn @ pos
+    if normalize and not absolute:
+        acc = acc / (lsum if unnormalised_L else Lr)[:, None]
+    if pad_leak:
+        acc[rows - 1] = acc[rows - 1] + acc[rows]
+    return M[:rows], L[:rows], acc[:rows]
+
+
+def combine_ref(ml, acc, absolute=False, unnormalised_L=False, lose_second_column_block=False):
+    """hicom_global_combine_fwd / _strided_fwd in float64: ml [nsets, rows, 2] = (M, L) per set, acc [nsets, rows, E] un-normalised:
+    ctx = sum_k e^(M_k - M) acc_k / sum_k e^(M_k - M) L_k,  M = max_k M_k.  Returns (ctx, L); absolute: the numerator on absolute values."""
+    Mk, Lk = ml[:, :, 0], ml[:, :, 1]
+    w = torch.exp(Mk - Mk.max(0).values[None])
+    L = (w * Lk).sum(0)
+    if absolute:
+        return (w[:, :, None] * acc.abs()).sum(0), L
+    ctx = (w[:, :, None] * acc).sum(0) / (Lk.sum(0) if unnormalised_L else L)[:, None]
+    if lose_second_column_block:
+        ctx[:, 256:] = (acc[0] / Lk[0][:, None])[:, 256:]
+    return ctx, L
+
+
+def merge_vproj_ref(part_m, part_l, part_acc, rows, w_v, normalised=False, absolute=False, head_off_by_one=False, lose_last_slab=False):
+    """hicom_merge_vproj_fwd / _fixed_fwd / _sets_fwd in float64, from the values the kernel received (bf16 weights and f16 partials
+    up-cast): (M, L) and ctx_h = sum_p e^(m_p - M) acc_p[h] / L of head h = row h, o[h hd + j] = W_v[h hd + j, :] . ctx_h, hd = E / rows.
+    normalised: part_acc holds the normalised contexts acc_p / l_p (the f16 form), weighed with l_p e^(m_p - M).
+    absolute: (M, L, sum_p w_p |acc_p| / L, sum_c |W_v| |ctx|).  head_off_by_one / lose_last_slab plant faults."""
+    E = part_acc.shape[-1]
+    hd = E // rows
+    m, l = part_m[:, :rows], part_l[:, :rows]
+    M = m.max(0).values
+    w = torch.exp(m - M[None])
+    L = (w * l).sum(0)
+    wa = w * l if normalised else w
+    ctx = (wa[:, :, None] * (part_acc[:, :rows].abs() if absolute else part_acc[:, :rows])).sum(0) / L[:, None]
+    wv = w_v.reshape(rows, hd, E)
+    if head_off_by_one:
+        wv = wv.roll(-1, 0)
+    cx = ctx.abs() if absolute else ctx
+    if lose_last_slab:
+        cx = cx.clone()
+        cx[:, E - 64:] = 0
+    o = torch.einsum("hjc,hc->hj", wv.abs() if absolute else wv, cx).reshape(E)
+    return M, L, ctx, o

@@ -560,3 +560,47 @@ def test_trilinear_pool_reference_equals_torch_interpolate(shape, out):
     on_grid = all(float(R._pool_taps(n, m)[2].abs().max()) == 0.0 for n, m in zip(shape, out))
     assert on_grid == (shape in ((8, 6, 6), (1, 6, 6)))
     assert (_maxabs(R.trilinear_pool_ref(x, *out, second_tap_is_first=True)[0], got) > 0.1) == (not on_grid)
+
+
+def test_merge_reference_equals_softmax_attention_over_x_plus_pos():
+    """merge_ref on partials formed from real values (chunk maxima, sums and accumulators of e^(s - m) x_n over contiguous token chunks)
+    is the plain attention softmax(S) (x + pos): the partial weights and the token-by-token positional term together."""
+    from global_stream_inputs import chunk_token_ranges
+    g = torch.Generator().manual_seed(11)
+    T, H, W, rows, E, nparts, rows_pad = 3, 4, 5, 5, 8, 3, 8
+    N, (t0, y0, x0) = T * H * W, (2, 7, 13)
+    x = torch.randn(N, E, generator=g, dtype=torch.float64)
+    S = 3.0 * torch.randn(rows_pad, N + 4, generator=g, dtype=torch.float64)
+    pe = torch.randn(x0 + W, E, generator=g, dtype=torch.float64)
+    pm, pl = torch.zeros(nparts, rows_pad, dtype=torch.float64), torch.zeros(nparts, rows_pad, dtype=torch.float64)
+    pacc = torch.zeros(nparts, rows_pad, E, dtype=torch.float64)
+    for i, (lo, hi) in enumerate(chunk_token_ranges(N, nparts)):
+        assert hi > lo
+        pm[i] = S[:, lo:hi].max(1).values
+        e = torch.exp(S[:, lo:hi] - pm[i][:, None])
+        pl[i], pacc[i] = e.sum(1), e @ x[lo:hi]
+    t, y, xx = R.token_axes(N, H, W)
+    val = x + pe[t0 + t] + pe[y0 + y] + pe[x0 + xx]
+    p = torch.softmax(S[:rows, :N], 1)
+    M, L, ctx = R.merge_ref(pm, pl, pacc, rows, S, N, H, W, pe, t0, y0, x0, normalize=True)
+    assert torch.allclose(ctx, p @ val, rtol=1e-12, atol=1e-13)
+    assert torch.allclose(M + torch.log(L), torch.logsumexp(S[:rows, :N], 1), rtol=1e-13, atol=0)
+    _, _, acc = R.merge_ref(pm, pl, pacc, rows, S, N, H, W, pe, t0, y0, x0, normalize=False)
+    assert torch.allclose(acc, L[:, None] * (p @ val), rtol=1e-12, atol=1e-13)
+    assert torch.allclose(R.merge_ref(pm, pl, pacc, rows, normalize=True)[2], p @ x, rtol=1e-12, atol=1e-13)
+    ab = R.merge_ref(pm, pl, pacc, rows, S, N, H, W, pe, t0, y0, x0, absolute=True)[2]
+    assert bool((ab >= acc.abs() - 1e-12).all())
+    # the combine of the partials seen as shard states, and merge + v_proj, are the same attention
+    cx, Lc = R.combine_ref(torch.stack([pm, pl], 2)[:, :rows], pacc[:, :rows])
+    assert torch.allclose(cx, p @ x, rtol=1e-12, atol=1e-13) and torch.allclose(Lc, L)
+    wv = torch.randn(rows * 4, rows * 4, generator=g, dtype=torch.float64)
+    x2 = torch.randn(N, rows * 4, generator=g, dtype=torch.float64)
+    for i, (lo, hi) in enumerate(chunk_token_ranges(N, nparts)):
+        e = torch.exp(S[:, lo:hi] - pm[i][:, None])
+        pacc2 = e @ x2[lo:hi] if i == 0 else torch.cat([pacc2, e @ x2[lo:hi]])
+    pacc2 = pacc2.reshape(nparts, rows_pad, rows * 4)
+    M2, L2, c2, o = R.merge_vproj_ref(pm, pl, pacc2, rows, wv)
+    want = torch.cat([wv[4 * h:4 * h + 4] @ (p[h] @ x2) for h in range(rows)])
+    assert torch.allclose(o, want, rtol=1e-12, atol=1e-13) and torch.equal(M2, M) and torch.allclose(L2, L)
+    o16 = R.merge_vproj_ref(pm, pl, pacc2 / pl[:, :, None], rows, wv, normalised=True)[3]
+    assert torch.allclose(o16, want, rtol=1e-12, atol=1e-13)
