@@ -25,6 +25,10 @@
 // with its own y planes for the k / v adaptor recipe.  Launches 3 and 4 are clips_local_kernel / clips_local_adapt_kernel and
 // clips_stream_kernel, which take an item's base pointers from a [B][4] device table the caller fills per call; checks, layout, table
 // region and every other launch are the functions of this file on the base block.
+//
+// Logits form: hicom_compressor_ragged_multiguide_logits_fwd is the plain sequence with launch 3 replaced by
+// rmg_local_logits_kernel, which takes every pair's local logits precomputed (hicom_head_scores_ragged_fwd) and reads the value rows only.
+// Same launch count, same workspace, same tables; frames_embed is not read.
 #include <vector>
 
 #include "multi_window.hpp"
@@ -74,6 +78,24 @@ __global__ __launch_bounds__(256) void rmg_local_kernel(const uint16_t* key, con
     const long first = (long)it.tok0 * D;
     multi_window_guides_ctx16<NV>(key + first, value + first, guide, it.pair0, it.Q, g, lane, scale,
                                   ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)wi * D);
+}
+
+// The logits form of launch 3: the same wave -> window -> item map with the local logits given
+// (multi_window.hpp: multi_window_guides_logits_ctx16).  logits f32 [Qmax][q_stride]: guide q of item i at q q_stride + tok0_i + n, the
+// layout hicom_head_scores_ragged_fwd writes; planes q >= Q_i of an item's columns are not read.  No key row is read.
+template <int NV>
+__global__ __launch_bounds__(256) void rmg_local_logits_kernel(const uint16_t* value, const float* logits, long q_stride, const RmgItem* items,
+                                                               const int* win_item, hicom_axis ay, hicom_axis ax, int nwin, float scale, _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const RmgItem it = items[win_item[win]];
+    const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+    const int wi = (it.T / it.kt) * ay.nwin * ax.nwin;
+    const WindowGeom g(at, ay, ax, win - it.win0);
+    multi_window_guides_logits_ctx16<NV>(value + (long)it.tok0 * D, logits + it.tok0, q_stride, it.Q, g, lane, scale,
+                                         ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)wi * D);
 }
 
 // ---- 4: segmented many-row stream, stream_segment (stream_body.hpp) with two row groups: 32 densely packed rows of ONE item per
@@ -346,11 +368,19 @@ struct ClipsCall {
     SegAdaptParams ad;
 };
 
+// the local logits of the logits step (hicom_compressor_ragged_multiguide_logits_fwd): f32 [max Q_i][q_stride], guide q of item i at
+// q q_stride + tok0_i + n; p NULL: the keyed forms
+struct LocalLogits {
+    const float* p;
+    long q_stride;
+};
+
 // the four launches that look their pair or item up in the table region (segment_host.hpp: seg_step)
 struct PairItems {
     const Args* a;
     const RmgLayout& l;
     const ClipsCall* clips;     // the items are prepared clips at their own addresses; NULL: the stacked tensor a->ff / a->fe
+    LocalLogits logits;         // the logits form on the stacked tensor: no key row is read
     char* ws() const { return (char*)a->ws; }
     hipStream_t s() const { return (hipStream_t)a->stream; }
     const RmgItem* items() const { return (const RmgItem*)(ws() + l.items); }
@@ -361,7 +391,10 @@ struct PairItems {
         const dim3 grid((unsigned)((l.item_windows + 3) / 4));
         const int* win_item = (const int*)(ws() + l.win_item);
         _Float16* ctx16 = (_Float16*)(ws() + l.s.ctx16);
-        if (clips && clips->adapted)
+        if (logits.p)
+            HICOM_LAUNCH(rmg_local_logits_kernel<3>, grid, dim3(256), 0, s(), (const uint16_t*)a->ff, logits.p, logits.q_stride, items(), win_item, ay, ax,
+                         (int)l.item_windows, a->l_scale, ctx16);
+        else if (clips && clips->adapted)
             HICOM_LAUNCH(clips_local_adapt_kernel<3>, grid, dim3(256), 0, s(), clips->ptrs, (const uint16_t*)a->guide, clips->ad, items(), win_item, ay, ax,
                          (int)l.item_windows, a->l_scale, ctx16);
         else if (clips)
@@ -424,10 +457,25 @@ struct PairItems {
 };
 
 // clips: the items are prepared clips at their own addresses (clips_fwd); every check runs as for the stacked tensor, only a->ff / a->fe
-// are not looked at
-int rmg_fwd(const Args* a, const ClipsCall* clips = nullptr) {
+// are not looked at.  logits: the logits form (the stacked tensor only): launch 3 is rmg_local_logits_kernel, a->fe is not looked at either.
+int rmg_fwd(const Args* a, const ClipsCall* clips = nullptr, LocalLogits logits = LocalLogits{nullptr, 0}) {
     int st = rmg_check(a);
     if (st != HICOM_OK) return st;
+    Args keyless;
+    if (logits.p) {
+        HICOM_REQUIRE(!clips, HICOM_EINVAL, "%s: the logits form reads the stacked tensor", kWho);
+        long tokens = 0;
+        int q_max = 0;
+        for (int i = 0; i < a->B; ++i) {
+            tokens += (long)a->items[i].T * a->H * a->W;
+            q_max = a->guide_counts[i] > q_max ? a->guide_counts[i] : q_max;
+        }
+        HICOM_REQUIRE(q_max == 1 || logits.q_stride >= tokens, HICOM_EINVAL, "%s: q_stride=%ld floats between the guides' logit planes of %ld tokens", kWho,
+                      logits.q_stride, tokens);
+        keyless = *a;
+        keyless.fe = nullptr;
+        a = &keyless;
+    }
     const RmgLayout l = rmg_layout(a);
     st = seg_check_fwd(kWho, a, nullptr, l.s.total, clips != nullptr);
     if (st != HICOM_OK) return st;
@@ -437,7 +485,7 @@ int rmg_fwd(const Args* a, const ClipsCall* clips = nullptr) {
                       "compressor_ragged_multiguide: item %d has newline rows and there is no newline token", i);
     Args pairs = *a;            // the shared host sees the pairs as its items: M guide rows, M global tokens, all pairs' window contexts
     pairs.B = l.M;
-    return seg_step(&pairs, nullptr, l.s, PairItems{a, l, clips});
+    return seg_step(&pairs, nullptr, l.s, PairItems{a, l, clips, logits});
 }
 
 // ---- prepared clips, Q_i guides each (hicom_compressor_clips_multiguide_*) -----------------------------------------------------------------
@@ -480,6 +528,13 @@ extern "C" int64_t hicom_compressor_ragged_multiguide_workspace_bytes(const hico
 extern "C" int hicom_compressor_ragged_multiguide_prepare(const hicom_compressor_ragged_multiguide_args* a) { return rmg_prepare(a); }
 
 extern "C" int hicom_compressor_ragged_multiguide_fwd(const hicom_compressor_ragged_multiguide_args* a) { return rmg_fwd(a); }
+
+// The logits form: a->fe is not read (the workspace, its size function and the prepare call are the keyed step's).
+extern "C" int hicom_compressor_ragged_multiguide_logits_fwd(const hicom_compressor_ragged_multiguide_args* a, const float* local_logits, int64_t q_stride) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", kWho);
+    HICOM_REQUIRE(local_logits && (uintptr_t)local_logits % 4 == 0, HICOM_EINVAL, "%s: local_logits is f32 [max Q_i][sum T_i H W]", kWho);
+    return rmg_fwd(a, nullptr, LocalLogits{local_logits, (long)q_stride});
+}
 
 // The planes and the tokens are the caller's: the workspace and its table region are the ragged multi-guide step's for the base block.
 extern "C" int64_t hicom_compressor_clips_multiguide_workspace_bytes(const hicom_compressor_clips_multiguide_args* a) {

@@ -20,6 +20,7 @@ the fc2 launch dots its fp32 rows (value + residual) with the guide in its epilo
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import native as nv
@@ -213,6 +214,81 @@ def siglip_head_scores_multi(last_hidden_state: torch.Tensor, head, guide_embeds
     logits = torch.empty((Q, x2.shape[0]), dtype=torch.float32, device=x.device)
     nv.head_scores_multi(x2, hid, kpad, guides, u_hi, u_lo, u_scale, c, logits)
     return logits.view((Q,) + tuple(x.shape[:-1]))
+
+
+SCORE_TILE = 32             # tokens of one workgroup of the scores kernels (csrc/head_scores.hip: kHsTok)
+MAX_SCORE_TABLES = 16       # cached (token counts, guide counts) mixes per device
+_score_tables = {}
+
+
+def ragged_score_tables(token_counts, guide_counts):
+    """The tables hicom_head_scores_ragged_fwd reads, on the host (int32): items [B, 8] = {tok0, N, pair0, Q, tile0, 0, 0, 0} and
+    tile_item [sum ceil(N_i / 32)], the item of every tile.  Tiles are counted per item, so no tile crosses into the next item."""
+    N = np.asarray(token_counts, np.int64)
+    Q = np.asarray(guide_counts, np.int64)
+    tiles = (N + SCORE_TILE - 1) // SCORE_TILE
+    first = lambda v: np.concatenate([[0], np.cumsum(v)[:-1]])
+    items = np.zeros((len(N), 8), np.int32)
+    items[:, 0], items[:, 1], items[:, 2], items[:, 3], items[:, 4] = first(N), N, first(Q), Q, first(tiles)
+    return items, np.repeat(np.arange(len(N), dtype=np.int32), tiles)
+
+
+def _device_score_tables(token_counts, guide_counts, dev):
+    """ragged_score_tables on the device, kept per (device, token counts, guide counts): a steady serving loop copies nothing.  At most
+    MAX_SCORE_TABLES mixes are kept; the oldest goes first."""
+    key = (str(dev), tuple(token_counts), tuple(guide_counts))
+    hit = _score_tables.pop(key, None)
+    if hit is None:
+        items, tile_item = ragged_score_tables(token_counts, guide_counts)
+        hit = (torch.from_numpy(items).to(dev), torch.from_numpy(tile_item).to(dev))
+        while len(_score_tables) >= MAX_SCORE_TABLES:
+            _score_tables.pop(next(iter(_score_tables)))
+    _score_tables[key] = hit                                    # (re-entered at the end: the order of the dict is the order of use)
+    return hit
+
+
+def siglip_head_scores_ragged(last_hidden_state: torch.Tensor, head, guide_embeds: torch.Tensor, split_sizes, guide_counts,
+                              hidden_act: str = None) -> torch.Tensor:
+    """The scores of a batch: last_hidden_state bf16 [sum T_i, H, W, D], the stacked tensor of `HIComProjector.forward_ragged_multi_guide`
+    with its `split_sizes` (frames per item) and `guide_counts` (1 <= Q_i <= 32), guide_embeds bf16 [sum Q_i, D], item after item
+    -> fp32 [max Q_i, sum T_i, H, W]: out[q, frames of item i] = guide q of item i . (x_n + head.mlp(head.layernorm(x_n))), raw dot products
+    in front of the 1/sqrt(D) scale as siglip_head_scores_multi returns them, for `forward_ragged_multi_guide(frames_feature, None, ...,
+    local_logits=out)`.  Item i's tokens meet item i's guides only (csrc/head_scores.hip: head_scores_ragged_kernel, DESIGN.md §3.19);
+    planes q >= Q_i of an item's frames are NOT written (uninitialised memory) and the step does not read them.  The tensor holds
+    max Q_i x sum N_i floats: 4.5 MB for 8 clips of 64 frames x 3 guides, 48 MB if one item of that batch has 32 guides -- such a batch is
+    cheaper in two calls.  The head's first half runs once over the whole stack; U and c of all sum Q_i guides in two launches.  The item /
+    tile tables depend on the counts only and stay on the device (a small bounded cache).  Inference only."""
+    from .projector import _require_bf16_cuda
+    from .ragged import check_splits
+    from .ragged_multi_guide import MAX_GUIDES
+    what = "siglip_head_scores_ragged"
+    x = last_hidden_state
+    if not isinstance(x, torch.Tensor) or x.ndim != 4:
+        raise ValueError(f"{what}: last_hidden_state is the stacked [sum T_i, H, W, D] tensor")
+    _require_bf16_cuda("last_hidden_state", x)
+
+    def check_counts(B, counts):
+        if len(counts) != B:
+            raise ValueError(f"{what}: {len(counts)} guide counts for {B} items (one per item)")
+        if any(not 1 <= q <= MAX_GUIDES for q in counts):
+            raise ValueError(f"{what}: guide_counts {counts}: 1 <= Q_i <= {MAX_GUIDES} guides per item")
+    split_sizes, _, guide_counts = check_splits(what, x, split_sizes, "video", guide_counts, check_counts)
+    D = x.shape[-1]
+    if not isinstance(guide_embeds, torch.Tensor) or guide_embeds.ndim != 2 or tuple(guide_embeds.shape) != (sum(guide_counts), D):
+        raise ValueError(f"{what}: guide_embeds is [sum Q_i, D] = [{sum(guide_counts)}, {D}], the guides of item i in the rows [sum_(j<i) Q_j, + Q_i) "
+                         f"(got {tuple(guide_embeds.shape) if isinstance(guide_embeds, torch.Tensor) else None})")
+    _require_bf16_cuda("guide_embeds", guide_embeds)
+    nv.begin_inference()
+    x2, hid, kpad, _ = _head_hidden(x, head, hidden_act, True)
+    fc2 = head.mlp.fc2
+    guides = guide_embeds.contiguous()
+    HW = x.shape[1] * x.shape[2]
+    items, tile_item = _device_score_tables([t * HW for t in split_sizes], guide_counts, x.device)
+    u_hi, u_lo, u_scale, c = nv.head_guide_fold_many(fc2.weight.detach().contiguous(), fc2.bias.detach(), guides, nv.head_fold_ldu(kpad))
+    q_max = max(guide_counts)
+    logits = torch.empty((q_max, x2.shape[0]), dtype=torch.float32, device=x.device)
+    nv.head_scores_ragged(x2, hid, kpad, guides, u_hi, u_lo, u_scale, c, items, tile_item, q_max, logits)
+    return logits.view((q_max,) + tuple(x.shape[:-1]))
 
 
 def _head_hidden(x, head, hidden_act, scores, keep=None):

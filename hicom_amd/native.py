@@ -420,6 +420,9 @@ SIGNATURES = {
     "hicom_head_scores_multi_fwd": (C.c_int, [vp, vp, i64, i64, i32, i32, vp, vp, vp, i64, vp, vp, i32, vp, i64, vp]),
     "hicom_multi_guide_local_logits_fwd": (C.c_int, [vp, vp, i64, Axis, Axis, Axis, i32, i32, f32, vp, vp]),
     "hicom_compressor_multiguide_logits_fwd": (C.c_int, [C.POINTER(CompressorMultiGuideArgs), vp, i64]),
+    "hicom_head_guide_fold_many_fwd": (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "hicom_head_scores_ragged_fwd": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, i64, vp]),
+    "hicom_compressor_ragged_multiguide_logits_fwd": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, i64]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -863,6 +866,39 @@ def head_scores_multi(x2, hid, kpad: int, guides, u_hi, u_lo, u_scale, c, logits
     Q = guides.shape[0]
     _check(lib().hicom_head_scores_multi_fwd(_ptr(x2), _ptr(hid), hid.shape[1], M, D, kpad, _ptr(guides), _ptr(u_hi), _ptr(u_lo), u_hi.shape[1], _ptr(u_scale),
                                              _ptr(c), Q, _ptr(logits), logits.shape[1], _stream()), "hicom_head_scores_multi_fwd")
+
+
+HEAD_FOLD_MANY_PAD = 32     # plane rows behind ceil16(M): a tile of the ragged scores kernel reads up to 32 rows from an item's first
+
+
+def head_guide_fold_many(w2, b2, guides, ldu: int):
+    """head_guide_fold for the M = sum Q_i guide rows of a batch in the same two launches (hicom_head_guide_fold_many_fwd), every row bit
+    for bit the single form's.  Returns (u_hi, u_lo fp16 [rows, ldu], u_scale, c f32 [rows]), rows = ceil16(M) + 32; rows >= M are zero
+    with scale 1 and c = 0."""
+    D, inter = w2.shape
+    M = guides.shape[0]
+    rows = (M + 15) // 16 * 16 + HEAD_FOLD_MANY_PAD
+    dev = guides.device
+    u = torch.empty((2, rows, ldu), dtype=torch.float16, device=dev)
+    sc = torch.empty((2, rows), dtype=torch.float32, device=dev)
+    ws = torch.empty((HEAD_FOLD_SLICES * M * ldu,), dtype=torch.float32, device=dev)
+    _check(lib().hicom_head_guide_fold_many_fwd(_ptr(w2), _ptr(b2), D, inter, _ptr(guides), M, _ptr(u[0]), _ptr(u[1]), ldu, _ptr(sc[0]), _ptr(sc[1]),
+                                                _ptr(ws), ws.numel() * 4, _stream()), "hicom_head_guide_fold_many_fwd")
+    return u[0], u[1], sc[0], sc[1]
+
+
+def head_scores_ragged(x2, hid, kpad: int, guides, u_hi, u_lo, u_scale, c, items, tile_item, q_max: int, logits):
+    """logits f32 [q_max, q_stride]: guide q of item i at [q, tok0_i + n] (hicom_head_scores_ragged_fwd).  x2 bf16 [sum N_i, D], hid fp16
+    [sum N_i, ld], the planes of head_guide_fold_many; items int32 device [B, 8] = {tok0, N, pair0, Q, tile0, 0, 0, 0}, tile_item int32
+    device [ntiles]."""
+    _check(lib().hicom_head_scores_ragged_fwd(_ptr(x2), _ptr(hid), hid.shape[1], x2.shape[1], kpad, _ptr(guides), _ptr(u_hi), _ptr(u_lo), u_hi.shape[1],
+                                              _ptr(u_scale), _ptr(c), _ptr(items), _ptr(tile_item), items.shape[0], tile_item.shape[0], q_max, _ptr(logits),
+                                              logits.shape[1], _stream()), "hicom_head_scores_ragged_fwd")
+
+
+def compressor_ragged_multiguide_logits_fwd(args: CompressorRaggedMultiGuideArgs, local_logits: int, q_stride: int):
+    """The ragged multi-guide step with the local logits given (address of f32 [max Q_i][q_stride]); args.fe is not read."""
+    _check(lib().hicom_compressor_ragged_multiguide_logits_fwd(C.byref(args), local_logits, q_stride), "hicom_compressor_ragged_multiguide_logits_fwd")
 
 
 def clip_adapt_prepare_workspace(N: int, E: int, ak: SegAdaptor, av: SegAdaptor, what: str = "prepare_clip") -> int:

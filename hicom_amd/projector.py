@@ -1312,7 +1312,7 @@ class HIComProjector(nn.Module):
         return clip_stream_group_adapt.ClipStreamGroupAdapt(self, guide_embeds, guide_counts, H, W, max_frames, image_newline)
 
     def forward_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
-                                   chunks=None):
+                                   chunks=None, local_logits=None):
         """B items of UNEQUAL length and mixed modality, item i with its own Q_i instructions, in one native call -- a Video-MME style
         evaluation batch (several videos x 3 questions), or a batch of multi-question items.  frames_feature / frames_embed bf16
         [sum T_i, H, W, E], split_sizes and modals as for forward_ragged (frames_embed may be None); guide_counts the B positive ints Q_i,
@@ -1328,10 +1328,14 @@ class HIComProjector(nn.Module):
         its share of 2 x #CUs work units by tiles x passes).  With `chunks` given, a pair's result depends on its item's tokens, its own
         guide and its row's pass only.
         Which path when: DESIGN.md §3.9 has the measured table against the loop of forward_multi_guide, forward_ragged on replicated
-        tokens and the loop of forward()."""
+        tokens and the loop of forward().
+        `local_logits` = fp32 [max Q_i, sum T_i, H, W] raw dot products frames_embed_n . guide from `hicom_amd.siglip_head_scores_ragged`
+        (guide q of item i in plane q, on the item's frames; planes q >= Q_i of an item are not read), passed with frames_embed=None: the
+        local stage then reads frames_feature and Q_i floats per token, frames_embed is never made, and the head's second GEMM is not run
+        (DESIGN.md §3.19).  The global rows do not change."""
         from . import ragged_multi_guide
         return ragged_multi_guide.run_ragged_multi_guide(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals,
-                                                         image_newline, chunks)
+                                                         image_newline, chunks, local_logits)
 
     def forward_stepwise(self, frames_feature, frames_embed, guide_embed, modal, image_newline=None):
         """Same result, one C-ABI call per operator (anyres dict inputs; also the cross-check of the

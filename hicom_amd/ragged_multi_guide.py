@@ -9,7 +9,11 @@ checks, plan and plan cache are segments.py's; the plain release recipe only.  P
 plan holds the host item descriptors and guide counts, and the head of its workspace holds the device tables.
 
 `plan_tables` / `table_image` restate the table arithmetic of hicom_compressor_ragged_multiguide_prepare in Python: the call takes the
-pairs' row counts from it, and the tests hold the device's table region against it."""
+pairs' row counts from it, and the tests hold the device's table region against it.
+
+Logits form: with `local_logits` = fp32 [max Q_i, sum T_i, H, W] from `siglip_head_scores_ragged` the local stage takes
+its scores from that tensor and reads the value rows only (hicom_compressor_ragged_multiguide_logits_fwd: the same sequence, workspace and
+tables, another launch 3); frames_embed is None.  The two forms do not share a plan: the key carries the form."""
 from __future__ import annotations
 
 import ctypes as C
@@ -141,14 +145,40 @@ def pair_views(plan, out):
     return [v.view(q, r, plan.hidden) for v, q, r in zip(out.split([q * r for q, r in zip(t.Q, t.rows)]), t.Q, t.rows)]
 
 
-def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None):
+def check_logits(ll, fe, ff, guide_counts):
+    """The checks of local_logits behind the scope checks of the keyed call and in front of any device work (multi_guide.check_logits for
+    the stack): frames_embed must be None, fp32 device [max Q_i, sum T_i, H, W]."""
+    from .multi_guide import _require_f32_cuda
+    if fe is not None:
+        raise ValueError(f"{WHAT}: local_logits replaces frames_embed: pass frames_embed=None")
+    want = (max(guide_counts),) + tuple(ff.shape[:3])
+    if not isinstance(ll, torch.Tensor) or tuple(ll.shape) != want:
+        raise ValueError(f"{WHAT}: local_logits is [max Q_i, sum T_i, H, W] = [{', '.join(map(str, want))}], plane q holding guide q of every item on "
+                         f"the item's frames (got {tuple(ll.shape) if isinstance(ll, torch.Tensor) else None})")
+    _require_f32_cuda("local_logits", ll)
+
+
+def plan_key(split_sizes, modals, H, W, E, has_fe, nl, out_dtype, stream, chunks, recipe, adapt_k, adapt_v, guide_counts, logits=False):
+    """The key of a plan; the keyed form's is what it was before the logits form (so its plans and their order in the store do not change)."""
+    key = (split_sizes, modals, H, W, E, has_fe, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0), recipe, adapt_k, adapt_v,
+           guide_counts)
+    return key + ("logits",) if logits else key
+
+
+def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None, local_logits=None):
     B, H, W, E, split_sizes, guide_counts, modals = check_inputs(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl)
+    if local_logits is not None:
+        check_logits(local_logits, fe, ff, guide_counts)
     dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, WHAT, ff, fe, guides, nl)
-    key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
-           seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v, guide_counts)
+    key = plan_key(split_sizes, modals, H, W, E, fe is not None, nl, out_dtype, stream, chunks, seg.seg_recipe(proj), proj.local_compressor.adapt_k,
+                   proj.local_compressor.adapt_v, guide_counts, local_logits is not None)
     plan = seg.cached_plan(proj, STORE, key, lambda: build_plan(proj, WHAT, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev,
                                                                 stream))       # (no adaptor recipe: check_inputs refuses it)
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
     seg.patch_io(plan.io, ff, fe, guides, nl, out, stream)      # (the newline pointer whenever given: items differ in their newline rows)
-    nv.compressor_ragged_multiguide_fwd(plan.args)
+    if local_logits is not None:
+        ll = local_logits.contiguous()
+        nv.compressor_ragged_multiguide_logits_fwd(plan.args, ll.data_ptr(), ff.shape[0] * H * W)
+    else:
+        nv.compressor_ragged_multiguide_fwd(plan.args)
     return pair_views(plan, out)

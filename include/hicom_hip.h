@@ -1543,6 +1543,33 @@ int hicom_multi_guide_local_logits_fwd(const void* value, const float* logits, i
                                        int32_t Q, int32_t nwin, float scale, void* ctx_f16, void* stream);
 int hicom_compressor_multiguide_logits_fwd(const hicom_compressor_multiguide_args* args, const float* local_logits, int64_t q_stride);
 
+/* ---- ragged multi-guide step without frames_embed: head scores per item -------------------------------------------------
+ * B items stacked, item i with N_i tokens and its own Q_i guides (rows [pair0_i, pair0_i + Q_i) of guides [M][D], M = sum Q_i): item i's
+ * tokens meet item i's guides only.
+ *
+ * hicom_head_guide_fold_many_fwd: hicom_head_guide_fold_fwd for 1 <= M <= 4096 guide rows in the same two launches, every row bit for bit
+ * what the single form gives it.  The planes hold ceil16(M) + 32 rows (u_hi / u_lo fp16 [rows][ldu], u_scale / c f32 [rows]); rows >= M are
+ * zero with scale 1 and c = 0.  ws: 16 M ldu floats.
+ *
+ * hicom_head_scores_ragged_fwd (one launch, one workgroup per tile of 32 tokens of ONE item): items is a DEVICE table [B][8] of
+ * {tok0, N, pair0, Q, tile0, 0, 0, 0} (first token in the stack, tokens, first guide row, guides, first tile; tiles are counted per item,
+ * ceil(N_i / 32) each), tile_item a DEVICE array [ntiles] with the item of every tile, q_max = max Q_i (1 .. 32).  x, hid, ld, D, kpad, ldu
+ * as for hicom_head_scores_multi_fwd; the planes are those of hicom_head_guide_fold_many_fwd (the rows behind an item's guides inside a tile
+ * of 16 or 32 guide rows are read, so the 32 pad rows must exist).  logits f32 [q_max][q_stride], q_stride >= sum N_i: guide q of item i at
+ * logits[q q_stride + tok0_i + n]; cells with q >= Q_i are not written.  That is q_max sum N_i floats: one item with many guides widens
+ * every item's column.  With B = 1 the result equals hicom_head_scores_multi_fwd's bit for bit.  The tables are not read on the host: what
+ * they hold is the caller's responsibility.
+ *
+ * hicom_compressor_ragged_multiguide_logits_fwd is hicom_compressor_ragged_multiguide_fwd with the local stage taking its scores from
+ * local_logits (that layout; planes q >= Q_i of an item are not read): the same launch count, the same workspace, size function and
+ * prepare call; args->fe is not read and may be NULL. */
+int hicom_head_guide_fold_many_fwd(const void* w2, const void* b2, int32_t D, int32_t inter, const void* guides, int32_t M, void* u_hi, void* u_lo,
+                                   int64_t ldu, float* u_scale, float* c, void* ws, int64_t ws_bytes, void* stream);
+int hicom_head_scores_ragged_fwd(const void* x, const void* hid, int64_t ld, int32_t D, int32_t kpad, const void* guides, const void* u_hi,
+                                 const void* u_lo, int64_t ldu, const float* u_scale, const float* c, const int32_t* items, const int32_t* tile_item,
+                                 int32_t B, int32_t ntiles, int32_t q_max, float* logits, int64_t q_stride, void* stream);
+int hicom_compressor_ragged_multiguide_logits_fwd(const hicom_compressor_ragged_multiguide_args* args, const float* local_logits, int64_t q_stride);
+
 #ifdef __cplusplus
 }
 #endif
