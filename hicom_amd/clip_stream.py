@@ -54,6 +54,26 @@ def _require_bf16_cuda(name, t):
     check(name, t)
 
 
+def _require_f32_cuda(name, t):
+    from .multi_guide import _require_f32_cuda as check
+    check(name, t)
+
+
+LOGITS_KEY = ("logits",)                         # what the plan key of a logits push has behind the keyed push's fields
+NOT_LINEAR = ("local_logits has no form on the k / v adaptor recipe: the keys pass an MLP and a LayerNorm blend in front of the score, so it is "
+              "not linear in frames_embed; push frames_embed")
+
+
+def logits_stride(what, ll, planes, tokens):
+    """The leading stride of local_logits [planes, ...tokens] as q_stride, behind the check that the planes are contiguous and `tokens`
+    floats or more apart (one plane: its stride is never used)."""
+    if not ll[0].is_contiguous():
+        raise ValueError(f"{what}: local_logits must be contiguous in its last three dimensions [T, H, W] (the leading stride travels as q_stride)")
+    if planes > 1 and ll.stride(0) < tokens:
+        raise ValueError(f"{what}: local_logits: the guides' planes are {ll.stride(0)} floats apart, a plane holds {tokens}")
+    return ll.stride(0) if planes > 1 else tokens
+
+
 def prefix_layout(proj, groups, gh, gw, has_newline):
     """(row at which a chunk behind `groups` window groups starts, HIComProjector._layout of that prefix).  The rows of a prefix that depend
     on the whole clip -- the `one_token` newline row behind the last token: a layout with newline rows but no interleaving -- belong to
@@ -162,6 +182,7 @@ class ClipStreamBase:
     NAME = WHAT = STORE = None                       # what the messages call the object and the entry that opens it; the plan store
     RECIPE, RECIPE_WORDS = "plain", "the plain release recipe"       # segments.seg_recipe of the modules the stream takes
     MULTI, GUIDE = False, "guide_embed"              # the guide is [E] (kept as `guide`) / the [Q, E] block (`guides`); the argument's name
+    NO_LOGITS = None                                 # why push(local_logits=) is refused by the class (None: it takes them)
 
     def __init__(self, proj, guide, H, W, max_frames, image_newline=None):
         from .projector import _out_dtype, _refuse_grad
@@ -176,6 +197,7 @@ class ClipStreamBase:
         self.newline = None if image_newline is None else image_newline.contiguous()
         self.device, self.out_dtype = guide.device, _out_dtype(proj)
         self.has_fe = None                        # decided by the first push; every chunk of a clip agrees
+        self.has_logits = None                    # the third form: the chunks come with local_logits (has_fe is then False)
         self.frames = 0
         self.n_pushes = 0
         self.cap_rows = proj._layout((max_frames // self.kt, self.gh, self.gw), "video", image_newline is not None, False).n_rows
@@ -242,12 +264,26 @@ class ClipStreamBase:
         """Local rows of the frames pushed so far, as forward() on them would lay them out."""
         return self.proj._layout((self.frames // self.kt, self.gh, self.gw), "video", self.newline is not None, False).n_rows
 
-    def _check_chunk(self, ff, fe, counters=None):
+    def _check_logits(self, what, ll, fe, Tc):
+        """The refusals of local_logits for one chunk of Tc frames: beside frames_embed, shape, dtype, device, autograd, layout."""
+        if fe is not None:
+            raise ValueError(f"{what}: local_logits replaces frames_embed: pass frames_embed=None")
+        want = ((self.Q,) if self.MULTI else ()) + (Tc, self.H, self.W)
+        if not isinstance(ll, torch.Tensor) or tuple(ll.shape) != want:
+            raise ValueError(f"{what}: local_logits is {'[Q, Tc, H, W]' if self.MULTI else '[Tc, H, W]'} = [{', '.join(map(str, want))}], the raw dot "
+                             f"products of the chunk's own tokens (got {tuple(ll.shape) if isinstance(ll, torch.Tensor) else None})")
+        _require_f32_cuda("local_logits", ll)
+        if ll.requires_grad:
+            raise RuntimeError(f"{what} builds no autograd graph: local_logits requires grad (compute it under torch.no_grad())")
+        logits_stride(what, ll if self.MULTI else ll.unsqueeze(0), self.Q, Tc * self.H * self.W)
+
+    def _check_chunk(self, ff, fe, counters=None, ll=None):
         """The chunk against the stream's scope and the clip's counters, in front of any device work; returns Tc.  counters: the (frames,
-        has_fe) pair the chunk continues (None: the stream's own; a ClipStreamGroup passes those of the chunk's slot)."""
+        has_fe, has_logits) triple the chunk continues (None: the stream's own; a ClipStreamGroup passes those of the chunk's slot).  ll: the
+        chunk's local_logits, or None."""
         from .projector import _refuse_grad
         what, WHAT = f"{self.NAME}.push", self.WHAT
-        frames, has_fe = (self.frames, self.has_fe) if counters is None else counters
+        frames, has_fe, has_logits = (self.frames, self.has_fe, self.has_logits) if counters is None else (tuple(counters) + (None,))[:3]
         if isinstance(ff, dict) or isinstance(fe, dict):
             raise NotImplementedError(f"{what}: anyres dict inputs have no clip-stream path (call forward() per image)")
         if seg.seg_recipe(self.proj) != self.RECIPE or self.proj.local_compressor.readout[0].weight.dtype != torch.bfloat16:
@@ -266,8 +302,12 @@ class ClipStreamBase:
                 raise NotImplementedError(f"{what}: {name} dtype {getattr(t, 'dtype', type(t))}; the clip stream takes bfloat16 tokens")
         if fe is not None and tuple(fe.shape) != tuple(ff.shape):
             raise ValueError(f"{what}: frames_embed {tuple(fe.shape)} vs frames_feature {tuple(ff.shape)}")
-        if has_fe is not None and (fe is not None) != has_fe:
-            raise ValueError(f"{what}: this clip's chunks came {'with' if has_fe else 'without'} frames_embed so far")
+        if ll is not None:
+            self._check_logits(what, ll, fe, Tc)
+        # the form of a clip: with frames_embed, without it, or with local_logits; every chunk agrees
+        if has_fe is not None and (bool(has_logits) != (ll is not None) or (ll is None and (fe is not None) != has_fe)):
+            was = "with local_logits" if has_logits else f"{'with' if has_fe else 'without'} frames_embed"
+            raise ValueError(f"{what}: this clip's chunks came {was} so far")
         _refuse_grad(self.proj, what)
         _require_bf16_cuda("frames_feature", ff)
         if fe is not None:
@@ -275,20 +315,27 @@ class ClipStreamBase:
         self._chunk_limits(what, self.proj, Tc, self.H, self.W, self.E)
         return Tc
 
-    def push(self, frames_feature, frames_embed=None):
+    def push(self, frames_feature, frames_embed=None, local_logits=None):
         """The next Tc frames of the clip (bf16 [Tc, H, W, E], Tc a positive multiple of kt; frames_embed None: the keys are
-        frames_feature).  Returns a view of this chunk's local output rows in their final place in the stream's output buffer
-        ([chunk rows, hidden]; [Q, chunk rows, hidden], strided over q, for Q guides), complete on the caller's stream; the chunk is not
-        referenced afterwards."""
-        Tc = self._check_chunk(frames_feature, frames_embed)
+        frames_feature).  local_logits (frames_embed None): fp32 [Tc, H, W] ([Q, Tc, H, W] for Q guides) from head_scores --
+        the local stage takes its scores from it and reads the value rows only; a clip keeps one of the three forms.  Returns a view of this
+        chunk's local output rows in their final place in the stream's output buffer ([chunk rows, hidden]; [Q, chunk rows, hidden], strided
+        over q, for Q guides), complete on the caller's stream; the chunk is not referenced afterwards."""
+        if local_logits is not None and self.NO_LOGITS:
+            raise NotImplementedError(f"{self.NAME}.push: {self.NO_LOGITS}")
+        Tc = self._check_chunk(frames_feature, frames_embed, None, local_logits)
         ff = frames_feature.contiguous()
         fe = frames_embed.contiguous() if frames_embed is not None else None
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(Tc, fe is not None, stream), lambda: self._build_plan(Tc, fe is not None))
+        key = self._plan_key(Tc, fe is not None, stream) + (LOGITS_KEY if local_logits is not None else ())
+        plan = seg.cached_plan(self.proj, self.STORE, key, lambda: self._build_plan(Tc, fe is not None))
         row0, nl_group, newline_rows, row1 = chunk_rows(self.proj, self.frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
-        self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
+        if local_logits is None:                  # (the keyed call as it always was: ClipStreamAdapt._launch has no local_logits keyword)
+            self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream)
+        else:
+            self._launch(plan, ff, fe, self.frames, row0, nl_group, newline_rows, stream, local_logits=local_logits)
         self.cur ^= 1
-        self.has_fe = fe is not None
+        self.has_fe, self.has_logits = fe is not None, local_logits is not None
         self.frames += Tc
         self.n_pushes += 1
         return self.out[:, row0:row1] if self.MULTI else self.out[row0:row1]
@@ -317,7 +364,7 @@ class ClipStreamBase:
                 raise ValueError(f"{self.NAME}.reset: {new.shape[0]} guides on a stream opened for Q={self.Q} (the buffers are sized by Q)")
             _require_bf16_cuda(self.GUIDE, new)
         _refuse_grad(self.proj, f"{self.NAME}.reset")
-        self.frames, self.n_pushes, self.has_fe = 0, 0, None
+        self.frames, self.n_pushes, self.has_fe, self.has_logits = 0, 0, None, None
         self._prepare(new)
 
 
@@ -368,12 +415,21 @@ class ClipStream(ClipStreamBase):
         a.rows = self.nh
         return StreamPlan(a, ws, keep, self.proj.local_compressor.readout_f16)
 
-    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
+    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream, local_logits=None):
         a = plan.args
         self._patch_common(a, ff, fe, t0, row0, nl_group, newline_rows, stream)
         a.pe_hi = self.pe_hi.data_ptr() if self.pe_hi is not None else None
         a.pe_lo = self.pe_lo.data_ptr() if self.pe_lo is not None else None
-        nv.compressor_stream_push(a)
+        if local_logits is None:
+            nv.compressor_stream_push(a)
+        else:
+            nv.compressor_stream_push_logits(a, local_logits.data_ptr())
+
+    def head_scores(self, last_hidden_state, head, hidden_act=None):
+        """fp32 [Tc, H, W]: what push(frames_feature, None, local_logits=) takes for the chunk whose tower output is last_hidden_state --
+        siglip_head_scores with the stream's guide.  U and c are folded from the live weights on every call: nothing is kept."""
+        from .encoder import siglip_head_scores
+        return siglip_head_scores(last_hidden_state, head, self.guide, hidden_act)
 
     def _finish_device(self, row0, tail):
         if tail:                                                                           # whole-clip newline rows (`one_token`)
@@ -479,9 +535,19 @@ class ClipStreamMulti(ClipStreamBase):
         (a.part_m, a.part_l, a.part_acc, a.scores, a.scratch, a.set_ml, a.set_acc, a.ctx_f16, a.hid_f16, a.loc) = at[:10]
         return ws, [p if n else None for p, n in zip(at[10:], extra)], keep
 
-    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream):
+    def _launch(self, plan, ff, fe, t0, row0, nl_group, newline_rows, stream, local_logits=None):
         self._patch(plan.args, ff, fe, t0, row0, nl_group, newline_rows, stream)
-        nv.compressor_stream_push_multi(plan.args)
+        if local_logits is None:
+            nv.compressor_stream_push_multi(plan.args)
+        else:
+            q_stride = logits_stride(f"{self.NAME}.push", local_logits, self.Q, ff.shape[0] * self.H * self.W)
+            nv.compressor_stream_push_multi_logits(plan.args, local_logits.data_ptr(), q_stride)
+
+    def head_scores(self, last_hidden_state, head, hidden_act=None):
+        """fp32 [Q, Tc, H, W]: what push(frames_feature, None, local_logits=) takes for the chunk whose tower output is last_hidden_state --
+        siglip_head_scores_multi with the stream's guides.  U and c are folded from the live weights on every call: nothing is kept."""
+        from .encoder import siglip_head_scores_multi
+        return siglip_head_scores_multi(last_hidden_state, head, self.guides, hidden_act)
 
     def _patch(self, a, ff, fe, t0, row0, nl_group, newline_rows, stream):
         """_patch_common on the plain push block `a`, and what only the multi-guide block has."""
@@ -516,6 +582,10 @@ class ClipStreamAdapt(ClipStreamMulti):
     per chunk."""
     NAME, WHAT, STORE = "ClipStreamAdapt", "open_stream_adapt", STORE_ADAPT
     RECIPE, RECIPE_WORDS = "adaptkv", "the k / v adaptor release recipe"
+    NO_LOGITS = NOT_LINEAR                           # (push is the base's: its local_logits keyword raises NotImplementedError here)
+
+    def head_scores(self, last_hidden_state, head, hidden_act=None):
+        raise NotImplementedError(f"{self.NAME}.head_scores: {NOT_LINEAR}")
 
     def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
         dims = super()._scope(proj, guide_embeds, H, W, max_frames, image_newline)

@@ -55,6 +55,8 @@ class ClipStreamGroup(cs.ClipStreamBase):
     MULTI, GUIDE = True, "guide_embeds"          # the guides come as one [sum Q_s, E] block: Q of the base is M, the pairs
     PAIRS = False                                # the push block has M, q and pair0 (ClipStreamGroupMulti); here a slot is its one pair
     STRIDE, ROWS = "slot_stride", "slot_rows"    # the push block's fields for the output's stride and rows per slot / pair
+    NO_LOGITS = ("local_logits has no form on the group of one guide per slot (its local stage is fused into a kernel of its own); open the group "
+                 "with open_stream_group_multi(guide_counts=(1,) * B), which takes them")
 
     def __init__(self, proj, guide_embeds, H, W, max_frames, image_newline=None):
         super().__init__(proj, guide_embeds, H, W, max_frames, image_newline)
@@ -63,6 +65,7 @@ class ClipStreamGroup(cs.ClipStreamBase):
             self.guide_counts, self.pair0 = (1,) * self.B, list(range(self.B))
         self.frames = [0] * self.B
         self.has_fe = [None] * self.B            # per slot, decided by the slot's first push; every chunk of a clip agrees
+        self.has_logits = [None] * self.B        # per slot: the clip's chunks come with local_logits (has_fe is then False)
         self._spans = {}
 
     def _chunk_limits(self, what, proj, Tc, H, W, E):
@@ -156,7 +159,7 @@ class ClipStreamGroup(cs.ClipStreamBase):
         plan's refresh).  Here nothing, and the plan follows the readout weights."""
         return [], self.proj.local_compressor.readout_f16
 
-    def _launch(self, plan, ff, fe, slots, t0s, row0s, stream):
+    def _launch(self, plan, ff, fe, slots, t0s, row0s, stream, local_logits=None):
         a = getattr(plan.args, "base", plan.args)
         a.B = self.B                             # of THIS group, as M and pair0: plans are shared by the groups of a module, and the C checks use them
         a.ff, a.fe, a.guide = ff.data_ptr(), (fe.data_ptr() if fe is not None else None), self.guides.data_ptr()
@@ -174,7 +177,10 @@ class ClipStreamGroup(cs.ClipStreamBase):
         if self.PAIRS:
             a.M, a.pair0[:len(slots)] = self.M, [self.pair0[s] for s in slots]
         a.stream = stream
-        self._native()[3](plan.args)
+        if local_logits is None:
+            self._native()[3](plan.args)
+        else:
+            self._push_logits(plan.args, local_logits, ff.shape[0] * self.H * self.W, max(self.guide_counts[s] for s in slots))
 
     # -- the public surface ---------------------------------------------------------------------------------------------------------------
     def _slot(self, what, slot):
@@ -187,8 +193,24 @@ class ClipStreamGroup(cs.ClipStreamBase):
         slot = self._slot(f"{self.NAME}.rows", slot)
         return self.proj._layout((self.frames[slot] // self.kt, self.gh, self.gw), "video", self.newline is not None, False).n_rows
 
-    def _check_push(self, ff, fe, split_sizes, slots):
-        """Every refusal of a push, in front of any device work: (chunk lengths, slots)."""
+    def _check_logits(self, what, ll, fe, Tc):
+        """(the base's per-chunk hook: a group checks the logits of the whole stack once, in _check_stack_logits)"""
+
+    def _check_stack_logits(self, what, ll, fe, ff, slots):
+        """The refusals of local_logits for the stack of a tick: beside frames_embed, shape, dtype, device, autograd, layout."""
+        if fe is not None:
+            raise ValueError(f"{what}: local_logits replaces frames_embed: pass frames_embed=None")
+        want = (max(self.guide_counts[s] for s in slots),) + tuple(ff.shape[:3])
+        if not isinstance(ll, torch.Tensor) or tuple(ll.shape) != want:
+            raise ValueError(f"{what}: local_logits is [max Q over the tick's slots, sum Tc, H, W] = [{', '.join(map(str, want))}], plane q holding guide "
+                             f"q of every item's slot on the item's frames (got {tuple(ll.shape) if isinstance(ll, torch.Tensor) else None})")
+        cs._require_f32_cuda("local_logits", ll)
+        if ll.requires_grad:
+            raise RuntimeError(f"{what} builds no autograd graph: local_logits requires grad (compute it under torch.no_grad())")
+        cs.logits_stride(what, ll, want[0], ff.shape[0] * self.H * self.W)
+
+    def _check_push(self, ff, fe, split_sizes, slots, ll=None):
+        """Every refusal of a push, in front of any device work: (chunk lengths, slots).  ll: the tick's local_logits, or None."""
         what = f"{self.NAME}.push"
         if isinstance(ff, dict) or isinstance(fe, dict):
             raise NotImplementedError(f"{what}: anyres dict inputs have no clip-stream path (call forward() per image)")
@@ -207,14 +229,16 @@ class ClipStreamGroup(cs.ClipStreamBase):
             raise ValueError(f"{what}: split_sizes {list(tcs)} add up to {sum(tcs)} frames, frames_feature has {ff.shape[0]}")
         if fe is not None and (not isinstance(fe, torch.Tensor) or tuple(fe.shape) != tuple(ff.shape)):
             raise ValueError(f"{what}: frames_embed {tuple(getattr(fe, 'shape', ()))} vs frames_feature {tuple(ff.shape)}")
+        if ll is not None:
+            self._check_stack_logits(what, ll, fe, ff, slots)
         # the base's chunk check per item, with the slot's counters; items that agree in length and counters (B streams in lock step) are
         # slices of one stack and share one check
         t, seen = 0, set()
         for n, s in zip(tcs, slots):
-            case = (n, self.frames[s], self.has_fe[s])
+            case = (n, self.frames[s], self.has_fe[s], self.has_logits[s])
             if case not in seen:
                 seen.add(case)
-                self._check_chunk(ff[t:t + max(n, 0)], None if fe is None else fe[t:t + max(n, 0)], case[1:])
+                self._check_chunk(ff[t:t + max(n, 0)], None if fe is None else fe[t:t + max(n, 0)], case[1:], ll)
             t += n
         return tcs, slots
 
@@ -225,23 +249,34 @@ class ClipStreamGroup(cs.ClipStreamBase):
             hit = self._spans[(frames, Tc)] = cs.chunk_rows(self.proj, frames // self.kt, Tc // self.kt, self.gh, self.gw, self.newline is not None)
         return hit
 
-    def push(self, frames_feature, frames_embed=None, split_sizes=(), slots=None):
+    def push(self, frames_feature, frames_embed=None, split_sizes=(), slots=None, local_logits=None):
         """The next chunks of the slots named: frames_feature bf16 [sum Tc_i, H, W, E] (frames_embed None: the keys are frames_feature; all or
         none within a call), split_sizes the chunk lengths Tc_i (positive multiples of kt), slots the slot of each item (module docstring).
+        local_logits (ClipStreamGroupMulti only; frames_embed None): fp32 [max Q over the tick's slots, sum Tc_i, H, W] from
+        head_scores for the same split_sizes and slots; a slot's clip keeps one of the three forms.
         Returns one view per item: that chunk's local rows ([chunk rows, hidden]; PAIRS: of every guide of the slot, [Q_slot, chunk rows,
         hidden]) in their final place in the output storage, complete on the caller's stream; the stack is not referenced afterwards."""
-        tcs, slots = self._check_push(frames_feature, frames_embed, split_sizes, slots)
+        if local_logits is None:
+            tcs, slots = self._check_push(frames_feature, frames_embed, split_sizes, slots)
+        elif self.NO_LOGITS:
+            raise NotImplementedError(f"{self.NAME}.push: {self.NO_LOGITS}")
+        else:
+            tcs, slots = self._check_push(frames_feature, frames_embed, split_sizes, slots, local_logits)
         ff = frames_feature.contiguous()
         fe = frames_embed.contiguous() if frames_embed is not None else None
         stream = torch.cuda.current_stream(self.device).cuda_stream
         # what an item gives the plan key: its length and, PAIRS, its guide count, which decides its work units
         items = tuple((n, self.guide_counts[s]) for n, s in zip(tcs, slots)) if self.PAIRS else tcs
-        plan = seg.cached_plan(self.proj, self.STORE, self._plan_key(items, fe is not None, stream), lambda: self._build_plan(items, fe is not None, stream))
+        key = self._plan_key(items, fe is not None, stream) + (cs.LOGITS_KEY if local_logits is not None else ())
+        plan = seg.cached_plan(self.proj, self.STORE, key, lambda: self._build_plan(items, fe is not None, stream))
         spans = [self._span(self.frames[s], n) for n, s in zip(tcs, slots)]
-        self._launch(plan, ff, fe, slots, [self.frames[s] for s in slots], [sp[0] for sp in spans], stream)
+        if local_logits is None:                  # (the keyed call as it always was: a class outside the feature may keep _launch's old signature)
+            self._launch(plan, ff, fe, slots, [self.frames[s] for s in slots], [sp[0] for sp in spans], stream)
+        else:
+            self._launch(plan, ff, fe, slots, [self.frames[s] for s in slots], [sp[0] for sp in spans], stream, local_logits=local_logits)
         for n, s in zip(tcs, slots):
             self.frames[s] += n
-            self.has_fe[s] = fe is not None
+            self.has_fe[s], self.has_logits[s] = fe is not None, local_logits is not None
         self.n_pushes += 1
         return [self.out[self._pairs(s) if self.PAIRS else s, sp[0]:sp[3]] for s, sp in zip(slots, spans)]
 
@@ -272,5 +307,5 @@ class ClipStreamGroup(cs.ClipStreamBase):
             cs.stream_scope(self.proj, guide, self.H, self.W, self.max_frames, self.newline, _SlotGuide)
             cs._require_bf16_cuda("guide_embed", guide)
         _refuse_grad(self.proj, what)
-        self.frames[slot], self.has_fe[slot] = 0, None
+        self.frames[slot], self.has_fe[slot], self.has_logits[slot] = 0, None, None
         self._prepare(guide, slot)

@@ -44,6 +44,10 @@ class ClipStreamGroupAdapt(cgm.ClipStreamGroupMulti):
     NAME, WHAT, STORE = "ClipStreamGroupAdapt", "open_stream_group_adapt", STORE_GROUP_ADAPT
     RECIPE, RECIPE_WORDS = "adaptkv", "the k / v adaptor release recipe"
     SLOT_GUIDES = _SlotGuides
+    NO_LOGITS = cs.NOT_LINEAR                    # (push is the base's: its local_logits keyword raises NotImplementedError here)
+
+    def head_scores(self, last_hidden_state, head, split_sizes, slots=None, hidden_act=None):
+        raise NotImplementedError(f"{self.NAME}.head_scores: {cs.NOT_LINEAR}")
 
     def _scope(self, proj, guide_embeds, H, W, max_frames, image_newline):
         dims = super()._scope(proj, guide_embeds, H, W, max_frames, image_newline)

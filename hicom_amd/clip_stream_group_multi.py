@@ -77,6 +77,7 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
     NAME, WHAT, STORE = "ClipStreamGroupMulti", "open_stream_group_multi", STORE_GROUP_MULTI
     PAIRS, STRIDE, ROWS = True, "pair_stride", "pair_rows"
     SLOT_GUIDES = _SlotGuides                    # what reset(slot, guides) tells stream_scope: the entry's name and the class's recipe
+    NO_LOGITS = None                             # push(local_logits=) is built for this class
 
     def __init__(self, proj, guide_embeds, guide_counts, H, W, max_frames, image_newline=None):
         # the open sequence is ClipStreamBase's (scope, allocate, prepare); _scope takes the counts from here and sets B (the slots, what
@@ -113,6 +114,25 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
 
     def _row_shapes(self, M, nh):
         return (M * nh,), (M * nh + 31) // 32 * 32       # whole 32-row passes, as the ragged multi-guide step pads its planes
+
+    def _push_logits(self, args, local_logits, tokens, q_max):
+        """The logits form of the native push: the same block, workspace and tables, launch 1 on the tick's logits."""
+        q_stride = cs.logits_stride(f"{self.NAME}.push", local_logits, q_max, tokens)
+        nv.compressor_stream_group_multi_push_logits(args, local_logits.data_ptr(), q_stride)
+
+    def head_scores(self, last_hidden_state, head, split_sizes, slots=None, hidden_act=None):
+        """fp32 [max Q over the tick's slots, sum Tc_i, H, W]: what push(frames_feature, None, split_sizes, slots, local_logits=) takes for the
+        same split_sizes and slots -- siglip_head_scores_ragged with the guides of the tick's slots gathered item after item (the order of
+        `slots`, not of the group) and those slots' guide counts.  U and c are folded from the live weights on every call: nothing is kept."""
+        from .encoder import siglip_head_scores_ragged
+        what = f"{self.NAME}.head_scores"
+        tcs = tuple(int(n) for n in split_sizes)
+        slots = tuple(range(self.B)) if slots is None and len(tcs) == self.B else slots
+        if slots is None or len(slots) != len(tcs):
+            raise ValueError(f"{what}: slots names the slot of each of the {len(tcs)} items (the default is range(B) for B = {self.B} items)")
+        slots = tuple(self._slot(what, s) for s in slots)
+        guides = torch.cat([self.guides[self._pairs(s)] for s in slots])
+        return siglip_head_scores_ragged(last_hidden_state, head, guides, tcs, [self.guide_counts[s] for s in slots], hidden_act)
 
     def _allocate(self, rows):
         super()._allocate(rows)
@@ -175,5 +195,5 @@ class ClipStreamGroupMulti(csg.ClipStreamGroup):
                                  "sized by the counts: open another group)")
             cs._require_bf16_cuda("guide_embeds", guides)
         _refuse_grad(self.proj, what)
-        self.frames[slot], self.has_fe[slot] = 0, None
+        self.frames[slot], self.has_fe[slot], self.has_logits[slot] = 0, None, None
         self._prepare(guides, slot)

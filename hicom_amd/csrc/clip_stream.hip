@@ -197,9 +197,15 @@ extern "C" int hicom_stream_state_fold_fwd(const float* part_m, const float* par
                        part_acc, (int)nparts, (int)rows_pad);
 }
 
-extern "C" int hicom_compressor_stream_push(const hicom_stream_push_args* a) {
-    constexpr const char* who = "compressor_stream_push";
+namespace {
+
+// One push of a single-guide stream, the body of both entry points.  local_logits NULL: the keyed form (hicom_compressor_stream_push).  Given
+// (hicom_compressor_stream_push_logits): f32 [Tc H W] in the chunk's own token order, launch 1 is the ring kernel's logits instantiation and
+// a->fe is not looked at.  `logits` names the entry, the pointer is its argument: the logits entry must REFUSE a NULL pointer, so NULL cannot
+// stand for "the keyed form".  Nothing is launched before every check has passed.
+int push_single(const char* who, const hicom_stream_push_args* a, const float* local_logits, bool logits) {
     HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", who);
+    if (logits) HICOM_REQUIRE(local_logits && (uintptr_t)local_logits % 4 == 0, HICOM_EINVAL, "%s: local_logits is f32 [Tc H W]", who);
     int st = chunk_check(who, a, a->rows, a->pos_a != nullptr);
     if (st != HICOM_OK) return st;
     HICOM_REQUIRE(a->rows <= 12, HICOM_EUNSUP, "%s: %d folded rows (<= 12)", who, a->rows);
@@ -209,13 +215,13 @@ extern "C" int hicom_compressor_stream_push(const hicom_stream_push_args* a) {
                       a->state_ml_out && a->state_acc && a->out, HICOM_EINVAL, "%s: NULL pointer", who);
     HICOM_REQUIRE((a->pos_a != nullptr) == (a->pe_hi != nullptr) && (a->pe_hi != nullptr) == (a->pe_lo != nullptr), HICOM_EINVAL,
                   "%s: pos_a, pe_hi and pe_lo come together", who);
-    HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (uintptr_t)a->fe % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned inputs", who);
+    HICOM_REQUIRE((uintptr_t)a->ff % 16 == 0 && (logits || (uintptr_t)a->fe % 16 == 0), HICOM_EINVAL, "%s: 16-byte aligned inputs", who);
     const long nw = (long)(a->Tc / a->kt) * (a->H / a->ks) * (a->W / a->ks);
     HICOM_REQUIRE(nw <= INT32_MAX && a->ldo >= a->hidden && a->row0 >= 0 && a->nl_group >= 0 && (a->nl_group == 0 || nw % a->nl_group == 0),
                   HICOM_EINVAL, "%s: output layout", who);
     HICOM_REQUIRE(a->nl_count >= 0 && (a->nl_count == 0 || (a->newline && a->nl_first >= a->row0 && a->nl_step > 0)), HICOM_EINVAL, "%s: newline rows", who);
     // (no frames_embed: the keys are frames_feature, reference projector.py:532 -- the ring kernel streams it as its key tensor too)
-    st = hicom_fused_stream_fwd(a->ff, a->fe ? a->fe : a->ff, nullptr, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->q_hi, a->q_lo, a->rows, a->l_scale, 0.f,
+    st = hicom_fused_stream_fwd(a->ff, logits ? nullptr : a->fe ? a->fe : a->ff, local_logits, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->q_hi, a->q_lo, a->rows, a->l_scale, 0.f,
                                 a->pos_a, a->P, a->pe_hi, a->pe_lo, a->t0, a->y_index0, a->x_index0, a->part_m, a->part_l, a->part_acc, a->nparts, nullptr, nullptr,
                                 nullptr, a->ctx_f16, nullptr, 0, nullptr, nullptr, 0, HICOM_DT_BF16, nullptr, a->stream);
     if (st != HICOM_OK) return st;
@@ -228,6 +234,15 @@ extern "C" int hicom_compressor_stream_push(const hicom_stream_push_args* a) {
                                   a->out_dt, a->ldo, a->row0, a->nl_group, nullptr, a->stream);
     if (st != HICOM_OK || a->nl_count == 0) return st;
     return hicom_scatter_rows_fwd(a->newline, HICOM_DT_BF16, 1, a->hidden, a->out, a->out_dt, a->ldo, a->nl_first, a->nl_step, 0, a->nl_count, a->stream);
+}
+
+}  // namespace
+
+extern "C" int hicom_compressor_stream_push(const hicom_stream_push_args* a) { return push_single("compressor_stream_push", a, nullptr, false); }
+
+// The logits form: the chunk's scores come precomputed (hicom_head_scores_multi_fwd with the stream's one guide); a->fe is not read.
+extern "C" int hicom_compressor_stream_push_logits(const hicom_stream_push_args* a, const float* local_logits) {
+    return push_single("compressor_stream_push_logits", a, local_logits, true);
 }
 
 // ---- several guides per stream ---------------------------------------------------------------------------------------------
@@ -342,6 +357,30 @@ extern "C" int hicom_compressor_stream_push_multi(const hicom_stream_push_multi_
     return push_multi("compressor_stream_push_multi", a, [] { return (int)HICOM_OK; }, [a] {
         return hicom_multi_guide_local_fwd(a->fe ? a->fe : a->ff, a->ff, a->guide, a->Q, a->Tc, a->H, a->W, a->E, a->kt, a->ks, a->l_scale, a->ctx_f16, a->stream);
     });
+}
+
+// The logits form: local_logits f32 [Q][q_stride], guide q's [Tc H W] plane (the chunk's own token order) q_stride floats
+// behind guide 0's, as hicom_head_scores_multi_fwd writes it; launch 1 reads the value rows only and a->fe is not looked at.
+extern "C" int hicom_compressor_stream_push_multi_logits(const hicom_stream_push_multi_args* a, const float* local_logits, int64_t q_stride) {
+    constexpr const char* who = "compressor_stream_push_multi_logits";
+    hicom_stream_push_multi_args keyless;
+    if (a) {                                    // (the shared checks look at the alignment of fe: an address left from a keyed push is not this entry's business)
+        keyless = *a;
+        keyless.fe = nullptr;
+        a = &keyless;
+    }
+    return push_multi(
+        who, a,
+        [&] {
+            HICOM_REQUIRE(local_logits && (uintptr_t)local_logits % 4 == 0, HICOM_EINVAL, "%s: local_logits is f32 [Q][Tc H W]", who);
+            HICOM_REQUIRE(q_stride >= (int64_t)a->Tc * a->H * a->W, HICOM_EINVAL, "%s: q_stride=%ld floats between the guides' logit planes of %ld tokens", who,
+                          (long)q_stride, (long)a->Tc * a->H * a->W);
+            return (int)HICOM_OK;
+        },
+        [&] {
+            const hicom_axis at{a->Tc, a->kt, a->Tc / a->kt, a->Tc / a->kt}, ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+            return hicom_multi_guide_local_logits_fwd(a->ff, local_logits, q_stride, at, ay, ax, a->Q, at.nwin * ay.nwin * ax.nwin, a->l_scale, a->ctx_f16, a->stream);
+        });
 }
 
 // ---- the k / v adaptor recipe: the adaptor MLPs over the chunk's tokens, then the adapt local stage, in front of launches 2 ...

@@ -74,6 +74,26 @@ __global__ __launch_bounds__(256) void gm_local_kernel(const uint16_t* key, cons
                                   ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)it.wins * D);
 }
 
+// The logits form of launch 1: the same wave -> window -> item map and the same pair-major context placement with the local
+// logits given (multi_window.hpp: multi_window_guides_logits_ctx16).  logits f32 [max Q over the push's items][q_stride]: guide q of item i
+// at q q_stride + tok0_i + n, n counted from the item's first token -- the layout hicom_head_scores_ragged_fwd writes for the tick's stack;
+// planes q >= Q_i of an item's columns are not read.  Guide q of an item is plane q, so the slot's first pair is not needed; no key row
+// and no guide row is read.
+template <int NV>
+__global__ __launch_bounds__(256) void gm_local_logits_kernel(const uint16_t* value, const float* logits, long q_stride, const GmItem* items,
+                                                              const int* win_item, hicom_axis ay, hicom_axis ax, int kt, int nwin, float scale,
+                                                              _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const GmItem it = items[win_item[win]];
+    const hicom_axis at{it.T, kt, it.T / kt, it.T / kt};
+    const WindowGeom g(at, ay, ax, win - it.win0);
+    multi_window_guides_logits_ctx16<NV>(value + (long)it.tok0 * D, logits + it.tok0, q_stride, it.Q, g, lane, scale,
+                                         ctx16 + ((long)it.ctx_row0 + (win - it.win0)) * D, (long)it.wins * D);
+}
+
 // The same wave -> window map for the k / v adaptor recipe: launch 3 of the adaptor flavour's push, behind the adaptor MLPs
 // over the tick's STACKED tokens.  ad: gamma / beta / alpha / eps of the call and the fp16 planes y = MLP(x) of the whole stack (either may
 // be NULL, not both), indexed like the tokens: the by-value copy has them advanced to the item's first token, as clips_local_adapt_kernel
@@ -299,11 +319,46 @@ struct MultiOf : GroupPlainFront<MultiOf<Names>> {
 
 typedef MultiOf<MultiNames> Multi;
 
+// The logits form: Multi with its front replaced -- launch 1 is gm_local_logits_kernel on the caller's logits.  No region, no
+// requirement on the tuple: the workspace, its size function, the prepare call and the tables are Multi's.  (MultiOf<LogitsNames> is a
+// second instantiation for the sake of the entry's name in the messages: its `local` and kFoldWho are never used, and group_push's
+// once-per-process hipFuncSetAttribute on the one stream kernel runs once more for it.)
+struct LogitsNames {
+    static constexpr const char *kWho = "compressor_stream_group_multi_push_logits", *kFoldWho = "stream_group_multi_merge_fold";
+};
+
+struct MultiLogits : MultiOf<LogitsNames> {
+    const float* logits;     // f32 [max Q_i][q_stride], hicom_head_scores_ragged_fwd's layout over the tick's stack
+    long q_stride;
+    MultiLogits(const float* logits_, long q_stride_) : logits(logits_), q_stride(q_stride_) {}
+
+    int check_push(const Args*, const GroupLayout& l) const {
+        HICOM_REQUIRE(logits && (uintptr_t)logits % 4 == 0, HICOM_EINVAL, "%s: local_logits is f32 [max Q_i][sum Tc_i H W]", kWho);
+        HICOM_REQUIRE(q_stride >= l.tokens, HICOM_EINVAL, "%s: q_stride=%ld floats between the guides' logit planes of %ld tokens", kWho, q_stride, l.tokens);
+        return HICOM_OK;
+    }
+    int front(const Args* a, const GroupLayout& l, const uint16_t*, const GroupPush&) const {
+        const char* ws = (const char*)a->ws;
+        const hicom_axis ay{a->H, a->ks, a->H / a->ks, a->H / a->ks}, ax{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+        HICOM_LAUNCH(gm_local_logits_kernel<3>, dim3((unsigned)((l.windows + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, (const uint16_t*)a->ff, logits, q_stride,
+                     (const GmItem*)(ws + l.items), (const int*)(ws + l.win_item), ay, ax, (int)a->kt, (int)l.windows, a->l_scale, (_Float16*)(ws + l.ctx16));
+        return seg_check_launch(kWho, "local stage");
+    }
+};
+
 }  // namespace
 
 extern "C" int64_t hicom_compressor_stream_group_multi_workspace_bytes(const hicom_stream_group_multi_push_args* a) { return group_workspace_bytes<Multi>(a); }
 extern "C" int hicom_compressor_stream_group_multi_prepare(const hicom_stream_group_multi_push_args* a) { return group_prepare<Multi>(a); }
 extern "C" int hicom_compressor_stream_group_multi_push(const hicom_stream_group_multi_push_args* a) { return group_push<Multi>(a); }
+
+// The logits form: a->fe is not read (an address left in the block by a keyed push is not looked at); a->guide stays the group's block.
+extern "C" int hicom_compressor_stream_group_multi_push_logits(const hicom_stream_group_multi_push_args* a, const float* local_logits, int64_t q_stride) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", LogitsNames::kWho);
+    hicom_stream_group_multi_push_args keyless = *a;
+    keyless.fe = nullptr;
+    return group_push<MultiLogits>(&keyless, MultiLogits(local_logits, (long)q_stride));
+}
 
 // The merge + fold kernel alone: `items` chunks of Tc frames with Q guides each; item i's partials in the slots [i S, (i + 1) S), S = 2 passes
 // nparts, ordered [pass][row group][chunk]; its logits [32 passes][ceil16(Tc H W)] at scores + i 32 passes ceil16(Tc H W); folded into the state

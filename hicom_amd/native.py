@@ -423,6 +423,9 @@ SIGNATURES = {
     "hicom_head_guide_fold_many_fwd": (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i64, vp]),
     "hicom_head_scores_ragged_fwd": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, i64, vp]),
     "hicom_compressor_ragged_multiguide_logits_fwd": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, i64]),
+    "hicom_compressor_stream_push_logits": (C.c_int, [C.POINTER(StreamPushArgs), vp]),
+    "hicom_compressor_stream_push_multi_logits": (C.c_int, [C.POINTER(StreamPushMultiArgs), vp, i64]),
+    "hicom_compressor_stream_group_multi_push_logits": (C.c_int, [C.POINTER(StreamGroupMultiPushArgs), vp, i64]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -958,6 +961,11 @@ def compressor_stream_push(args: StreamPushArgs):
     _check(lib().hicom_compressor_stream_push(C.byref(args)), "hicom_compressor_stream_push")
 
 
+def compressor_stream_push_logits(args: StreamPushArgs, local_logits: int):
+    """The push of a ClipStream with the chunk's local logits given (address of f32 [Tc H W], chunk-local order); args.fe is not read."""
+    _check(lib().hicom_compressor_stream_push_logits(C.byref(args), local_logits), "hicom_compressor_stream_push_logits")
+
+
 def stream_state_fold_set(set_ml, set_acc, ml_in, ml_out, acc, rows=None):
     """Folds ONE un-normalised set (set_ml [rows, 2] = interleaved (M, L), set_acc [rows, E]: a merge with normalize = 0) into the carried
     state: (M, L) from ml_in to ml_out (two different blocks), acc in place (hicom_stream_state_fold_set_fwd)."""
@@ -977,6 +985,11 @@ def stream_place_global(tok, newline, tail_newline, n_rows, out, row0):
 
 def compressor_stream_push_multi(args: StreamPushMultiArgs):
     _check(lib().hicom_compressor_stream_push_multi(C.byref(args)), "hicom_compressor_stream_push_multi")
+
+
+def compressor_stream_push_multi_logits(args: StreamPushMultiArgs, local_logits: int, q_stride: int):
+    """The push of a ClipStreamMulti with the chunk's local logits given (address of f32 [Q][q_stride]); args.fe is not read."""
+    _check(lib().hicom_compressor_stream_push_multi_logits(C.byref(args), local_logits, q_stride), "hicom_compressor_stream_push_multi_logits")
 
 
 def multi_guide_local(key_x: int, ff: int, guide: int, Q: int, T: int, H: int, W: int, E: int, kt: int, ks: int, scale: float, ctx_f16: int, stream: int):
@@ -1036,6 +1049,13 @@ def compressor_stream_group_multi_prepare(args: StreamGroupMultiPushArgs):
 
 def compressor_stream_group_multi_push(args: StreamGroupMultiPushArgs):
     _check(lib().hicom_compressor_stream_group_multi_push(C.byref(args)), "hicom_compressor_stream_group_multi_push")
+
+
+def compressor_stream_group_multi_push_logits(args: StreamGroupMultiPushArgs, local_logits: int, q_stride: int):
+    """The push of a ClipStreamGroupMulti with the tick's local logits given (address of f32 [max Q_i][q_stride], head_scores_ragged's layout);
+    args.fe is not read."""
+    _check(lib().hicom_compressor_stream_group_multi_push_logits(C.byref(args), local_logits, q_stride),
+           "hicom_compressor_stream_group_multi_push_logits")
 
 
 def stream_group_multi_merge_fold(part_m, part_l, part_acc, scores, items, rows, Q, Tc, H, W, pe, y0, x0, pair0s, t0s, state_ml, state_acc):

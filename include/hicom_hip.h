@@ -1570,6 +1570,26 @@ int hicom_head_scores_ragged_fwd(const void* x, const void* hid, int64_t ld, int
                                  int32_t B, int32_t ntiles, int32_t q_max, float* logits, int64_t q_stride, void* stream);
 int hicom_compressor_ragged_multiguide_logits_fwd(const hicom_compressor_ragged_multiguide_args* args, const float* local_logits, int64_t q_stride);
 
+/* ---- clip streams without frames_embed: head scores per chunk -------------------------------------------------------------
+ * The three plain pushes with the local stage taking its scores precomputed: the raw dot products frames_embed[n] . guide in front of
+ * l_scale, f32, indexed by the token's place in the CHUNK (the stack of a tick for the group), never by its place in the clip.  Each entry
+ * takes the keyed entry's argument block unchanged: args->fe is not read and may be NULL or stale; t0 positions the chunk on the time axis
+ * for the positional tables only.  Launch count, workspace, size function, prepare call, tables and every other launch are the keyed
+ * push's.  Nothing is launched before every check has passed (NULL or unaligned logits -- 4 bytes --, a short q_stride: HICOM_EINVAL).
+ *
+ * hicom_compressor_stream_push_logits: local_logits f32 [Tc H W]; launch 1 is hicom_fused_stream_fwd(ff, NULL, local_logits, ...).
+ *
+ * hicom_compressor_stream_push_multi_logits: local_logits f32 [Q][q_stride], q_stride >= Tc H W, guide q's plane q_stride floats behind
+ * guide 0's (what hicom_head_scores_multi_fwd writes); launch 1 is hicom_multi_guide_local_logits_fwd.
+ *
+ * hicom_compressor_stream_group_multi_push_logits: local_logits f32 [max Q_i over the push's items][q_stride], q_stride >= sum Tc_i H W:
+ * guide q of item i at logits[q q_stride + tok0_i + n], tok0_i = the item's first token in the stack, n < Tc_i H W -- the layout
+ * hicom_head_scores_ragged_fwd writes for the tick's items.  Guide q of an item is plane q, whichever pairs its slot owns; planes q >= Q_i
+ * over an item's tokens and the gap behind sum Tc_i H W are never read.  Launch 1 reads neither key rows nor guide rows. */
+int hicom_compressor_stream_push_logits(const hicom_stream_push_args* args, const float* local_logits);
+int hicom_compressor_stream_push_multi_logits(const hicom_stream_push_multi_args* args, const float* local_logits, int64_t q_stride);
+int hicom_compressor_stream_group_multi_push_logits(const hicom_stream_group_multi_push_args* args, const float* local_logits, int64_t q_stride);
+
 #ifdef __cplusplus
 }
 #endif
