@@ -822,14 +822,15 @@ def _local_backward(st, lc, nl, dout, is_anyres, adaptor_saved, ctx_local16):
     return lay.n_rows, d_nl, d_fe
 
 
-def _global_tail_backward(st, nh, hd, ml, acc, q32, dtok):
-    """Everything behind the global attention, forward and backward on [nq, E] tensors: fills readout.* / out_proj.* / v_proj.*, returns (dpre, dctx, delta)."""
+def _global_tail_backward(st, nh, hd, ml, acc, q32, dtok, ctxg=None):
+    """Everything behind the global attention, forward and backward on [nq, E] tensors: fills readout.* / out_proj.* / v_proj.*, returns (dpre, dctx, delta).
+    ctxg: the merged contexts [nq nh, E] where the forward kept those (the many-item steps) instead of (ml, acc)."""
     f32, grads, P = st.f32, st.grads, "global_compressor."
     nq, E = q32.shape
     Wv, bv = f32[P + "attn_layer.v_proj.weight"], f32[P + "attn_layer.v_proj.bias"]
     Wo, bo = f32[P + "attn_layer.out_proj.weight"], f32[P + "attn_layer.out_proj.bias"]
     G0, gb0 = f32[P + "readout.0.weight"], f32[P + "readout.0.bias"]
-    ctxg = (acc / ml[:, 1:2]).view(nq, nh, E)                          # per-(query, head) contexts
+    ctxg = (acc / ml[:, 1:2] if ctxg is None else ctxg).view(nq, nh, E)   # per-(query, head) contexts
     o = torch.einsum("hje,qhe->qhj", Wv.view(nh, hd, E), ctxg).reshape(nq, E) + bv    # ref :182,:215 after folding
     pre = o @ Wo.t() + bo + q32                                        # out_proj + residual with the injected query (:646)
     dpre = _readout_backward(pre, pre @ G0.t() + gb0, f32[P + "readout.2.weight"], dtok, P + "readout.", grads) @ G0
@@ -891,19 +892,30 @@ def _global_dff(st, att, q_in, Wq, bq, Wk, scores, ds, ml, dctx):
         cur.copy_(dxg + cur.float() if have else dxg)
 
 
-def _global_fold_backward(st, att, part, marg, pe, pos0, q32, Wq, bq, Wk):
-    """Through the fold qt[q,h] = scale W_k,h^T (W_q q + b_q)[q, h-slice] (ref :180-181,:193-197): fills k_proj.*, returns d (W_q q + b_q)."""
-    T, H, W, E = st.ff.shape
+def _global_fold_backward(st, att, part, marg, pe, pos0, q32, Wq, bq, Wk, dqt=None):
+    """Through the fold qt[q,h] = scale W_k,h^T (W_q q + b_q)[q, h-slice] (ref :180-181,:193-197): fills k_proj.*, returns d (W_q q + b_q).
+    dqt: [nq nh, E] = sum_n dS[r, n] (x_n + pe_n) where a kernel has merged it already (hicom_compressor_ragged_global_bwd); part, marg,
+    pe and pos0 are then not looked at."""
+    E = q32.shape[1]
     nq, nh, hd, P = q32.shape[0], att.num_heads, att.head_dim, "global_compressor."
-    dqt = part.sum(0)[:nq * nh]                                        # sum_n dS[r, n] x_n
-    if pe is not None:
-        (t0i, y0i, x0i), (mT, mY, mX) = pos0, marg
-        dqt = dqt + mT @ pe[t0i:t0i + T] + mY @ pe[y0i:y0i + H] + mX @ pe[x0i:x0i + W]
+    if dqt is None:
+        T, H, W, _ = st.ff.shape
+        dqt = part.sum(0)[:nq * nh]                                    # sum_n dS[r, n] x_n
+        if pe is not None:
+            (t0i, y0i, x0i), (mT, mY, mX) = pos0, marg
+            dqt = dqt + mT @ pe[t0i:t0i + T] + mY @ pe[y0i:y0i + H] + mX @ pe[x0i:x0i + W]
     dqt = dqt.view(nq, nh, E)
     qp = (q32 @ Wq.t() + bq).view(nq, nh, hd)
     st.grads[P + "attn_layer.k_proj.weight"] = att.scale * torch.einsum("qhj,qhe->hje", qp, dqt).reshape(E, E)
     st.grads[P + "attn_layer.k_proj.bias"] = torch.zeros(E, device=st.dev)   # a per-row logit shift: softmax cancels it exactly
     return att.scale * torch.einsum("hje,qhe->qhj", Wk.view(nh, hd, E), dqt).reshape(nq, E)
+
+
+def _q_proj_backward(grads, dqp, q32):
+    """q_proj.* from dqp = d (W_q q + b_q) [nq, E] and the injected queries q32."""
+    A = "global_compressor.attn_layer."
+    grads[A + "q_proj.weight"] = dqp.t() @ q32
+    grads[A + "q_proj.bias"] = _sum0(dqp)
 
 
 def _global_query_backward(st, gc, d_in):
@@ -957,8 +969,7 @@ def _global_backward(st, gc, dout, n_local, global_saved):
     else:
         dqp = _global_clip_backward(ff, pe, pos0, scores, ds, ml.shape[0], nq, nh, hd, q32, Wq, bq, Wk, f32.get(A + "k_proj.bias"),
                                     float(clip_g[0]), grads, "global_compressor.")
-    grads[A + "q_proj.weight"] = dqp.t() @ q32
-    grads[A + "q_proj.bias"] = _sum0(dqp)
+    _q_proj_backward(grads, dqp, q32)
     if gc.use_guide != "direct" or gc.adapt_guide or st.want_guide:    # (plain direct: `query` does not enter the forward, ref :352-368 uses only its shape)
         _global_query_backward(st, gc, dqp @ Wq + dpre)
 

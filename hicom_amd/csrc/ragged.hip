@@ -16,6 +16,9 @@
 // stream_segment (stream_body.hpp: the one body of the four-wave stream machine, also behind hicom_global_stream_fwd's narrow kernel)
 // with one row group; the per-item requirements, the chunk share, the tile ranges and the table upload
 // are segment_host.hpp's, shared with ragged_multi_guide.hip.
+// Training (plain recipe, hicom_amd/ragged_train.py): hicom_compressor_ragged_train_state hands the forward's state out of the workspace,
+// hicom_compressor_ragged_global_bwd runs the global stage's attention backward over all items on the forward's unit table -- the same
+// stream_segment in StreamMode::Bwd, then dq_merge_segments per (item, head).
 #include <vector>
 
 #include "segment_host.hpp"
@@ -105,6 +108,64 @@ __global__ __launch_bounds__(256) void ragged_merge_kernel(RaggedMergeParams p) 
     const long stride = (it.N + 15) / 16 * 16;
     merge_segments(p.c, ms, r, threadIdx.x, it.T, it.chunks, (long)it.slot0, p.scores + (long)it.score_off * 16 + r * stride,
                    p.ctx + ((long)item * p.rows + r) * p.c.E);
+}
+
+// ---- training: (M, L) per (item, head) from the partial states, merge_segments' own order.  grid = B, 64 threads ----
+__global__ __launch_bounds__(64) void ragged_state_ml_kernel(const float* part_m, const float* part_l, const RaggedItem* items, int rows, float* ml) {
+    const int item = blockIdx.x, r = threadIdx.x;
+    if (r >= rows) return;
+    const RaggedItem it = items[item];
+    const long pbase = (long)it.slot0 * 16 + r;
+    float M = -1.0e30f;
+    for (int c = 0; c < it.chunks; ++c) M = fmaxf(M, part_m[pbase + c * 16]);
+    float L = 0.f;
+    for (int c = 0; c < it.chunks; ++c) L += part_l[pbase + c * 16] * expf(part_m[pbase + c * 16] - M);
+    ml[2 * ((long)item * rows + r)] = M;
+    ml[2 * ((long)item * rows + r) + 1] = L;
+}
+
+// ---- training: the segmented backward of the global stream, the forward's unit table and slots (stream_body.hpp: StreamMode::Bwd).
+// c.qhi / c.qlo: the planes of dctx, c.pos_a: pos_b = dctx . pe^T, c.part_acc: partial sums of dS x; part_m / part_l are not written ----
+struct RaggedStreamBwdParams {
+    SegStreamParams c;
+    const uint16_t* x;      // [sum N_i][E]
+    const float* s_in;      // the forward's scores region
+    const float* ml;        // [B * rows][2]
+    const float* delta;     // [B * rows]
+    float* ds;              // laid out as s_in
+    const int4* units;
+    const RaggedItem* items;
+};
+
+template <int NB>
+__global__ __launch_bounds__(256, 2) void ragged_global_stream_bwd_kernel(RaggedStreamBwdParams p) {
+    constexpr int E = NB * 128;
+    const int4 u = p.units[blockIdx.x];
+    const int N = p.items[u.x].N, tok0 = p.items[u.x].tok0, soff = p.items[u.x].score_off;
+    StreamModeArgs ma{};
+    ma.s_in = p.s_in + (long)soff * 16;
+    ma.ml = p.ml + 2 * (long)u.x * p.c.rows;
+    ma.delta = p.delta + (long)u.x * p.c.rows;
+    stream_segment<NB, 1, StreamMode::Bwd>(p.c, p.x + (long)tok0 * E, N, u.y, u.z, 0, p.c.rows, (long)u.x * p.c.rows, p.ds + (long)soff * 16,
+                                           (long)((N + 15) / 16 * 16), (long)u.w, 0, ma);
+}
+
+// ---- training: dq merge per (item, head), grid = (rows, B), the forward merge's LDS ----
+struct RaggedDqMergeParams {
+    SegDqMergeParams c;
+    const float* ds;
+    const RaggedItem* items;
+    int rows;
+    float* dqt;             // [B * rows][E]
+};
+
+__global__ __launch_bounds__(256) void ragged_dq_merge_kernel(RaggedDqMergeParams p) {
+    extern __shared__ float ms[];
+    const int r = blockIdx.x, item = blockIdx.y;
+    const RaggedItem it = p.items[item];
+    const long stride = (it.N + 15) / 16 * 16;
+    dq_merge_segments(p.c, ms, r, threadIdx.x, it.T, it.chunks, (long)it.slot0, p.ds + (long)it.score_off * 16 + r * stride,
+                      p.dqt + ((long)item * p.rows + r) * p.c.E);
 }
 
 // ---- 12: placement, one output row per workgroup over all items' rows ----
@@ -295,7 +356,119 @@ int ragged_fwd(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
     return seg_step(a, ad, l.s, RaggedItems{a, l});
 }
 
+// ---- training (plain recipe): the state a backward reads, and the global stage's attention backward ---------------------------------
+constexpr const char* kWhoBwd = "compressor_ragged_global_bwd";
+
+struct RaggedBwdLayout { long dhi, dlo, pos_b, part_acc, total; };
+
+RaggedBwdLayout ragged_bwd_layout(const hicom_compressor_ragged_args* a, const RaggedLayout& l) {
+    RaggedBwdLayout b{};
+    long off = 0;
+    auto take = [&](long bytes) { const long at = off; off += (bytes + 255) / 256 * 256; return at; };
+    const long R = l.s.n.rows, E = a->E;
+    b.dhi = take(R * E * 2);
+    b.dlo = take(R * E * 2);
+    b.pos_b = take(a->pe ? R * (long)a->P * 4 : 0);
+    b.part_acc = take(l.s.n.part_rows * E * 4);
+    b.total = off;
+    return b;
+}
+
+int ragged_train_state(const hicom_compressor_ragged_args* a, void* ctx16_out, float* scores_out, float* ml_out, float* ctxg_out) {
+    constexpr const char* who = "compressor_ragged_train_state";
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(who, a, l.s.total);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(ctx16_out && scores_out && ml_out && ctxg_out, HICOM_EINVAL, "%s: NULL pointer", who);
+    const char* ws = (const char*)a->ws;
+    hipStream_t s = (hipStream_t)a->stream;
+    const long E = a->E;
+    if (hipMemcpyAsync(ctx16_out, ws + l.s.ctx16, (size_t)(l.s.n.windows * E * 2), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(scores_out, ws + l.s.scores, (size_t)(l.s.n.score_floats * 4), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(ctxg_out, ws + l.s.ctxg, (size_t)(l.s.n.rows * E * 4), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        set_error("%s: copying the state: %s", who, hipGetErrorString(hipGetLastError()));
+        return HICOM_ELAUNCH;
+    }
+    HICOM_LAUNCH(ragged_state_ml_kernel, dim3((unsigned)a->B), dim3(64), 0, s, (const float*)(ws + l.s.part_m), (const float*)(ws + l.s.part_l),
+                 (const RaggedItem*)(ws + l.items), a->nh, ml_out);
+    return seg_check_launch(who, "softmax state");
+}
+
+int64_t ragged_global_bwd_workspace_bytes(const hicom_compressor_ragged_args* a) {
+    const int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    return ragged_bwd_layout(a, ragged_layout(a, nullptr)).total;
+}
+
+int ragged_global_bwd(const hicom_compressor_ragged_args* a, const void* x, const float* dctx, const float* delta, const float* scores, const float* ml,
+                      float* ds_out, float* dqt_out, void* bws, int64_t bws_bytes) {
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(kWhoBwd, a, l.s.total);                 // (the table region at its head is what is read)
+    if (st != HICOM_OK) return st;
+    const RaggedBwdLayout b = ragged_bwd_layout(a, l);
+    HICOM_REQUIRE(x && dctx && delta && scores && ml && ds_out && dqt_out, HICOM_EINVAL, "%s: NULL pointer", kWhoBwd);
+    HICOM_REQUIRE(bws && bws_bytes >= b.total && (uintptr_t)bws % 256 == 0, HICOM_EINVAL, "%s: workspace of %ld bytes, 256-byte aligned", kWhoBwd, b.total);
+    HICOM_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)scores % 16 == 0 && (uintptr_t)ds_out % 16 == 0 && (uintptr_t)dctx % 16 == 0, HICOM_EINVAL,
+                  "%s: 16-byte aligned inputs", kWhoBwd);
+    HICOM_REQUIRE(ds_out != scores, HICOM_EINVAL, "%s: dS cannot overwrite the logits", kWhoBwd);
+    char* w = (char*)bws;
+    const char* tab = (const char*)a->ws;
+    const int R = (int)l.s.n.rows, E = a->E;
+    hipStream_t s = (hipStream_t)a->stream;
+
+    // 1: dctx -> bf16 hi / lo planes
+    st = hicom_split_bf16_fwd(dctx, R, R, E, w + b.dhi, w + b.dlo, a->stream);
+    if (st != HICOM_OK) return st;
+    // 2: the score-side positional table of dP
+    float* pos_b = a->pe ? (float*)(w + b.pos_b) : nullptr;
+    if (a->pe) {
+        st = hicom_linear_fwd(dctx, HICOM_DT_F32, a->pe, HICOM_DT_F32, nullptr, 0, nullptr, 0, R, a->P, E, 0, 0, HICOM_ACT_NONE, pos_b, a->stream);
+        if (st != HICOM_OK) return st;
+    }
+    // 3: the segmented backward stream
+    {
+        RaggedStreamBwdParams p;
+        p.c.qhi = (const uint16_t*)(w + b.dhi); p.c.qlo = (const uint16_t*)(w + b.dlo);
+        p.c.pos_a = pos_b; p.c.pos_stride = a->P; p.c.rows = a->nh;
+        p.c.H = a->H; p.c.W = a->W; p.c.HW = a->H * a->W;
+        p.c.t0i = a->t_index0; p.c.y0i = a->y_index0; p.c.x0i = a->x_index0;
+        p.c.part_m = nullptr; p.c.part_l = nullptr; p.c.part_acc = (float*)(w + b.part_acc);
+        p.x = (const uint16_t*)x; p.s_in = scores; p.ml = ml; p.delta = delta; p.ds = ds_out;
+        p.units = (const int4*)(tab + l.units); p.items = (const RaggedItem*)(tab + l.items);
+        static bool attr_set = false;
+        if (!attr_set) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(ragged_global_stream_bwd_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, seg_stream_smem(1));
+            attr_set = true;
+        }
+        HICOM_LAUNCH(ragged_global_stream_bwd_kernel<9>, dim3((unsigned)l.s.n.slots), dim3(256), seg_stream_smem(1), s, p);
+        st = seg_check_launch(kWhoBwd, "backward stream");
+        if (st != HICOM_OK) return st;
+    }
+    // 4: dq merge per (item, head)
+    RaggedDqMergeParams p;
+    p.c.part_acc = (const float*)(w + b.part_acc); p.c.pe = a->pe; p.c.E = E; p.c.H = a->H; p.c.W = a->W;
+    p.c.t0i = a->t_index0; p.c.y0i = a->y_index0; p.c.x0i = a->x_index0;
+    p.ds = ds_out; p.items = (const RaggedItem*)(tab + l.items); p.rows = a->nh; p.dqt = dqt_out;
+    HICOM_LAUNCH(ragged_dq_merge_kernel, dim3((unsigned)a->nh, (unsigned)a->B), dim3(256), (size_t)seg_merge_smem(l.max_T, a->H, a->W), s, p);
+    return seg_check_launch(kWhoBwd, "dq merge");
+}
+
 }  // namespace
+
+extern "C" int hicom_compressor_ragged_train_state(const hicom_compressor_ragged_args* a, void* ctx16_out, float* scores_out, float* ml_out, float* ctxg_out) {
+    return ragged_train_state(a, ctx16_out, scores_out, ml_out, ctxg_out);
+}
+
+extern "C" int64_t hicom_compressor_ragged_global_bwd_workspace_bytes(const hicom_compressor_ragged_args* a) { return ragged_global_bwd_workspace_bytes(a); }
+
+extern "C" int hicom_compressor_ragged_global_bwd(const hicom_compressor_ragged_args* a, const void* x, const float* dctx, const float* delta, const float* scores,
+                                                  const float* ml, float* ds_out, float* dqt_out, void* ws, int64_t ws_bytes) {
+    return ragged_global_bwd(a, x, dctx, delta, scores, ml, ds_out, dqt_out, ws, ws_bytes);
+}
 
 extern "C" int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compressor_ragged_args* a) { return ragged_workspace_bytes(a, nullptr); }
 

@@ -191,6 +191,65 @@ __device__ __forceinline__ void merge_segments(const SegMergeParams& p, float* m
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The backward twin of merge_segments, one (item, head) row: dqt = sum_p ACC_p + sum_s marg[s] pe[s], ACC_p the partial sums of
+// dS x the backward stream left in the item's slots, marg the PLAIN sums of the row's dS over the other two axes (no exp, no rescale:
+// dS is final).  Same LDS (T (H + W) + T + H + W floats) and the same fixed summation orders: the result depends on the item's tokens,
+// its cotangent and nparts only.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct SegDqMergeParams {
+    const float* part_acc;
+    const float* pe;        // [P][E] or NULL
+    int E, H, W;
+    int t0i, y0i, x0i;
+};
+
+__device__ __forceinline__ void dq_merge_segments(const SegDqMergeParams& p, float* ms, int r, int tid, int T, int nparts, long slot0, const float* ds,
+                                                  float* dqt) {
+    const int H = p.H, W = p.W;
+    float* rowsum = ms;                 // [T][H]: dS summed over x
+    float* colsum = ms + T * H;         // [T][W]: dS summed over y
+    float* marg = colsum + T * W;       // [T + H + W]
+    if (p.pe) {
+        for (int i = tid; i < T * H; i += 256) {
+            float a = 0.f;
+            for (int x = 0; x < W; ++x) a += ds[(long)i * W + x];
+            rowsum[i] = a;
+        }
+        for (int i = tid; i < T * W; i += 256) {
+            const int t = i / W, x = i - t * W;
+            float a = 0.f;
+            for (int y = 0; y < H; ++y) a += ds[((long)t * H + y) * W + x];
+            colsum[i] = a;
+        }
+        __syncthreads();
+        for (int i = tid; i < T + H + W; i += 256) {
+            float a = 0.f;
+            if (i < T) {
+                for (int y = 0; y < H; ++y) a += rowsum[i * H + y];
+            } else if (i < T + H) {
+                for (int t = 0; t < T; ++t) a += rowsum[t * H + (i - T)];
+            } else {
+                for (int t = 0; t < T; ++t) a += colsum[t * W + (i - T - H)];
+            }
+            marg[i] = a;
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < p.E; e += 256) {
+        float v = 0.f;
+        for (int c = 0; c < nparts; ++c) v += p.part_acc[(slot0 + c) * 16 * p.E + (long)r * p.E + e];
+        if (p.pe) {
+            float pos = 0.f;
+            for (int t = 0; t < T; ++t) pos = fmaf(marg[t], p.pe[(long)(p.t0i + t) * p.E + e], pos);
+            for (int y = 0; y < H; ++y) pos = fmaf(marg[T + y], p.pe[(long)(p.y0i + y) * p.E + e], pos);
+            for (int x = 0; x < W; ++x) pos = fmaf(marg[T + H + x], p.pe[(long)(p.x0i + x) * p.E + e], pos);
+            v += pos;
+        }
+        dqt[e] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Placement of one packed output row (byte work), r = the row inside its item, o = the row's element offset in `out`:
 //   rows >= global_row0: the item's global row `tok` (f32, rounded once: the copies are bit-identical);
 //   newline rows nl_first + i nl_step, i < nl_count; every other row: local token m = r - r / (nl_group + 1), row loc_row0 + m of loc.

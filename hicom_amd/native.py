@@ -426,6 +426,9 @@ SIGNATURES = {
     "hicom_compressor_stream_push_logits": (C.c_int, [C.POINTER(StreamPushArgs), vp]),
     "hicom_compressor_stream_push_multi_logits": (C.c_int, [C.POINTER(StreamPushMultiArgs), vp, i64]),
     "hicom_compressor_stream_group_multi_push_logits": (C.c_int, [C.POINTER(StreamGroupMultiPushArgs), vp, i64]),
+    "hicom_compressor_ragged_train_state": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp]),
+    "hicom_compressor_ragged_global_bwd_workspace_bytes": (i64, [C.POINTER(CompressorRaggedArgs)]),
+    "hicom_compressor_ragged_global_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, vp, vp, i64]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -815,6 +818,24 @@ def compressor_ragged_prepare(args):
 
 def compressor_ragged_fwd(args):
     _seg_call(args, "ragged", "fwd")
+
+
+def compressor_ragged_train_state(args: CompressorRaggedArgs, ctx16, scores, ml, ctxg):
+    """What a backward of the call just made reads, out of the plan's workspace into tensors of the caller's (hicom_compressor_ragged_train_state)."""
+    _check(lib().hicom_compressor_ragged_train_state(C.byref(args), _ptr(ctx16), _ptr(scores), _ptr(ml), _ptr(ctxg)), "hicom_compressor_ragged_train_state")
+
+
+def compressor_ragged_global_bwd_workspace(args: CompressorRaggedArgs) -> int:
+    n = lib().hicom_compressor_ragged_global_bwd_workspace_bytes(C.byref(args))
+    if n < 0:
+        raise HicomNativeError(f"hicom_compressor_ragged_global_bwd_workspace_bytes failed ({n}): {lib().hicom_last_error().decode(errors='replace')}")
+    return int(n)
+
+
+def compressor_ragged_global_bwd(args: CompressorRaggedArgs, x, dctx, delta, scores, ml, ds, dqt, ws):
+    """The global stage's attention backward over all items of a ragged plan (hicom_compressor_ragged_global_bwd): fills ds and dqt."""
+    _check(lib().hicom_compressor_ragged_global_bwd(C.byref(args), _ptr(x), _ptr(dctx), _ptr(delta), _ptr(scores), _ptr(ml), _ptr(ds), _ptr(dqt), _ptr(ws),
+                                                    ws.numel()), "hicom_compressor_ragged_global_bwd")
 
 
 def compressor_multiguide_workspace(args) -> int:

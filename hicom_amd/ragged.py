@@ -97,17 +97,32 @@ def check_splits(what, ff, split_sizes, modals, guide_counts=None, check_counts=
     return split_sizes, modals, guide_counts
 
 
-def _scope(proj, ff, fe, guides, split_sizes, modals, nl):
+def train_row_maps(t):
+    """Where the rows of the packed output come from, for the backward of the call (ragged_train.py), from plan_tables' result alone:
+    (local, newline, glob) int64 arrays of output rows -- local[w] the row of window w of the concatenated window list (the packing's
+    row map: a newline gap after every nl_group local tokens), newline the newline rows of all items, glob [B, n_global_rows] the copies
+    of each item's global token."""
+    local, newline, glob = [], [], []
+    for i, it in enumerate(t.items):
+        _, _, nl_group, nl_count, nl_first, nl_step, n_global = it
+        m = np.arange(t.windows[i], dtype=np.int64)
+        local.append(t.row0[i] + m + (m // nl_group if nl_group else 0))
+        newline.append(t.row0[i] + nl_first + np.arange(nl_count, dtype=np.int64) * (nl_step if nl_step > 0 else 1))
+        glob.append(t.row0[i] + t.global_row0[i] + np.arange(n_global, dtype=np.int64))
+    return np.concatenate(local), np.concatenate(newline), np.stack(glob)
+
+
+def _scope(proj, ff, fe, guides, split_sizes, modals, nl, what="forward_ragged"):
     """Raises for everything outside the ragged step's scope that does not need the per-item geometry; returns (B, H, W, E,
     split_sizes, modals) with the last two as tuples."""
     def count_items():
         nonlocal split_sizes, modals
-        split_sizes, modals, _ = check_splits("forward_ragged", ff, split_sizes, modals)
+        split_sizes, modals, _ = check_splits(what, ff, split_sizes, modals)
         return len(split_sizes)
-    B, E = seg.check_inputs("forward_ragged", "ragged", proj, ff, fe, guides, nl, 4, "the stacked [sum T_i, H, W, E] tensor", count_items)
+    B, E = seg.check_inputs(what, "ragged", proj, ff, fe, guides, nl, 4, "the stacked [sum T_i, H, W, E] tensor", count_items)
     for i, (t, m) in enumerate(zip(split_sizes, modals)):
         if m == "image" and t != 1:
-            raise ValueError(f"forward_ragged: item {i}: image modality expects a single frame (T = {t})")
+            raise ValueError(f"{what}: item {i}: image modality expects a single frame (T = {t})")
     return B, ff.shape[1], ff.shape[2], E, split_sizes, modals
 
 
@@ -143,9 +158,11 @@ def _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, strea
     return plan
 
 
-def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
-    B, H, W, E, split_sizes, modals = _scope(proj, ff, fe, guides, split_sizes, modals, nl)
-    dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, "forward_ragged", ff, fe, guides, nl)
+def call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, what="forward_ragged", refuse_grad=True):
+    """The one C call of forward_ragged and of forward_ragged_train (ragged_train.py: refuse_grad False): returns (the [sum rows_i,
+    hidden] output, the plan, the contiguous frames_feature and guides the call read)."""
+    B, H, W, E, split_sizes, modals = _scope(proj, ff, fe, guides, split_sizes, modals, nl, what)
+    dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, what, ff, fe, guides, nl, refuse_grad=refuse_grad)
     key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
            seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
     plan = seg.cached_plan(proj, "_ragged_plans", key, lambda: _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, stream))
@@ -153,4 +170,9 @@ def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
     seg.patch_io(a, ff, fe, guides, nl, out, stream)         # (the newline pointer whenever given: items differ in their newline rows)
     nv.compressor_ragged_fwd(plan.args)
+    return out, plan, ff, guides
+
+
+def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
+    out, plan, _, _ = call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks)
     return list(out.split(plan.rows))

@@ -1,0 +1,149 @@
+"""HIComProjector.forward_ragged_train: the training step of a mixed batch -- forward_ragged's one C call under autograd.
+
+The reference trains on exactly the shape forward_ragged reads (hicom_arch.py:146-180 with mm_tunable_parts="mm_projector",
+train.py:709-713): one projector call and one backward per item.  Here the forward is the C call of forward_ragged (same plan cache,
+same bits) and the backward is ONE eager pass over all items: the same call sequence, four HIP launches among it, whatever B and the mix are:
+
+  local stage    dY gathered from the cotangent through the packing's row maps (ragged.train_row_maps), the readout backward
+                 (autograd._readout_backward) over the sum of all items' windows; d image_newline = the sum of all newline rows.
+                 The window backward never runs in this scope (autograd._window_backward_runs is false for it).
+  global stage   rows item-major (item nh + head): autograd._global_tail_backward with the B guides as the B queries, then
+                 hicom_compressor_ragged_global_bwd (csrc/ragged.hip: the segmented backward stream + the dq merge, four launches),
+                 then autograd._global_fold_backward and the q_proj gradients.
+
+The autograd node owns what its backward reads (window contexts, logits, softmax state, merged contexts: copied out of the plan's
+workspace by hicom_compressor_ragged_train_state), so forward, forward, backward, backward on one plan works.
+
+Scope: the plain release recipe `local43_global32` (use_guide="direct", no adaptors, no clip-scale, bf16 module and inputs, exact window
+partition per item); gradients of every projector parameter that requires grad and of image_newline.  Everything else raises
+NotImplementedError naming the loop of forward(): nothing is detached silently."""
+from __future__ import annotations
+
+import types
+
+import torch
+
+from . import autograd as ag
+from . import native as nv
+from . import ragged
+from . import segments as seg
+
+WHAT = "forward_ragged_train"
+_LOOP = "run the loop of forward() per item instead"
+
+
+def check_scope(proj, ff, fe, guides):
+    """The refusals of forward_ragged_train that forward_ragged does not make; no device is touched."""
+    if isinstance(ff, dict) or isinstance(fe, dict):
+        raise NotImplementedError(f"{WHAT}: anyres dict inputs have no ragged training step; {_LOOP}")
+    if proj.local_use_clip_scale or proj.global_use_clip_scale:
+        raise NotImplementedError(f"{WHAT}: clip-scale is not built for the ragged training step; {_LOOP}")
+    recipe = seg.seg_recipe(proj)
+    if recipe == "adaptkv":
+        raise NotImplementedError(f"{WHAT}: the k / v adaptor recipe (local43_adaptkv_global32) is not built for the ragged training step; {_LOOP}")
+    if recipe is None:
+        raise NotImplementedError(f"{WHAT} is built for the plain release recipe local43_global32 only (local + global compressor, "
+                                  f"use_guide='direct', no adaptors, no clip scale); {_LOOP}")
+    for name, t in (("frames_feature", ff), ("frames_embed", fe), ("guide_embeds", guides)):
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise NotImplementedError(f"{WHAT}: the gradient w.r.t. {name} (stage 3) is not built for the ragged training step; detach it, or {_LOOP}")
+
+
+def _device_maps(plan, dev):
+    """ragged.train_row_maps of the plan as device index tensors, made once per plan."""
+    if plan.train_maps is None:
+        plan.train_maps = tuple(torch.from_numpy(m).to(dev) for m in ragged.train_row_maps(plan.tables))
+    return plan.train_maps
+
+
+class _RaggedTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, proj, ff, fe, guides, nl, meta, names, *params):
+        split_sizes, modals, chunks, rows = meta
+        with torch.no_grad():
+            out, plan, x, g = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
+            t, a, dev = plan.tables, plan.io, x.device
+            R, E = a.B * a.nh, a.E
+            f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+            ctx16 = torch.empty((sum(t.windows), E), dtype=torch.float16, device=dev)
+            scores, ml, ctxg = f(16 * 16 * sum(t.ntiles)), f(R, 2), f(R, E)
+            nv.compressor_ragged_train_state(a, ctx16, scores, ml, ctxg)      # (the workspace belongs to the plan's next call)
+        rows.extend(plan.rows)                                 # (for the caller: how to split the output)
+        ctx.proj, ctx.plan, ctx.names = proj, plan, names
+        ctx.nl_meta = None if nl is None else nl.dtype
+        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, guides, ctx16, scores, ml, ctxg = ctx.saved_tensors
+        proj, plan, names = ctx.proj, ctx.plan, ctx.names
+        need = ctx.needs_input_grad            # (proj, ff, fe, guides, nl, meta, names, *params)
+        want = {n for k, n in enumerate(names) if need[7 + k]}
+        with torch.no_grad():
+            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]))
+        ag.LAST_FP32_GRADS = dict(grads)               # (test hook, as the single-item backward leaves it; here with d image_newline)
+        if d_nl is not None:
+            ag.LAST_FP32_GRADS["image_newline"] = d_nl
+        plist = dict(proj.named_parameters())
+        out = [None] * len(names)
+        by_dtype = {}
+        for k, n in enumerate(names):
+            if n in want and grads.get(n) is not None:
+                by_dtype.setdefault(plist[n].dtype, []).append((k, n))
+        for dt, group in by_dtype.items():                     # views of ONE buffer per parameter dtype, cast once
+            flat, o = torch.cat([grads[n].reshape(-1) for _, n in group]).to(dt), 0
+            for k, n in group:
+                cnt = plist[n].numel()
+                out[k] = flat[o:o + cnt].view(plist[n].shape)
+                o += cnt
+        return (None, None, None, None, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
+
+
+def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl):
+    """(fp32 gradients {parameter name: tensor} of sum(out * dout) over all items, d image_newline or None).  `want`: the names of the
+    parameters whose gradient is asked for; a stage none of whose parameters is wanted does not run."""
+    lc, gc = proj.local_compressor, proj.global_compressor
+    dev, a = x.device, plan.io
+    local_rows, nl_rows, glob_rows = _device_maps(plan, dev)
+    dout = dout.float()
+    st = types.SimpleNamespace(proj=proj, ff=x, dev=dev, f32=ag._f32_params(proj), grads={})
+    f32, L = st.f32, "local_compressor.readout."
+    d_nl = dout[nl_rows].sum(0) if (want_nl and nl_rows.numel()) else None
+    if any(n.startswith("local_compressor.") for n in want):
+        assert not ag._window_backward_runs(lc, False, False, proj.local_logit, False)
+        ctx_l = ctx16.float()
+        W0, b0 = f32[L + "0.weight"], f32[L + "0.bias"]
+        ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
+    if any(n.startswith("global_compressor.") for n in want):
+        att = gc.attn_layer
+        nh, hd = att.num_heads, att.head_dim
+        q32 = guides.float()
+        dtok = dout[glob_rows].sum(1)                          # [B, hidden]: an item's global rows are copies of one row
+        _, dctx, delta = ag._global_tail_backward(st, nh, hd, ml, None, q32, dtok, ctxg=ctxg)
+        ds = torch.empty_like(scores)
+        dqt = torch.empty_like(ctxg)
+        if plan.train_ws_bytes is None:                        # (fixed per plan, like the row maps)
+            plan.train_ws_bytes = nv.compressor_ragged_global_bwd_workspace(a)
+        ws = torch.empty((plan.train_ws_bytes,), dtype=torch.uint8, device=dev)
+        nv.compressor_ragged_global_bwd(a, x, dctx, delta, scores, ml, ds, dqt, ws)
+        A = "global_compressor.attn_layer."
+        dqp = ag._global_fold_backward(st, att, None, None, None, None, q32, f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"],
+                                       dqt=dqt)
+        ag._q_proj_backward(st.grads, dqp, q32)
+    return st.grads, d_nl
+
+
+def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
+    check_scope(proj, ff, fe, guides)
+    params = [(n, p) for n, p in proj.named_parameters()]
+    trainable = torch.is_grad_enabled() and (any(p.requires_grad for _, p in params) or (isinstance(nl, torch.Tensor) and nl.requires_grad))
+    if not trainable:                                          # nothing to differentiate: forward_ragged's call, no graph
+        nv.begin_inference()
+        out, plan, _, _ = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
+        return list(out.split(plan.rows))
+    nv.note_training_forward()                                 # (the plan's refresh() then rebuilds the weight-derived tables from the live weights)
+    names, ps = zip(*params)
+    rows = []
+    out = _RaggedTrainFn.apply(proj, ff, fe, guides, nl, (split_sizes, modals, chunks, rows), names, *ps)
+    return list(out.split(rows))

@@ -23,7 +23,7 @@ cached_plan, MAX_PLANS = engine.cached_plan, engine.MAX_PLANS       # (the steps
 
 
 class SegPlan:
-    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes")
+    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes", "train_maps", "train_ws_bytes")
 
     def __init__(self, args, ws, rows, hidden, items=None, tables=None):
         # args: the block the entry point takes; io: the plain block inside it (args itself for the plain recipe), whose input / output
@@ -31,7 +31,7 @@ class SegPlan:
         # items / tables: the host item descriptors and the table arithmetic of a ragged plan, None for a batch plan
         self.args, self.ws, self.rows, self.hidden, self.items, self.tables = args, ws, rows, hidden, items, tables
         self.io = getattr(args, "base", args)
-        self.sig = self.fresh = self.refresh = self.keep = None
+        self.sig = self.fresh = self.refresh = self.keep = self.train_maps = self.train_ws_bytes = None   # (train_*: ragged_train.py's row maps and workspace size)
         self.hits = self.adapt_bytes = 0
 
 
@@ -209,10 +209,12 @@ def build_equal_plan(proj, what, plain, adapt, count, shape, tiles, modal, nl, o
     return plan
 
 
-def call_inputs(proj, what, ff, fe, guides, nl):
-    """The prologue of a call behind its scope checks: (device, the four inputs made contiguous, output dtype, stream)."""
+def call_inputs(proj, what, ff, fe, guides, nl, refuse_grad=True):
+    """The prologue of a call behind its scope checks: (device, the four inputs made contiguous, output dtype, stream).  refuse_grad
+    False: the caller builds the autograd graph itself (forward_ragged_train) and has told native.py which kind of forward this is."""
     from .projector import _out_dtype, _refuse_grad
-    _refuse_grad(proj, f"HIComProjector.{what}")
+    if refuse_grad:
+        _refuse_grad(proj, f"HIComProjector.{what}")
     dev = ff.device
 
     def dense(t):

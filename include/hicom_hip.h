@@ -941,6 +941,30 @@ int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compressor_ragged_ar
 int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_args* args);
 int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* args);
 
+/* ---- training step of the ragged call (plain recipe; HIComProjector.forward_ragged_train) -----------
+ * Rows are item-major, R = B nh of them: row = item nh + head.  The scores region is the forward's own: item i's logits at
+ * 16 score_off_i floats, [16][ceil16(N_i)], score_off_i = 16 sum_{j<i} ceil(N_j / 16).
+ * hicom_compressor_ragged_train_state, after hicom_compressor_ragged_fwd on the same block: copies out of args->ws what a backward
+ * reads -- ctx16 fp16 [windows, E], the scores region, ctxg f32 [R, E] -- and writes ml f32 [R][2] = (M, L) of every row from the
+ * partial states, in the merge's summation order.  Device-to-device copies and one launch on args->stream; no synchronisation.
+ * hicom_compressor_ragged_global_bwd: the attention backward of the global stage over all items, four launches whatever B and the
+ * mix are (dctx -> bf16 hi / lo planes; pos_b = dctx . pe^T; the segmented backward stream, one workgroup per work unit of the
+ * forward's unit table; the dq merge per (item, head)).  It reads only the table region of args->ws (hicom_compressor_ragged_prepare
+ * wrote it) and args' shape, pe and stream; x are the tokens the forward read (args->ff may have been patched since).
+ *   dctx f32 [R, E], delta f32 [R] = dctx_r . ctx_r, scores / ml as train_state left them
+ *   ds_out   : f32, laid out as the scores region: dS; the padded tail columns of a row are zero
+ *   dqt_out  : f32 [R, E] = sum_n dS[r, n] (x_n + pe_n): the x part from the stream, the positional part from dS's marginals
+ *   ws       : hicom_compressor_ragged_global_bwd_workspace_bytes(args) bytes, 256-byte aligned
+ * Neither call takes the sizes of the caller's buffers; with N_i = T_i H W tokens and w_i = (T_i / kt_i)(H / ks)(W / ks) windows per item:
+ *   ctx16_out            2 E sum w_i bytes
+ *   scores_out, ds_out   4 * 16 * sum 16 ceil(N_i / 16) bytes each (16 rows per item, the item's tokens padded to a tile)
+ *   ml_out               8 B nh bytes;   ctxg_out, dqt_out, dctx   4 E B nh bytes each;   delta   4 B nh bytes
+ * Only launches: no allocation, no host copy, no synchronisation. */
+int hicom_compressor_ragged_train_state(const hicom_compressor_ragged_args* args, void* ctx16_out, float* scores_out, float* ml_out, float* ctxg_out);
+int64_t hicom_compressor_ragged_global_bwd_workspace_bytes(const hicom_compressor_ragged_args* args);
+int hicom_compressor_ragged_global_bwd(const hicom_compressor_ragged_args* args, const void* x, const float* dctx, const float* delta,
+                                       const float* scores, const float* ml, float* ds_out, float* dqt_out, void* ws, int64_t ws_bytes);
+
 /* ---- the batched and the ragged step for the k / v adaptor recipe (`local43_adaptkv_global32`) ----------------------
  * The adaptors sit on the local stage only (projector.py:431-457, :533-534: key = (1 - a_k) x + a_k LN(MLP_k(x)) over ALL tokens of
  * the key stream, likewise the values over ff); the global stage reads the raw tokens, so launches 1-2 and 4-12 are those of the
