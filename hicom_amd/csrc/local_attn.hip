@@ -265,106 +265,21 @@ struct LocalBwdParams {
     int accumulate, par_mask, par_val;
 };
 
+// the body is window_rows.hpp's local_window_bwd, shared with the ragged training step (ragged.hip: ragged_local_attn_bwd_kernel)
 template <int NV>
 __global__ __launch_bounds__(256) void local_attn_bwd_kernel(LocalBwdParams p) {
     constexpr int D = NV * 384;
     extern __shared__ __attribute__((aligned(16))) float lsm[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int win = blockIdx.x;
     const WindowGeom w(p.at, p.ay, p.ax, win);
-    const int WIN = w.WIN, WP = (WIN + 3) & ~3;
-    float* sc = lsm;                              // [WIN] scores, then dS
-    float* dp = lsm + WP;                         // [WIN] dP
-    float* rin = lsm + 2 * WP;                    // [WIN] 1 / ||k_i|| (1 without l2norm_key)
-    float* sraw = lsm + 3 * WP;                   // [WIN] q . khat_i
-    float* pwt = lsm + 4 * WP;                    // [WIN] softmax weights p_i
-    float* part = lsm + 5 * WP;                   // [4][D] partial dq
     if ((((w.t1 & 1) | ((w.h1 & 1) << 1) | ((w.w1 & 1) << 2)) & p.par_mask) != p.par_val) return;      // (another launch's parity class)
 
-    float q[NV][6], g[NV][6];
+    float q[NV][6];
     load_query<NV>(p.query, p.query_f32, p.query_stride, win, lane, q);
-    load_row_f32<NV>(p.dctx + (long)win * D, lane, g);
-
-    // ---- phase 1: scores and dP ------------------------------------------------------------------
-    for (int i0 = wave; i0 < WIN; i0 += 8) {      // 2 tokens (key + value rows) in flight per wave
-        float k[2][NV][6], v[2][NV][6];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int i = i0 + 4 * u;
-            if (i < WIN) {
-                const long tok = w.token_of(i);
-                load_row<NV>(p.key + tok * D, lane, k[u]);
-                load_row<NV>(p.value + tok * D, lane, v[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int i = i0 + 4 * u;
-            if (i < WIN) {
-                float dot = wave_sum_fast(row_dot<NV>(q, k[u]));
-                const float dd = wave_sum_fast(row_dot<NV>(g, v[u]));
-                float ri = 1.0f;
-                if (p.l2norm_key) {
-                    ri = 1.0f / sqrtf(wave_sum_fast(row_dot<NV>(k[u], k[u])));
-                    dot *= ri;
-                }
-                if (lane == 0) { sc[i] = dot * p.scale + p.bias; dp[i] = dd; rin[i] = ri; sraw[i] = dot; }
-            }
-        }
-    }
-    __syncthreads();
-    float mx, inv_sum, delta;
-    softmax_stats(sc, WIN, lane, mx, inv_sum, dp, &delta);
-    __syncthreads();                               // every wave has read sc / dp as scores
-    if (wave == 0) {
-        float dl = 0.f;
-        for (int i = lane; i < WIN; i += 64) {
-            const float s_i = sc[i], pi_ = expf(s_i - mx) * inv_sum, dS = pi_ * (dp[i] - delta);
-            dl = fmaf(dS, s_i - p.bias, dl);
-            sc[i] = dS;
-            pwt[i] = pi_;
-        }
-        if (p.dls) {
-            dl = wave_sum_fast(dl);
-            if (lane == 0) p.dls[win] = dl;
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: dq = scale sum_i dS_i k_i ;  dkey_i = scale dS_i q -----------------------------------------
-    float acc[NV][6];
-    row_zero<NV>(acc);
-    for (int i0 = wave; i0 < WIN; i0 += 12) {
-        float k[3][NV][6];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int i = i0 + 4 * u;
-            if (i < WIN) load_row<NV>(p.key + w.token_of(i) * D, lane, k[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int i = i0 + 4 * u;
-            if (i < WIN) {
-                // (plain: dsk = ds, kc = 0.  clip-scale: d k_i = ds / ||k|| (q - khat (q . khat)) = dsk q - kc k with dsk = ds / ||k||,
-                // kc = dsk (q . khat) / ||k||; the dq sum runs over khat = k / ||k||)
-                const float ds = sc[i] * p.scale, dsk = ds * rin[i], kc = p.l2norm_key ? dsk * sraw[i] * rin[i] : 0.f;
-                row_axpy<NV>(dsk, k[u], acc);
-                auto dk = [&](int s, int j) { return fmaf(dsk, q[s][j], -kc * k[u][s][j]); };
-                if (p.dkey) store_row_bf16<NV>(p.dkey + w.token_of(i) * D, lane, p.accumulate, dk);
-                if (p.dvalue) {
-                    const float pi_ = pwt[i];
-                    store_row_bf16<NV>(p.dvalue + w.token_of(i) * D, lane, p.accumulate, [&](int s, int j) {
-                        float e = pi_ * g[s][j];
-                        if (p.value_is_key) e += dk(s, j);
-                        return e;
-                    });
-                }
-            }
-        }
-    }
-    store_partial_row<NV>(part, wave, lane, acc);
-    __syncthreads();
-    sum_partial_rows<NV>(part, tid, p.dq + (long)win * D);
+    const WindowBwdArgs a{p.key, p.value, p.scale, p.bias, p.dctx + (long)win * D, p.dq + (long)win * D, p.dkey, p.l2norm_key,
+                          p.dls ? p.dls + win : nullptr, p.dvalue, p.value_is_key, p.accumulate};
+    local_window_bwd<NV>(a, w, q, lsm, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -19,8 +19,12 @@
 // Training (plain recipe, hicom_amd/ragged_train.py): hicom_compressor_ragged_train_state hands the forward's state out of the workspace,
 // hicom_compressor_ragged_global_bwd runs the global stage's attention backward over all items on the forward's unit table -- the same
 // stream_segment in StreamMode::Bwd, then dq_merge_segments per (item, head).
+// Input gradients (stage 3): hicom_compressor_ragged_local_bwd is the window backward over the concatenated window list (window_rows.hpp:
+// local_window_bwd, the body of local_attn_bwd_kernel) with dq summed per item in a fixed order, hicom_compressor_ragged_global_dx the global
+// stage's d x with an item per workgroup (global_dx.hpp: global_dx_tile, the body of global_dx_kernel).
 #include <vector>
 
+#include "global_dx.hpp"
 #include "segment_host.hpp"
 
 namespace hicom {
@@ -166,6 +170,99 @@ __global__ __launch_bounds__(256) void ragged_dq_merge_kernel(RaggedDqMergeParam
     const long stride = (it.N + 15) / 16 * 16;
     dq_merge_segments(p.c, ms, r, threadIdx.x, it.T, it.chunks, (long)it.slot0, p.ds + (long)it.score_off * 16 + r * stride,
                       p.dqt + ((long)item * p.rows + r) * p.c.E);
+}
+
+// ---- training, input gradients: the window backward over the concatenated window list, one 4-wave workgroup per window (the mapping and
+// the body of local_attn_bwd_kernel: window_rows.hpp, local_window_bwd).  The workgroup learns its item from win_item, builds the window
+// from the item's own (T, kt), offsets the tokens by tok0 and takes the item's guide row as the query.  dq f32 [sum windows][D]; dkey /
+// dvalue bf16 [sum N_i][D] or NULL, plain stores: the windows of an item partition it, every token is written once ----
+struct RaggedLocalBwdParams {
+    const uint16_t* key;
+    const uint16_t* value;
+    const uint16_t* guide;  // [B][D]
+    const RaggedItem* items;
+    const int* win_item;
+    hicom_axis ay, ax;
+    float scale;
+    const float* dctx;      // [sum windows][D]
+    float* dq;              // [sum windows][D]
+    uint16_t* dkey;
+    uint16_t* dvalue;
+    int value_is_key;
+};
+
+template <int NV>
+__global__ __launch_bounds__(256) void ragged_local_attn_bwd_kernel(RaggedLocalBwdParams p) {
+    constexpr int D = NV * 384;
+    extern __shared__ __attribute__((aligned(16))) float lsm[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int win = blockIdx.x;
+    const int item = p.win_item[win];
+    const RaggedItem it = p.items[item];
+    const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+    const WindowGeom w(at, p.ay, p.ax, win - it.win0);
+    const long first = (long)it.tok0 * D;
+    float q[NV][6];
+    load_row<NV>(p.guide + (long)item * D, lane, q);
+    const WindowBwdArgs a{p.key + first, p.value + first, p.scale, 0.f, p.dctx + (long)win * D, p.dq + (long)win * D,
+                          p.dkey ? p.dkey + first : nullptr, 0, nullptr, p.dvalue ? p.dvalue + first : nullptr, p.value_is_key, 0};
+    local_window_bwd<NV>(a, w, q, lsm, tid);
+}
+
+// ... and the local share of d guide: dq_item[i] = sum of the dq rows of item i's windows, in a fixed order and without atomics.
+// grid = (E / 64, B), 256 threads = 16 stripes x 16 lanes of 4 channels: stripe s sums windows s, s + 16, ... in order, the sixteen partial
+// rows are added pairwise through LDS.
+__global__ __launch_bounds__(256) void ragged_dq_item_kernel(const float* dq, const RaggedItem* items, int wps, int E, float* dq_item) {
+    __shared__ float4 red[16][16];
+    const int item = blockIdx.y, lane = threadIdx.x & 15, stripe = threadIdx.x >> 4;
+    const int c = blockIdx.x * 64 + 4 * lane;
+    const RaggedItem it = items[item];
+    const int nwin = (it.T / it.kt) * wps;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < E)
+        for (int w = stripe; w < nwin; w += 16) {
+            const float4 v = *reinterpret_cast<const float4*>(dq + (long)(it.win0 + w) * E + c);
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+    red[stripe][lane] = a;
+    __syncthreads();
+    for (int half = 8; half > 0; half >>= 1) {
+        if (stripe < half) {
+            const float4 u = red[stripe][lane], v = red[stripe + half][lane];
+            red[stripe][lane] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+        }
+        __syncthreads();
+    }
+    if (stripe == 0 && c < E) *reinterpret_cast<float4*>(dq_item + (long)item * E + c) = red[0][lane];
+}
+
+// ---- training, input gradients: d x of the global stage, global_dx_kernel<9> with an item per workgroup (global_dx.hpp: the one body).
+// A workgroup takes 64 tokens of ONE item: tiles are counted from the item's first token (item offsets are 36, 144, 180 ... tokens), the
+// last tile of an item is masked at the item's end.  tiles: {item, first token of the tile inside the item} per workgroup, derived on the
+// host once per plan (hicom_amd/ragged.py: dx_tile_table) ----
+struct RaggedGlobalDxParams {
+    const float* S;         // the forward's scores region
+    const float* dS;        // laid out as S
+    const float* ml;        // [B * rows][2]
+    const float* qt;        // [B * rows][E]
+    const float* dctx;      // [B * rows][E]
+    const int2* tiles;
+    const RaggedItem* items;
+    int B, rows, E;
+    uint16_t* dx;           // [sum N_i][E]
+    int accumulate;
+};
+
+template <int RMAX>
+__global__ __launch_bounds__(320) void ragged_global_dx_kernel(RaggedGlobalDxParams p) {
+    __shared__ float coef[64][2 * RMAX];
+    const int2 tile = p.tiles[blockIdx.x];
+    if (tile.x < 0 || tile.x >= p.B) return;            // (a table that is not this plan's: nothing is indexed through it)
+    const RaggedItem it = p.items[tile.x];
+    if (tile.y < 0 || tile.y >= it.N) return;
+    const long row0 = (long)tile.x * p.rows, stride = (it.N + 15) / 16 * 16;
+    global_dx_tile<RMAX>(p.S + (long)it.score_off * 16, p.dS + (long)it.score_off * 16, stride, p.ml + 2 * row0, p.qt + row0 * p.E, p.dctx + row0 * p.E,
+                      p.rows, (long)tile.y, (long)it.N, p.E, p.dx + (long)it.tok0 * p.E, p.accumulate, coef);
 }
 
 // ---- 12: placement, one output row per workgroup over all items' rows ----
@@ -457,7 +554,75 @@ int ragged_global_bwd(const hicom_compressor_ragged_args* a, const void* x, cons
     return seg_check_launch(kWhoBwd, "dq merge");
 }
 
+// ---- training, input gradients (stage 3): the window backward over all items, and d x of the global stage -----------------------------------
+// Both read the table region at the head of args->ws; the pointers and the per-item partition are checked in front of everything that
+// needs a device (the layout asks for the CU count when chunks == 0).
+int ragged_local_bwd(const hicom_compressor_ragged_args* a, const void* key, const void* value, const void* guide, const float* dctx, float* dq,
+                     float* dq_item, void* dkey, void* dvalue, int value_is_key) {
+    constexpr const char* who = "compressor_ragged_local_bwd";
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(key && value && guide && dctx && dq, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE(!(value_is_key && dkey), HICOM_EINVAL, "%s: value_is_key writes the summed gradient to dvalue (dkey must be NULL)", who);
+    HICOM_REQUIRE(!value_is_key || key == value, HICOM_EINVAL, "%s: value_is_key: the keys are the value rows", who);
+    HICOM_REQUIRE((uintptr_t)key % 4 == 0 && (uintptr_t)value % 4 == 0 && (uintptr_t)guide % 4 == 0 && (uintptr_t)dctx % 16 == 0 && (uintptr_t)dq % 16 == 0 &&
+                      (uintptr_t)dq_item % 16 == 0 && (uintptr_t)dkey % 4 == 0 && (uintptr_t)dvalue % 4 == 0, HICOM_EINVAL, "%s: aligned pointers", who);
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(who, a, l.s.total);                     // (the table region at its head is what is read)
+    if (st != HICOM_OK) return st;
+    int max_kt = 1;
+    for (int i = 0; i < a->B; ++i) max_kt = a->items[i].kt > max_kt ? a->items[i].kt : max_kt;
+    const long WIN = (long)max_kt * a->ks * a->ks;             // (<= 64: seg_check_ragged_items)
+    const size_t smem = 5 * (((size_t)WIN + 3) & ~(size_t)3) * 4 + 4 * (size_t)a->E * 4;
+    const char* tab = (const char*)a->ws;
+    hipStream_t s = (hipStream_t)a->stream;
+    RaggedLocalBwdParams p;
+    p.key = (const uint16_t*)key; p.value = (const uint16_t*)value; p.guide = (const uint16_t*)guide;
+    p.items = (const RaggedItem*)(tab + l.items); p.win_item = (const int*)(tab + l.win_item);
+    p.ay = hicom_axis{a->H, a->ks, a->H / a->ks, a->H / a->ks}; p.ax = hicom_axis{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+    p.scale = a->l_scale; p.dctx = dctx; p.dq = dq; p.dkey = (uint16_t*)dkey; p.dvalue = (uint16_t*)dvalue; p.value_is_key = value_is_key ? 1 : 0;
+    HICOM_LAUNCH(ragged_local_attn_bwd_kernel<3>, dim3((unsigned)l.s.n.windows), dim3(256), smem, s, p);      // (E == 1152: ragged_check)
+    st = seg_check_launch(who, "window backward");
+    if (st != HICOM_OK || !dq_item) return st;
+    HICOM_LAUNCH(ragged_dq_item_kernel, dim3((unsigned)((a->E + 63) / 64), (unsigned)a->B), dim3(256), 0, s, (const float*)dq, p.items, l.wps, a->E, dq_item);
+    return seg_check_launch(who, "dq per item");
+}
+
+int ragged_global_dx(const hicom_compressor_ragged_args* a, const float* scores, const float* ds, const float* ml, const float* qt, const float* dctx,
+                     const int32_t* tiles, int ntiles, void* dx, int accumulate) {
+    constexpr const char* who = "compressor_ragged_global_dx";
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(scores && ds && ml && qt && dctx && tiles && dx, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE((uintptr_t)dx % 8 == 0 && (uintptr_t)qt % 16 == 0 && (uintptr_t)dctx % 16 == 0 && (uintptr_t)tiles % 8 == 0, HICOM_EINVAL, "%s: aligned pointers", who);
+    HICOM_REQUIRE(a->nh > 0 && a->nh <= 16 && a->E % 4 == 0 && a->E <= 1280, HICOM_EUNSUP, "%s: nh=%d (<= 16), E=%d (<= 1280, %% 4)", who, a->nh, a->E);
+    long want = 0;
+    for (int i = 0; i < a->B; ++i) want += ((long)a->items[i].T * a->H * a->W + 63) / 64;
+    HICOM_REQUIRE(ntiles == want, HICOM_EINVAL, "%s: %d tiles, the items have %ld tiles of 64 tokens", who, ntiles, want);
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(who, a, l.s.total);                     // (the table region at its head is what is read)
+    if (st != HICOM_OK) return st;
+    RaggedGlobalDxParams p;
+    p.S = scores; p.dS = ds; p.ml = ml; p.qt = qt; p.dctx = dctx; p.tiles = (const int2*)tiles;
+    p.items = (const RaggedItem*)((const char*)a->ws + l.items);
+    p.B = a->B; p.rows = a->nh; p.E = a->E; p.dx = (uint16_t*)dx; p.accumulate = accumulate ? 1 : 0;
+    hipStream_t s = (hipStream_t)a->stream;
+    if (a->nh <= 9) HICOM_LAUNCH(ragged_global_dx_kernel<9>, dim3((unsigned)ntiles), dim3(320), 0, s, p);
+    else HICOM_LAUNCH(ragged_global_dx_kernel<16>, dim3((unsigned)ntiles), dim3(320), 0, s, p);
+    return seg_check_launch(who, "global dx");
+}
+
 }  // namespace
+
+extern "C" int hicom_compressor_ragged_local_bwd(const hicom_compressor_ragged_args* a, const void* key, const void* value, const void* guide, const float* dctx,
+                                                 float* dq, float* dq_item, void* dkey, void* dvalue, int32_t value_is_key) {
+    return ragged_local_bwd(a, key, value, guide, dctx, dq, dq_item, dkey, dvalue, value_is_key);
+}
+
+extern "C" int hicom_compressor_ragged_global_dx(const hicom_compressor_ragged_args* a, const float* scores, const float* ds, const float* ml, const float* qt,
+                                                 const float* dctx, const int32_t* tiles, int32_t ntiles, void* dx, int32_t accumulate) {
+    return ragged_global_dx(a, scores, ds, ml, qt, dctx, tiles, ntiles, dx, accumulate);
+}
 
 extern "C" int hicom_compressor_ragged_train_state(const hicom_compressor_ragged_args* a, void* ctx16_out, float* scores_out, float* ml_out, float* ctxg_out) {
     return ragged_train_state(a, ctx16_out, scores_out, ml_out, ctxg_out);

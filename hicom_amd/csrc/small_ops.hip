@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "common.hpp"
+#include "global_dx.hpp"
 
 namespace hicom_host {
 static thread_local char g_err[512] = "";
@@ -467,57 +468,13 @@ __global__ __launch_bounds__(256) void partials_sum_tall_kernel(const float* par
 
 using namespace hicom;
 
-// d frames_feature of the global stage (direct recipe: <= 16 folded rows).  A workgroup takes 64 tokens; thread t owns channels
-// 4t .. 4t+3 with the 2 * rows coefficient rows (qt | dctx) of those channels in registers and walks the tokens: per token 2 * rows
-// broadcast LDS reads of the coefficients (dS, p), 8 * rows FMAs, one 8-byte store.
+// d frames_feature of the global stage (direct recipe: <= 16 folded rows).  A workgroup takes 64 tokens of the call's one token run; the body
+// is global_dx.hpp's global_dx_tile, shared with the ragged training step (ragged.hip: ragged_global_dx_kernel)
 template <int RMAX>
 __global__ __launch_bounds__(320) void global_dx_kernel(const float* S, const float* dS, long stride, const float* ml, const float* qt, const float* dctx,
                                                           int rows, long N, int E, uint16_t* dx, int accumulate) {
     __shared__ float coef[64][2 * RMAX];
-    const int tid = threadIdx.x;
-    const long n0 = (long)blockIdx.x * 64;
-    // every coefficient the unrolled loop below reads is written here: rows >= `rows` as zeros (stale LDS holding Inf / NaN would
-    // otherwise meet the zeroed wq / wd and give NaN)
-    for (int idx = tid; idx < 64 * RMAX; idx += blockDim.x) {
-        const int r = idx / 64, t = idx - r * 64;
-        const long n = n0 + t;
-        float a = 0.f, b = 0.f;
-        if (r < rows && n < N) {
-            a = dS[(long)r * stride + n];
-            b = expf(S[(long)r * stride + n] - ml[2 * r]) / ml[2 * r + 1];
-        }
-        coef[t][r] = a;
-        coef[t][RMAX + r] = b;
-    }
-    const int c4 = 4 * tid;
-    float4 wq[RMAX], wd[RMAX];
-#pragma unroll
-    for (int r = 0; r < RMAX; ++r) {
-        wq[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-        wd[r] = wq[r];
-        if (r < rows && c4 < E) {
-            wq[r] = *reinterpret_cast<const float4*>(qt + (long)r * E + c4);
-            wd[r] = *reinterpret_cast<const float4*>(dctx + (long)r * E + c4);
-        }
-    }
-    __syncthreads();
-    if (c4 >= E) return;
-    for (int t = 0; t < 64 && n0 + t < N; ++t) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        uint16_t* o = dx + (n0 + t) * (long)E + c4;
-        if (accumulate) {
-            const uint2 old = *reinterpret_cast<const uint2*>(o);
-            a = make_float4(bf16lo_to_f32(old.x), bf16hi_to_f32(old.x), bf16lo_to_f32(old.y), bf16hi_to_f32(old.y));
-        }
-#pragma unroll
-        for (int r = 0; r < RMAX; ++r) {
-            const float ca = coef[t][r], cb = coef[t][RMAX + r];
-            a.x = fmaf(ca, wq[r].x, a.x); a.y = fmaf(ca, wq[r].y, a.y); a.z = fmaf(ca, wq[r].z, a.z); a.w = fmaf(ca, wq[r].w, a.w);
-            a.x = fmaf(cb, wd[r].x, a.x); a.y = fmaf(cb, wd[r].y, a.y); a.z = fmaf(cb, wd[r].z, a.z); a.w = fmaf(cb, wd[r].w, a.w);
-        }
-        *reinterpret_cast<uint2*>(o) = make_uint2((unsigned)f32_to_bf16(a.x) | ((unsigned)f32_to_bf16(a.y) << 16),
-                                                  (unsigned)f32_to_bf16(a.z) | ((unsigned)f32_to_bf16(a.w) << 16));
-    }
+    global_dx_tile<RMAX>(S, dS, stride, ml, qt, dctx, rows, (long)blockIdx.x * 64, N, E, dx, accumulate, coef);
 }
 
 extern "C" int hicom_global_dx_fwd(const float* S, const float* dS, int64_t score_stride, const float* ml, const float* qt, const float* dctx,

@@ -250,4 +250,122 @@ __device__ __forceinline__ void sum_partial_rows(const float* part, int tid, flo
     sum_partial_rows<NV>(part, tid, [&](int c, float v) { out[c] = v; });
 }
 
+// ---- backward of one window of the plain windowed attention: the one body of local_attn_bwd_kernel (local_attn.hip: the window comes from
+// blockIdx and the call's one grid) and ragged_local_attn_bwd_kernel (ragged.hip: the window's item comes from a device table, the grid is
+// the item's own).  Per window, autograd through projector.py:550-553 (local_attn.hip has the algebra and the clip-scale terms):
+//     s_i = scale q.k_i + bias,  p = softmax(s),  dP_i = dctx . v_i,  dS_i = p_i (dP_i - sum_j p_j dP_j),
+//     dq = scale sum_i dS_i k_i,  dk_i = scale dS_i q,  dv_i = p_i dctx (+ dk_i with value_is_key)
+// key / value / dkey / dvalue point at the first token of the grid `w` indexes; dctx / dq at the window's own row; dls at the window's own
+// element or NULL.  One 4-wave workgroup, lsm: 5 per-token arrays of the window + the [4][D] slab (window_smem(WIN, D, 5)).
+struct WindowBwdArgs {
+    const uint16_t* key;
+    const uint16_t* value;
+    float scale, bias;
+    const float* dctx;     // [D]
+    float* dq;             // [D]
+    uint16_t* dkey;        // bf16 [N, D] or NULL
+    int l2norm_key;
+    float* dls;            // one float or NULL
+    uint16_t* dvalue;      // bf16 [N, D] or NULL
+    int value_is_key;
+    int accumulate;
+};
+
+template <int NV>
+__device__ __forceinline__ void local_window_bwd(const WindowBwdArgs& p, const WindowGeom& w, const float (&q)[NV][6], float* lsm, int tid) {
+    constexpr int D = NV * 384;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int WIN = w.WIN, WP = (WIN + 3) & ~3;
+    float* sc = lsm;                              // [WIN] scores, then dS
+    float* dp = lsm + WP;                         // [WIN] dP
+    float* rin = lsm + 2 * WP;                    // [WIN] 1 / ||k_i|| (1 without l2norm_key)
+    float* sraw = lsm + 3 * WP;                   // [WIN] q . khat_i
+    float* pwt = lsm + 4 * WP;                    // [WIN] softmax weights p_i
+    float* part = lsm + 5 * WP;                   // [4][D] partial dq
+
+    float g[NV][6];
+    load_row_f32<NV>(p.dctx, lane, g);
+
+    // ---- phase 1: scores and dP ------------------------------------------------------------------
+    for (int i0 = wave; i0 < WIN; i0 += 8) {      // 2 tokens (key + value rows) in flight per wave
+        float k[2][NV][6], v[2][NV][6];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = i0 + 4 * u;
+            if (i < WIN) {
+                const long tok = w.token_of(i);
+                load_row<NV>(p.key + tok * D, lane, k[u]);
+                load_row<NV>(p.value + tok * D, lane, v[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = i0 + 4 * u;
+            if (i < WIN) {
+                float dot = wave_sum_fast(row_dot<NV>(q, k[u]));
+                const float dd = wave_sum_fast(row_dot<NV>(g, v[u]));
+                float ri = 1.0f;
+                if (p.l2norm_key) {
+                    ri = 1.0f / sqrtf(wave_sum_fast(row_dot<NV>(k[u], k[u])));
+                    dot *= ri;
+                }
+                if (lane == 0) { sc[i] = dot * p.scale + p.bias; dp[i] = dd; rin[i] = ri; sraw[i] = dot; }
+            }
+        }
+    }
+    __syncthreads();
+    float mx, inv_sum, delta;
+    softmax_stats(sc, WIN, lane, mx, inv_sum, dp, &delta);
+    __syncthreads();                               // every wave has read sc / dp as scores
+    if (wave == 0) {
+        float dl = 0.f;
+        for (int i = lane; i < WIN; i += 64) {
+            const float s_i = sc[i], pi_ = expf(s_i - mx) * inv_sum, dS = pi_ * (dp[i] - delta);
+            dl = fmaf(dS, s_i - p.bias, dl);
+            sc[i] = dS;
+            pwt[i] = pi_;
+        }
+        if (p.dls) {
+            dl = wave_sum_fast(dl);
+            if (lane == 0) *p.dls = dl;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: dq = scale sum_i dS_i k_i ;  dkey_i = scale dS_i q -----------------------------------------
+    float acc[NV][6];
+    row_zero<NV>(acc);
+    for (int i0 = wave; i0 < WIN; i0 += 12) {
+        float k[3][NV][6];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int i = i0 + 4 * u;
+            if (i < WIN) load_row<NV>(p.key + w.token_of(i) * D, lane, k[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int i = i0 + 4 * u;
+            if (i < WIN) {
+                // (plain: dsk = ds, kc = 0.  clip-scale: d k_i = ds / ||k|| (q - khat (q . khat)) = dsk q - kc k with dsk = ds / ||k||,
+                // kc = dsk (q . khat) / ||k||; the dq sum runs over khat = k / ||k||)
+                const float ds = sc[i] * p.scale, dsk = ds * rin[i], kc = p.l2norm_key ? dsk * sraw[i] * rin[i] : 0.f;
+                row_axpy<NV>(dsk, k[u], acc);
+                auto dk = [&](int s, int j) { return fmaf(dsk, q[s][j], -kc * k[u][s][j]); };
+                if (p.dkey) store_row_bf16<NV>(p.dkey + w.token_of(i) * D, lane, p.accumulate, dk);
+                if (p.dvalue) {
+                    const float pi_ = pwt[i];
+                    store_row_bf16<NV>(p.dvalue + w.token_of(i) * D, lane, p.accumulate, [&](int s, int j) {
+                        float e = pi_ * g[s][j];
+                        if (p.value_is_key) e += dk(s, j);
+                        return e;
+                    });
+                }
+            }
+        }
+    }
+    store_partial_row<NV>(part, wave, lane, acc);
+    __syncthreads();
+    sum_partial_rows<NV>(part, tid, p.dq);
+}
+
 }  // namespace hicom

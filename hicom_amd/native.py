@@ -429,6 +429,8 @@ SIGNATURES = {
     "hicom_compressor_ragged_train_state": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp]),
     "hicom_compressor_ragged_global_bwd_workspace_bytes": (i64, [C.POINTER(CompressorRaggedArgs)]),
     "hicom_compressor_ragged_global_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "hicom_compressor_ragged_local_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, vp, vp, i32]),
+    "hicom_compressor_ragged_global_dx": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, i32, vp, i32]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -836,6 +838,22 @@ def compressor_ragged_global_bwd(args: CompressorRaggedArgs, x, dctx, delta, sco
     """The global stage's attention backward over all items of a ragged plan (hicom_compressor_ragged_global_bwd): fills ds and dqt."""
     _check(lib().hicom_compressor_ragged_global_bwd(C.byref(args), _ptr(x), _ptr(dctx), _ptr(delta), _ptr(scores), _ptr(ml), _ptr(ds), _ptr(dqt), _ptr(ws),
                                                     ws.numel()), "hicom_compressor_ragged_global_bwd")
+
+
+def compressor_ragged_local_bwd(args: CompressorRaggedArgs, key, value, guide, dctx, dq, dq_item=None, dkey=None, dvalue=None, value_is_key=False):
+    """The window backward over all items of a ragged plan (hicom_compressor_ragged_local_bwd): fills dq [windows, E], dq_item [B, E] (the
+    windows of an item summed in a fixed order) and whichever of dkey / dvalue bf16 [tokens, E] is given."""
+    assert key.dtype == value.dtype == guide.dtype == torch.bfloat16 and dctx.dtype == dq.dtype == torch.float32
+    _check(lib().hicom_compressor_ragged_local_bwd(C.byref(args), _ptr(key), _ptr(value), _ptr(guide), _ptr(dctx), _ptr(dq), _ptr(dq_item), _ptr(dkey),
+                                                   _ptr(dvalue), int(bool(value_is_key))), "hicom_compressor_ragged_local_bwd")
+
+
+def compressor_ragged_global_dx(args: CompressorRaggedArgs, scores, ds, ml, qt, dctx, tiles, dx, accumulate):
+    """d frames_feature of the global stage over all items of a ragged plan (hicom_compressor_ragged_global_dx); tiles: the device int32
+    [ntiles, 2] table of ragged.dx_tile_table."""
+    assert tiles.dtype == torch.int32 and tiles.is_contiguous() and dx.dtype == torch.bfloat16
+    _check(lib().hicom_compressor_ragged_global_dx(C.byref(args), _ptr(scores), _ptr(ds), _ptr(ml), _ptr(qt), _ptr(dctx), _ptr(tiles), tiles.shape[0],
+                                                   _ptr(dx), int(bool(accumulate))), "hicom_compressor_ragged_global_dx")
 
 
 def compressor_multiguide_workspace(args) -> int:

@@ -1110,7 +1110,8 @@ class HIComProjector(nn.Module):
         from . import ragged
         return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
 
-    def forward_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None):
+    def forward_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None,
+                             input_grads=False):
         """forward_ragged under autograd: the training step of a mixed batch (reference hicom_arch.py:146-180 with the projector trainable,
         train.py:709-713) in one forward call and ONE backward over all items.  Arguments, scope checks, plan cache and return value are
         forward_ragged's (a uniform batch is split_sizes = (T,) * B on the 4-D view), the outputs are bit-equal to it, and they carry a
@@ -1118,9 +1119,15 @@ class HIComProjector(nn.Module):
         eager, one pass over all items whose call sequence depends neither on B nor on the mix (ragged_train.py).
         The plain release recipe `local43_global32` only.  NotImplementedError, naming the loop of forward() to use instead, for the
         k / v adaptor recipe, clip-scale, anyres dicts and a frames_feature, frames_embed or guide_embeds that requires grad (stage 3):
-        nothing is detached silently.  With nothing trainable, or under no_grad, it is forward_ragged's call without a graph."""
+        nothing is detached silently.  With nothing trainable, or under no_grad, it is forward_ragged's call without a graph.
+        `input_grads=True` (stage 3 of the reference's script, train.py:712-726: the SigLIP head, the guide encoder and, under
+        `pure_vision_model`, the tower body train too): each of frames_feature, frames_embed and guide_embeds that requires grad gets its
+        gradient through autograd, in its own dtype and shape, from two more native calls over all items; an input that
+        does not require grad costs nothing, and the parameter gradients are bit-equal to those of the same step with the inputs detached.
+        The default False keeps the three refusals."""
         from . import ragged_train
-        return ragged_train.run_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
+        return ragged_train.run_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks,
+                                             input_grads)
 
     def forward_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None, local_logits=None):
         """ONE image or clip, Q instructions in one native call: frames_feature / frames_embed bf16 [T, H, W, E] as for forward()

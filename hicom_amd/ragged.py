@@ -112,6 +112,16 @@ def train_row_maps(t):
     return np.concatenate(local), np.concatenate(newline), np.stack(glob)
 
 
+DX_TILE = 64             # tokens per workgroup of ragged_global_dx_kernel (csrc/ragged.hip)
+
+
+def dx_tile_table(t) -> np.ndarray:
+    """The tile -> item table of hicom_compressor_ragged_global_dx from plan_tables' result alone: int32 [sum ceil(N_i / 64), 2] rows
+    (item, first token of the tile inside the item).  Tiles are counted from each item's first token, so no tile spans two items; an
+    item's last tile ends at the item's end (the kernel masks it there)."""
+    return np.array([(i, n0) for i, N in enumerate(t.N) for n0 in range(0, N, DX_TILE)], dtype=np.int32).reshape(-1, 2)
+
+
 def _scope(proj, ff, fe, guides, split_sizes, modals, nl, what="forward_ragged"):
     """Raises for everything outside the ragged step's scope that does not need the per-item geometry; returns (B, H, W, E,
     split_sizes, modals) with the last two as tuples."""

@@ -14,6 +14,16 @@ same bits) and the backward is ONE eager pass over all items: the same call sequ
 The autograd node owns what its backward reads (window contexts, logits, softmax state, merged contexts: copied out of the plan's
 workspace by hicom_compressor_ragged_train_state), so forward, forward, backward, backward on one plan works.
 
+Input gradients (stage 3 of the reference's script, train.py:712-726; `input_grads=True`): every one of frames_feature,
+frames_embed and guide_embeds that requires grad gets its gradient, from two more native calls over all items:
+
+  local stage    hicom_compressor_ragged_local_bwd: the window backward over the concatenated window list (dq per window, d frames_embed,
+                 the value-side share of d frames_feature -- with the key-side term where frames_embed is None), and dq summed per item;
+  global stage   hicom_compressor_ragged_global_dx: dS^T qt + P^T dctx per item, added into the rows the window backward left.
+
+d guide_embeds[i] = dq_item[i] + row i of (dqp Wq + dpre): the injected query of the direct recipe is the guide, one row per item.  A stage
+whose parameters are all frozen runs only where an input gradient needs it (d frames_feature and d guide_embeds: both; d frames_embed: local).
+
 Scope: the plain release recipe `local43_global32` (use_guide="direct", no adaptors, no clip-scale, bf16 module and inputs, exact window
 partition per item); gradients of every projector parameter that requires grad and of image_newline.  Everything else raises
 NotImplementedError naming the loop of forward(): nothing is detached silently."""
@@ -32,7 +42,7 @@ WHAT = "forward_ragged_train"
 _LOOP = "run the loop of forward() per item instead"
 
 
-def check_scope(proj, ff, fe, guides):
+def check_scope(proj, ff, fe, guides, input_grads=False):
     """The refusals of forward_ragged_train that forward_ragged does not make; no device is touched."""
     if isinstance(ff, dict) or isinstance(fe, dict):
         raise NotImplementedError(f"{WHAT}: anyres dict inputs have no ragged training step; {_LOOP}")
@@ -45,8 +55,9 @@ def check_scope(proj, ff, fe, guides):
         raise NotImplementedError(f"{WHAT} is built for the plain release recipe local43_global32 only (local + global compressor, "
                                   f"use_guide='direct', no adaptors, no clip scale); {_LOOP}")
     for name, t in (("frames_feature", ff), ("frames_embed", fe), ("guide_embeds", guides)):
-        if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"{WHAT}: the gradient w.r.t. {name} (stage 3) is not built for the ragged training step; detach it, or {_LOOP}")
+        if not input_grads and isinstance(t, torch.Tensor) and t.requires_grad:
+            raise NotImplementedError(f"{WHAT}: the gradient w.r.t. {name} (stage 3) is not built for the ragged training step without "
+                                      f"input_grads=True; pass it, detach {name}, or {_LOOP}")
 
 
 def _device_maps(plan, dev):
@@ -56,6 +67,13 @@ def _device_maps(plan, dev):
     return plan.train_maps
 
 
+def _device_tiles(plan, dev):
+    """ragged.dx_tile_table of the plan as a device int32 [ntiles, 2] tensor, made once per plan."""
+    if plan.train_tiles is None:
+        plan.train_tiles = torch.from_numpy(ragged.dx_tile_table(plan.tables)).to(dev)
+    return plan.train_tiles
+
+
 class _RaggedTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, proj, ff, fe, guides, nl, meta, names, *params):
@@ -63,6 +81,8 @@ class _RaggedTrainFn(torch.autograd.Function):
         with torch.no_grad():
             out, plan, x, g = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
             t, a, dev = plan.tables, plan.io, x.device
+            # frames_embed, by reference, only where the window backward will run (an input gradient is asked for)
+            keys = fe.contiguous() if (fe is not None and any(ctx.needs_input_grad[1:4])) else None
             R, E = a.B * a.nh, a.E
             f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
             ctx16 = torch.empty((sum(t.windows), E), dtype=torch.float16, device=dev)
@@ -71,20 +91,29 @@ class _RaggedTrainFn(torch.autograd.Function):
         rows.extend(plan.rows)                                 # (for the caller: how to split the output)
         ctx.proj, ctx.plan, ctx.names = proj, plan, names
         ctx.nl_meta = None if nl is None else nl.dtype
-        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg)
+        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg, keys)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, guides, ctx16, scores, ml, ctxg = ctx.saved_tensors
+        x, guides, ctx16, scores, ml, ctxg, keys = ctx.saved_tensors
         proj, plan, names = ctx.proj, ctx.plan, ctx.names
         need = ctx.needs_input_grad            # (proj, ff, fe, guides, nl, meta, names, *params)
         want = {n for k, n in enumerate(names) if need[7 + k]}
+        inputs = None
+        if any(need[1:4]):
+            inputs = types.SimpleNamespace(want_ff=bool(need[1]), want_fe=bool(need[2]), want_guide=bool(need[3]), fe=keys, d_ff=None, d_fe=None, d_guide=None)
         with torch.no_grad():
-            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]))
+            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]), inputs)
         ag.LAST_FP32_GRADS = dict(grads)               # (test hook, as the single-item backward leaves it; here with d image_newline)
         if d_nl is not None:
             ag.LAST_FP32_GRADS["image_newline"] = d_nl
+        d_ff = d_fe = d_g = None
+        if inputs is not None:
+            d_ff, d_fe = inputs.d_ff, inputs.d_fe
+            if inputs.d_guide is not None:
+                ag.LAST_FP32_GRADS["__guide_embeds__"] = inputs.d_guide        # (fp32 [B, E], as the single-item path leaves "__guide_embed__")
+                d_g = inputs.d_guide.to(guides.dtype)
         plist = dict(proj.named_parameters())
         out = [None] * len(names)
         by_dtype = {}
@@ -97,12 +126,14 @@ class _RaggedTrainFn(torch.autograd.Function):
                 cnt = plist[n].numel()
                 out[k] = flat[o:o + cnt].view(plist[n].shape)
                 o += cnt
-        return (None, None, None, None, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
+        return (None, d_ff, d_fe, d_g, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
 
 
-def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl):
+def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl, inputs=None):
     """(fp32 gradients {parameter name: tensor} of sum(out * dout) over all items, d image_newline or None).  `want`: the names of the
-    parameters whose gradient is asked for; a stage none of whose parameters is wanted does not run."""
+    parameters whose gradient is asked for; a stage none of whose parameters is wanted does not run unless an input gradient needs it.
+    inputs (None: no input gradient is asked for): want_ff / want_fe / want_guide and the contiguous frames_embed (or None) in, d_ff / d_fe
+    (bf16, the inputs' shapes) and d_guide (fp32 [B, E]) out."""
     lc, gc = proj.local_compressor, proj.global_compressor
     dev, a = x.device, plan.io
     local_rows, nl_rows, glob_rows = _device_maps(plan, dev)
@@ -110,17 +141,31 @@ def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, 
     st = types.SimpleNamespace(proj=proj, ff=x, dev=dev, f32=ag._f32_params(proj), grads={})
     f32, L = st.f32, "local_compressor.readout."
     d_nl = dout[nl_rows].sum(0) if (want_nl and nl_rows.numel()) else None
-    if any(n.startswith("local_compressor.") for n in want):
-        assert not ag._window_backward_runs(lc, False, False, proj.local_logit, False)
+    want_ff = inputs is not None and inputs.want_ff
+    want_fe = inputs is not None and inputs.want_fe and inputs.fe is not None
+    want_guide = inputs is not None and inputs.want_guide
+    window = want_ff or want_fe or want_guide                  # (the window backward: every input gradient has a local share)
+    dq_item = None
+    if window or any(n.startswith("local_compressor.") for n in want):
+        assert ag._window_backward_runs(lc, want_fe, want_guide, proj.local_logit, want_ff) == window
         ctx_l = ctx16.float()
         W0, b0 = f32[L + "0.weight"], f32[L + "0.bias"]
-        ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
-    if any(n.startswith("global_compressor.") for n in want):
+        dpre = ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
+        if window:
+            fe = inputs.fe
+            dctx_l = (dpre @ W0).contiguous()
+            dq_w = torch.empty_like(dctx_l)
+            dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=dev) if want_guide else None
+            inputs.d_fe = torch.empty_like(fe) if want_fe else None
+            inputs.d_ff = torch.empty_like(x) if want_ff else None          # (value-side share; without frames_embed the key-side term is added in)
+            nv.compressor_ragged_local_bwd(a, fe if fe is not None else x, x, guides, dctx_l, dq_w, dq_item, inputs.d_fe, inputs.d_ff,
+                                           value_is_key=want_ff and fe is None)
+    if want_ff or want_guide or any(n.startswith("global_compressor.") for n in want):
         att = gc.attn_layer
         nh, hd = att.num_heads, att.head_dim
         q32 = guides.float()
         dtok = dout[glob_rows].sum(1)                          # [B, hidden]: an item's global rows are copies of one row
-        _, dctx, delta = ag._global_tail_backward(st, nh, hd, ml, None, q32, dtok, ctxg=ctxg)
+        dpre_g, dctx, delta = ag._global_tail_backward(st, nh, hd, ml, None, q32, dtok, ctxg=ctxg)
         ds = torch.empty_like(scores)
         dqt = torch.empty_like(ctxg)
         if plan.train_ws_bytes is None:                        # (fixed per plan, like the row maps)
@@ -131,13 +176,25 @@ def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, 
         dqp = ag._global_fold_backward(st, att, None, None, None, None, q32, f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"],
                                        dqt=dqt)
         ag._q_proj_backward(st.grads, dqp, q32)
+        if want_ff:
+            # d frames_feature, global share (the algebra of autograd._global_dff with the B guides as the B queries): qt for all B nh rows,
+            # then one call over all items, added to the rows the window backward left
+            Wq, bq, Wk = f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"]
+            E = q32.shape[1]
+            qp_ = (q32 @ Wq.t() + bq).view(-1, nh, hd)
+            qt_ = (att.scale * torch.einsum("hje,qhj->qhe", Wk.view(nh, hd, E), qp_)).reshape(-1, E).contiguous()
+            nv.compressor_ragged_global_dx(a, scores, ds, ml, qt_, dctx, _device_tiles(plan, dev), inputs.d_ff.view(-1, E), accumulate=True)
+        if want_guide:
+            # direct recipe: the injected query IS the guide, one row per item (autograd._global_query_backward) + the local stage's share
+            inputs.d_guide = dq_item + (dqp @ f32[A + "q_proj.weight"] + dpre_g)
     return st.grads, d_nl
 
 
-def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
-    check_scope(proj, ff, fe, guides)
+def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, input_grads=False):
+    check_scope(proj, ff, fe, guides, input_grads)
     params = [(n, p) for n, p in proj.named_parameters()]
-    trainable = torch.is_grad_enabled() and (any(p.requires_grad for _, p in params) or (isinstance(nl, torch.Tensor) and nl.requires_grad))
+    trainable = torch.is_grad_enabled() and (any(p.requires_grad for _, p in params) or (isinstance(nl, torch.Tensor) and nl.requires_grad)
+                                             or (input_grads and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (ff, fe, guides))))
     if not trainable:                                          # nothing to differentiate: forward_ragged's call, no graph
         nv.begin_inference()
         out, plan, _, _ = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)

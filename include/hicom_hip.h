@@ -965,6 +965,28 @@ int64_t hicom_compressor_ragged_global_bwd_workspace_bytes(const hicom_compresso
 int hicom_compressor_ragged_global_bwd(const hicom_compressor_ragged_args* args, const void* x, const float* dctx, const float* delta,
                                        const float* scores, const float* ml, float* ds_out, float* dqt_out, void* ws, int64_t ws_bytes);
 
+/* ---- input gradients of the ragged training step (stage 3; forward_ragged_train(input_grads=True)) ----
+ * Both calls read only the table region of args->ws and args' shape, l_scale and stream; both check their pointers and the per-item
+ * partition in front of everything that needs a device.  Only launches: no allocation, no host copy, no synchronisation.
+ * hicom_compressor_ragged_local_bwd: hicom_local_attn_bwd over the concatenated window list, one 4-wave workgroup per window with the
+ * window's geometry from its item's own (T, kt), the tokens offset by the item's first token and the item's guide row as the query.
+ *   key, value : bf16 [sum N_i, E] (frames_embed and frames_feature; the same pointer twice without frames_embed), guide bf16 [B, E]
+ *   dctx       : f32 [sum w_i, E], the cotangent of the window contexts
+ *   dq         : f32 [sum w_i, E] per window;  dq_item f32 [B, E] or NULL: the rows of an item's windows summed in a fixed order (a
+ *                second launch, no atomics): the local share of d guide
+ *   dkey, dvalue : bf16 [sum N_i, E] or NULL, plain stores (every token lies in one window: nothing is cleared); value_is_key: key ==
+ *                value, dkey NULL, and the key-side gradient of a row is added into dvalue
+ * hicom_compressor_ragged_global_dx: hicom_global_dx_fwd with an item per workgroup,
+ *   dx[n] (+)= sum_r ds[i nh + r, n] qt[i nh + r] + softmax(scores)[i nh + r, n] dctx[i nh + r]   for the tokens n of item i.
+ *   scores, ds, ml : as hicom_compressor_ragged_global_bwd read and left them;  qt, dctx f32 [B nh, E]
+ *   tiles      : DEVICE array of ntiles pairs {item, first token of the tile inside the item}, tiles of 64 tokens counted from each item's
+ *                first token, ntiles = sum ceil(N_i / 64); a pair that names no item or no token of it is skipped
+ *   dx         : bf16 [sum N_i, E]; accumulate: read, added to and rewritten (the rows the window backward left) */
+int hicom_compressor_ragged_local_bwd(const hicom_compressor_ragged_args* args, const void* key, const void* value, const void* guide, const float* dctx,
+                                      float* dq, float* dq_item, void* dkey, void* dvalue, int32_t value_is_key);
+int hicom_compressor_ragged_global_dx(const hicom_compressor_ragged_args* args, const float* scores, const float* ds, const float* ml, const float* qt,
+                                      const float* dctx, const int32_t* tiles, int32_t ntiles, void* dx, int32_t accumulate);
+
 /* ---- the batched and the ragged step for the k / v adaptor recipe (`local43_adaptkv_global32`) ----------------------
  * The adaptors sit on the local stage only (projector.py:431-457, :533-534: key = (1 - a_k) x + a_k LN(MLP_k(x)) over ALL tokens of
  * the key stream, likewise the values over ff); the global stage reads the raw tokens, so launches 1-2 and 4-12 are those of the
