@@ -97,13 +97,21 @@ def _adaptor_recompute(x2, mlp, out=None, a16=None):
     out = (h1, _, y) buffers to fill (the training forward's per-shape store), else fresh tensors."""
     from . import injector as inj
     N, D = x2.shape
-    w1, b1 = mlp[0].weight.detach(), mlp[0].bias.detach()
-    h1, _, y = out if out is not None else (torch.empty((N, w1.shape[0]), dtype=torch.float16, device=x2.device), None,
-                                            torch.empty((N, mlp[2].weight.shape[0]), dtype=torch.float16, device=x2.device))
-    a16 = torch.empty_like(h1) if a16 is None else a16
-    nv.dense16_gemm(x2, w1, b1, act=nv.ACT_GELU, out_f16=a16, pre_f16=h1)
+    h1, _, y = out if out is not None else (None, None, torch.empty((N, mlp[2].weight.shape[0]), dtype=torch.float16, device=x2.device))
+    h1, a16 = _adaptor_hidden(x2, mlp, h1, a16)
     nv.dense16_gemm(a16, inj._f16_weight(mlp[2]), mlp[2].bias.detach(), out_f16=y)
     return h1, None, y
+
+
+def _adaptor_hidden(x2, mlp, h1=None, a16=None):
+    """Layer 1 of one adaptor MLP over all tokens, in the inference forward's arithmetic: (h1 = W1 x + b1 before the activation, a16 =
+    GELU(h1)), both fp16, from ONE GEMM (the epilogue's two outputs).  Alone it is what the ragged training step recomputes in its backward
+    (ragged_train.py keeps y, the forward's own bits, and no hidden plane)."""
+    w1, b1 = mlp[0].weight.detach(), mlp[0].bias.detach()
+    h1 = torch.empty((x2.shape[0], w1.shape[0]), dtype=torch.float16, device=x2.device) if h1 is None else h1
+    a16 = torch.empty_like(h1) if a16 is None else a16
+    nv.dense16_gemm(x2, w1, b1, act=nv.ACT_GELU, out_f16=a16, pre_f16=h1)
+    return h1, a16
 
 
 class _AdaptorStore:
@@ -194,11 +202,18 @@ def _adaptor_store(proj, ff):
     return st
 
 
-def _adaptor_mlp_backward(x2, mlp, norm, alpha, rec, coef, vec, vec_stride, axes, prefix, which, grads, want_x):
+def _single_item_dy(vec_stride, axes):
+    """The dy step of ONE item's tokens: hicom_adapt_dy_fwd on the item's axes, the rank-1 vector indexed by the window (stride 0: shared)."""
+    return lambda y, gamma, vec, coef, alpha, dy, r1, **kw: nv.adapt_dy(y, gamma, vec, vec_stride, coef, alpha, axes, dy, r1, **kw)
+
+
+def _adaptor_mlp_backward(x2, mlp, norm, alpha, rec, coef, vec, dy_step, prefix, which, grads, want_x):
     """Backward of (1 - a) x + a LN(MLP(x)) over ALL tokens (adapt_k / adapt_v, reference projector.py:533-534) for the rank-1 upstream
     gradient coef[tok] * vec[w(tok)] the window attention leaves (hicom_local_attn_adapt_bwd), on HIP kernels: hicom_adapt_dy_fwd (LayerNorm
     backward per token -> dy bf16), the weight gradients dW = dY^T X on the TN form of the dense MFMA GEMM, d hidden = dy W2 on its NT form,
-    GELU' and the bias sums as streaming kernels.  Returns d x (bf16 [N, D]) when want_x."""
+    GELU' and the bias sums as streaming kernels.  Returns d x (bf16 [N, D]) when want_x.
+    dy_step(y, gamma, vec, coef, alpha, dy, r1, eps=, colsum=) is the one launch that knows where a token's window lies: _single_item_dy for
+    one item's grid, the ragged call over the stacked tokens of a mixed batch (ragged_train.py); everything behind it is per token."""
     h1, abf, y = rec
     N, D = x2.shape
     dev = x2.device
@@ -208,8 +223,7 @@ def _adaptor_mlp_backward(x2, mlp, norm, alpha, rec, coef, vec, vec_stride, axes
     dy = torch.empty((N, y.shape[1]), dtype=torch.bfloat16, device=dev)
     r1 = torch.empty((N, D), dtype=torch.bfloat16, device=dev) if want_x else None
     # (the bias gradients -- column sums of dy and of d h1 -- come out of the launches that write those matrices)
-    grads[f"{prefix}{which}_proj.2.bias"] = nv.adapt_dy(y, norm.weight.detach(), vec, vec_stride, coef, alpha.detach(), axes, dy, r1, eps=norm.eps,
-                                                        colsum=True)
+    grads[f"{prefix}{which}_proj.2.bias"] = dy_step(y, norm.weight.detach(), vec, coef, alpha.detach(), dy, r1, eps=norm.eps, colsum=True)
     grads[f"{prefix}{which}_proj.2.weight"] = nv.dense16_tn(dy, abf)                       # dW2[o, h] = sum_n dy[n, o] a[n, h]
     da = torch.empty((N, h1.shape[1]), dtype=torch.bfloat16, device=dev)
     nv.dense16_gemm(dy, mlp[2].weight.detach().t().contiguous(), None, y=da)                # da[n, h] = sum_o dy[n, o] W2[o, h]
@@ -675,10 +689,10 @@ def _window_queries(st, lc, mode, guide_q, grid):
     return q, pooled
 
 
-def _plain_stream_grad(y, norm, vec, vec_stride, coef, axes):
-    """d x_n = coef_n vec[w(n)] of a PLAIN stream beside an adapted one (its y, norm): the rank-1 branch of hicom_adapt_dy_fwd (alpha = 0)."""
+def _plain_stream_grad(y, norm, vec, coef, dy_step):
+    """d x_n = coef_n vec[w(n)] of a PLAIN stream beside an adapted one (its y, norm): the rank-1 branch of the dy step (alpha = 0)."""
     dx, junk = torch.empty(y.shape, dtype=torch.bfloat16, device=y.device), torch.empty(y.shape, dtype=torch.bfloat16, device=y.device)
-    nv.adapt_dy(y, norm.weight.detach(), vec, vec_stride, coef, torch.zeros(1, dtype=torch.float32, device=y.device), axes, junk, dx, eps=norm.eps)
+    dy_step(y, norm.weight.detach(), vec, coef, torch.zeros(1, dtype=torch.float32, device=y.device), junk, dx, eps=norm.eps)
     return dx
 
 
@@ -700,32 +714,46 @@ def _window_backward_adapt(st, lc, axes, exact, q, scale, dctx_l, rec_k, rec_v):
     nv.local_attn_adapt_bwd(key, rec_k[2] if rec_k else None, lc.k_norm if rec_k else None, lc.k_alpha.detach() if rec_k else None,
                             ff, rec_v[2] if rec_v else None, lc.v_norm if rec_v else None, lc.v_alpha.detach() if rec_v else None,
                             axes, qc, q_stride, scale, 0.0, dctx_l, ds, pw, sxk, syk, sxv, syv, eps=(lc.k_norm if rec_k else lc.v_norm).eps)
-    L = "local_compressor."
     qf = qc.float().reshape(1 if shared_q else nw, E)
-    d_kx = d_vx = None
     # the key stream's input gradient: for d frames_embed, or -- without frames_embed the keys are frames_feature rows (reference :532) -- d frames_feature
     want_kx = (st.want_fe and fe is not None) or (st.ff_grad is not None and fe is None)
     if st.ff_grad is not None and not exact:
         raise NotImplementedError("hicom_amd backward: d frames_feature needs an exact window partition")
+    return _adaptor_streams_backward(lc, f32, grads, kx2, vx2, rec_k, rec_v, qf, qc, dctx_l, (ds, pw, sxk, syk, sxv, syv), want_kx,
+                                     st.ff_grad is not None, _single_item_dy(q_stride, axes), _single_item_dy(E, axes))
+
+
+def _adaptor_streams_backward(lc, f32, grads, kx2, vx2, rec_k, rec_v, qf, qvec, dctx_l, sums, want_kx, want_vx, dy_k, dy_v, want_dq=True):
+    """What follows the window backward through the blends, whoever launched it (one item: _window_backward_adapt; a mixed batch:
+    ragged_train.py): d alpha, d norm.weight, d norm.bias of both adaptors as reductions over the windows, then the adaptor MLPs' backward over
+    all tokens.  kx2 / vx2 [N, E] the streams' inputs, rec_* = (h1, bf16 GELU(h1) or None, y) of an adapted stream; qf fp32 [Nw | 1, E]: the
+    query row of every window; qvec / dctx_l: the rank-1 vectors as the dy steps dy_k / dy_v index them; sums = (ds, pw, sxk, syk, sxv, syv)
+    of the window backward (sxk may be None when neither the k adaptor nor want_dq reads it, sxv without a v adaptor).  Fills `grads`,
+    returns (dq_w or None, d_kx, d_vx)."""
+    ds, pw, sxk, syk, sxv, syv = sums
+    L = "local_compressor."
+    E, dev = dctx_l.shape[1], dctx_l.device
+    d_kx = d_vx = dq_w = None
     if lc.adapt_k:
         ak, gk = lc.k_alpha.detach().float(), f32[L + "k_norm.weight"]
-        dq_w = (1.0 - ak) * sxk + ak * gk * syk
+        if want_dq:
+            dq_w = (1.0 - ak) * sxk + ak * gk * syk
         grads[L + "k_alpha"] = (qf * (gk * syk - sxk)).sum().reshape(1)
         grads[L + "k_norm.weight"] = ak * (qf * syk).sum(0)
         grads[L + "k_norm.bias"] = torch.zeros(E, dtype=torch.float32, device=dev)    # a k sum_w q_w sum_n dS_n: the dS of a window sum to zero
-        d_kx = _adaptor_mlp_backward(kx2, lc.k_proj, lc.k_norm, lc.k_alpha, rec_k, ds, qc, q_stride, axes, L, "k", grads, want_kx)
+        d_kx = _adaptor_mlp_backward(kx2, lc.k_proj, lc.k_norm, lc.k_alpha, rec_k, ds, qvec, dy_k, L, "k", grads, want_kx)
     else:
         dq_w = sxk
         if want_kx:                                                        # plain key stream beside a value adaptor: d key_n = ds_n q_w
-            d_kx = _plain_stream_grad(rec_v[2], lc.v_norm, qc, q_stride, ds, axes)
+            d_kx = _plain_stream_grad(rec_v[2], lc.v_norm, qvec, ds, dy_k)
     if lc.adapt_v:
         av, gv, bvv = lc.v_alpha.detach().float(), f32[L + "v_norm.weight"], f32[L + "v_norm.bias"]
         grads[L + "v_alpha"] = (dctx_l * (gv * syv + bvv - sxv)).sum().reshape(1)
         grads[L + "v_norm.weight"] = av * (dctx_l * syv).sum(0)
         grads[L + "v_norm.bias"] = av * dctx_l.sum(0)
-        d_vx = _adaptor_mlp_backward(vx2, lc.v_proj, lc.v_norm, lc.v_alpha, rec_v, pw, dctx_l, E, axes, L, "v", grads, st.ff_grad is not None)
-    elif st.ff_grad is not None:                                           # plain value stream beside a key adaptor: d value_n = p_n dctx_w
-        d_vx = _plain_stream_grad(rec_k[2], lc.k_norm, dctx_l, E, pw, axes)
+        d_vx = _adaptor_mlp_backward(vx2, lc.v_proj, lc.v_norm, lc.v_alpha, rec_v, pw, dctx_l, dy_v, L, "v", grads, want_vx)
+    elif want_vx:                                                          # plain value stream beside a key adaptor: d value_n = p_n dctx_w
+        d_vx = _plain_stream_grad(rec_k[2], lc.k_norm, dctx_l, pw, dy_v)
     return dq_w, d_kx, d_vx
 
 

@@ -310,98 +310,21 @@ struct LocalAdaptBwdParams {
     float* sxk; float* syk; float* sxv; float* syv;     // [Nw, D] (syk / syv NULL when that stream has no adaptor)
 };
 
+// the body is window_rows.hpp's local_window_adapt_bwd, shared with the ragged training step (ragged.hip: ragged_local_attn_adapt_bwd_kernel)
 template <int NV>
 __global__ __launch_bounds__(256) void local_attn_adapt_bwd_kernel(LocalAdaptBwdParams p) {
     constexpr int D = NV * 384;
     extern __shared__ __attribute__((aligned(16))) float lsm[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int win = blockIdx.x;
     const WindowGeom w(p.at, p.ay, p.ax, win);
-    const int WIN = w.WIN, WP = (WIN + 3) & ~3;
-    float* sc = lsm;                               // [WIN] scores, then ds
-    float* dp = lsm + WP;                          // [WIN] dP, then p
-    float* stk = lsm + 2 * WP;                     // [2][WIN] mu, rstd of y_k
-    float* stv = lsm + 4 * WP;                     // [2][WIN] mu, rstd of y_v
-    float* part = lsm + 6 * WP;                    // [4][D]
     const float ak = p.ky ? read_alpha(p.kalpha, p.alpha_f32) : 0.f, av = p.vy ? read_alpha(p.valpha, p.alpha_f32) : 0.f;
-
-    float q[NV][6], g[NV][6];
+    float q[NV][6];
     load_query<NV>(p.query, p.query_f32, p.query_stride, win, lane, q);
-    load_row_f32<NV>(p.dctx + (long)win * D, lane, g);
-    // q gamma_k, sum(q gamma_k), q . beta_k  and  g gamma_v, sum(g gamma_v), g . beta_v
-    float qg[NV][6], gg[NV][6];
-    float cgk = 0.f, cbk = 0.f, cgv = 0.f, cbv = 0.f;
-    if (p.ky) affine_prep<NV>(q, p.kgamma, p.kbeta, lane, qg, cgk, cbk);
-    if (p.vy) affine_prep<NV>(g, p.vgamma, p.vbeta, lane, gg, cgv, cbv);
-
-    // ---- phase 1: scores, dP, LayerNorm statistics (one token per wave in flight: four rows) -----------------------------------
-    for (int i = wave; i < WIN; i += 4) {
-        const long tok = w.token_of(i);
-        float kx[NV][6], ky[NV][6], vx[NV][6], vy[NV][6];
-        load_row<NV>(p.kx + tok * D, lane, kx);
-        if (p.ky) load_row_f16<NV>(p.ky + tok * D, lane, ky);
-        load_row<NV>(p.vx + tok * D, lane, vx);
-        if (p.vy) load_row_f16<NV>(p.vy + tok * D, lane, vy);
-        float muk = 0.f, rsk = 0.f, muv = 0.f, rsv = 0.f;
-        const float logit = blend_dot<NV>(kx, ky, p.ky != nullptr, q, qg, cgk, cbk, ak, p.eps, muk, rsk);
-        const float dpi = blend_dot<NV>(vx, vy, p.vy != nullptr, g, gg, cgv, cbv, av, p.eps, muv, rsv);
-        if (lane == 0) {
-            sc[i] = logit * p.scale + p.bias;
-            dp[i] = dpi;
-            stk[i] = muk; stk[WP + i] = rsk;
-            stv[i] = muv; stv[WP + i] = rsv;
-        }
-    }
-    __syncthreads();
-    float mx, inv_sum, delta;
-    softmax_stats(sc, WIN, lane, mx, inv_sum, dp, &delta);
-    __syncthreads();                               // every wave has read sc / dp as scores / dP
-    if (wave == 0)
-        for (int i = lane; i < WIN; i += 64) {
-            const float pi = expf(sc[i] - mx) * inv_sum;
-            const float dsi = pi * (dp[i] - delta) * p.scale;
-            sc[i] = dsi;
-            dp[i] = pi;
-            const long tok = w.token_of(i);
-            p.ds[tok] = dsi;
-            p.pw[tok] = pi;
-        }
-    __syncthreads();
-    // ---- phase 2: the four weighted sums over the window ------------------------------------------------------------------------
-    float axk[NV][6], ayk[NV][6], axv[NV][6], ayv[NV][6];
-    row_zero<NV>(axk);
-    row_zero<NV>(ayk);
-    row_zero<NV>(axv);
-    row_zero<NV>(ayv);
-    for (int i = wave; i < WIN; i += 4) {
-        const long tok = w.token_of(i);
-        float kx[NV][6], ky[NV][6], vx[NV][6], vy[NV][6];
-        load_row<NV>(p.kx + tok * D, lane, kx);
-        if (p.ky) load_row_f16<NV>(p.ky + tok * D, lane, ky);
-        load_row<NV>(p.vx + tok * D, lane, vx);
-        if (p.vy) load_row_f16<NV>(p.vy + tok * D, lane, vy);
-        const float dsi = sc[i], pi = dp[i];
-        const float muk = stk[i], wk = dsi * stk[WP + i], muv = stv[i], wv = pi * stv[WP + i];
-        row_axpy<NV>(dsi, kx, axk);
-        row_axpy<NV>(pi, vx, axv);
-#pragma unroll
-        for (int s = 0; s < NV; ++s)
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                if (p.ky) ayk[s][j] = fmaf(wk, ky[s][j] - muk, ayk[s][j]);
-                if (p.vy) ayv[s][j] = fmaf(wv, vy[s][j] - muv, ayv[s][j]);
-            }
-    }
-    auto reduce_out = [&](const float (&a)[NV][6], float* dst) {
-        __syncthreads();
-        store_partial_row<NV>(part, wave, lane, a);
-        __syncthreads();
-        sum_partial_rows<NV>(part, tid, dst + (long)win * D);
-    };
-    reduce_out(axk, p.sxk);
-    reduce_out(axv, p.sxv);
-    if (p.ky) reduce_out(ayk, p.syk);
-    if (p.vy) reduce_out(ayv, p.syv);
+    const WindowAdaptBwdArgs a{p.kx, p.ky, p.kgamma, p.kbeta, ak, p.vx, p.vy, p.vgamma, p.vbeta, av, p.eps, p.scale, p.bias, p.dctx + (long)win * D,
+                               p.ds, p.pw, p.sxk + (long)win * D, p.syk ? p.syk + (long)win * D : nullptr, p.sxv + (long)win * D,
+                               p.syv ? p.syv + (long)win * D : nullptr};
+    local_window_adapt_bwd<NV>(a, w, q, lsm, tid);
 }
 
 // ---- d y of one adaptor stream: backward of the LayerNorm blend for a rank-1 upstream gradient ---------------------------------------
@@ -431,37 +354,12 @@ __global__ __launch_bounds__(256) void adapt_dy_kernel(AdaptDyParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float csum[NV][6];
     row_zero<NV>(csum);
-    for (long tok = (long)blockIdx.x * 4 + wave; tok < p.N; tok += (long)gridDim.x * 4) {
+    for (long tok = (long)blockIdx.x * 4 + wave; tok < p.N; tok += (long)gridDim.x * 4) {      // (the token's body: window_rows.hpp, adapt_dy_token)
         const long win = WindowGeom::window_of(p.at, p.ay, p.ax, tok);
-        const float alpha = read_alpha(p.alpha, p.alpha_f32);
-        const float c = p.coef[tok];
-        float y[NV][6], v[NV][6], vg[NV][6];
-        load_row_f16<NV>(p.y + tok * D, lane, y);
-        if (p.vec_f32) load_row_f32<NV>(reinterpret_cast<const float*>(p.vec) + win * p.vec_stride, lane, v);
-        else load_row<NV>(reinterpret_cast<const uint16_t*>(p.vec) + win * p.vec_stride, lane, v);
-        load_row<NV>(p.gamma, lane, vg);
-        float mu, rstd;
-        ln_stats<NV>(y, p.eps, mu, rstd);
-#pragma unroll
-        for (int s = 0; s < NV; ++s)
-#pragma unroll
-            for (int j = 0; j < 6; ++j) y[s][j] = (y[s][j] - mu) * rstd;      // yhat
-        row_mul<NV>(v, vg, vg);                                               // (vec gamma)
-        const float m1 = wave_sum_fast(row_sum<NV>(vg)) * (1.0f / D);
-        const float m2 = wave_sum_fast(row_dot<NV>(vg, y)) * (1.0f / D);
-        const float k = alpha * c * rstd;
-        uint16_t* o = p.dy + tok * D;
-#pragma unroll
-        for (int s = 0; s < NV; ++s) {
-            float r[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) r[j] = k * (vg[s][j] - m1 - y[s][j] * m2);
-            seg12_accum(csum[s], store_seg12(o + 384 * s + 6 * lane, r));
-        }
-        if (p.r1) {
-            const float k1 = (1.0f - alpha) * c;
-            store_row_bf16<NV>(p.r1 + tok * D, lane, false, [&](int s, int j) { return k1 * v[s][j]; });
-        }
+        const void* vec = p.vec_f32 ? (const void*)(reinterpret_cast<const float*>(p.vec) + win * p.vec_stride)
+                                    : (const void*)(reinterpret_cast<const uint16_t*>(p.vec) + win * p.vec_stride);
+        adapt_dy_token<NV>(p.y + tok * D, p.gamma, vec, p.vec_f32, p.coef[tok], read_alpha(p.alpha, p.alpha_f32), p.eps, p.dy + tok * D,
+                           p.r1 ? p.r1 + tok * D : nullptr, lane, csum);
     }
     if (p.col_parts) {
         __shared__ float red[4 * D];

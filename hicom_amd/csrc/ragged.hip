@@ -22,6 +22,9 @@
 // Input gradients (stage 3): hicom_compressor_ragged_local_bwd is the window backward over the concatenated window list (window_rows.hpp:
 // local_window_bwd, the body of local_attn_bwd_kernel) with dq summed per item in a fixed order, hicom_compressor_ragged_global_dx the global
 // stage's d x with an item per workgroup (global_dx.hpp: global_dx_tile, the body of global_dx_kernel).
+// The adaptor recipe's training step: hicom_compressor_ragged_local_adapt_bwd (window_rows.hpp: local_window_adapt_bwd, the body of
+// local_attn_adapt_bwd_kernel), hicom_compressor_ragged_adapt_dy (adapt_dy_token, the body of adapt_dy_kernel; the token's item by a search
+// of the item table), hicom_compressor_ragged_dq_item and hicom_compressor_ragged_adapt_train_state (the y planes out of the workspace).
 #include <vector>
 
 #include "global_dx.hpp"
@@ -234,6 +237,98 @@ __global__ __launch_bounds__(256) void ragged_dq_item_kernel(const float* dq, co
         __syncthreads();
     }
     if (stripe == 0 && c < E) *reinterpret_cast<float4*>(dq_item + (long)item * E + c) = red[0][lane];
+}
+
+// ---- training, the adaptor recipe: the window backward through the LayerNorm blends over the concatenated window list, one 4-wave
+// workgroup per window (the body of local_attn_adapt_bwd_kernel: window_rows.hpp, local_window_adapt_bwd).  Item, window geometry, token
+// offset and query as in ragged_local_attn_bwd_kernel; the y rows of an item start at its first token like its x rows.  ds / pw f32
+// [sum N_i], the four sums f32 [sum windows][D] or NULL; plain stores ----
+struct RaggedLocalAdaptBwdParams {
+    const uint16_t* kx; const _Float16* ky; const uint16_t* kgamma; const uint16_t* kbeta; const void* kalpha;
+    const uint16_t* vx; const _Float16* vy; const uint16_t* vgamma; const uint16_t* vbeta; const void* valpha;
+    int alpha_f32;
+    float eps;
+    const uint16_t* guide;  // [B][D]
+    const RaggedItem* items;
+    const int* win_item;
+    hicom_axis ay, ax;
+    float scale;
+    const float* dctx;      // [sum windows][D]
+    float* ds;              // [sum N_i]
+    float* pw;              // [sum N_i]
+    float* sxk; float* syk; float* sxv; float* syv;
+};
+
+template <int NV>
+__global__ __launch_bounds__(256) void ragged_local_attn_adapt_bwd_kernel(RaggedLocalAdaptBwdParams p) {
+    constexpr int D = NV * 384;
+    extern __shared__ __attribute__((aligned(16))) float lsm[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int win = blockIdx.x;
+    const int item = p.win_item[win];
+    const RaggedItem it = p.items[item];
+    const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+    const WindowGeom w(at, p.ay, p.ax, win - it.win0);
+    const long first = (long)it.tok0 * D, row = (long)win * D;
+    const float ak = p.ky ? read_alpha(p.kalpha, p.alpha_f32) : 0.f, av = p.vy ? read_alpha(p.valpha, p.alpha_f32) : 0.f;
+    float q[NV][6];
+    load_row<NV>(p.guide + (long)item * D, lane, q);
+    const WindowAdaptBwdArgs a{p.kx + first, p.ky ? p.ky + first : nullptr, p.kgamma, p.kbeta, ak, p.vx + first, p.vy ? p.vy + first : nullptr,
+                               p.vgamma, p.vbeta, av, p.eps, p.scale, 0.f, p.dctx + row, p.ds + it.tok0, p.pw + it.tok0,
+                               p.sxk ? p.sxk + row : nullptr, p.syk ? p.syk + row : nullptr, p.sxv ? p.sxv + row : nullptr,
+                               p.syv ? p.syv + row : nullptr};
+    local_window_adapt_bwd<NV>(a, w, q, lsm, tid);
+}
+
+// ... and d y of an adaptor stream over the stacked tokens, adapt_dy_kernel with the item looked up (the token's body: window_rows.hpp,
+// adapt_dy_token).  One wave per token in flight; the wave finds its item by a binary search of tok0 in the item table (B entries, no table
+// of token size), the window from the item's own (T, kt) plus win0.  The rank-1 vector: one row per item (K stream: the guide) or per
+// window (V stream: dctx).  col_parts as adapt_dy_kernel: this workgroup's column sums of dy ----
+struct RaggedAdaptDyParams {
+    const _Float16* y;      // [sum N_i][D]
+    const uint16_t* gamma;
+    const void* vec;        // f32 | bf16 [B | sum windows][D]
+    int vec_f32, vec_per_item;
+    const float* coef;      // [sum N_i]
+    const void* alpha; int alpha_f32;
+    float eps;
+    const RaggedItem* items;
+    int B;
+    hicom_axis ay, ax;
+    uint16_t* dy;           // bf16 [sum N_i][D]
+    uint16_t* r1;           // bf16 [sum N_i][D] or NULL
+    long N;                 // sum N_i
+    float* col_parts;       // f32 [gridDim.x][D] or NULL
+};
+
+template <int NV>
+__global__ __launch_bounds__(256) void ragged_adapt_dy_kernel(RaggedAdaptDyParams p) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float csum[NV][6];
+    row_zero<NV>(csum);
+    for (long tok = (long)blockIdx.x * 4 + wave; tok < p.N; tok += (long)gridDim.x * 4) {
+        int lo = 0, hi = p.B;                      // the last item whose first token is <= tok (tok0 rises strictly, items[0].tok0 == 0)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (p.items[mid].tok0 <= tok) lo = mid;
+            else hi = mid;
+        }
+        const RaggedItem it = p.items[lo];
+        const hicom_axis at{it.T, it.kt, it.T / it.kt, it.T / it.kt};
+        const long win = it.win0 + WindowGeom::window_of(at, p.ay, p.ax, tok - it.tok0);
+        const long vrow = (p.vec_per_item ? (long)lo : win) * D;
+        const void* vec = p.vec_f32 ? (const void*)(reinterpret_cast<const float*>(p.vec) + vrow)
+                                    : (const void*)(reinterpret_cast<const uint16_t*>(p.vec) + vrow);
+        adapt_dy_token<NV>(p.y + tok * D, p.gamma, vec, p.vec_f32, p.coef[tok], read_alpha(p.alpha, p.alpha_f32), p.eps, p.dy + tok * D,
+                           p.r1 ? p.r1 + tok * D : nullptr, lane, csum);
+    }
+    if (p.col_parts) {
+        __shared__ float red[4 * D];
+        store_partial_row<NV>(red, wave, lane, csum);
+        __syncthreads();
+        sum_partial_rows<NV>(red, threadIdx.x, p.col_parts + (long)blockIdx.x * D);
+    }
 }
 
 // ---- training, input gradients: d x of the global stage, global_dx_kernel<9> with an item per workgroup (global_dx.hpp: the one body).
@@ -612,7 +707,140 @@ int ragged_global_dx(const hicom_compressor_ragged_args* a, const float* scores,
     return seg_check_launch(who, "global dx");
 }
 
+// ---- training, the adaptor recipe (hicom_amd/ragged_train.py, adaptors=True) ------------------------------------------------------------------
+// What the three calls check alike behind their own pointer checks, in front of everything that needs a device: the per-item partition
+// (ragged_check) and tokens * E < 2^32 (the operands of the adaptor GEMMs that take these matrices).  Leaves the token total.
+int ragged_adapt_bwd_check(const char* who, const hicom_compressor_ragged_args* a, long& tokens) {
+    tokens = 0;
+    for (int i = 0; i < a->B; ++i) tokens += (long)a->items[i].T * a->H * a->W;
+    HICOM_REQUIRE(tokens * a->E < (1L << 32), HICOM_EUNSUP, "%s: %ld tokens: the adaptor GEMMs take operands below 2^32 elements", who, tokens);
+    return HICOM_OK;
+}
+
+int ragged_local_adapt_bwd(const hicom_compressor_ragged_args* a, const void* key_x, const void* key_y, const void* k_gamma, const void* k_beta,
+                           const void* k_alpha, const void* value_x, const void* value_y, const void* v_gamma, const void* v_beta, const void* v_alpha,
+                           int alpha_dt, float eps, const void* guide, const float* dctx, float* ds, float* pw, float* sxk, float* syk, float* sxv,
+                           float* syv) {
+    constexpr const char* who = "compressor_ragged_local_adapt_bwd";
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(key_x && value_x && guide && dctx && ds && pw && (key_y || value_y), HICOM_EINVAL, "%s: NULL pointer / no adapted stream", who);
+    HICOM_REQUIRE((!key_y || (k_gamma && k_beta && k_alpha)) && (!value_y || (v_gamma && v_beta && v_alpha)), HICOM_EINVAL, "%s: adaptor parameters", who);
+    HICOM_REQUIRE((key_y || !syk) && (value_y || !syv), HICOM_EINVAL, "%s: syk / syv are the sums of an ADAPTED stream (NULL without its y)", who);
+    HICOM_REQUIRE(alpha_dt == HICOM_DT_BF16 || alpha_dt == HICOM_DT_F32, HICOM_EINVAL, "%s: alpha dtype %d (bf16 | f32)", who, alpha_dt);
+    for (const void* q : {key_x, key_y, k_gamma, k_beta, value_x, value_y, v_gamma, v_beta, guide, (const void*)ds, (const void*)pw})
+        HICOM_REQUIRE((uintptr_t)q % 4 == 0, HICOM_EINVAL, "%s: 4-byte aligned rows", who);
+    for (const void* q : {(const void*)dctx, (const void*)sxk, (const void*)syk, (const void*)sxv, (const void*)syv})
+        HICOM_REQUIRE((uintptr_t)q % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned f32 matrices", who);
+    long tokens;
+    st = ragged_adapt_bwd_check(who, a, tokens);
+    if (st != HICOM_OK) return st;
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(who, a, l.s.total);                     // (the table region at its head is what is read)
+    if (st != HICOM_OK) return st;
+    int max_kt = 1;
+    for (int i = 0; i < a->B; ++i) max_kt = a->items[i].kt > max_kt ? a->items[i].kt : max_kt;
+    const long WIN = (long)max_kt * a->ks * a->ks;             // (<= 64: seg_check_ragged_items)
+    const size_t smem = 6 * (((size_t)WIN + 3) & ~(size_t)3) * 4 + 4 * (size_t)a->E * 4;
+    const char* tab = (const char*)a->ws;
+    RaggedLocalAdaptBwdParams p;
+    p.kx = (const uint16_t*)key_x; p.ky = (const _Float16*)key_y; p.kgamma = (const uint16_t*)k_gamma; p.kbeta = (const uint16_t*)k_beta; p.kalpha = k_alpha;
+    p.vx = (const uint16_t*)value_x; p.vy = (const _Float16*)value_y; p.vgamma = (const uint16_t*)v_gamma; p.vbeta = (const uint16_t*)v_beta; p.valpha = v_alpha;
+    p.alpha_f32 = alpha_dt == HICOM_DT_F32; p.eps = eps; p.guide = (const uint16_t*)guide;
+    p.items = (const RaggedItem*)(tab + l.items); p.win_item = (const int*)(tab + l.win_item);
+    p.ay = hicom_axis{a->H, a->ks, a->H / a->ks, a->H / a->ks}; p.ax = hicom_axis{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+    p.scale = a->l_scale; p.dctx = dctx; p.ds = ds; p.pw = pw; p.sxk = sxk; p.syk = syk; p.sxv = sxv; p.syv = syv;
+    HICOM_LAUNCH(ragged_local_attn_adapt_bwd_kernel<3>, dim3((unsigned)l.s.n.windows), dim3(256), smem, (hipStream_t)a->stream, p);      // (E == 1152: ragged_check)
+    return seg_check_launch(who, "window backward");
+}
+
+int ragged_adapt_dy(const hicom_compressor_ragged_args* a, const void* y, const void* gamma, const void* vec, int vec_dt, int vec_per_item, const float* coef,
+                    const void* alpha, int alpha_dt, float eps, void* dy, void* r1, float* col_parts, int nparts) {
+    constexpr const char* who = "compressor_ragged_adapt_dy";
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(y && gamma && vec && coef && alpha && dy && (!col_parts || nparts > 0), HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE((vec_dt == HICOM_DT_BF16 || vec_dt == HICOM_DT_F32) && (alpha_dt == HICOM_DT_BF16 || alpha_dt == HICOM_DT_F32), HICOM_EINVAL, "%s: dtypes", who);
+    HICOM_REQUIRE((uintptr_t)y % 4 == 0 && (uintptr_t)gamma % 4 == 0 && (uintptr_t)vec % 4 == 0 && (uintptr_t)coef % 4 == 0 && (uintptr_t)dy % 4 == 0 &&
+                      (uintptr_t)r1 % 4 == 0 && (uintptr_t)col_parts % 4 == 0, HICOM_EINVAL, "%s: 4-byte aligned rows", who);
+    long tokens;
+    st = ragged_adapt_bwd_check(who, a, tokens);
+    if (st != HICOM_OK) return st;
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(who, a, l.s.total);                     // (the table region at its head is what is read)
+    if (st != HICOM_OK) return st;
+    RaggedAdaptDyParams p;
+    p.y = (const _Float16*)y; p.gamma = (const uint16_t*)gamma; p.vec = vec; p.vec_f32 = vec_dt == HICOM_DT_F32; p.vec_per_item = vec_per_item ? 1 : 0;
+    p.coef = coef; p.alpha = alpha; p.alpha_f32 = alpha_dt == HICOM_DT_F32; p.eps = eps;
+    p.items = (const RaggedItem*)((const char*)a->ws + l.items); p.B = a->B;
+    p.ay = hicom_axis{a->H, a->ks, a->H / a->ks, a->H / a->ks}; p.ax = hicom_axis{a->W, a->ks, a->W / a->ks, a->W / a->ks};
+    p.dy = (uint16_t*)dy; p.r1 = (uint16_t*)r1; p.N = tokens; p.col_parts = col_parts;
+    // with column partials: `nparts` workgroups walk the tokens (each leaves one partial row); without: one token per wave
+    const unsigned grid = col_parts ? (unsigned)nparts : (unsigned)((tokens + 3) / 4);
+    HICOM_LAUNCH(ragged_adapt_dy_kernel<3>, dim3(grid), dim3(256), 0, (hipStream_t)a->stream, p);      // (E == 1152: ragged_check)
+    return seg_check_launch(who, "adapt dy");
+}
+
+int ragged_dq_item(const hicom_compressor_ragged_args* a, const float* dq, float* dq_item) {
+    constexpr const char* who = "compressor_ragged_dq_item";
+    int st = ragged_check(a, nullptr);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(dq && dq_item, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE((uintptr_t)dq % 16 == 0 && (uintptr_t)dq_item % 16 == 0, HICOM_EINVAL, "%s: 16-byte aligned pointers", who);
+    long tokens;
+    st = ragged_adapt_bwd_check(who, a, tokens);
+    if (st != HICOM_OK) return st;
+    const RaggedLayout l = ragged_layout(a, nullptr);
+    st = seg_check_ws(who, a, l.s.total);                     // (the table region at its head is what is read)
+    if (st != HICOM_OK) return st;
+    HICOM_LAUNCH(ragged_dq_item_kernel, dim3((unsigned)((a->E + 63) / 64), (unsigned)a->B), dim3(256), 0, (hipStream_t)a->stream, dq,
+                 (const RaggedItem*)((const char*)a->ws + l.items), l.wps, a->E, dq_item);
+    return seg_check_launch(who, "dq per item");
+}
+
+// the y planes of the adapted streams out of the adaptor regions of the workspace (hicom_compressor_ragged_adapt_fwd left them there)
+int ragged_adapt_train_state(const hicom_compressor_ragged_args* a, const SegAdapt* ad, void* ky_out, void* vy_out) {
+    constexpr const char* who = "compressor_ragged_adapt_train_state";
+    int st = ragged_check(a, ad);
+    if (st != HICOM_OK) return st;
+    HICOM_REQUIRE(ky_out || vy_out, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE((!ky_out || ad->k()) && (!vy_out || ad->v()), HICOM_EINVAL, "%s: a y plane of a stream without adaptor", who);
+    const RaggedLayout l = ragged_layout(a, ad);
+    st = seg_check_ws(who, a, l.s.total);
+    if (st != HICOM_OK) return st;
+    const char* ws = (const char*)a->ws;
+    hipStream_t s = (hipStream_t)a->stream;
+    const size_t bytes = (size_t)(l.s.n.tokens * a->E * 2);
+    if ((ky_out && hipMemcpyAsync(ky_out, ws + l.s.ad.ky, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+        (vy_out && hipMemcpyAsync(vy_out, ws + l.s.ad.vy, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)) {
+        set_error("%s: copying the state: %s", who, hipGetErrorString(hipGetLastError()));
+        return HICOM_ELAUNCH;
+    }
+    return HICOM_OK;
+}
+
 }  // namespace
+
+extern "C" int hicom_compressor_ragged_local_adapt_bwd(const hicom_compressor_ragged_args* a, const void* key_x, const void* key_y, const void* k_gamma,
+                                                       const void* k_beta, const void* k_alpha, const void* value_x, const void* value_y, const void* v_gamma,
+                                                       const void* v_beta, const void* v_alpha, int32_t alpha_dt, float eps, const void* guide, const float* dctx,
+                                                       float* ds, float* pw, float* sxk, float* syk, float* sxv, float* syv) {
+    return ragged_local_adapt_bwd(a, key_x, key_y, k_gamma, k_beta, k_alpha, value_x, value_y, v_gamma, v_beta, v_alpha, alpha_dt, eps, guide, dctx, ds, pw, sxk,
+                                  syk, sxv, syv);
+}
+
+extern "C" int hicom_compressor_ragged_adapt_dy(const hicom_compressor_ragged_args* a, const void* y, const void* gamma, const void* vec, int32_t vec_dt,
+                                                int32_t vec_per_item, const float* coef, const void* alpha, int32_t alpha_dt, float eps, void* dy, void* r1,
+                                                float* col_parts, int32_t nparts) {
+    return ragged_adapt_dy(a, y, gamma, vec, vec_dt, vec_per_item, coef, alpha, alpha_dt, eps, dy, r1, col_parts, nparts);
+}
+
+extern "C" int hicom_compressor_ragged_dq_item(const hicom_compressor_ragged_args* a, const float* dq, float* dq_item) { return ragged_dq_item(a, dq, dq_item); }
+
+extern "C" int hicom_compressor_ragged_adapt_train_state(const hicom_compressor_ragged_adapt_args* a, void* ky_out, void* vy_out) {
+    return seg_with_adapt("compressor_ragged_adapt_train_state", a,
+                          [&](const hicom_compressor_ragged_args* b, const SegAdapt* ad) { return ragged_adapt_train_state(b, ad, ky_out, vy_out); });
+}
 
 extern "C" int hicom_compressor_ragged_local_bwd(const hicom_compressor_ragged_args* a, const void* key, const void* value, const void* guide, const float* dctx,
                                                  float* dq, float* dq_item, void* dkey, void* dvalue, int32_t value_is_key) {

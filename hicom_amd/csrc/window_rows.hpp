@@ -368,4 +368,144 @@ __device__ __forceinline__ void local_window_bwd(const WindowBwdArgs& p, const W
     sum_partial_rows<NV>(part, tid, p.dq);
 }
 
+// ---- backward of one window of the windowed attention WITH the k / v adaptor blends: the one body of local_attn_adapt_bwd_kernel
+// (local_attn.hip has the algebra: the window comes from blockIdx and the call's one grid) and ragged_local_attn_adapt_bwd_kernel
+// (ragged.hip: the window's item comes from a device table, the grid is the item's own).  kx / ky / vx / vy / ds / pw point at the first
+// token of the grid `w` indexes; dctx and the four sums at the window's own row.  A sum whose pointer is NULL is not written (syk / syv
+// of a stream without adaptor: its y pointer is NULL too).  One 4-wave workgroup, lsm: 6 per-token arrays of the window + the [4][D] slab.
+struct WindowAdaptBwdArgs {
+    const uint16_t* kx; const _Float16* ky; const uint16_t* kgamma; const uint16_t* kbeta; float ak;
+    const uint16_t* vx; const _Float16* vy; const uint16_t* vgamma; const uint16_t* vbeta; float av;
+    float eps, scale, bias;
+    const float* dctx;      // [D]
+    float* ds;              // [N] token-indexed
+    float* pw;              // [N]
+    float* sxk; float* syk; float* sxv; float* syv;     // [D] or NULL
+};
+
+template <int NV>
+__device__ __forceinline__ void local_window_adapt_bwd(const WindowAdaptBwdArgs& p, const WindowGeom& w, const float (&q)[NV][6], float* lsm, int tid) {
+    constexpr int D = NV * 384;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int WIN = w.WIN, WP = (WIN + 3) & ~3;
+    float* sc = lsm;                               // [WIN] scores, then ds
+    float* dp = lsm + WP;                          // [WIN] dP, then p
+    float* stk = lsm + 2 * WP;                     // [2][WIN] mu, rstd of y_k
+    float* stv = lsm + 4 * WP;                     // [2][WIN] mu, rstd of y_v
+    float* part = lsm + 6 * WP;                    // [4][D]
+    const float ak = p.ak, av = p.av;
+
+    float g[NV][6];
+    load_row_f32<NV>(p.dctx, lane, g);
+    // q gamma_k, sum(q gamma_k), q . beta_k  and  g gamma_v, sum(g gamma_v), g . beta_v
+    float qg[NV][6], gg[NV][6];
+    float cgk = 0.f, cbk = 0.f, cgv = 0.f, cbv = 0.f;
+    if (p.ky) affine_prep<NV>(q, p.kgamma, p.kbeta, lane, qg, cgk, cbk);
+    if (p.vy) affine_prep<NV>(g, p.vgamma, p.vbeta, lane, gg, cgv, cbv);
+
+    // ---- phase 1: scores, dP, LayerNorm statistics (one token per wave in flight: four rows) -----------------------------------
+    for (int i = wave; i < WIN; i += 4) {
+        const long tok = w.token_of(i);
+        float kx[NV][6], ky[NV][6], vx[NV][6], vy[NV][6];
+        load_row<NV>(p.kx + tok * D, lane, kx);
+        if (p.ky) load_row_f16<NV>(p.ky + tok * D, lane, ky);
+        load_row<NV>(p.vx + tok * D, lane, vx);
+        if (p.vy) load_row_f16<NV>(p.vy + tok * D, lane, vy);
+        float muk = 0.f, rsk = 0.f, muv = 0.f, rsv = 0.f;
+        const float logit = blend_dot<NV>(kx, ky, p.ky != nullptr, q, qg, cgk, cbk, ak, p.eps, muk, rsk);
+        const float dpi = blend_dot<NV>(vx, vy, p.vy != nullptr, g, gg, cgv, cbv, av, p.eps, muv, rsv);
+        if (lane == 0) {
+            sc[i] = logit * p.scale + p.bias;
+            dp[i] = dpi;
+            stk[i] = muk; stk[WP + i] = rsk;
+            stv[i] = muv; stv[WP + i] = rsv;
+        }
+    }
+    __syncthreads();
+    float mx, inv_sum, delta;
+    softmax_stats(sc, WIN, lane, mx, inv_sum, dp, &delta);
+    __syncthreads();                               // every wave has read sc / dp as scores / dP
+    if (wave == 0)
+        for (int i = lane; i < WIN; i += 64) {
+            const float pi = expf(sc[i] - mx) * inv_sum;
+            const float dsi = pi * (dp[i] - delta) * p.scale;
+            sc[i] = dsi;
+            dp[i] = pi;
+            const long tok = w.token_of(i);
+            p.ds[tok] = dsi;
+            p.pw[tok] = pi;
+        }
+    __syncthreads();
+    // ---- phase 2: the four weighted sums over the window ------------------------------------------------------------------------
+    float axk[NV][6], ayk[NV][6], axv[NV][6], ayv[NV][6];
+    row_zero<NV>(axk);
+    row_zero<NV>(ayk);
+    row_zero<NV>(axv);
+    row_zero<NV>(ayv);
+    for (int i = wave; i < WIN; i += 4) {
+        const long tok = w.token_of(i);
+        float kx[NV][6], ky[NV][6], vx[NV][6], vy[NV][6];
+        load_row<NV>(p.kx + tok * D, lane, kx);
+        if (p.ky) load_row_f16<NV>(p.ky + tok * D, lane, ky);
+        load_row<NV>(p.vx + tok * D, lane, vx);
+        if (p.vy) load_row_f16<NV>(p.vy + tok * D, lane, vy);
+        const float dsi = sc[i], pi = dp[i];
+        const float muk = stk[i], wk = dsi * stk[WP + i], muv = stv[i], wv = pi * stv[WP + i];
+        row_axpy<NV>(dsi, kx, axk);
+        row_axpy<NV>(pi, vx, axv);
+#pragma unroll
+        for (int s = 0; s < NV; ++s)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                if (p.ky) ayk[s][j] = fmaf(wk, ky[s][j] - muk, ayk[s][j]);
+                if (p.vy) ayv[s][j] = fmaf(wv, vy[s][j] - muv, ayv[s][j]);
+            }
+    }
+    auto reduce_out = [&](const float (&a)[NV][6], float* dst) {
+        __syncthreads();
+        store_partial_row<NV>(part, wave, lane, a);
+        __syncthreads();
+        sum_partial_rows<NV>(part, tid, dst);
+    };
+    if (p.sxk) reduce_out(axk, p.sxk);             // (the pointers are the same for the whole workgroup: the barriers inside are uniform)
+    if (p.sxv) reduce_out(axv, p.sxv);
+    if (p.ky && p.syk) reduce_out(ayk, p.syk);
+    if (p.vy && p.syv) reduce_out(ayv, p.syv);
+}
+
+// ---- d y of one token of an adaptor stream (local_attn.hip: adapt_dy_kernel has the algebra), the one body of adapt_dy_kernel and
+// ragged_adapt_dy_kernel (ragged.hip): the caller finds the token's rows and the row of the rank-1 vector.  One wave; csum: this lane's
+// column sums of dy as stored (bf16-rounded).
+template <int NV>
+__device__ __forceinline__ void adapt_dy_token(const _Float16* y_row, const uint16_t* gamma, const void* vec_row, int vec_f32, float c, float alpha, float eps,
+                                               uint16_t* dy_row, uint16_t* r1_row, int lane, float (&csum)[NV][6]) {
+    constexpr int D = NV * 384;
+    float y[NV][6], v[NV][6], vg[NV][6];
+    load_row_f16<NV>(y_row, lane, y);
+    if (vec_f32) load_row_f32<NV>(reinterpret_cast<const float*>(vec_row), lane, v);
+    else load_row<NV>(reinterpret_cast<const uint16_t*>(vec_row), lane, v);
+    load_row<NV>(gamma, lane, vg);
+    float mu, rstd;
+    ln_stats<NV>(y, eps, mu, rstd);
+#pragma unroll
+    for (int s = 0; s < NV; ++s)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) y[s][j] = (y[s][j] - mu) * rstd;      // yhat
+    row_mul<NV>(v, vg, vg);                                               // (vec gamma)
+    const float m1 = wave_sum_fast(row_sum<NV>(vg)) * (1.0f / D);
+    const float m2 = wave_sum_fast(row_dot<NV>(vg, y)) * (1.0f / D);
+    const float k = alpha * c * rstd;
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        float r[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) r[j] = k * (vg[s][j] - m1 - y[s][j] * m2);
+        seg12_accum(csum[s], store_seg12(dy_row + 384 * s + 6 * lane, r));
+    }
+    if (r1_row) {
+        const float k1 = (1.0f - alpha) * c;
+        store_row_bf16<NV>(r1_row, lane, false, [&](int s, int j) { return k1 * v[s][j]; });
+    }
+}
+
 }  // namespace hicom

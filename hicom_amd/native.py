@@ -431,6 +431,11 @@ SIGNATURES = {
     "hicom_compressor_ragged_global_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "hicom_compressor_ragged_local_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, vp, vp, i32]),
     "hicom_compressor_ragged_global_dx": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, i32, vp, i32]),
+    "hicom_compressor_ragged_adapt_train_state": (C.c_int, [C.POINTER(CompressorRaggedAdaptArgs), vp, vp]),
+    "hicom_compressor_ragged_local_adapt_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp,
+                                                          vp, vp, vp, vp]),
+    "hicom_compressor_ragged_adapt_dy": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, i32, i32, vp, vp, i32, f32, vp, vp, vp, i32]),
+    "hicom_compressor_ragged_dq_item": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -854,6 +859,47 @@ def compressor_ragged_global_dx(args: CompressorRaggedArgs, scores, ds, ml, qt, 
     assert tiles.dtype == torch.int32 and tiles.is_contiguous() and dx.dtype == torch.bfloat16
     _check(lib().hicom_compressor_ragged_global_dx(C.byref(args), _ptr(scores), _ptr(ds), _ptr(ml), _ptr(qt), _ptr(dctx), _ptr(tiles), tiles.shape[0],
                                                    _ptr(dx), int(bool(accumulate))), "hicom_compressor_ragged_global_dx")
+
+
+def compressor_ragged_adapt_train_state(args: CompressorRaggedAdaptArgs, ky, vy):
+    """The fp16 y planes [tokens, E] of the adapted streams out of an adaptor plan's workspace (hicom_compressor_ragged_adapt_train_state);
+    None for a stream without adaptor."""
+    _check(lib().hicom_compressor_ragged_adapt_train_state(C.byref(args), _ptr(ky), _ptr(vy)), "hicom_compressor_ragged_adapt_train_state")
+
+
+def compressor_ragged_local_adapt_bwd(args: CompressorRaggedArgs, key_x, key_y, k_norm, k_alpha, value_x, value_y, v_norm, v_alpha, guide, dctx, ds, pw,
+                                      sxk=None, syk=None, sxv=None, syv=None, eps=1e-6):
+    """The window backward through the k / v adaptor blends over all items of a ragged plan (hicom_compressor_ragged_local_adapt_bwd);
+    key_y / value_y fp16 [tokens, E] or None, the four sums f32 [windows, E] or None."""
+    alpha = k_alpha if key_y is not None else v_alpha
+
+    def affine(y, norm, al):           # (gamma, beta, alpha) of an adapted stream, three NULLs otherwise
+        return (_ptr(norm.weight.detach()), _ptr(norm.bias.detach()), _ptr(al.detach())) if y is not None else (None, None, None)
+    _check(lib().hicom_compressor_ragged_local_adapt_bwd(C.byref(args), _ptr(key_x), _ptr(key_y), *affine(key_y, k_norm, k_alpha), _ptr(value_x),
+                                                         _ptr(value_y), *affine(value_y, v_norm, v_alpha), _dt(alpha), eps, _ptr(guide), _ptr(dctx),
+                                                         _ptr(ds), _ptr(pw), _ptr(sxk), _ptr(syk), _ptr(sxv), _ptr(syv)),
+           "hicom_compressor_ragged_local_adapt_bwd")
+
+
+def compressor_ragged_adapt_dy(args: CompressorRaggedArgs, y, gamma, vec, vec_per_item, coef, alpha, dy, r1=None, eps=1e-6, colsum=False):
+    """adapt_dy over the stacked tokens of a ragged plan (hicom_compressor_ragged_adapt_dy): vec has one row per item (vec_per_item) or per
+    window.  colsum=True: also returns the column sums of dy (f32 [E]) from partials the same launch leaves."""
+    D = y.shape[-1]
+    parts = _col_parts(dy.shape[0], D, dy.device) if colsum else None
+    _check(lib().hicom_compressor_ragged_adapt_dy(C.byref(args), _ptr(y), _ptr(gamma), _ptr(vec), _dt(vec), int(bool(vec_per_item)), _ptr(coef), _ptr(alpha),
+                                                  _dt(alpha), eps, _ptr(dy), _ptr(r1), _ptr(parts), parts.shape[0] if colsum else 0),
+           "hicom_compressor_ragged_adapt_dy")
+    if not colsum:
+        return None
+    out = torch.empty((D,), dtype=torch.float32, device=dy.device)
+    partials_sum(parts, out)
+    return out
+
+
+def compressor_ragged_dq_item(args: CompressorRaggedArgs, dq, dq_item):
+    """dq_item [B, E] = the rows of dq [windows, E] summed per item of a ragged plan (hicom_compressor_ragged_dq_item)."""
+    assert dq.dtype == dq_item.dtype == torch.float32
+    _check(lib().hicom_compressor_ragged_dq_item(C.byref(args), _ptr(dq), _ptr(dq_item)), "hicom_compressor_ragged_dq_item")
 
 
 def compressor_multiguide_workspace(args) -> int:

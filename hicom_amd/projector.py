@@ -1111,7 +1111,7 @@ class HIComProjector(nn.Module):
         return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
 
     def forward_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None,
-                             input_grads=False):
+                             input_grads=False, adaptors=False):
         """forward_ragged under autograd: the training step of a mixed batch (reference hicom_arch.py:146-180 with the projector trainable,
         train.py:709-713) in one forward call and ONE backward over all items.  Arguments, scope checks, plan cache and return value are
         forward_ragged's (a uniform batch is split_sizes = (T,) * B on the 4-D view), the outputs are bit-equal to it, and they carry a
@@ -1124,10 +1124,15 @@ class HIComProjector(nn.Module):
         `pure_vision_model`, the tower body train too): each of frames_feature, frames_embed and guide_embeds that requires grad gets its
         gradient through autograd, in its own dtype and shape, from two more native calls over all items; an input that
         does not require grad costs nothing, and the parameter gradients are bit-equal to those of the same step with the inputs detached.
-        The default False keeps the three refusals."""
+        The default False keeps the three refusals.
+        `adaptors=True` opens the second release recipe, `local43_adaptkv_global32` (adapt_k, adapt_v or both on the local stage; DESIGN.md
+        §3.23): the forward is forward_ragged's adaptor call (bit-equal outputs), the backward runs the window backward through the LayerNorm
+        blends over all items in one launch and the adaptor MLPs' backward once over the stacked [sum N_i, E] tokens, and composes with
+        input_grads.  The node keeps the adaptors' fp16 outputs (2 E bytes per token and adapted stream).  On a plain module the keyword
+        changes nothing; with the default False the adaptor recipe is refused as before."""
         from . import ragged_train
         return ragged_train.run_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks,
-                                             input_grads)
+                                             input_grads, adaptors)
 
     def forward_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None, local_logits=None):
         """ONE image or clip, Q instructions in one native call: frames_feature / frames_embed bf16 [T, H, W, E] as for forward()

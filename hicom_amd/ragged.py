@@ -122,6 +122,20 @@ def dx_tile_table(t) -> np.ndarray:
     return np.array([(i, n0) for i, N in enumerate(t.N) for n0 in range(0, N, DX_TILE)], dtype=np.int32).reshape(-1, 2)
 
 
+def token_item_window(t, H: int, W: int, ks: int):
+    """(item, window) int64 arrays over all sum N_i stacked tokens, found as ragged_adapt_dy_kernel (csrc/ragged.hip) finds them, from
+    plan_tables' result alone: the item is the last one whose first token is <= the token (a search of tok0, no table of token size), the
+    window WindowGeom::window_of on the item's own (T, kt) axes plus the item's first window."""
+    tok = np.arange(sum(t.N), dtype=np.int64)
+    tok0, win0 = np.asarray(t.tok0, np.int64), np.asarray(t.win0, np.int64)
+    item = np.searchsorted(tok0, tok, side="right") - 1
+    kt = np.asarray([it[1] for it in t.items], np.int64)[item]
+    loc = tok - tok0[item]
+    frame, rem = loc // (H * W), loc % (H * W)
+    win = ((frame // kt) * (H // ks) + (rem // W) // ks) * (W // ks) + (rem % W) // ks
+    return item, win0[item] + win
+
+
 def _scope(proj, ff, fe, guides, split_sizes, modals, nl, what="forward_ragged"):
     """Raises for everything outside the ragged step's scope that does not need the per-item geometry; returns (B, H, W, E,
     split_sizes, modals) with the last two as tuples."""

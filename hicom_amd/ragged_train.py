@@ -24,9 +24,24 @@ frames_embed and guide_embeds that requires grad gets its gradient, from two mor
 d guide_embeds[i] = dq_item[i] + row i of (dqp Wq + dpre): the injected query of the direct recipe is the guide, one row per item.  A stage
 whose parameters are all frozen runs only where an input gradient needs it (d frames_feature and d guide_embeds: both; d frames_embed: local).
 
-Scope: the plain release recipe `local43_global32` (use_guide="direct", no adaptors, no clip-scale, bf16 module and inputs, exact window
-partition per item); gradients of every projector parameter that requires grad and of image_newline.  Everything else raises
-NotImplementedError naming the loop of forward(): nothing is detached silently."""
+The k / v adaptor recipe `local43_adaptkv_global32` (`adaptors=True`): the forward is forward_ragged's adaptor C call; the
+node also keeps the fp16 y planes of the adapted streams (the MLPs' outputs over all sum N_i tokens, the forward's own bits, copied out of
+the workspace by hicom_compressor_ragged_adapt_train_state; the hidden planes are recomputed in the backward, one layer-1 GEMM per stream).
+The local stage of the backward is then
+
+  window backward  hicom_compressor_ragged_local_adapt_bwd over the concatenated window list (ds, pw per token; the four sums per window);
+                   d alpha, d norm.weight, d norm.bias of both adaptors are reductions of those (autograd._adaptor_streams_backward, the
+                   single-item code: the query row of a window is its item's guide, gathered through a cached window -> item index);
+  adaptor MLPs     autograd._adaptor_mlp_backward over the stacked [sum N_i, E] tokens -- the per-token GEMMs do not care where an item
+                   ends, so B chains of small GEMMs are one chain of large ones -- with hicom_compressor_ragged_adapt_dy as its dy step;
+  input gradients  d frames_embed = d_kx, d frames_feature = d_vx (+ d_kx without frames_embed) and then the global share as above,
+                   d guide's local share = hicom_compressor_ragged_dq_item of dq = (1 - a_k) sxk + a_k gamma_k syk.
+
+Frozen adaptors with no input gradient asked for: neither the window call nor the MLP backward runs, and no y plane is kept.
+
+Scope: the two release recipes `local43_global32` and, with adaptors=True, `local43_adaptkv_global32` (use_guide="direct", no other
+adaptors, no clip-scale, bf16 module and inputs, exact window partition per item); gradients of every projector parameter that requires
+grad and of image_newline.  Everything else raises NotImplementedError naming the loop of forward(): nothing is detached silently."""
 from __future__ import annotations
 
 import types
@@ -42,18 +57,19 @@ WHAT = "forward_ragged_train"
 _LOOP = "run the loop of forward() per item instead"
 
 
-def check_scope(proj, ff, fe, guides, input_grads=False):
+def check_scope(proj, ff, fe, guides, input_grads=False, adaptors=False):
     """The refusals of forward_ragged_train that forward_ragged does not make; no device is touched."""
     if isinstance(ff, dict) or isinstance(fe, dict):
         raise NotImplementedError(f"{WHAT}: anyres dict inputs have no ragged training step; {_LOOP}")
     if proj.local_use_clip_scale or proj.global_use_clip_scale:
         raise NotImplementedError(f"{WHAT}: clip-scale is not built for the ragged training step; {_LOOP}")
     recipe = seg.seg_recipe(proj)
-    if recipe == "adaptkv":
-        raise NotImplementedError(f"{WHAT}: the k / v adaptor recipe (local43_adaptkv_global32) is not built for the ragged training step; {_LOOP}")
+    if recipe == "adaptkv" and not adaptors:
+        raise NotImplementedError(f"{WHAT}: the k / v adaptor recipe (local43_adaptkv_global32) trains through the ragged training step with "
+                                  f"adaptors=True only; pass adaptors=True or {_LOOP}")
     if recipe is None:
-        raise NotImplementedError(f"{WHAT} is built for the plain release recipe local43_global32 only (local + global compressor, "
-                                  f"use_guide='direct', no adaptors, no clip scale); {_LOOP}")
+        raise NotImplementedError(f"{WHAT} is built for the release recipes local43_global32 and (adaptors=True) local43_adaptkv_global32 only "
+                                  f"(local + global compressor, use_guide='direct', no adaptors but adapt_k / adapt_v, no clip scale); {_LOOP}")
     for name, t in (("frames_feature", ff), ("frames_embed", fe), ("guide_embeds", guides)):
         if not input_grads and isinstance(t, torch.Tensor) and t.requires_grad:
             raise NotImplementedError(f"{WHAT}: the gradient w.r.t. {name} (stage 3) is not built for the ragged training step without "
@@ -74,6 +90,21 @@ def _device_tiles(plan, dev):
     return plan.train_tiles
 
 
+def _device_win_item(plan, dev):
+    """The window -> item index of the plan (plan_tables' win_item) as a device int64 tensor, made once per plan: the query row of a window
+    is its item's guide."""
+    if plan.train_win_item is None:
+        plan.train_win_item = torch.from_numpy(plan.tables.win_item.astype("int64")).to(dev)
+    return plan.train_win_item
+
+
+_ADAPTOR_PARAMS = tuple(f"local_compressor.{s}_{part}" for s in "kv" for part in ("proj.", "norm.", "alpha"))
+
+
+def _adaptor_wanted(names):
+    return any(n.startswith(_ADAPTOR_PARAMS) for n in names)
+
+
 class _RaggedTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, proj, ff, fe, guides, nl, meta, names, *params):
@@ -81,22 +112,31 @@ class _RaggedTrainFn(torch.autograd.Function):
         with torch.no_grad():
             out, plan, x, g = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
             t, a, dev = plan.tables, plan.io, x.device
-            # frames_embed, by reference, only where the window backward will run (an input gradient is asked for)
-            keys = fe.contiguous() if (fe is not None and any(ctx.needs_input_grad[1:4])) else None
+            # frames_embed, by reference, only where the window backward will run (an input gradient is asked for, or an adaptor trains)
+            lc = proj.local_compressor
+            adapt = lc.adapt_k or lc.adapt_v
+            window = any(ctx.needs_input_grad[1:4]) or (adapt and _adaptor_wanted(n for k, n in enumerate(names) if ctx.needs_input_grad[7 + k]))
+            keys = fe.contiguous() if (fe is not None and window) else None
             R, E = a.B * a.nh, a.E
             f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
             ctx16 = torch.empty((sum(t.windows), E), dtype=torch.float16, device=dev)
             scores, ml, ctxg = f(16 * 16 * sum(t.ntiles)), f(R, 2), f(R, E)
             nv.compressor_ragged_train_state(a, ctx16, scores, ml, ctxg)      # (the workspace belongs to the plan's next call)
+            ky = vy = None
+            if adapt and window:                                   # the y planes of the adapted streams, the forward's own bits
+                N = x.numel() // E
+                ky = torch.empty((N, E), dtype=torch.float16, device=dev) if lc.adapt_k else None
+                vy = torch.empty((N, E), dtype=torch.float16, device=dev) if lc.adapt_v else None
+                nv.compressor_ragged_adapt_train_state(plan.args, ky, vy)
         rows.extend(plan.rows)                                 # (for the caller: how to split the output)
         ctx.proj, ctx.plan, ctx.names = proj, plan, names
         ctx.nl_meta = None if nl is None else nl.dtype
-        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg, keys)
+        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg, keys, ky, vy)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, guides, ctx16, scores, ml, ctxg, keys = ctx.saved_tensors
+        x, guides, ctx16, scores, ml, ctxg, keys, ky, vy = ctx.saved_tensors
         proj, plan, names = ctx.proj, ctx.plan, ctx.names
         need = ctx.needs_input_grad            # (proj, ff, fe, guides, nl, meta, names, *params)
         want = {n for k, n in enumerate(names) if need[7 + k]}
@@ -104,7 +144,7 @@ class _RaggedTrainFn(torch.autograd.Function):
         if any(need[1:4]):
             inputs = types.SimpleNamespace(want_ff=bool(need[1]), want_fe=bool(need[2]), want_guide=bool(need[3]), fe=keys, d_ff=None, d_fe=None, d_guide=None)
         with torch.no_grad():
-            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]), inputs)
+            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]), inputs, adapt=(keys, ky, vy))
         ag.LAST_FP32_GRADS = dict(grads)               # (test hook, as the single-item backward leaves it; here with d image_newline)
         if d_nl is not None:
             ag.LAST_FP32_GRADS["image_newline"] = d_nl
@@ -129,11 +169,36 @@ class _RaggedTrainFn(torch.autograd.Function):
         return (None, d_ff, d_fe, d_g, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
 
 
-def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl, inputs=None):
+def _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, ky, vy, want_kx, want_vx, want_guide):
+    """The local stage behind the readout for the k / v adaptor recipe: the window backward through the blends over all items, the adaptors'
+    reductions and the MLPs' backward over the stacked tokens.  Fills st.grads; returns (dq_w or None, d_kx, d_vx), bf16 [sum N_i, E] each."""
+    a, x, dev = plan.io, st.ff, st.dev
+    E = a.E
+    kx2, vx2 = (fe if fe is not None else x).view(-1, E), x.view(-1, E)
+    N, nw = vx2.shape[0], dctx_l.shape[0]
+    f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+    ds, pw = f(N), f(N)
+    sxk = f(nw, E) if (lc.adapt_k or want_guide) else None
+    syk = f(nw, E) if lc.adapt_k else None
+    sxv, syv = (f(nw, E), f(nw, E)) if lc.adapt_v else (None, None)
+    nv.compressor_ragged_local_adapt_bwd(a, kx2, ky, lc.k_norm, lc.k_alpha, vx2, vy, lc.v_norm, lc.v_alpha, guides, dctx_l, ds, pw, sxk, syk, sxv, syv,
+                                         eps=(lc.k_norm if lc.adapt_k else lc.v_norm).eps)
+    # the hidden planes, recomputed: one layer-1 GEMM per adapted stream, in the forward's arithmetic
+    rec_k = (ag._adaptor_hidden(kx2, lc.k_proj)[0], None, ky) if lc.adapt_k else None
+    rec_v = (ag._adaptor_hidden(vx2, lc.v_proj)[0], None, vy) if lc.adapt_v else None
+    qf = guides.float()[_device_win_item(plan, dev)] if lc.adapt_k else None           # the query row of every window: its item's guide
+    dy_k = lambda y, gamma, vec, coef, alpha, dy, r1, **kw: nv.compressor_ragged_adapt_dy(a, y, gamma, vec, True, coef, alpha, dy, r1, **kw)
+    dy_v = lambda y, gamma, vec, coef, alpha, dy, r1, **kw: nv.compressor_ragged_adapt_dy(a, y, gamma, vec, False, coef, alpha, dy, r1, **kw)
+    return ag._adaptor_streams_backward(lc, st.f32, st.grads, kx2, vx2, rec_k, rec_v, qf, guides, dctx_l, (ds, pw, sxk, syk, sxv, syv), want_kx, want_vx,
+                                        dy_k, dy_v, want_dq=want_guide)
+
+
+def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl, inputs=None, adapt=(None, None, None)):
     """(fp32 gradients {parameter name: tensor} of sum(out * dout) over all items, d image_newline or None).  `want`: the names of the
     parameters whose gradient is asked for; a stage none of whose parameters is wanted does not run unless an input gradient needs it.
     inputs (None: no input gradient is asked for): want_ff / want_fe / want_guide and the contiguous frames_embed (or None) in, d_ff / d_fe
-    (bf16, the inputs' shapes) and d_guide (fp32 [B, E]) out."""
+    (bf16, the inputs' shapes) and d_guide (fp32 [B, E]) out.  adapt: (frames_embed or None, ky, vy) of the adaptor recipe, the y planes the
+    forward kept (None for a stream without adaptor; all None for the plain recipe)."""
     lc, gc = proj.local_compressor, proj.global_compressor
     dev, a = x.device, plan.io
     local_rows, nl_rows, glob_rows = _device_maps(plan, dev)
@@ -144,14 +209,27 @@ def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, 
     want_ff = inputs is not None and inputs.want_ff
     want_fe = inputs is not None and inputs.want_fe and inputs.fe is not None
     want_guide = inputs is not None and inputs.want_guide
-    window = want_ff or want_fe or want_guide                  # (the window backward: every input gradient has a local share)
+    adaptors = lc.adapt_k or lc.adapt_v
+    # the window backward: every input gradient has a local share; with adaptors, also where one of them trains
+    window = want_ff or want_fe or want_guide or (adaptors and _adaptor_wanted(want))
     dq_item = None
     if window or any(n.startswith("local_compressor.") for n in want):
-        assert ag._window_backward_runs(lc, want_fe, want_guide, proj.local_logit, want_ff) == window
+        assert adaptors or ag._window_backward_runs(lc, want_fe, want_guide, proj.local_logit, want_ff) == window
         ctx_l = ctx16.float()
         W0, b0 = f32[L + "0.weight"], f32[L + "0.bias"]
         dpre = ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
-        if window:
+        if window and adaptors:
+            fe, ky, vy = adapt
+            dctx_l = (dpre @ W0).contiguous()
+            dq_w, d_kx, d_vx = _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, ky, vy, want_fe or (want_ff and fe is None), want_ff, want_guide)
+            if want_guide:
+                dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=dev)
+                nv.compressor_ragged_dq_item(a, dq_w.contiguous(), dq_item)
+            if want_fe:
+                inputs.d_fe = d_kx.view(fe.shape)
+            if want_ff:                                        # the value stream's input gradient and, without frames_embed, the key's
+                inputs.d_ff = (d_vx if fe is not None else (d_vx.float() + d_kx.float()).to(x.dtype)).view(x.shape)
+        elif window:
             fe = inputs.fe
             dctx_l = (dpre @ W0).contiguous()
             dq_w = torch.empty_like(dctx_l)
@@ -190,8 +268,8 @@ def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, 
     return st.grads, d_nl
 
 
-def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, input_grads=False):
-    check_scope(proj, ff, fe, guides, input_grads)
+def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, input_grads=False, adaptors=False):
+    check_scope(proj, ff, fe, guides, input_grads, adaptors)
     params = [(n, p) for n, p in proj.named_parameters()]
     trainable = torch.is_grad_enabled() and (any(p.requires_grad for _, p in params) or (isinstance(nl, torch.Tensor) and nl.requires_grad)
                                              or (input_grads and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (ff, fe, guides))))

@@ -1028,6 +1028,37 @@ int64_t hicom_compressor_ragged_adapt_workspace_bytes(const hicom_compressor_rag
 int hicom_compressor_ragged_adapt_prepare(const hicom_compressor_ragged_adapt_args* args);
 int hicom_compressor_ragged_adapt_fwd(const hicom_compressor_ragged_adapt_args* args);
 
+/* ---- training step of the ragged call for the k / v adaptor recipe (forward_ragged_train(adaptors=True)) ----
+ * hicom_compressor_ragged_adapt_train_state, after hicom_compressor_ragged_adapt_fwd on the same block: copies the fp16 y planes
+ * (the adaptor MLPs' outputs over all sum N_i tokens, 2 E sum N_i bytes each) out of the adaptor regions of args->base.ws; ky_out / vy_out
+ * may be NULL (not copied), one of them is not, and neither names a stream without adaptor.  The rest of the state is
+ * hicom_compressor_ragged_train_state(&args->base, ...): the plain layout does not move with the adaptors.
+ * The three calls below take the PLAIN block (&args->base of an adaptor plan): they read only the table region of args->ws and args'
+ * shape, l_scale and stream, and check their pointers, the alignment, the per-item partition and tokens x E < 2^32 in front of
+ * everything that needs a device.  Only launches: no allocation, no host copy, no synchronisation.
+ * hicom_compressor_ragged_local_adapt_bwd: hicom_local_attn_adapt_bwd over the concatenated window list, one 4-wave workgroup per window
+ * with the window's geometry from its item's own (T, kt), the x and y rows offset by the item's first token, the item's guide row (bf16
+ * [B, E]) as the query and bias 0.  key_x / value_x bf16, key_y / value_y fp16 [sum N_i, E] (NULL: that stream has no adaptor; not both),
+ * dctx f32 [sum w_i, E].  Outputs, plain stores:
+ *   ds, pw               f32 [sum N_i]
+ *   sxk, syk, sxv, syv   f32 [sum w_i, E] each or NULL (not written); syk / syv must be NULL for a stream without adaptor
+ * Per item the outputs are those of hicom_local_attn_adapt_bwd on that item alone, bit for bit.
+ * hicom_compressor_ragged_adapt_dy: hicom_adapt_dy_fwd over the stacked tokens, one wave per token.  The token's item is found by a
+ * search of the plan's item table, its window from the item's own axes; vec (bf16 | f32, rows of E) has one row per item (vec_per_item != 0:
+ * the K stream's guide rows) or one per window of the concatenated list (the V stream's dctx).  y fp16, coef f32 [sum N_i], dy / r1 bf16
+ * [sum N_i, E] (r1 may be NULL), col_parts f32 [nparts, E] or NULL as hicom_adapt_dy_fwd.
+ * hicom_compressor_ragged_dq_item: dq_item f32 [B, E] = the rows of dq f32 [sum w_i, E] summed per item in a fixed order, no atomics
+ * (the second launch of hicom_compressor_ragged_local_bwd on a dq of the caller's). */
+int hicom_compressor_ragged_adapt_train_state(const hicom_compressor_ragged_adapt_args* args, void* ky_out, void* vy_out);
+int hicom_compressor_ragged_local_adapt_bwd(const hicom_compressor_ragged_args* args, const void* key_x, const void* key_y, const void* k_gamma,
+                                            const void* k_beta, const void* k_alpha, const void* value_x, const void* value_y, const void* v_gamma,
+                                            const void* v_beta, const void* v_alpha, int32_t alpha_dt, float eps, const void* guide, const float* dctx,
+                                            float* ds, float* pw, float* sxk, float* syk, float* sxv, float* syv);
+int hicom_compressor_ragged_adapt_dy(const hicom_compressor_ragged_args* args, const void* y, const void* gamma, const void* vec, int32_t vec_dt,
+                                     int32_t vec_per_item, const float* coef, const void* alpha, int32_t alpha_dt, float eps, void* dy, void* r1,
+                                     float* col_parts, int32_t nparts);
+int hicom_compressor_ragged_dq_item(const hicom_compressor_ragged_args* args, const float* dq, float* dq_item);
+
 /* ---- multi-guide compressor step: ONE clip, Q instructions, the tokens read once ------------------------------------
  * What hicom/eval/video/inference_video_mcqa_videomme.py:268-303 does with one projector call per question on the same video tensor.
  * The guide enters both stages only as a query, so Q guides cost one pass over the tokens plus Q times the window-sized work.  The
