@@ -157,3 +157,10 @@ void* take_stop_event();
             return (code);                        \
         }                                         \
     } while (0)
+
+// a status that is not HICOM_OK ends the calling function with it (the callee has set the message)
+#define HICOM_TRY(call)                           \
+    do {                                          \
+        const int try_st_ = (call);               \
+        if (try_st_ != HICOM_OK) return try_st_;  \
+    } while (0)

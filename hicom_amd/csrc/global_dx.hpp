@@ -1,5 +1,5 @@
 // d frames_feature of the global stage for 64 tokens of ONE token run: the one body of global_dx_kernel (small_ops.hip: the run is the
-// whole call, the tile comes from blockIdx) and ragged_global_dx_kernel (ragged.hip: the run is an item, the tile comes from a device table).
+// whole call, the tile comes from blockIdx) and ragged_global_dx_kernel (ragged_train.hip: the run is an item, the tile comes from a device table).
 //     dx[n] (+)= sum_r dS[r, n] qt[r] + exp(S[r, n] - M_r) / L_r dctx[r]          (direct recipe: <= 16 folded rows)
 // Thread t owns channels 4t .. 4t+3 with the 2 * rows coefficient rows (qt | dctx) of those channels in registers and walks the tokens:
 // per token 2 * rows broadcast LDS reads of the coefficients (dS, p), 8 * rows FMAs, one 8-byte store.  Every pointer is the run's own:

@@ -265,7 +265,7 @@ struct LocalBwdParams {
     int accumulate, par_mask, par_val;
 };
 
-// the body is window_rows.hpp's local_window_bwd, shared with the ragged training step (ragged.hip: ragged_local_attn_bwd_kernel)
+// the body is window_rows.hpp's local_window_bwd, shared with the ragged training step (ragged_train.hip: ragged_local_attn_bwd_kernel)
 template <int NV>
 __global__ __launch_bounds__(256) void local_attn_bwd_kernel(LocalBwdParams p) {
     constexpr int D = NV * 384;
@@ -310,7 +310,7 @@ struct LocalAdaptBwdParams {
     float* sxk; float* syk; float* sxv; float* syv;     // [Nw, D] (syk / syv NULL when that stream has no adaptor)
 };
 
-// the body is window_rows.hpp's local_window_adapt_bwd, shared with the ragged training step (ragged.hip: ragged_local_attn_adapt_bwd_kernel)
+// the body is window_rows.hpp's local_window_adapt_bwd, shared with the ragged training step (ragged_train.hip: ragged_local_attn_adapt_bwd_kernel)
 template <int NV>
 __global__ __launch_bounds__(256) void local_attn_adapt_bwd_kernel(LocalAdaptBwdParams p) {
     constexpr int D = NV * 384;

@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void partials_sum_tall_kernel(const float* par
 using namespace hicom;
 
 // d frames_feature of the global stage (direct recipe: <= 16 folded rows).  A workgroup takes 64 tokens of the call's one token run; the body
-// is global_dx.hpp's global_dx_tile, shared with the ragged training step (ragged.hip: ragged_global_dx_kernel)
+// is global_dx.hpp's global_dx_tile, shared with the ragged training step (ragged_train.hip: ragged_global_dx_kernel)
 template <int RMAX>
 __global__ __launch_bounds__(320) void global_dx_kernel(const float* S, const float* dS, long stride, const float* ml, const float* qt, const float* dctx,
                                                           int rows, long N, int E, uint16_t* dx, int accumulate) {

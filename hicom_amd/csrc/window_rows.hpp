@@ -251,7 +251,7 @@ __device__ __forceinline__ void sum_partial_rows(const float* part, int tid, flo
 }
 
 // ---- backward of one window of the plain windowed attention: the one body of local_attn_bwd_kernel (local_attn.hip: the window comes from
-// blockIdx and the call's one grid) and ragged_local_attn_bwd_kernel (ragged.hip: the window's item comes from a device table, the grid is
+// blockIdx and the call's one grid) and ragged_local_attn_bwd_kernel (ragged_train.hip: the window's item comes from a device table, the grid is
 // the item's own).  Per window, autograd through projector.py:550-553 (local_attn.hip has the algebra and the clip-scale terms):
 //     s_i = scale q.k_i + bias,  p = softmax(s),  dP_i = dctx . v_i,  dS_i = p_i (dP_i - sum_j p_j dP_j),
 //     dq = scale sum_i dS_i k_i,  dk_i = scale dS_i q,  dv_i = p_i dctx (+ dk_i with value_is_key)
@@ -370,7 +370,7 @@ __device__ __forceinline__ void local_window_bwd(const WindowBwdArgs& p, const W
 
 // ---- backward of one window of the windowed attention WITH the k / v adaptor blends: the one body of local_attn_adapt_bwd_kernel
 // (local_attn.hip has the algebra: the window comes from blockIdx and the call's one grid) and ragged_local_attn_adapt_bwd_kernel
-// (ragged.hip: the window's item comes from a device table, the grid is the item's own).  kx / ky / vx / vy / ds / pw point at the first
+// (ragged_train.hip: the window's item comes from a device table, the grid is the item's own).  kx / ky / vx / vy / ds / pw point at the first
 // token of the grid `w` indexes; dctx and the four sums at the window's own row.  A sum whose pointer is NULL is not written (syk / syv
 // of a stream without adaptor: its y pointer is NULL too).  One 4-wave workgroup, lsm: 6 per-token arrays of the window + the [4][D] slab.
 struct WindowAdaptBwdArgs {
@@ -474,7 +474,7 @@ __device__ __forceinline__ void local_window_adapt_bwd(const WindowAdaptBwdArgs&
 }
 
 // ---- d y of one token of an adaptor stream (local_attn.hip: adapt_dy_kernel has the algebra), the one body of adapt_dy_kernel and
-// ragged_adapt_dy_kernel (ragged.hip): the caller finds the token's rows and the row of the rank-1 vector.  One wave; csum: this lane's
+// ragged_adapt_dy_kernel (ragged_train.hip): the caller finds the token's rows and the row of the rank-1 vector.  One wave; csum: this lane's
 // column sums of dy as stored (bf16-rounded).
 template <int NV>
 __device__ __forceinline__ void adapt_dy_token(const _Float16* y_row, const uint16_t* gamma, const void* vec_row, int vec_f32, float c, float alpha, float eps,

@@ -827,44 +827,47 @@ def compressor_ragged_fwd(args):
     _seg_call(args, "ragged", "fwd")
 
 
+def _ragged_train_call(fn, args, *rest):
+    """hicom_compressor_ragged_<fn>(&args, rest...) of the ragged training surface (csrc/ragged_train.hip); a tensor or None of `rest` goes as
+    its address, everything else as it is.  Returns the result, raises for a negative one."""
+    sym = "hicom_compressor_ragged_" + fn
+    n = getattr(lib(), sym)(C.byref(args), *(_ptr(r) if r is None or isinstance(r, torch.Tensor) else r for r in rest))
+    _check(min(n, 0), sym)               # (a positive result is a size, not a status)
+    return int(n)
+
+
 def compressor_ragged_train_state(args: CompressorRaggedArgs, ctx16, scores, ml, ctxg):
     """What a backward of the call just made reads, out of the plan's workspace into tensors of the caller's (hicom_compressor_ragged_train_state)."""
-    _check(lib().hicom_compressor_ragged_train_state(C.byref(args), _ptr(ctx16), _ptr(scores), _ptr(ml), _ptr(ctxg)), "hicom_compressor_ragged_train_state")
+    _ragged_train_call("train_state", args, ctx16, scores, ml, ctxg)
 
 
 def compressor_ragged_global_bwd_workspace(args: CompressorRaggedArgs) -> int:
-    n = lib().hicom_compressor_ragged_global_bwd_workspace_bytes(C.byref(args))
-    if n < 0:
-        raise HicomNativeError(f"hicom_compressor_ragged_global_bwd_workspace_bytes failed ({n}): {lib().hicom_last_error().decode(errors='replace')}")
-    return int(n)
+    return _ragged_train_call("global_bwd_workspace_bytes", args)
 
 
 def compressor_ragged_global_bwd(args: CompressorRaggedArgs, x, dctx, delta, scores, ml, ds, dqt, ws):
     """The global stage's attention backward over all items of a ragged plan (hicom_compressor_ragged_global_bwd): fills ds and dqt."""
-    _check(lib().hicom_compressor_ragged_global_bwd(C.byref(args), _ptr(x), _ptr(dctx), _ptr(delta), _ptr(scores), _ptr(ml), _ptr(ds), _ptr(dqt), _ptr(ws),
-                                                    ws.numel()), "hicom_compressor_ragged_global_bwd")
+    _ragged_train_call("global_bwd", args, x, dctx, delta, scores, ml, ds, dqt, ws, ws.numel())
 
 
 def compressor_ragged_local_bwd(args: CompressorRaggedArgs, key, value, guide, dctx, dq, dq_item=None, dkey=None, dvalue=None, value_is_key=False):
     """The window backward over all items of a ragged plan (hicom_compressor_ragged_local_bwd): fills dq [windows, E], dq_item [B, E] (the
     windows of an item summed in a fixed order) and whichever of dkey / dvalue bf16 [tokens, E] is given."""
     assert key.dtype == value.dtype == guide.dtype == torch.bfloat16 and dctx.dtype == dq.dtype == torch.float32
-    _check(lib().hicom_compressor_ragged_local_bwd(C.byref(args), _ptr(key), _ptr(value), _ptr(guide), _ptr(dctx), _ptr(dq), _ptr(dq_item), _ptr(dkey),
-                                                   _ptr(dvalue), int(bool(value_is_key))), "hicom_compressor_ragged_local_bwd")
+    _ragged_train_call("local_bwd", args, key, value, guide, dctx, dq, dq_item, dkey, dvalue, int(bool(value_is_key)))
 
 
 def compressor_ragged_global_dx(args: CompressorRaggedArgs, scores, ds, ml, qt, dctx, tiles, dx, accumulate):
     """d frames_feature of the global stage over all items of a ragged plan (hicom_compressor_ragged_global_dx); tiles: the device int32
     [ntiles, 2] table of ragged.dx_tile_table."""
     assert tiles.dtype == torch.int32 and tiles.is_contiguous() and dx.dtype == torch.bfloat16
-    _check(lib().hicom_compressor_ragged_global_dx(C.byref(args), _ptr(scores), _ptr(ds), _ptr(ml), _ptr(qt), _ptr(dctx), _ptr(tiles), tiles.shape[0],
-                                                   _ptr(dx), int(bool(accumulate))), "hicom_compressor_ragged_global_dx")
+    _ragged_train_call("global_dx", args, scores, ds, ml, qt, dctx, tiles, tiles.shape[0], dx, int(bool(accumulate)))
 
 
 def compressor_ragged_adapt_train_state(args: CompressorRaggedAdaptArgs, ky, vy):
     """The fp16 y planes [tokens, E] of the adapted streams out of an adaptor plan's workspace (hicom_compressor_ragged_adapt_train_state);
     None for a stream without adaptor."""
-    _check(lib().hicom_compressor_ragged_adapt_train_state(C.byref(args), _ptr(ky), _ptr(vy)), "hicom_compressor_ragged_adapt_train_state")
+    _ragged_train_call("adapt_train_state", args, ky, vy)
 
 
 def compressor_ragged_local_adapt_bwd(args: CompressorRaggedArgs, key_x, key_y, k_norm, k_alpha, value_x, value_y, v_norm, v_alpha, guide, dctx, ds, pw,
@@ -874,11 +877,9 @@ def compressor_ragged_local_adapt_bwd(args: CompressorRaggedArgs, key_x, key_y, 
     alpha = k_alpha if key_y is not None else v_alpha
 
     def affine(y, norm, al):           # (gamma, beta, alpha) of an adapted stream, three NULLs otherwise
-        return (_ptr(norm.weight.detach()), _ptr(norm.bias.detach()), _ptr(al.detach())) if y is not None else (None, None, None)
-    _check(lib().hicom_compressor_ragged_local_adapt_bwd(C.byref(args), _ptr(key_x), _ptr(key_y), *affine(key_y, k_norm, k_alpha), _ptr(value_x),
-                                                         _ptr(value_y), *affine(value_y, v_norm, v_alpha), _dt(alpha), eps, _ptr(guide), _ptr(dctx),
-                                                         _ptr(ds), _ptr(pw), _ptr(sxk), _ptr(syk), _ptr(sxv), _ptr(syv)),
-           "hicom_compressor_ragged_local_adapt_bwd")
+        return (norm.weight.detach(), norm.bias.detach(), al.detach()) if y is not None else (None, None, None)
+    _ragged_train_call("local_adapt_bwd", args, key_x, key_y, *affine(key_y, k_norm, k_alpha), value_x, value_y, *affine(value_y, v_norm, v_alpha), _dt(alpha),
+                       eps, guide, dctx, ds, pw, sxk, syk, sxv, syv)
 
 
 def compressor_ragged_adapt_dy(args: CompressorRaggedArgs, y, gamma, vec, vec_per_item, coef, alpha, dy, r1=None, eps=1e-6, colsum=False):
@@ -886,9 +887,8 @@ def compressor_ragged_adapt_dy(args: CompressorRaggedArgs, y, gamma, vec, vec_pe
     window.  colsum=True: also returns the column sums of dy (f32 [E]) from partials the same launch leaves."""
     D = y.shape[-1]
     parts = _col_parts(dy.shape[0], D, dy.device) if colsum else None
-    _check(lib().hicom_compressor_ragged_adapt_dy(C.byref(args), _ptr(y), _ptr(gamma), _ptr(vec), _dt(vec), int(bool(vec_per_item)), _ptr(coef), _ptr(alpha),
-                                                  _dt(alpha), eps, _ptr(dy), _ptr(r1), _ptr(parts), parts.shape[0] if colsum else 0),
-           "hicom_compressor_ragged_adapt_dy")
+    _ragged_train_call("adapt_dy", args, y, gamma, vec, _dt(vec), int(bool(vec_per_item)), coef, alpha, _dt(alpha), eps, dy, r1, parts,
+                       parts.shape[0] if colsum else 0)
     if not colsum:
         return None
     out = torch.empty((D,), dtype=torch.float32, device=dy.device)
@@ -899,7 +899,7 @@ def compressor_ragged_adapt_dy(args: CompressorRaggedArgs, y, gamma, vec, vec_pe
 def compressor_ragged_dq_item(args: CompressorRaggedArgs, dq, dq_item):
     """dq_item [B, E] = the rows of dq [windows, E] summed per item of a ragged plan (hicom_compressor_ragged_dq_item)."""
     assert dq.dtype == dq_item.dtype == torch.float32
-    _check(lib().hicom_compressor_ragged_dq_item(C.byref(args), _ptr(dq), _ptr(dq_item)), "hicom_compressor_ragged_dq_item")
+    _ragged_train_call("dq_item", args, dq, dq_item)
 
 
 def compressor_multiguide_workspace(args) -> int:

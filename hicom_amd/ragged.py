@@ -112,7 +112,7 @@ def train_row_maps(t):
     return np.concatenate(local), np.concatenate(newline), np.stack(glob)
 
 
-DX_TILE = 64             # tokens per workgroup of ragged_global_dx_kernel (csrc/ragged.hip)
+DX_TILE = 64             # tokens per workgroup of ragged_global_dx_kernel (csrc/ragged_train.hip)
 
 
 def dx_tile_table(t) -> np.ndarray:
@@ -123,7 +123,7 @@ def dx_tile_table(t) -> np.ndarray:
 
 
 def token_item_window(t, H: int, W: int, ks: int):
-    """(item, window) int64 arrays over all sum N_i stacked tokens, found as ragged_adapt_dy_kernel (csrc/ragged.hip) finds them, from
+    """(item, window) int64 arrays over all sum N_i stacked tokens, found as ragged_adapt_dy_kernel (csrc/ragged_train.hip) finds them, from
     plan_tables' result alone: the item is the last one whose first token is <= the token (a search of tok0, no table of token size), the
     window WindowGeom::window_of on the item's own (T, kt) axes plus the item's first window."""
     tok = np.arange(sum(t.N), dtype=np.int64)

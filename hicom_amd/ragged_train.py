@@ -8,7 +8,7 @@ same bits) and the backward is ONE eager pass over all items: the same call sequ
                  (autograd._readout_backward) over the sum of all items' windows; d image_newline = the sum of all newline rows.
                  The window backward never runs in this scope (autograd._window_backward_runs is false for it).
   global stage   rows item-major (item nh + head): autograd._global_tail_backward with the B guides as the B queries, then
-                 hicom_compressor_ragged_global_bwd (csrc/ragged.hip: the segmented backward stream + the dq merge, four launches),
+                 hicom_compressor_ragged_global_bwd (csrc/ragged_train.hip: the segmented backward stream + the dq merge, four launches),
                  then autograd._global_fold_backward and the q_proj gradients.
 
 The autograd node owns what its backward reads (window contexts, logits, softmax state, merged contexts: copied out of the plan's
@@ -44,6 +44,7 @@ adaptors, no clip-scale, bf16 module and inputs, exact window partition per item
 grad and of image_newline.  Everything else raises NotImplementedError naming the loop of forward(): nothing is detached silently."""
 from __future__ import annotations
 
+import functools
 import types
 
 import torch
@@ -76,26 +77,19 @@ def check_scope(proj, ff, fe, guides, input_grads=False, adaptors=False):
                                       f"input_grads=True; pass it, detach {name}, or {_LOOP}")
 
 
-def _device_maps(plan, dev):
-    """ragged.train_row_maps of the plan as device index tensors, made once per plan."""
-    if plan.train_maps is None:
-        plan.train_maps = tuple(torch.from_numpy(m).to(dev) for m in ragged.train_row_maps(plan.tables))
-    return plan.train_maps
+class _PlanTrain:
+    """What the backward derives from a ragged plan (SegPlan.train): each field is made when first asked for and kept with the plan."""
 
+    def __init__(self, plan, dev):
+        self._tables, self._io, self._dev = plan.tables, plan.io, dev
 
-def _device_tiles(plan, dev):
-    """ragged.dx_tile_table of the plan as a device int32 [ntiles, 2] tensor, made once per plan."""
-    if plan.train_tiles is None:
-        plan.train_tiles = torch.from_numpy(ragged.dx_tile_table(plan.tables)).to(dev)
-    return plan.train_tiles
-
-
-def _device_win_item(plan, dev):
-    """The window -> item index of the plan (plan_tables' win_item) as a device int64 tensor, made once per plan: the query row of a window
-    is its item's guide."""
-    if plan.train_win_item is None:
-        plan.train_win_item = torch.from_numpy(plan.tables.win_item.astype("int64")).to(dev)
-    return plan.train_win_item
+    # ragged.train_row_maps as device index tensors: (local rows, newline rows, global rows)
+    row_maps = functools.cached_property(lambda s: tuple(torch.from_numpy(m).to(s._dev) for m in ragged.train_row_maps(s._tables)))
+    # ragged.dx_tile_table as a device int32 [ntiles, 2] tensor
+    dx_tiles = functools.cached_property(lambda s: torch.from_numpy(ragged.dx_tile_table(s._tables)).to(s._dev))
+    # the window -> item index (plan_tables' win_item) as a device int64 tensor: the query row of a window is its item's guide
+    win_item = functools.cached_property(lambda s: torch.from_numpy(s._tables.win_item.astype("int64")).to(s._dev))
+    bwd_ws_bytes = functools.cached_property(lambda s: nv.compressor_ragged_global_bwd_workspace(s._io))
 
 
 _ADAPTOR_PARAMS = tuple(f"local_compressor.{s}_{part}" for s in "kv" for part in ("proj.", "norm.", "alpha"))
@@ -112,6 +106,7 @@ class _RaggedTrainFn(torch.autograd.Function):
         with torch.no_grad():
             out, plan, x, g = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
             t, a, dev = plan.tables, plan.io, x.device
+            plan.train = plan.train or _PlanTrain(plan, dev)
             # frames_embed, by reference, only where the window backward will run (an input gradient is asked for, or an adaptor trains)
             lc = proj.local_compressor
             adapt = lc.adapt_k or lc.adapt_v
@@ -140,20 +135,16 @@ class _RaggedTrainFn(torch.autograd.Function):
         proj, plan, names = ctx.proj, ctx.plan, ctx.names
         need = ctx.needs_input_grad            # (proj, ff, fe, guides, nl, meta, names, *params)
         want = {n for k, n in enumerate(names) if need[7 + k]}
-        inputs = None
-        if any(need[1:4]):
-            inputs = types.SimpleNamespace(want_ff=bool(need[1]), want_fe=bool(need[2]), want_guide=bool(need[3]), fe=keys, d_ff=None, d_fe=None, d_guide=None)
+        inputs = types.SimpleNamespace(want_ff=bool(need[1]), want_fe=bool(need[2]), want_guide=bool(need[3]), fe=keys, d_ff=None, d_fe=None, d_guide=None)
         with torch.no_grad():
-            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]), inputs, adapt=(keys, ky, vy))
+            grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]), inputs, adapt=(ky, vy))
         ag.LAST_FP32_GRADS = dict(grads)               # (test hook, as the single-item backward leaves it; here with d image_newline)
         if d_nl is not None:
             ag.LAST_FP32_GRADS["image_newline"] = d_nl
-        d_ff = d_fe = d_g = None
-        if inputs is not None:
-            d_ff, d_fe = inputs.d_ff, inputs.d_fe
-            if inputs.d_guide is not None:
-                ag.LAST_FP32_GRADS["__guide_embeds__"] = inputs.d_guide        # (fp32 [B, E], as the single-item path leaves "__guide_embed__")
-                d_g = inputs.d_guide.to(guides.dtype)
+        d_g = None
+        if inputs.d_guide is not None:
+            ag.LAST_FP32_GRADS["__guide_embeds__"] = inputs.d_guide        # (fp32 [B, E], as the single-item path leaves "__guide_embed__")
+            d_g = inputs.d_guide.to(guides.dtype)
         plist = dict(proj.named_parameters())
         out = [None] * len(names)
         by_dtype = {}
@@ -166,14 +157,13 @@ class _RaggedTrainFn(torch.autograd.Function):
                 cnt = plist[n].numel()
                 out[k] = flat[o:o + cnt].view(plist[n].shape)
                 o += cnt
-        return (None, d_ff, d_fe, d_g, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
+        return (None, inputs.d_ff, inputs.d_fe, d_g, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
 
 
 def _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, ky, vy, want_kx, want_vx, want_guide):
     """The local stage behind the readout for the k / v adaptor recipe: the window backward through the blends over all items, the adaptors'
     reductions and the MLPs' backward over the stacked tokens.  Fills st.grads; returns (dq_w or None, d_kx, d_vx), bf16 [sum N_i, E] each."""
-    a, x, dev = plan.io, st.ff, st.dev
-    E = a.E
+    a, x, dev, E = plan.io, st.ff, st.dev, plan.io.E
     kx2, vx2 = (fe if fe is not None else x).view(-1, E), x.view(-1, E)
     N, nw = vx2.shape[0], dctx_l.shape[0]
     f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
@@ -186,85 +176,92 @@ def _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, ky, vy, want_kx, wan
     # the hidden planes, recomputed: one layer-1 GEMM per adapted stream, in the forward's arithmetic
     rec_k = (ag._adaptor_hidden(kx2, lc.k_proj)[0], None, ky) if lc.adapt_k else None
     rec_v = (ag._adaptor_hidden(vx2, lc.v_proj)[0], None, vy) if lc.adapt_v else None
-    qf = guides.float()[_device_win_item(plan, dev)] if lc.adapt_k else None           # the query row of every window: its item's guide
-    dy_k = lambda y, gamma, vec, coef, alpha, dy, r1, **kw: nv.compressor_ragged_adapt_dy(a, y, gamma, vec, True, coef, alpha, dy, r1, **kw)
-    dy_v = lambda y, gamma, vec, coef, alpha, dy, r1, **kw: nv.compressor_ragged_adapt_dy(a, y, gamma, vec, False, coef, alpha, dy, r1, **kw)
+    qf = guides.float()[plan.train.win_item] if lc.adapt_k else None           # the query row of every window: its item's guide
+    dy_of = lambda per_item: lambda y, gamma, vec, coef, alpha, dy, r1, **kw: nv.compressor_ragged_adapt_dy(a, y, gamma, vec, per_item, coef, alpha, dy, r1, **kw)
     return ag._adaptor_streams_backward(lc, st.f32, st.grads, kx2, vx2, rec_k, rec_v, qf, guides, dctx_l, (ds, pw, sxk, syk, sxv, syv), want_kx, want_vx,
-                                        dy_k, dy_v, want_dq=want_guide)
+                                        dy_of(True), dy_of(False), want_dq=want_guide)
 
 
-def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl, inputs=None, adapt=(None, None, None)):
-    """(fp32 gradients {parameter name: tensor} of sum(out * dout) over all items, d image_newline or None).  `want`: the names of the
-    parameters whose gradient is asked for; a stage none of whose parameters is wanted does not run unless an input gradient needs it.
-    inputs (None: no input gradient is asked for): want_ff / want_fe / want_guide and the contiguous frames_embed (or None) in, d_ff / d_fe
-    (bf16, the inputs' shapes) and d_guide (fp32 [B, E]) out.  adapt: (frames_embed or None, ky, vy) of the adaptor recipe, the y planes the
-    forward kept (None for a stream without adaptor; all None for the plain recipe)."""
-    lc, gc = proj.local_compressor, proj.global_compressor
-    dev, a = x.device, plan.io
-    local_rows, nl_rows, glob_rows = _device_maps(plan, dev)
-    dout = dout.float()
-    st = types.SimpleNamespace(proj=proj, ff=x, dev=dev, f32=ag._f32_params(proj), grads={})
-    f32, L = st.f32, "local_compressor.readout."
-    d_nl = dout[nl_rows].sum(0) if (want_nl and nl_rows.numel()) else None
-    want_ff = inputs is not None and inputs.want_ff
-    want_fe = inputs is not None and inputs.want_fe and inputs.fe is not None
-    want_guide = inputs is not None and inputs.want_guide
+def _local_backward(st, ctx16, dout, local_rows, window, adapt):
+    """The local stage: the readout backward over the sum of all items' windows and, where `window`, the window backward of the module's
+    recipe behind it, which leaves d frames_embed and the local share of d frames_feature in st.inputs.  Returns dq_item (fp32 [B, E], the
+    local share of d guide) or None."""
+    lc, plan, x, guides, inputs, f32 = st.proj.local_compressor, st.plan, st.ff, st.guides, st.inputs, st.f32
+    a, fe, L = plan.io, inputs.fe, "local_compressor.readout."
     adaptors = lc.adapt_k or lc.adapt_v
+    assert adaptors or ag._window_backward_runs(lc, st.want_fe, st.want_guide, st.proj.local_logit, st.want_ff) == window
+    ctx_l = ctx16.float()
+    W0, b0 = f32[L + "0.weight"], f32[L + "0.bias"]
+    dpre = ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
+    if not window:
+        return None
+    dctx_l = (dpre @ W0).contiguous()
+    dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=st.dev) if st.want_guide else None
+    if adaptors:
+        dq_w, d_kx, d_vx = _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, *adapt, st.want_fe or (st.want_ff and fe is None), st.want_ff, st.want_guide)
+        if st.want_guide:
+            nv.compressor_ragged_dq_item(a, dq_w.contiguous(), dq_item)
+        d_fe = d_kx.view(fe.shape) if st.want_fe else None
+        # the value stream's input gradient and, without frames_embed, the key's
+        d_ff = (d_vx if fe is not None else (d_vx.float() + d_kx.float()).to(x.dtype)).view(x.shape) if st.want_ff else None
+    else:
+        dq_w = torch.empty_like(dctx_l)
+        d_fe = torch.empty_like(fe) if st.want_fe else None
+        d_ff = torch.empty_like(x) if st.want_ff else None      # (value-side share; without frames_embed the key-side term is added in)
+        nv.compressor_ragged_local_bwd(a, fe if fe is not None else x, x, guides, dctx_l, dq_w, dq_item, d_fe, d_ff, value_is_key=st.want_ff and fe is None)
+    inputs.d_fe, inputs.d_ff = d_fe, d_ff
+    return dq_item
+
+
+def _global_backward(st, scores, ml, ctxg, dout, glob_rows, dq_item):
+    """The global stage, rows item-major: the tail, the attention backward over all items in one native call, the fold and q_proj; then the
+    global shares of d frames_feature (added into st.inputs.d_ff) and of d guide (st.inputs.d_guide = dq_item + it)."""
+    plan, x, inputs, f32 = st.plan, st.ff, st.inputs, st.f32
+    a, dev = plan.io, st.dev
+    att = st.proj.global_compressor.attn_layer
+    nh, hd = att.num_heads, att.head_dim
+    q32 = st.guides.float()
+    dtok = dout[glob_rows].sum(1)                              # [B, hidden]: an item's global rows are copies of one row
+    dpre_g, dctx, delta = ag._global_tail_backward(st, nh, hd, ml, None, q32, dtok, ctxg=ctxg)
+    ds, dqt = torch.empty_like(scores), torch.empty_like(ctxg)
+    ws = torch.empty((plan.train.bwd_ws_bytes,), dtype=torch.uint8, device=dev)
+    nv.compressor_ragged_global_bwd(a, x, dctx, delta, scores, ml, ds, dqt, ws)
+    A = "global_compressor.attn_layer."
+    Wq, bq, Wk = f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"]
+    dqp = ag._global_fold_backward(st, att, None, None, None, None, q32, Wq, bq, Wk, dqt=dqt)
+    ag._q_proj_backward(st.grads, dqp, q32)
+    if st.want_ff:
+        # d frames_feature, global share (the algebra of autograd._global_dff with the B guides as the B queries): qt for all B nh rows,
+        # then one call over all items, added to the rows the window backward left
+        E = q32.shape[1]
+        qp_ = (q32 @ Wq.t() + bq).view(-1, nh, hd)
+        qt_ = (att.scale * torch.einsum("hje,qhj->qhe", Wk.view(nh, hd, E), qp_)).reshape(-1, E).contiguous()
+        nv.compressor_ragged_global_dx(a, scores, ds, ml, qt_, dctx, plan.train.dx_tiles, inputs.d_ff.view(-1, E), accumulate=True)
+    if st.want_guide:
+        # direct recipe: the injected query IS the guide, one row per item (autograd._global_query_backward) + the local stage's share
+        inputs.d_guide = dq_item + (dqp @ Wq + dpre_g)
+
+
+def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl, inputs, adapt=(None, None)):
+    """(fp32 gradients {parameter name: tensor} of sum(out * dout) over all items, d image_newline or None): _local_backward, then
+    _global_backward, over one shared state `st`.  `want`: the names of the parameters whose gradient is asked for; a stage none of whose
+    parameters is wanted does not run unless an input gradient needs it.
+    inputs: want_ff / want_fe / want_guide (the input gradients asked for) and the contiguous frames_embed (or None) in, d_ff / d_fe (bf16,
+    the inputs' shapes) and d_guide (fp32 [B, E]) out.  adapt: (ky, vy) of the adaptor recipe, the y planes the forward kept (None for a
+    stream without adaptor; both None for the plain recipe)."""
+    lc, dev = proj.local_compressor, x.device
+    local_rows, nl_rows, glob_rows = plan.train.row_maps
+    dout = dout.float()
+    st = types.SimpleNamespace(proj=proj, plan=plan, ff=x, guides=guides, dev=dev, f32=ag._f32_params(proj), grads={}, inputs=inputs,
+                               want_ff=inputs.want_ff, want_fe=inputs.want_fe and inputs.fe is not None, want_guide=inputs.want_guide)
+    d_nl = dout[nl_rows].sum(0) if (want_nl and nl_rows.numel()) else None
     # the window backward: every input gradient has a local share; with adaptors, also where one of them trains
-    window = want_ff or want_fe or want_guide or (adaptors and _adaptor_wanted(want))
+    window = st.want_ff or st.want_fe or st.want_guide or ((lc.adapt_k or lc.adapt_v) and _adaptor_wanted(want))
     dq_item = None
     if window or any(n.startswith("local_compressor.") for n in want):
-        assert adaptors or ag._window_backward_runs(lc, want_fe, want_guide, proj.local_logit, want_ff) == window
-        ctx_l = ctx16.float()
-        W0, b0 = f32[L + "0.weight"], f32[L + "0.bias"]
-        dpre = ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
-        if window and adaptors:
-            fe, ky, vy = adapt
-            dctx_l = (dpre @ W0).contiguous()
-            dq_w, d_kx, d_vx = _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, ky, vy, want_fe or (want_ff and fe is None), want_ff, want_guide)
-            if want_guide:
-                dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=dev)
-                nv.compressor_ragged_dq_item(a, dq_w.contiguous(), dq_item)
-            if want_fe:
-                inputs.d_fe = d_kx.view(fe.shape)
-            if want_ff:                                        # the value stream's input gradient and, without frames_embed, the key's
-                inputs.d_ff = (d_vx if fe is not None else (d_vx.float() + d_kx.float()).to(x.dtype)).view(x.shape)
-        elif window:
-            fe = inputs.fe
-            dctx_l = (dpre @ W0).contiguous()
-            dq_w = torch.empty_like(dctx_l)
-            dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=dev) if want_guide else None
-            inputs.d_fe = torch.empty_like(fe) if want_fe else None
-            inputs.d_ff = torch.empty_like(x) if want_ff else None          # (value-side share; without frames_embed the key-side term is added in)
-            nv.compressor_ragged_local_bwd(a, fe if fe is not None else x, x, guides, dctx_l, dq_w, dq_item, inputs.d_fe, inputs.d_ff,
-                                           value_is_key=want_ff and fe is None)
-    if want_ff or want_guide or any(n.startswith("global_compressor.") for n in want):
-        att = gc.attn_layer
-        nh, hd = att.num_heads, att.head_dim
-        q32 = guides.float()
-        dtok = dout[glob_rows].sum(1)                          # [B, hidden]: an item's global rows are copies of one row
-        dpre_g, dctx, delta = ag._global_tail_backward(st, nh, hd, ml, None, q32, dtok, ctxg=ctxg)
-        ds = torch.empty_like(scores)
-        dqt = torch.empty_like(ctxg)
-        if plan.train_ws_bytes is None:                        # (fixed per plan, like the row maps)
-            plan.train_ws_bytes = nv.compressor_ragged_global_bwd_workspace(a)
-        ws = torch.empty((plan.train_ws_bytes,), dtype=torch.uint8, device=dev)
-        nv.compressor_ragged_global_bwd(a, x, dctx, delta, scores, ml, ds, dqt, ws)
-        A = "global_compressor.attn_layer."
-        dqp = ag._global_fold_backward(st, att, None, None, None, None, q32, f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"],
-                                       dqt=dqt)
-        ag._q_proj_backward(st.grads, dqp, q32)
-        if want_ff:
-            # d frames_feature, global share (the algebra of autograd._global_dff with the B guides as the B queries): qt for all B nh rows,
-            # then one call over all items, added to the rows the window backward left
-            Wq, bq, Wk = f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"]
-            E = q32.shape[1]
-            qp_ = (q32 @ Wq.t() + bq).view(-1, nh, hd)
-            qt_ = (att.scale * torch.einsum("hje,qhj->qhe", Wk.view(nh, hd, E), qp_)).reshape(-1, E).contiguous()
-            nv.compressor_ragged_global_dx(a, scores, ds, ml, qt_, dctx, _device_tiles(plan, dev), inputs.d_ff.view(-1, E), accumulate=True)
-        if want_guide:
-            # direct recipe: the injected query IS the guide, one row per item (autograd._global_query_backward) + the local stage's share
-            inputs.d_guide = dq_item + (dqp @ f32[A + "q_proj.weight"] + dpre_g)
+        dq_item = _local_backward(st, ctx16, dout, local_rows, window, adapt)
+    if st.want_ff or st.want_guide or any(n.startswith("global_compressor.") for n in want):
+        _global_backward(st, scores, ml, ctxg, dout, glob_rows, dq_item)
     return st.grads, d_nl
 
 

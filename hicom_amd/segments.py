@@ -23,8 +23,7 @@ cached_plan, MAX_PLANS = engine.cached_plan, engine.MAX_PLANS       # (the steps
 
 
 class SegPlan:
-    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes", "train_maps", "train_ws_bytes",
-                 "train_tiles", "train_win_item")
+    __slots__ = ("args", "io", "items", "ws", "rows", "hidden", "sig", "fresh", "refresh", "hits", "keep", "tables", "adapt_bytes", "train")
 
     def __init__(self, args, ws, rows, hidden, items=None, tables=None):
         # args: the block the entry point takes; io: the plain block inside it (args itself for the plain recipe), whose input / output
@@ -32,7 +31,7 @@ class SegPlan:
         # items / tables: the host item descriptors and the table arithmetic of a ragged plan, None for a batch plan
         self.args, self.ws, self.rows, self.hidden, self.items, self.tables = args, ws, rows, hidden, items, tables
         self.io = getattr(args, "base", args)
-        self.sig = self.fresh = self.refresh = self.keep = self.train_maps = self.train_ws_bytes = self.train_tiles = self.train_win_item = None   # (train_*: ragged_train.py's row maps, workspace size, dx tile table, window -> item index)
+        self.sig = self.fresh = self.refresh = self.keep = self.train = None   # (train: what ragged_train.py derives from the plan once, made there)
         self.hits = self.adapt_bytes = 0
 
 

@@ -1,4 +1,4 @@
-"""hicom_compressor_ragged_global_bwd alone (csrc/ragged.hip: planes of dctx, pos_b = dctx . pe^T, ragged_global_stream_bwd_kernel,
+"""hicom_compressor_ragged_global_bwd alone (csrc/ragged_train.hip: planes of dctx, pos_b = dctx . pe^T, ragged_global_stream_bwd_kernel,
 ragged_dq_merge_kernel), from synthetic state built on the host -- no forward is run -- in the style of tests/test_gpu_global_stream.py.
 
 Inputs per item (five items of 1, 4, 1, 8, 1 frames at 6 x 6: token offsets 36, 180, 216, 504, none a multiple of a tile, a masked tail

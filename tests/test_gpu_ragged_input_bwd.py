@@ -1,4 +1,4 @@
-"""hicom_compressor_ragged_local_bwd and hicom_compressor_ragged_global_dx alone (csrc/ragged.hip: ragged_local_attn_bwd_kernel,
+"""hicom_compressor_ragged_local_bwd and hicom_compressor_ragged_global_dx alone (csrc/ragged_train.hip: ragged_local_attn_bwd_kernel,
 ragged_dq_item_kernel, ragged_global_dx_kernel), from synthetic state built on the host -- no forward is run -- against the float64
 references of tests/ragged_input_bwd_reference.py.
 

@@ -1,5 +1,5 @@
 """HIComProjector.forward_ragged_train (GPU): the training step of a mixed batch in one forward call and one backward over all items
-(hicom_amd/ragged_train.py, csrc/ragged.hip) against fp64 autograd through the oracle, per item, summed (tests/ragged_train_inputs.py
+(hicom_amd/ragged_train.py, csrc/ragged_train.hip) against fp64 autograd through the oracle, per item, summed (tests/ragged_train_inputs.py
 has the cases, the cotangents and the bar: tests/test_gpu_backward.py's rule on the fp32 gradients).  Every gradient test prints, per
 parameter, the error of the new path and of the loop of forward() + backward per item, the code the step replaces.
 Measured on an MI355X: both paths are inside the bar on every case; the new path's error is 0.8 .. 1.3 x the loop's per parameter

@@ -1,5 +1,5 @@
 """HIComProjector.forward_ragged_train(adaptors=True) (GPU): the training step of a mixed batch for the k / v adaptor recipe in one forward
-call and one backward over all items (hicom_amd/ragged_train.py; csrc/ragged.hip: ragged_local_attn_adapt_bwd_kernel,
+call and one backward over all items (hicom_amd/ragged_train.py; csrc/ragged_train.hip: ragged_local_attn_adapt_bwd_kernel,
 ragged_adapt_dy_kernel) against fp64 autograd through the oracle per item, summed.  tests/ragged_train_adapt_inputs.py has the cases, the
 yardstick, the bars and the fallback rule; every gradient test prints the new path's error beside that of the loop of forward() + backward
 per item, the code the step replaces.  Every test here fails without the feature: the keyword does not exist there.

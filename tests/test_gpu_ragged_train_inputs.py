@@ -1,5 +1,5 @@
 """HIComProjector.forward_ragged_train(input_grads=True) (GPU): the stage-3 input gradients of a mixed batch -- d frames_feature,
-d frames_embed, d guide_embeds -- from one forward call and one backward over all items (hicom_amd/ragged_train.py, csrc/ragged.hip:
+d frames_embed, d guide_embeds -- from one forward call and one backward over all items (hicom_amd/ragged_train.py, csrc/ragged_train.hip:
 ragged_local_attn_bwd_kernel, ragged_dq_item_kernel, ragged_global_dx_kernel) against fp64 autograd through the oracle per item
 (tests/ragged_train_input_grads.py has the yardstick and the bars).  Every gradient test prints the error of the new path and of the loop
 of forward() + backward per item with the same inputs requiring grad, the code the step replaces.  Every test here fails without the

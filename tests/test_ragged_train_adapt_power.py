@@ -1,6 +1,6 @@
 """Whether the GPU tests of forward_ragged_train(adaptors=True) can see the mistakes a ragged adaptor backward can make (CPU, fp64).
 
-A model of the step's local stage as ragged_train.py and csrc/ragged.hip compute it -- the window backward's per-token (ds, pw) and per-window
+A model of the step's local stage as ragged_train.py and csrc/ragged_train.hip compute it -- the window backward's per-token (ds, pw) and per-window
 sums, the dy step with the token -> (item, window) lookup of ragged.token_item_window, the adaptor MLPs' backward over the stacked tokens, the
 input gradients -- is held against torch autograd (fp64) through the same local stage written as a plain forward, on the inputs and weights of
 every case of tests/test_gpu_ragged_train_adapt.py with a seeded cotangent of the window contexts.  Without a defect the model equals autograd
