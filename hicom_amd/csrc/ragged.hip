@@ -19,6 +19,7 @@
 // layout are ragged_host.hpp's, shared with the training surface of this step (ragged_train.hip).
 #include <vector>
 
+#include "multi_window.hpp"
 #include "ragged_host.hpp"
 
 namespace hicom {
@@ -49,6 +50,20 @@ __global__ __launch_bounds__(256) void ragged_local_attn_adapt_kernel(const uint
     const RaggedWindow w(items, win_item, ay, ax, win, D);
     local_window_adapt_ctx16<NV>(key + w.first, ad.ky ? ad.ky + w.first : nullptr, value + w.first, ad.vy ? ad.vy + w.first : nullptr, ad,
                                  guide + (long)w.item * D, w.geom, lane, scale, ctx16 + (long)win * D);
+}
+
+// ... and the logits form: the same wave -> window -> item map with the raw scores key_n . guide_item given, f32 [sum N_i]
+// over the stacked tokens (one guide per item: token n of item i at tok0_i + n).  Lane i fetches the score of the window's token i; no key
+// row and no guide row is read (multi_window.hpp: multi_window_logits_ctx16 with one guide)
+template <int NV>
+__global__ __launch_bounds__(256) void ragged_local_logits_kernel(const uint16_t* value, const float* logits, const RaggedItem* items, const int* win_item,
+                                                                  hicom_axis ay, hicom_axis ax, int nwin, float scale, _Float16* ctx16) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= nwin) return;
+    const RaggedWindow w(items, win_item, ay, ax, win, D);
+    multi_window_logits_ctx16<NV, 1>(value + w.first, logits + w.it.tok0, 0, w.geom, lane, scale, ctx16 + (long)win * D, 0);
 }
 
 // ---- 4: segmented global stream, one workgroup per work unit (one row group: the item's nh rows) ----
@@ -152,6 +167,7 @@ int ragged_prepare(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
 struct RaggedItems {
     const hicom_compressor_ragged_args* a;
     const RaggedLayout& l;
+    const float* logits;        // the logits form: f32 [sum N_i], no key row is read; NULL: the keyed forms
     char* ws() const { return (char*)a->ws; }
     hipStream_t s() const { return (hipStream_t)a->stream; }
     const RaggedItem* items() const { return (const RaggedItem*)(ws() + l.items); }
@@ -159,7 +175,10 @@ struct RaggedItems {
     int local(const uint16_t* key_x, const SegAdaptParams* ad) const {
         const long windows = l.s.n.windows;
         const RaggedAxes g = ragged_axes(a);
-        if (ad)
+        if (logits)
+            HICOM_LAUNCH(ragged_local_logits_kernel<3>, dim3((unsigned)((windows + 3) / 4)), dim3(256), 0, s(), (const uint16_t*)a->ff, logits, items(),
+                         (const int*)(ws() + l.win_item), g.ay, g.ax, (int)windows, a->l_scale, (_Float16*)(ws() + l.s.ctx16));
+        else if (ad)
             HICOM_LAUNCH(ragged_local_attn_adapt_kernel<3>, dim3((unsigned)((windows + 3) / 4)), dim3(256), 0, s(), key_x, (const uint16_t*)a->ff,
                          (const uint16_t*)a->guide, *ad, items(), (const int*)(ws() + l.win_item), g.ay, g.ax, (int)windows, a->l_scale,
                          (_Float16*)(ws() + l.s.ctx16));
@@ -204,15 +223,24 @@ struct RaggedItems {
     }
 };
 
-int ragged_fwd(const hicom_compressor_ragged_args* a, const SegAdapt* ad) {
+// logits: the logits form (plain recipe only): launch 3 is ragged_local_logits_kernel, a->fe is not looked at
+int ragged_fwd_form(const hicom_compressor_ragged_args* a, const SegAdapt* ad, const float* logits) {
     HICOM_TRY(ragged_check(a, ad));
+    hicom_compressor_ragged_args keyless;
+    if (logits) {
+        keyless = *a;
+        keyless.fe = nullptr;
+        a = &keyless;
+    }
     const RaggedLayout l = ragged_layout(a, ad);
     HICOM_TRY(seg_check_fwd(kWho, a, ad, l.s.total));
     HICOM_REQUIRE(a->ldo >= a->hidden, HICOM_EINVAL, "compressor_ragged: output layout");
     for (int i = 0; i < a->B; ++i)
         HICOM_REQUIRE(a->items[i].nl_count == 0 || a->newline, HICOM_EINVAL, "compressor_ragged: item %d has newline rows and there is no newline token", i);
-    return seg_step(a, ad, l.s, RaggedItems{a, l});
+    return seg_step(a, ad, l.s, RaggedItems{a, l, logits});
 }
+
+int ragged_fwd(const hicom_compressor_ragged_args* a, const SegAdapt* ad) { return ragged_fwd_form(a, ad, nullptr); }
 
 }  // namespace
 
@@ -221,6 +249,13 @@ extern "C" int64_t hicom_compressor_ragged_workspace_bytes(const hicom_compresso
 extern "C" int hicom_compressor_ragged_prepare(const hicom_compressor_ragged_args* a) { return ragged_prepare(a, nullptr); }
 
 extern "C" int hicom_compressor_ragged_fwd(const hicom_compressor_ragged_args* a) { return ragged_fwd(a, nullptr); }
+
+// The logits form: a->fe is not read (the plan, the workspace, its size function and the prepare call are the keyed step's).
+extern "C" int hicom_compressor_ragged_logits_fwd(const hicom_compressor_ragged_args* a, const float* local_logits) {
+    HICOM_REQUIRE(a, HICOM_EINVAL, "%s: NULL arguments", kWho);
+    HICOM_REQUIRE(local_logits && (uintptr_t)local_logits % 4 == 0, HICOM_EINVAL, "%s: local_logits is f32 [sum T_i H W]", kWho);
+    return ragged_fwd_form(a, nullptr, local_logits);
+}
 
 // ---- the adaptor recipe: the same step with the k / v adaptors on the local stage; the table region is the plain one ----------------
 extern "C" int64_t hicom_compressor_ragged_adapt_workspace_bytes(const hicom_compressor_ragged_adapt_args* a) { return seg_with_adapt(kWho, a, ragged_workspace_bytes); }

@@ -7,6 +7,9 @@
 // Input gradients (stage 3): hicom_compressor_ragged_local_bwd is the window backward over the concatenated window list (window_rows.hpp:
 // local_window_bwd, the body of local_attn_bwd_kernel) with dq summed per item in a fixed order, hicom_compressor_ragged_global_dx the global
 // stage's d x with an item per workgroup (global_dx.hpp: global_dx_tile, the body of global_dx_kernel).
+// The logits form (the forward took the local scores precomputed: ragged.hip, hicom_compressor_ragged_logits_fwd):
+// hicom_compressor_ragged_local_logits_bwd, one wave per window on the row helpers of window_rows.hpp: d local_logits and the value-side
+// share of d frames_feature, no dq.
 // The adaptor recipe's training step: hicom_compressor_ragged_local_adapt_bwd (window_rows.hpp: local_window_adapt_bwd, the body of
 // local_attn_adapt_bwd_kernel), hicom_compressor_ragged_adapt_dy (adapt_dy_token, the body of adapt_dy_kernel; the token's item by a search
 // of the item table), hicom_compressor_ragged_dq_item and hicom_compressor_ragged_adapt_train_state (the y planes out of the workspace).
@@ -134,6 +137,66 @@ __global__ __launch_bounds__(256) void ragged_dq_item_kernel(const float* dq, co
         __syncthreads();
     }
     if (stripe == 0 && c < E) *reinterpret_cast<float4*>(dq_item + (long)item * E + c) = red[0][lane];
+}
+
+// ---- the logits form: the window backward where the forward took its scores precomputed, l_n = key_n . guide_item as f32
+// [sum N_i].  One wave per window, four windows per workgroup -- the forward's wave -> window -> item map (ragged_local_logits_kernel).
+// Lane i holds token i of the window: p = softmax(scale l) as the forward forms it, then ONE walk over the window's value rows:
+//     dp_i = dctx . v_i (a wave sum, kept by lane i),   dvalue_i = p_i dctx (bf16 row, or not written with dvalue NULL)
+// and behind it  dl_i = scale p_i (dp_i - sum_j p_j dp_j).  No key row, no guide row, no dq: the guide does not enter the local stage.
+// Every sum is a fixed-order wave reduction or one lane's chain; every token lies in one window, so dl and dvalue are plain stores ----
+struct RaggedLocalLogitsBwdParams {
+    const uint16_t* value;  // [sum N_i][D]
+    const float* logits;    // [sum N_i]
+    const RaggedItem* items;
+    const int* win_item;
+    hicom_axis ay, ax;
+    int nwin;
+    float scale;
+    const float* dctx;      // [sum windows][D]
+    float* dlogits;         // [sum N_i]
+    uint16_t* dvalue;       // bf16 [sum N_i][D] or NULL
+};
+
+template <int NV>
+__global__ __launch_bounds__(256) void ragged_local_logits_bwd_kernel(RaggedLocalLogitsBwdParams p) {
+    constexpr int D = NV * 384;
+    const int lane = threadIdx.x & 63;
+    const int win = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (win >= p.nwin) return;
+    const RaggedWindow w(p.items, p.win_item, p.ay, p.ax, win, D);
+    const WindowGeom& g = w.geom;
+    const bool live = lane < g.WIN;
+    const long mine = w.it.tok0 + g.token_of(live ? lane : 0);
+    const float sc = live ? p.logits[mine] * p.scale : -3.0e38f;
+    const float mx = wave_max_fast(sc);
+    const float e = live ? expf(sc - mx) : 0.f;
+    const float pw = e / wave_sum_fast(e);
+    float dc[NV][6];
+    load_row_f32<NV>(p.dctx + (long)win * D, lane, dc);
+    const uint16_t* value = p.value + w.first;
+    uint16_t* dvalue = p.dvalue ? p.dvalue + w.first : nullptr;
+    float dp = 0.f;
+    for (int i0 = 0; i0 < g.WIN; i0 += 2) {          // two value rows in flight
+        float v[2][NV][6];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+            if (i0 + u < g.WIN) load_row<NV>(value + g.token_of(i0 + u) * D, lane, v[u]);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = i0 + u;
+            if (i < g.WIN) {
+                const float d = wave_sum_fast(row_dot<NV>(dc, v[u]));
+                if (lane == i) dp = d;
+                if (dvalue) {
+                    const float pi_ = __shfl(pw, i, 64);
+                    store_row_bf16<NV>(dvalue + g.token_of(i) * D, lane, false, [&](int s, int j) { return pi_ * dc[s][j]; });
+                }
+            }
+        }
+    }
+    const float delta = wave_sum_fast(pw * dp);      // (lanes >= WIN: pw = 0, dp = 0)
+    if (live) p.dlogits[mine] = p.scale * pw * (dp - delta);
 }
 
 // ---- the adaptor recipe: the window backward through the LayerNorm blends over the concatenated window list, one 4-wave workgroup per
@@ -430,6 +493,27 @@ extern "C" int hicom_compressor_ragged_global_dx(const hicom_compressor_ragged_a
     if (a->nh <= 9) HICOM_LAUNCH(ragged_global_dx_kernel<9>, dim3((unsigned)ntiles), dim3(320), 0, s, p);
     else HICOM_LAUNCH(ragged_global_dx_kernel<16>, dim3((unsigned)ntiles), dim3(320), 0, s, p);
     return seg_check_launch(who, "global dx");
+}
+
+// ---- the logits form (forward_ragged_train(local_logits=), input_grads=True): d local_logits and the value-side share of d frames_feature ----
+extern "C" int hicom_compressor_ragged_local_logits_bwd(const hicom_compressor_ragged_args* a, const void* value, const float* local_logits, const float* dctx,
+                                                        float* dlogits, void* dvalue) {
+    constexpr const char* who = "compressor_ragged_local_logits_bwd";
+    HICOM_TRY(ragged_check(a, nullptr));
+    HICOM_REQUIRE(value && local_logits && dctx && dlogits, HICOM_EINVAL, "%s: NULL pointer", who);
+    HICOM_REQUIRE((uintptr_t)value % 4 == 0 && (uintptr_t)local_logits % 4 == 0 && (uintptr_t)dctx % 16 == 0 && (uintptr_t)dlogits % 4 == 0 &&
+                      (uintptr_t)dvalue % 4 == 0, HICOM_EINVAL, "%s: aligned pointers", who);
+    HICOM_REQUIRE(dlogits != local_logits, HICOM_EINVAL, "%s: d local_logits cannot overwrite the scores", who);
+    RaggedTables t;
+    HICOM_TRY(ragged_tables(who, a, nullptr, t));
+    const RaggedAxes ax = ragged_axes(a);
+    const long windows = t.l.s.n.windows;
+    RaggedLocalLogitsBwdParams p;
+    p.value = (const uint16_t*)value; p.logits = local_logits;
+    p.items = t.items; p.win_item = t.win_item; p.ay = ax.ay; p.ax = ax.ax; p.nwin = (int)windows;
+    p.scale = a->l_scale; p.dctx = dctx; p.dlogits = dlogits; p.dvalue = (uint16_t*)dvalue;
+    HICOM_LAUNCH(ragged_local_logits_bwd_kernel<3>, dim3((unsigned)((windows + 3) / 4)), dim3(256), 0, (hipStream_t)a->stream, p);   // (E == 1152: ragged_check)
+    return seg_check_launch(who, "window backward");
 }
 
 // ---- the adaptor recipe (hicom_amd/ragged_train.py, adaptors=True) ---------------------------------------------------------------------------

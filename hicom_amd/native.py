@@ -436,6 +436,8 @@ SIGNATURES = {
                                                           vp, vp, vp, vp]),
     "hicom_compressor_ragged_adapt_dy": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, i32, i32, vp, vp, i32, f32, vp, vp, vp, i32]),
     "hicom_compressor_ragged_dq_item": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp]),
+    "hicom_compressor_ragged_logits_fwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp]),
+    "hicom_compressor_ragged_local_logits_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -900,6 +902,20 @@ def compressor_ragged_dq_item(args: CompressorRaggedArgs, dq, dq_item):
     """dq_item [B, E] = the rows of dq [windows, E] summed per item of a ragged plan (hicom_compressor_ragged_dq_item)."""
     assert dq.dtype == dq_item.dtype == torch.float32
     _ragged_train_call("dq_item", args, dq, dq_item)
+
+
+def compressor_ragged_logits_fwd(args: CompressorRaggedArgs, local_logits):
+    """The ragged step with the local scores given, f32 [sum T_i, H, W] (hicom_compressor_ragged_logits_fwd); args.fe is not read."""
+    assert local_logits.dtype == torch.float32
+    _ragged_train_call("logits_fwd", args, local_logits)
+
+
+def compressor_ragged_local_logits_bwd(args: CompressorRaggedArgs, value, local_logits, dctx, dlogits, dvalue=None):
+    """The window backward of the logits form over all items of a ragged plan (hicom_compressor_ragged_local_logits_bwd): fills dlogits f32
+    [tokens] and, where given, dvalue bf16 [tokens, E] (the value-side share of d frames_feature)."""
+    assert value.dtype == torch.bfloat16 and local_logits.dtype == dctx.dtype == dlogits.dtype == torch.float32
+    assert dvalue is None or dvalue.dtype == torch.bfloat16
+    _ragged_train_call("local_logits_bwd", args, value, local_logits, dctx, dlogits, dvalue)
 
 
 def compressor_multiguide_workspace(args) -> int:

@@ -1093,7 +1093,7 @@ class HIComProjector(nn.Module):
         from . import batch
         return batch.run_batch(self, frames_feature, frames_embed, guide_embeds, modal, image_newline, chunks)
 
-    def forward_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None):
+    def forward_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None, local_logits=None):
         """B items of UNEQUAL length and mixed modality in one native call: frames_feature / frames_embed bf16 [sum T_i, H, W, E], the
         stacked tensor of reference hicom_arch.py:159-164 before `.split` (read in place; frames_embed may be None), guide_embeds bf16
         [B, E], split_sizes the B frame counts T_i, modals "image" / "video" as one string or one per item.  H and W are common to the
@@ -1106,12 +1106,17 @@ class HIComProjector(nn.Module):
         `chunks`: work units per item of the segmented global stream, each clamped to the item's 16-token tiles (None: every item gets
         its share of 2 x #CUs units by token count).
         Not timed yet (tools/ragged_bench.py).  It is the twelve launches of forward_batch, so its ~180 us floor is to
-        be expected here too: one to three small items are probably faster through a loop of forward()."""
+        be expected here too: one to three small items are probably faster through a loop of forward().
+        `local_logits` = fp32 [sum T_i, H, W] raw dot products frames_embed_n . guide of the token's item from
+        `hicom_amd.siglip_head_scores_ragged(..., guide_counts=(1,) * B)` (its [1, sum T_i, H, W] result is taken as it is), passed with
+        frames_embed=None (the rule of forward(..., local_logits=)): the local stage then reads frames_feature and one float per token,
+        frames_embed is never made, and the head's second GEMM is not run.  The plain recipe only (the adaptor recipe's
+        score is not linear in frames_embed: NotImplementedError).  The global rows do not change."""
         from . import ragged
-        return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks)
+        return ragged.run_ragged(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks, local_logits)
 
     def forward_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline=None, *, chunks=None,
-                             input_grads=False, adaptors=False):
+                             input_grads=False, adaptors=False, local_logits=None):
         """forward_ragged under autograd: the training step of a mixed batch (reference hicom_arch.py:146-180 with the projector trainable,
         train.py:709-713) in one forward call and ONE backward over all items.  Arguments, scope checks, plan cache and return value are
         forward_ragged's (a uniform batch is split_sizes = (T,) * B on the 4-D view), the outputs are bit-equal to it, and they carry a
@@ -1129,10 +1134,19 @@ class HIComProjector(nn.Module):
         §3.23): the forward is forward_ragged's adaptor call (bit-equal outputs), the backward runs the window backward through the LayerNorm
         blends over all items in one launch and the adaptor MLPs' backward once over the stacked [sum N_i, E] tokens, and composes with
         input_grads.  The node keeps the adaptors' fp16 outputs (2 E bytes per token and adapted stream).  On a plain module the keyword
-        changes nothing; with the default False the adaptor recipe is refused as before."""
+        changes nothing; with the default False the adaptor recipe is refused as before.
+        `local_logits` (the plain recipe, frames_embed=None): the local scores of forward_ragged(local_logits=) in the place
+        of frames_embed.  With the head frozen (stages 1 and 2) the forward runs without frames_embed and the backward is the one of the
+        keyed step, with no further launch: there the window backward never runs.  With `input_grads=True` every one of frames_feature,
+        guide_embeds and local_logits that requires grad gets its gradient from the same one backward, d local_logits as fp32 in the
+        tensor's own shape from one more launch over all windows.  d guide_embeds is then the GLOBAL share only: the local share flows
+        through the scores into the caller's graph (the scores are a function of the guide there), where autograd adds it.
+        local_logits.requires_grad without input_grads=True raises like the other inputs; the k / v adaptor recipe refuses local_logits
+        (NotImplementedError: its score is not linear in frames_embed).  The parameter gradients are bit-equal to those of the same step
+        with the inputs detached."""
         from . import ragged_train
         return ragged_train.run_ragged_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, modals, image_newline, chunks,
-                                             input_grads, adaptors)
+                                             input_grads, adaptors, local_logits)
 
     def forward_multi_guide(self, frames_feature, frames_embed, guide_embeds, modal, image_newline=None, *, chunks=None, local_logits=None):
         """ONE image or clip, Q instructions in one native call: frames_feature / frames_embed bf16 [T, H, W, E] as for forward()

@@ -6,6 +6,10 @@ stacked tensor is read in place by ONE C call and the twelve launches of the bat
 whatever B and the mix are.  Scope, plan and plan cache are segments.py's, shared with forward_batch.  Plans are keyed by (split_sizes,
 modals, grid, ...); a ragged plan also holds the host item descriptors, and the head of its workspace holds the device tables.
 
+Logits form: with `local_logits` = fp32 [sum T_i, H, W] from `siglip_head_scores_ragged` (one guide per item) the local
+stage takes its scores from it and reads value rows only (hicom_compressor_ragged_logits_fwd); frames_embed is None, the plan is the one of
+the call without frames_embed.
+
 `plan_tables` restates the table arithmetic of hicom_compressor_ragged_prepare in Python: forward_ragged takes the items' row counts
 from it, and the tests hold the device's table region against it."""
 from __future__ import annotations
@@ -182,10 +186,38 @@ def _build(proj, H, W, E, split_sizes, modals, nl, out_dtype, chunks, dev, strea
     return plan
 
 
-def call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, what="forward_ragged", refuse_grad=True):
+NOT_LINEAR = ("local_logits has no form on the k / v adaptor recipe: the keys pass an MLP and a LayerNorm blend in front of the score, so it is "
+              "not linear in frames_embed; pass frames_embed")
+
+
+def check_logits(what, proj, ll, fe, ff):
+    """The checks of local_logits behind the scope checks of the keyed call and in front of any device work: frames_embed must be None (the
+    rule of forward(..., local_logits=)), the plain recipe, fp32 device [sum T_i, H, W] -- or [1, sum T_i, H, W], what
+    siglip_head_scores_ragged returns for one guide per item.  Returns the [sum T_i, H, W] view."""
+    from .multi_guide import _require_f32_cuda
+    if fe is not None:
+        raise ValueError(f"{what}: local_logits replaces frames_embed: pass frames_embed=None")
+    if seg.seg_recipe(proj) != "plain":
+        raise NotImplementedError(f"{what}: {NOT_LINEAR}")
+    want = tuple(ff.shape[:3])
+    if not isinstance(ll, torch.Tensor) or tuple(ll.shape) not in (want, (1,) + want):
+        raise ValueError(f"{what}: local_logits is [sum T_i, H, W] = [{', '.join(map(str, want))}] (or [1, sum T_i, H, W], as siglip_head_scores_ragged "
+                         f"returns it for one guide per item), the raw dot products frames_embed_n . guide of the token's item "
+                         f"(got {tuple(ll.shape) if isinstance(ll, torch.Tensor) else None})")
+    _require_f32_cuda("local_logits", ll)
+    return ll.view(want) if ll.is_contiguous() else ll.reshape(want)
+
+
+def call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, what="forward_ragged", refuse_grad=True, local_logits=None):
     """The one C call of forward_ragged and of forward_ragged_train (ragged_train.py: refuse_grad False): returns (the [sum rows_i,
-    hidden] output, the plan, the contiguous frames_feature and guides the call read)."""
+    hidden] output, the plan, the contiguous frames_feature and guides the call read).  local_logits (frames_embed None):
+    the logits form of the call, on the plan of the call without frames_embed."""
     B, H, W, E, split_sizes, modals = _scope(proj, ff, fe, guides, split_sizes, modals, nl, what)
+    if local_logits is not None:
+        local_logits = check_logits(what, proj, local_logits, fe, ff)
+        if refuse_grad and local_logits.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{what} builds no autograd graph: local_logits requires grad (compute it under torch.no_grad(), or train through "
+                               "forward_ragged_train(local_logits=))")
     dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, what, ff, fe, guides, nl, refuse_grad=refuse_grad)
     key = (split_sizes, modals, H, W, E, fe is not None, None if nl is None else tuple(nl.shape), out_dtype, stream, int(chunks or 0),
            seg.seg_recipe(proj), proj.local_compressor.adapt_k, proj.local_compressor.adapt_v)
@@ -193,10 +225,13 @@ def call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, what
     a = plan.io
     out = torch.empty((sum(plan.rows), plan.hidden), dtype=out_dtype, device=dev)
     seg.patch_io(a, ff, fe, guides, nl, out, stream)         # (the newline pointer whenever given: items differ in their newline rows)
-    nv.compressor_ragged_fwd(plan.args)
+    if local_logits is not None:
+        nv.compressor_ragged_logits_fwd(plan.io, local_logits.detach().contiguous())
+    else:
+        nv.compressor_ragged_fwd(plan.args)
     return out, plan, ff, guides
 
 
-def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None):
-    out, plan, _, _ = call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks)
+def run_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, local_logits=None):
+    out, plan, _, _ = call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, local_logits=local_logits)
     return list(out.split(plan.rows))

@@ -37,6 +37,12 @@ The local stage of the backward is then
   input gradients  d frames_embed = d_kx, d frames_feature = d_vx (+ d_kx without frames_embed) and then the global share as above,
                    d guide's local share = hicom_compressor_ragged_dq_item of dq = (1 - a_k) sxk + a_k gamma_k syk.
 
+The logits form (`local_logits=`; the plain recipe, frames_embed None): the forward is hicom_compressor_ragged_logits_fwd, the
+local scores given in the place of frames_embed.  A parameters-only step (stages 1 and 2: the head is frozen) has the backward above with no
+further launch.  With input_grads=True the local stage of the backward is ONE launch, hicom_compressor_ragged_local_logits_bwd: d local_logits
+(fp32) and the value-side share of d frames_feature; there is no dq, so d guide_embeds is the global share alone -- the local share flows
+through the scores into the caller's graph.  The node keeps the scores by reference only where that launch will run.
+
 Frozen adaptors with no input gradient asked for: neither the window call nor the MLP backward runs, and no y plane is kept.
 
 Scope: the two release recipes `local43_global32` and, with adaptors=True, `local43_adaptkv_global32` (use_guide="direct", no other
@@ -58,7 +64,7 @@ WHAT = "forward_ragged_train"
 _LOOP = "run the loop of forward() per item instead"
 
 
-def check_scope(proj, ff, fe, guides, input_grads=False, adaptors=False):
+def check_scope(proj, ff, fe, guides, input_grads=False, adaptors=False, local_logits=None):
     """The refusals of forward_ragged_train that forward_ragged does not make; no device is touched."""
     if isinstance(ff, dict) or isinstance(fe, dict):
         raise NotImplementedError(f"{WHAT}: anyres dict inputs have no ragged training step; {_LOOP}")
@@ -71,7 +77,11 @@ def check_scope(proj, ff, fe, guides, input_grads=False, adaptors=False):
     if recipe is None:
         raise NotImplementedError(f"{WHAT} is built for the release recipes local43_global32 and (adaptors=True) local43_adaptkv_global32 only "
                                   f"(local + global compressor, use_guide='direct', no adaptors but adapt_k / adapt_v, no clip scale); {_LOOP}")
-    for name, t in (("frames_feature", ff), ("frames_embed", fe), ("guide_embeds", guides)):
+    if local_logits is not None and fe is not None:
+        raise ValueError(f"{WHAT}: local_logits replaces frames_embed: pass frames_embed=None")
+    if local_logits is not None and recipe != "plain":
+        raise NotImplementedError(f"{WHAT}: {ragged.NOT_LINEAR}")
+    for name, t in (("frames_feature", ff), ("frames_embed", fe), ("guide_embeds", guides), ("local_logits", local_logits)):
         if not input_grads and isinstance(t, torch.Tensor) and t.requires_grad:
             raise NotImplementedError(f"{WHAT}: the gradient w.r.t. {name} (stage 3) is not built for the ragged training step without "
                                       f"input_grads=True; pass it, detach {name}, or {_LOOP}")
@@ -101,17 +111,20 @@ def _adaptor_wanted(names):
 
 class _RaggedTrainFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, proj, ff, fe, guides, nl, meta, names, *params):
+    def forward(ctx, proj, ff, fe, guides, nl, ll, meta, names, *params):
         split_sizes, modals, chunks, rows = meta
         with torch.no_grad():
-            out, plan, x, g = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
+            out, plan, x, g = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False, local_logits=ll)
             t, a, dev = plan.tables, plan.io, x.device
             plan.train = plan.train or _PlanTrain(plan, dev)
             # frames_embed, by reference, only where the window backward will run (an input gradient is asked for, or an adaptor trains)
             lc = proj.local_compressor
             adapt = lc.adapt_k or lc.adapt_v
-            window = any(ctx.needs_input_grad[1:4]) or (adapt and _adaptor_wanted(n for k, n in enumerate(names) if ctx.needs_input_grad[7 + k]))
+            window = any(ctx.needs_input_grad[1:4]) or (adapt and _adaptor_wanted(n for k, n in enumerate(names) if ctx.needs_input_grad[8 + k]))
             keys = fe.contiguous() if (fe is not None and window) else None
+            # the logits form: the scores, by reference, only where its window backward will run (d frames_feature or d local_logits)
+            needs_scores = ll is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[5])
+            lsaved = ll.detach().reshape(x.shape[:3]).contiguous() if needs_scores else None
             R, E = a.B * a.nh, a.E
             f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
             ctx16 = torch.empty((sum(t.windows), E), dtype=torch.float16, device=dev)
@@ -126,16 +139,18 @@ class _RaggedTrainFn(torch.autograd.Function):
         rows.extend(plan.rows)                                 # (for the caller: how to split the output)
         ctx.proj, ctx.plan, ctx.names = proj, plan, names
         ctx.nl_meta = None if nl is None else nl.dtype
-        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg, keys, ky, vy)
+        ctx.logits_form, ctx.ll_shape = ll is not None, None if ll is None else ll.shape
+        ctx.save_for_backward(x, g, ctx16, scores, ml, ctxg, keys, ky, vy, lsaved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, guides, ctx16, scores, ml, ctxg, keys, ky, vy = ctx.saved_tensors
+        x, guides, ctx16, scores, ml, ctxg, keys, ky, vy, ll = ctx.saved_tensors
         proj, plan, names = ctx.proj, ctx.plan, ctx.names
-        need = ctx.needs_input_grad            # (proj, ff, fe, guides, nl, meta, names, *params)
-        want = {n for k, n in enumerate(names) if need[7 + k]}
-        inputs = types.SimpleNamespace(want_ff=bool(need[1]), want_fe=bool(need[2]), want_guide=bool(need[3]), fe=keys, d_ff=None, d_fe=None, d_guide=None)
+        need = ctx.needs_input_grad            # (proj, ff, fe, guides, nl, ll, meta, names, *params)
+        want = {n for k, n in enumerate(names) if need[8 + k]}
+        inputs = types.SimpleNamespace(want_ff=bool(need[1]), want_fe=bool(need[2]), want_guide=bool(need[3]), fe=keys, d_ff=None, d_fe=None, d_guide=None,
+                                       logits_form=ctx.logits_form, ll=ll, want_ll=bool(need[5]), d_ll=None)
         with torch.no_grad():
             grads, d_nl = ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, bool(need[4]), inputs, adapt=(ky, vy))
         ag.LAST_FP32_GRADS = dict(grads)               # (test hook, as the single-item backward leaves it; here with d image_newline)
@@ -157,7 +172,8 @@ class _RaggedTrainFn(torch.autograd.Function):
                 cnt = plist[n].numel()
                 out[k] = flat[o:o + cnt].view(plist[n].shape)
                 o += cnt
-        return (None, inputs.d_ff, inputs.d_fe, d_g, None if d_nl is None else d_nl.to(ctx.nl_meta), None, None, *out)
+        d_ll = None if inputs.d_ll is None else inputs.d_ll.view(ctx.ll_shape)
+        return (None, inputs.d_ff, inputs.d_fe, d_g, None if d_nl is None else d_nl.to(ctx.nl_meta), d_ll, None, None, *out)
 
 
 def _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, ky, vy, want_kx, want_vx, want_guide):
@@ -189,13 +205,21 @@ def _local_backward(st, ctx16, dout, local_rows, window, adapt):
     lc, plan, x, guides, inputs, f32 = st.proj.local_compressor, st.plan, st.ff, st.guides, st.inputs, st.f32
     a, fe, L = plan.io, inputs.fe, "local_compressor.readout."
     adaptors = lc.adapt_k or lc.adapt_v
-    assert adaptors or ag._window_backward_runs(lc, st.want_fe, st.want_guide, st.proj.local_logit, st.want_ff) == window
+    assert adaptors or inputs.logits_form or ag._window_backward_runs(lc, st.want_fe, st.want_guide, st.proj.local_logit, st.want_ff) == window
     ctx_l = ctx16.float()
     W0, b0 = f32[L + "0.weight"], f32[L + "0.bias"]
     dpre = ag._readout_backward(ctx_l, torch.addmm(b0, ctx_l, W0.t()), f32[L + "2.weight"], dout[local_rows], L, st.grads)
     if not window:
         return None
     dctx_l = (dpre @ W0).contiguous()
+    if inputs.logits_form:
+        # the scores were given: d local_logits and the value-side share of d frames_feature from one launch; the guide does not enter this stage
+        inputs.d_ll = torch.empty_like(inputs.ll)
+        inputs.d_ff = torch.empty_like(x) if st.want_ff else None
+        nv.compressor_ragged_local_logits_bwd(a, x, inputs.ll, dctx_l, inputs.d_ll, inputs.d_ff)
+        if not inputs.want_ll:
+            inputs.d_ll = None
+        return None
     dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=st.dev) if st.want_guide else None
     if adaptors:
         dq_w, d_kx, d_vx = _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, *adapt, st.want_fe or (st.want_ff and fe is None), st.want_ff, st.want_guide)
@@ -239,7 +263,8 @@ def _global_backward(st, scores, ml, ctxg, dout, glob_rows, dq_item):
         nv.compressor_ragged_global_dx(a, scores, ds, ml, qt_, dctx, plan.train.dx_tiles, inputs.d_ff.view(-1, E), accumulate=True)
     if st.want_guide:
         # direct recipe: the injected query IS the guide, one row per item (autograd._global_query_backward) + the local stage's share
-        inputs.d_guide = dq_item + (dqp @ Wq + dpre_g)
+        glob = dqp @ Wq + dpre_g
+        inputs.d_guide = glob if dq_item is None else dq_item + glob       # (the logits form: the global share only)
 
 
 def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, want_nl, inputs, adapt=(None, None)):
@@ -257,6 +282,8 @@ def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, 
     d_nl = dout[nl_rows].sum(0) if (want_nl and nl_rows.numel()) else None
     # the window backward: every input gradient has a local share; with adaptors, also where one of them trains
     window = st.want_ff or st.want_fe or st.want_guide or ((lc.adapt_k or lc.adapt_v) and _adaptor_wanted(want))
+    if inputs.logits_form:                                     # the guide has no local share there; the scores have
+        window = st.want_ff or inputs.want_ll
     dq_item = None
     if window or any(n.startswith("local_compressor.") for n in want):
         dq_item = _local_backward(st, ctx16, dout, local_rows, window, adapt)
@@ -265,17 +292,20 @@ def ragged_backward(proj, plan, x, guides, ctx16, scores, ml, ctxg, dout, want, 
     return st.grads, d_nl
 
 
-def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, input_grads=False, adaptors=False):
-    check_scope(proj, ff, fe, guides, input_grads, adaptors)
+def run_ragged_train(proj, ff, fe, guides, split_sizes, modals, nl, chunks=None, input_grads=False, adaptors=False, local_logits=None):
+    check_scope(proj, ff, fe, guides, input_grads, adaptors, local_logits)
+    if local_logits is not None:                               # shape, dtype and device in front of any device work
+        ragged._scope(proj, ff, fe, guides, split_sizes, modals, nl, WHAT)
+        ragged.check_logits(WHAT, proj, local_logits, fe, ff)
     params = [(n, p) for n, p in proj.named_parameters()]
     trainable = torch.is_grad_enabled() and (any(p.requires_grad for _, p in params) or (isinstance(nl, torch.Tensor) and nl.requires_grad)
-                                             or (input_grads and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (ff, fe, guides))))
+                                             or (input_grads and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (ff, fe, guides, local_logits))))
     if not trainable:                                          # nothing to differentiate: forward_ragged's call, no graph
         nv.begin_inference()
-        out, plan, _, _ = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False)
+        out, plan, _, _ = ragged.call_ragged(proj, ff, fe, guides, split_sizes, modals, nl, chunks, what=WHAT, refuse_grad=False, local_logits=local_logits)
         return list(out.split(plan.rows))
     nv.note_training_forward()                                 # (the plan's refresh() then rebuilds the weight-derived tables from the live weights)
     names, ps = zip(*params)
     rows = []
-    out = _RaggedTrainFn.apply(proj, ff, fe, guides, nl, (split_sizes, modals, chunks, rows), names, *ps)
+    out = _RaggedTrainFn.apply(proj, ff, fe, guides, nl, local_logits, (split_sizes, modals, chunks, rows), names, *ps)
     return list(out.split(rows))

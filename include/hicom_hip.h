@@ -1667,6 +1667,25 @@ int hicom_compressor_stream_push_logits(const hicom_stream_push_args* args, cons
 int hicom_compressor_stream_push_multi_logits(const hicom_stream_push_multi_args* args, const float* local_logits, int64_t q_stride);
 int hicom_compressor_stream_group_multi_push_logits(const hicom_stream_group_multi_push_args* args, const float* local_logits, int64_t q_stride);
 
+/* ---- ragged step and its training step without frames_embed: local scores given ---------------------------------------------
+ * One guide per item.  local_logits f32 [sum T_i H W]: the raw dot products frames_embed[n] . guide_item in front of l_scale, token n of item
+ * i at tok0_i + n (plane 0 of what hicom_head_scores_ragged_fwd writes with one guide per item).  Plain recipe only.
+ *
+ * hicom_compressor_ragged_logits_fwd is hicom_compressor_ragged_fwd with the local stage taking its scores from local_logits: the same launch
+ * count, the same workspace, size function and prepare call; args->fe is not read and may be NULL or stale; only value rows are read by the
+ * local stage.  hicom_compressor_ragged_train_state works unchanged behind it.
+ *
+ * hicom_compressor_ragged_local_logits_bwd: the window backward of that local stage over the concatenated window list, one launch, one wave
+ * per window.  Per window, p = softmax(l_scale l) over its tokens, dp_n = dctx_w . value_n:
+ *   dlogits f32 [sum T_i H W]:  l_scale p_n (dp_n - sum_m p_m dp_m)
+ *   dvalue  bf16 [sum T_i H W, E] or NULL:  p_n dctx_w, the value-side share of d frames_feature (hicom_compressor_ragged_global_dx adds the
+ *           global share with accumulate = 1)
+ * Every token lies in exactly one window: plain stores, fixed summation orders, no atomics.  There is no dq: the guide does not enter the
+ * local stage.  value bf16 [sum T_i H W, E], dctx f32 [sum w_i, E] (16-byte aligned).  It reads only the table region of args->ws. */
+int hicom_compressor_ragged_logits_fwd(const hicom_compressor_ragged_args* args, const float* local_logits);
+int hicom_compressor_ragged_local_logits_bwd(const hicom_compressor_ragged_args* args, const void* value, const float* local_logits, const float* dctx,
+                                             float* dlogits, void* dvalue);
+
 #ifdef __cplusplus
 }
 #endif
