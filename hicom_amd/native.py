@@ -438,6 +438,9 @@ SIGNATURES = {
     "hicom_compressor_ragged_dq_item": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp]),
     "hicom_compressor_ragged_logits_fwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp]),
     "hicom_compressor_ragged_local_logits_bwd": (C.c_int, [C.POINTER(CompressorRaggedArgs), vp, vp, vp, vp, vp]),
+    "hicom_compressor_ragged_multiguide_train_state": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp, vp, vp]),
+    "hicom_compressor_ragged_multiguide_global_bwd_workspace_bytes": (i64, [C.POINTER(CompressorRaggedMultiGuideArgs)]),
+    "hicom_compressor_ragged_multiguide_global_bwd": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp, vp, vp, vp, vp, vp, vp, i64]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -1030,6 +1033,22 @@ def compressor_ragged_multiguide_prepare(args: CompressorRaggedMultiGuideArgs):
 
 def compressor_ragged_multiguide_fwd(args: CompressorRaggedMultiGuideArgs):
     _seg_call(args, "ragged_multiguide", "fwd")
+
+
+def compressor_ragged_multiguide_train_state(args: CompressorRaggedMultiGuideArgs, ctx16, scores, ml, ctxg):
+    """What a backward of the call just made reads, out of the plan's workspace into tensors of the caller's, pair-major
+    (hicom_compressor_ragged_multiguide_train_state)."""
+    _ragged_train_call("multiguide_train_state", args, ctx16, scores, ml, ctxg)
+
+
+def compressor_ragged_multiguide_global_bwd_workspace(args: CompressorRaggedMultiGuideArgs) -> int:
+    return _ragged_train_call("multiguide_global_bwd_workspace_bytes", args)
+
+
+def compressor_ragged_multiguide_global_bwd(args: CompressorRaggedMultiGuideArgs, x, dctx, delta, scores, ml, ds, dqt, ws):
+    """The global stage's attention backward over all (item, guide) pairs of a ragged multi-guide plan
+    (hicom_compressor_ragged_multiguide_global_bwd): fills ds and dqt."""
+    _ragged_train_call("multiguide_global_bwd", args, x, dctx, delta, scores, ml, ds, dqt, ws, ws.numel())
 
 
 def compressor_clips_multiguide_workspace(args: CompressorClipsMultiGuideArgs) -> int:

@@ -165,11 +165,14 @@ def plan_key(split_sizes, modals, H, W, E, has_fe, nl, out_dtype, stream, chunks
     return key + ("logits",) if logits else key
 
 
-def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None, local_logits=None):
+def call_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None, local_logits=None, refuse_grad=True):
+    """The one C call of forward_ragged_multi_guide and of forward_ragged_multi_guide_train (ragged_multi_guide_train.py: refuse_grad
+    False): returns (the [sum Q_i rows_i, hidden] output, the plan, the contiguous frames_feature and guides the call read)."""
     B, H, W, E, split_sizes, guide_counts, modals = check_inputs(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl)
     if local_logits is not None:
         check_logits(local_logits, fe, ff, guide_counts)
-    dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, WHAT, ff, fe, guides, nl)
+    grad_kw = {} if refuse_grad else {"refuse_grad": False}     # (the inference call is made as it always was)
+    dev, ff, fe, guides, nl, out_dtype, stream = seg.call_inputs(proj, WHAT, ff, fe, guides, nl, **grad_kw)
     key = plan_key(split_sizes, modals, H, W, E, fe is not None, nl, out_dtype, stream, chunks, seg.seg_recipe(proj), proj.local_compressor.adapt_k,
                    proj.local_compressor.adapt_v, guide_counts, local_logits is not None)
     plan = seg.cached_plan(proj, STORE, key, lambda: build_plan(proj, WHAT, H, W, E, split_sizes, guide_counts, modals, nl, out_dtype, chunks, dev,
@@ -181,4 +184,25 @@ def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, moda
         nv.compressor_ragged_multiguide_logits_fwd(plan.args, ll.data_ptr(), ff.shape[0] * H * W)
     else:
         nv.compressor_ragged_multiguide_fwd(plan.args)
+    return out, plan, ff, guides
+
+
+def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks=None, local_logits=None):
+    out, plan, _, _ = call_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, modals, nl, chunks, local_logits)
     return pair_views(plan, out)
+
+
+def train_row_maps(t):
+    """Where the rows of the pair-major packed output come from, for the backward of the call (ragged_multi_guide_train.py), from
+    plan_tables' result alone: (local, newline, glob) int64 arrays of output rows -- local[c] the row of context row c (pair p owns the
+    context rows [ctx_row0_p, + windows_i) in window order; the packing's row map: a newline gap after every nl_group local tokens),
+    newline the newline rows of all pairs, glob [M, n_global_rows] the copies of each pair's global token.  With one guide per item these
+    are ragged.train_row_maps."""
+    local, newline, glob = [], [], []
+    for i, _, _, row0 in t.pairs:
+        _, _, nl_group, nl_count, nl_first, nl_step, n_global = t.items[i]
+        m = np.arange(t.windows[i], dtype=np.int64)
+        local.append(row0 + m + (m // nl_group if nl_group else 0))
+        newline.append(row0 + nl_first + np.arange(nl_count, dtype=np.int64) * (nl_step if nl_step > 0 else 1))
+        glob.append(row0 + t.global_row0[i] + np.arange(n_global, dtype=np.int64))
+    return np.concatenate(local), np.concatenate(newline), np.stack(glob)

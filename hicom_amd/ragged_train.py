@@ -100,6 +100,9 @@ class _PlanTrain:
     # the window -> item index (plan_tables' win_item) as a device int64 tensor: the query row of a window is its item's guide
     win_item = functools.cached_property(lambda s: torch.from_numpy(s._tables.win_item.astype("int64")).to(s._dev))
     bwd_ws_bytes = functools.cached_property(lambda s: nv.compressor_ragged_global_bwd_workspace(s._io))
+    # the native attention backward of the global stage over the plan's rows (looked up per call).  ragged_backward reads row_maps,
+    # bwd_ws_bytes and global_bwd only: a plan whose rows are (item, guide) pairs brings its own three (ragged_multi_guide_train.py)
+    global_bwd = property(lambda s: nv.compressor_ragged_global_bwd)
 
 
 _ADAPTOR_PARAMS = tuple(f"local_compressor.{s}_{part}" for s in "kv" for part in ("proj.", "norm.", "alpha"))
@@ -238,7 +241,8 @@ def _local_backward(st, ctx16, dout, local_rows, window, adapt):
 
 
 def _global_backward(st, scores, ml, ctxg, dout, glob_rows, dq_item):
-    """The global stage, rows item-major: the tail, the attention backward over all items in one native call, the fold and q_proj; then the
+    """The global stage, rows item-major (pair-major where the plan's rows are (item, guide) pairs: the M guides are then the M queries): the
+    tail, the attention backward over all rows in one native call (plan.train.global_bwd), the fold and q_proj; then the
     global shares of d frames_feature (added into st.inputs.d_ff) and of d guide (st.inputs.d_guide = dq_item + it)."""
     plan, x, inputs, f32 = st.plan, st.ff, st.inputs, st.f32
     a, dev = plan.io, st.dev
@@ -249,7 +253,7 @@ def _global_backward(st, scores, ml, ctxg, dout, glob_rows, dq_item):
     dpre_g, dctx, delta = ag._global_tail_backward(st, nh, hd, ml, None, q32, dtok, ctxg=ctxg)
     ds, dqt = torch.empty_like(scores), torch.empty_like(ctxg)
     ws = torch.empty((plan.train.bwd_ws_bytes,), dtype=torch.uint8, device=dev)
-    nv.compressor_ragged_global_bwd(a, x, dctx, delta, scores, ml, ds, dqt, ws)
+    plan.train.global_bwd(a, x, dctx, delta, scores, ml, ds, dqt, ws)
     A = "global_compressor.attn_layer."
     Wq, bq, Wk = f32[A + "q_proj.weight"], f32[A + "q_proj.bias"], f32[A + "k_proj.weight"]
     dqp = ag._global_fold_backward(st, att, None, None, None, None, q32, Wq, bq, Wk, dqt=dqt)

@@ -1686,6 +1686,31 @@ int hicom_compressor_ragged_logits_fwd(const hicom_compressor_ragged_args* args,
 int hicom_compressor_ragged_local_logits_bwd(const hicom_compressor_ragged_args* args, const void* value, const float* local_logits, const float* dctx,
                                              float* dlogits, void* dvalue);
 
+/* ---- training step of the ragged multi-guide step: Q_i guides per item, one backward ---------------------------------------
+ * Behind hicom_compressor_ragged_multiguide_fwd (or _logits_fwd) on the same block.  M = sum Q_i pairs, numbered item-major then guide-major;
+ * rows are pair-major: row nh p + h is head h of pair p.  Each call reads the table region at the head of args->ws and checks its pointers,
+ * their alignment and the workspace size in front of any launch or copy.  Plain recipe only.
+ *
+ * hicom_compressor_ragged_multiguide_train_state copies out of args->ws what a backward reads:
+ *   ctx16_out  fp16 [sum Q_i windows_i, E]  the window contexts, pair-major (pair p owns windows_i rows)
+ *   scores_out f32, the scores region: item i at 16 score_off_i, [32 passes_i][ceil16(N_i)], row nh q + h of the item's row space
+ *   ml_out     f32 [M nh, 2]  (M, L) of the global softmax per (pair, head), from the partial states in the merge's own summation order
+ *   ctxg_out   f32 [M nh, E]  the merged contexts
+ *
+ * hicom_compressor_ragged_multiguide_global_bwd: the attention backward of the global stage over all pairs, four launches whatever B, the Q_i
+ * and the mix are: dctx -> bf16 hi / lo planes; pos_b = dctx pe^T; the two-row-group backward stream on the forward's work units (an
+ * item's tokens are read once per 32 folded rows); the dq merge per (pair, head).
+ *   x        bf16 [sum T_i H W, E] the tokens the forward read (16-byte aligned)
+ *   dctx     f32 [M nh, E], delta f32 [M nh] = dctx_r . ctx_r, scores / ml as train_state left them
+ *   ds_out   f32, laid out as scores (!= scores): dS; rows >= nh Q_i of an item's last pass are not written
+ *   dqt_out  f32 [M nh, E]: d of the folded queries
+ *   bws      hicom_compressor_ragged_multiguide_global_bwd_workspace_bytes(args) bytes, 256-byte aligned */
+int hicom_compressor_ragged_multiguide_train_state(const hicom_compressor_ragged_multiguide_args* args, void* ctx16_out, float* scores_out, float* ml_out,
+                                                   float* ctxg_out);
+int64_t hicom_compressor_ragged_multiguide_global_bwd_workspace_bytes(const hicom_compressor_ragged_multiguide_args* args);
+int hicom_compressor_ragged_multiguide_global_bwd(const hicom_compressor_ragged_multiguide_args* args, const void* x, const float* dctx, const float* delta,
+                                                  const float* scores, const float* ml, float* ds_out, float* dqt_out, void* bws, int64_t bws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
