@@ -741,3 +741,84 @@ def merge_vproj_ref(part_m, part_l, part_acc, rows, w_v, normalised=False, absol
         cx[:, E - 64:] = 0
     o = torch.einsum("hjc,hc->hj", wv.abs() if absolute else wv, cx).reshape(E)
     return M, L, ctx, o
+
+
+# ---- readout GEMMs (hicom_readout_gemm_fwd, hicom_planes_gemm_fwd, hicom_readout16_gemm_fwd) ---------------------------------------
+ERF_AS_ERR = 1.5e-7         # Abramowitz-Stegun 7.1.26: |erf_as7126(x) - erf(x)| <= 1.5e-7 (its stated error; gelu_erf of csrc/common.hpp)
+GELU_SLOPE = 1.13           # max |GELU'(h)| = Phi(h) + h phi(h) at h = sqrt 2: 1.12893
+
+
+def erf_as7126(x):
+    """gelu_erf's erf restated in float64: 1 - (a1 t + .. + a5 t^5) exp(-x^2), t = 1 / (1 + 0.3275911 |x|), odd in x."""
+    z = x.abs()
+    t = 1.0 / (1.0 + 0.3275911 * z)
+    poly = ((((1.061405429 * t - 1.453152027) * t + 1.421413741) * t - 0.284496736) * t + 0.254829592) * t
+    return torch.sign(x) * (1.0 - poly * torch.exp(-z * z))
+
+
+def split_bf16_ref(x):
+    """split_bf16 of csrc/common.hpp on an f32 tensor: hi = RNE bf16 of x, lo = RNE bf16 of the fp32 remainder x - hi."""
+    assert x.dtype == torch.float32
+    hi = x.bfloat16()
+    return hi, (x - hi.float()).bfloat16()
+
+
+def packed_rows(M, row0, nl_group, gap_late=False):
+    """Output row of token row m: row0 + m + m // nl_group (no gaps with nl_group = 0).  gap_late plants (m + 1) // nl_group."""
+    m = torch.arange(M)
+    return row0 + m + ((m + (1 if gap_late else 0)) // nl_group if nl_group > 0 else 0)
+
+
+def place_rows(val, rows, ld, orow, pitch=None):
+    """The [rows, ld] output image with val [M, N] stored at flat index orow[m] * pitch + n (pitch = ld unless a fault is planted) and
+    NaN everywhere else."""
+    M, N = val.shape
+    flat = torch.full((rows * ld,), float("nan"), dtype=torch.float64)
+    flat[(orow[:, None] * (ld if pitch is None else pitch) + torch.arange(N)[None, :]).reshape(-1)] = val.reshape(-1)
+    return flat.view(rows, ld)
+
+
+def readout_gemm_ref(a_terms, w, b, act="none", *, drop_lo_stage=None, stale_stage=None, drop_stage=None, double_stage=None, lost_half=None,
+                     row_of=None, col_of=None, bias_of=None, gelu_before_bias=False):
+    """y = act(sum_p a_terms[p] . w^T + b) in float64 on the operands the kernel multiplies, already up-cast: a_terms = [hi, lo] (the
+    split forms), [hi] (planes_gemm without a lo plane) or [a16]; each [M, K], w [N, K], b [N] or None, act "none" | "gelu" (erf).
+    Returns (value, sum of |terms| including |b|, pre-activation).  K runs in stages of 64, as in the kernels.  The keywords plant the
+    faults of tests/test_readout_gemm_power.py:
+      drop_lo_stage s      the planes behind the first (lo) leave stage s out
+      stale_stage s        stage s contributes what stage s - 1 does (a ring slot read before its data landed)
+      drop_stage s / double_stage s   stage s missing / counted twice
+      lost_half (s, h, n_lo, n_hi)    columns [n_lo, n_hi) lose the 32-wide k half h of stage s
+      row_of [M] / col_of [N]         the row of a_terms / the row of w that output row m / column n is computed from
+      bias_of [N]          the bias element column n takes;   gelu_before_bias: act(acc) + b"""
+    M, K = a_terms[0].shape
+    N = w.shape[0]
+    assert K % 64 == 0 and w.shape[1] == K
+    acc = torch.zeros(M, N, dtype=torch.float64)
+    ab = torch.zeros(M, N, dtype=torch.float64)
+    for p, a in enumerate(a_terms):
+        for s in range(K // 64):
+            if s == drop_stage or (p >= 1 and s == drop_lo_stage):
+                continue
+            src = s - 1 if s == stale_stage else s
+            ks = slice(64 * src, 64 * src + 64)
+            t, ta = a[:, ks] @ w[:, ks].t(), a[:, ks].abs() @ w[:, ks].abs().t()
+            if lost_half is not None and lost_half[0] == s:
+                _, h, n_lo, n_hi = lost_half
+                kh = slice(64 * src + 32 * h, 64 * src + 32 * h + 32)
+                t[:, n_lo:n_hi] -= a[:, kh] @ w[n_lo:n_hi, kh].t()
+                ta[:, n_lo:n_hi] -= a[:, kh].abs() @ w[n_lo:n_hi, kh].abs().t()
+            mult = 2.0 if s == double_stage else 1.0
+            acc += mult * t
+            ab += mult * ta
+    if row_of is not None:
+        acc, ab = acc[row_of], ab[row_of]
+    if col_of is not None:
+        acc, ab = acc[:, col_of], ab[:, col_of]
+    bias = torch.zeros(N, dtype=torch.float64) if b is None else (b if bias_of is None else b[bias_of])
+    pre = acc + bias
+    if act == "gelu":
+        val = gelu_ref(acc)[0] + bias if gelu_before_bias else gelu_ref(pre)[0]
+    else:
+        assert act == "none"
+        val = pre
+    return val, ab + bias.abs(), pre

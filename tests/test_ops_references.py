@@ -604,3 +604,81 @@ def test_merge_reference_equals_softmax_attention_over_x_plus_pos():
     assert torch.allclose(o, want, rtol=1e-12, atol=1e-13) and torch.equal(M2, M) and torch.allclose(L2, L)
     o16 = R.merge_vproj_ref(pm, pl, pacc2 / pl[:, :, None], rows, wv, normalised=True)[3]
     assert torch.allclose(o16, want, rtol=1e-12, atol=1e-13)
+
+
+# ---- readout GEMMs ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M,N,K,planes,bias", [(5, 7, 128, 2, True), (3, 4, 64, 1, False), (9, 2, 192, 2, True)])
+def test_readout_gemm_reference_is_linear_plus_erf_gelu(M, N, K, planes, bias):
+    g = torch.Generator().manual_seed(M * 31 + N)
+    a_terms = [torch.randn(M, K, generator=g, dtype=torch.float64) * 2.0 ** (-9 * p) for p in range(planes)]
+    w = torch.randn(N, K, generator=g, dtype=torch.float64)
+    b = torch.randn(N, generator=g, dtype=torch.float64) if bias else None
+    lin = torch.nn.functional.linear(sum(a_terms), w, b)
+    val, ab, pre = R.readout_gemm_ref(a_terms, w, b)
+    assert _maxabs(val, lin) <= TOL and torch.equal(val, pre) and bool((ab >= val.abs() - 1e-12).all())
+    want_ab = sum(a.abs() for a in a_terms) @ w.abs().t() + (b.abs() if bias else 0.0)
+    assert _maxabs(ab, want_ab) <= TOL
+    val, _, pre = R.readout_gemm_ref(a_terms, w, b, "gelu")
+    assert _maxabs(val, torch.nn.functional.gelu(lin)) <= TOL and _maxabs(pre, lin) <= TOL
+    # every planted fault is a different function; the stage faults are what their names say
+    s = K // 64 - 1
+    ks = slice(64 * s, 64 * s + 64)
+    last = sum(a_terms)[:, ks] @ w[:, ks].t()
+    assert _maxabs(R.readout_gemm_ref(a_terms, w, b, drop_stage=s)[0], lin - last) <= TOL
+    assert _maxabs(R.readout_gemm_ref(a_terms, w, b, double_stage=s)[0], lin + last) <= TOL
+    if planes == 2:
+        assert _maxabs(R.readout_gemm_ref(a_terms, w, b, drop_lo_stage=s)[0], lin - a_terms[1][:, ks] @ w[:, ks].t()) <= TOL
+    if s >= 1:
+        prev = sum(a_terms)[:, 64 * s - 64:64 * s] @ w[:, 64 * s - 64:64 * s].t()
+        assert _maxabs(R.readout_gemm_ref(a_terms, w, b, stale_stage=s)[0], lin - last + prev) <= TOL
+    half = sum(a_terms)[:, 64 * s + 32:64 * s + 64] @ w[1:2, 64 * s + 32:64 * s + 64].t()
+    lost = R.readout_gemm_ref(a_terms, w, b, lost_half=(s, 1, 1, 2))[0]
+    assert _maxabs(lost[:, 1:2], lin[:, 1:2] - half) <= TOL and _maxabs(lost[:, :1], lin[:, :1]) <= TOL
+    if bias:
+        early = R.readout_gemm_ref(a_terms, w, b, "gelu", gelu_before_bias=True)[0]
+        assert _maxabs(early, torch.nn.functional.gelu(lin - b) + b) <= TOL
+
+
+def test_the_rational_erf_of_gelu_erf_keeps_its_stated_error_and_the_gelu_slope_its_bound():
+    x = torch.linspace(-8, 8, 400001, dtype=torch.float64)
+    assert _maxabs(R.erf_as7126(x), torch.erf(x)) <= R.ERF_AS_ERR
+    assert 1.128 < float(R.gelu_grad_ref(x)[0].abs().max()) <= R.GELU_SLOPE
+
+
+def test_split_bf16_reference_carries_sixteen_bits():
+    g = torch.Generator().manual_seed(5)
+    x = torch.cat([torch.randn(4096, generator=g) * 3, torch.randn(4096, generator=g) * 1e-3, torch.tensor([0.0, 1.0, -1.0, 1 + 2.0 ** -9, 255.0 / 256])])
+    hi, lo = R.split_bf16_ref(x)
+    assert hi.dtype == lo.dtype == torch.bfloat16 and torch.equal(hi, x.bfloat16())
+    assert bool(((R.up(hi) + R.up(lo) - R.up(x)).abs() <= 2.0 ** -17 * R.up(x).abs()).all())
+    assert bool((R.up(lo).abs() <= 2.0 ** -8 * R.up(hi).abs()).all())                      # the remainder is at most one bf16 ulp of hi
+    assert float(lo[-2]) == 2.0 ** -9 and float(lo[-1]) == 0.0
+
+
+@pytest.mark.parametrize("M,row0,g", [(1, 0, 0), (20, 3, 9), (7, 2, 1), (9, 0, 9), (8, 5, 9)])
+def test_packed_rows_and_place_rows_against_an_explicit_loop(M, row0, g):
+    rows, gaps = [], 0
+    for m in range(M):
+        if g > 0 and m > 0 and m % g == 0:
+            gaps += 1
+        rows.append(row0 + m + gaps)
+    got = R.packed_rows(M, row0, g)
+    assert got.tolist() == rows
+    val = torch.arange(M * 3, dtype=torch.float64).reshape(M, 3) + 1
+    img = R.place_rows(val, rows[-1] + 3, 5, got)
+    for r in range(img.shape[0]):
+        for col in range(5):
+            want = val[rows.index(r), col] if (r in rows and col < 3) else None
+            assert (want is None and math.isnan(float(img[r, col]))) or float(img[r, col]) == float(want)
+    if g > 0 and M >= g:
+        assert R.packed_rows(M, row0, g, gap_late=True).tolist() != rows
+
+
+@pytest.mark.parametrize("pos,modal,t,h,w,anyres", [("grid", "video", 2, 3, 4, False), ("frame", "video", 3, 2, 5, False), ("one_token", "video", 2, 2, 2, False),
+                                                     ("grid", "image", 1, 4, 3, True)])
+def test_packed_rows_are_the_token_rows_of_the_packing_layout(pos, modal, t, h, w, anyres):
+    from hicom_amd import geometry as geo
+    lay = geo.pack_layout("spatial_unpad", pos, modal, t, h, w, True, anyres)
+    tokens = [r for r in range(lay.n_rows) if r not in set(lay.newline_rows)]
+    assert R.packed_rows(lay.n_tokens, 0, lay.nl_group).tolist() == tokens
+    assert [lay.row_of(m) for m in range(lay.n_tokens)] == tokens
