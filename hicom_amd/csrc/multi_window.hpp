@@ -80,6 +80,149 @@ __device__ __forceinline__ void multi_window_guides_ctx16(const uint16_t* key, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// Backward of one window for all Q guides of its item (ragged_multi_guide_train.hip: rmg_local_bwd_kernel), one 4-wave workgroup.
+// Per guide q the algebra and the arithmetic of local_window_bwd (window_rows.hpp) without clip-scale:
+//     s_qi = scale guide_q . k_i,  p_q = softmax(s_q),  dP_qi = dctx_q . v_i,  dS_qi = p_qi (dP_qi - sum_j p_qj dP_qj),
+//     dq_q = scale sum_i dS_qi k_i                                  (f32, one row per (guide, window), written once)
+// and per token, summed over the guides in fp32 in the order q = 0 .. Q - 1, rounded to bf16 once and stored plainly:
+//     dkey_i = scale sum_q dS_qi guide_q,   dvalue_i = (dkey_i with value_is_key +) sum_q p_qi dctx_q
+// Every dot product, softmax and dq sum is its own chain, written as the single-guide body writes it (token i of the window goes to wave
+// i & 3 in both), so a guide's dS, p and dq do not depend on Q or on its place in a group, and with Q = 1 dq, dkey and dvalue have the
+// single-guide kernel's values.  The guides go through the key / value walk in groups of kGuideGroup as in the forward: a row is loaded
+// once per group.  key / value / dkey / dvalue point at the first token of the grid `w` indexes; guide at the item's first guide row;
+// dctx / dq at guide 0's row of this window, guide q's `plane` elements times q further.  dkey / dvalue may be NULL.
+// lsm: dS [Q][WP], p [Q][WP] (WP = WIN rounded up to 4) and the [4][D] slab: multi_window_bwd_smem.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct MultiWindowBwdArgs {
+    const uint16_t* key;
+    const uint16_t* value;
+    const uint16_t* guide;  // [Q][D]
+    int Q;
+    float scale;
+    const float* dctx;      // [Q] rows of D, `plane` apart
+    float* dq;              // likewise
+    long plane;
+    uint16_t* dkey;         // bf16 [N, D] or NULL
+    uint16_t* dvalue;       // bf16 [N, D] or NULL
+    int value_is_key;
+};
+
+__host__ __device__ inline size_t multi_window_bwd_smem(int Q, int WIN, int D) { return ((size_t)2 * Q * ((WIN + 3) & ~3) + 4 * (size_t)D) * 4; }
+
+// scores and dP of the guides g0 .. g0 + NG - 1: sc / dp rows g0 .. of [Q][WP]
+template <int NV, int NG>
+__device__ __forceinline__ void multi_window_bwd_scores(const MultiWindowBwdArgs& p, const WindowGeom& w, int g0, float* sc, float* dp, int WP, int lane,
+                                                        int wave) {
+    constexpr int D = NV * 384;
+    float q[NG][NV][6], g[NG][NV][6];
+#pragma unroll
+    for (int u = 0; u < NG; ++u) {
+        load_row<NV>(p.guide + (long)(g0 + u) * D, lane, q[u]);
+        load_row_f32<NV>(p.dctx + (long)(g0 + u) * p.plane, lane, g[u]);
+    }
+    for (int i = wave; i < w.WIN; i += 4) {
+        float k[NV][6], v[NV][6];
+        const long tok = w.token_of(i);
+        load_row<NV>(p.key + tok * D, lane, k);
+        load_row<NV>(p.value + tok * D, lane, v);
+#pragma unroll
+        for (int u = 0; u < NG; ++u) {
+            const float dot = wave_sum_fast(row_dot<NV>(q[u], k));
+            const float dd = wave_sum_fast(row_dot<NV>(g[u], v));
+            if (lane == 0) { sc[(g0 + u) * WP + i] = dot * p.scale; dp[(g0 + u) * WP + i] = dd; }
+        }
+    }
+}
+
+// dq of the guides g0 .. g0 + NG - 1 from dS (in sc): per wave one chain per guide over its tokens, the four waves' rows through the slab
+template <int NV, int NG>
+__device__ __forceinline__ void multi_window_bwd_dq(const MultiWindowBwdArgs& p, const WindowGeom& w, int g0, const float* sc, int WP, float* part, int tid) {
+    constexpr int D = NV * 384;
+    const int lane = tid & 63, wave = tid >> 6;
+    float acc[NG][NV][6];
+#pragma unroll
+    for (int u = 0; u < NG; ++u) row_zero<NV>(acc[u]);
+    for (int i = wave; i < w.WIN; i += 4) {
+        float k[NV][6];
+        load_row<NV>(p.key + w.token_of(i) * D, lane, k);
+#pragma unroll
+        for (int u = 0; u < NG; ++u) row_axpy<NV>(sc[(g0 + u) * WP + i] * p.scale, k, acc[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < NG; ++u) {
+        __syncthreads();                           // (the slab's readers of the guide before)
+        store_partial_row<NV>(part, wave, lane, acc[u]);
+        __syncthreads();
+        sum_partial_rows<NV>(part, tid, p.dq + (long)(g0 + u) * p.plane);
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void multi_window_bwd(const MultiWindowBwdArgs& p, const WindowGeom& w, float* lsm, int tid) {
+    constexpr int D = NV * 384;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int WIN = w.WIN, WP = (WIN + 3) & ~3, Q = p.Q;
+    float* sc = lsm;                               // [Q][WP] scores, then dS
+    float* dp = lsm + Q * WP;                      // [Q][WP] dP, then p
+    float* part = lsm + 2 * Q * WP;                // [4][D]
+
+    // ---- phase 1: scores and dP, every key / value row once per group of guides ----
+    for (int g0 = 0; g0 < Q; g0 += kGuideGroup)
+        switch (Q - g0 < kGuideGroup ? Q - g0 : kGuideGroup) {
+            case 1: multi_window_bwd_scores<NV, 1>(p, w, g0, sc, dp, WP, lane, wave); break;
+            case 2: multi_window_bwd_scores<NV, 2>(p, w, g0, sc, dp, WP, lane, wave); break;
+            case 3: multi_window_bwd_scores<NV, 3>(p, w, g0, sc, dp, WP, lane, wave); break;
+            default: multi_window_bwd_scores<NV, 4>(p, w, g0, sc, dp, WP, lane, wave); break;
+        }
+    __syncthreads();
+    // ---- softmax, delta, dS and p per guide: wave `wave` takes the guides q = wave, wave + 4, ...; a lane rewrites what it alone read ----
+    for (int q = wave; q < Q; q += 4) {
+        float* s = sc + q * WP;
+        float* d = dp + q * WP;
+        float mx, inv_sum, delta;
+        softmax_stats(s, WIN, lane, mx, inv_sum, d, &delta);
+        for (int i = lane; i < WIN; i += 64) {
+            const float pi_ = expf(s[i] - mx) * inv_sum;
+            s[i] = pi_ * (d[i] - delta);
+            d[i] = pi_;
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: dq per guide ----
+    for (int g0 = 0; g0 < Q; g0 += kGuideGroup)
+        switch (Q - g0 < kGuideGroup ? Q - g0 : kGuideGroup) {
+            case 1: multi_window_bwd_dq<NV, 1>(p, w, g0, sc, WP, part, tid); break;
+            case 2: multi_window_bwd_dq<NV, 2>(p, w, g0, sc, WP, part, tid); break;
+            case 3: multi_window_bwd_dq<NV, 3>(p, w, g0, sc, WP, part, tid); break;
+            default: multi_window_bwd_dq<NV, 4>(p, w, g0, sc, WP, part, tid); break;
+        }
+    // ---- phase 3: the token side, one fp32 chain per token and channel over the guides in order, one rounding, one plain store ----
+    if (!p.dkey && !p.dvalue) return;
+    const bool key_side = p.dkey || p.value_is_key;
+    for (int i = wave; i < WIN; i += 4) {
+        const long tok = w.token_of(i);
+        float dk[NV][6];
+        row_zero<NV>(dk);
+        if (key_side)
+            for (int q = 0; q < Q; ++q) {
+                float gq[NV][6];
+                load_row<NV>(p.guide + (long)q * D, lane, gq);
+                row_axpy<NV>(sc[q * WP + i] * p.scale, gq, dk);
+            }
+        if (p.dkey) store_row_bf16<NV>(p.dkey + tok * D, lane, false, [&](int s, int j) { return dk[s][j]; });
+        if (p.dvalue) {
+            if (!p.value_is_key) row_zero<NV>(dk);
+            for (int q = 0; q < Q; ++q) {
+                float gc[NV][6];
+                load_row_f32<NV>(p.dctx + (long)q * p.plane, lane, gc);
+                row_axpy<NV>(dp[q * WP + i], gc, dk);
+            }
+            store_row_bf16<NV>(p.dvalue + tok * D, lane, false, [&](int s, int j) { return dk[s][j]; });
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // The logits form: the raw dot products key_n . guide_q come precomputed, logits f32 [Q][tokens] with guide q's
 // plane q_stride floats behind guide 0's (hicom_head_scores_multi_fwd writes them).  No key row is read and there is no dot product
 // over the channels: lane i of the wave fetches the logit of the window's token i, `scale` and the softmax follow as in

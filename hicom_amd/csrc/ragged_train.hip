@@ -112,31 +112,12 @@ __global__ __launch_bounds__(256) void ragged_local_attn_bwd_kernel(RaggedLocalB
     local_window_bwd<NV>(a, w.geom, q, lsm, tid);
 }
 
-// ... and the local share of d guide: dq_item[i] = sum of the dq rows of item i's windows, in a fixed order and without atomics.
-// grid = (E / 64, B), 256 threads = 16 stripes x 16 lanes of 4 channels: stripe s sums windows s, s + 16, ... in order, the sixteen partial
-// rows are added pairwise through LDS.
+// ... and the local share of d guide: dq_item[i] = sum of the dq rows of item i's windows, in a fixed order and without atomics
+// (window_rows.hpp: sum_rows_striped has the order).  grid = (E / 64, B), 256 threads.
 __global__ __launch_bounds__(256) void ragged_dq_item_kernel(const float* dq, const RaggedItem* items, int wps, int E, float* dq_item) {
     __shared__ float4 red[16][16];
-    const int item = blockIdx.y, lane = threadIdx.x & 15, stripe = threadIdx.x >> 4;
-    const int c = blockIdx.x * 64 + 4 * lane;
-    const RaggedItem it = items[item];
-    const int nwin = (it.T / it.kt) * wps;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < E)
-        for (int w = stripe; w < nwin; w += 16) {
-            const float4 v = *reinterpret_cast<const float4*>(dq + (long)(it.win0 + w) * E + c);
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-    red[stripe][lane] = a;
-    __syncthreads();
-    for (int half = 8; half > 0; half >>= 1) {
-        if (stripe < half) {
-            const float4 u = red[stripe][lane], v = red[stripe + half][lane];
-            red[stripe][lane] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
-        }
-        __syncthreads();
-    }
-    if (stripe == 0 && c < E) *reinterpret_cast<float4*>(dq_item + (long)item * E + c) = red[0][lane];
+    const RaggedItem it = items[blockIdx.y];
+    sum_rows_striped(dq, (long)it.win0, (it.T / it.kt) * wps, E, dq_item + (long)blockIdx.y * E, red);
 }
 
 // ---- the logits form: the window backward where the forward took its scores precomputed, l_n = key_n . guide_item as f32

@@ -508,4 +508,29 @@ __device__ __forceinline__ void adapt_dy_token(const _Float16* y_row, const uint
     }
 }
 
+// ---- rows [first, first + count) of an f32 [*, E] matrix summed into out[E], in a fixed order and without atomics: the one body of
+// ragged_dq_item_kernel (ragged_train.hip: the dq rows of an item's windows) and rmg_dq_pair_kernel (ragged_multi_guide_train.hip: of a
+// pair's).  Workgroup x of E / 64, 256 threads = 16 stripes x 16 lanes of 4 channels: stripe s sums rows s, s + 16, ... in order, the sixteen
+// partial rows are added pairwise through LDS.
+__device__ __forceinline__ void sum_rows_striped(const float* m, long first, int count, int E, float* out, float4 (*red)[16]) {
+    const int lane = threadIdx.x & 15, stripe = threadIdx.x >> 4;
+    const int c = blockIdx.x * 64 + 4 * lane;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < E)
+        for (int w = stripe; w < count; w += 16) {
+            const float4 v = *reinterpret_cast<const float4*>(m + (first + w) * E + c);
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+    red[stripe][lane] = a;
+    __syncthreads();
+    for (int half = 8; half > 0; half >>= 1) {
+        if (stripe < half) {
+            const float4 u = red[stripe][lane], v = red[stripe + half][lane];
+            red[stripe][lane] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+        }
+        __syncthreads();
+    }
+    if (stripe == 0 && c < E) *reinterpret_cast<float4*>(out + c) = red[0][lane];
+}
+
 }  // namespace hicom

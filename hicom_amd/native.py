@@ -441,6 +441,9 @@ SIGNATURES = {
     "hicom_compressor_ragged_multiguide_train_state": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp, vp, vp]),
     "hicom_compressor_ragged_multiguide_global_bwd_workspace_bytes": (i64, [C.POINTER(CompressorRaggedMultiGuideArgs)]),
     "hicom_compressor_ragged_multiguide_global_bwd": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "hicom_compressor_ragged_multiguide_local_bwd": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp, vp, vp, vp, vp, vp, i32]),
+    "hicom_compressor_ragged_multiguide_dq_pair": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp]),
+    "hicom_compressor_ragged_multiguide_global_dx": (C.c_int, [C.POINTER(CompressorRaggedMultiGuideArgs), vp, vp, vp, vp, vp, vp, i32, vp, i32]),
 }
 EXPORTS = tuple(SIGNATURES)
 
@@ -1049,6 +1052,30 @@ def compressor_ragged_multiguide_global_bwd(args: CompressorRaggedMultiGuideArgs
     """The global stage's attention backward over all (item, guide) pairs of a ragged multi-guide plan
     (hicom_compressor_ragged_multiguide_global_bwd): fills ds and dqt."""
     _ragged_train_call("multiguide_global_bwd", args, x, dctx, delta, scores, ml, ds, dqt, ws, ws.numel())
+
+
+def compressor_ragged_multiguide_local_bwd(args: CompressorRaggedMultiGuideArgs, key, value, guide, dctx, dq, dq_pair=None, dkey=None, dvalue=None,
+                                           value_is_key=False):
+    """The window backward over all windows of a ragged multi-guide plan, every window for all guides of its item
+    (hicom_compressor_ragged_multiguide_local_bwd): fills dq [sum Q_i windows_i, E] and whichever of dkey / dvalue bf16 [tokens, E] is given;
+    with dq_pair [M, E], then hicom_compressor_ragged_multiguide_dq_pair (compressor_ragged_local_bwd's arguments, a pair for an item)."""
+    assert key.dtype == value.dtype == guide.dtype == torch.bfloat16 and dctx.dtype == dq.dtype == torch.float32
+    _ragged_train_call("multiguide_local_bwd", args, key, value, guide, dctx, dq, dkey, dvalue, int(bool(value_is_key)))
+    if dq_pair is not None:
+        compressor_ragged_multiguide_dq_pair(args, dq, dq_pair)
+
+
+def compressor_ragged_multiguide_dq_pair(args: CompressorRaggedMultiGuideArgs, dq, dq_pair):
+    """dq_pair [M, E] = the rows of dq [sum Q_i windows_i, E] summed per pair (hicom_compressor_ragged_multiguide_dq_pair)."""
+    assert dq.dtype == dq_pair.dtype == torch.float32
+    _ragged_train_call("multiguide_dq_pair", args, dq, dq_pair)
+
+
+def compressor_ragged_multiguide_global_dx(args: CompressorRaggedMultiGuideArgs, scores, ds, ml, qt, dctx, tiles, dx, accumulate):
+    """d frames_feature of the global stage over all items of a ragged multi-guide plan, every token against the nh Q_i rows of its item
+    (hicom_compressor_ragged_multiguide_global_dx); tiles: the device int32 [ntiles, 2] table of ragged.dx_tile_table."""
+    assert tiles.dtype == torch.int32 and tiles.is_contiguous() and dx.dtype == torch.bfloat16
+    _ragged_train_call("multiguide_global_dx", args, scores, ds, ml, qt, dctx, tiles, tiles.shape[0], dx, int(bool(accumulate)))
 
 
 def compressor_clips_multiguide_workspace(args: CompressorClipsMultiGuideArgs) -> int:

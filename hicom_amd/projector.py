@@ -1376,16 +1376,24 @@ class HIComProjector(nn.Module):
                                                          image_newline, chunks, local_logits)
 
     def forward_ragged_multi_guide_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts, modals, image_newline=None, *,
-                                         chunks=None, local_logits=None):
+                                         chunks=None, local_logits=None, input_grads=False):
         """forward_ragged_multi_guide under autograd: the training step of a mixed batch whose item i has Q_i instructions (a multi-turn
         item: one clip, one instruction per turn).  Arguments, input checks, plan cache and return value are forward_ragged_multi_guide's
         -- B views [Q_i, rows_i, hidden] of one storage, bit-equal to it -- and the result carries an autograd graph: one backward, eager,
         over all M = sum Q_i pairs, whose call sequence depends neither on B nor on the Q_i nor on the mix (ragged_multi_guide_train.py,
         csrc/ragged_multi_guide_train.hip).  An item's tokens are read once per 32 folded rows in both directions, never
         once per guide, and no token-sized copy is made.
-        Gradients: every projector parameter that requires grad, and image_newline (stages 1 and 2 of the release script).  Scope: the
-        plain release recipe, bf16 module and inputs, exact window partition per item, 1 <= Q_i <= 32.  The k / v adaptor recipe,
-        clip-scale, anyres dicts, fp16 / fp32 and any of frames_feature, frames_embed, guide_embeds, local_logits that requires grad raise
+        Gradients: every projector parameter that requires grad, and image_newline (stages 1 and 2 of the release script).
+        `input_grads=True` (stage 3; the keyword of forward_ragged_train): each of frames_feature [sum T_i, H, W, E],
+        frames_embed (same shape, or None: the keys are then the value rows and the key-side term is added into d frames_feature) and
+        guide_embeds [sum Q_i, E] that requires grad gets its gradient through autograd, in its own dtype and shape, from the same one
+        backward: a token's gradient is the sum over its item's Q_i guides, formed in fp32 and rounded to bf16 once per stage.  An input
+        that does not require grad costs nothing; a step with every parameter frozen and an input requiring grad is trainable; the
+        parameter gradients are bit-equal to the same step with the inputs detached.  The fp32 [sum Q_i, E] d guide_embeds stays in
+        autograd.LAST_FP32_GRADS["__guide_embeds__"].
+        Scope: the plain release recipe, bf16 module and inputs, exact window partition per item, 1 <= Q_i <= 32.  The k / v adaptor recipe,
+        clip-scale, anyres dicts, fp16 / fp32, any of frames_feature, frames_embed, guide_embeds that requires grad without
+        input_grads=True, and local_logits that requires grad (the logits form with input gradients is not built) raise
         NotImplementedError (ValueError for a malformed call) in front of any device work and name the loop of forward() per pair:
         nothing is detached silently.  With nothing trainable, or under no_grad, it is forward_ragged_multi_guide's call without a graph.
         `local_logits` (frames_embed=None): the scores of forward_ragged_multi_guide(local_logits=), computed under no_grad -- the head is
@@ -1394,7 +1402,7 @@ class HIComProjector(nn.Module):
         forward() per pair): a batch whose items all have ONE guide belongs to forward_ragged_train."""
         from . import ragged_multi_guide_train
         return ragged_multi_guide_train.run_ragged_multi_guide_train(self, frames_feature, frames_embed, guide_embeds, split_sizes, guide_counts,
-                                                                     modals, image_newline, chunks, local_logits)
+                                                                     modals, image_newline, chunks, local_logits, input_grads)
 
     def forward_stepwise(self, frames_feature, frames_embed, guide_embed, modal, image_newline=None):
         """Same result, one C-ABI call per operator (anyres dict inputs; also the cross-check of the

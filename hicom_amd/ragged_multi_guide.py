@@ -192,6 +192,19 @@ def run_ragged_multi_guide(proj, ff, fe, guides, split_sizes, guide_counts, moda
     return pair_views(plan, out)
 
 
+def dx_tile_table(t) -> np.ndarray:
+    """The tile -> item table of hicom_compressor_ragged_multiguide_global_dx from plan_tables' result alone: ragged.dx_tile_table -- int32
+    [sum ceil(N_i / 64), 2] rows (item, first token of the tile inside the item).  A tile belongs to an ITEM, not to a pair: its workgroup
+    adds all nh Q_i rows of the item's row space."""
+    return ragged.dx_tile_table(t)
+
+
+def pair_dq_table(t) -> np.ndarray:
+    """The (first row, count) table hicom_compressor_ragged_multiguide_dq_pair sums by, from plan_tables' result alone: int64 [M, 2], pair p's
+    rows of the pair-major dq [sum Q_i windows_i, E] (its window contexts' rows)."""
+    return np.array([(ctx_row0, t.windows[i]) for i, _, ctx_row0, _ in t.pairs], dtype=np.int64).reshape(-1, 2)
+
+
 def train_row_maps(t):
     """Where the rows of the pair-major packed output come from, for the backward of the call (ragged_multi_guide_train.py), from
     plan_tables' result alone: (local, newline, glob) int64 arrays of output rows -- local[c] the row of context row c (pair p owns the

@@ -100,9 +100,12 @@ class _PlanTrain:
     # the window -> item index (plan_tables' win_item) as a device int64 tensor: the query row of a window is its item's guide
     win_item = functools.cached_property(lambda s: torch.from_numpy(s._tables.win_item.astype("int64")).to(s._dev))
     bwd_ws_bytes = functools.cached_property(lambda s: nv.compressor_ragged_global_bwd_workspace(s._io))
-    # the native attention backward of the global stage over the plan's rows (looked up per call).  ragged_backward reads row_maps,
-    # bwd_ws_bytes and global_bwd only: a plan whose rows are (item, guide) pairs brings its own three (ragged_multi_guide_train.py)
+    # the native calls of the backward over the plan's rows (looked up per call): the global stage's attention backward and, for the input
+    # gradients, the window backward and the global stage's d x.  ragged_backward reads row_maps, dx_tiles, bwd_ws_bytes and these three
+    # only: a plan whose rows are (item, guide) pairs brings its own (ragged_multi_guide_train.py), with the same arguments
     global_bwd = property(lambda s: nv.compressor_ragged_global_bwd)
+    local_bwd = property(lambda s: nv.compressor_ragged_local_bwd)
+    global_dx = property(lambda s: nv.compressor_ragged_global_dx)
 
 
 _ADAPTOR_PARAMS = tuple(f"local_compressor.{s}_{part}" for s in "kv" for part in ("proj.", "norm.", "alpha"))
@@ -223,7 +226,7 @@ def _local_backward(st, ctx16, dout, local_rows, window, adapt):
         if not inputs.want_ll:
             inputs.d_ll = None
         return None
-    dq_item = torch.empty((a.B, a.E), dtype=torch.float32, device=st.dev) if st.want_guide else None
+    dq_item = torch.empty((guides.shape[0], a.E), dtype=torch.float32, device=st.dev) if st.want_guide else None     # (a row per item, or per pair)
     if adaptors:
         dq_w, d_kx, d_vx = _local_adapt_backward(st, lc, plan, guides, dctx_l, fe, *adapt, st.want_fe or (st.want_ff and fe is None), st.want_ff, st.want_guide)
         if st.want_guide:
@@ -235,7 +238,7 @@ def _local_backward(st, ctx16, dout, local_rows, window, adapt):
         dq_w = torch.empty_like(dctx_l)
         d_fe = torch.empty_like(fe) if st.want_fe else None
         d_ff = torch.empty_like(x) if st.want_ff else None      # (value-side share; without frames_embed the key-side term is added in)
-        nv.compressor_ragged_local_bwd(a, fe if fe is not None else x, x, guides, dctx_l, dq_w, dq_item, d_fe, d_ff, value_is_key=st.want_ff and fe is None)
+        plan.train.local_bwd(a, fe if fe is not None else x, x, guides, dctx_l, dq_w, dq_item, d_fe, d_ff, value_is_key=st.want_ff and fe is None)
     inputs.d_fe, inputs.d_ff = d_fe, d_ff
     return dq_item
 
@@ -264,7 +267,7 @@ def _global_backward(st, scores, ml, ctxg, dout, glob_rows, dq_item):
         E = q32.shape[1]
         qp_ = (q32 @ Wq.t() + bq).view(-1, nh, hd)
         qt_ = (att.scale * torch.einsum("hje,qhj->qhe", Wk.view(nh, hd, E), qp_)).reshape(-1, E).contiguous()
-        nv.compressor_ragged_global_dx(a, scores, ds, ml, qt_, dctx, plan.train.dx_tiles, inputs.d_ff.view(-1, E), accumulate=True)
+        plan.train.global_dx(a, scores, ds, ml, qt_, dctx, plan.train.dx_tiles, inputs.d_ff.view(-1, E), accumulate=True)
     if st.want_guide:
         # direct recipe: the injected query IS the guide, one row per item (autograd._global_query_backward) + the local stage's share
         glob = dqp @ Wq + dpre_g

@@ -1711,6 +1711,32 @@ int64_t hicom_compressor_ragged_multiguide_global_bwd_workspace_bytes(const hico
 int hicom_compressor_ragged_multiguide_global_bwd(const hicom_compressor_ragged_multiguide_args* args, const void* x, const float* dctx, const float* delta,
                                                   const float* scores, const float* ml, float* ds_out, float* dqt_out, void* bws, int64_t bws_bytes);
 
+/* ---- input gradients of that training step (stage 3) ---------------------------------------------------------------------
+ * A token's gradient is a sum over its item's Q_i guides: it is formed in fp32 in the order q = 0 .. Q_i - 1 and written once.  The calls
+ * check their pointers and the per-item partition in front of anything that needs a device, and read the tables from the head of args->ws.
+ *
+ * hicom_compressor_ragged_multiguide_local_bwd: the window backward, one workgroup per window of the stacked tensor (sum windows_i of them);
+ * a window's key and value rows serve all guides of its item.
+ *   key / value  bf16 [sum N_i, E]: frames_embed (or frames_feature without it) / frames_feature;  guide bf16 [M, E]
+ *   dctx         f32 [sum Q_i windows_i, E], pair-major as the window contexts;  dq f32, the same shape: scale sum_i dS_qi k_i
+ *   dkey         bf16 [sum N_i, E] or NULL: scale sum_q dS_qi guide_q
+ *   dvalue       bf16 [sum N_i, E] or NULL: sum_q p_qi dctx_q (+ dkey_i with value_is_key: key == value, dkey NULL)
+ * Plain stores: every token lies in one window.  With every Q_i = 1 dq, dkey and dvalue have hicom_compressor_ragged_local_bwd's values.
+ *
+ * hicom_compressor_ragged_multiguide_dq_pair: dq_pair f32 [M, E] = the sum of a pair's windows_i rows of dq, in
+ * hicom_compressor_ragged_local_bwd's fixed order, without atomics.
+ *
+ * hicom_compressor_ragged_multiguide_global_dx: dx[n] (+)= sum over the nh Q_i rows R of the token's item of dS[R, n] qt[R] + softmax(S)[R, n]
+ * dctx[R]; one fp32 chain per token and channel in row order from the bf16 row dx holds (accumulate), one bf16 store.
+ *   scores / ds / ml as train_state / global_bwd left them;  qt, dctx f32 [M nh, E]
+ *   tiles  DEVICE int32 [ntiles, 2]: (item, first token of the tile inside the item), 64 tokens per tile, ntiles = sum ceil(N_i / 64)
+ *   dx     bf16 [sum N_i, E] */
+int hicom_compressor_ragged_multiguide_local_bwd(const hicom_compressor_ragged_multiguide_args* args, const void* key, const void* value, const void* guide,
+                                                 const float* dctx, float* dq, void* dkey, void* dvalue, int32_t value_is_key);
+int hicom_compressor_ragged_multiguide_dq_pair(const hicom_compressor_ragged_multiguide_args* args, const float* dq, float* dq_pair);
+int hicom_compressor_ragged_multiguide_global_dx(const hicom_compressor_ragged_multiguide_args* args, const float* scores, const float* ds, const float* ml,
+                                                 const float* qt, const float* dctx, const int32_t* tiles, int32_t ntiles, void* dx, int32_t accumulate);
+
 #ifdef __cplusplus
 }
 #endif
